@@ -72,6 +72,9 @@ def parse_args(argv=None):
     ap.add_argument("--pmc", action="store_true", help="collect FETCH_SIZE / WRITE_SIZE of k_lk_track under rocprofv3")
     ap.add_argument("--stub", action="store_true",
                     help="CPU test hook: no GPU work, gloo instead of RCCL; exercises rank spawning + result exchange only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step "
+                    "(rank 0's streams: poses, states, landmarks of the current frame, the local map's last correction) as DIR/<name>.npy, "
+                    "float64, at most 64 MB (a fixed, seeded sample of the streams beyond that)")
     return ap.parse_args(argv)
 
 
@@ -91,7 +94,7 @@ def free_port():
 
 
 def maybe_spawn(args, argv):
-    """`bench.py --gpus N` outside torchrun: start the N ranks (one per GPU) and replace this process."""
+    """`bench.py --gpus N` outside torchrun: start the N ranks (one per GPU) and exit with their launcher's status."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     if not args.stub:
@@ -102,7 +105,8 @@ def maybe_spawn(args, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + argv
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a child process, not exec: the device count above may have initialised the HIP runtime in this one
+    raise SystemExit(subprocess.call(cmd))
 
 
 def bind_to_gpu_numa_node(local_rank):
@@ -229,15 +233,18 @@ def run_stub(args, rank, world):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend="gloo")
+
+    def barrier():   # (a host all-reduce: dist.barrier() asks the runtime for an accelerator first, which opens the GPU in every rank)
+        if world > 1:
+            dist.all_reduce(torch.zeros(1))
+
     S = plan.streams_per_gpu(args.scaling, world, args.streams, args.total_streams)
     sched = plan.frame_schedule(args.steps, args.warmup, 50)
     ids = fdist.shard_streams(rank, world, S)
-    if world > 1:
-        dist.barrier()
+    barrier()
     t0 = time.perf_counter()
     time.sleep(0.01 * (rank + 1))
-    if world > 1:
-        dist.barrier()
+    barrier()
     elapsed = fdist.max_over_ranks(time.perf_counter() - t0)
     poses = torch.tensor([[float(s), 0, 0, 0, 0, 0, 1.0] for s in ids], dtype=torch.float64)
     K = sched["timed"][1] - sched["timed"][0]
@@ -249,8 +256,8 @@ def run_stub(args, rank, world):
                           "scaling": args.scaling, "vs_baseline": None, "data": "none (stub)",
                           "config": {"workload": "stub", "streams_per_gpu": S, "streams_total": world * S,
                                      "frames_exchanged": csum[0], "streams_tracking_at_end": csum[3]}}))
+    barrier()
     if world > 1:
-        dist.barrier()
         dist.destroy_process_group()
 
 
@@ -626,6 +633,8 @@ def main():
     ba_in_region -= ba_at_start
     lk_stages = read_stages()
     chain_ms = read_steps(chain_idx, K)
+    if args.dump_outputs and rank == 0:   # (outside the clock, before the epilogue moves the tracker on)
+        dump_outputs(args.dump_outputs, trk, S, sched["timed"][1] - 1)
     # ---- untimed epilogue: all stages
     stages = None
     lk_iters = None
@@ -793,6 +802,55 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     ctx.close()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together, .npy headers included
+# the library's per-stream capacities (flvis_amd/csrc/pipeline.hpp): landmarks of a frame (NMAX), of a correction (BA_LMAX), its
+# outlier ids (BA_EMAX) -- the padded widths of the dumped lists, so that every array's shape depends on the stream count alone
+DUMP_LM_CAP, DUMP_CORR_LM_CAP, DUMP_CORR_OUTLIER_CAP = 1024, 4096, 8192
+
+
+def dump_outputs(path, trk, S, frame):
+    """--dump-outputs: what a caller of the timed path receives after its last step (frame `frame`) -- every stream's trajectory row, the
+    landmarks of its current frame and the local map's last correction -- as float64 arrays DIR/<name>.npy.  Per-stream lists are padded to
+    the library's capacity (ids with -1, values with 0; the *_count arrays say how many entries are real).  Beyond DUMP_BUDGET_BYTES only a fixed,
+    seeded sample of the streams is written; stream_ids.npy names the streams of the rows."""
+    rows = np.stack([trk.trajectory(s, frame, 1)[0] for s in range(S)])
+    lms = [trk.landmarks(s) for s in range(S)]
+    cors = [trk.correction(s) for s in range(S)]
+    empty = dict(frame_id=-1, pose7=np.zeros(7), lm_id=np.zeros(0), lm_3d=np.zeros((0, 3)), outlier_id=np.zeros(0))
+    cors = [c if c is not None else empty for c in cors]
+
+    def padded(arrs, width, fill=0.0):
+        out = np.full((len(arrs), width) + np.shape(arrs[0])[1:], fill, np.float64)
+        for i, a in enumerate(arrs):
+            out[i, :len(a)] = a
+        return out
+
+    flags = rows[:, 8].astype(np.int64)
+    out = {"stream_ids": np.arange(S, dtype=np.float64), "stamp": rows[:, 0], "pose_T_c_w": rows[:, 1:8],
+           "state": (flags & 15).astype(np.float64), "new_keyframe": ((flags >> 4) & 1).astype(np.float64),
+           "landmark_count": np.array([len(l["ids"]) for l in lms], np.float64),
+           "landmark_id": padded([l["ids"] for l in lms], DUMP_LM_CAP, -1.0), "landmark_px": padded([l["p2d"] for l in lms], DUMP_LM_CAP),
+           "landmark_px_rectified": padded([l["p2u"] for l in lms], DUMP_LM_CAP), "landmark_world": padded([l["p3w"] for l in lms], DUMP_LM_CAP),
+           "landmark_flags": padded([l["flags"] for l in lms], DUMP_LM_CAP),
+           "correction_present": np.array([c is not empty for c in cors], np.float64),
+           "correction_frame_id": np.array([c["frame_id"] for c in cors], np.float64),
+           "correction_T_c_w": np.stack([c["pose7"] for c in cors]),
+           "correction_landmark_count": np.array([len(c["lm_id"]) for c in cors], np.float64),
+           "correction_landmark_id": padded([c["lm_id"] for c in cors], DUMP_CORR_LM_CAP, -1.0),
+           "correction_landmark_world": padded([c["lm_3d"] for c in cors], DUMP_CORR_LM_CAP),
+           "correction_outlier_count": np.array([len(c["outlier_id"]) for c in cors], np.float64),
+           "correction_outlier_id": padded([c["outlier_id"] for c in cors], DUMP_CORR_OUTLIER_CAP, -1.0)}
+    total = sum(a.nbytes for a in out.values())
+    room = DUMP_BUDGET_BYTES - 1024 * len(out)   # (a header takes 128 bytes)
+    if total > room:
+        keep = max(1, S * room // total)
+        sel = np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+        out = {k: a[sel] for k, a in out.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def measure_copy_bandwidth(dev, nbytes=1 << 30, reps=10):

@@ -75,11 +75,8 @@ def test_config_loader_matches_oracle_on_both_rigs():
         p = os.path.join(tempfile.gettempdir(), "flvis_cfgpar_%s.yaml" % tag)
         open(p, "w").write(text)
         files.append((tag, p))
-    for rel in ("launch/EuRoC_MAV/euroc.yaml", "launch/d435i/sn943222072828_stereo.yaml", "launch/d435i/sn943222072828_depth.yaml",
-                "launch/d435_pixhawk/sn943222072828_stereo_px4.yaml", "launch/KITTI/KITTI.yaml"):
-        p = os.path.join("/root/reference", rel)          # (absent on the GPU box: this is a CPU test)
-        if os.path.exists(p):
-            files.append((rel, p))
+    for name in ("euroc", "d435i_stereo", "d435i_depth", "d435_stereo_px4", "kitti"):   # the reference's launch files, stored as fixtures
+        files.append((name, os.path.join(ROOT, "tests", "golden", "yaml_ref_%s.yaml" % name)))
     for tag, p in files:
         a, b = flvis_amd.load_config(p), O.load_config(p)
         assert C.sizeof(a) == C.sizeof(b)

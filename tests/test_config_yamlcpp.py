@@ -1,7 +1,7 @@
 """Pins the yaml loaders (product: flvis_config_load, csrc/config.cpp; oracle: ref_config_load_yaml) on the reference's OWN
-yaml dependency: tests/golden/yaml_*.txt hold what yaml-cpp 0.6.2 (compiled from /root/reference/3rdPartLib by
+yaml dependency: tests/golden/yaml_*.txt hold what yaml-cpp 0.6.2 (compiled from the reference's 3rdPartLib by
 oracle/Makefile, read through the accessors of src/utils/include/yamlRead.h) returns for every key -- see
-scripts/make_yaml_fixtures.py.  SURVEY.md §8b: "must accept the reference's yaml files byte-for-byte"."""
+scripts/make_yaml_fixtures.py.  The reference's own launch files are stored beside them (tests/golden/yaml_ref_*.yaml).  SURVEY.md §8b: "must accept the reference's yaml files byte-for-byte"."""
 import os
 import subprocess
 import tempfile
@@ -86,20 +86,16 @@ def test_loaders_match_yaml_cpp_on_the_synthetic_rig_files(name):
     check_cfg_against_dump(O.load_config(p), d, "oracle")
 
 
-REF = {"euroc": "/root/reference/launch/EuRoC_MAV/euroc.yaml",
-       "d435i_stereo": "/root/reference/launch/d435i/sn943222072828_stereo.yaml",
-       "d435_stereo_px4": "/root/reference/launch/d435_pixhawk/sn943222072828_stereo_px4.yaml",
-       "d435i_depth": "/root/reference/launch/d435i/sn943222072828_depth.yaml",
-       "d435_depth_px4": "/root/reference/launch/d435_pixhawk/sn841512070537_depth_px4.yaml",
-       "kitti": "/root/reference/launch/KITTI/KITTI.yaml"}
+# the reference's own launch files, stored unchanged as fixtures: launch/EuRoC_MAV/euroc.yaml, launch/d435i/sn943222072828_stereo.yaml,
+# launch/d435_pixhawk/sn943222072828_stereo_px4.yaml, launch/d435i/sn943222072828_depth.yaml,
+# launch/d435_pixhawk/sn841512070537_depth_px4.yaml, launch/KITTI/KITTI.yaml
+REF = {name: os.path.join(GOLD, "yaml_ref_%s.yaml" % name)
+       for name in ("euroc", "d435i_stereo", "d435_stereo_px4", "d435i_depth", "d435_depth_px4", "kitti")}
 
 
 @pytest.mark.parametrize("name", sorted(REF))
 def test_loaders_match_yaml_cpp_on_the_reference_launch_files(name):
-    """the reference's own launch files, read in place (they are not copied into this repo): skipped where /root/reference
-    does not exist (the GPU box)."""
-    if not os.path.exists(REF[name]):
-        pytest.skip("reference not present")
+    """the reference's own launch files (tests/golden/yaml_ref_*.yaml, byte for byte as the reference ships them)"""
     import flvis_amd
     gold = open(os.path.join(GOLD, "yaml_ref_%s.txt" % name)).read()
     dump = os.path.join(ROOT, "oracle", "_ref", "yaml_dump")

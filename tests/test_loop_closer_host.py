@@ -1,5 +1,5 @@
 """CPU: the host side of the loop closer -- the LC_PARAS block of the yaml (pinned on what the reference's yaml-cpp reads from
-launch/KITTI/KITTI.yaml) and the oracle-assembled control flow of the nodelet (tests/_loop_chain.py) on a rendered sequence that
+launch/KITTI/KITTI.yaml, stored as tests/golden/yaml_ref_kitti.yaml) and the oracle-assembled control flow of the nodelet (tests/_loop_chain.py) on a rendered sequence that
 returns to its start: a loop is found, verified and the pose graph pulls the drifted end back."""
 import os
 import tempfile
@@ -23,8 +23,6 @@ def test_lc_params_match_yaml_cpp_on_the_reference_kitti_file():
     d = read_dump(open(os.path.join(GOLD, "yaml_ref_kitti.txt")).read())
     assert all(k in d for k in FIELDS)
     assert {k: float(d[k][0]) for k in FIELDS} == {k: float(v) for k, v in LC.LC_PARAMS.items()}       # what the tests use
-    if not os.path.exists(REF["kitti"]):
-        pytest.skip("reference not present")
     prm = flvis_amd.load_lc_params(REF["kitti"])
     for k in FIELDS:
         assert float(getattr(prm, k)) == float(d[k][0]), k

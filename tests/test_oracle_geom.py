@@ -300,9 +300,8 @@ def test_stereo_rectify_d435_and_euroc_sanity():
     assert np.allclose(np.array(cfg.R0).reshape(3, 3), np.eye(3), atol=1e-12)
     assert abs(cfg.P0[0] - 384.16455) < 1.5 and abs(cfg.P0[2] - 320.2144) < 1.0     # alpha=0 crop scale ~1.002
     assert np.isclose(cfg.P1[3], -0.05 * cfg.P1[0], rtol=1e-9)                        # baseline * f
-    ref_yaml = "/root/reference/launch/EuRoC_MAV/euroc.yaml"
-    if os.path.exists(ref_yaml):      # SURVEY Appendix B plausibility values (public EuRoC rectification)
-        e = O.load_config(ref_yaml)
-        assert e.cam_type == 1 and e.need_equal_hist == 1 and e.skip_first_n_imgs == 0 and e.window_size == 10
-        assert abs(e.P0[0] - 435.2) < 2.0 and abs(e.P0[2] - 367.45) < 2.0 and abs(e.P0[6] - 252.2) < 2.0
-        assert abs(e.P1[3] + 47.9) < 0.5
+    # the reference's launch/EuRoC_MAV/euroc.yaml: SURVEY Appendix B plausibility values (public EuRoC rectification)
+    e = O.load_config(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "yaml_ref_euroc.yaml"))
+    assert e.cam_type == 1 and e.need_equal_hist == 1 and e.skip_first_n_imgs == 0 and e.window_size == 10
+    assert abs(e.P0[0] - 435.2) < 2.0 and abs(e.P0[2] - 367.45) < 2.0 and abs(e.P0[6] - 252.2) < 2.0
+    assert abs(e.P1[3] + 47.9) < 0.5

@@ -8,6 +8,10 @@ import pytest
 from flvis_amd import traj_io as T
 traj_io = T
 
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLD_KITTI = os.path.join(GOLD, "kitti_poses_04_head.txt")
+GOLD_KITTI_ZIP = os.path.join(GOLD, "kitti_poses_04.zip")   # the reference's bag/KITTI/dataset/poses.zip, sequence 04 only
+
 
 def _rand_rot(rng):
     q = rng.normal(size=4)
@@ -53,16 +57,14 @@ def test_kitti_round_trip_and_reference_poses_zip():
     assert len(open(p).readline().split()) == 12
     R2, t2 = T.read_kitti(p)
     assert np.allclose(R2, Rs, atol=1e-5) and np.allclose(t2, ts, rtol=1e-5, atol=1e-5)
-    ref_zip = "/root/reference/bag/KITTI/dataset/poses.zip"
-    if os.path.exists(ref_zip):           # present in the build container only
-        R, t = T.read_kitti(ref_zip)
-        assert len(R) > 100 and np.allclose(R[0], np.eye(3), atol=1e-9) and np.allclose(t[0], 0, atol=1e-9)
-        dets = np.linalg.det(R)
-        assert np.allclose(dets, 1.0, atol=1e-4)
-        # a trajectory is its own ground truth: ATE 0; shifted/rotated copy: ATE 0 after alignment
-        Rg = _rand_rot(rng)
-        moved = (Rg @ t.T).T + np.array([5.0, -3.0, 1.0])
-        assert T.ate_rmse(moved, t) < 1e-6 * np.abs(t).max()
+    R, t = T.read_kitti(GOLD_KITTI_ZIP)
+    assert len(R) > 100 and np.allclose(R[0], np.eye(3), atol=1e-9) and np.allclose(t[0], 0, atol=1e-9)
+    dets = np.linalg.det(R)
+    assert np.allclose(dets, 1.0, atol=1e-4)
+    # a trajectory is its own ground truth: ATE 0; shifted/rotated copy: ATE 0 after alignment
+    Rg = _rand_rot(rng)
+    moved = (Rg @ t.T).T + np.array([5.0, -3.0, 1.0])
+    assert T.ate_rmse(moved, t) < 1e-6 * np.abs(t).max()
 
 
 def test_umeyama_recovers_similarity_and_ate_of_noise():
@@ -119,7 +121,6 @@ def test_euroc_csv_readers():
 
 
 # ---------------------------------------------------------------- KITTI ground truth shipped with the reference (data fixture)
-GOLD_KITTI = os.path.join(os.path.dirname(__file__), "golden", "kitti_poses_04_head.txt")
 
 
 def test_kitti_ground_truth_fixture_roundtrip_and_ate(tmp_path):
@@ -146,21 +147,17 @@ def test_kitti_ground_truth_fixture_roundtrip_and_ate(tmp_path):
     assert traj_io.ate_rmse(1.7 * moved, t, with_scale=False) > 1.0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/bag/KITTI/dataset/poses.zip"), reason="reference data not present")
 def test_kitti_zip_reader_matches_fixture():
-    R, t = traj_io.read_kitti("/root/reference/bag/KITTI/dataset/poses.zip", "poses/04.txt")
+    R, t = traj_io.read_kitti(GOLD_KITTI_ZIP, "poses/04.txt")
     Rf, tf = traj_io.read_kitti(GOLD_KITTI)
     assert len(R) == 271 and np.array_equal(R[:120], Rf) and np.array_equal(t[:120], tf)
 
 
 def test_reads_the_trajectories_the_reference_submitted_to_kitti():
     """results/flvis_results/*.zip holds FLVIS's own KITTI-benchmark output (sequences 11-21, the recorder's 12-column
-    format, vo_repub_rec.cpp:100-111): the reader must take them as they are.  Skipped where the reference is absent."""
-    import glob
-    zips = glob.glob("/root/reference/results/flvis_results/*.zip")
-    if not zips:
-        pytest.skip("reference not present")
-    R, t = traj_io.read_kitti(zips[0], "17.txt")
+    format, vo_repub_rec.cpp:100-111): the reader must take them as they are.  Sequence 17 of that archive is stored as
+    tests/golden/flvis_results_17.zip."""
+    R, t = traj_io.read_kitti(os.path.join(GOLD, "flvis_results_17.zip"), "17.txt")
     assert len(R) > 400 and R.shape[1:] == (3, 3) and t.shape == (len(R), 3)
     for k in range(0, len(R), 97):
         assert np.allclose(R[k] @ R[k].T, np.eye(3), atol=1e-4) and abs(np.linalg.det(R[k]) - 1) < 1e-4
