@@ -999,6 +999,22 @@ class Tracker:
         self.ctx._check(self.lib.flvis_get_counters(self.ctx._h, c), "get_counters")
         return list(c)
 
+    def _stream_list(self, streams, what):
+        ids = [int(k) for k in streams]
+        arr = (C.c_int * max(1, len(ids)))(*ids)
+        fn = getattr(self.lib, what)
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        self.ctx._check(fn(self.ctx._h, len(ids), arr), what[len("flvis_"):])
+
+    def reset_streams(self, streams):
+        """flvis_reset_streams: the named streams start over as streams of a new tracker (the others go on undisturbed); from the next
+        frame step on.  FlvisError for an index outside [0, S)."""
+        self._stream_list(streams, "flvis_reset_streams")
+
+    def local_map_reset(self, streams):
+        """flvis_local_map_reset: KFMSG_CMD_RESET_LM for the named streams' local maps (what is queued ahead is processed first)."""
+        self._stream_list(streams, "flvis_local_map_reset")
+
     def dropped_keyframes(self):
         """keyframes that met a full keyframe queue (flvis_get_counters_n [3]; 0 under the tracker's back-pressure)"""
         c = (C.c_int64 * 4)()

@@ -2602,7 +2602,7 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
 __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slot, unsigned launch_tag) {
   const int t = threadIdx.x;
   __shared__ int s_go, s_pick;
-  __shared__ unsigned s_head, s_tail;
+  __shared__ unsigned s_head, s_tail, s_skip;
   __shared__ int s_cnt[BA_NW];
   if (p.ba_remap) {
     if (t < 64) {
@@ -2660,6 +2660,7 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
         // the tail as read BEFORE the fence: the fence synchronises with the release stores of the keyframes up to that value only.  A
         // keyframe k_frame_end appends after it is seen by the loop below (tl2 != tl), which acquires again before its slot is read.
         s_tail = tl;
+        s_skip = __hip_atomic_load(&p.kfq_skip[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     __syncthreads();
@@ -2667,11 +2668,17 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
     int taken = 0;
     bool capped = false;
     while (true) {
-      const unsigned hd = s_head, tl = s_tail;
+      const unsigned hd = s_head, tl = s_tail, sk = s_skip;
       __syncthreads();  // (everybody has read the two words before thread 0 rewrites them below)
       if (hd == tl) break;
       const KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (hd % KFQ)];
       const long long frame_id = kf.frame_id;
+      // a reset command (k_stream_reset) empties the window in order with the keyframes; the entries queued ahead of a stream reset's
+      // command are discarded unread (the skip word may be newer than the tail read above: whatever it covers lies ahead of a command)
+      if ((int)(sk - hd) > 0) {
+      } else if (kf.valid == KFQ_CMD_RESET) {
+        window_reset_dev(p, s);
+      } else {
 #ifdef FLVIS_BA_PROF
       const long long tu0 = (long long)wall_clock64();
 #endif
@@ -2684,6 +2691,7 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
       }
 #endif
       if (p.win[s].solve) ba_solve_dev(p, s, frame_id);
+      }
       __syncthreads();
       if (t == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the window, the landmarks, CorrectionInf: before the head moves
@@ -2692,6 +2700,7 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
         const unsigned tl2 = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (tl2 != tl) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // keyframes appended since the last look: their slots are read afresh
         s_tail = tl2;
+        s_skip = __hip_atomic_load(&p.kfq_skip[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       __syncthreads();
       if (p.ba_drain > 0 && ++taken >= p.ba_drain) {
@@ -2730,14 +2739,19 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
       if (t == 0) {
         s_head = my_head;
         s_tail = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        s_skip = __hip_atomic_load(&p.kfq_skip[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       __syncthreads();
-      const unsigned hd = s_head, tl = s_tail;
+      const unsigned hd = s_head, tl = s_tail, sk = s_skip;
       __syncthreads();
       if (hd == tl) break;
       __atomic_thread_fence(__ATOMIC_ACQUIRE);
       const KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (hd % KFQ)];
       const long long frame_id = kf.frame_id;
+      if ((int)(sk - hd) > 0) {  // (reset commands: as in the default form above)
+      } else if (kf.valid == KFQ_CMD_RESET) {
+        window_reset_dev(p, s);
+      } else {
 #ifdef FLVIS_BA_PROF
       const long long tu0 = (long long)wall_clock64();
 #endif
@@ -2750,6 +2764,7 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
       }
 #endif
       if (p.win[s].solve) ba_solve_dev(p, s, frame_id);
+      }
       __atomic_thread_fence(__ATOMIC_RELEASE);
       __syncthreads();
       if (t == 0) __hip_atomic_store(&p.kfq_head[s], hd + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);

@@ -73,6 +73,7 @@ int flvis_hip_create(int device, void* hip_stream, flvis_ctx** out) {
 void flvis_pipeline_destroy_internal(flvis_ctx* ctx);  // pipeline.cpp
 void flvis_pipeline_sync_internal(flvis_ctx* ctx);
 long long flvis_pipeline_join_timeout_internal(flvis_ctx* ctx);
+int flvis_pipeline_reset_overflow_internal(flvis_ctx* ctx);
 
 void flvis_hip_destroy(flvis_ctx* ctx) {
   if (!ctx) return;
@@ -97,6 +98,12 @@ int flvis_hip_synchronize(flvis_ctx* ctx) {
     char msg[128];
     snprintf(msg, sizeof msg, "a stream join or an upload wait timed out (sequence number %lld): results since then are invalid", seq);
     return ctx->fail(FLVIS_ERR_HIP, msg);
+  }
+  // a reset command that found its stream's keyframe queue full (the back-pressure rules it out): that stream's local map was not reset
+  if (const int s = flvis_pipeline_reset_overflow_internal(ctx)) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "flvis_reset_streams / flvis_local_map_reset: the keyframe queue of stream %d was full; its local map was not reset", s - 1);
+    return ctx->fail(FLVIS_ERR_CAPACITY, msg);
   }
   return FLVIS_OK;
 }

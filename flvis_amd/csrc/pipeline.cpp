@@ -113,6 +113,12 @@ struct Lane {
   long long ba_launches = 0;
   bool ba_pending = false;       // FLVIS_BA_START > 0: the local-map launch for the last frame's keyframes has not been enqueued yet
   unsigned ba_tag = 0;           // tag of the lane's last local-map launch (k_ba_worker's stream list is valid for one tag; 0 is never used)
+  // reset commands in the keyframe queues (flvis_reset_streams / flvis_local_map_reset): per stream, the lane frame count when its last
+  // command was appended (-1: none, or keyframes pushed behind it) -- a second request before the next frame adds no entry; and the lane
+  // frame counts at which any stream of the lane had one appended, for the back-pressure (lane_backpressure_depth)
+  std::vector<long long> cmd_frame;
+  std::vector<long long> cmd_steps;
+  bool cmd_since_frame = false;  // a command was appended since the lane's last frame (a frame without the local map applies it: k_kfq_drop)
 };
 
 struct Pipeline {
@@ -282,19 +288,6 @@ void pose7_from_mat44(const double* m, double* out7, bool inverse) {
   out7[6] = q[0];
 }
 
-void glibc_seed(unsigned s, int* r34) {
-  std::vector<int> v(344);
-  v[0] = (int)s;
-  for (int i = 1; i < 31; i++) {
-    long long w = (16807LL * v[i - 1]) % 2147483647;
-    if (w < 0) w += 2147483647;
-    v[i] = (int)w;
-  }
-  for (int i = 31; i < 34; i++) v[i] = v[i - 31];
-  for (int i = 34; i < 344; i++) v[i] = (int)((unsigned)v[i - 31] + (unsigned)v[i - 3]);
-  for (int i = 0; i < 34; i++) r34[i] = v[344 - 34 + i];
-}
-
 }  // namespace flvis
 namespace {
 }  // namespace
@@ -341,6 +334,18 @@ extern "C" long long flvis_pipeline_join_timeout_internal(flvis_ctx* ctx) {
         L->h_progress[2] = 0;
       }
   return seq;
+}
+
+// the stream (context-wide index) + 1 whose reset command met a full keyframe queue (word 3 of a lane's host-mapped block), or 0; cleared when read
+extern "C" int flvis_pipeline_reset_overflow_internal(flvis_ctx* ctx) {
+  int s = 0;
+  if (ctx && ctx->pipe)
+    for (Lane* L : ctx->pipe->lanes)
+      if (L->h_progress && L->h_progress[3]) {
+        s = L->s0 + (int)L->h_progress[3];
+        L->h_progress[3] = 0;
+      }
+  return s;
 }
 
 extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
@@ -458,6 +463,10 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   DA(kfq, KeyFrameDev, (size_t)S * KFQ);
   DA(kfq_tail, unsigned, S);
   DA(kfq_head, unsigned, S);
+  DA(kfq_cmd, unsigned, S);
+  DA(kfq_skip, unsigned, S);
+  DA(kfq_base, unsigned, S);
+  DA(kfq_kf, unsigned, S);
   DA(ba_busy, int, S);
   DA(ba_plan, unsigned, (size_t)BA_PLAN_SLOTS * (3 + S));
   DA(win, WindowDev, S);
@@ -610,31 +619,18 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   ok = ok && ((L->d_join = dalloc<long long>(L->allocs, (size_t)Lane::JOIN_IDS * 8)) != nullptr);
   ok = ok && ((L->d_join_cnt = dalloc<unsigned>(L->allocs, (size_t)Lane::JOIN_IDS)) != nullptr);
   if (!ok) return false;
-  // initial per-stream state (F2FTracking::init, VIMOTION ctor, landmark id counter 100, glibc rand seed 1)
-  std::vector<StreamState> hs(S);
-  memset(hs.data(), 0, sizeof(StreamState) * S);
+  // initial per-stream state (F2FTracking::init, VIMOTION ctor, landmark id counter 100, glibc rand seed 1): the kernel flvis_reset_streams
+  // runs, so that a reset stream and a new one cannot differ (tracker_create synchronises the device before it returns)
+  for (int b = 0; b < S; b += RESET_LIST) {
+    ResetList rl{};
+    rl.n = std::min(RESET_LIST, S - b);
+    for (int i = 0; i < rl.n; i++) rl.s[i] = b + i, rl.mode[i] = RS_TRACKER | RS_CREATE;
+    launch_stream_reset(nullptr, p, rl, nullptr);
+  }
   std::vector<unsigned long long> hseed(S);
-  for (int s = 0; s < S; s++) {
-    StreamState& st = hs[s];
-    st.state = ST_UNINIT;
-    st.cur = 0;
-    st.skip_n = cfg->skip_first_n_imgs;
-    st.lm_id_counter = 100;
-    st.vi_first = 1;
-    st.kf_dq[0] = 1.0;
-    for (int k = 0; k < 2; k++) st.T_c_w[k][6] = 1.0;
-    st.T_kf[6] = 1.0;
-    st.guess[6] = 1.0;
-    glibc_seed(1, st.rnd_r);
-    st.rnd_pos = 0;
-    hseed[s] = seed_base + (unsigned long long)(s0 + s);  // the seed of a stream does not depend on the lane partition
-  }
-  hipMemcpy(p.st, hs.data(), sizeof(StreamState) * S, hipMemcpyHostToDevice);
-  {
-    std::vector<int> one(S, 1);  // cur = 0: the first image goes to slot 1
-    hipMemcpy(p.img_slot_in, one.data(), sizeof(int) * S, hipMemcpyHostToDevice);
-  }
+  for (int s = 0; s < S; s++) hseed[s] = seed_base + (unsigned long long)(s0 + s);  // the seed of a stream does not depend on the lane partition
   hipMemcpy(seeds, hseed.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice);
+  L->cmd_frame.assign(S, -1);
   L->h_imu.assign((size_t)S * IMU_MAX * 7, 0.0);
   L->h_nimu.assign(S, 0);
   L->imu_read.assign(S, 0);
@@ -654,7 +650,8 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
     if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) return false;
     L->h_progress = (volatile long long*)hp;
     L->d_progress = (long long*)dp;
-    for (int k = 0; k < 8; k++) L->h_progress[k] = 0;  // (word 0: frame progress, 1: scratch, 2: a timed-out join's sequence number)
+    for (int k = 0; k < 8; k++) L->h_progress[k] = 0;  // (word 0: frame progress, 1: scratch, 2: a timed-out join's sequence number,
+                                                        // 3: stream + 1 of a reset command that met a full keyframe queue)
   }
   if (own_stream) {
     if (hipStreamCreateWithFlags(&L->st, hipStreamNonBlocking) != hipSuccess) return false;
@@ -1145,6 +1142,24 @@ static void sync_all(flvis_ctx* ctx) {
   }
 }
 
+// FLVIS_BA_START (see lane_frame)
+static int ba_start_knob() {
+  static const int ba_start = getenv("FLVIS_BA_START") ? atoi(getenv("FLVIS_BA_START")) : 2;
+  return ba_start;
+}
+
+// How many local-map launches back the tracking stream waits before it appends to the keyframe queues (lane_frame).  A reset command
+// (k_stream_reset) takes a queue entry like a keyframe: every lane frame with a command among the frames the bound counts moves the wait
+// one launch closer.  Without commands: the depth of rounds 1-6.
+static long long lane_backpressure_depth(Pipeline* pl, Lane* L) {
+  long long D = std::max(0, KFQ / 2 / pl->ba_every - 2 - (ba_start_knob() != 0 ? 1 : 0));  // (a deferred launch is one frame late)
+  if (L->cmd_steps.empty()) return D;
+  const long long window = (D + pl->nba_lane + 2) * pl->ba_every;
+  std::vector<long long>& c = L->cmd_steps;
+  c.erase(std::remove_if(c.begin(), c.end(), [&](long long f) { return L->frames_uploaded - f > window; }), c.end());
+  return std::max(0LL, D - (long long)c.size());
+}
+
 // One frame of one lane: stages the lane's host inputs, uploads them as one block and enqueues the fixed kernel sequence
 // on the lane's streams.  d_img0 / d_img1 already point at the lane's first stream.
 static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
@@ -1189,6 +1204,9 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   ptab[1] = d_img1;
   memcpy(pn, L->h_nimu.data(), sizeof(int) * S);
   std::fill(L->h_nimu.begin(), L->h_nimu.end(), 0);
+  // a reset command appended since the lane's last frame (flvis_reset_streams / flvis_local_map_reset)
+  const bool cmd_pending = L->cmd_since_frame;
+  L->cmd_since_frame = false;
   // (round 4, measured: uploading the block on the detection stream into a per-frame device slot -- so that k_frame_head(n + 1) follows
   // k_frame_end(n) without the copy between them -- shortens the gap between two frames by ~19 us and lengthens the chain by ~16 us
   // (1.1914 against 1.1943 ms per step): not kept.  profiles/r04_lk_ab.md)
@@ -1222,7 +1240,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // which is on the critical path of the detection stream), 58.74k / 58.58k with 2 (default; temporal LK 0.212 -> 0.196 ms, frame chain
   // p50 1.065 -> 1.048 ms).  Only between the steps of one flvis_run_steps call -- the next frame is known to follow at once; a
   // per-frame caller (the ROS wrapper) gets its local-map launch when its frame ends, as before, and so does the last step of a batch.
-  static const int ba_start = getenv("FLVIS_BA_START") ? atoi(getenv("FLVIS_BA_START")) : 2;
+  const int ba_start = ba_start_knob();
   hipEvent_t* prof18 = (prof && ((pl->prof_mask >> 18) & 1ull)) ? &pev[2 * 18] : nullptr;
   const bool skipped = pl->frames_fed < (long long)pl->cfg.skip_first_n_imgs;
   const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;  // the second image is the Z16 depth map, read in place
@@ -1554,7 +1572,8 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
     // waiting for the launches of D frames ago (the last one on each of the lane's local-map streams) keeps a queue at
     // KFQ / 2 - 1 + (D + 2) * ba_every < KFQ when k_frame_end appends: no keyframe is dropped, whatever the optimiser's pace.
     // (ba_every <= KFQ / 4, flvis_tracker_create.)
-    const long long D = std::max(0, KFQ / 2 / pl->ba_every - 2 - (ba_start != 0 ? 1 : 0));  // (a deferred launch is one frame late)
+    // (a reset command counts as a keyframe: lane_backpressure_depth)
+    const long long D = lane_backpressure_depth(pl, L);
     for (int k = 0; k < pl->nba_lane; k++) {
       const long long j = L->ba_launches - 1 - D - k;
       if (j >= 0 && L->ba_launches - j <= Lane::BAQ) {
@@ -1574,8 +1593,13 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
     else if (L->endf_valid) launch_local_map(pl, L, L->ev_endf, false, prof18);  // (k_frame_end has stored the word itself)
     else launch_local_map(pl, L, L->ev_fe, true, prof18);
   } else if (!with_local_map) {
-    // without a local map nobody consumes the keyframe queue: drop what frame_end appended
-    hipMemcpyAsync(p.kfq_head, p.kfq_tail, sizeof(unsigned) * S, hipMemcpyDeviceToDevice, st);
+    // without a local map nobody consumes the keyframe queue: drop what frame_end appended (and apply a reset command queued since the
+    // last frame: k_kfq_drop)
+    // (a reset command is applied to the window here: behind the lane's last local-map launch, so that no workgroup of it owns the window)
+    if (cmd_pending) {
+      if (L->ba_launches > 0) join_wait(pl, L, st, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
+      launch_kfq_drop(st, p);
+    } else hipMemcpyAsync(p.kfq_head, p.kfq_tail, sizeof(unsigned) * S, hipMemcpyDeviceToDevice, st);
     if (prof) {
       PB(18, st);
       PE(18, st);
@@ -2019,8 +2043,8 @@ int flvis_get_keyframe(flvis_ctx* ctx, int stream, int cap, int64_t* frame_id, d
   FrameOut fo;
   hipMemcpy(&fo, L.pipe.out + ls, sizeof(FrameOut), hipMemcpyDeviceToHost);
   if (!fo.new_keyframe) return 0;  // the last frame of this stream did not become a keyframe
-  unsigned tl = 0;
-  hipMemcpy(&tl, L.pipe.kfq_tail + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
+  unsigned tl = 0;  // (the stream's last keyframe entry: the queue's last entry may be a reset command)
+  hipMemcpy(&tl, L.pipe.kfq_kf + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
   if (tl == 0) return 0;
   hipMemcpy(&kf, L.pipe.kfq + (size_t)ls * KFQ + ((tl - 1) % KFQ), sizeof(KeyFrameDev), hipMemcpyDeviceToHost);
   *frame_id = kf.frame_id;
@@ -2049,7 +2073,7 @@ int flvis_get_keyframe_msg(flvis_ctx* ctx, int stream, int cap, flvis_keyframe* 
   unsigned tl = 0;
   double stamp = 0;
   int slot = 0;
-  hipMemcpy(&tl, L.pipe.kfq_tail + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
+  hipMemcpy(&tl, L.pipe.kfq_kf + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
   hipMemcpy(&stamp, &L.pipe.kfq[(size_t)ls * KFQ + ((tl - 1) % KFQ)].stamp, sizeof(double), hipMemcpyDeviceToHost);
   hipMemcpy(&slot, L.pipe.img_slot + ls, sizeof(int), hipMemcpyDeviceToHost);
   kf->frame_id = fid;
@@ -2214,11 +2238,12 @@ int flvis_get_local_map_counts(flvis_ctx* ctx, int64_t* h_keyframes, int64_t* h_
   if (!ctx || !ctx->pipe) return FLVIS_ERR_INVALID_ARG;
   sync_all(ctx);
   for (Lane* L : ctx->pipe->lanes) {
-    if (h_keyframes) {
-      std::vector<unsigned> tl(L->S);
+    if (h_keyframes) {  // (the entries behind the stream's last reset command)
+      std::vector<unsigned> tl(L->S), base(L->S);
       hipError_t e = hipMemcpy(tl.data(), L->pipe.kfq_tail, sizeof(unsigned) * L->S, hipMemcpyDeviceToHost);
+      if (e == hipSuccess) e = hipMemcpy(base.data(), L->pipe.kfq_base, sizeof(unsigned) * L->S, hipMemcpyDeviceToHost);
       if (e != hipSuccess) return ctx->hip_fail(e, "get_local_map_counts");
-      for (int i = 0; i < L->S; i++) h_keyframes[L->s0 + i] = tl[i];
+      for (int i = 0; i < L->S; i++) h_keyframes[L->s0 + i] = tl[i] - base[i];
     }
     if (h_ba_runs) {
       std::vector<long long> r(L->S);
@@ -2230,6 +2255,70 @@ int flvis_get_local_map_counts(flvis_ctx* ctx, int64_t* h_keyframes, int64_t* h_
   }
   return FLVIS_OK;
 }
+
+// Per-stream reset (include/flvis_hip.h).  Host side: the stream's staged IMU samples and the IMU-state rows not yet fetched are dropped;
+// device side, in stream order on the lane's tracking stream: k_stream_reset (the tracker state of a new stream, and a reset command
+// in the keyframe queue that the local map applies in order with the keyframes).  No host synchronisation.
+static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, const char* what) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  Pipeline* pl = ctx->pipe;
+  if (!pl) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": no tracker (flvis_tracker_create)");
+  if (n < 0 || (n > 0 && !streams)) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": bad stream list");
+  for (int i = 0; i < n; i++)
+    if (streams[i] < 0 || streams[i] >= pl->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": stream out of range");
+  if (n == 0) return FLVIS_OK;
+  hipSetDevice(ctx->device);
+  std::vector<char> named(pl->S, 0);
+  for (int i = 0; i < n; i++) named[streams[i]] = 1;  // (duplicates: one reset)
+  for (Lane* L : pl->lanes) {
+    std::vector<std::pair<int, unsigned char>> todo;
+    bool new_cmd = false;
+    for (int ls = 0; ls < L->S; ls++) {
+      if (!named[L->s0 + ls]) continue;
+      // a command appended since the lane's last frame with nothing behind it already does what a second one would: a stream reset makes
+      // it skip what is queued ahead of it, a local-map reset adds nothing
+      const bool queued = L->cmd_frame[ls] == L->frames_uploaded;
+      if (!tracker && queued) continue;
+      unsigned char mode = (unsigned char)((tracker ? RS_TRACKER | RS_SKIP : 0) | (queued ? 0 : RS_CMD));
+      if (!queued) {
+        L->cmd_frame[ls] = L->frames_uploaded;
+        new_cmd = true;
+      }
+      if (tracker) {
+        L->h_nimu[ls] = 0;
+        L->imu_read[ls] = 0;
+      }
+      todo.emplace_back(ls, mode);
+    }
+    if (todo.empty()) continue;
+    if (new_cmd) {
+      // the command takes a queue entry: the back-pressure of a keyframe append, counting it (lane_backpressure_depth)
+      if (L->cmd_steps.empty() || L->cmd_steps.back() != L->frames_uploaded) L->cmd_steps.push_back(L->frames_uploaded);
+      L->cmd_since_frame = true;
+      const long long D = lane_backpressure_depth(pl, L);
+      for (int k = 0; k < pl->nba_lane; k++) {
+        const long long j = L->ba_launches - 1 - D - k;
+        if (j >= 0 && L->ba_launches - j <= Lane::BAQ) join_wait(pl, L, L->st, L->ev_ba_done[j % Lane::BAQ]);
+      }
+    }
+    for (size_t b = 0; b < todo.size(); b += RESET_LIST) {
+      ResetList rl{};
+      rl.n = (int)std::min(todo.size() - b, (size_t)RESET_LIST);
+      for (int i = 0; i < rl.n; i++) rl.s[i] = todo[b + i].first, rl.mode[i] = todo[b + i].second;
+      launch_stream_reset(L->st, L->pipe, rl, L->d_progress + 3);
+    }
+    // the next frame's image ingest (detection stream) writes the slot k_stream_reset chose: it waits for a signal behind this launch, not
+    // for the word the last k_frame_end stored
+    L->endf_valid = false;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  return FLVIS_OK;
+}
+
+int flvis_reset_streams(flvis_ctx* ctx, int n, const int* streams) { return reset_impl(ctx, n, streams, true, "reset_streams"); }
+
+int flvis_local_map_reset(flvis_ctx* ctx, int n, const int* streams) { return reset_impl(ctx, n, streams, false, "local_map_reset"); }
 
 // test aid: the tracker's pyramid construction on its own (see include/flvis_hip.h for the layout of d_out)
 int flvis_debug_pyramid(flvis_ctx* ctx, const uint8_t* d_src, int w, int h, int n_img, int levels, int bx, int by, int ingest, uint8_t* d_out,
@@ -2344,7 +2433,7 @@ int flvis_get_keyframe_imu_pos(flvis_ctx* ctx, int stream, double* dp3, double* 
   int ls;
   Lane& L = pl->lane_of(stream, ls);
   unsigned tl = 0;
-  hipMemcpy(&tl, L.pipe.kfq_tail + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
+  hipMemcpy(&tl, L.pipe.kfq_kf + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
   if (tl == 0) return 0;
   double h[6];
   static_assert(offsetof(KeyFrameDev, imu_va) == offsetof(KeyFrameDev, imu_dp) + 24, "KeyFrameDev imu position block layout");
@@ -2365,7 +2454,7 @@ int flvis_get_keyframe_imu(flvis_ctx* ctx, int stream, double* dq_wxyz, double* 
   FrameOut fo;
   hipMemcpy(&fo, L.pipe.out + ls, sizeof(FrameOut), hipMemcpyDeviceToHost);
   unsigned tl = 0;
-  hipMemcpy(&tl, L.pipe.kfq_tail + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
+  hipMemcpy(&tl, L.pipe.kfq_kf + ls, sizeof(unsigned), hipMemcpyDeviceToHost);
   if (!fo.new_keyframe || tl == 0) return 0;
   struct {
     double dq[4], dt;
@@ -2445,6 +2534,8 @@ static int ba_push_impl(flvis_ctx* ctx, int stream, int64_t frame_id, const doub
   hipMemcpy(L.pipe.kfq + (size_t)ls * KFQ + (tl % KFQ), &kf, sizeof(kf), hipMemcpyHostToDevice);
   tl++;
   hipMemcpy(L.pipe.kfq_tail + ls, &tl, sizeof(unsigned), hipMemcpyHostToDevice);
+  L.cmd_frame[ls] = -1;  // (a reset command queued before this keyframe is no longer the last entry)
+  hipMemcpy(L.pipe.kfq_kf + ls, &tl, sizeof(unsigned), hipMemcpyHostToDevice);
   hipMemcpy(&L.pipe.corr[ls].valid, &zero, sizeof(int), hipMemcpyHostToDevice);
   launch_ba_worker(pl->ba_stream[0], L.pipe, 0, ++L.ba_tag);
   hipError_t e = hipStreamSynchronize(pl->ba_stream[0]);

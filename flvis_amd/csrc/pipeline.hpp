@@ -169,8 +169,43 @@ struct WindowDev {
   long long ba_runs;
 };
 
+// KeyFrameDev::valid of a keyframe queue entry: a keyframe, or KFMSG_CMD_RESET_LM (keyframe_msg.h:11) -- the local map empties its window
+// when it reaches the entry, in order with the keyframes (flvis_local_map_reset, flvis_reset_streams)
+enum { KFQ_KEYFRAME = 1, KFQ_CMD_RESET = 2 };
+
 // host helpers shared by the tracker set-up and the one-call entry points (pipeline.cpp)
 void pose7_from_mat44(const double* m44, double* out7, bool inverse);
-void glibc_seed(unsigned s, int* r34);  // the state srand(s) leaves: the last 34 words of glibc's TYPE_3 table
+
+// the state srand(s) leaves: the last 34 words of glibc's TYPE_3 table (r[i] = r[i - 31] + r[i - 3] over 344 words, kept in a ring of 34)
+__host__ __device__ inline void glibc_seed(unsigned s, int* r34) {
+  int v[34];
+  v[0] = (int)s;
+  for (int i = 1; i < 31; i++) {
+    long long w = (16807LL * v[i - 1]) % 2147483647;
+    if (w < 0) w += 2147483647;
+    v[i] = (int)w;
+  }
+  for (int i = 31; i < 34; i++) v[i] = v[i - 31];
+  for (int i = 34; i < 344; i++) v[i % 34] = (int)((unsigned)v[(i - 31) % 34] + (unsigned)v[(i - 3) % 34]);
+  for (int i = 0; i < 34; i++) r34[i] = v[(344 - 34 + i) % 34];
+}
+
+// The state of a stream that has seen nothing (F2FTracking::init + the VIMOTION ctor, f2f_tracking.cpp:5-38: landmark id counter 100,
+// glibc rand seeded with 1, skip_first_n_imgs to skip).  Written by k_stream_reset, at tracker creation and at flvis_reset_streams.
+__host__ __device__ inline void stream_state_init(StreamState& st, int skip_first_n) {
+  int* w = reinterpret_cast<int*>(&st);
+  for (int i = 0; i < (int)(sizeof(StreamState) / sizeof(int)); i++) w[i] = 0;
+  st.state = ST_UNINIT;
+  st.cur = 0;
+  st.skip_n = skip_first_n;
+  st.lm_id_counter = 100;
+  st.vi_first = 1;
+  st.kf_dq[0] = 1.0;
+  for (int k = 0; k < 2; k++) st.T_c_w[k][6] = 1.0;
+  st.T_kf[6] = 1.0;
+  st.guess[6] = 1.0;
+  glibc_seed(1, st.rnd_r);
+  st.rnd_pos = 0;
+}
 
 }  // namespace flvis

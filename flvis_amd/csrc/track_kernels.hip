@@ -2682,7 +2682,8 @@ __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
       }
       st.kf_dq[0] = 1.0, st.kf_dq[1] = st.kf_dq[2] = st.kf_dq[3] = 0.0;
       st.kf_dt = 0;
-      kf.valid = 1;
+      kf.valid = KFQ_KEYFRAME;
+      p.kfq_kf[s] = s_tail + 1u;
     }
     // (one release, by the thread that publishes: the barrier orders the other threads' stores before it, and a `buffer_wbl2` per wave
     // -- what a fence executed by every thread costs -- writes the XCD's L2 back once per wave, k_ba_worker)
@@ -2696,7 +2697,120 @@ __global__ __launch_bounds__(FE_T) void k_frame_end(Pipe p) {
   kj_signal(p.kj);
 }
 
+// ------------------------------------------------------------------------------------------------ per-stream reset
+// One workgroup per listed stream, on the lane's tracking stream between two frames (the frame before it has finished every kernel that
+// touches the stream's tracker state: the detection and template streams join the chain before k_frame_end).
+//  RS_TRACKER: the stream's tracker state as a new tracker has it (stream_state_init; the frame slots' landmarks, the VIMOTION ring, the
+//    pose records, the IMU-state ring, the trajectory rows, the per-frame words, the headers of its template-cache slots, a correction
+//    handed over and not yet applied).  Not the word the local map owns (StreamState::lm_state): the reset command resets it.
+//  RS_CMD: a reset command appended to the stream's keyframe queue, published as k_frame_end publishes a keyframe; RS_SKIP: the local
+//    map discards the entries queued ahead of it (without RS_CMD: ahead of the command already last in the queue).
+//  RS_CREATE: tracker creation -- the local map's word too (no worker exists yet).
+__global__ __launch_bounds__(256) void k_stream_reset(Pipe p, ResetList list, long long* err_word) {
+  const int s = list.s[blockIdx.x];
+  const unsigned mode = list.mode[blockIdx.x];
+  const int t = threadIdx.x, nt = blockDim.x;
+  if (s < 0 || s >= p.S) return;
+  if (mode & RS_TRACKER) {
+    __shared__ StreamState s_st;
+    if (t == 0) stream_state_init(s_st, p.cam.skip_first_n);
+    __syncthreads();
+    const int* src = reinterpret_cast<const int*>(&s_st);
+    int* dst = reinterpret_cast<int*>(p.st + s);
+    const int lm_word = (int)(offsetof(StreamState, lm_state) / sizeof(int));
+    for (int i = t; i < (int)(sizeof(StreamState) / sizeof(int)); i += nt)
+      if (i != lm_word || (mode & RS_CREATE)) dst[i] = src[i];
+    static_assert(sizeof(Landmark) % 8 == 0 && sizeof(MotionState) % 8 == 0 && sizeof(FrameOut) % 8 == 0, "records cleared in 8-byte words");
+    for (int k = 0; k < 2; k++) {
+      long long* l = reinterpret_cast<long long*>(lm_ptr(p, k, s));
+      for (int i = t; i < (int)(NMAX * sizeof(Landmark) / 8); i += nt) l[i] = 0;
+    }
+    {
+      long long* v = reinterpret_cast<long long*>(p.vi + (size_t)s * VI_QUEUE);
+      for (int i = t; i < (int)(VI_QUEUE * sizeof(MotionState) / 8); i += nt) v[i] = 0;
+    }
+    for (int i = t; i < IMU_OUT_CAP * 11; i += nt) p.imu_out[(size_t)s * IMU_OUT_CAP * 11 + i] = 0.0;
+    for (int i = t; i < POSE_REC; i += nt) p.rec_id[(size_t)s * POSE_REC + i] = 0;
+    for (int i = t; i < POSE_REC * 7; i += nt) p.rec_T[(size_t)s * POSE_REC * 7 + i] = 0.0;
+    if (p.traj)
+      for (int i = t; i < p.traj_cap * 9; i += nt) p.traj[(size_t)s * p.traj_cap * 9 + i] = 0.0;
+    {
+      long long* o = reinterpret_cast<long long*>(p.out + s);
+      for (int i = t; i < (int)(sizeof(FrameOut) / 8); i += nt) o[i] = 0;
+    }
+    // no slot header may match a pixel and frame id of the new sequence (frame ids start over): as tracker_create leaves them
+    if (p.tc) {
+      uint32_t* tc = const_cast<uint32_t*>(p.tc) + (size_t)s * p.tc_cap * p.tc_stride;
+      for (int i = t; i < p.tc_cap * 8; i += nt) tc[(size_t)(i >> 3) * p.tc_stride + (i & 7)] = 0xffffffffu;
+    }
+    if (t == 0) {
+      p.img_slot_in[s] = 1;  // cur = 0: the first image goes to slot 1
+      p.img_slot[s] = 0;
+      p.lk_count[s] = 0;
+      p.lk_tag[s] = 0;
+      p.tpl_count[s] = 0;
+      p.tpl_tag[s] = 0;
+      p.n_new[s] = 0;
+      p.n_exist[s] = 0;
+      p.act_img[s] = 0;
+      p.act_track[s] = 0;
+      p.det_mode[s] = 0;
+      p.det_maxc[s] = 0;
+      p.gftt_act[s] = 0;
+      p.gftt_maxc[s] = 0;
+      p.kfq_kf[s] = 0;  // (the keyframe getters: no keyframe yet)
+      if (p.corr_in) p.corr_in[s].valid = 0;
+    }
+  }
+  if (t != 0) return;
+  if (mode & RS_CMD) {
+    const unsigned tl = p.kfq_tail[s];
+    if (tl - __hip_atomic_load(&p.kfq_head[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)KFQ) {
+      // the host's back-pressure counts the command, so this is not reached; should it be, the window would not be reset: say so
+      if (err_word) __hip_atomic_store(err_word, (long long)s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return;
+    }
+    KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (tl % KFQ)];
+    kf.frame_id = -1;
+    kf.lm_count = 0;
+    kf.stamp = 0.0;
+    kf.imu_valid = 0;
+    kf.valid = KFQ_CMD_RESET;
+    p.kfq_cmd[s] = tl + 1u;
+    p.kfq_base[s] = tl + 1u;
+    if (mode & RS_SKIP) __hip_atomic_store(&p.kfq_skip[s], tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&p.kfq_tail[s], tl + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  } else if (mode & RS_SKIP) {
+    const unsigned c = p.kfq_cmd[s];
+    if (c) __hip_atomic_store(&p.kfq_skip[s], c - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// without a local map nobody consumes the keyframe queues: their entries are dropped -- and a reset command among them applied here.
+// No local-map workgroup owns a window meanwhile: the host enqueues this behind the lane's last local-map launch (lane_frame).
+__global__ __launch_bounds__(256) void k_kfq_drop(Pipe p) {
+  const int s = blockIdx.x;
+  __shared__ int s_apply;
+  __shared__ unsigned s_tail;
+  if (threadIdx.x == 0) {
+    const unsigned tl = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned hd = __hip_atomic_load(&p.kfq_head[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned c = p.kfq_cmd[s];
+    s_apply = c != 0u && c - 1u - hd < tl - hd;  // the stream's last command lies in [head, tail)
+    s_tail = tl;
+  }
+  __syncthreads();
+  if (s_apply) window_reset_dev(p, s);
+  if (threadIdx.x == 0) __hip_atomic_store(&p.kfq_head[s], s_tail, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
+void launch_stream_reset(hipStream_t st, const Pipe& p, const ResetList& list, long long* err_word) {
+  if (list.n > 0) hipLaunchKernelGGL(k_stream_reset, dim3(list.n), dim3(256), 0, st, p, list, err_word);
+}
+void launch_kfq_drop(hipStream_t st, const Pipe& p) {
+  hipLaunchKernelGGL(k_kfq_drop, dim3(p.S), dim3(256), 0, st, p);
+}
 void launch_imu_feed(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_imu_feed, dim3((p.S + 63) / 64), dim3(64), 0, st, p);
 }

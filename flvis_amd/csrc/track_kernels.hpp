@@ -55,6 +55,14 @@ struct Pipe {
   KeyFrameDev* kfq;         // [S][KFQ]
   unsigned* kfq_tail;       // [S] keyframes produced
   unsigned* kfq_head;       // [S] keyframes consumed
+  // reset commands in the queue (k_stream_reset): the entry index + 1 of the stream's last command (0: none), the entries the local map
+  // discards unread (index < kfq_skip: queued ahead of a flvis_reset_streams), and the tail behind the last command (the keyframes the
+  // stream has emitted since its last reset are kfq_tail - kfq_base, flvis_get_local_map_counts)
+  unsigned* kfq_cmd;        // [S]
+  unsigned* kfq_skip;       // [S]
+  unsigned* kfq_base;       // [S]
+  unsigned* kfq_kf;         // [S] entry index + 1 of the stream's last keyframe (0: none since creation or its last flvis_reset_streams): the
+                            // keyframe getters read it, the last entry may be a command
   int* ba_busy;             // [S] a worker workgroup owns the stream's window
   unsigned* ba_plan;        // [BA_PLAN_SLOTS][3 + S] per local-map HIP stream: arrival counter, tag of the launch whose list is valid, count, the streams
                             // with a keyframe waiting (written by the first workgroup of a launch to arrive, k_ba_worker)
@@ -93,6 +101,20 @@ struct Pipe {
   KJoin kj;                 // joins folded into THIS launch (set by the host in front of it, cleared behind it)
 };
 
+// KFMSG_CMD_RESET_LM as vo_localmap.cpp:87-98 applies it (optimizer_state = UN_INITIALIZED, bag->reset(), kfs.clear(), optimizer.clear(),
+// edges.clear()): the stream's window back to the state of a new tracker, the published correction withdrawn.  All threads of one
+// workgroup, by the owner of the stream's window (k_ba_worker) or where no local map runs (k_kfq_drop).
+__device__ inline void window_reset_dev(const Pipe& p, int s) {
+  long long* w = reinterpret_cast<long long*>(p.win + s);
+  static_assert(sizeof(WindowDev) % 8 == 0, "WindowDev is cleared in 8-byte words");
+  for (int i = threadIdx.x; i < (int)(sizeof(WindowDev) / 8); i += blockDim.x) w[i] = 0;
+  if (threadIdx.x == 0) {
+    p.corr[s].valid = 0;
+    p.st[s].lm_state = 0;
+  }
+  __syncthreads();
+}
+
 int ba_lds_budget_max();
 void launch_imu_feed(hipStream_t st, const Pipe& p);
 void launch_frame_begin(hipStream_t st, const Pipe& p, const double* d_time);
@@ -125,6 +147,17 @@ void launch_add_new_seeds(hipStream_t st, const Pipe& p);      // the two above 
 void launch_depth_triangulate(hipStream_t st, const Pipe& p);  // two-view triangulation for k_depth_innovate (beside the stereo LK)
 void launch_depth_innovate(hipStream_t st, const Pipe& p);
 void launch_frame_end(hipStream_t st, const Pipe& p);
+// per-stream reset (flvis_reset_streams / flvis_local_map_reset, and the initial state at tracker creation): one workgroup per listed stream
+constexpr int RESET_LIST = 64;  // streams per launch
+enum { RS_TRACKER = 1, RS_CMD = 2, RS_SKIP = 4, RS_CREATE = 8 };  // what k_stream_reset does for a stream (bits)
+struct ResetList {
+  int n;
+  int s[RESET_LIST];              // lane-local stream indices
+  unsigned char mode[RESET_LIST];  // RS_* bits
+};
+// err_word (host-mapped): a command that met a full queue stores the stream's lane-local index + 1 there (flvis_hip_synchronize reports it)
+void launch_stream_reset(hipStream_t st, const Pipe& p, const ResetList& list, long long* err_word);
+void launch_kfq_drop(hipStream_t st, const Pipe& p);  // the queues emptied without a local map, a pending reset command applied
 // local map
 constexpr int BA_PLAN_SLOTS = 8;  // (= Pipeline::NBA: one list per local-map HIP stream, launches on one stream do not overlap)
 void launch_ba_worker(hipStream_t st, const Pipe& p, int plan_slot, unsigned launch_tag);

@@ -460,7 +460,26 @@ int flvis_write_imu_trajectory(const double* h_rows11, int n, const char* path, 
  * within min_dt of t_first are dropped in EVERY batch, also when the batch that created the file was shorter than min_dt
  * (the recorder's last_time is set once and never updated, vo_repub_rec.cpp:77-78). */
 int flvis_write_imu_trajectory_run(const double* h_rows11, int n, const char* path, double min_dt, int append, double t_first);
-/* Counters: [0] frames fed, [1] keyframes, [2] BA runs. */
+/* Start over on the named streams (lane-independent indices in [0, n_streams)): from the next frame step on, each behaves exactly as
+ * stream s of a tracker just made by flvis_tracker_create with the same cfg / seed_base / traj_capacity (F2FTracking::init + VIMOTION
+ * ctor + an empty local map, src/frontend/f2f_tracking.cpp:5-38): frame ids, landmark ids (from 100), the dummy depth's rand() state,
+ * skip_first_n_imgs, the IMU filter, the pose records, the trajectory rows (from row 0) and the local map all start over; time may go
+ * backwards across the reset.  Discarded: IMU samples staged and not yet integrated, IMU-state rows not yet fetched, a correction
+ * handed over with flvis_correction_feed and not yet applied, keyframes queued for the local map and not yet optimised (an optimisation
+ * running at the reset publishes no correction that outlives it).  Other streams are not disturbed.  Duplicates are one reset; two
+ * resets before the next frame step are one.  Enqueued in stream order; does not wait for the device.  n == 0: no-op.  A stream out of
+ * range: FLVIS_ERR_INVALID_ARG and nothing changes.  The context-wide counters (flvis_get_counters(_n)) stay cumulative.  The
+ * keyframe getters (flvis_get_keyframe, _msg, _imu, _imu_pos) return the stream's last keyframe since its last reset, none before the
+ * next one.  The reset takes a keyframe-queue entry, which the tracker's back-pressure keeps free; should a full queue be met all the
+ * same, the next flvis_hip_synchronize returns FLVIS_ERR_CAPACITY. */
+int flvis_reset_streams(flvis_ctx* ctx, int n, const int* streams);
+/* KFMSG_CMD_RESET_LM for the named streams' local maps alone (vo_localmap.cpp:87-98): keyframes queued before the command are
+ * processed first, then the window, the graph and the keyframe deque are emptied and the optimiser returns to UN_INITIALIZED; the
+ * published correction is withdrawn and the stream's flvis_get_local_map_counts entries start from 0.  The tracker is not touched.
+ * The keyframe getters still return the stream's last keyframe.  Enqueued in stream order, in order with the keyframes; does not
+ * wait for the device.  Arguments and errors as flvis_reset_streams. */
+int flvis_local_map_reset(flvis_ctx* ctx, int n, const int* streams);
+/* Counters: [0] frames fed, [1] keyframes, [2] BA runs.  Cumulative over the context's work: a stream reset does not take them back. */
 int flvis_get_counters(flvis_ctx* ctx, int64_t* h_counters3);
 /* The first n (1 .. 4) of: [0] frames fed, [1] keyframes, [2] BA runs, [3] keyframes dropped at a full keyframe queue -- what the
  * reference's /vo_kf subscriber (queue size 10, src/backend/vo_localmap.cpp:452-456) does when the local map is slower than the tracker.
@@ -468,7 +487,8 @@ int flvis_get_counters(flvis_ctx* ctx, int64_t* h_counters3);
  * (flvis_ba_push_keyframe) faster than it lets the local map run. */
 int flvis_get_counters_n(flvis_ctx* ctx, int n, int64_t* h_counters);
 /* Per stream (arrays of n_streams, either may be NULL): keyframes the tracker has emitted and optimisations the stream's local map has
- * run (one per keyframe once the window holds window_size keyframes, vo_localmap.cpp:211-214,292-366).  Drains the queues first. */
+ * run (one per keyframe once the window holds window_size keyframes, vo_localmap.cpp:211-214,292-366), both since the stream's last
+ * reset (flvis_reset_streams, flvis_local_map_reset).  Drains the queues first. */
 int flvis_get_local_map_counts(flvis_ctx* ctx, int64_t* h_keyframes, int64_t* h_ba_runs);
 /* Test aid: poses (tx ty tz qx qy qz qw) of a stream's last Tracking frame right after PnP-RANSAC and after the pose-only LM
  * (the two fp64 stages of LKORBTracking::tracking / OptimizeInFrame::optimize), h_out21 = 3 x 7 doubles (the third: the pose the LM starts from). */

@@ -45,7 +45,12 @@ class LocalMapNodelet : public nodelet::Nodelet {
   }
 
   void keyframeCallback(const flvis::KeyFrameConstPtr& kf) {
-    if (kf->command != 0) return;  // KFMSG_CMD_RESET_LM: never published by the reference's v2 (vo_tracking.cpp:431)
+    if (kf->command == 1) {  // KFMSG_CMD_RESET_LM (keyframe_msg.h:11): empty the window, in order with the keyframes (vo_localmap.cpp:87-98)
+      const int stream = 0;
+      if (flvis_local_map_reset(ctx_, 1, &stream) != FLVIS_OK) NODELET_ERROR_THROTTLE(1.0, "local_map_reset: %s", flvis_last_error(ctx_));
+      return;
+    }
+    if (kf->command != 0) return;
     const int n = kf->lm_count;
     std::vector<double> p2(2 * n), p3(3 * n);
     for (int i = 0; i < n; i++) {
