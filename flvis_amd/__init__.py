@@ -697,18 +697,30 @@ class LoopCloser:
 
 
 class Tracker:
-    """Batched F2FTracking + LocalMap for n_streams independent streams on one GPU (flvis_tracker_create)."""
+    """Batched F2FTracking + LocalMap for n_streams independent streams on one GPU (flvis_tracker_create).
+
+    cfg: one config for every stream, or a sequence of n_streams configs -- one per stream, each camera with its own calibration
+    (flvis_tracker_create_rigs: the batch-wide fields must agree, FlvisError otherwise).  self.cfg is stream 0's."""
 
     def __init__(self, ctx, cfg, n_streams, seed_base=0xF1715, traj_capacity=0):
         import numpy as np
         self.ctx = ctx
         self.lib = ctx._lib
         self.S = n_streams
-        self.cfg = cfg
         self.np = np
-        self.lib.flvis_tracker_create.argtypes = [C.c_void_p, C.POINTER(FlvisCfg), C.c_int, C.c_uint64, C.c_int]
-        ctx._check(self.lib.flvis_tracker_create(ctx._h, C.byref(cfg), n_streams, seed_base, traj_capacity),
-                   "tracker_create")
+        if isinstance(cfg, FlvisCfg):
+            self.cfg = cfg
+            self.lib.flvis_tracker_create.argtypes = [C.c_void_p, C.POINTER(FlvisCfg), C.c_int, C.c_uint64, C.c_int]
+            ctx._check(self.lib.flvis_tracker_create(ctx._h, C.byref(cfg), n_streams, seed_base, traj_capacity),
+                       "tracker_create")
+        else:
+            cfgs = list(cfg)
+            if len(cfgs) != n_streams:
+                raise ValueError("Tracker: %d configs for %d streams" % (len(cfgs), n_streams))
+            self.cfg = cfgs[0]
+            arr = (FlvisCfg * n_streams)(*cfgs)
+            self.lib.flvis_tracker_create_rigs.argtypes = [C.c_void_p, C.POINTER(FlvisCfg), C.c_int, C.c_uint64, C.c_int]
+            ctx._check(self.lib.flvis_tracker_create_rigs(ctx._h, arr, n_streams, seed_base, traj_capacity), "tracker_create_rigs")
         self._out = (FrameOut * n_streams)()
 
     def imu_feed_flvis(self, stream, samples7):
@@ -1006,10 +1018,30 @@ class Tracker:
         fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         self.ctx._check(fn(self.ctx._h, len(ids), arr), what[len("flvis_"):])
 
-    def reset_streams(self, streams):
+    def reset_streams(self, streams, cfgs=None):
         """flvis_reset_streams: the named streams start over as streams of a new tracker (the others go on undisturbed); from the next
-        frame step on.  FlvisError for an index outside [0, S)."""
-        self._stream_list(streams, "flvis_reset_streams")
+        frame step on.  FlvisError for an index outside [0, S).  cfgs: one config per named stream, which it starts over on
+        (flvis_reset_streams_rigs; FlvisError and nothing changes if one of them fails the checks)."""
+        if cfgs is None:
+            self._stream_list(streams, "flvis_reset_streams")
+            return
+        ids = [int(k) for k in streams]
+        cfgs = [cfgs] if isinstance(cfgs, FlvisCfg) else list(cfgs)
+        if len(cfgs) != len(ids):
+            raise ValueError("reset_streams: %d configs for %d streams" % (len(cfgs), len(ids)))
+        arr = (C.c_int * max(1, len(ids)))(*ids)
+        carr = (FlvisCfg * max(1, len(ids)))(*cfgs)
+        fn = self.lib.flvis_reset_streams_rigs
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(FlvisCfg)]
+        self.ctx._check(fn(self.ctx._h, len(ids), arr, carr), "reset_streams_rigs")
+
+    def stream_cfg(self, s):
+        """flvis_get_stream_cfg: the config stream s runs on (as created, or as last reset with reset_streams(..., cfgs))."""
+        out = FlvisCfg()
+        fn = self.lib.flvis_get_stream_cfg
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlvisCfg)]
+        self.ctx._check(fn(self.ctx._h, int(s), C.byref(out)), "get_stream_cfg")
+        return out
 
     def local_map_reset(self, streams):
         """flvis_local_map_reset: KFMSG_CMD_RESET_LM for the named streams' local maps (what is queued ahead is processed first)."""

@@ -2391,10 +2391,10 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
     sh.W = W;
     sh.use_mfma = p.ba_mfma;
     sh.balance = p.ba_balance && !p.ba_mfma;
-    sh.K[0] = p.cam.fx;
-    sh.K[1] = p.cam.fy;
-    sh.K[2] = p.cam.cx;
-    sh.K[3] = p.cam.cy;
+    sh.K[0] = w.K[0];  // (the window's rig: WindowDev::K)
+    sh.K[1] = w.K[1];
+    sh.K[2] = w.K[2];
+    sh.K[3] = w.K[3];
     // IMU rotation edges of this window: slot j is linked to its chronological predecessor (the previous ring slot) unless j
     // is the oldest pose
     int ne = 0;
@@ -2414,8 +2414,8 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
         }
         ne++;
       }
-      sh.q_c_b[0] = p.cam.T_c_i[6], sh.q_c_b[1] = p.cam.T_c_i[3], sh.q_c_b[2] = p.cam.T_c_i[4], sh.q_c_b[3] = p.cam.T_c_i[5];
-      sh.t_c_b[0] = p.cam.T_c_i[0], sh.t_c_b[1] = p.cam.T_c_i[1], sh.t_c_b[2] = p.cam.T_c_i[2];
+      sh.q_c_b[0] = w.T_c_i[6], sh.q_c_b[1] = w.T_c_i[3], sh.q_c_b[2] = w.T_c_i[4], sh.q_c_b[3] = w.T_c_i[5];
+      sh.t_c_b[0] = w.T_c_i[0], sh.t_c_b[1] = w.T_c_i[1], sh.t_c_b[2] = w.T_c_i[2];
     }
     sh.n_imu = ne;
     sh.n_trials = 0;

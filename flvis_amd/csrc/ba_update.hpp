@@ -217,6 +217,9 @@ __device__ __noinline__ void ba_update_dev(const Pipe& p, int s, const KeyFrameD
       dst.imu_dt = src.imu_dt;
       dst.imu_valid = src.imu_valid;
       for (int j = 0; j < 3; j++) dst.imu_dp[j] = src.imu_dp[j], dst.imu_va[j] = src.imu_va[j];
+      // the window's rig: every keyframe since the stream's last reset command carries the same one
+      for (int j = 0; j < 4; j++) w.K[j] = src.rig_K[j];
+      for (int j = 0; j < 7; j++) w.T_c_i[j] = src.rig_T_c_i[j];
       w.kfs_size++;
       if (p.counters) atomicAdd((unsigned long long*)&p.counters[1], 1ull);
     }

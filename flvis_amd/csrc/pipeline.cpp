@@ -123,7 +123,9 @@ struct Lane {
 
 struct Pipeline {
   int S = 0;
-  flvis_cfg cfg;
+  flvis_cfg cfg;                 // the batch-wide fields every stream shares (stream 0's config)
+  std::vector<flvis_cfg> cfgs;   // [S] the config each stream runs on (flvis_get_stream_cfg) ...
+  std::vector<RigParams> rigs;   // [S] ... and its rig as the device has it (host mirror of the lanes' Pipe::rig)
   int lane_size = 0;
   std::vector<Lane*> lanes;
   int levels_t = 0, levels_s = 0, levels = 0;
@@ -288,6 +290,31 @@ void pose7_from_mat44(const double* m, double* out7, bool inverse) {
   out7[6] = q[0];
 }
 
+// the per-stream part of a finalized config (RigParams): the one place a rig is made, for tracker creation and flvis_reset_streams_rigs
+void rig_from_cfg(const flvis_cfg& cfg, RigParams& r) {
+  memset(&r, 0, sizeof(r));
+  r.fx = cfg.P0[0];
+  r.fy = cfg.P0[5];
+  r.cx = cfg.P0[2];
+  r.cy = cfg.P0[6];
+  memcpy(r.K0, cfg.cam0_intrinsics, 32);
+  memcpy(r.D0, cfg.cam0_distortion, 32);
+  memcpy(r.K1, cfg.cam1_intrinsics, 32);
+  memcpy(r.D1, cfg.cam1_distortion, 32);
+  memcpy(r.R0, cfg.R0, 72);
+  memcpy(r.R1, cfg.R1, 72);
+  memcpy(r.P0, cfg.P0, 96);
+  memcpy(r.P1, cfg.P1, 96);
+  pose7_from_mat44(cfg.T_cam0_cam1, r.T_c1_c0, true);
+  pose7_from_mat44(cfg.T_imu_cam0, r.T_i_c, false);
+  pose7_from_mat44(cfg.T_imu_cam0, r.T_c_i, true);
+  r.iir_ratio = (float)cfg.dr_para[0];
+  r.range = (float)cfg.dr_para[1];
+  r.depth_scale = cfg.depth_factor;
+  r.enable_dummy = !(cfg.dr_para[2] < 0.5);
+  for (int i = 0; i < 4; i++) r.vi_para[i] = cfg.vifusion_para[i];
+}
+
 }  // namespace flvis
 namespace {
 }  // namespace
@@ -395,28 +422,8 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   c.cam_type = cfg->cam_type;
   c.w = w;
   c.h = h;
-  c.fx = cfg->P0[0];
-  c.fy = cfg->P0[5];
-  c.cx = cfg->P0[2];
-  c.cy = cfg->P0[6];
-  memcpy(c.K0, cfg->cam0_intrinsics, 32);
-  memcpy(c.D0, cfg->cam0_distortion, 32);
-  memcpy(c.K1, cfg->cam1_intrinsics, 32);
-  memcpy(c.D1, cfg->cam1_distortion, 32);
-  memcpy(c.R0, cfg->R0, 72);
-  memcpy(c.R1, cfg->R1, 72);
-  memcpy(c.P0, cfg->P0, 96);
-  memcpy(c.P1, cfg->P1, 96);
-  pose7_from_mat44(cfg->T_cam0_cam1, c.T_c1_c0, true);
-  pose7_from_mat44(cfg->T_imu_cam0, c.T_i_c, false);
-  pose7_from_mat44(cfg->T_imu_cam0, c.T_c_i, true);
-  c.iir_ratio = (float)cfg->dr_para[0];
-  c.range = (float)cfg->dr_para[1];
-  c.depth_scale = cfg->depth_factor;
-  c.enable_dummy = !(cfg->dr_para[2] < 0.5);
   c.need_equal_hist = cfg->need_equal_hist;
   c.skip_first_n = cfg->skip_first_n_imgs;
-  for (int i = 0; i < 4; i++) c.vi_para[i] = cfg->vifusion_para[i];
   c.dem.regionWidth = (int)std::floor(w / 4.0);
   c.dem.regionHeight = (int)std::floor(h / 4.0);
   c.dem.boundary_dis = (int)std::floor(cfg->feature_para[2] / 2.0);
@@ -429,6 +436,9 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
 
   bool ok = true;
 #define DA(field, T, n) ok = ok && ((p.field = dalloc<T>(L->allocs, (n))) != nullptr)
+  RigParams* rig = dalloc<RigParams>(L->allocs, S);
+  ok = ok && rig;
+  p.rig = rig;
   DA(st, StreamState, S);
   DA(lm, Landmark, (size_t)2 * S * NMAX);
   DA(vi, MotionState, (size_t)S * VI_QUEUE);
@@ -630,6 +640,7 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   std::vector<unsigned long long> hseed(S);
   for (int s = 0; s < S; s++) hseed[s] = seed_base + (unsigned long long)(s0 + s);  // the seed of a stream does not depend on the lane partition
   hipMemcpy(seeds, hseed.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice);
+  hipMemcpy(rig, pl->rigs.data() + s0, sizeof(RigParams) * S, hipMemcpyHostToDevice);
   L->cmd_frame.assign(S, -1);
   L->h_imu.assign((size_t)S * IMU_MAX * 7, 0.0);
   L->h_nimu.assign(S, 0);
@@ -681,18 +692,56 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
 
 extern "C" {
 
-int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, uint64_t seed_base, int traj_capacity) {
-  if (!ctx || !cfg || n_streams <= 0) return FLVIS_ERR_INVALID_ARG;
-  if (ctx->pipe) flvis_pipeline_destroy_internal(ctx);
+}  // extern "C"
+
+// The checks a tracker's config has to pass (every stream's, with a prefix naming it, for the per-stream entry points)
+static int check_cfg(flvis_ctx* ctx, const flvis_cfg* cfg, const std::string& pre) {
   const int w = cfg->image_width, h = cfg->image_height;
-  if (w < 64 || h < 64) return ctx->fail(FLVIS_ERR_CONFIG, "image must be at least 64 x 64");
-  if (cfg->need_equal_hist && (w & 15)) return ctx->fail(FLVIS_ERR_CONFIG, "equalizeHist rigs need an image width that is a multiple of 16");
-  if (cfg->feature_para[5] > 64.0) return ctx->fail(FLVIS_ERR_CAPACITY, "feature_para6 (GFTT minDistance) > 64 is not supported");
-  if (cfg->window_size > BA_WMAX) return ctx->fail(FLVIS_ERR_CAPACITY, "window_size exceeds the LDS-resident solver (16)");
-  if (16 * (int)cfg->feature_para[0] > 512) return ctx->fail(FLVIS_ERR_CAPACITY, "feature_para1 (landmarks per region) must be <= 32: the pose LM holds 512 edges");
-  if ((int)cfg->feature_para[3] * 2 > 4096) return ctx->fail(FLVIS_ERR_CAPACITY, "feature_para4 (gftt_num) must be <= 2048");
-  if ((size_t)((w + 31) / 32) * h * 4 > 96 * 1024) return ctx->fail(FLVIS_ERR_CAPACITY, "image too large for the GFTT LDS bitmap");
-  if (cfg->cam_type == CAM_DEPTH && !(cfg->depth_factor > 0)) return ctx->fail(FLVIS_ERR_CONFIG, "depth mode needs depth_factor > 0");
+  if (w < 64 || h < 64) return ctx->fail(FLVIS_ERR_CONFIG, pre + "image must be at least 64 x 64");
+  if (cfg->need_equal_hist && (w & 15)) return ctx->fail(FLVIS_ERR_CONFIG, pre + "equalizeHist rigs need an image width that is a multiple of 16");
+  if (cfg->feature_para[5] > 64.0) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para6 (GFTT minDistance) > 64 is not supported");
+  if (cfg->window_size > BA_WMAX) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "window_size exceeds the LDS-resident solver (16)");
+  if (16 * (int)cfg->feature_para[0] > 512) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para1 (landmarks per region) must be <= 32: the pose LM holds 512 edges");
+  if ((int)cfg->feature_para[3] * 2 > 4096) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para4 (gftt_num) must be <= 2048");
+  if ((size_t)((w + 31) / 32) * h * 4 > 96 * 1024) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "image too large for the GFTT LDS bitmap");
+  if (cfg->cam_type == CAM_DEPTH && !(cfg->depth_factor > 0)) return ctx->fail(FLVIS_ERR_CONFIG, pre + "depth mode needs depth_factor > 0");
+  return FLVIS_OK;
+}
+
+// The batch-wide fields (CamParams: buffer sizes, launch geometry, code paths): the name of the first one in which c differs from ref, or
+// nullptr when they all agree.  Compared bit for bit (memcmp): a config loaded from the same yaml always matches.
+static const char* batch_field_mismatch(const flvis_cfg& ref, const flvis_cfg& c) {
+  if (c.type_of_vi != ref.type_of_vi) return "type_of_vi";
+  if (c.cam_type != ref.cam_type) return "cam_type";
+  if (c.imu_type != ref.imu_type) return "imu_type";
+  if (c.image_width != ref.image_width) return "image_width";
+  if (c.image_height != ref.image_height) return "image_height";
+  static const char* const fp[6] = {"feature_para[0]", "feature_para[1]", "feature_para[2]", "feature_para[3]", "feature_para[4]", "feature_para[5]"};
+  for (int i = 0; i < 6; i++)
+    if (memcmp(&c.feature_para[i], &ref.feature_para[i], sizeof(double))) return fp[i];
+  if (c.window_size != ref.window_size) return "window_size";
+  if (c.skip_first_n_imgs != ref.skip_first_n_imgs) return "skip_first_n_imgs";
+  if (c.need_equal_hist != ref.need_equal_hist) return "need_equal_hist";
+  return nullptr;
+}
+
+// Every config of a per-stream entry point: flvis_tracker_create's checks, and the batch-wide fields of `ref`
+static int check_stream_cfgs(flvis_ctx* ctx, const flvis_cfg& ref, int n, const flvis_cfg* cfgs, const int* streams, const char* what) {
+  for (int i = 0; i < n; i++) {
+    const int s = streams ? streams[i] : i;
+    const std::string pre = std::string(what) + ": stream " + std::to_string(s) + ": ";
+    const int rc = check_cfg(ctx, &cfgs[i], pre);
+    if (rc != FLVIS_OK) return rc;
+    if (const char* f = batch_field_mismatch(ref, cfgs[i]))
+      return ctx->fail(FLVIS_ERR_CONFIG, pre + "batch-wide field " + f + " differs from the tracker's (stream 0)");
+  }
+  return FLVIS_OK;
+}
+
+// cfgs: one config for all streams (n_cfgs 1, flvis_tracker_create) or one per stream (n_cfgs = n_streams), checked by the caller
+static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs, int n_streams, uint64_t seed_base, int traj_capacity) {
+  const flvis_cfg* cfg = &cfgs[0];
+  const int w = cfg->image_width, h = cfg->image_height;
   hipSetDevice(ctx->device);
   Pipeline* pl = new Pipeline();
   ctx->pipe = pl;
@@ -719,6 +768,13 @@ int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, ui
   const int S = n_streams;
   pl->S = S;
   pl->cfg = *cfg;
+  pl->cfgs.resize(S);
+  pl->rigs.resize(S);
+  for (int k = 0; k < S; k++) {
+    pl->cfgs[k] = cfgs[n_cfgs == 1 ? 0 : k];
+    if (k > 0 && n_cfgs == 1) pl->rigs[k] = pl->rigs[0];
+    else rig_from_cfg(pl->cfgs[k], pl->rigs[k]);
+  }
   pl->max_pts = std::min(NMAX, 16 * (int)cfg->feature_para[0]);
   // pyramid geometry
   pl->levels_t = lk_levels(w, h, 31, 10);
@@ -816,6 +872,33 @@ int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, ui
     return ctx->fail(FLVIS_ERR_HIP, "tracker_create: cannot reserve LDS for the BA kernel");
   }
   hipDeviceSynchronize();
+  return FLVIS_OK;
+}
+
+extern "C" {
+
+int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, uint64_t seed_base, int traj_capacity) {
+  if (!ctx || !cfg || n_streams <= 0) return FLVIS_ERR_INVALID_ARG;
+  if (ctx->pipe) flvis_pipeline_destroy_internal(ctx);
+  const int rc = check_cfg(ctx, cfg, "");
+  if (rc != FLVIS_OK) return rc;
+  return tracker_create_impl(ctx, cfg, 1, n_streams, seed_base, traj_capacity);
+}
+
+int flvis_tracker_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_streams, uint64_t seed_base, int traj_capacity) {
+  if (!ctx || !cfgs || n_streams <= 0) return FLVIS_ERR_INVALID_ARG;
+  const int rc = check_stream_cfgs(ctx, cfgs[0], n_streams, cfgs, nullptr, "tracker_create_rigs");
+  if (rc != FLVIS_OK) return rc;  // (nothing created: a tracker the context holds stays)
+  if (ctx->pipe) flvis_pipeline_destroy_internal(ctx);
+  return tracker_create_impl(ctx, cfgs, n_streams, n_streams, seed_base, traj_capacity);
+}
+
+int flvis_get_stream_cfg(flvis_ctx* ctx, int stream, flvis_cfg* out) {
+  if (!ctx || !out) return FLVIS_ERR_INVALID_ARG;
+  Pipeline* pl = ctx->pipe;
+  if (!pl) return ctx->fail(FLVIS_ERR_INVALID_ARG, "get_stream_cfg: no tracker (flvis_tracker_create)");
+  if (stream < 0 || stream >= pl->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, "get_stream_cfg: stream out of range");
+  *out = pl->cfgs[stream];
   return FLVIS_OK;
 }
 
@@ -2259,17 +2342,25 @@ int flvis_get_local_map_counts(flvis_ctx* ctx, int64_t* h_keyframes, int64_t* h_
 // Per-stream reset (include/flvis_hip.h).  Host side: the stream's staged IMU samples and the IMU-state rows not yet fetched are dropped;
 // device side, in stream order on the lane's tracking stream: k_stream_reset (the tracker state of a new stream, and a reset command
 // in the keyframe queue that the local map applies in order with the keyframes).  No host synchronisation.
-static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, const char* what) {
+// cfgs (flvis_reset_streams_rigs): the config each named stream starts over on, validated before anything changes; its rig reaches the
+// device in stream order ahead of the stream's k_stream_reset (k_set_rig), so the frames before the reset read the old rig and those after
+// it the new one.  The local map needs no such point: a keyframe carries the rig it was made with (KeyFrameDev::rig_K).
+static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, const char* what, const flvis_cfg* cfgs = nullptr) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
   Pipeline* pl = ctx->pipe;
   if (!pl) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": no tracker (flvis_tracker_create)");
   if (n < 0 || (n > 0 && !streams)) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": bad stream list");
   for (int i = 0; i < n; i++)
     if (streams[i] < 0 || streams[i] >= pl->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": stream out of range");
+  if (cfgs) {
+    const int rc = check_stream_cfgs(ctx, pl->cfg, n, cfgs, streams, what);
+    if (rc != FLVIS_OK) return rc;
+  }
   if (n == 0) return FLVIS_OK;
   hipSetDevice(ctx->device);
   std::vector<char> named(pl->S, 0);
-  for (int i = 0; i < n; i++) named[streams[i]] = 1;  // (duplicates: one reset)
+  std::vector<int> cfg_of(pl->S, -1);
+  for (int i = 0; i < n; i++) named[streams[i]] = 1, cfg_of[streams[i]] = i;  // (duplicates: one reset, on the last entry's config)
   for (Lane* L : pl->lanes) {
     std::vector<std::pair<int, unsigned char>> todo;
     bool new_cmd = false;
@@ -2301,6 +2392,14 @@ static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, c
         if (j >= 0 && L->ba_launches - j <= Lane::BAQ) join_wait(pl, L, L->st, L->ev_ba_done[j % Lane::BAQ]);
       }
     }
+    if (cfgs) {
+      for (const auto& e : todo) {
+        const int g = L->s0 + e.first;
+        pl->cfgs[g] = cfgs[cfg_of[g]];
+        rig_from_cfg(pl->cfgs[g], pl->rigs[g]);
+        launch_set_rig(L->st, L->pipe, e.first, pl->rigs[g]);
+      }
+    }
     for (size_t b = 0; b < todo.size(); b += RESET_LIST) {
       ResetList rl{};
       rl.n = (int)std::min(todo.size() - b, (size_t)RESET_LIST);
@@ -2317,6 +2416,11 @@ static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, c
 }
 
 int flvis_reset_streams(flvis_ctx* ctx, int n, const int* streams) { return reset_impl(ctx, n, streams, true, "reset_streams"); }
+
+int flvis_reset_streams_rigs(flvis_ctx* ctx, int n, const int* streams, const flvis_cfg* cfgs) {
+  if (ctx && n > 0 && !cfgs) return ctx->fail(FLVIS_ERR_INVALID_ARG, "reset_streams_rigs: no configs");
+  return reset_impl(ctx, n, streams, true, "reset_streams_rigs", cfgs);
+}
 
 int flvis_local_map_reset(flvis_ctx* ctx, int n, const int* streams) { return reset_impl(ctx, n, streams, false, "local_map_reset"); }
 
@@ -2511,6 +2615,11 @@ static int ba_push_impl(flvis_ctx* ctx, int stream, int64_t frame_id, const doub
   kf.lm_count = lm_count;
   kf.valid = 1;
   memcpy(kf.T_c_w, T7, 56);
+  {  // the stream's rig, as k_frame_end gives it to the keyframes it makes
+    const RigParams& r = pl->rigs[stream];
+    kf.rig_K[0] = r.fx, kf.rig_K[1] = r.fy, kf.rig_K[2] = r.cx, kf.rig_K[3] = r.cy;
+    memcpy(kf.rig_T_c_i, r.T_c_i, 56);
+  }
   kf.imu_dq[0] = 1.0;
   if (imu_dq && imu_dt > 0) {
     memcpy(kf.imu_dq, imu_dq, 32);

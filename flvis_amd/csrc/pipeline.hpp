@@ -47,17 +47,11 @@ struct MotionState {  // MOTION_STATE (vi_motion.h:12-17)
   double pos[3], vel[3], q[4] /*w x y z*/, acc[3], gyro[3], t;
 };
 
+// The batch-wide part of a tracker's configuration: what sizes buffers, sets the launch geometry or picks a code path.  Every stream
+// of a tracker shares it (flvis_tracker_create_rigs checks that every stream's config agrees on it).
 struct CamParams {
   int cam_type, w, h;
-  double fx, fy, cx, cy;  // rectified (from P0)
-  double K0[4], D0[4], K1[4], D1[4];
-  double R0[9], R1[9], P0[12], P1[12];
-  double T_c1_c0[7];  // pose7
-  double T_i_c[7], T_c_i[7];
-  float iir_ratio, range;
-  double depth_scale;  // DEPTH_D435: cam_scale_factor (Z16 units per metre)
-  int enable_dummy, need_equal_hist, skip_first_n;
-  double vi_para[4];
+  int need_equal_hist, skip_first_n;
   DemParams dem;
   int gftt_num;
   double gftt_ql;
@@ -65,6 +59,36 @@ struct CamParams {
   int window;
   unsigned long long seed;
 };
+
+// The per-stream part: one camera's calibration and the tuning that goes with it (Pipe::rig, one per stream).  Built from a stream's
+// flvis_cfg by rig_from_cfg (pipeline.cpp), at tracker creation and at flvis_reset_streams_rigs.
+struct RigParams {
+  double fx, fy, cx, cy;  // rectified (from P0)
+  double K0[4], D0[4], K1[4], D1[4];
+  double R0[9], R1[9], P0[12], P1[12];
+  double T_c1_c0[7];  // pose7
+  double T_i_c[7], T_c_i[7];
+  double depth_scale;  // DEPTH_D435: cam_scale_factor (Z16 units per metre)
+  double vi_para[4];
+  float iir_ratio, range;
+  int enable_dummy, pad;
+};
+static_assert(sizeof(RigParams) % 8 == 0, "RigParams layout");
+// a stream's rig as the kernels see it (rig_of, track_kernels.hpp)
+#define FLVIS_CONST_AS __attribute__((address_space(4)))
+typedef const FLVIS_CONST_AS RigParams CRig;
+// a rig array as a value in registers, for the helpers that take plain pointers
+template <int N>
+struct RigArr {
+  double v[N];
+};
+template <int N>
+__device__ inline RigArr<N> rig_arr(const FLVIS_CONST_AS double (&a)[N]) {
+  RigArr<N> r;
+#pragma unroll
+  for (int i = 0; i < N; i++) r.v[i] = a[i];
+  return r;
+}
 
 struct StreamState {
   int state, phase, ok, cur;
@@ -122,6 +146,9 @@ struct KeyFrameDev {
   // ... with the position part: dp = preintegrated body displacement over the same interval (body frame of the previous keyframe),
   // va = the filter's body velocity (world frame) when the previous keyframe was made
   double imu_dp[3], imu_va[3];
+  // (addition) the intrinsics (fx, fy, cx, cy) and the camera-from-IMU pose7 of the rig the keyframe was made with: the local map's
+  // optimisation of the stream's window reads them (WindowDev::K)
+  double rig_K[4], rig_T_c_i[7];
   long long lm_id[KF_MAXLM];
   double lm_2d[KF_MAXLM][2];
   double lm_3d[KF_MAXLM][3];
@@ -167,6 +194,8 @@ struct WindowDev {
   int solve;        // set by the bookkeeping kernel when this keyframe triggers an optimisation
   int overflow;     // a capacity (BA_LMAX / BA_EMAX) was exceeded; the window stops accepting work
   long long ba_runs;
+  // the rig of the window's keyframes (KeyFrameDev::rig_K / rig_T_c_i of the last one added): what its optimisation projects with
+  double K[4], T_c_i[7];
 };
 
 // KeyFrameDev::valid of a keyframe queue entry: a keyframe, or KFMSG_CMD_RESET_LM (keyframe_msg.h:11) -- the local map empties its window
@@ -175,6 +204,10 @@ enum { KFQ_KEYFRAME = 1, KFQ_CMD_RESET = 2 };
 
 // host helpers shared by the tracker set-up and the one-call entry points (pipeline.cpp)
 void pose7_from_mat44(const double* m44, double* out7, bool inverse);
+}  // namespace flvis
+struct flvis_cfg;
+namespace flvis {
+void rig_from_cfg(const flvis_cfg& cfg, RigParams& r);  // a stream's rig from its finalized config
 
 // the state srand(s) leaves: the last 34 words of glibc's TYPE_3 table (r[i] = r[i - 31] + r[i - 3] over 344 words, kept in a ring of 34)
 __host__ __device__ inline void glibc_seed(unsigned s, int* r34) {

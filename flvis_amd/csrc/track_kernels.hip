@@ -73,9 +73,10 @@ __device__ inline void imu_feed_dev(const Pipe& p, int s, const double* in) {
   // F2FTracking::imu_feed's per-sample outputs go to the stream's output ring (row = sample number % IMU_OUT_CAP)
   double* const out = p.imu_out + (size_t)s * IMU_OUT_CAP * IMU_ROW;
   long long seen = st.imu_seen;
+  const ViGain gain{{rig_of(p, s).vi_para[0]}};
   int i = 0;
   for (; i < n && !st.vi_initialized; i++, seen++)  // start-up: attitude initialisation, sample by sample
-    vi_imu_feed(p.cam, st, ring, in[7 * i], V3{in[7 * i + 1], in[7 * i + 2], in[7 * i + 3]},
+    vi_imu_feed(gain, st, ring, in[7 * i], V3{in[7 * i + 1], in[7 * i + 2], in[7 * i + 3]},
                 V3{in[7 * i + 4], in[7 * i + 5], in[7 * i + 6]}, out + (size_t)(seen % IMU_OUT_CAP) * IMU_ROW);
   if (i < n) {
     const V3 acc_bias = ld3(st.acc_bias), gyro_bias = ld3(st.gyro_bias);
@@ -86,7 +87,7 @@ __device__ inline void imu_feed_dev(const Pipe& p, int s, const double* in) {
     V3 kdp = ld3(st.kf_dp), kdv = ld3(st.kf_dv);
     for (; i < n; i++, seen++) {
       MotionState cur;
-      vi_propagate(p.cam, prev, in[7 * i], V3{in[7 * i + 1], in[7 * i + 2], in[7 * i + 3]},
+      vi_propagate(gain, prev, in[7 * i], V3{in[7 * i + 1], in[7 * i + 2], in[7 * i + 3]},
                    V3{in[7 * i + 4], in[7 * i + 5], in[7 * i + 6]}, acc_bias, gyro_bias, cur, kdq, kdt, kdp, kdv);
       imu_row_store(out + (size_t)(seen % IMU_OUT_CAP) * IMU_ROW, cur.t, ms_q(cur), ld3(cur.pos), ld3(cur.vel));
       ring.base[(head + count) % VI_QUEUE] = cur;  // ViRing::push_back on the local cursor
@@ -107,7 +108,8 @@ __device__ inline void imu_feed_dev(const Pipe& p, int s, const double* in) {
   st.imu_seen = seen;
   p.n_imu[s] = 0;
 }
-__global__ void k_imu_feed(Pipe p) {
+// (64 threads per workgroup, launch_imu_feed: the bound lets the sample loop keep its state in registers -- a rig is read per lane)
+__global__ __launch_bounds__(64) void k_imu_feed(Pipe p) {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= p.S) return;
   imu_feed_dev(p, s, p.imu_in + (size_t)s * IMU_MAX * 7);
@@ -269,7 +271,7 @@ __device__ inline void frame_begin_dev(const Pipe& p, int s, double time) {
           if (st.vi_initialized) {
             Q4 q_init;
             vi_vision_trigger(ring, q_init);
-            M3 R = q_to_mat(q_init) * q_to_mat(load_pose7(p.cam.T_i_c).q);
+            M3 R = q_to_mat(q_init) * q_to_mat(load_pose7(rig_arr(rig_of(p, s).T_i_c).v).q);
             T = se3_inverse(se3_from_mat(R, V3{0, 0, 0}));
           } else {
             go = false;
@@ -284,7 +286,7 @@ __device__ inline void frame_begin_dev(const Pipe& p, int s, double time) {
       }
       case ST_TRACKING: {
         SE3d g = se3_identity();
-        if (st.has_imu) st.use_guess = vi_get_corr_frame_state(p.cam, ring, time, g) ? 1 : 0;
+        if (st.has_imu) st.use_guess = vi_get_corr_frame_state(rig_of(p, s), ring, time, g) ? 1 : 0;
         store_pose7(st.guess, g);
         st.phase = PH_TRACK;
         break;
@@ -293,7 +295,7 @@ __device__ inline void frame_begin_dev(const Pipe& p, int s, double time) {
         st.tf_cnt++;
         if ((st.tf_cnt % 3) == 0) {
           SE3d T;
-          if (vi_get_corr_frame_state(p.cam, ring, time, T)) {
+          if (vi_get_corr_frame_state(rig_of(p, s), ring, time, T)) {
             store_pose7(st.T_c_w[c], T);
             st.phase = PH_INIT;
             det_mode = 1;
@@ -324,6 +326,7 @@ __device__ inline void frame_begin_dev(const Pipe& p, int s, double time) {
 
 // ------------------------------------------------------------------------------------------------ temporal LK inputs
 __device__ __forceinline__ void track_prepare_dev(const Pipe& p, int s, int i) {
+  CRig& rg = rig_of(p, s);
   const StreamState& st = p.st[s];
   if (st.phase != PH_TRACK) return;
   const int last = st.cur ^ 1;
@@ -347,10 +350,10 @@ __device__ __forceinline__ void track_prepare_dev(const Pipe& p, int s, int i) {
     float p3[3] = {(float)lm.p3w[0], (float)lm.p3w[1], (float)lm.p3w[2]};
     if (p.cam.cam_type == CAM_DEPTH) {  // lkorb_tracking.cpp:41-52: pinhole projection of the float-narrowed landmark
       const V3 pc = se3_act(g, V3{(double)p3[0], (double)p3[1], (double)p3[2]});
-      np[0] = (float)(p.cam.fx * pc.x / pc.z + p.cam.cx);
-      np[1] = (float)(p.cam.fy * pc.y / pc.z + p.cam.cy);
+      np[0] = (float)(rg.fx * pc.x / pc.z + rg.cx);
+      np[1] = (float)(rg.fy * pc.y / pc.z + rg.cy);
     } else {
-      project_point(p3, q_to_mat(g.q), g.t, p.cam.K0, p.cam.D0, np);
+      project_point(p3, q_to_mat(g.q), g.t, rig_arr(rg.K0).v, rig_arr(rg.D0).v, np);
     }
   } else {
     np[0] = px;
@@ -395,6 +398,7 @@ __global__ __launch_bounds__(256) void k_frame_head_prepare(Pipe p, const double
 // of k_ransac_f (FLVIS_CHAIN_MERGE bit 1: one launch less on the frame's chain, sixteen waves instead of one).
 template <int T>
 __device__ __forceinline__ void track_collect_dev(const Pipe& p, int s, int* s_cnt /* [NMAX / 64 + 1] LDS */) {
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (st.phase != PH_TRACK) {
@@ -440,7 +444,7 @@ __device__ __forceinline__ void track_collect_dev(const Pipe& p, int s, int* s_c
         fu[1] = (float)lm.p2d[1];
       } else {
         float src[2] = {tx, ty};
-        undistort_point(src, p.cam.K0, p.cam.D0, p.cam.R0, p.cam.P0, und);
+        undistort_point(src, rig_arr(rg.K0).v, rig_arr(rg.D0).v, rig_arr(rg.R0).v, rig_arr(rg.P0).v, und);
         fu[0] = (float)lm.p2u[0];
         fu[1] = (float)lm.p2u[1];
       }
@@ -1666,6 +1670,7 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
 __device__ __forceinline__ void k_ransac_pnp_body(const Pipe& p) {
   chain_priority();
   const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   if (st.phase != PH_TRACK || !st.ok) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1719,7 +1724,7 @@ __device__ __forceinline__ void k_ransac_pnp_body(const Pipe& p) {
   int inliers = 0;
   // solvePnPRansac(..., 100, 3.0, 0.99, ...) of LKORBTracking::tracking (lkorb_tracking.cpp:170-177)
   pnp_ransac_core<kProf>(PnpShared{s2d, s3d, smask, hcnt, hpose, ctl, ssub, bpose, gterms, gn, ework, sinl}, np, st.use_guess != 0, load_pose7(st.guess),
-                         p.cam.fx, p.cam.fy, p.cam.cx, p.cam.cy, 0ull /* no seed: cv::RNG((uint64)-1) per call */,
+                         rg.fx, rg.fy, rg.cx, rg.cy, 0ull /* no seed: cv::RNG((uint64)-1) per call */,
                          100, 9.0f, 0.99, p.counters ? p.counters + 32 : nullptr, tlast_, T, inliers);
   if (wv != 0) return;
   __syncthreads();
@@ -1757,6 +1762,7 @@ struct PnpTailLanes {  // the 64 lanes of the stream's wave; sync: what one lane
 };
 __global__ __launch_bounds__(64) void k_pnp_tail_cv(Pipe p) {
   const int s = blockIdx.x, lane = threadIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   if (st.phase != PH_TRACK || !st.ok || st.use_guess == 0 || st.pnp_cnt <= 0) return;
   const int cur = st.cur;
@@ -1782,7 +1788,7 @@ __global__ __launch_bounds__(64) void k_pnp_tail_cv(Pipe p) {
   ln.sync();
   double rv[3], tv[3];
   // (every lane runs the function: the dense algebra redundantly, the loops over the correspondences dealt out -- cv_solvers.hpp)
-  if (!cvs::find_extrinsic_iterative(n, M, m, p.cam.fx, p.cam.fy, p.cam.cx, p.cam.cy, work, rv, tv, nullptr, ln)) return;
+  if (!cvs::find_extrinsic_iterative(n, M, m, rg.fx, rg.fy, rg.cx, rg.cy, work, rv, tv, nullptr, ln)) return;
   if (lane != 0) return;
   double Rm[9];
   cvs::rodrigues(rv, Rm, nullptr);
@@ -1899,7 +1905,7 @@ __device__ inline bool track_post_dev(const Pipe& p, int s) {
   if (st.has_imu) {
     ViRing ring{p.vi + (size_t)s * VI_QUEUE, &st};
     SE3d T = load_pose7(st.T_c_w[st.cur]);
-    vi_vision_rp_compensation(p.cam, ring, st.frame_time[st.cur], T);
+    vi_vision_rp_compensation(rig_of(p, s), ring, st.frame_time[st.cur], T);
     store_pose7(st.T_c_w[st.cur], T);
   }
   return true;
@@ -2074,6 +2080,7 @@ __device__ inline void pose_lm_optimize(SE3d& T, PoseLMShared& sh, int n, int it
 __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
   chain_priority();
   const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   if (st.phase != PH_TRACK) return;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2129,7 +2136,7 @@ __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
       sh.alive[rank] = 1;
     }
     __syncthreads();
-    const double fx = p.cam.fx, fy = p.cam.fy, cx = p.cam.cx, cy = p.cam.cy;
+    const double fx = rg.fx, fy = rg.fy, cx = rg.cx, cy = rg.cy;
     SE3d T0 = load_pose7(st.T_c_w[cur]);
     if (tid == 0) store_pose7(st.dbg_T_pre, T0);
     SE3d T = g2o_from_mat(q_to_mat(T0.q), T0.t);
@@ -2176,6 +2183,7 @@ __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
 __device__ __forceinline__ void k_reproj_filter_body(const Pipe& p) {
   chain_priority();
   const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   if (st.phase != PH_TRACK) return;
   const int i = threadIdx.x;
@@ -2192,7 +2200,7 @@ __device__ __forceinline__ void k_reproj_filter_body(const Pipe& p) {
   if (i < n) {
     lm = lms[i];
     V3 pc = se3_act(T, V3{lm.p3w[0], lm.p3w[1], lm.p3w[2]});
-    double u = p.cam.fx * pc.x / pc.z + p.cam.cx, vv = p.cam.fy * pc.y / pc.z + p.cam.cy;
+    double u = rg.fx * pc.x / pc.z + rg.cx, vv = rg.fy * pc.y / pc.z + rg.cy;
     double ex = lm.p2u[0] - u, ey = lm.p2u[1] - vv;
     d = sqrt(ex * ex + ey * ey);
     v = d < 3.0;
@@ -2260,7 +2268,7 @@ __global__ void k_vi_correction(Pipe p) {
   st.vi_corr_due = 0;
   const int cur = st.cur;
   ViRing ring{p.vi + (size_t)s * VI_QUEUE, &st};
-  vi_correction_from_vision(p.cam, st, ring, st.frame_time[cur], load_pose7(st.T_c_w[cur]), st.frame_time[cur ^ 1],
+  vi_correction_from_vision(rig_of(p, s), st, ring, st.frame_time[cur], load_pose7(st.T_c_w[cur]), st.frame_time[cur ^ 1],
                             load_pose7(st.T_c_w[cur ^ 1]));
 }
 
@@ -2269,6 +2277,7 @@ template <int T>
 __device__ __forceinline__ void k_add_new_body(const Pipe& p) {
   chain_priority();
   const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   const int mode = p.det_mode[s];
   if (mode == 0) return;
@@ -2285,7 +2294,7 @@ __device__ __forceinline__ void k_add_new_body(const Pipe& p) {
     float und[2] = {src[0], src[1]};
     // init_frame undistorts in both stereo modes, redetect only in STEREO_UNRECT, DEPTH_D435 never (f2f_tracking.cpp:294-304,410-437)
     if ((mode == 1 && p.cam.cam_type != CAM_DEPTH) || p.cam.cam_type == CAM_STEREO_UNRECT)
-      undistort_point(src, p.cam.K0, p.cam.D0, p.cam.R0, p.cam.P0, und);
+      undistort_point(src, rig_arr(rg.K0).v, rig_arr(rg.D0).v, rig_arr(rg.R0).v, rig_arr(rg.P0).v, und);
     Landmark lm;
     lm.id = st.lm_id_counter + k;
     lm.p3w[0] = lm.p3w[1] = lm.p3w[2] = 0;
@@ -2320,6 +2329,7 @@ __global__ __launch_bounds__(64) void k_add_new(Pipe p) {
 // Two kernels, because only the first is on the critical path: the stereo matcher needs its seeds; the two-view triangulation of
 // recover3DPts_c_FromTriangulation is consumed by k_depth_innovate and runs beside the stereo LK on the detection stream.
 __device__ __forceinline__ void depth_seed_dev(const Pipe& p, int s, int i) {
+  CRig& rg = rig_of(p, s);
   const StreamState& st = p.st[s];
   const int cur = st.cur;
   const int n = st.n_lm[cur];
@@ -2356,9 +2366,9 @@ __device__ __forceinline__ void depth_seed_dev(const Pipe& p, int s, int i) {
   }
   if (lm.has3d) {
     const SE3d T = load_pose7(st.T_c_w[cur]);
-    SE3d T1c = se3_mul(load_pose7(p.cam.T_c1_c0), T);
+    SE3d T1c = se3_mul(load_pose7(rig_arr(rg.T_c1_c0).v), T);
     float p3[3] = {(float)lm.p3w[0], (float)lm.p3w[1], (float)lm.p3w[2]};
-    project_point(p3, q_to_mat(T1c.q), T1c.t, p.cam.K1, p.cam.D1, p1);
+    project_point(p3, q_to_mat(T1c.q), T1c.t, rig_arr(rg.K1).v, rig_arr(rg.D1).v, p1);
   } else {
     p1[0] = p0[0];
     p1[1] = p0[1];
@@ -2392,6 +2402,7 @@ __global__ __launch_bounds__(256) void k_add_new_seeds(Pipe p) {
 __device__ __forceinline__ void k_depth_triangulate_body(const Pipe& p) {
   chain_priority();
   const int s = blockIdx.y;
+  CRig& rg = rig_of(p, s);
   const StreamState& st = p.st[s];
   if (p.det_mode[s] == 0) return;
   const int cur = st.cur;
@@ -2407,10 +2418,10 @@ __device__ __forceinline__ void k_depth_triangulate_body(const Pipe& p) {
   unsigned char tm = 0;
   tri[0] = tri[1] = tri[2] = 0;
   if (norm(baseline) >= 0.2) {
-    V3 pw = triangulate_two_view(lm.first2d[0], lm.first2d[1], lm.p2u[0], lm.p2u[1], T1, T, p.cam.fx, p.cam.fy, p.cam.cx,
-                                 p.cam.cy);
+    V3 pw = triangulate_two_view(lm.first2d[0], lm.first2d[1], lm.p2u[0], lm.p2u[1], T1, T, rg.fx, rg.fy, rg.cx,
+                                 rg.cy);
     V3 pc = se3_act(T, pw);
-    if (pc.z >= 0.5 && pc.z <= (double)p.cam.range) {
+    if (pc.z >= 0.5 && pc.z <= (double)rg.range) {
       tri[0] = pc.x;
       tri[1] = pc.y;
       tri[2] = pc.z;
@@ -2433,6 +2444,7 @@ __global__ __launch_bounds__(256) void k_depth_triangulate(Pipe p) {
 __device__ __forceinline__ void k_depth_innovate_body(const Pipe& p) {
   chain_priority();
   const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
   if (p.det_mode[s] == 0) return;
   const int i = threadIdx.x;
@@ -2443,7 +2455,7 @@ __device__ __forceinline__ void k_depth_innovate_body(const Pipe& p) {
   __shared__ int s_cnt[NMAX / 64];
   const float* p1 = p.next_pts + (size_t)s * NMAX * 2;
   const uint8_t* status = p.lk_status + (size_t)s * NMAX;
-  const double range = (double)p.cam.range;
+  const double range = (double)rg.range;
   const bool valid = i < n;
   Landmark lm;
   bool ok = false;
@@ -2460,16 +2472,16 @@ __device__ __forceinline__ void k_depth_innovate_body(const Pipe& p) {
       // (landmarks live in the open box (0, W-1) x (0, H-1), lkorb_tracking.cpp:95-102; the clamp only guards the read)
       const int ix = min(max(__float2int_rn(ptx), 0), p.cam.w - 1), iy = min(max(__float2int_rn(pty), 0), p.cam.h - 1);
       const uint16_t d16 = reinterpret_cast<const uint16_t*>(p.in_img1)[(size_t)s * p.cam.w * p.cam.h + (size_t)iy * p.cam.w + ix];
-      const float z = (float)((double)d16 / p.cam.depth_scale);
-      if ((double)z >= 0.3 && z <= p.cam.range) {
-        meas = V3{((double)ptx - p.cam.cx) * (double)z / p.cam.fx, ((double)pty - p.cam.cy) * (double)z / p.cam.fy, (double)z};
+      const float z = (float)((double)d16 / rg.depth_scale);
+      if ((double)z >= 0.3 && z <= rg.range) {
+        meas = V3{((double)ptx - rg.cx) * (double)z / rg.fx, ((double)pty - rg.cy) * (double)z / rg.fy, (double)z};
         ok = true;
       }
     } else if (status[i] == 1) {
       float src[2] = {p1[2 * i], p1[2 * i + 1]}, u1[2];
-      undistort_point(src, p.cam.K1, p.cam.D1, p.cam.R1, p.cam.P1, u1);
+      undistort_point(src, rig_arr(rg.K1).v, rig_arr(rg.D1).v, rig_arr(rg.R1).v, rig_arr(rg.P1).v, u1);
       float u0x = (float)lm.p2u[0], u0y = (float)lm.p2u[1];
-      V3 pc = triangulate_dlt((double)u0x, (double)u0y, (double)u1[0], (double)u1[1], p.cam.P0, p.cam.P1);
+      V3 pc = triangulate_dlt((double)u0x, (double)u0y, (double)u1[0], (double)u1[1], rig_arr(rg.P0).v, rig_arr(rg.P1).v);
       if (!(pc.z < 0 || pc.z > range)) {
         meas = pc;
         ok = true;
@@ -2485,19 +2497,19 @@ __device__ __forceinline__ void k_depth_innovate_body(const Pipe& p) {
   if (valid) {
     const SE3d T = load_pose7(st.T_c_w[cur]);
     const SE3d Tinv = se3_inverse(T);
-    const float iir = p.cam.iir_ratio;
+    const float iir = rg.iir_ratio;
     const bool tm = p.tri_mask[(size_t)s * NMAX + i] != 0;
     if (!ok) {
       double depth = (double)rnd[frank];
       if (depth_cam) {  // pixel2camera(lm_2d_plane, ..., d_rand): the double plane position (camera_frame.cpp:200-207)
-        meas = V3{(lm.p2d[0] - p.cam.cx) * depth / p.cam.fx, (lm.p2d[1] - p.cam.cy) * depth / p.cam.fy, depth};
+        meas = V3{(lm.p2d[0] - rg.cx) * depth / rg.fx, (lm.p2d[1] - rg.cy) * depth / rg.fy, depth};
       } else {
         float u0x = (float)lm.p2u[0], u0y = (float)lm.p2u[1];
-        meas = V3{((double)u0x - p.cam.cx) * depth / p.cam.fx, ((double)u0y - p.cam.cy) * depth / p.cam.fy, depth};
+        meas = V3{((double)u0x - rg.cx) * depth / rg.fx, ((double)u0y - rg.cy) * depth / rg.fy, depth};
       }
     }
     if (!ok && !tm) {
-      if (!depth_cam && !lm.has3d && p.cam.enable_dummy) {  // camera_frame.cpp:288-301: stereo types only
+      if (!depth_cam && !lm.has3d && rg.enable_dummy) {  // camera_frame.cpp:288-301: stereo types only
         V3 pw = se3_act(Tinv, meas);
         lm.p3c[0] = meas.x; lm.p3c[1] = meas.y; lm.p3c[2] = meas.z;
         lm.p3w[0] = pw.x; lm.p3w[1] = pw.y; lm.p3w[2] = pw.z;
@@ -2682,6 +2694,11 @@ __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
       }
       st.kf_dq[0] = 1.0, st.kf_dq[1] = st.kf_dq[2] = st.kf_dq[3] = 0.0;
       st.kf_dt = 0;
+      {  // the rig the keyframe was made with (the local map's optimisation projects with it)
+        CRig& rg = rig_of(p, s);
+        kf.rig_K[0] = rg.fx, kf.rig_K[1] = rg.fy, kf.rig_K[2] = rg.cx, kf.rig_K[3] = rg.cy;
+        for (int j = 0; j < 7; j++) kf.rig_T_c_i[j] = rg.T_c_i[j];
+      }
       kf.valid = KFQ_KEYFRAME;
       p.kfq_kf[s] = s_tail + 1u;
     }
@@ -2807,6 +2824,13 @@ __global__ __launch_bounds__(256) void k_kfq_drop(Pipe p) {
 // ------------------------------------------------------------------------------------------------ launchers
 void launch_stream_reset(hipStream_t st, const Pipe& p, const ResetList& list, long long* err_word) {
   if (list.n > 0) hipLaunchKernelGGL(k_stream_reset, dim3(list.n), dim3(256), 0, st, p, list, err_word);
+}
+// flvis_reset_streams_rigs: the new rig travels as the kernel's argument (no host buffer has to outlive the call)
+__global__ void k_set_rig(RigParams* rig, int ls, RigParams r) {
+  if (threadIdx.x == 0) rig[ls] = r;
+}
+void launch_set_rig(hipStream_t st, const Pipe& p, int ls, const RigParams& r) {
+  hipLaunchKernelGGL(k_set_rig, dim3(1), dim3(64), 0, st, const_cast<RigParams*>(p.rig), ls, r);
 }
 void launch_kfq_drop(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_kfq_drop, dim3(p.S), dim3(256), 0, st, p);

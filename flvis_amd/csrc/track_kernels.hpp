@@ -8,7 +8,8 @@ constexpr int NEW_MAX = 1024;  // capacity of FeatureDEM's output per stream and
 
 struct Pipe {
   int S;
-  CamParams cam;
+  CamParams cam;            // batch-wide
+  const RigParams* rig;     // [S] each stream's calibration (rig_of)
   StreamState* st;          // [S]
   Landmark* lm;             // [2][S][NMAX]
   MotionState* vi;          // [S][VI_QUEUE]
@@ -101,6 +102,11 @@ struct Pipe {
   KJoin kj;                 // joins folded into THIS launch (set by the host in front of it, cleared behind it)
 };
 
+// The rig of stream s, read through the constant address space: with a workgroup-uniform s the fields are scalar loads, as they were
+// when the one calibration of the tracker was a kernel argument (a thread-per-stream kernel reads them per lane).  The array is only
+// written between kernels (tracker creation, k_set_rig).
+__device__ inline CRig& rig_of(const Pipe& p, int s) { return ((CRig*)p.rig)[s]; }
+
 // KFMSG_CMD_RESET_LM as vo_localmap.cpp:87-98 applies it (optimizer_state = UN_INITIALIZED, bag->reset(), kfs.clear(), optimizer.clear(),
 // edges.clear()): the stream's window back to the state of a new tracker, the published correction withdrawn.  All threads of one
 // workgroup, by the owner of the stream's window (k_ba_worker) or where no local map runs (k_kfq_drop).
@@ -157,7 +163,9 @@ struct ResetList {
 };
 // err_word (host-mapped): a command that met a full queue stores the stream's lane-local index + 1 there (flvis_hip_synchronize reports it)
 void launch_stream_reset(hipStream_t st, const Pipe& p, const ResetList& list, long long* err_word);
-void launch_kfq_drop(hipStream_t st, const Pipe& p);  // the queues emptied without a local map, a pending reset command applied
+void launch_kfq_drop(hipStream_t st, const Pipe& p);
+// flvis_reset_streams_rigs: stream ls (lane-local) of the lane takes the rig r -- in stream order, ahead of its k_stream_reset
+void launch_set_rig(hipStream_t st, const Pipe& p, int ls, const RigParams& r);  // the queues emptied without a local map, a pending reset command applied
 // local map
 constexpr int BA_PLAN_SLOTS = 8;  // (= Pipeline::NBA: one list per local-map HIP stream, launches on one stream do not overlap)
 void launch_ba_worker(hipStream_t st, const Pipe& p, int plan_slot, unsigned launch_tag);

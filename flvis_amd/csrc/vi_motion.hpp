@@ -7,6 +7,12 @@
 
 namespace flvis {
 
+// the part of a rig the sample-by-sample integration reads (vifusion_para1, the Madgwick gain): taken into a register once per stream
+// ahead of the sample loop (the functions below take it or the stream's whole rig, CRig)
+struct ViGain {
+  double vi_para[1];
+};
+
 struct ViRing {
   MotionState* base;  // [VI_QUEUE] of this stream
   StreamState* st;
@@ -74,7 +80,8 @@ FD void madgwick_feedback(Q4 q_prev, V3 acc, double acc_norm, double gain, Q4& q
 
 // VIMOTION::viIMUPropagation (vi_motion.cpp:78-100) on values: the state after one sample from the state before it, plus the gyro
 // rotation preintegration since the last keyframe (an addition, see KeyFrameDev::imu_dq)
-__device__ inline void vi_propagate(const CamParams& cam, const MotionState& s_prev, double t, V3 acc_raw, V3 gyro_raw, V3 acc_bias,
+template <class Rig>
+__device__ inline void vi_propagate(const Rig& cam, const MotionState& s_prev, double t, V3 acc_raw, V3 gyro_raw, V3 acc_bias,
                                     V3 gyro_bias, MotionState& s_new, Q4& kf_dq, double& kf_dt, V3& kf_dp, V3& kf_dv) {
   const double g = 9.81;
   const V3 acc = acc_raw - acc_bias, gyro = gyro_raw - gyro_bias;
@@ -113,7 +120,8 @@ FD void imu_row_store(double* row, double t, Q4 q, V3 p, V3 v) {
 // F2FTracking::imu_feed for one sample (f2f_tracking.cpp:46-57); `row` receives the outputs of the call: during the attitude
 // initialisation viIMUinitialization returns the identity / zeros (vi_motion.cpp:39-40) except for the sample that sets the first
 // attitude (:60), afterwards viIMUPropagation returns the new state (:206-208)
-__device__ inline void vi_imu_feed(const CamParams& cam, StreamState& st, const ViRing& ring, double t, V3 acc_raw,
+template <class Rig>
+__device__ inline void vi_imu_feed(const Rig& cam, StreamState& st, const ViRing& ring, double t, V3 acc_raw,
                                    V3 gyro_raw, double* row) {
   const double g = 9.81;
   V3 acc = acc_raw - ld3(st.acc_bias), gyro = gyro_raw - ld3(st.gyro_bias);
@@ -193,17 +201,19 @@ __device__ inline void vi_vision_trigger(const ViRing& ring, Q4& init_q) {
   init_q = q;
 }
 
-__device__ inline bool vi_get_corr_frame_state(const CamParams& cam, const ViRing& ring, double time, SE3d& T_c_w) {
+template <class Rig>
+__device__ inline bool vi_get_corr_frame_state(const Rig& cam, const ViRing& ring, double time, SE3d& T_c_w) {
   int idx;
   if (!vi_find_state_idx(ring, time, idx)) return false;
   const MotionState& m = ring.at(idx);
   SE3d T_w_i = se3_from_quat(ms_q(m), ld3(m.pos));
-  T_c_w = se3_inverse(se3_mul(T_w_i, load_pose7(cam.T_i_c)));
+  T_c_w = se3_inverse(se3_mul(T_w_i, load_pose7(rig_arr(cam.T_i_c).v)));
   return true;
 }
 
-__device__ inline void vi_vision_rp_compensation(const CamParams& cam, const ViRing& ring, double time, SE3d& T_c_w) {
-  SE3d T_w_i_before = se3_mul(se3_inverse(T_c_w), load_pose7(cam.T_c_i));
+template <class Rig>
+__device__ inline void vi_vision_rp_compensation(const Rig& cam, const ViRing& ring, double time, SE3d& T_c_w) {
+  SE3d T_w_i_before = se3_mul(se3_inverse(T_c_w), load_pose7(rig_arr(cam.T_c_i).v));
   V3 rpy_before = Q2rpy(T_w_i_before.q);
   int idx;
   if (vi_find_state_idx(ring, time, idx)) {
@@ -212,11 +222,12 @@ __device__ inline void vi_vision_rp_compensation(const CamParams& cam, const ViR
     double p2 = cam.vi_para[1];
     V3 after = rpy_before * (1 - p2) + rpy_vimotion * p2;
     SE3d T_w_i_after{q_normalized(rpy2Q(after)), T_w_i_before.t};
-    T_c_w = se3_inverse(se3_mul(T_w_i_after, load_pose7(cam.T_i_c)));
+    T_c_w = se3_inverse(se3_mul(T_w_i_after, load_pose7(rig_arr(cam.T_i_c).v)));
   }
 }
 
-__device__ inline void vi_correction_from_vision(const CamParams& cam, StreamState& st, const ViRing& ring, double t_curr,
+template <class Rig>
+__device__ inline void vi_correction_from_vision(const Rig& cam, StreamState& st, const ViRing& ring, double t_curr,
                                                  const SE3d& Tcw_curr, double t_last, const SE3d& Tcw_last) {
   const double ba_sat = 0.5, bw_sat = 0.1;  // vifusion_para5/6 never reach VIMOTION (quirk A19)
   int idx_curr, idx_last;
@@ -224,7 +235,7 @@ __device__ inline void vi_correction_from_vision(const CamParams& cam, StreamSta
   if (idx_last == idx_curr) return;
   double dt = t_curr - t_last;
   int idx_mid = idx_last + (int)floor((double)((idx_curr - idx_last) / 2));
-  SE3d T_c_i = load_pose7(cam.T_c_i);
+  SE3d T_c_i = load_pose7(rig_arr(cam.T_c_i).v);
   SE3d T_w_iA = se3_mul(se3_inverse(Tcw_last), T_c_i);
   SE3d T_w_iB = se3_mul(se3_inverse(Tcw_curr), T_c_i);
   SE3d T_w_ia = se3_from_quat(ms_q(ring.at(idx_last)), ld3(ring.at(idx_last).pos));

@@ -451,3 +451,114 @@ class Renderer:
         i0 = self.render(torch.from_numpy(np.stack(R0)).to(self.dev), torch.from_numpy(np.stack(c0)).to(self.dev), seed=2 * frame_idx, cam=0)
         i1 = self.render(torch.from_numpy(np.stack(R1)).to(self.dev), torch.from_numpy(np.stack(c1)).to(self.dev), seed=2 * frame_idx + 1, cam=1)
         return i0, i1
+
+
+# ---- rig variants: the same camera model with another unit's calibration (a batch of per-stream rigs, flvis_tracker_create_rigs)
+RIG_KINDS = ("d435i_stereo", "euroc_like", "d435i_depth", "kitti_like")
+
+
+def _g(v):
+    return "%.17g" % float(v)
+
+
+def _vec(vals):
+    return "[" + ", ".join(_g(v) for v in vals) + "]"
+
+
+def _mat44(m):
+    return "[" + ",\n ".join(", ".join(_g(v) for v in row) for row in np.asarray(m, np.float64)) + "]"
+
+
+def _small_rotation(a):
+    """rotation by the small angles a = (ax, ay, az) rad about x, then y, then z"""
+    cx, sx, cy, sy, cz, sz = math.cos(a[0]), math.sin(a[0]), math.cos(a[1]), math.sin(a[1]), math.cos(a[2]), math.sin(a[2])
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def _replace_key(yaml, key, value, lines=1):
+    """yaml with the entry `key:` (its line and the `lines - 1` lines after it) replaced by `key: value`"""
+    out, skip = [], 0
+    for ln in yaml.split("\n"):
+        if skip:
+            skip -= 1
+            continue
+        if ln.startswith(key + ":"):
+            out.append(key + ":" + ("" if value.startswith("\n") else " ") + value)
+            skip = lines - 1
+            continue
+        out.append(ln)
+    return "\n".join(out)
+
+
+def rig_variant(kind, k):
+    """Variant k of a stock rig (kind in RIG_KINDS; k = 0: the stock calibration): another unit of the same camera model.
+    Returns (Rig, yaml): the Rig to render with and the yaml text that describes exactly that rig -- fx / fy within a few percent,
+    cx / cy shifted by a few pixels, another stereo baseline and a small extra IMU-camera rotation; the EuRoC-like rig also gets other
+    distortion coefficients, the depth rig another depth_factor (Rig.depth_factor: pass it to Renderer.depth_frame).  The KITTI-like
+    yaml has no IMU and no T_imu_cam0: its variants keep the stock camera-body rotation.  Only per-stream fields change: every variant
+    of one kind can share a batch with the others."""
+    if kind not in RIG_KINDS:
+        raise ValueError("rig_variant: unknown kind %r" % (kind,))
+    rng = np.random.default_rng(0x516 + 7919 * int(k))
+    z = int(k) == 0
+    sfx, sfy = (1.0, 1.0) if z else 1.0 + rng.uniform(-0.04, 0.04, 2)
+    dcx, dcy = (0.0, 0.0) if z else rng.uniform(-8.0, 8.0, 2)
+    sb = 1.0 if z else rng.uniform(0.8, 1.25)
+    Rd = np.eye(3) if z else _small_rotation(rng.uniform(-0.02, 0.02, 3))
+    sd = 1.0 if z else rng.uniform(0.9, 1.1)
+    sdf = 1.0 if z else rng.uniform(0.8, 1.25)
+
+    def scaleK(K):
+        return (K[0] * sfx, K[1] * sfy, K[2] + dcx, K[3] + dcy)
+
+    if kind in ("d435i_stereo", "d435i_depth"):
+        K = scaleK((FX, FY, CX, CY))
+        T_i_c = np.eye(4)
+        T_i_c[:3, :3] = R_I_C @ Rd
+        T01 = np.eye(4)
+        T01[0, 3] = BASELINE * sb
+        yaml = D435I_STEREO_YAML if kind == "d435i_stereo" else D435I_DEPTH_YAML
+        yaml = _replace_key(yaml, "cam0_intrinsics", _vec(K))
+        yaml = _replace_key(yaml, "T_imu_cam0", "\n" + _mat44(T_i_c), lines=5)
+        rig = Rig(W, H, K, (0.0, 0.0, 0.0, 0.0), K, (0.0, 0.0, 0.0, 0.0), T_i_c, T01)
+        if kind == "d435i_stereo":
+            yaml = _replace_key(yaml, "cam1_intrinsics", _vec(K))
+            yaml = _replace_key(yaml, "T_cam0_cam1", "\n" + _mat44(T01), lines=5)
+        else:
+            rig.depth_factor = 1000.0 * sdf
+            yaml = _replace_key(yaml, "depth_factor", _g(rig.depth_factor))
+        return rig, yaml
+    if kind == "euroc_like":
+        K0, K1 = scaleK(_EUROC_K0), scaleK(_EUROC_K1)
+        D0 = (_EUROC_D0[0] * sd, _EUROC_D0[1] * sd, _EUROC_D0[2], _EUROC_D0[3])
+        D1 = (_EUROC_D1[0] * sd, _EUROC_D1[1] * sd, _EUROC_D1[2], _EUROC_D1[3])
+        T_b_c0 = _EUROC_T_B_C0.copy()
+        T_b_c0[:3, :3] = T_b_c0[:3, :3] @ Rd
+        T01 = np.linalg.inv(_EUROC_T_B_C0) @ _EUROC_T_B_C1
+        T01[:3, 3] *= sb
+        T_b_c1 = T_b_c0 @ T01
+        yaml = _replace_key(EUROC_LIKE_YAML, "cam0_intrinsics", _vec(K0))
+        yaml = _replace_key(yaml, "cam1_intrinsics", _vec(K1))
+        yaml = _replace_key(yaml, "cam0_distortion_coeffs", _vec(D0))
+        yaml = _replace_key(yaml, "cam1_distortion_coeffs", _vec(D1))
+        yaml = _replace_key(yaml, "T_mavimu_cam0", "\n" + _mat44(T_b_c0), lines=5)
+        yaml = _replace_key(yaml, "T_mavimu_cam1", "\n" + _mat44(T_b_c1), lines=5)
+        # the renderer's extrinsics from the same matrices the yaml holds, composed as the loader composes them
+        return Rig(752, 480, K0, D0, K1, D1, _EUROC_T_IMU_MAVIMU @ T_b_c0, np.linalg.inv(T_b_c0) @ T_b_c1), yaml
+    # kitti_like: P0 = K [I | 0], P1 = K [I | -fx b]
+    K = scaleK((KITTI_FX, KITTI_FX, KITTI_CX, KITTI_CY))
+    b = KITTI_LIKE_BASELINE * sb
+    P0 = [[K[0], 0.0, K[2], 0.0], [0.0, K[1], K[3], 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 0.0]]
+    P1 = [[K[0], 0.0, K[2], -K[0] * b], [0.0, K[1], K[3], 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 0.0]]
+    yaml = _replace_key(KITTI_LIKE_YAML, "cam0_intrinsics", _vec(K))
+    yaml = _replace_key(yaml, "cam1_intrinsics", _vec(K))
+    yaml = _replace_key(yaml, "cam0_projection_matrix", "\n" + _mat44(P0), lines=5)
+    yaml = _replace_key(yaml, "cam1_projection_matrix", "\n" + _mat44(P1), lines=5)
+    T_i_c = np.eye(4)
+    T_i_c[:3, :3] = R_I_C
+    T01 = np.eye(4)
+    T01[0, 3] = -P1[0][3] / K[0]
+    return Rig(KITTI_W, KITTI_H, K, (0.0, 0.0, 0.0, 0.0), K, (0.0, 0.0, 0.0, 0.0), T_i_c, T01), yaml

@@ -288,6 +288,16 @@ int flvis_hip_stereo_depth(flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* 
 /* Creates the batched tracker (and local map) for n_streams independent streams inside `ctx`.  seed_base + stream is the
  * RANSAC seed of each stream.  traj_capacity > 0 keeps a device-side trajectory of that many frames per stream. */
 int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, uint64_t seed_base, int traj_capacity);
+/* The same with one finalized config per stream (cfgs[0 .. n_streams)): a batch of cameras that are calibrated each on its own.
+ * Stream s behaves bit for bit as stream s of flvis_tracker_create(ctx, &cfgs[s], n_streams, seed_base, traj_capacity).
+ * Per stream: the intrinsics and distortion of both cameras, R0 / R1 / P0 / P1, T_imu_cam0, T_cam0_cam1, depth_factor, dr_para and
+ * vifusion_para.  Batch-wide -- every config must match cfgs[0] exactly, as they size buffers and pick code paths: type_of_vi (and so
+ * cam_type, imu_type), image_width, image_height, feature_para[0..5], window_size, skip_first_n_imgs, need_equal_hist.  A config that
+ * differs in one of them returns FLVIS_ERR_CONFIG (flvis_last_error names the field and the stream) and creates nothing: a tracker the
+ * context already holds is kept.  Every check of flvis_tracker_create applies to each config.  The loop closer keeps its single config. */
+int flvis_tracker_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_streams, uint64_t seed_base, int traj_capacity);
+/* The config stream `stream` runs on: the one it was created or last reset with (flvis_reset_streams_rigs). */
+int flvis_get_stream_cfg(flvis_ctx* ctx, int stream, flvis_cfg* out);
 
 /* Number of lanes (sub-batches with their own HIP streams and device state) the tracker splits its streams into.  One by
  * default; the environment variable FLVIS_LANES (1..16) is a tuning knob (more lanes measured slower on MI355X, DESIGN.md
@@ -473,6 +483,13 @@ int flvis_write_imu_trajectory_run(const double* h_rows11, int n, const char* pa
  * next one.  The reset takes a keyframe-queue entry, which the tracker's back-pressure keeps free; should a full queue be met all the
  * same, the next flvis_hip_synchronize returns FLVIS_ERR_CAPACITY. */
 int flvis_reset_streams(flvis_ctx* ctx, int n, const int* streams);
+/* flvis_reset_streams with a new rig: stream streams[i] starts over on cfgs[i] (a duplicate: its last entry) and then equals stream
+ * streams[i] of a tracker just made by flvis_tracker_create_rigs with that config in its place.  The reset's ordering holds for the rig
+ * too: no frame or optimisation of the old sequence -- one already running, or a lane ahead under flvis_set_input_hold -- publishes
+ * anything computed with the new rig, and nothing of the new sequence uses the old one.  Every config is checked first, as
+ * flvis_tracker_create_rigs checks it against the tracker's batch-wide fields: one that fails returns FLVIS_ERR_CONFIG (or
+ * FLVIS_ERR_CAPACITY) and nothing changes. */
+int flvis_reset_streams_rigs(flvis_ctx* ctx, int n, const int* streams, const flvis_cfg* cfgs);
 /* KFMSG_CMD_RESET_LM for the named streams' local maps alone (vo_localmap.cpp:87-98): keyframes queued before the command are
  * processed first, then the window, the graph and the keyframe deque are emptied and the optimiser returns to UN_INITIALIZED; the
  * published correction is withdrawn and the stream's flvis_get_local_map_counts entries start from 0.  The tracker is not touched.
