@@ -174,6 +174,37 @@ struct BAShared {
 extern __shared__ __attribute__((aligned(16))) unsigned char ba_smem[];
 constexpr size_t BA_SH_BYTES = ((sizeof(BAShared) + 15) / 16) * 16;
 FD BAShared& ba_sh() { return *reinterpret_cast<BAShared*>(ba_smem); }
+// (ba_update_dev stages the bag's landmark ids at the start of the dynamic LDS -- and reads up to seven entries past them --: any admitted budget holds them)
+static_assert(BA_SH_BYTES + 8 * (BA_LMAX + 8) <= 64 * 1024, "the bookkeeping's id list must fit the smallest LDS budget");
+
+// Layout of a window's dynamic LDS, in doubles behind the BAShared header (ba_build_structure; the host's budget check, ba_lds_admits, uses the
+// same arithmetic): Hs[NR + 1][LD] and Linv[P][36] -- the linearisation's per-wave partials (BA_NW x P x 27) lie over them --, the IMU
+// blocks (120 doubles per window slot, only when the factor is on), then the chunk buffers of the Schur phase.
+struct BALayout {
+  int NR, LD, off_linv, off_imu, off_stage;
+};
+__host__ __device__ inline BALayout ba_layout(int P, int W, bool imu) {
+  BALayout g;
+  // leading dimension of the reduced system: rows 16-byte aligned (128-bit LDS reads of a row's 6-column blocks) and LD / 2 odd
+  // (the rows a wave's lanes read together fall into different bank groups)
+  g.NR = 6 * P;
+  g.LD = (P & 1) ? g.NR + 4 : g.NR + 2;
+  g.off_linv = (g.NR + 1) * g.LD;  // (row NR: the right-hand side rides through the factorisation, ba_chol_factor_wg)
+  // the per-wave partials of the linearisation lie over Hs / Linv: nothing behind them may start inside
+  const int wacc_end = BA_NW * 27 * P;
+  g.off_imu = g.off_linv + P * 36 > wacc_end ? g.off_linv + P * 36 : wacc_end;
+  g.off_stage = g.off_imu + (imu ? 120 * W : 0);
+  return g;
+}
+// doubles left for the chunk buffers by a budget of lds_budget bytes (an even count)
+__host__ __device__ inline int ba_stage_avail(int lds_budget, int off_stage) { return ((int)((lds_budget - BA_SH_BYTES) / 8) - off_stage) & ~1; }
+// A window whose items do not fit one resident chunk streams through two buffers of bufd doubles: CL landmarks, CI items per chunk
+__host__ __device__ inline void ba_stream_caps(int avail, int& CL, int& CI, int& bufd) {
+  bufd = (avail / 2) & ~1;
+  CL = 256;
+  while (CL > 32 && CL * 10 > bufd / 4) CL >>= 1;  // (the landmark arrays take at most a quarter of a buffer)
+  CI = ((bufd - 10 * CL) / 6) & ~1;
+}
 FD double* ba_dyn() { return reinterpret_cast<double*>(ba_smem + BA_SH_BYTES); }
 // IMU edge k's blocks: which = 0 Ja^T W Ja, 1 Jb^T W Jb, 2 Ja^T W Jb (36 doubles each), 3 / 4 the gradients Ja^T W r / Jb^T W r (6 each)
 // Chunk buffer `buf` of the Schur phase.  Per item (an observation by a free pose) a record of three 16-byte pairs [3][CI]:
@@ -504,16 +535,13 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
       }
     sh.fixed_slot = nfs == 1 ? fs : -1;
     sh.fused = nfs <= 1 ? 1 : 0;  // (and one chunk, not the matrix-core variant: decided with the chunk table below)
-    // leading dimension of the reduced system: rows 16-byte aligned (128-bit LDS reads of a row's 6-column blocks) and LD / 2 odd
-    // (the rows a wave's lanes read together fall into different bank groups)
-    const int NR = 6 * P, LD = (P & 1) ? NR + 4 : NR + 2;
+    const BALayout g = ba_layout(P, W, sh.n_imu > 0);
+    const int NR = g.NR;
     sh.NR = NR;
-    sh.LD = LD;
-    sh.off_linv = (NR + 1) * LD;  // (row NR: the right-hand side rides through the factorisation, ba_chol_factor_wg)
-    // the per-wave partials of the linearisation (BA_NW x P x 27) lie over Hs / Linv: nothing behind them may start inside
-    const int wacc_end = BA_NW * 27 * P;
-    sh.off_imu = (NR + 1) * LD + P * 36 > wacc_end ? (NR + 1) * LD + P * 36 : wacc_end;
-    sh.off_stage = sh.off_imu + (sh.n_imu > 0 ? 120 * W : 0);
+    sh.LD = g.LD;
+    sh.off_linv = g.off_linv;
+    sh.off_imu = g.off_imu;
+    sh.off_stage = g.off_stage;
     // pair groups of the Schur accumulate: the P diagonal pairs first, padded to whole waves -- a wave that held both kinds of pairs
     // would run the two product bodies one after the other --, then the P (P - 1) / 2 pairs i1 < i2
     int slices = 64, npairs = 0;
@@ -529,7 +557,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     sh.max_slices = slices;
     // MFMA variant: the chunk is the DENSE (NR + 1 rows padded to 16) x (3 columns per landmark) slice of Z' = [Z; c^T]
     const int NRp = (NR + 1 + 15) & ~15;
-    const int avail_m = ((int)((sh.lds_budget - BA_SH_BYTES) / 8) - sh.off_stage) & ~1;
+    const int avail_m = ba_stage_avail(sh.lds_budget, sh.off_stage);
     int CLm = (avail_m / (3 * NRp)) & ~3;  // 3 * CLm columns, a multiple of the MFMA's K = 4
     if (CLm > 252) CLm = 252;
     sh.NRp = NRp;
@@ -603,7 +631,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     // Chunk buffers of the Schur phase (ba_schur_buf): 6 doubles per item, 10 per landmark.  A window whose items all fit (~1900 at
     // 159 KB, 7 free poses and 550 landmarks: the D435 windows) is ONE chunk in one buffer -- its records stay resident, no barrier
     // inside the phase; larger windows stream through two buffers.
-    const int avail = ((int)((sh.lds_budget - BA_SH_BYTES) / 8) - sh.off_stage) & ~1;
+    const int avail = ba_stage_avail(sh.lds_budget, sh.off_stage);
     const int nit = lbase[L];
     int CI, CL, bufd;
     if (6 * ((nit + 1) & ~1) + 10 * ((L + 1) & ~1) <= avail) {
@@ -611,10 +639,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
       CL = L > 0 ? ((L + 1) & ~1) : 2;
       bufd = avail;
     } else {
-      bufd = (avail / 2) & ~1;
-      CL = 256;
-      while (CL > 32 && CL * 10 > bufd / 4) CL >>= 1;  // (the landmark arrays take at most a quarter of a buffer)
-      CI = ((bufd - 10 * CL) / 6) & ~1;
+      ba_stream_caps(avail, CL, CI, bufd);
     }
     sh.CL = CL;
     sh.CI = CI;
@@ -636,7 +661,9 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     }
     sh.chunk_l0[c] = L;
     sh.chunk_i0[c] = lbase[L];
-    sh.nchunk = c;
+    // landmarks left over: the table is full, and a last chunk past CI / CL would run off its buffer.  nchunk = -1: the window is not
+    // optimised (ba_optimize), ba_solve_dev marks and reports it.  (Unreachable at the budgets flvis_tracker_create admits: ba_lds_admits)
+    sh.nchunk = l0 < L ? -1 : c;
     if (c != 1 || sh.use_mfma) sh.fused = 0;
   }
   __syncthreads();
@@ -2249,7 +2276,7 @@ __device__ __noinline__ void ba_optimize(const WindowDev& w, int iterations) {
   BAPROF(0);
   ba_build_structure(w);
   BAPROF(1);
-  if (sh.cnt == 0) return;
+  if (sh.cnt == 0 || sh.nchunk < 0) return;
   double lambda = -1, ni = 2;
   double currentChi = 0;
   bool have_lin = false;  // resident records: the accepted trial's evaluation left the linearisation of the state it produced behind
@@ -2376,6 +2403,34 @@ __device__ __noinline__ void ba_optimize(const WindowDev& w, int iterations) {
   }
 }
 
+// a window that exceeded a capacity (BA_OVF_* bits): the host-mapped word flvis_hip_synchronize reads (the last report wins)
+FD void ba_report_overflow(const Pipe& p, int s, int bits) {
+  if (p.ba_ovf_word)
+    __hip_atomic_store(p.ba_ovf_word, ((long long)bits << 32) | (long long)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// behind an optimize() call (after its barrier): the path counters, and a window whose chunk table overflowed is marked and reported.
+// True: the optimisation stops here (no outputs; the window takes no further keyframes until the stream's local map is reset)
+FD bool ba_pass_done(const Pipe& p, int s) {
+  BAShared& sh = ba_sh();
+  const int nchunk = sh.nchunk;
+  if (threadIdx.x == 0) {
+#ifndef FLVIS_BA_PROF
+    if (p.counters) {  // (debug counters 24 / 25: optimize() calls that streamed their records in chunks, the largest chunk count)
+      if (!sh.fused) atomicAdd((unsigned long long*)&p.counters[24], 1ull);
+      if (nchunk > 0) atomicMax((unsigned long long*)&p.counters[25], (unsigned long long)nchunk);
+    }
+#endif
+    if (nchunk < 0) {
+      WindowDev& w = p.win[s];
+      w.overflow |= BA_OVF_CHUNK;
+      w.solve = 0;
+      ba_report_overflow(p, s, w.overflow);
+    }
+  }
+  return nchunk < 0;
+}
+
 #include "ba_update.hpp"
 
 // the OPTIMIZING block for the window of stream s (w.solve set by ba_update_dev); frame_id = the keyframe that triggered it
@@ -2452,6 +2507,7 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
   __syncthreads();
   ba_optimize(w, FLVIS_BA_IT1);
   __syncthreads();
+  if (ba_pass_done(p, s)) return;
   BAPROF(0);
   // chi2 > 3 cull (vo_localmap.cpp:301-317): reverse edge order => outlier ids by descending edge id
   CorrectionDev& out = p.corr[s];
@@ -2489,6 +2545,7 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
   BAPROF(11);
   ba_optimize(w, FLVIS_BA_IT2);
   __syncthreads();
+  if (ba_pass_done(p, s)) return;
   BAPROF(0);
   const BAScratch sc = sh.sc;
   const int Lc = sc.Lc;
@@ -2797,6 +2854,38 @@ void launch_ba_worker(hipStream_t st, const Pipe& p, int plan_slot, unsigned lau
   hipLaunchKernelGGL(k_ba_worker, dim3(p.S), dim3(BA_T), p.ba_lds_bytes, st, p, plan_slot, launch_tag);
 }
 int ba_lds_budget_max() { return BA_LDS_BUDGET; }
+
+// The most chunks the greedy loop of ba_build_structure can make for a window of P free poses with `avail` doubles of chunk buffers, over
+// any window of at most BA_LMAX landmarks and BA_EMAX observations (items, the observations by free poses, are at most as many; one
+// landmark has at most P).  Every chunk but the last ends either at CL landmarks, or because the next landmark's items would pass CI: it
+// then holds at least CI - P + 1 items on at least ceil((CI - P + 1) / P) landmarks.  Taking as many chunks of the second kind as the
+// landmarks and the observations allow (they take no more landmarks than the first) bounds the count.  A window that fits one resident
+// chunk is one chunk.  -1: the buffers cannot hold the item numbering (BA_LMAX + 1 ints) or one landmark's items.
+static int ba_chunks_worst(int avail, int P) {
+  if (2 * avail < BA_LMAX + 1) return -1;
+  int CL, CI, bufd;
+  ba_stream_caps(avail, CL, CI, bufd);
+  if (CI < P) return -1;
+  const int items = CI - P + 1, lms = (items + P - 1) / P;
+  const int by_items = lms > CL ? 0 : (BA_EMAX / items < BA_LMAX / lms ? BA_EMAX / items : BA_LMAX / lms);
+  return by_items + (BA_LMAX - lms * by_items) / CL + 1;
+}
+// whether a budget of `bytes` holds every window of `window` keyframes: any number of free poses, the IMU factor on or off (it can be
+// switched on at any time), BA_LMAX landmarks, BA_EMAX observations, within BA_MAXCHUNK chunks
+bool ba_lds_admits(int bytes, int window) {
+  if (bytes > BA_LDS_BUDGET) return false;
+  for (int P = 1; P < window && P <= BA_PMAX; P++)
+    for (int imu = 0; imu < 2; imu++) {
+      const int n = ba_chunks_worst(ba_stage_avail(bytes, ba_layout(P, window, imu != 0).off_stage), P);
+      if (n < 0 || n > BA_MAXCHUNK) return false;
+    }
+  return true;
+}
+int ba_lds_min_bytes(int window) {
+  for (int kb = 64; kb * 1024 <= BA_LDS_BUDGET; kb++)
+    if (ba_lds_admits(kb * 1024, window)) return kb * 1024;
+  return BA_LDS_BUDGET + 1;  // (no budget the knob accepts)
+}
 hipError_t ba_kernels_init() {
   return hipFuncSetAttribute((const void*)k_ba_worker, hipFuncAttributeMaxDynamicSharedMemorySize, BA_LDS_BUDGET);
 }

@@ -149,14 +149,14 @@ __device__ inline void bag_add_keyframe(WindowDev& w, long long* sid, int* s_cnt
     int nn = nl0 + appended;
     if (nn > BA_LMAX) {
       nn = BA_LMAX;
-      w.overflow = 1;
+      w.overflow |= BA_OVF_LMAX;
     }
     w.n_lm = nn;
     if (slot >= 0) {
       int ne = e0 + n;
       if (ne > BA_EMAX) {
         ne = BA_EMAX;
-        w.overflow = 1;
+        w.overflow |= BA_OVF_EMAX;
       }
       w.n_edge = ne;
       w.edge_next_id += n;
@@ -322,6 +322,7 @@ __device__ __noinline__ void ba_update_dev(const Pipe& p, int s, const KeyFrameD
   __syncthreads();
   if (tid == 0) {
     w.solve = w.overflow ? 0 : 1;
+    if (w.overflow) ba_report_overflow(p, s, w.overflow);  // (the keyframe that set it: the window's later ones return above)
     // kfs.pop_front() happens after the optimisation in the reference; nothing reads kfs in between
     w.kfs_head = (w.kfs_head + 1) % W;
     w.kfs_size--;

@@ -74,6 +74,7 @@ void flvis_pipeline_destroy_internal(flvis_ctx* ctx);  // pipeline.cpp
 void flvis_pipeline_sync_internal(flvis_ctx* ctx);
 long long flvis_pipeline_join_timeout_internal(flvis_ctx* ctx);
 int flvis_pipeline_reset_overflow_internal(flvis_ctx* ctx);
+long long flvis_pipeline_ba_overflow_internal(flvis_ctx* ctx);
 
 void flvis_hip_destroy(flvis_ctx* ctx) {
   if (!ctx) return;
@@ -103,6 +104,15 @@ int flvis_hip_synchronize(flvis_ctx* ctx) {
   if (const int s = flvis_pipeline_reset_overflow_internal(ctx)) {
     char msg[128];
     snprintf(msg, sizeof msg, "flvis_reset_streams / flvis_local_map_reset: the keyframe queue of stream %d was full; its local map was not reset", s - 1);
+    return ctx->fail(FLVIS_ERR_CAPACITY, msg);
+  }
+  // a local-map window that exceeded a capacity: that stream's local map stopped optimising (until flvis_local_map_reset / flvis_reset_streams)
+  if (const long long v = flvis_pipeline_ba_overflow_internal(ctx)) {
+    const int s = (int)(v & 0xffffffffll) - 1, bits = (int)(v >> 32);
+    char msg[256];
+    snprintf(msg, sizeof msg, "local map of stream %d exceeded%s%s%s; it stops optimising until the stream's local map is reset", s,
+             (bits & BA_OVF_LMAX) ? " BA_LMAX (4096 landmarks in the window)" : "", (bits & BA_OVF_EMAX) ? " BA_EMAX (8192 observations in the window)" : "",
+             (bits & BA_OVF_CHUNK) ? " BA_MAXCHUNK (the Schur phase's chunk table)" : "");
     return ctx->fail(FLVIS_ERR_CAPACITY, msg);
   }
   return FLVIS_OK;

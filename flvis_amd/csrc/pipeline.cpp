@@ -375,6 +375,20 @@ extern "C" int flvis_pipeline_reset_overflow_internal(flvis_ctx* ctx) {
   return s;
 }
 
+// a local-map window that exceeded a capacity (word 4 of a lane's host-mapped block): BA_OVF_* bits << 32 | context-wide stream + 1, or 0;
+// cleared when read
+extern "C" long long flvis_pipeline_ba_overflow_internal(flvis_ctx* ctx) {
+  long long v = 0;
+  if (ctx && ctx->pipe)
+    for (Lane* L : ctx->pipe->lanes)
+      if (L->h_progress && L->h_progress[4]) {
+        const long long w = L->h_progress[4];
+        v = (w & ~0xffffffffll) | (long long)(L->s0 + (int)(w & 0xffffffffll));
+        L->h_progress[4] = 0;
+      }
+  return v;
+}
+
 extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
   if (!ctx || !ctx->pipe) return;
   Pipeline* pl = ctx->pipe;
@@ -407,6 +421,18 @@ extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
   for (void* p : pl->allocs) hipFree(p);
   delete pl;
   ctx->pipe = nullptr;
+}
+
+// LDS a local-map workgroup claims (FLVIS_BA_LDS_KB, 64 .. 159; other values are ignored): whatever it leaves of the CU's 160 KB lets LK /
+// corner-response waves run on the same CU, whose SIMDs a latency-bound BA workgroup keeps mostly idle.  A/B knob, see DESIGN.md section 4;
+// a tracker is only created with a budget that holds its window (check_cfg)
+static int ba_lds_bytes_env() {
+  int bytes = ba_lds_budget_max();
+  if (const char* e = getenv("FLVIS_BA_LDS_KB")) {
+    const int kb = atoi(e);
+    if (kb >= 64 && kb * 1024 <= ba_lds_budget_max()) bytes = kb * 1024;
+  }
+  return bytes;
 }
 
 // device state + streams of one lane; false on any allocation failure (the caller destroys the pipeline)
@@ -522,13 +548,7 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   p.kf_check = getenv("FLVIS_KF_CHECK") && atoi(getenv("FLVIS_KF_CHECK")) == 1;
   p.ba_balance = 0;
   if (const char* e = getenv("FLVIS_BA_BALANCE")) p.ba_balance = atoi(e) != 0;
-  // LDS a local-map workgroup claims (FLVIS_BA_LDS_KB, 64 .. 159): whatever it leaves of the CU's 160 KB lets LK / corner-response
-  // waves run on the same CU, whose SIMDs a latency-bound BA workgroup keeps mostly idle
-  p.ba_lds_bytes = ba_lds_budget_max();
-  if (const char* e = getenv("FLVIS_BA_LDS_KB")) {
-    const int kb = atoi(e);
-    if (kb >= 64 && kb * 1024 <= ba_lds_budget_max()) p.ba_lds_bytes = kb * 1024;
-  }  // A/B knob, see DESIGN.md section 4
+  p.ba_lds_bytes = ba_lds_bytes_env();  // (admitted for the config's window by check_cfg)
   DA(ba_scratch, double, (size_t)S * p.ba_scratch_stride);
   // FLVIS_PNP_TAIL=cv (opt-in fidelity mode, round 6): behind k_ransac_pnp the pose of the ITERATIVE flag is replaced by what
   // cv::solvePnP(ITERATIVE, useExtrinsicGuess = false) leaves on the RANSAC's inliers -- a DLT start and CvLevMarq, the very function the
@@ -662,7 +682,9 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
     L->h_progress = (volatile long long*)hp;
     L->d_progress = (long long*)dp;
     for (int k = 0; k < 8; k++) L->h_progress[k] = 0;  // (word 0: frame progress, 1: scratch, 2: a timed-out join's sequence number,
-                                                        // 3: stream + 1 of a reset command that met a full keyframe queue)
+                                                        // 3: stream + 1 of a reset command that met a full keyframe queue,
+                                                        // 4: BA_OVF_* << 32 | stream + 1 of a local-map window that exceeded a capacity)
+    L->pipe.ba_ovf_word = L->d_progress + 4;
   }
   if (own_stream) {
     if (hipStreamCreateWithFlags(&L->st, hipStreamNonBlocking) != hipSuccess) return false;
@@ -701,6 +723,12 @@ static int check_cfg(flvis_ctx* ctx, const flvis_cfg* cfg, const std::string& pr
   if (cfg->need_equal_hist && (w & 15)) return ctx->fail(FLVIS_ERR_CONFIG, pre + "equalizeHist rigs need an image width that is a multiple of 16");
   if (cfg->feature_para[5] > 64.0) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para6 (GFTT minDistance) > 64 is not supported");
   if (cfg->window_size > BA_WMAX) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "window_size exceeds the LDS-resident solver (16)");
+  if (!ba_lds_admits(ba_lds_bytes_env(), cfg->window_size)) {
+    char msg[192];
+    snprintf(msg, sizeof msg, "FLVIS_BA_LDS_KB=%d is below the %d KB the local-map solver needs for window_size %d", ba_lds_bytes_env() / 1024,
+             ba_lds_min_bytes(cfg->window_size) / 1024, cfg->window_size);
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + msg);
+  }
   if (16 * (int)cfg->feature_para[0] > 512) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para1 (landmarks per region) must be <= 32: the pose LM holds 512 edges");
   if ((int)cfg->feature_para[3] * 2 > 4096) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "feature_para4 (gftt_num) must be <= 2048");
   if ((size_t)((w + 31) / 32) * h * 4 > 96 * 1024) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "image too large for the GFTT LDS bitmap");
@@ -2468,7 +2496,7 @@ int flvis_debug_counters(flvis_ctx* ctx, int64_t* h64) {
   for (Lane* L : ctx->pipe->lanes) {
     long long c[64];
     hipMemcpy(c, L->pipe.counters, sizeof(c), hipMemcpyDeviceToHost);
-    for (int i = 0; i < 64; i++) h64[i] += c[i];
+    for (int i = 0; i < 64; i++) h64[i] = i == 25 ? std::max<int64_t>(h64[i], c[i]) : h64[i] + c[i];  // ([25] is a maximum)
   }
   return FLVIS_OK;
 }

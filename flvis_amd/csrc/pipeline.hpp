@@ -22,6 +22,10 @@ constexpr int KFQ = 32;            // per-stream keyframe queue between the trac
 constexpr int BA_WMAX = 16;       // window sizes supported by the LDS-resident solver
 constexpr int BA_LMAX = 4096;     // landmarks in the window
 constexpr int BA_EMAX = 8192;     // observations (edges) in the window
+// WindowDev::overflow: which capacity a window exceeded (published to the host once, flvis_hip_synchronize reports it)
+constexpr int BA_OVF_LMAX = 1;   // more than BA_LMAX landmarks
+constexpr int BA_OVF_EMAX = 2;   // more than BA_EMAX observations
+constexpr int BA_OVF_CHUNK = 4;  // the Schur phase's chunk table (BA_MAXCHUNK entries) could not hold the window
 constexpr int POSE_REC = 1024;    // ring behind F2FTracking::pose_records (the reference keeps < 1000, f2f_tracking.cpp:334)
 
 enum { ST_UNINIT = 0, ST_TRACKING = 1, ST_TRACKFAIL = 2 };
@@ -192,7 +196,7 @@ struct WindowDev {
   // keyframe queue (the `kfs` deque of vo_localmap.cpp:55): ring of the last `window` payloads, storage in Pipe::kfs_ring
   int kfs_head, kfs_size;
   int solve;        // set by the bookkeeping kernel when this keyframe triggers an optimisation
-  int overflow;     // a capacity (BA_LMAX / BA_EMAX) was exceeded; the window stops accepting work
+  int overflow;     // a capacity was exceeded (BA_OVF_* bits); the window stops accepting work until the stream's local map is reset
   long long ba_runs;
   // the rig of the window's keyframes (KeyFrameDev::rig_K / rig_T_c_i of the last one added): what its optimisation projects with
   double K[4], T_c_i[7];

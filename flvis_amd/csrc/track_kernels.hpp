@@ -89,6 +89,7 @@ struct Pipe {
   int kf_check;             // keyframe payloads carry a checksum the local-map worker verifies (FLVIS_KF_CHECK=1: stress test of the hand-over's fences)
   int ba_balance;           // Schur accumulate: lanes per pose pair in proportion to the landmarks the pair shares (1) or 16 each (0)
   long long* counters;      // [8]: frames, keyframes, ba_runs, track_fail frames ...
+  long long* ba_ovf_word;   // host-mapped: a window that exceeds a capacity stores (BA_OVF_* bits) << 32 | (lane-local stream + 1) (k_ba_worker)
   // local-map feedback (F2FTracking::correction_feed, dead in the reference's v2)
   int* rec_id;              // [S][POSE_REC]  ID_POSE::frame_id (an int in the reference)
   double* rec_T;            // [S][POSE_REC][7]
@@ -122,6 +123,10 @@ __device__ inline void window_reset_dev(const Pipe& p, int s) {
 }
 
 int ba_lds_budget_max();
+// whether a dynamic LDS of `bytes` holds k_ba_worker's reduced system, IMU blocks and chunk table for every window of `window` keyframes,
+// and the smallest such budget (a whole number of KB, as FLVIS_BA_LDS_KB sets it)
+bool ba_lds_admits(int bytes, int window);
+int ba_lds_min_bytes(int window);
 void launch_imu_feed(hipStream_t st, const Pipe& p);
 void launch_frame_begin(hipStream_t st, const Pipe& p, const double* d_time);
 // cv::solvePnPRansac on caller arrays (one workgroup per correspondence set): the loop closing's geometric check

@@ -57,7 +57,9 @@ const char* flvis_version(void);
 int flvis_hip_create(int device, void* hip_stream, flvis_ctx** out);
 void flvis_hip_destroy(flvis_ctx* ctx);
 const char* flvis_last_error(const flvis_ctx* ctx);
-/* Blocks until all work queued on the context's stream has finished. */
+/* Blocks until all work queued on the context's stream has finished.  Then reports, once each, what the device flagged since the last
+ * call: a stream join that timed out (FLVIS_ERR_HIP), a reset command that met a full keyframe queue and a local-map window past BA_LMAX /
+ * BA_EMAX (FLVIS_ERR_CAPACITY, see flvis_ba_push_keyframe). */
 int flvis_hip_synchronize(flvis_ctx* ctx);
 /* The hipStream_t the context launches on (for event timing by the caller). */
 void* flvis_hip_stream(flvis_ctx* ctx);
@@ -533,11 +535,16 @@ int flvis_hip_debug_corner_response(flvis_ctx* ctx, const uint8_t* d_img, int w,
  * [first_bits, first_bits + n); *h_mismatches = arguments on which the two differ (0 over the kernel's domain, see eig_walk.hip). */
 int flvis_hip_debug_sqrt_check(flvis_ctx* ctx, uint32_t first_bits, uint32_t n, uint64_t* h_mismatches);
 /* Raw device counter block (64 x int64): [0..7] as above, [8..] per-phase cycle counters of the BA kernel, filled only by
- * builds with -DFLVIS_BA_PROF (tuning aid, not part of the reference interface). */
+ * builds with -DFLVIS_BA_PROF (tuning aid, not part of the reference interface).  In other builds the local-map solver's path:
+ * [24] optimize() calls (two per optimisation: before and after the cull) whose records streamed through the LDS in chunks instead of
+ * staying resident, [25] the largest chunk count of any call (a maximum over the lanes, not a sum); [28] optimisations whose last call
+ * streamed, [29] their duration in 10 ns ticks. */
 int flvis_debug_counters(flvis_ctx* ctx, int64_t* h_counters64);
 
 /* LocalMapNodeletClass::frame_callback for one stream with a caller-supplied KeyFrame (host arrays).  Returns 1 and fills
- * the outputs when an optimisation ran, 0 while the window is still filling. */
+ * the outputs when an optimisation ran, 0 while the window is still filling -- or once the window has exceeded BA_LMAX (4096
+ * landmarks) or BA_EMAX (8192 observations): that stream's local map then stops until it is reset, and the next flvis_hip_synchronize
+ * returns FLVIS_ERR_CAPACITY naming the stream and the limit. */
 int flvis_ba_push_keyframe(flvis_ctx* ctx, int stream, int64_t frame_id, const double* T_c_w7, int lm_count,
                            const int64_t* h_lm_id, const double* h_lm_2d, const double* h_lm_3d, int cap,
                            int64_t* out_frame_id, double* out_T_c_w7, int* out_lm_count, int64_t* out_lm_id,

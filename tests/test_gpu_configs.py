@@ -218,6 +218,7 @@ def _config2_frontend_and_ba(imu_factor, sigma_a=0.0):
     t_prev = -0.05
     n_corr, max_lm = 0, 0
     want_c = None
+    kf_obs = []  # observations of every keyframe pushed: a window's edges before any cull
     for f in range(nframes):
         t = f / synth.FRAME_HZ
         smp = synth.imu_samples(tr, sid, t_prev, t)
@@ -236,6 +237,7 @@ def _config2_frontend_and_ba(imu_factor, sigma_a=0.0):
         if not w["new_keyframe"]:
             continue
         kf = ref.keyframe()
+        kf_obs.append(len(kf["lm_id"]))
         valid, dq, dt = ref.keyframe_imu()
         if imu_factor and valid:
             lmap.next_imu(dq, dt)
@@ -257,6 +259,16 @@ def _config2_frontend_and_ba(imu_factor, sigma_a=0.0):
         assert np.array_equal(got_c["outlier_id"], want_c["outlier_id"]), where
         assert np.allclose(got_c["pose7"], want_c["pose7"], atol=1e-6, rtol=0), (where, got_c["pose7"] - want_c["pose7"])
         assert np.allclose(got_c["lm_3d"], want_c["lm_3d"], atol=1e-6, rtol=0), (where, np.abs(got_c["lm_3d"] - want_c["lm_3d"]).max())
+    # how close the rig's windows come to the solver's capacity: the most observations a window was pushed (BA_EMAX = 8192), the
+    # optimize() calls that streamed their records and the largest chunk count (debug counters 24 / 25); no capacity report
+    dbg = (C.c_int64 * 64)()
+    ctx._check(ctx._lib.flvis_debug_counters(ctx._h, dbg), "debug_counters")
+    ctx.synchronize()
+    W = cfg.window_size
+    win_obs = max([sum(kf_obs[i:i + W]) for i in range(max(1, len(kf_obs) - W + 1))] or [0])
+    print("euroc-like window: at most %d observations in a window, %d of %d optimize() calls streamed, largest chunk count %d" %
+          (win_obs, dbg[24], 2 * int(dbg[2]), dbg[25]))
+    assert win_obs <= 8192 and dbg[25] >= 1
     ctx.close()
     assert n_corr >= 3, n_corr
     assert 250 <= max_lm <= 480, max_lm
