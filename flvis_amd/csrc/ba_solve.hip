@@ -684,10 +684,9 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
   }
 }
 
-// blocked (6x6) left-looking Cholesky of the lower triangle of Hs (leading dimension LD) by ONE wave, then the two
-// triangular solves on sh.x; Linv receives the inverted diagonal blocks.  Returns false on a non-positive pivot.
-FD void ba_chol_subst(bool fwd);
-__device__ FLVIS_BA_PHASE_FN bool ba_chol_solve() {
+// the backward solve on sh.x with the factor in Hs / Linv, by ONE wave: the forward substitution happened inside the factorisation
+// (ba_chol_factor_wg), y is row NR of Hs.
+FD void ba_chol_subst() {
   BAShared& sh = ba_sh();
   double* Hs = ba_dyn();
   double* Linv = Hs + sh.off_linv;
@@ -695,170 +694,8 @@ __device__ FLVIS_BA_PHASE_FN bool ba_chol_solve() {
   const int P = sh.P, LD = sh.LD;
   const int lane = threadIdx.x & 63;
   const int NR = 6 * P;
-  bool okc = true;
-  for (int jb = 0; jb < P; jb++) {
-    const int c0 = 6 * jb;
-    // panel rows (including the diagonal block's rows): subtract the contributions of the finished block columns
-#ifdef FLVIS_BA_SOLVE_MFMA
-    // (build variant, round 5: this update -- panel -= L[rows, 0 : c0] L[c0 : c0 + 6, 0 : c0]^T -- on the matrix cores: 16-row tiles x the 6
-    // columns padded to 16 x c0 / 4 k-steps of v_mfma_f64_16x16x4_f64; north_star names "an MFMA dense solve only for the reduced
-    // camera block", this is the A/B that settles it.  profiles/r05_ba_phases.md)
-    if (jb > 0) {
-      typedef double mf_d4 __attribute__((ext_vector_type(4)));
-      const int ar = lane & 15, ak = lane >> 4, ksteps = (c0 + 3) >> 2;
-      for (int ti = 0; 16 * ti < NR; ti++) {
-        if (16 * ti + 15 < c0) continue;
-        const int row = 16 * ti + ar;
-        mf_d4 acc = {0, 0, 0, 0};
-        for (int ks = 0; ks < ksteps; ks++) {
-          const int k = 4 * ks + ak;
-          const double a = (row < NR && k < c0) ? Hs[row * LD + k] : 0.0;
-          const double b = (ar < 6 && k < c0) ? Hs[(c0 + ar) * LD + k] : 0.0;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int v = 0; v < 4; v++) {  // D[(lane >> 4) + 4 v][lane & 15]
-          const int r = 16 * ti + (lane >> 4) + 4 * v, c = lane & 15;
-          if (r >= c0 && r < NR && c < 6) Hs[r * LD + c0 + c] -= acc[v];
-        }
-      }
-    }
-    for (int rr = lane; false && rr < NR; rr += 64) {
-#else
-    for (int rr = lane; rr < NR; rr += 64) {
-#endif
-      if (rr < c0) continue;
-      double2* own = reinterpret_cast<double2*>(Hs + rr * LD);  // (rows are 16-byte aligned: three 128-bit accesses per 6-column block)
-      double2 a0 = own[c0 / 2], a1 = own[c0 / 2 + 1], a2 = own[c0 / 2 + 2];
-      double a[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
-      for (int kb = 0; kb < jb; kb++) {
-        const double2 l0 = own[3 * kb], l1 = own[3 * kb + 1], l2 = own[3 * kb + 2];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          const double2* dr = reinterpret_cast<const double2*>(Hs + (c0 + c) * LD) + 3 * kb;  // (the same address in every lane: a broadcast)
-          const double2 d0 = dr[0], d1 = dr[1], d2 = dr[2];
-          a[c] = fma(-l2.y, d2.y, fma(-l2.x, d2.x, fma(-l1.y, d1.y, fma(-l1.x, d1.x, fma(-l0.y, d0.y, fma(-l0.x, d0.x, a[c]))))));
-        }
-      }
-      own[c0 / 2] = double2{a[0], a[1]};
-      own[c0 / 2 + 1] = double2{a[2], a[3]};
-      own[c0 / 2 + 2] = double2{a[4], a[5]};
-    }
-    wave_lds_fence();
-    // diagonal block: every lane factors it redundantly in registers and inverts the factor
-    double d[6][6], li[6][6];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-      for (int c = 0; c <= r; c++) d[r][c] = Hs[(c0 + r) * LD + c0 + c];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      double s = d[j][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= d[j][k] * d[j][k];
-      if (!(s > 0) || !isfinite(s)) {
-        okc = false;
-        s = 1.0;
-      }
-      const double inv = rsqrt_nr(s), dj = s * inv;
-      d[j][j] = dj;
-      li[j][j] = inv;
-#pragma unroll
-      for (int i = j + 1; i < 6; i++) {
-        double v = d[i][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) v -= d[i][k] * d[j][k];
-        d[i][j] = v * inv;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 6; c++)  // li = d^-1 (lower): column c by forward substitution
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        double v = 0;
-#pragma unroll
-        for (int k = c; k < r; k++) v -= d[r][k] * li[k][c];
-        li[r][c] = v * li[r][r];
-      }
-    wave_lds_fence();
-    if (lane < 36) {
-      const int r = lane / 6, c = lane - 6 * r;
-      double dv = 0, lv = 0;
-#pragma unroll
-      for (int rr = 0; rr < 6; rr++)
-#pragma unroll
-        for (int cc = 0; cc <= rr; cc++)
-          if (rr == r && cc == c) {
-            dv = d[rr][cc];
-            lv = li[rr][cc];
-          }
-      Linv[jb * 36 + lane] = lv;  // zero above the diagonal
-      if (r >= c) Hs[(c0 + r) * LD + c0 + c] = dv;
-    }
-    // rows below the block: L_row = a_row * d^-T
-    for (int rr = lane; rr < NR; rr += 64) {
-      if (rr < c0 + 6) continue;
-      double a[6], xr[6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) a[c] = Hs[rr * LD + c0 + c];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        double v = 0;
-#pragma unroll
-        for (int k = 0; k <= c; k++) v = fma(a[k], li[c][k], v);
-        xr[c] = v;
-      }
-#pragma unroll
-      for (int c = 0; c < 6; c++) Hs[rr * LD + c0 + c] = xr[c];
-    }
-    wave_lds_fence();
-  }
-  BAPROF(5);
-  ba_chol_subst(true);
-  return okc;
-}
-
-// the two triangular solves on sh.x with the factor in Hs / Linv, by ONE wave.  fwd = false: the forward substitution happened inside
-// the factorisation (ba_chol_factor_wg), y is row NR of Hs.
-FD void ba_chol_subst(bool fwd) {
-  BAShared& sh = ba_sh();
-  double* Hs = ba_dyn();
-  double* Linv = Hs + sh.off_linv;
-  double* xs = sh.x;
-  const int P = sh.P, LD = sh.LD;
-  const int lane = threadIdx.x & 63;
-  const int NR = 6 * P;
-  if (!fwd) {
-    for (int i = lane; i < NR; i += 64) xs[i] = Hs[NR * LD + i];
-    wave_lds_fence();
-  }
-  // forward substitution L y = rhs (block-wise)
-  for (int jb = 0; fwd && jb < P; jb++) {
-    const int c0 = 6 * jb;
-    double y[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-      double v = 0;
-#pragma unroll
-      for (int k = 0; k <= r; k++) v = fma(Linv[jb * 36 + 6 * r + k], xs[c0 + k], v);
-      y[r] = v;
-    }
-    wave_lds_fence();
-    if (lane < 6) {
-      double v = 0;
-#pragma unroll
-      for (int r = 0; r < 6; r++)
-        if (r == lane) v = y[r];
-      xs[c0 + lane] = v;
-    }
-    for (int rr = lane; rr < NR; rr += 64) {
-      if (rr < c0 + 6) continue;
-      const double2* own = reinterpret_cast<const double2*>(Hs + rr * LD) + c0 / 2;
-      const double2 l0 = own[0], l1 = own[1], l2 = own[2];
-      xs[rr] = fma(-l2.y, y[5], fma(-l2.x, y[4], fma(-l1.y, y[3], fma(-l1.x, y[2], fma(-l0.y, y[1], fma(-l0.x, y[0], xs[rr]))))));
-    }
-    wave_lds_fence();
-  }
+  for (int i = lane; i < NR; i += 64) xs[i] = Hs[NR * LD + i];
+  wave_lds_fence();
   // backward substitution L^T x = y
   for (int jb = P - 1; jb >= 0; jb--) {
     const int c0 = 6 * jb;
@@ -888,19 +725,12 @@ FD void ba_chol_subst(bool fwd) {
   }
 }
 
-#ifndef FLVIS_BA_CHOL_WG
-#ifdef FLVIS_BA_SOLVE_MFMA
-#define FLVIS_BA_CHOL_WG 0
-#else
-#define FLVIS_BA_CHOL_WG 1
-#endif
-#endif
 // The factorisation of the reduced system by the WHOLE workgroup (round 6), right-looking.  Wave 0 factors the diagonal block of block
 // column jb and scales the rows below it -- the chain of six pivots nobody can help with; then every wave takes one block column kb > jb
-// of the trailing matrix, lane = row: the very products, in the very order, that the one-wave left-looking form (ba_chol_solve) subtracts
-// when it reaches column kb, so the factor is the same bit for bit.  The one-wave form walked all finished block columns per panel with
-// seven waves waiting at the phase's barrier (12.5 us per LM trial, 20 trials per optimisation); here a block column costs its pivot chain,
-// one 36-FMA update and two barriers.  -DFLVIS_BA_CHOL_WG=0 keeps the one-wave form.
+// of the trailing matrix, lane = row: the very products, in the very order, that rounds 1-5's one-wave left-looking form subtracted
+// when it reached column kb, so the factor is the same bit for bit.  The one-wave form walked all finished block columns per panel with
+// seven waves waiting at the phase's barrier (12.5 us per LM trial, 20 trials per optimisation; profiles/r06_ba_phases.md); here a block
+// column costs its pivot chain, one 36-FMA update and two barriers.
 __device__ FLVIS_BA_PHASE_FN bool ba_chol_factor_wg() {
   BAShared& sh = ba_sh();
   double* Hs = ba_dyn();
@@ -2036,12 +1866,8 @@ __device__ __noinline__ void ba_phase_schur_mfma(double lambda) {
 __device__ FLVIS_BA_PHASE_FN void ba_phase_solve_poses(bool okc_wg) {
   BAShared& sh = ba_sh();
   const int lane = threadIdx.x & 63;
-#if FLVIS_BA_CHOL_WG
   const bool okc = okc_wg;
-  ba_chol_subst(false);
-#else
-  const bool okc = ba_chol_solve();
-#endif
+  ba_chol_subst();
   wave_lds_fence();
   BAPROF(6);
   if (lane == 0) sh.flag = okc ? 1 : 0;
@@ -2334,11 +2160,7 @@ __device__ __noinline__ void ba_optimize(const WindowDev& w, int iterations) {
         __syncthreads();
       }
       BAPROF(7);
-#if FLVIS_BA_CHOL_WG
       const bool okc_wg = ba_chol_factor_wg();  // (ends behind wave 0's last diagonal block: the substitutions below are wave 0's too)
-#else
-      const bool okc_wg = true;
-#endif
       if (t < 64) ba_phase_solve_poses(okc_wg);
       __syncthreads();
       BAPROF(8);

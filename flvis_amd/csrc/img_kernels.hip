@@ -932,53 +932,14 @@ constexpr int DEM_T = 256;
 // region offsets.  In the tracker it runs on the detection stream right after k_gftt_pick.  k_feature_dem is what stays on the frame's
 // critical path: the existing landmarks fill their regions, the greedy spacing walk, the output.
 constexpr int DEMP_T = 1024;  // k_feature_dem_prep: 16 waves, one per region where a region is sorted once more (ties)
-// Accessor of dem_sort.hpp for an array of up to 64 NREG elements that lives in NREG (1 or 2) vector registers ACROSS the lanes of the
-// wave (element e in lane e & 63 of register e >> 6): every index is wave-uniform, so get / set are v_readlane / v_writelane and the sequential
-// algorithm runs on the scalar unit.  An element is (class << 16) | position, class = number of candidates of the region with a
-// strictly greater score: a greater score <=> a smaller class, equal scores <=> equal classes (sortbysecdesc through integers).
-#ifndef FLVIS_DEM_SORT_LANES
-#define FLVIS_DEM_SORT_LANES 0
-#endif
-// ... and for the same packed elements as a plain array (LDS)
+// Accessor of dem_sort.hpp for the packed elements of a region in LDS.  An element is (class << 16) | position, class = number of
+// candidates of the region with a strictly greater score: a greater score <=> a smaller class, equal scores <=> equal classes
+// (sortbysecdesc through integers).  (An array held across the lanes' registers was measured no faster: DESIGN.md appendix A, FeatureDEM tie order.)
 struct PackedArray {
   typedef int value_type;
   int* v;
   __device__ __forceinline__ int get(int i) const { return v[i]; }
   __device__ __forceinline__ void set(int i, int x) const { v[i] = x; }
-  __device__ __forceinline__ bool before(int a, int b) const { return (a >> 16) < (b >> 16); }
-};
-template <int NREG>
-struct LaneArray {
-  typedef int value_type;
-  int& r0;
-  int& r1;  // (NREG == 1: unused)
-  // v_writelane_b32 with the value in an SGPR and the lane in M0 (a VOP3 reads one SGPR on gfx9); M0 is saved and restored
-  static __device__ __forceinline__ int writelane(int old, int val, int lane) {
-    int tmp;
-    val = __builtin_amdgcn_readfirstlane(val);    // (wave-uniform by construction; the constraint "s" needs the compiler to know it)
-    lane = __builtin_amdgcn_readfirstlane(lane);
-    asm volatile("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
-                 : "+v"(old), "=&s"(tmp)
-                 : "s"(val), "s"(lane));
-    return old;
-  }
-  __device__ __forceinline__ int get(int i) const {
-    i = __builtin_amdgcn_readfirstlane(i);
-    const int a = __builtin_amdgcn_readlane(r0, i & 63);
-    if (NREG == 1) return a;
-    const int b = __builtin_amdgcn_readlane(r1, i & 63);
-    return i < 64 ? a : b;
-  }
-  __device__ __forceinline__ void set(int i, int x) const {
-    i = __builtin_amdgcn_readfirstlane(i);
-    if (NREG == 1) {
-      r0 = writelane(r0, x, i);
-    } else {  // (both registers are written, one result is kept: no pointer selects, the array stays in registers)
-      const int n0 = writelane(r0, x, i & 63), n1 = writelane(r1, x, i & 63);
-      r0 = i < 64 ? n0 : r0;
-      r1 = i < 64 ? r1 : n1;
-    }
-  }
   __device__ __forceinline__ bool before(int a, int b) const { return (a >> 16) < (b >> 16); }
 };
 
@@ -1075,26 +1036,12 @@ __device__ __forceinline__ void k_feature_dem_prep_body(ImgSel src, int w, int h
   // one wave per region with a tie: libstdc++'s introsort on the region's candidates in their input order, as packed (class, position)
   // integers.  Up to 16 candidates std::sort IS an insertion sort, i.e. stable: the ranks above are its result already.  Beyond that
   // only std::sort's first phase -- the quicksort levels on ranges longer than 16 -- is walked through sequentially (lane 0 of the
-  // region's wave, array in LDS; FLVIS_DEM_SORT_LANES: in registers across the lanes): the insertion sort that follows is stable, so its
+  // region's wave, array in LDS): the insertion sort that follows is stable, so its
   // result is the STABLE order of what the first phase leaves, and that is a rank every lane computes for its own elements (position =
   // class + equal classes earlier in the array): n log2(n / 16) sequential element visits instead of n log2 n + n^2 / 64.
   if (wv < 16 && rtie[wv] && roff[wv + 1] - roff[wv] > demsort::THRESHOLD) {
     const int r0 = roff[wv], n = roff[wv + 1] - r0;
-#if FLVIS_DEM_SORT_LANES
-    if (n <= 128) {
-      int a0 = lane < n ? ccls[r0 + lane] : 0;
-      int a1 = 64 + lane < n ? ccls[r0 + 64 + lane] : 0;
-      if (n <= 64)
-        demsort::quicksort_phase(LaneArray<1>{a0, a1}, n, sstack[wv]);
-      else
-        demsort::quicksort_phase(LaneArray<2>{a0, a1}, n, sstack[wv]);
-      if (lane < n) ccls[r0 + lane] = a0;
-      if (64 + lane < n) ccls[r0 + 64 + lane] = a1;
-    } else
-#endif
-    {
-      if (lane == 0) demsort::quicksort_phase(PackedArray{ccls + r0}, n, sstack[wv]);
-    }
+    if (lane == 0) demsort::quicksort_phase(PackedArray{ccls + r0}, n, sstack[wv]);
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     for (int e = lane; e < n; e += 64) {

@@ -153,47 +153,21 @@ __device__ __forceinline__ bool lk_load_region(const uint8_t* __restrict__ img, 
   ((((K)&3) == 3) ? __builtin_amdgcn_perm((D)[((K) >> 2) + 1], (D)[(K) >> 2], 0x0c040c03u)                         \
                   : __builtin_amdgcn_perm(0u, (D)[(K) >> 2], 0x0c000c00u | (uint32_t)((K)&3) | ((uint32_t)(((K)&3) + 1) << 16)))
 
-// sum of v over the wave as a wave-uniform value: 4 DPP steps give every lane its row-of-16 total, two row broadcasts
-// (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) carry the row totals upwards, lane 63 holds the wave total --
-// one readlane instead of four readlanes + three scalar adds (integer sums: any order is exact)
-__device__ __forceinline__ int lk_wave_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15, rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31, rows 2 and 3
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// exact 64-bit total of a per-lane int32: 16-bit halves cannot overflow 32 bits over 64 lanes
-__device__ __forceinline__ long long lk_wave_sum_wide(int v) {
-  const int lo = lk_wave_sum_i32(v & 0xffff), hi = lk_wave_sum_i32(v >> 16);
-  return ((long long)hi << 16) + (long long)lo;
-}
-
 // Instruction diet of the iteration (round 6).  The LK launches are bound by INSTRUCTION ISSUE -- one instruction of any kind per 4 cycles
 // and SIMD, vector, scalar, LDS, wait and no-op alike (profiles/r06_chain_ab.md; SQ counters: 0.44 scalar instructions per vector one) --
-// not by latency: what shortens them is fewer instructions per iteration.  -DFLVIS_LK_DIET=0 keeps rounds 3-5's forms.
-#ifndef FLVIS_LK_DIET
-#define FLVIS_LK_DIET 1
-#endif
+// not by latency: what shortens them is fewer instructions per iteration (rounds 3-5's forms were measured against these there).
 // a . b + c with c in a SCALAR register (v_dot2_i32_i16, the three-source form): the rounding bias of a bilinear interpolation is a
 // constant, and the accumulate-in-place form the compiler picks for the builtin (v_dot2c_i32_i16) needs a v_mov of it per pixel
 __device__ __forceinline__ int lk_dot2_bias(lk_s2 a, lk_s2 b, int bias_uniform) {
-#if FLVIS_LK_DIET
   int r;
   asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(bias_uniform));
   return r;
-#else
-  return __builtin_amdgcn_sdot2(a, b, bias_uniform, false);
-#endif
 }
 // the exact wave totals of two per-lane int32 as floats, (float)(long long) of each (round to nearest even): the four 16-bit-half chains
 // advance together, step by step (every DPP step's operands were written four instructions earlier: no wait states to fill), and the
 // totals are put together in double -- hi * 65536 + lo is exact below 2^53, one rounding into float -- on the vector unit in lane 63
 // instead of ~13 scalar instructions per value (count leading zeros, shift, sticky bit, convert, scale); two read-lanes instead of four
 __device__ __forceinline__ void lk_wave_sum2_f32(int v1, int v2, float& f1, float& f2) {
-#if FLVIS_LK_DIET
   int a = v1 & 0xffff, b = v1 >> 16, c = v2 & 0xffff, d = v2 >> 16;
 #define LK_STEP4(CTRL, RM)                                           \
   {                                                                  \
@@ -213,17 +187,12 @@ __device__ __forceinline__ void lk_wave_sum2_f32(int v1, int v2, float& f1, floa
   const float g1 = (float)__builtin_fma((double)b, 65536.0, (double)a), g2 = (float)__builtin_fma((double)d, 65536.0, (double)c);
   f1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g1), 63));
   f2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g2), 63));
-#else
-  f1 = (float)lk_wave_sum_wide(v1);
-  f2 = (float)lk_wave_sum_wide(v2);
-#endif
 }
 
 // the exact 64-bit wave totals of three per-lane int32 (the Hessian sums of a template level): six 16-bit-half chains advancing together
 // -- a DPP step's operand was written six instructions earlier, so none of the ~30 wait-state no-ops of three reductions one after the
-// other (lk_wave_sum_wide x 3)
+// other
 __device__ __forceinline__ void lk_wave_sum3_wide(int v1, int v2, int v3, long long& s1, long long& s2, long long& s3) {
-#if FLVIS_LK_DIET
   int a = v1 & 0xffff, b = v1 >> 16, c = v2 & 0xffff, d = v2 >> 16, e = v3 & 0xffff, f = v3 >> 16;
 #define LK_STEP6(CTRL, RM)                                                    \
   {                                                                           \
@@ -245,11 +214,6 @@ __device__ __forceinline__ void lk_wave_sum3_wide(int v1, int v2, int v3, long l
   s1 = ((long long)__builtin_amdgcn_readlane(b, 63) << 16) + (long long)__builtin_amdgcn_readlane(a, 63);
   s2 = ((long long)__builtin_amdgcn_readlane(d, 63) << 16) + (long long)__builtin_amdgcn_readlane(c, 63);
   s3 = ((long long)__builtin_amdgcn_readlane(f, 63) << 16) + (long long)__builtin_amdgcn_readlane(e, 63);
-#else
-  s1 = lk_wave_sum_wide(v1);
-  s2 = lk_wave_sum_wide(v2);
-  s3 = lk_wave_sum_wide(v3);
-#endif
 }
 
 // The interpolated template of one level: I, Ix, Iy of the 31 x 31 window as packed int16 pairs in the lane's registers (lane = window
@@ -424,9 +388,6 @@ __device__ __forceinline__ const uint8_t* lk_level_ptr(const PyrSel& P, int leve
   return I.b[I.cur ? (kc ^ I.flip) : 0] + (size_t)s * P.stride[level];
 }
 
-#ifndef FLVIS_LK_PREFETCH
-#define FLVIS_LK_PREFETCH 0  // (build-variant knob; measured: the 24 registers it holds cost more than the round trip it saves)
-#endif
 #ifndef FLVIS_LK_EARLY_REGION
 #define FLVIS_LK_EARLY_REGION 1  // (build-variant knob, round 6: a cached level stages its first search region beside the template loads)
 #endif
@@ -494,9 +455,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
   // (epsilon^2 in a VECTOR register pair: the scalar registers are oversubscribed by the two pyramids' argument blocks, and the compiler
   // re-read this kernel argument with an s_load + s_waitcnt in front of the convergence test of EVERY iteration)
   double eps2 = prm.eps2;
-#if FLVIS_LK_DIET
   if (ROLE == 1 || ROLE == 4) asm volatile("" : "+v"(eps2));  // (the launches with registers to spare: 121 of 128; the others are at 128)
-#endif
   const float FLT_SCALE = 1.f / (1 << 20);
   const float halfWin = (LK_WIN - 1) * 0.5f;
 
@@ -609,16 +568,6 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
 #pragma unroll
         for (int k = 0; k < 6; k++) q[k] = pq[k];
         pq_level = -1;
-#if FLVIS_LK_PREFETCH
-        // the next level's templates are requested now: they travel while this level iterates, together with the search region's loads
-        // (one memory round trip per level instead of two)
-        if (level > 0 && ((tc_mask >> (level - 1)) & 1u)) {
-          const lk_u4* src = reinterpret_cast<const lk_u4*>(tc_ptr + LK_TC_HDR + (size_t)(level - 1) * LK_TC_LVL) + lane;
-#pragma unroll
-          for (int k = 0; k < 6; k++) pq[k] = __builtin_nontemporal_load(src + 64 * k);
-          pq_level = level - 1;
-        }
-#endif
         // (the three Hessian sums ride in lane 63's registers: the lanes of window row 31 hold no template)
         iA11 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)q[0].y, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)q[0].x, 63));
         iA12 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)q[0].w, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)q[0].z, 63));

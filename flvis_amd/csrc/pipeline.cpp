@@ -67,7 +67,7 @@ struct Lane {
   // when the GPU gets to them.
   static constexpr int PIN_RING = 4;
   void* pinned[PIN_RING] = {};      // page-locked staging of a frame's inputs (host view) ...
-  uint8_t* pinned_dev[PIN_RING] = {};  // ... and the same memory as the device sees it (FLVIS_INPUT_ZEROCOPY: k_frame_head reads it in place)
+  uint8_t* pinned_dev[PIN_RING] = {};  // ... and the same memory as the device sees it (k_frame_head reads it in place)
   const uint8_t* h_tab[2] = {nullptr, nullptr};  // the image bases of the last frame fed (host copy of the table)
   size_t in_off_imu = 0, in_off_tab = 0, in_off_n = 0;
   // the slot of frame n may be refilled once frame n's upload is done: k_frame_head (the first kernel after the upload) stores the
@@ -80,7 +80,7 @@ struct Lane {
   std::vector<void*> allocs;
   std::vector<hipEvent_t> prof_ev;  // optional per-stage HIP-event timing (flvis_prof_enable)
   std::vector<unsigned char> prof18_rec;  // per armed step: the local-map launch's event pair (stage 18) was recorded -- a deferred launch
-                                          // (FLVIS_BA_START) belongs to the NEXT step, the first step of a batch has none, the last one two
+                                          // (Pipeline::defer_ba) belongs to the NEXT step, the first step of a batch has none, the last one two
   // corner detection on its own HIP stream: goodFeaturesToTrack only needs the new image, so it runs beside the temporal
   // tracking chain (LK -> RANSACs -> pose LM) and joins before FeatureDEM consumes the corners
   hipStream_t det_stream = nullptr;
@@ -111,7 +111,7 @@ struct Lane {
   unsigned* d_join_cnt = nullptr;          // [JOIN_IDS] arrival counters of the launches that signal a word themselves (KJoin)
   long long join_seq[JOIN_IDS] = {};
   long long ba_launches = 0;
-  bool ba_pending = false;       // FLVIS_BA_START > 0: the local-map launch for the last frame's keyframes has not been enqueued yet
+  bool ba_pending = false;       // the local-map launch for the last frame's keyframes has not been enqueued yet (Pipeline::defer_ba)
   unsigned ba_tag = 0;           // tag of the lane's last local-map launch (k_ba_worker's stream list is valid for one tag; 0 is never used)
   // reset commands in the keyframe queues (flvis_reset_streams / flvis_local_map_reset): per stream, the lane frame count when its last
   // command was appended (-1: none, or keyframes pushed behind it) -- a second request before the next frame adds no entry; and the lane
@@ -133,9 +133,17 @@ struct Pipeline {
   size_t lstride[LK_MAX_LEVELS];
   int lbx = 0, lby = 0;  // physical border of every pyramid level (columns / rows on each side)
   int max_pts = 0;  // bound on the landmarks of a frame (16 regions x max_region_feature_num): sizes the LK grid
+  // The environment knobs the tracker honours, read once when it is created (read_knobs; INTEGRATION.md lists them)
+  int n_lanes_req = 1;  // FLVIS_LANES: sub-batches of streams (1 .. 16)
+  bool lk_border = true;  // FLVIS_LK_BORDER: pyramid levels with a physical border
+  bool lk_tcache = true;  // FLVIS_LK_TCACHE: the LK template cache between a frame's stereo and the next frame's temporal LK
+  bool tpl_ahead = false;  // FLVIS_TPL_AHEAD: the stereo matcher's templates computed ahead, on a stream of their own
   int tpl_start = 1;  // FLVIS_TPL_START: where k_lk_templates_ahead starts (lane_frame)
-  int lk_order = 2;     // FLVIS_LK_ORDER (bits: 1 temporal, 2 stereo; default 2): the launch takes a stream's points from the last to the first
   int chain_merge = 3;  // FLVIS_CHAIN_MERGE: launches of the frame's chain folded into their neighbours (lane_frame)
+  bool head_prepare = true;  // FLVIS_HEAD_PREPARE: k_frame_head and k_track_prepare as one launch
+  bool ba_mfma = false, ba_balance = false, kf_check = false;  // FLVIS_BA_MFMA, FLVIS_BA_BALANCE, FLVIS_KF_CHECK (Pipe fields)
+  bool pnp_tail_cv = false;  // FLVIS_PNP_TAIL=cv
+  unsigned prof_scope = 0;  // FLVIS_PROF_EVENT_SCOPE: release scope of the stage-timing events
   long long frames_fed = 0;
   std::vector<void*> allocs;  // context-level device allocations (host-feed staging)
   int prof_cap = 0, prof_step = 0;
@@ -145,21 +153,20 @@ struct Pipeline {
   // back into the tracker in the reference (src/frontend/vo_tracking.cpp:373-385).
   static constexpr int NBA = 8;
   static_assert(NBA == BA_PLAN_SLOTS, "one stream list per local-map HIP stream");
-  int nba = 2;                   // local-map streams in use: 2 per lane (FLVIS_BA_STREAMS per lane, tuning knob)
+  int nba = 2;                   // local-map streams in use: 2 per lane (profiles/r04_local_map_and_streams_ab.md) ...
   int nba_lane = 2;              // ... of which every lane uses its own nba_lane
   int host_lead = 3;             // frames the host may run ahead of the GPU (FLVIS_HOST_LEAD, 1 .. PIN_RING; 2 until round 6: a host thread that is held up for a millisecond then leaves the GPU dry)
   int host_lead_cap = 4;         // (flvis_image_feed_host lowers it to 1 for its call: its copies and events add to the queued commands)
   int input_hold = 0;            // flvis_set_input_hold: frames the caller keeps its input buffers untouched after handing them over
-  bool stagger = true;           // FLVIS_LANE_STAGGER=0: lanes start their first frame together
   double host_ms_total = 0, host_ms_wait = 0;  // host time inside flvis_image_feed / of it blocked on the pinned ring
   bool sync_each_frame = false;  // FLVIS_SYNC_EACH_FRAME=1: image_feed waits for the previous frame (tuning knob)
   int ba_every = 1;              // launch the local-map worker every n-th frame (FLVIS_BA_EVERY)
   bool lk_stats = false;         // flvis_debug_lk_stats: the LK launches count their iterations per level into counters[36 .. 59]
   hipStream_t ba_stream[NBA] = {};
-  std::vector<hipStream_t> pad_streams;  // idle streams in front of the lanes' template streams (FLVIS_TPL_QPAD)
+  std::vector<hipStream_t> pad_streams;  // idle streams in front of the lanes' template streams (tracker_create_impl)
   long long ba_rr = 0;           // round-robin counter over the local-map streams
   hipEvent_t ev_in = nullptr;    // the caller's inputs are ready (recorded on the context's stream)
-  bool defer_ba = false;         // inside flvis_run_steps, not its last step: the local-map launch of this frame may wait for the next frame (FLVIS_BA_START)
+  bool defer_ba = false;         // inside flvis_run_steps, not its last step: the local-map launch of this frame waits for the next frame (lane_frame)
   bool feedback_used = false;    // flvis_correction_feed was called: k_apply_correction runs after every frame_begin
   // flvis_image_feed_host: double-buffered device staging filled by async H2D copies on a copy stream, so that the upload of
   // frame N+1 overlaps the kernels of frame N (allocated by the first call)
@@ -172,7 +179,7 @@ struct Pipeline {
     // sequence numbers (FLAG_WORDS x the call's number, from a page-locked ring: large enough not to be turned into a blit kernel);
     // k_wait_flag on the stream that ingests the images waits for it; the host learns that the uploads are done from hipStreamQuery
     // and that a slot is free from the frame-progress word.  No event, no kernel, no AQL barrier packet on the copy stream's queue.
-    int mode = 2;
+    int mode = 2;  // FLVIS_H2D_MODE
     static constexpr int FLAG_WORDS = 4096, FLAG_RING = 4;
     long long* h_flag[FLAG_RING] = {};
     long long* d_flag = nullptr;
@@ -192,12 +199,11 @@ struct Pipeline {
     bool timed[2] = {false, false};
     size_t timed_bytes[2] = {0, 0};
     double up_ms = 0, up_bytes = 0, up_calls = 0;
-    hipStream_t pad_strm[4] = {};  // FLVIS_H2D_QPAD (A/B knob): streams created in front of the copy stream, so that its hardware queue is another one
   } hf;
   hipEvent_t up_event = nullptr;  // set by flvis_image_feed_host for its flvis_image_feed call: the upload's event, waited for on the stream that ingests the images
   const long long* up_flag = nullptr;  // ... or (mode 2) the sequence block the copy engine writes behind the images, and the number to wait for
   long long up_seq = 0;
-  unsigned ev_flags = hipEventDisableTiming;  // flags of every event of the pipeline (FLVIS_EVENT_SCOPE)
+  static constexpr unsigned ev_flags = hipEventDisableTiming;  // flags of every event of the pipeline (system scope: profiles/r06_h2d.md)
   bool flag_joins = false;                    // FLVIS_JOIN=flag
   bool fold_joins = false;                    // FLVIS_JOIN_FOLD: the chain's own kernels wait for / store the words (KJoin)
   bool chain_continuous = false;              // this frame follows the previous one on the main stream with nothing of the caller's in between
@@ -411,8 +417,6 @@ extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
       if (pl->hf.ev_t0[k]) hipEventDestroy(pl->hf.ev_t0[k]);
       if (pl->hf.ev_t1[k]) hipEventDestroy(pl->hf.ev_t1[k]);
     }
-    for (hipStream_t ps : pl->hf.pad_strm)
-      if (ps) hipStreamSynchronize(ps), hipStreamDestroy(ps);
     if (pl->hf.h_up) hipHostFree((void*)pl->hf.h_up);
     for (long long* fp : pl->hf.h_flag)
       if (fp) hipHostFree(fp);
@@ -524,18 +528,15 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   // stream's next keyframe, and the two local-map streams never fall behind: 54.2-54.3k frames/s in four runs of four, against
   // 36.8-54.1k (profiles/r04_local_map_and_streams_ab.md).
   p.ba_drain = 1;
-  if (const char* e = getenv("FLVIS_BA_DRAIN")) p.ba_drain = std::max(0, atoi(e));
   // ... with a bound: an owner that finds KFQ / 2 or more keyframes still waiting after its share stays and goes on (a stream whose
   // optimisations take longer than its keyframes arrive -- every frame a keyframe -- would otherwise grow a backlog that only ends at
   // the full queue, where k_frame_end drops keyframes).  A launch takes at least the keyframes of the frames between two launches.
-  if (p.ba_drain > 0) p.ba_drain = std::max(p.ba_drain, pl->ba_every);
+  p.ba_drain = std::max(p.ba_drain, pl->ba_every);
   p.ba_backlog = KFQ / 2;
-  // FLVIS_BA_REMAP=1 (round 5, A/B knob): workgroup r of a local-map launch serves the r-th stream with a keyframe waiting, not stream r,
-  // so that the working workgroups -- a CU each -- are dealt to the XCDs evenly (k_ba_worker).  Measured (one box, two runs each): 57.3k /
-  // 57.0k frames/s against 57.4k / 57.3k, LK launches 0.226 / 0.264 ms either way: which XCD loses the CUs is not what the LK pays for
-  p.ba_remap = getenv("FLVIS_BA_REMAP") && atoi(getenv("FLVIS_BA_REMAP")) == 1;
-  p.ba_mfma = 0;
-  if (const char* e = getenv("FLVIS_BA_MFMA")) p.ba_mfma = atoi(e) != 0;
+  // workgroup r of a local-map launch serves stream r (dealing the working workgroups to the XCDs evenly was no faster:
+  // profiles/r05_local_map_cost.md)
+  p.ba_remap = 0;
+  p.ba_mfma = pl->ba_mfma;
   // FLVIS_BA_BALANCE=1 (opt-in, round 6): the Schur accumulate's lanes per pose pair in proportion to the landmarks the pair shares
   // (ba_balance_pairs) instead of 16 each.  Measured (profiles/r06_ba_phases.md): the benchmark's windows share their landmarks almost
   // evenly (155 per pose, 76-114 per pair of poses), the per-SIMD sums of the accumulate are 262-300 us either way -- the "wait for the
@@ -545,9 +546,8 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   // payload, the local-map worker -- another workgroup, usually on another XCD -- recomputes it from what it reads after its acquire:
   // debug counters 30 (payloads checked) and 31 (mismatches).  The hand-over publishes with ONE agent-scope release by one thread behind a
   // workgroup barrier; tests/test_gpu_pipeline.py runs 64 streams under this check.
-  p.kf_check = getenv("FLVIS_KF_CHECK") && atoi(getenv("FLVIS_KF_CHECK")) == 1;
-  p.ba_balance = 0;
-  if (const char* e = getenv("FLVIS_BA_BALANCE")) p.ba_balance = atoi(e) != 0;
+  p.kf_check = pl->kf_check;
+  p.ba_balance = pl->ba_balance;
   p.ba_lds_bytes = ba_lds_bytes_env();  // (admitted for the config's window by check_cfg)
   DA(ba_scratch, double, (size_t)S * p.ba_scratch_stride);
   // FLVIS_PNP_TAIL=cv (opt-in fidelity mode, round 6): behind k_ransac_pnp the pose of the ITERATIVE flag is replaced by what
@@ -556,10 +556,9 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   // Gauss-Newton refinement of the winning model.  One wave per stream: the small dense algebra (the 12 x 12 and 6 x 6 Jacobi SVDs, OpenCV's
   // loops as they are written) redundantly in every lane, the sums over the correspondences dealt to the lanes; still milliseconds per
   // frame, which is why it is not the default (the two tails agree to 4.4e-9 m on the first tracked frames: the checker's README).
-  p.pnp_tail_cv = 0;
+  p.pnp_tail_cv = pl->pnp_tail_cv;
   p.pnp_tail_ws = nullptr;
   p.pnp_tail_stride = 0;
-  if (const char* e = getenv("FLVIS_PNP_TAIL")) p.pnp_tail_cv = !strcmp(e, "cv");
   if (p.pnp_tail_cv) {
     p.pnp_tail_stride = (size_t)29 * NMAX + 192;  // world points (3 n), pixels (2 n), find_extrinsic_iterative's work (24 n + 192)
     DA(pnp_tail_ws, double, (size_t)S * p.pnp_tail_stride);
@@ -600,21 +599,16 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   p.tc_stride = 0;
   L->tc = nullptr;
   {
-    const char* e = getenv("FLVIS_LK_TCACHE");
-    const bool on = !(e && atoi(e) == 0) && pl->cfg.cam_type != CAM_DEPTH && pl->levels_s == pl->levels_t;
+    const bool on = pl->lk_tcache && pl->cfg.cam_type != CAM_DEPTH && pl->levels_s == pl->levels_t;
     // FLVIS_TPL_AHEAD=1 (round 6, opt-in A/B knob; default 0 = rounds 4-5): the templates of the landmarks the temporal tracker has followed
     // into the frame are computed by k_lk_templates_ahead beside the frame's geometry kernels, the stereo launch takes them from the cache
-    // (lane_frame).  Needs the corner detection behind the F-RANSAC (FLVIS_DET_START >= 2, the default): the signal that starts it starts
-    // this too.  Bit-identical results (test_templates_ahead_leave_the_same_results).  Measured (profiles/r06_templates_ahead.md): the
-    // stereo launch 0.259 -> 0.215 ms, and the kernels the template kernel runs beside pay it back -- k_ransac_pnp 0.187 -> 0.211 ms,
-    // k_gftt_pick 0.121 -> 0.157 ms (FeatureDEM then waits 25 us longer for the corners): 59.0k against 59.9k frames/s; and only with the
-    // template stream on a hardware queue of its own that does not share the main or the detection stream's pipe (FLVIS_TPL_QPAD,
+    // (lane_frame).  The signal that starts the corner detection behind the F-RANSAC starts it too.  Bit-identical results
+    // (test_templates_ahead_leave_the_same_results).  Measured (profiles/r06_templates_ahead.md): the stereo launch 0.259 -> 0.215 ms,
+    // and the kernels the template kernel runs beside pay it back -- k_ransac_pnp 0.187 -> 0.211 ms, k_gftt_pick 0.121 -> 0.157 ms
+    // (FeatureDEM then waits 25 us longer for the corners): 59.0k against 59.9k frames/s; and only with the template stream on a hardware
+    // queue of its own that does not share the main or the detection stream's pipe (two idle streams in front of it, tracker_create_impl;
     // GPU_MAX_HW_QUEUES=8): 47.7k on the detection stream's pipe, 38.6k on the main stream's.
-    const char* ea = getenv("FLVIS_TPL_AHEAD");
-    const bool det_late = !(getenv("FLVIS_DET_START") && atoi(getenv("FLVIS_DET_START")) < 2) &&
-                          !(getenv("FLVIS_DET_ORDER") && atoi(getenv("FLVIS_DET_ORDER")) == 0);
-    const bool ahead = ea && atoi(ea) == 1 && det_late;
-    pl->tpl_start = getenv("FLVIS_TPL_START") && atoi(getenv("FLVIS_TPL_START")) == 0 ? 0 : 1;
+    const bool ahead = pl->tpl_ahead;
     if (ok && on) {
       // slots: the stereo launch's points (rounds 4-5) or, with templates ahead, the survivors of the temporal tracker followed by the
       // frame's new landmarks
@@ -692,16 +686,8 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   } else {
     L->st = ctx->stream;
   }
-  // (FLVIS_DET_PRIO=1, A/B knob: the detection stream at the lowest queue priority, so that corner-response workgroups that start beside
-  // the tracking chain's kernels do not take a compute unit one of those is waiting for)
-  bool evok;
-  if (getenv("FLVIS_DET_PRIO") && atoi(getenv("FLVIS_DET_PRIO")) != 0) {
-    int lo = 0, hi = 0;
-    hipDeviceGetStreamPriorityRange(&lo, &hi);
-    evok = hipStreamCreateWithPriority(&L->det_stream, hipStreamNonBlocking, lo) == hipSuccess;
-  } else {
-    evok = hipStreamCreateWithFlags(&L->det_stream, hipStreamNonBlocking) == hipSuccess;
-  }
+  // (the detection stream at the default priority; the lowest was measured no faster: DESIGN.md section 4)
+  bool evok = hipStreamCreateWithFlags(&L->det_stream, hipStreamNonBlocking) == hipSuccess;
   if (L->pipe.tpl_ahead) evok = evok && hipEventCreateWithFlags(&L->ev_tpl, pl->ev_flags) == hipSuccess;  // (its stream: flvis_tracker_create)
   static_assert(Lane::HOLD_RING == 8, "event list below");  // (ev_endf included)
   for (hipEvent_t* e : {&L->ev_img, &L->ev_det, &L->ev_gftt, &L->ev_fe, &L->ev_lm, &L->ev_tri, &L->ev_head, &L->ev_endf, &L->ev_stagger, &L->ev_end[0], &L->ev_end[1], &L->ev_end[2],
@@ -766,6 +752,48 @@ static int check_stream_cfgs(flvis_ctx* ctx, const flvis_cfg& ref, int n, const 
   return FLVIS_OK;
 }
 
+// Every environment knob the tracker honours, read once when it is created (INTEGRATION.md's table lists them with their defaults).
+// (FLVIS_BA_LDS_KB is read by ba_lds_bytes_env: check_cfg needs it before a tracker exists.)
+static bool env_is(const char* name, int v) {
+  const char* e = getenv(name);
+  return e && atoi(e) == v;
+}
+static void read_knobs(Pipeline* pl) {
+  const char* j = getenv("FLVIS_JOIN");
+  pl->flag_joins = !(j && !strcmp(j, "event"));  // (default since round 6: 58.6k -> 60.4k frames/s, chain p50 1.047 -> 1.012 ms; "event": rounds 1-5)
+  // Under a profiler that collects hardware counters (rocprofv3 --pmc sets ROCPROF_COUNTER_COLLECTION in the application's environment)
+  // kernels run ONE AT A TIME: a k_wait_flag that sleeps until a kernel of another stream has stored its word would wait for a kernel
+  // that cannot start, and end by its 4 s limit.  Events are resolved by the command processor between kernels: taken there unless
+  // FLVIS_JOIN says otherwise.  (The wait for an upload is not affected: the copy engine runs beside a serialised kernel.)
+  if (!j) {
+    const char* cc = getenv("ROCPROF_COUNTER_COLLECTION");
+    if (cc && cc[0] && strcmp(cc, "0") && strcmp(cc, "False") && strcmp(cc, "false")) pl->flag_joins = false;
+  }
+  pl->fold_joins = pl->flag_joins && !env_is("FLVIS_JOIN_FOLD", 0);
+  if (const char* e = getenv("FLVIS_LANES")) {
+    const int v = atoi(e);
+    if (v >= 1 && v <= 16) pl->n_lanes_req = v;
+  }
+  pl->lk_border = !env_is("FLVIS_LK_BORDER", 0);
+  pl->lk_tcache = !env_is("FLVIS_LK_TCACHE", 0);
+  pl->tpl_ahead = env_is("FLVIS_TPL_AHEAD", 1);
+  pl->tpl_start = env_is("FLVIS_TPL_START", 0) ? 0 : 1;
+  pl->head_prepare = !env_is("FLVIS_HEAD_PREPARE", 0);
+  if (const char* e = getenv("FLVIS_HOST_LEAD")) pl->host_lead = std::max(1, std::min(atoi(e), (int)Lane::PIN_RING));
+  if (const char* e = getenv("FLVIS_SYNC_EACH_FRAME")) pl->sync_each_frame = atoi(e) != 0;
+  if (const char* e = getenv("FLVIS_CHAIN_MERGE")) pl->chain_merge = atoi(e) & 3;
+  if (const char* e = getenv("FLVIS_BA_EVERY")) {
+    const int v = atoi(e);
+    if (v >= 1 && v <= KFQ / 4) pl->ba_every = v;  // (the back-pressure in lane_frame needs (D + 2) * ba_every <= KFQ / 2)
+  }
+  if (const char* e = getenv("FLVIS_BA_MFMA")) pl->ba_mfma = atoi(e) != 0;
+  if (const char* e = getenv("FLVIS_BA_BALANCE")) pl->ba_balance = atoi(e) != 0;
+  pl->kf_check = env_is("FLVIS_KF_CHECK", 1);
+  if (const char* e = getenv("FLVIS_PNP_TAIL")) pl->pnp_tail_cv = !strcmp(e, "cv");
+  if (const char* e = getenv("FLVIS_H2D_MODE")) pl->hf.mode = atoi(e) == 1 ? 1 : 2;
+  if (const char* e = getenv("FLVIS_PROF_EVENT_SCOPE")) pl->prof_scope = !strcmp(e, "agent") ? hipEventReleaseToDevice : 0u;
+}
+
 // cfgs: one config for all streams (n_cfgs 1, flvis_tracker_create) or one per stream (n_cfgs = n_streams), checked by the caller
 static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs, int n_streams, uint64_t seed_base, int traj_capacity) {
   const flvis_cfg* cfg = &cfgs[0];
@@ -773,26 +801,7 @@ static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs
   hipSetDevice(ctx->device);
   Pipeline* pl = new Pipeline();
   ctx->pipe = pl;
-  // FLVIS_EVENT_SCOPE=agent (round 6, A/B knob): events created with hipEventReleaseToDevice.  The runtime turns every hipEventRecord into a
-  // barrier packet that acquires and releases at SYSTEM scope (AMD_LOG_LEVEL=4: "BarrierValue ... acquire=2, release=2", ~30 per frame) where
-  // agent scope would do for events that order kernels of one device.  Measured: the flag changes neither the logged header nor the
-  // rate (58.6k / 56.7k frames/s resident / host images with it, 58.5k / 56.5k without): left off.
-  {
-    const char* e = getenv("FLVIS_EVENT_SCOPE");
-    if (e && !strcmp(e, "agent")) pl->ev_flags |= hipEventReleaseToDevice;
-    const char* j = getenv("FLVIS_JOIN");
-    pl->flag_joins = !(j && !strcmp(j, "event"));  // (default since round 6: 58.6k -> 60.4k frames/s, chain p50 1.047 -> 1.012 ms; "event": rounds 1-5)
-    // Under a profiler that collects hardware counters (rocprofv3 --pmc sets ROCPROF_COUNTER_COLLECTION in the application's environment)
-    // kernels run ONE AT A TIME: a k_wait_flag that sleeps until a kernel of another stream has stored its word would wait for a kernel
-    // that cannot start, and end by its 4 s limit.  Events are resolved by the command processor between kernels: taken there unless
-    // FLVIS_JOIN says otherwise.  (The wait for an upload is not affected: the copy engine runs beside a serialised kernel.)
-    if (!j) {
-      const char* cc = getenv("ROCPROF_COUNTER_COLLECTION");
-      if (cc && cc[0] && strcmp(cc, "0") && strcmp(cc, "False") && strcmp(cc, "false")) pl->flag_joins = false;
-    }
-    const char* f = getenv("FLVIS_JOIN_FOLD");
-    pl->fold_joins = pl->flag_joins && !(f && atoi(f) == 0);
-  }
+  read_knobs(pl);
   const int S = n_streams;
   pl->S = S;
   pl->cfg = *cfg;
@@ -809,12 +818,8 @@ static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs
   pl->levels_s = lk_levels(w, h, 31, 5);
   pl->levels = std::max(pl->levels_t, pl->levels_s);
   if (pl->levels >= LK_MAX_LEVELS) pl->levels = LK_MAX_LEVELS - 1;
-  {
-    const char* e = getenv("FLVIS_LK_BORDER");
-    const bool on = !(e && atoi(e) == 0);
-    pl->lbx = on ? LK_BORDER_X : 0;
-    pl->lby = on ? LK_BORDER_Y : 0;
-  }
+  pl->lbx = pl->lk_border ? LK_BORDER_X : 0;
+  pl->lby = pl->lk_border ? LK_BORDER_Y : 0;
   int lw = w, lh = h;
   for (int l = 0; l <= pl->levels; l++) {
     pl->lw[l] = lw;
@@ -830,29 +835,11 @@ static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs
   // lanes: one by default.  Measured on MI355X with 64 streams (bench.py, round 2): 1 lane 1.67 ms per step, 2 lanes 2.23 ms,
   // 4 lanes 2.94 ms -- a lane's one-workgroup-per-stream geometry kernels share their CUs with the other lanes' LK waves and
   // slow down by more than the overlap gains.  FLVIS_LANES (1..16) is kept as a tuning knob.
-  int n_lanes = 1;
-  if (const char* e = getenv("FLVIS_LANES")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= 16) n_lanes = v;
-  }
-  n_lanes = std::min(n_lanes, S);
+  int n_lanes = std::min(pl->n_lanes_req, S);
   pl->lane_size = (S + n_lanes - 1) / n_lanes;
   n_lanes = (S + pl->lane_size - 1) / pl->lane_size;
-  if (const char* e = getenv("FLVIS_BA_STREAMS")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= 4) pl->nba_lane = v;
-  }
   pl->nba_lane = std::max(1, std::min(pl->nba_lane, Pipeline::NBA / n_lanes));
   pl->nba = std::min(Pipeline::NBA, pl->nba_lane * n_lanes);  // (more than NBA / nba_lane lanes share local-map streams)
-  if (const char* e = getenv("FLVIS_LANE_STAGGER")) pl->stagger = atoi(e) != 0;
-  if (const char* e = getenv("FLVIS_HOST_LEAD")) pl->host_lead = std::max(1, std::min(atoi(e), (int)Lane::PIN_RING));
-  if (const char* e = getenv("FLVIS_SYNC_EACH_FRAME")) pl->sync_each_frame = atoi(e) != 0;
-  if (const char* e = getenv("FLVIS_CHAIN_MERGE")) pl->chain_merge = atoi(e) & 3;
-  if (const char* e = getenv("FLVIS_LK_ORDER")) pl->lk_order = atoi(e) & 3;
-  if (const char* e = getenv("FLVIS_BA_EVERY")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= KFQ / 4) pl->ba_every = v;  // (the back-pressure in lane_frame needs (D + 2) * ba_every <= KFQ / 2)
-  }
   bool ok = true;
   for (int k = 0; k < n_lanes && ok; k++) {
     Lane* L = new Lane();
@@ -864,30 +851,25 @@ static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs
   // the local map must not displace the tracking chain: its streams get the lowest queue priority
   int prio_least = 0, prio_greatest = 0;
   hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  if (const char* e = getenv("FLVIS_BA_PRIORITY")) prio_least = atoi(e);  // tuning knob
   for (int k = 0; k < pl->nba && ok; k++)
     ok = hipStreamCreateWithPriority(&pl->ba_stream[k], hipStreamNonBlocking, prio_least) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&pl->ev_in, pl->ev_flags) == hipSuccess;
-  // the streams of k_lk_templates_ahead, created LAST and behind FLVIS_TPL_QPAD idle streams: a fifth compute queue shares a pipe of the
-  // command processor with one of the first four (queue i sits on pipe i mod 4 in creation order, profiles/r06_h2d.md), and whichever
-  // queue that is pays for the neighbour in every dispatch -- it must not be the main stream's
+  // the streams of k_lk_templates_ahead, at the lowest priority, created LAST and behind two idle streams: a fifth compute queue shares a
+  // pipe of the command processor with one of the first four (queue i sits on pipe i mod 4 in creation order, profiles/r06_h2d.md), and
+  // whichever queue that is pays for the neighbour in every dispatch -- it must not be the main stream's (profiles/r06_templates_ahead.md)
   {
-    int lo = 0, hi = 0;
-    hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (const char* e = getenv("FLVIS_TPL_PRIO")) lo = atoi(e);  // A/B knob
-    const int qpad = getenv("FLVIS_TPL_QPAD") ? std::max(0, std::min(atoi(getenv("FLVIS_TPL_QPAD")), 8)) : 2;
     bool any = false;
     for (Lane* L : pl->lanes) any = any || L->pipe.tpl_ahead;
-    for (int k = 0; k < qpad && ok && any; k++) {
+    for (int k = 0; k < 2 && ok && any; k++) {
       hipStream_t ps = nullptr;
-      ok = hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, lo) == hipSuccess;
+      ok = hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, prio_least) == hipSuccess;
       if (ok) {
         pl->pad_streams.push_back(ps);
         launch_store_progress(ps, pl->lanes[0]->d_progress + 1, 0);  // (a scratch word: the stream gets its hardware queue)
       }
     }
     for (Lane* L : pl->lanes)
-      if (ok && L->pipe.tpl_ahead) ok = hipStreamCreateWithPriority(&L->tpl_stream, hipStreamNonBlocking, lo) == hipSuccess;
+      if (ok && L->pipe.tpl_ahead) ok = hipStreamCreateWithPriority(&L->tpl_stream, hipStreamNonBlocking, prio_least) == hipSuccess;
   }
   if (!ok) {
     flvis_pipeline_destroy_internal(ctx);
@@ -1086,23 +1068,20 @@ static void fill_pyr(Pipeline* pl, PyrSel& ps, uint8_t* const* l0, uint8_t* cons
 // written by the kernel that produces the level wherever it can; the return value is the mask of the levels whose border is still to
 // fill (k_pyr_border).  level0_todo: level 0 has a border that nobody has written yet (equalizeHist / the unaligned copy made it).
 // Walking kernels (pyr_walk.hip) where the geometry allows -- 16-pixel lanes: widths that are multiples of 16 up to 1024 --, else the
-// LDS-tile kernels level by level.  FLVIS_PYR_PLAN (A/B knob): levels per walking launch, first launch first ("12": default).
+// LDS-tile kernels level by level.
 static unsigned pyramid_levels(hipStream_t ds, bool bordered, ImgSel src0, int spitch0, size_t sstride0, bool ingest, bool level0_is_buffer,
                                const PyrSel& pyr, int S, const int* active) {
   const int levels = pyr.levels;
   unsigned border_left = bordered ? (1u << (levels + 1)) - 1u : 0u;
   if (!level0_is_buffer && !ingest) border_left &= ~1u;  // (level 0 is the caller's buffer: no border to fill)
-  static const char* plan_env = getenv("FLVIS_PYR_PLAN");
-  // default: one level, then two ("12": the fastest for 640-pixel rows, profiles/r04_lk_ab.md) -- unless level 1 is not a whole number of
-  // 16-pixel lanes while level 0 is (752-pixel rows: 376): then the first launch takes two levels ("21") and only the last one is left
-  // to the tile kernels
-  const char* plan = plan_env && *plan_env ? plan_env : ((pyr.w[0] & 15) == 0 && (((pyr.w[0] + 1) >> 1) & 15) != 0 ? "21" : "12");
+  // levels per walking launch: one, then two ("12": the fastest for 640-pixel rows; other plans: profiles/r04_lk_ab.md) -- unless level 1
+  // is not a whole number of 16-pixel lanes while level 0 is (752-pixel rows: 376): then the first launch takes two levels ("21") and only
+  // the last one is left to the tile kernels
+  const char* plan = (pyr.w[0] & 15) == 0 && (((pyr.w[0] + 1) >> 1) & 15) != 0 ? "21" : "12";
   int step = 0, l = 0;
   while (l < levels) {
     int nout = plan[step] ? plan[step] - '0' : 1;
     if (plan[step]) step++;
-    if (nout < 1) nout = 1;
-    if (nout > 3) nout = 3;
     if (nout > levels - l) nout = levels - l;
     const bool from0 = l == 0 && (ingest || !level0_is_buffer);
     ImgSel src = from0 ? src0 : pyr.lvl[l];
@@ -1253,17 +1232,11 @@ static void sync_all(flvis_ctx* ctx) {
   }
 }
 
-// FLVIS_BA_START (see lane_frame)
-static int ba_start_knob() {
-  static const int ba_start = getenv("FLVIS_BA_START") ? atoi(getenv("FLVIS_BA_START")) : 2;
-  return ba_start;
-}
-
 // How many local-map launches back the tracking stream waits before it appends to the keyframe queues (lane_frame).  A reset command
 // (k_stream_reset) takes a queue entry like a keyframe: every lane frame with a command among the frames the bound counts moves the wait
 // one launch closer.  Without commands: the depth of rounds 1-6.
 static long long lane_backpressure_depth(Pipeline* pl, Lane* L) {
-  long long D = std::max(0, KFQ / 2 / pl->ba_every - 2 - (ba_start_knob() != 0 ? 1 : 0));  // (a deferred launch is one frame late)
+  long long D = std::max(0, KFQ / 2 / pl->ba_every - 3);  // (-2, and -1 because a deferred launch is one frame late)
   if (L->cmd_steps.empty()) return D;
   const long long window = (D + pl->nba_lane + 2) * pl->ba_every;
   std::vector<long long>& c = L->cmd_steps;
@@ -1289,8 +1262,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // then runs dry while the queue is refilled (measured)
   // (zero-copy inputs: k_frame_head publishes its progress word when it STARTS, while its other workgroups may still be reading the
   // slot -- one slot of slack, so that the slot the host refills belongs to a frame whose successor has started, i.e. that is over)
-  static const bool zc_lead = !(getenv("FLVIS_INPUT_ZEROCOPY") && atoi(getenv("FLVIS_INPUT_ZEROCOPY")) == 0);
-  const long long lead = std::min(std::min(pl->host_lead, pl->host_lead_cap), (int)Lane::PIN_RING - (zc_lead ? 1 : 0));
+  const long long lead = std::min(std::min(pl->host_lead, pl->host_lead_cap), (int)Lane::PIN_RING - 1);
   if (frame_no > lead && *L->h_progress < frame_no - lead) {
     const auto tw = std::chrono::steady_clock::now();
     int polls = 0;
@@ -1318,14 +1290,11 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // a reset command appended since the lane's last frame (flvis_reset_streams / flvis_local_map_reset)
   const bool cmd_pending = L->cmd_since_frame;
   L->cmd_since_frame = false;
-  // (round 4, measured: uploading the block on the detection stream into a per-frame device slot -- so that k_frame_head(n + 1) follows
-  // k_frame_end(n) without the copy between them -- shortens the gap between two frames by ~19 us and lengthens the chain by ~16 us
-  // (1.1914 against 1.1943 ms per step): not kept.  profiles/r04_lk_ab.md)
-  // FLVIS_INPUT_ZEROCOPY (default 1): no copy at all -- k_frame_head reads the block where the host staged it (page-locked, mapped into
-  // the device's address space: a few KB per stream over PCIe, in parallel over the streams), and the image bases travel as kernel
-  // arguments.  A staging slot is rewritten PIN_RING frames later, when the frame that read it is long over (the host-lead wait above).
-  static const bool zerocopy_knob = !(getenv("FLVIS_INPUT_ZEROCOPY") && atoi(getenv("FLVIS_INPUT_ZEROCOPY")) == 0);
-  const bool zerocopy = zerocopy_knob && L->pinned_dev[pslot] != nullptr;
+  // No copy: k_frame_head reads the block where the host staged it (page-locked, mapped into the device's address space: a few KB per
+  // stream over PCIe, in parallel over the streams), and the image bases travel as kernel arguments.  A staging slot is rewritten PIN_RING
+  // frames later, when the frame that read it is long over (the host-lead wait above).  Copying forms: profiles/r04_lk_ab.md.  (The copy
+  // below only serves a runtime that maps no device pointer for the staging slot.)
+  const bool zerocopy = L->pinned_dev[pslot] != nullptr;
   L->h_tab[0] = d_img0, L->h_tab[1] = d_img1;
   p.in_img1 = d_img1;
   {
@@ -1343,15 +1312,10 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
 #define PE(i, strm) \
   if (prof && ((pl->prof_mask >> (i)) & 1ull)) hipEventRecord(pev[2 * (i) + 1], strm)
   PB(19, st);  // the whole main-stream chain of this frame: per-frame GPU latency (p50/p99 in bench.py)
-  // FLVIS_BA_START (round 5): where the local-map launch for the keyframes of frame n is enqueued.  A launch lasts ~1.4 ms, a frame 1.1 ms:
-  // for 0.3 ms of every frame TWO launches hold their workgroups' CUs (2 x ~31 of 256), for the rest one.  0: straight behind
-  // k_frame_end(n) -- the 0.3 ms are then the head of frame n + 1 and its temporal LK, a kernel that wants every CU.  1 / 2: inside frame
-  // n + 1, behind its F-RANSAC / its PnP RANSAC -- the 0.3 ms fall on the one-workgroup-per-stream kernels of the geometry chain.
-  // Measured (one box, two runs each): 57.80k / 57.86k frames/s with 0, 58.03k / 58.21k with 1 (the 0.3 ms then fall on the corner response,
-  // which is on the critical path of the detection stream), 58.74k / 58.58k with 2 (default; temporal LK 0.212 -> 0.196 ms, frame chain
-  // p50 1.065 -> 1.048 ms).  Only between the steps of one flvis_run_steps call -- the next frame is known to follow at once; a
-  // per-frame caller (the ROS wrapper) gets its local-map launch when its frame ends, as before, and so does the last step of a batch.
-  const int ba_start = ba_start_knob();
+  // The local-map launch for the keyframes of frame n is enqueued inside frame n + 1, behind its PnP RANSAC, where the ~0.3 ms in which two
+  // launches hold CUs fall on the one-workgroup-per-stream geometry kernels (other placements: profiles/r05_local_map_cost.md).  Only
+  // between the steps of one flvis_run_steps call -- the next frame is known to follow at once; a per-frame caller (the ROS wrapper) gets
+  // its local-map launch when its frame ends, and so does the last step of a batch.
   hipEvent_t* prof18 = (prof && ((pl->prof_mask >> 18) & 1ull)) ? &pev[2 * 18] : nullptr;
   const bool skipped = pl->frames_fed < (long long)pl->cfg.skip_first_n_imgs;
   const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;  // the second image is the Z16 depth map, read in place
@@ -1359,17 +1323,8 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // rows of whole 16-byte lanes at 16-byte aligned bases (the walking kernels' dwordx4 loads); otherwise (KITTI: 1241 x 376 tightly packed
   // rows, or a caller's buffer at an odd offset) both images are copied into pitch-aligned level 0
   const bool aligned = (w & 15) == 0 && !(((uintptr_t)d_img0 | (depth_cam ? (uintptr_t)0 : (uintptr_t)d_img1)) & 15);
+  // the left image on the detection stream, k_frame_head on the main one (the two swapped: profiles/r05_local_map_cost.md)
   hipStream_t ds = L->det_stream;
-  // FLVIS_HEAD_STREAM=1 (round 5, A/B knob): the two halves of the frame's head change streams -- the left pyramid on the MAIN stream,
-  // straight behind k_frame_end of the previous frame, k_frame_head on the detection stream; the temporal LK then waits for one event
-  // (the head's) instead of following the head and waiting for the pyramid's.  Only with the detection behind the F-RANSAC (modes >= 2).
-  // Measured (one box, two runs each): 57.1k / 57.3k frames/s against 57.3k / 57.4k; the temporal LK starts 75 us after the head either
-  // way -- the pyramid's two launches take 46 + 22 us beside the local map's workgroups (19 + 12 us alone), and they are what it waits for
-  static const bool head_stream_knob = getenv("FLVIS_HEAD_STREAM") && atoi(getenv("FLVIS_HEAD_STREAM")) == 1 &&
-                                       !(getenv("FLVIS_DET_START") && atoi(getenv("FLVIS_DET_START")) < 2) &&
-                                       !(getenv("FLVIS_DET_ORDER") && atoi(getenv("FLVIS_DET_ORDER")) == 0);
-  const bool head_on_det = head_stream_knob && !skipped;
-  hipStream_t s_img = head_on_det ? st : ds, s_head = head_on_det ? ds : st;
   ImgSel in0 = img_plain(d_img0), in1 = img_plain(d_img1);  // (kernel arguments: no graph is captured)
   ImgSel l0cur{{L->pyr0[0][0], L->pyr0[1][0]}, p.img_slot, 0, nullptr};
   if (!skipped) {
@@ -1389,42 +1344,40 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
       join_signal(pl, L, L->ev_lm, st);  // (the frame's input table has been uploaded)
       join_wait(pl, L, ds, L->ev_lm);
     }
-    // host images (flvis_image_feed_host, FLVIS_H2D_WAIT=1): the upload's event is waited for by the stream that ingests the left image; the
+    // host images (flvis_image_feed_host, single-lane stereo): the upload's signal is waited for by the stream that ingests the left image; the
     // main stream only sees the joins it has anyway (left pyramid in front of the temporal LK, right pyramid in front of the stereo LK)
     if (pl->up_event) hipStreamWaitEvent(ds, pl->up_event, 0);
     if (pl->up_flag) launch_wait_flag(ds, pl->up_flag, Pipeline::HostFeed::FLAG_WORDS, pl->up_seq, L->d_progress + 2);
-    PB(1, s_img);
-    if (eq) launch_equalize_hist(s_img, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, nullptr);
-    else if (!aligned) launch_copy_image_any(s_img, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
-    PE(1, s_img);
-    PB(2, s_img);
+    PB(1, ds);
+    if (eq) launch_equalize_hist(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, nullptr);
+    else if (!aligned) launch_copy_image_any(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
+    PE(1, ds);
+    PB(2, ds);
     // the borders of the levels: written by the pyrDown kernel that produces the level (every pixel also goes to the border positions
     // that mirror it); k_pyr_border only for what is left (level 0 when another kernel makes it, levels smaller than the border)
     PyrSel pyl;
     fill_pyr(pl, pyl, L->pyr0[0], L->pyr0[1], p.img_slot_in, 0, pl->levels);
-    unsigned border_left = pyramid_levels(s_img, pl->lbx != 0, in0, w, (size_t)w * h, !eq && aligned, true, pyl, S, nullptr);
-    if (pl->levels == 0 && !eq && aligned) launch_copy_image(s_img, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
-    if (border_left) launch_pyr_border(s_img, pyl, S, nullptr, border_left);
-    PE(2, s_img);
-    if (!head_on_det) join_signal(pl, L, L->ev_img, ds);
+    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in0, w, (size_t)w * h, !eq && aligned, true, pyl, S, nullptr);
+    if (pl->levels == 0 && !eq && aligned) launch_copy_image(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
+    if (border_left) launch_pyr_border(ds, pyl, S, nullptr, border_left);
+    PE(2, ds);
+    join_signal(pl, L, L->ev_img, ds);
   }
-  PB(0, s_head);
+  PB(0, st);
   // the staged IMU samples, then frame_begin -- and, unless the local-map feedback has to be applied in between, the temporal tracker's
   // inputs in the same launch (FLVIS_HEAD_PREPARE=0, A/B knob: two launches)
-  static const bool head_prepare_knob = !(getenv("FLVIS_HEAD_PREPARE") && atoi(getenv("FLVIS_HEAD_PREPARE")) == 0);
-  const bool head_prepare = head_prepare_knob && !pl->feedback_used && !skipped;
+  const bool head_prepare = pl->head_prepare && !pl->feedback_used && !skipped;
   const bool head_signals = !pl->feedback_used && fold_signal(pl, L, L->ev_head, p.kj);  // (the head kernel is the last one in front of the signal)
   // ... and it does not end before the left pyramid is there (the temporal LK follows it, directly or behind k_track_prepare)
-  const bool head_posts = !skipped && !head_on_det && fold_post(pl, L, L->ev_img, p.kj);
-  if (head_prepare) launch_frame_head_prepare(s_head, p, L->d_time, L->d_progress, frame_no);
-  else launch_frame_head(s_head, p, L->d_time, L->d_progress, frame_no);
+  const bool head_posts = !skipped && fold_post(pl, L, L->ev_img, p.kj);
+  if (head_prepare) launch_frame_head_prepare(st, p, L->d_time, L->d_progress, frame_no);
+  else launch_frame_head(st, p, L->d_time, L->d_progress, frame_no);
   p.kj = KJoin{};
-  if (pl->feedback_used) launch_apply_correction(s_head, p);  // STEP1 of the Tracking case (local-map feedback, opt-in)
-  PE(0, s_head);
+  if (pl->feedback_used) launch_apply_correction(st, p);  // STEP1 of the Tracking case (local-map feedback, opt-in)
+  PE(0, st);
   // the detection stream's kernels that read what k_frame_head decides (act_img, gftt_act, gftt_maxc, img_slot) wait for this event:
-  // the corner detection and the right pyramid in every FLVIS_DET_START mode (in the default mode they start behind the F-RANSAC anyway)
-  if (!head_signals) join_signal(pl, L, L->ev_head, s_head);
-  if (head_on_det) join_wait(pl, L, st, L->ev_head);  // join: the head (the left pyramid is on this stream)
+  // the corner detection and the right pyramid (they start behind the F-RANSAC anyway)
+  if (!head_signals) join_signal(pl, L, L->ev_head, st);
   if (skipped) {
     // the reference drops the first skip_first_n_imgs frames before any processing (vo_tracking.cpp image callback): every
     // stream is idle for this frame, so only the IMU filter, the frame counter and the per-frame outputs are advanced
@@ -1445,78 +1398,19 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // lanes out of phase: a lane's first processed frame starts when the previous lane has finished the temporal LK of its own, so
   // that from then on the image kernels of one lane overlap the one-workgroup-per-stream geometry chain of another
   const bool first_processed = pl->frames_fed == (long long)pl->cfg.skip_first_n_imgs;
-  if (first_processed && pl->stagger && L->idx > 0) hipStreamWaitEvent(st, pl->lanes[L->idx - 1]->ev_stagger, 0);
+  if (first_processed && L->idx > 0) hipStreamWaitEvent(st, pl->lanes[L->idx - 1]->ev_stagger, 0);
   // (the guesses of the temporal tracker only need the state frame_begin left)
   PB(3, st);
   if (!head_prepare) launch_track_prepare(st, p);
   PE(3, st);
-  if (!head_on_det && !head_posts) join_wait(pl, L, st, L->ev_img);  // join: the left pyramid
-  // fork: the right pyramid (first used by the stereo matcher) and the corner detection of the new left image (speculative
-  // for tracking frames: used only if tracking succeeds) run beside the temporal tracking chain.  The right image is only
-  // read within this frame, so without equalizeHist the caller's buffer IS level 0 of the right pyramid (no copy).
+  if (!head_posts) join_wait(pl, L, st, L->ev_img);  // join: the left pyramid
   // The right image is only read within this frame: without equalizeHist the caller's buffer IS level 0 of the right pyramid (no copy;
   // that level then has no border, and the few stereo search regions that leave the image at level 0 are staged by the kernel's
-  // index-reflecting path).  FLVIS_RIGHT_COPY=1 (A/B knob): a bordered copy instead, written by the first pyrDown.
-  static const bool right_copy = getenv("FLVIS_RIGHT_COPY") && atoi(getenv("FLVIS_RIGHT_COPY")) != 0;
-  const bool r_in_place = !eq && aligned && !(pl->lbx && right_copy);
+  // index-reflecting path; a bordered copy: DESIGN.md section 4).
+  const bool r_in_place = !eq && aligned;
   ImgSel r0 = r_in_place ? in1 : img_plain(L->pyr1[0]);
   const int r0pitch = r_in_place ? w : pl->lpitch[0];
   const size_t r0stride = r_in_place ? (size_t)w * h : pl->lstride[0];
-  // order on the detection stream: the corner response first (FeatureDEM waits for it at the join; it then overlaps the
-  // temporal LK instead of the one-workgroup-per-stream RANSAC kernels it would slow down), the right pyramid after it (only
-  // the stereo matcher needs it, much later).  FLVIS_DET_ORDER=0 restores the round-1 order (A/B knob).
-  static const bool gftt_first = !(getenv("FLVIS_DET_ORDER") && atoi(getenv("FLVIS_DET_ORDER")) == 0);
-  // FLVIS_DET_START (A/B knob) = where the detection stream's work starts: 0 beside the temporal LK (rounds 1-2), 1 when the LK has
-  // finished, 2 when the F-RANSAC has finished, 3 (default) like 2 with the right pyramid behind the corner detection.  Measured in one
-  // session (64 streams, local map on): 0: 1.643 ms/step (the LK is stretched from 0.40 to 0.45 ms by the corner response and the
-  // pyramid kernels), 1: 1.721 (k_ransac_f, 1024 threads per stream, goes from 0.07 to 0.18 ms under k_eig_walk), 2: 1.622, 3: 1.602:
-  // k_ransac_pnp / k_pose_lm / k_reproj_filter are latency chains on 64 CUs and leave the rest of the chip to the detection.
-  static const int gftt_after_lk = getenv("FLVIS_DET_START") ? atoi(getenv("FLVIS_DET_START")) : 3;
-  auto detect_corners = [&] {
-    if (!head_on_det) join_wait(pl, L, ds, L->ev_head);
-    launch_gftt(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, L->gftt, nullptr, p.cam.gftt_ql, p.gftt_maxc, p.cam.gftt_num,
-                (double)p.cam.gftt_dis, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num, p.gftt_act,
-                (prof && ((pl->prof_mask >> 10) & 7ull) == 7ull) ? &pev[2 * 10] : nullptr, false);
-    // FeatureDEM's image part (regions, Harris scores, per-region order of the corners) follows at once, off the critical path
-    KJoin prep_kj{};
-    const bool prep_signals = fold_signal(pl, L, L->ev_gftt, prep_kj);
-    launch_feature_dem_prep(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, p.cam.dem, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num,
-                            p.gftt_act, L->dem_sorted, L->dem_roff, &prep_kj);
-    if (!prep_signals) join_signal(pl, L, L->ev_gftt, ds);
-  };
-  if (gftt_first && !gftt_after_lk) detect_corners();
-  auto right_pyramid_on = [&](hipStream_t ds, bool on_main) {  // (ds: the stream it runs on -- the detection stream, or the main one)
-    if (!on_main && !head_on_det) join_wait(pl, L, ds, L->ev_head);
-    if (!depth_cam) {
-      if (eq) launch_equalize_hist(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, p.act_img);
-      else if (!aligned) launch_copy_image_any(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, p.act_img);
-      const bool ingest = !r_in_place && !eq && aligned;  // level 0 = a copy of the caller's image, written by the first pyrDown
-      PyrSel pyr_r;
-      fill_pyr(pl, pyr_r, L->pyr1, nullptr, nullptr, 0, pl->levels);
-      unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in1, w, (size_t)w * h, ingest, !r_in_place, pyr_r, S, p.act_img);
-      if (pl->levels == 0 && ingest)
-        launch_copy_image(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, p.act_img);
-      if (border_left) launch_pyr_border(ds, pyr_r, S, p.act_img, border_left);
-    }
-    if (!gftt_first) {
-      launch_gftt(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, L->gftt, nullptr, p.cam.gftt_ql, p.gftt_maxc, p.cam.gftt_num,
-                  (double)p.cam.gftt_dis, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num, p.gftt_act,
-                  (prof && ((pl->prof_mask >> 10) & 7ull) == 7ull) ? &pev[2 * 10] : nullptr, false);
-      launch_feature_dem_prep(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, p.cam.dem, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num,
-                              p.gftt_act, L->dem_sorted, L->dem_roff);
-    }
-    if (!on_main) join_signal(pl, L, L->ev_det, ds);
-  };
-  auto right_pyramid = [&] { right_pyramid_on(ds, false); };
-  // 5 (round 5, A/B knob): the corners as in 3; the right pyramid -- two light launches, 36 us -- on the MAIN stream behind the reprojection
-  // filter, where that stream waits ~50 us for the corner detection anyway, and no join in front of the stereo LK.  Measured (two runs
-  // each, one box): 56.2k / 56.4k frames/s against 56.6k / 56.7k for 3 -- the stereo LK stage does not get shorter: not adopted
-  const bool pyramid_main = gftt_first && gftt_after_lk == 5;
-  const bool pyramid_late = gftt_first && gftt_after_lk == 3;  // 3: the right pyramid waits for the F-RANSAC too
-  // 4 (round 4): like 3 for the corners, but the right pyramid -- a light, memory-bound pass that only the stereo matcher needs -- runs
-  // when the temporal LK has finished, beside the F-RANSAC, instead of behind the corner detection where the stereo LK waited for it
-  const bool pyramid_mid = gftt_first && gftt_after_lk == 4;
-  if (!pyramid_late && !pyramid_mid && !pyramid_main) right_pyramid();
   // temporal tracking
   PB(4, st);
   {
@@ -1535,20 +1429,9 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
       prm.tc_tag = p.lk_tag;
     }
     prm.dbg_slot = (int)(pl->frames_fed & 7);
-    prm.order = pl->lk_order & 1;
     launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, prm, p.act_track, pl->max_pts, 1);
   }
   PE(4, st);
-  if (gftt_first && gftt_after_lk == 1) {
-    join_signal(pl, L, L->ev_lm, st);
-    join_wait(pl, L, ds, L->ev_lm);
-    detect_corners();
-  }
-  if (pyramid_mid) {
-    join_signal(pl, L, L->ev_lm, st);
-    join_wait(pl, L, ds, L->ev_lm);
-    right_pyramid();
-  }
   // templates ahead of the stereo matcher (lane_create: FLVIS_TPL_AHEAD): the survivors' pixels are known when k_track_collect has run.
   // FLVIS_TPL_START (A/B knob): 1 (default) the kernel starts with the corner detection, behind the F-RANSAC, on that join's word;
   // 0 behind k_track_collect, beside the F-RANSAC, on a word of its own (one more one-lane launch on the chain)
@@ -1575,20 +1458,40 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   }
   if (first_processed && pl->lanes.size() > 1) hipEventRecord(L->ev_stagger, st);
   PB(6, st);
-  const bool rf_signals = gftt_first && gftt_after_lk >= 2 && fold_signal(pl, L, L->ev_lm, p.kj);
+  const bool rf_signals = fold_signal(pl, L, L->ev_lm, p.kj);
   launch_ransac_f(st, p, merge_collect);
   p.kj = KJoin{};
   PE(6, st);
-  if (gftt_first && gftt_after_lk >= 2) {
-    if (!rf_signals) join_signal(pl, L, L->ev_lm, st);
-    if (p.tpl_ahead && tpl_start == 1) templates_ahead();
-    join_wait(pl, L, ds, L->ev_lm);
-    detect_corners();
-    if (pyramid_late) right_pyramid();
-    if (ba_start == 1 && L->ba_pending) launch_local_map(pl, L, L->ev_lm, false, prof18);
+  if (!rf_signals) join_signal(pl, L, L->ev_lm, st);
+  if (p.tpl_ahead && tpl_start == 1) templates_ahead();
+  // fork, behind the F-RANSAC: the corner detection of the new left image (speculative for tracking frames: used only if tracking
+  // succeeds), then the right pyramid (first used by the stereo matcher), on the detection stream beside the PnP RANSAC / pose
+  // optimisation -- latency chains on 64 CUs that leave the rest of the chip to the detection (other placements and orders:
+  // profiles/r03_stream_structure_ab.md)
+  join_wait(pl, L, ds, L->ev_lm);
+  join_wait(pl, L, ds, L->ev_head);
+  launch_gftt(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, L->gftt, nullptr, p.cam.gftt_ql, p.gftt_maxc, p.cam.gftt_num,
+              (double)p.cam.gftt_dis, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num, p.gftt_act,
+              (prof && ((pl->prof_mask >> 10) & 7ull) == 7ull) ? &pev[2 * 10] : nullptr, false);
+  {  // FeatureDEM's image part (regions, Harris scores, per-region order of the corners) follows at once, off the critical path
+    KJoin prep_kj{};
+    const bool prep_signals = fold_signal(pl, L, L->ev_gftt, prep_kj);
+    launch_feature_dem_prep(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, p.cam.dem, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num,
+                            p.gftt_act, L->dem_sorted, L->dem_roff, &prep_kj);
+    if (!prep_signals) join_signal(pl, L, L->ev_gftt, ds);
   }
+  join_wait(pl, L, ds, L->ev_head);
+  if (!depth_cam) {
+    if (eq) launch_equalize_hist(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, p.act_img);
+    else if (!aligned) launch_copy_image_any(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, p.act_img);
+    PyrSel pyr_r;
+    fill_pyr(pl, pyr_r, L->pyr1, nullptr, nullptr, 0, pl->levels);
+    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in1, w, (size_t)w * h, false, !r_in_place, pyr_r, S, p.act_img);
+    if (border_left) launch_pyr_border(ds, pyr_r, S, p.act_img, border_left);
+  }
+  join_signal(pl, L, L->ev_det, ds);
   PB(7, st);
-  const bool ba_here = ba_start == 2 && L->ba_pending;
+  const bool ba_here = L->ba_pending;
   const bool pnp_signals = ba_here && fold_signal(pl, L, L->ev_fe, p.kj);  // (the deferred local-map launch starts behind this kernel)
   launch_ransac_pnp(st, p);
   p.kj = KJoin{};
@@ -1599,18 +1502,17 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   launch_pose_lm(st, p);  // (with k_track_post's work in its prologue)
   PE(8, st);
   PB(9, st);
-  const bool rp_signals = !pyramid_main && fold_signal(pl, L, L->ev_lm, p.kj);
+  const bool rp_signals = fold_signal(pl, L, L->ev_lm, p.kj);
   launch_reproj_filter(st, p);
   p.kj = KJoin{};
   PE(9, st);
-  if (pyramid_main) right_pyramid_on(st, true);
   // the IMU filter's correction from this frame's pose: on the detection stream (joined with the triangulation before the depth innovation)
   if (!rp_signals) join_signal(pl, L, L->ev_lm, st);
   join_wait(pl, L, ds, L->ev_lm);
   launch_vi_correction(ds, p);
   // join: FeatureDEM (init: detect, tracking: redetect) consumes the corners; the right pyramid is joined before the stereo LK
   KJoin dem_kj{};
-  if (!fold_wait(pl, L, gftt_first ? L->ev_gftt : L->ev_det, dem_kj, 0)) join_wait(pl, L, st, gftt_first ? L->ev_gftt : L->ev_det);
+  if (!fold_wait(pl, L, L->ev_gftt, dem_kj, 0)) join_wait(pl, L, st, L->ev_gftt);
   PB(13, st);
   launch_feature_dem(st, w, h, S, p.cam.dem, L->dem_sorted, L->dem_roff, 2 * p.cam.gftt_num, p.det_mode, p.exist_xy, p.n_exist, NMAX,
                      p.new_xy, p.n_new, NEW_MAX, &dem_kj);
@@ -1629,7 +1531,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // XCD's L2, and beside the stereo LK's template stores the kernels doubled their time: 5.9 -> 12.7 us, 87 -> 180 us)
   const bool ds_signals = an_signals;
   // ... and k_depth_seeds does not end before the right pyramid is there (the stereo LK follows it)
-  const bool seeds_post = gftt_first && !pyramid_main && fold_post(pl, L, L->ev_det, p.kj);
+  const bool seeds_post = fold_post(pl, L, L->ev_det, p.kj);
   // ... and with templates ahead it looks them up: they must be there
   if (p.tpl_ahead && !fold_wait(pl, L, L->ev_tpl, p.kj, 0)) join_wait(pl, L, st, L->ev_tpl);
   if (merge_seeds) launch_add_new_seeds(st, p);
@@ -1639,10 +1541,9 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // the two-view triangulation that k_depth_innovate consumes: on the detection stream (idle by now), under the stereo LK
   if (!ds_signals) join_signal(pl, L, L->ev_lm, st);
   join_wait(pl, L, ds, L->ev_lm);
-  const bool tri_signals = false;
   launch_depth_triangulate(ds, p);
-  if (!tri_signals) join_signal(pl, L, L->ev_tri, ds);
-  if (gftt_first && !pyramid_main && !seeds_post) join_wait(pl, L, st, L->ev_det);
+  join_signal(pl, L, L->ev_tri, ds);
+  if (!seeds_post) join_wait(pl, L, st, L->ev_det);
   PB(15, st);
   if (!depth_cam) {
     PyrSel prev, next;
@@ -1664,7 +1565,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
       prm.tc_slot = p.lk_slot;
     }
     prm.dbg_slot = (int)(pl->frames_fed & 7);
-    prm.order = (pl->lk_order >> 1) & 1;
+    prm.order = 1;  // the frame's new landmarks, which have no depth to start from, first (profiles/r06_chain_ab.md)
     launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, prm, p.det_mode, pl->max_pts,
                     L->tc && p.tpl_ahead ? 4 : 2);
   }
@@ -1700,7 +1601,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   PE(19, st);
   if (with_local_map && (pl->frames_fed % pl->ba_every) == 0) {
     if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a deferred launch this frame had no place for: skipped frames)
-    if (ba_start != 0 && pl->defer_ba) L->ba_pending = true;
+    if (pl->defer_ba) L->ba_pending = true;
     else if (L->endf_valid) launch_local_map(pl, L, L->ev_endf, false, prof18);  // (k_frame_end has stored the word itself)
     else launch_local_map(pl, L, L->ev_fe, true, prof18);
   } else if (!with_local_map) {
@@ -1789,13 +1690,7 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
   hipSetDevice(ctx->device);
   Pipeline::HostFeed& hf = pl->hf;
   if (!hf.strm) {
-    bool ok = true;
-    const int qpad = getenv("FLVIS_H2D_QPAD") ? std::max(0, std::min(atoi(getenv("FLVIS_H2D_QPAD")), 4)) : 0;
-    for (int k = 0; k < qpad && ok; k++) {
-      ok = hipStreamCreateWithFlags(&hf.pad_strm[k], hipStreamNonBlocking) == hipSuccess;
-      if (ok) launch_store_progress(hf.pad_strm[k], ctx->pipe->lanes[0]->d_progress + 1, 0);  // (a scratch word: the stream gets its hardware queue)
-    }
-    ok = ok && hipStreamCreateWithFlags(&hf.strm, hipStreamNonBlocking) == hipSuccess;
+    bool ok = hipStreamCreateWithFlags(&hf.strm, hipStreamNonBlocking) == hipSuccess;
     for (int k = 0; k < 2 && ok; k++)
       ok = hipEventCreateWithFlags(&hf.ev_done[k], pl->ev_flags) == hipSuccess &&
            hipEventCreateWithFlags(&hf.ev_free[k], pl->ev_flags) == hipSuccess && hipEventCreate(&hf.ev_t0[k]) == hipSuccess &&
@@ -1809,7 +1704,6 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
     hf.d_up = (long long*)dp;
     *hf.h_up = 0;
     hf.times.assign(S, 0.0);
-    if (const char* e = getenv("FLVIS_H2D_MODE")) hf.mode = atoi(e) == 1 ? 1 : 2;
     if (hf.mode == 2) {
       // (fine-grained device memory: the copy engine writes it past the XCDs' L2 caches, the waiting wave must never see a cached line)
       void* dfp = nullptr;
@@ -1909,17 +1803,8 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
     bool contiguous = true;  // one block [S][h][w*bpp]: a single copy
     for (int s = 0; s < S && contiguous; s++)
       contiguous = (size_t)im[s].pitch == row && im[s].data == im[0].data + (size_t)s * img_bytes;
-    // (FLVIS_H2D_CHUNK_MB, A/B knob of round 5, mode 1 only: the block in chunks with a tiny kernel between two of them -- the engine switch
-    // leaves the link idle for a few microseconds, a window for the command processor's own traffic.  Measured, lost: 32.6k frames/s at 4 and
-    // 8 MB, 22.7k at 2 MB against 28.7-37k in one piece: the uploads take longer and the chain is as long, profiles/r05_h2d.md)
-    static const size_t h2d_chunk = getenv("FLVIS_H2D_CHUNK_MB") ? (size_t)atoi(getenv("FLVIS_H2D_CHUNK_MB")) << 20 : 0;
-    if (contiguous && h2d_chunk && hf.mode == 1) {
-      const size_t total = img_bytes * S;
-      for (size_t off = 0; off < total && e == hipSuccess; off += h2d_chunk) {
-        e = hipMemcpyAsync(hf.raw[slot][c] + off, im[0].data + off, std::min(h2d_chunk, total - off), hipMemcpyHostToDevice, hf.strm);
-        if (off + h2d_chunk < total) launch_store_progress(hf.strm, hf.d_up + 1, (long long)off);  // (a scratch word beside the progress word)
-      }
-    } else if (contiguous) {
+    // (in one piece: chunked uploads were slower, profiles/r05_h2d.md)
+    if (contiguous) {
       e = hipMemcpyAsync(hf.raw[slot][c], im[0].data, img_bytes * S, hipMemcpyHostToDevice, hf.strm);
     } else {
       for (int s = 0; s < S && e == hipSuccess; s++)
@@ -1946,12 +1831,11 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
     launch_store_progress(hf.strm, hf.d_up, seq);
   }
   hipStream_t st = ctx->stream;
-  // Which stream waits for the uploads.  The detection stream, in front of the left image's ingest (mode 2, or mode 1 with FLVIS_H2D_WAIT=1):
-  // every reader of the staged images is ordered behind that stream already -- the left pyramid's join in front of the temporal LK, the
-  // right pyramid's in front of the stereo LK, which reads the right image in place.  Only for single-channel stereo input on a single
-  // lane past the skipped start-up frames; otherwise the main stream waits, in front of the frame (rounds 1-5: always).
-  static const int h2d_wait = getenv("FLVIS_H2D_WAIT") ? atoi(getenv("FLVIS_H2D_WAIT")) : -1;
-  const bool wait_on_det = (h2d_wait < 0 ? hf.mode == 2 : h2d_wait == 1) && ch0 == 1 && ch1 == 1 && !depth_cam && pl->lanes.size() == 1 &&
+  // Which stream waits for the uploads.  In mode 2 the detection stream, in front of the left image's ingest: every reader of the staged
+  // images is ordered behind that stream already -- the left pyramid's join in front of the temporal LK, the right pyramid's in front of
+  // the stereo LK, which reads the right image in place.  Only for single-channel stereo input on a single lane past the skipped start-up
+  // frames; otherwise, and in mode 1, the main stream waits, in front of the frame (rounds 1-5: always; profiles/r06_h2d.md).
+  const bool wait_on_det = hf.mode == 2 && ch0 == 1 && ch1 == 1 && !depth_cam && pl->lanes.size() == 1 &&
                            pl->frames_fed >= (long long)pl->cfg.skip_first_n_imgs;
   if (hf.mode == 2) {
     if (wait_on_det) pl->up_flag = hf.d_flag, pl->up_seq = seq;
@@ -1972,9 +1856,8 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
   }
   for (int s = 0; s < S; s++) hf.times[s] = h_img0[s].t;
   // one frame of lead in this mode: with two, the uploads' copies and events push the queued commands over what the HIP runtime
-  // accepts without blocking the caller for milliseconds (measured: 16k vs 28k frames/s when that happened mid-run)
-  static const int h2d_lead = getenv("FLVIS_H2D_LEAD") ? std::max(1, std::min(atoi(getenv("FLVIS_H2D_LEAD")), 4)) : 1;  // (A/B knob)
-  pl->host_lead_cap = h2d_lead;
+  // accepts without blocking the caller for milliseconds (measured: 16k vs 28k frames/s when that happened mid-run, profiles/r05_h2d.md)
+  pl->host_lead_cap = 1;
   const auto th2 = std::chrono::steady_clock::now();
   pl->chain_continuous = wait_on_det && hf.mode == 2 && hf.last_call_frame == pl->frames_fed;  // (the previous frame was this entry's too)
   const int rc = flvis_image_feed(ctx, d0, d1, hf.times.data(), h_out, with_local_map);
@@ -2041,8 +1924,7 @@ int flvis_prof_enable_stages(flvis_ctx* ctx, int max_steps, uint64_t stage_mask)
   pl->prof_cap = max_steps;
   pl->prof_step = 0;
   // release scope of the stage events (FLVIS_PROF_EVENT_SCOPE=agent|system; default: what the pipeline's own events use)
-  unsigned prof_scope = pl->ev_flags & hipEventReleaseToDevice;
-  if (const char* e = getenv("FLVIS_PROF_EVENT_SCOPE")) prof_scope = !strcmp(e, "agent") ? hipEventReleaseToDevice : 0u;
+  const unsigned prof_scope = pl->prof_scope;
   for (Lane* L : pl->lanes) {
     for (hipEvent_t e : L->prof_ev) hipEventDestroy(e);
     L->prof_ev.clear();
@@ -2081,7 +1963,7 @@ int flvis_prof_read(flvis_ctx* ctx, double* h_ms_per_stage, int* n_steps) {
           if (!L->prof18_rec[(size_t)k]) continue;
           rec18++;
         }
-        // (a stage that was not enqueued in this frame -- a deferred local-map launch, FLVIS_BA_START -- has no recorded events: it counts 0)
+        // (a stage that was not enqueued in this frame -- a deferred local-map launch (Pipeline::defer_ba) -- has no recorded events: it counts 0)
         if (hipEventElapsedTime(&ms, L->prof_ev[(size_t)k * (2 * PROF_STAGES) + 2 * i], L->prof_ev[(size_t)k * (2 * PROF_STAGES) + 2 * i + 1]) != hipSuccess) {
           (void)hipGetLastError();
           ms = 0;

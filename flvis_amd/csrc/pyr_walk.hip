@@ -327,13 +327,10 @@ void launch_pyr_walk(hipStream_t st, ImgSel src, int sw, int sh, int spitch, siz
     a.bx[j] = pyr.bx[first + j], a.by[j] = pyr.by[first + j];
   }
   a.active = active;
-  // rows of the last produced level per wave (A/B knobs; FLVIS_PYR_BAND: launches of one level, FLVIS_PYR_BAND2: of two)
-  static const int rows_env = getenv("FLVIS_PYR_BAND") ? atoi(getenv("FLVIS_PYR_BAND")) : 0;
-  static const int rows_env2 = getenv("FLVIS_PYR_BAND2") ? atoi(getenv("FLVIS_PYR_BAND2")) : 0;
+  // rows of the last produced level per wave: 4 in a launch of one level, 2 in one of two or three (other bands: profiles/r04_lk_ab.md)
   int hl = sh;
   for (int j = 0; j < nout; j++) hl = (hl + 1) >> 1;
-  static const int rows_env3 = getenv("FLVIS_PYR_BAND3") ? atoi(getenv("FLVIS_PYR_BAND3")) : 0;
-  a.rows_per_band = nout == 1 ? (rows_env > 0 ? rows_env : 4) : nout == 2 ? (rows_env2 > 0 ? rows_env2 : 2) : (rows_env3 > 0 ? rows_env3 : 2);
+  a.rows_per_band = nout == 1 ? 4 : 2;
   const int bands = (hl + a.rows_per_band - 1) / a.rows_per_band;
   const dim3 grid((bands + 3) / 4, S), block(256);
   if (nout == 1) {

@@ -387,7 +387,7 @@ def test_host_feed_without_readback_equals_the_resident_run(ctx, hold):
 
 def test_run_steps_batches_equal_frame_by_frame_feeds(ctx):
     """flvis_run_steps (what bench.py times) against flvis_imu_feed_all + flvis_image_feed frame by frame, local map on: between the
-    steps of a batch the local-map launch of a step is enqueued inside the NEXT step (FLVIS_BA_START, pipeline.cpp), the last step of
+    steps of a batch the local-map launch of a step is enqueued inside the NEXT step (Pipeline::defer_ba, pipeline.cpp), the last step of
     a batch launches at its end -- batches of 1, 2 and many steps, back to back without a synchronise, must leave the same
     trajectories, landmarks, CorrectionInf and counters, bit for bit."""
     import flvis_amd
