@@ -11,6 +11,7 @@ from . import build as _build
 _LIB = None
 
 FLVIS_OK = 0
+FLVIS_ERR_INVALID_ARG = -1
 FLVIS_ERR_NO_DEVICE = -2
 
 
@@ -777,14 +778,29 @@ class Tracker:
             raise FlvisError("write_imu_trajectory failed (%d)" % n)
         return n
 
-    def image_feed(self, img0, img1, times, want_out=True, with_local_map=True):
-        """img0/img1: uint8 cuda tensors [S,H,W]; times: sequence of S floats."""
+    def _presence(self, present, shape):
+        """present (sequence of truth values, `shape`) as the uint8 array the _present entry points take, or None for None."""
+        if present is None:
+            return None
+        pr = (self.np.asarray(present) != 0).astype(self.np.uint8)
+        assert pr.shape == shape, "present must have shape %s" % (shape,)
+        return self.np.ascontiguousarray(pr)
+
+    def image_feed(self, img0, img1, times, want_out=True, with_local_map=True, present=None):
+        """img0/img1: uint8 cuda tensors [S,H,W]; times: sequence of S floats.  present (optional, S truth values): only the streams
+        marked present have a frame in this step (flvis_image_feed_present); None: all of them."""
         np = self.np
         assert img0.is_cuda and img0.is_contiguous() and img1.is_contiguous() and img0.shape[0] == self.S
         t = np.ascontiguousarray(times, np.float64)
         out = C.cast(self._out, C.c_void_p) if want_out else C.c_void_p(0)
-        self.ctx._check(self.lib.flvis_image_feed(self.ctx._h, _ptr(img0), _ptr(img1), _P(t, C.c_double), out,
-                                                  int(with_local_map)), "image_feed")
+        pr = self._presence(present, (self.S,))
+        if pr is None:
+            rc = self.lib.flvis_image_feed(self.ctx._h, _ptr(img0), _ptr(img1), _P(t, C.c_double), out, int(with_local_map))
+        else:
+            self.lib.flvis_image_feed_present.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            rc = self.lib.flvis_image_feed_present(self.ctx._h, _ptr(img0), _ptr(img1), _P(t, C.c_double), pr.ctypes.data, out,
+                                                   int(with_local_map))
+        self.ctx._check(rc, "image_feed")
         if not want_out:
             return None
         res = []
@@ -795,10 +811,11 @@ class Tracker:
                             reprojection_error=o.reprojection_error))
         return res
 
-    def run_steps(self, steps, with_local_map=True):
+    def run_steps(self, steps, with_local_map=True, present=None):
         """flvis_run_steps: a batch of frames whose images are already in HBM, one C call (what bench.py times).  steps: a sequence of
         (img0, img1, times[, imu_counts, imu_samples]) -- uint8 cuda tensors [S,H,W], S floats, and optionally the IMU samples of the
-        step for all streams (int32 [S], float64 [S, n, 7]).  The tensors must stay alive until the context is synchronised."""
+        step for all streams (int32 [S], float64 [S, n, 7]).  The tensors must stay alive until the context is synchronised.
+        present (optional, [n_steps][S] truth values): the streams that have a frame in each step (flvis_run_steps_present)."""
         np = self.np
 
         class Step(C.Structure):
@@ -818,9 +835,15 @@ class Tracker:
                 assert cnt.shape == (self.S,) and smp.ndim == 3 and smp.shape[0] == self.S and smp.shape[2] == 7
                 keep += [cnt, smp]
                 arr[j].h_imu_counts, arr[j].h_imu_samples, arr[j].imu_samples_per_stream = cnt.ctypes.data, smp.ctypes.data, smp.shape[1]
-        self.lib.flvis_run_steps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        self.ctx._check(self.lib.flvis_run_steps(self.ctx._h, len(steps), C.cast(arr, C.c_void_p), int(with_local_map), C.c_void_p(0)),
-                        "run_steps")
+        pr = self._presence(present, (len(steps), self.S))
+        if pr is None:
+            self.lib.flvis_run_steps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+            rc = self.lib.flvis_run_steps(self.ctx._h, len(steps), C.cast(arr, C.c_void_p), int(with_local_map), C.c_void_p(0))
+        else:
+            self.lib.flvis_run_steps_present.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+            rc = self.lib.flvis_run_steps_present(self.ctx._h, len(steps), C.cast(arr, C.c_void_p), pr.ctypes.data, int(with_local_map),
+                                                  C.c_void_p(0))
+        self.ctx._check(rc, "run_steps")
 
     def _frame_outs(self):
         np = self.np
@@ -829,17 +852,22 @@ class Tracker:
                      dbg=np.array([o.of_inliers, o.f_inliers, o.pnp_inliers]),
                      reprojection_error=o.reprojection_error) for o in self._out]
 
-    def image_feed_host(self, imgs0, imgs1, times, want_out=True, with_local_map=True, hold_buffers=False):
+    def image_feed_host(self, imgs0, imgs1, times, want_out=True, with_local_map=True, hold_buffers=False, present=None):
         """flvis_image_feed_host: the frame handed over as HOST images, the call a nodelet makes (vo_tracking.cpp:396-430).
         imgs0 / imgs1: one numpy array per stream, [H, W] (mono8; uint16 for the depth image of a depth rig) or [H, W, 3|4]
         (BGR / BGRA); rows may be padded (a strided view whose pixels are contiguous).  With hold_buffers the arrays must stay
-        untouched until the next call on this context has returned."""
+        untouched until the next call on this context has returned.  present (optional, S truth values): only the streams
+        marked present have a frame in this step (flvis_image_feed_host_present); an absent stream's images and time may be None
+        (handed over as NULL)."""
         np = self.np
         assert len(imgs0) == self.S and len(imgs1) == self.S
         a = (FlvisImage * self.S)()
         b = (FlvisImage * self.S)()
         for arr, imgs in ((a, imgs0), (b, imgs1)):
             for s, im in enumerate(imgs):
+                if im is None:  # (NULL data: legal for an absent stream only, the library checks)
+                    arr[s].t = float(times[s]) if times[s] is not None else 0.0
+                    continue
                 px = im.itemsize * (im.shape[2] if im.ndim == 3 else 1)
                 assert im.strides[1] == px and (im.ndim == 2 or im.strides[2] == im.itemsize), "pixels of a row must be contiguous"
                 arr[s].data = C.cast(im.ctypes.data, C.POINTER(C.c_uint8))
@@ -847,9 +875,16 @@ class Tracker:
                 arr[s].channels = im.shape[2] if im.ndim == 3 else 1
                 arr[s].t = float(times[s])
         out = C.cast(self._out, C.c_void_p) if want_out else C.c_void_p(0)
-        self.lib.flvis_image_feed_host.argtypes = [C.c_void_p, C.POINTER(FlvisImage), C.POINTER(FlvisImage), C.c_void_p, C.c_int, C.c_int]
-        self.ctx._check(self.lib.flvis_image_feed_host(self.ctx._h, a, b, out, int(with_local_map), int(hold_buffers)),
-                        "image_feed_host")
+        pr = self._presence(present, (self.S,))
+        if pr is None:
+            self.lib.flvis_image_feed_host.argtypes = [C.c_void_p, C.POINTER(FlvisImage), C.POINTER(FlvisImage), C.c_void_p, C.c_int,
+                                                       C.c_int]
+            rc = self.lib.flvis_image_feed_host(self.ctx._h, a, b, out, int(with_local_map), int(hold_buffers))
+        else:
+            self.lib.flvis_image_feed_host_present.argtypes = [C.c_void_p, C.POINTER(FlvisImage), C.POINTER(FlvisImage), C.c_void_p,
+                                                               C.c_void_p, C.c_int, C.c_int]
+            rc = self.lib.flvis_image_feed_host_present(self.ctx._h, a, b, pr.ctypes.data, out, int(with_local_map), int(hold_buffers))
+        self.ctx._check(rc, "image_feed_host")
         return self._frame_outs() if want_out else None
 
     def landmarks(self, stream, cap=2048):

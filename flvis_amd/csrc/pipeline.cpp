@@ -54,7 +54,7 @@ struct Lane {
   int* gftt_n = nullptr;
   unsigned* eq_hist = nullptr;
   uint8_t* eq_lut = nullptr;
-  // per-frame inputs of the lane, uploaded as ONE block: [times S][imu S*IMU_MAX*7][input image bases 2][n_imu S]
+  // per-frame inputs of the lane, uploaded as ONE block: [times S][imu S*IMU_MAX*7][input image bases 2][n_imu S][present S]
   uint8_t* d_inputs = nullptr;
   double* d_time = nullptr;
   const uint8_t** d_tab = nullptr;
@@ -69,7 +69,7 @@ struct Lane {
   void* pinned[PIN_RING] = {};      // page-locked staging of a frame's inputs (host view) ...
   uint8_t* pinned_dev[PIN_RING] = {};  // ... and the same memory as the device sees it (k_frame_head reads it in place)
   const uint8_t* h_tab[2] = {nullptr, nullptr};  // the image bases of the last frame fed (host copy of the table)
-  size_t in_off_imu = 0, in_off_tab = 0, in_off_n = 0;
+  size_t in_off_imu = 0, in_off_tab = 0, in_off_n = 0, in_off_pres = 0;
   // the slot of frame n may be refilled once frame n's upload is done: k_frame_head (the first kernel after the upload) stores the
   // frame number into this host-mapped word and the host polls it.  (hipEventSynchronize on an event recorded after the upload
   // returned only when EVERYTHING enqueued so far had finished -- measured: the host then slept through four queued frames and the
@@ -145,6 +145,7 @@ struct Pipeline {
   bool pnp_tail_cv = false;  // FLVIS_PNP_TAIL=cv
   unsigned prof_scope = 0;  // FLVIS_PROF_EVENT_SCOPE: release scope of the stage-timing events
   long long frames_fed = 0;
+  long long stream_frames = 0;  // stream-frames fed (flvis_get_counters [0]): frames_fed * S unless steps left streams absent
   std::vector<void*> allocs;  // context-level device allocations (host-feed staging)
   int prof_cap = 0, prof_step = 0;
   unsigned long long prof_mask = ~0ull;  // stages that record events (an event record costs a few us on the GPU queue)
@@ -572,8 +573,10 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   // per-frame input block
   const size_t off_imu = sizeof(double) * S, off_tab = off_imu + sizeof(double) * (size_t)S * IMU_MAX * 7,
                off_n = off_tab + 2 * sizeof(void*);
-  L->input_bytes = off_n + sizeof(int) * S;
-  L->in_off_imu = off_imu, L->in_off_tab = off_tab, L->in_off_n = off_n;
+  const size_t off_pres = off_n + sizeof(int) * S;
+  L->input_bytes = off_pres + sizeof(int) * S;
+  L->in_off_imu = off_imu, L->in_off_tab = off_tab, L->in_off_n = off_n, L->in_off_pres = off_pres;
+  p.present = nullptr;
   ok = ok && ((L->d_inputs = dalloc<uint8_t>(L->allocs, L->input_bytes)) != nullptr);
   if (ok) {
     L->d_time = reinterpret_cast<double*>(L->d_inputs);
@@ -1246,8 +1249,9 @@ static long long lane_backpressure_depth(Pipeline* pl, Lane* L) {
 
 // One frame of one lane: stages the lane's host inputs, uploads them as one block and enqueues the fixed kernel sequence
 // on the lane's streams.  d_img0 / d_img1 already point at the lane's first stream.
+// present: the lane's slice of the step's presence bytes (flvis_image_feed_present), nullptr when every stream has a frame.
 static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
-                       int with_local_map) {
+                       const uint8_t* present, int with_local_map) {
   Pipe& p = L->pipe;
   const int S = L->S;
   hipStream_t st = L->st;
@@ -1276,6 +1280,15 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   double* pi = pt + S;
   const uint8_t** ptab = (const uint8_t**)(pi + (size_t)S * IMU_MAX * 7);
   int* pn = (int*)(ptab + 2);
+  int* ppres = (int*)((uint8_t*)pin + L->in_off_pres);
+  // presence: the stream's word in the table (read by k_frame_head, k_frame_end and the left image's ingest); a lane whose streams all
+  // have a frame passes nullptr, the form of a plain flvis_image_feed
+  int n_present = S;
+  if (present) {
+    n_present = 0;
+    for (int s = 0; s < S; s++) n_present += (ppres[s] = present[s] ? 1 : 0);
+  }
+  const bool all_present = n_present == S, none_present = n_present == 0;
   memcpy(pt, h_times, sizeof(double) * S);
   // only the staged samples travel (the block keeps its layout: [S][IMU_MAX][7])
   int max_n = 0;
@@ -1302,6 +1315,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
     L->d_time = reinterpret_cast<double*>(din);
     p.imu_in = reinterpret_cast<double*>(din + L->in_off_imu);
     p.n_imu = reinterpret_cast<int*>(din + L->in_off_n);
+    p.present = all_present ? nullptr : reinterpret_cast<const int*>(din + L->in_off_pres);
   }
   if (!zerocopy) hipMemcpyAsync(L->d_inputs, pin, L->input_bytes, hipMemcpyHostToDevice, st);
   // ---- fixed kernel sequence
@@ -1318,6 +1332,10 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // its local-map launch when its frame ends, and so does the last step of a batch.
   hipEvent_t* prof18 = (prof && ((pl->prof_mask >> 18) & 1ull)) ? &pev[2 * 18] : nullptr;
   const bool skipped = pl->frames_fed < (long long)pl->cfg.skip_first_n_imgs;
+  // a step in which no stream of the lane has a frame runs as a skipped one (the IMU, and k_frame_end, which writes nothing for an absent
+  // stream) -- plus the local map, which goes on with the keyframes queued before.  (While frames_fed < skip_first_n_imgs every stream that
+  // has a frame is in its skip window, whichever steps it was absent from: the skipped form holds with presence too.)
+  const bool idle_step = skipped || none_present;
   const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;  // the second image is the Z16 depth map, read in place
   const bool eq = pl->cfg.need_equal_hist != 0;
   // rows of whole 16-byte lanes at 16-byte aligned bases (the walking kernels' dwordx4 loads); otherwise (KITTI: 1241 x 376 tightly packed
@@ -1327,11 +1345,11 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   hipStream_t ds = L->det_stream;
   ImgSel in0 = img_plain(d_img0), in1 = img_plain(d_img1);  // (kernel arguments: no graph is captured)
   ImgSel l0cur{{L->pyr0[0][0], L->pyr0[1][0]}, p.img_slot, 0, nullptr};
-  if (!skipped) {
+  if (!idle_step) {
     // left image -> level 0 of the slot this frame is going to use (+ the pyramid), on the detection stream BESIDE k_frame_head: the
     // slot was fixed when the previous frame ended (img_slot_in), so the image work does not wait for the IMU integration and the
-    // state machine (one thread per stream, 45 us).  Every stream's image is ingested, also that of a stream this frame leaves idle.
-    // Without equalizeHist the first pyrDown reads the caller's image and writes level 0 and level 1 in one pass; with it the
+    // state machine (one thread per stream, 45 us).  Every present stream's image is ingested, also that of a stream this frame leaves
+    // idle.  Without equalizeHist the first pyrDown reads the caller's image and writes level 0 and level 1 in one pass; with it the
     // equalised image is level 0.
     ImgSel l0in{{L->pyr0[0][0], L->pyr0[1][0]}, p.img_slot_in, 0, nullptr};
     // what the detection stream needs from the main one here is k_frame_end of the previous frame (the slot the image goes to) and, in
@@ -1349,27 +1367,29 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
     if (pl->up_event) hipStreamWaitEvent(ds, pl->up_event, 0);
     if (pl->up_flag) launch_wait_flag(ds, pl->up_flag, Pipeline::HostFeed::FLAG_WORDS, pl->up_seq, L->d_progress + 2);
     PB(1, ds);
-    if (eq) launch_equalize_hist(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, nullptr);
-    else if (!aligned) launch_copy_image_any(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
+    // (an absent stream's workgroups retire at once: its image is not read, the slots of its pyramid are not written)
+    const int* pg = p.present;
+    if (eq) launch_equalize_hist(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, pg);
+    else if (!aligned) launch_copy_image_any(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, pg);
     PE(1, ds);
     PB(2, ds);
     // the borders of the levels: written by the pyrDown kernel that produces the level (every pixel also goes to the border positions
     // that mirror it); k_pyr_border only for what is left (level 0 when another kernel makes it, levels smaller than the border)
     PyrSel pyl;
     fill_pyr(pl, pyl, L->pyr0[0], L->pyr0[1], p.img_slot_in, 0, pl->levels);
-    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in0, w, (size_t)w * h, !eq && aligned, true, pyl, S, nullptr);
-    if (pl->levels == 0 && !eq && aligned) launch_copy_image(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, nullptr);
-    if (border_left) launch_pyr_border(ds, pyl, S, nullptr, border_left);
+    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in0, w, (size_t)w * h, !eq && aligned, true, pyl, S, pg);
+    if (pl->levels == 0 && !eq && aligned) launch_copy_image(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, pg);
+    if (border_left) launch_pyr_border(ds, pyl, S, pg, border_left);
     PE(2, ds);
     join_signal(pl, L, L->ev_img, ds);
   }
   PB(0, st);
   // the staged IMU samples, then frame_begin -- and, unless the local-map feedback has to be applied in between, the temporal tracker's
   // inputs in the same launch (FLVIS_HEAD_PREPARE=0, A/B knob: two launches)
-  const bool head_prepare = pl->head_prepare && !pl->feedback_used && !skipped;
+  const bool head_prepare = pl->head_prepare && !pl->feedback_used && !idle_step;
   const bool head_signals = !pl->feedback_used && fold_signal(pl, L, L->ev_head, p.kj);  // (the head kernel is the last one in front of the signal)
   // ... and it does not end before the left pyramid is there (the temporal LK follows it, directly or behind k_track_prepare)
-  const bool head_posts = !skipped && fold_post(pl, L, L->ev_img, p.kj);
+  const bool head_posts = !idle_step && fold_post(pl, L, L->ev_img, p.kj);
   if (head_prepare) launch_frame_head_prepare(st, p, L->d_time, L->d_progress, frame_no);
   else launch_frame_head(st, p, L->d_time, L->d_progress, frame_no);
   p.kj = KJoin{};
@@ -1378,7 +1398,29 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   // the detection stream's kernels that read what k_frame_head decides (act_img, gftt_act, gftt_maxc, img_slot) wait for this event:
   // the corner detection and the right pyramid (they start behind the F-RANSAC anyway)
   if (!head_signals) join_signal(pl, L, L->ev_head, st);
-  if (skipped) {
+  // behind k_frame_end: the local-map launch for the lane (or, without a local map, the keyframe queues' drop); `timed`: stage 18's pair
+  auto local_map_tail = [&](hipEvent_t* p18, bool timed) {
+    if (with_local_map && (pl->frames_fed % pl->ba_every) == 0) {
+      if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a deferred launch this frame had no place for: skipped frames)
+      if (pl->defer_ba) L->ba_pending = true;
+      else if (L->endf_valid) launch_local_map(pl, L, L->ev_endf, false, p18);  // (k_frame_end has stored the word itself)
+      else launch_local_map(pl, L, L->ev_fe, true, p18);
+    } else if (!with_local_map) {
+      // without a local map nobody consumes the keyframe queue: drop what frame_end appended (and apply a reset command queued since the
+      // last frame: k_kfq_drop)
+      // (a reset command is applied to the window here: behind the lane's last local-map launch, so that no workgroup of it owns the window)
+      if (cmd_pending) {
+        if (L->ba_launches > 0) join_wait(pl, L, st, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
+        launch_kfq_drop(st, p);
+      } else hipMemcpyAsync(p.kfq_head, p.kfq_tail, sizeof(unsigned) * S, hipMemcpyDeviceToDevice, st);
+      if (timed) {
+        PB(18, st);
+        PE(18, st);
+        L->prof18_rec[(size_t)pl->prof_step] = 1;
+      }
+    }
+  };
+  if (idle_step) {
     // the reference drops the first skip_first_n_imgs frames before any processing (vo_tracking.cpp image callback): every
     // stream is idle for this frame, so only the IMU filter, the frame counter and the per-frame outputs are advanced
     PB(17, st);
@@ -1393,6 +1435,9 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
           PB(i, st);
           PE(i, st);
         }
+    // no stream of the lane has a frame: the keyframes queued before this step keep being optimised (the skip window's steps come before
+    // any keyframe)
+    if (!skipped) local_map_tail(nullptr, false);
     return;
   }
   // lanes out of phase: a lane's first processed frame starts when the previous lane has finished the temporal LK of its own, so
@@ -1599,25 +1644,7 @@ static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_i
   p.kj = KJoin{};
   PE(17, st);
   PE(19, st);
-  if (with_local_map && (pl->frames_fed % pl->ba_every) == 0) {
-    if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a deferred launch this frame had no place for: skipped frames)
-    if (pl->defer_ba) L->ba_pending = true;
-    else if (L->endf_valid) launch_local_map(pl, L, L->ev_endf, false, prof18);  // (k_frame_end has stored the word itself)
-    else launch_local_map(pl, L, L->ev_fe, true, prof18);
-  } else if (!with_local_map) {
-    // without a local map nobody consumes the keyframe queue: drop what frame_end appended (and apply a reset command queued since the
-    // last frame: k_kfq_drop)
-    // (a reset command is applied to the window here: behind the lane's last local-map launch, so that no workgroup of it owns the window)
-    if (cmd_pending) {
-      if (L->ba_launches > 0) join_wait(pl, L, st, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
-      launch_kfq_drop(st, p);
-    } else hipMemcpyAsync(p.kfq_head, p.kfq_tail, sizeof(unsigned) * S, hipMemcpyDeviceToDevice, st);
-    if (prof) {
-      PB(18, st);
-      PE(18, st);
-      L->prof18_rec[(size_t)pl->prof_step] = 1;
-    }
-  }
+  local_map_tail(prof18, prof);
 #undef PB
 #undef PE
 }
@@ -1626,8 +1653,19 @@ extern "C" {
 
 int flvis_image_feed(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
                      flvis_frame_out* h_out, int with_local_map) {
+  return flvis_image_feed_present(ctx, d_img0, d_img1, h_times, nullptr, h_out, with_local_map);
+}
+
+// h_present (may be NULL: every stream): the streams that have a frame in this step (include/flvis_hip.h)
+int flvis_image_feed_present(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times, const uint8_t* h_present,
+                             flvis_frame_out* h_out, int with_local_map) {
   if (!ctx || !ctx->pipe || !d_img0 || !d_img1 || !h_times) return FLVIS_ERR_INVALID_ARG;
   Pipeline* pl = ctx->pipe;
+  if (h_present) {
+    bool all = true;
+    for (int s = 0; s < pl->S && all; s++) all = h_present[s] != 0;
+    if (all) h_present = nullptr;  // (the plain step)
+  }
   hipSetDevice(ctx->device);
   const size_t img_px = (size_t)pl->cfg.image_width * pl->cfg.image_height;
   const size_t img1_bytes = img_px * (pl->cfg.cam_type == CAM_DEPTH ? 2 : 1);
@@ -1640,7 +1678,8 @@ int flvis_image_feed(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img
   if (multi) hipEventRecord(pl->ev_in, ctx->stream);
   for (Lane* L : pl->lanes) {
     if (multi) hipStreamWaitEvent(L->st, pl->ev_in, 0);
-    lane_frame(ctx, pl, L, d_img0 + (size_t)L->s0 * img_px, d_img1 + (size_t)L->s0 * img1_bytes, h_times + L->s0, with_local_map);
+    lane_frame(ctx, pl, L, d_img0 + (size_t)L->s0 * img_px, d_img1 + (size_t)L->s0 * img1_bytes, h_times + L->s0,
+               h_present ? h_present + L->s0 : nullptr, with_local_map);
     if (multi) {
       hipEventRecord(L->ev_end[pl->frames_fed % Lane::HOLD_RING], L->st);
       const long long rel = pl->frames_fed - pl->input_hold;
@@ -1651,6 +1690,11 @@ int flvis_image_feed(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img
   const bool prof = pl->prof_cap > 0 && pl->prof_step < pl->prof_cap;
   if (prof) pl->prof_step++;
   pl->frames_fed++;
+  if (h_present) {
+    for (int s = 0; s < pl->S; s++) pl->stream_frames += h_present[s] != 0;
+  } else {
+    pl->stream_frames += pl->S;
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ctx->hip_fail(e, "image_feed launch");
   if (h_out) {
@@ -1672,15 +1716,26 @@ int flvis_image_feed(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img
 // hand-over with plain structs.  Uploads run on a copy stream into double-buffered device staging.
 int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, flvis_frame_out* h_out,
                           int with_local_map, int hold_buffers) {
+  return flvis_image_feed_host_present(ctx, h_img0, h_img1, nullptr, h_out, with_local_map, hold_buffers);
+}
+
+// h_present (may be NULL: every stream): an absent stream's two flvis_image entries are not looked at and nothing of it is uploaded
+int flvis_image_feed_host_present(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, const uint8_t* h_present,
+                                  flvis_frame_out* h_out, int with_local_map, int hold_buffers) {
   if (!ctx || !ctx->pipe || !h_img0 || !h_img1) return FLVIS_ERR_INVALID_ARG;
   Pipeline* pl = ctx->pipe;
   const int S = pl->S, w = pl->cfg.image_width, h = pl->cfg.image_height;
   const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;
-  const int ch0 = h_img0[0].channels, ch1 = h_img1[0].channels;
+  auto present = [&](int s) { return !h_present || h_present[s] != 0; };
+  int first = 0;  // the first stream with a frame: its images set the channel counts every other one must match
+  while (first < S && !present(first)) first++;
+  const bool any = first < S;
+  const int ch0 = any ? h_img0[first].channels : 1, ch1 = any ? h_img1[first].channels : 1;
   if ((ch0 != 1 && ch0 != 3 && ch0 != 4) || (ch1 != 1 && ch1 != 3 && ch1 != 4) || (depth_cam && ch1 != 1))
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "image_feed_host: channels must be 1, 3 or 4 (depth image: 1)");
   const size_t bpp[2] = {(size_t)ch0, depth_cam ? (size_t)2 : (size_t)ch1};  // bytes per pixel as handed over
   for (int s = 0; s < S; s++) {
+    if (!present(s)) continue;
     const flvis_image* im[2] = {&h_img0[s], &h_img1[s]};
     for (int c = 0; c < 2; c++)
       if (!im[c]->data || im[c]->width != w || im[c]->height != h || im[c]->channels != (c ? ch1 : ch0) ||
@@ -1800,7 +1855,7 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
   for (int c = 0; c < 2 && e == hipSuccess; c++) {
     const flvis_image* im = c ? h_img1 : h_img0;
     const size_t row = (size_t)w * bpp[c], img_bytes = row * h;
-    bool contiguous = true;  // one block [S][h][w*bpp]: a single copy
+    bool contiguous = !h_present;  // one block [S][h][w*bpp]: a single copy (every stream's image)
     for (int s = 0; s < S && contiguous; s++)
       contiguous = (size_t)im[s].pitch == row && im[s].data == im[0].data + (size_t)s * img_bytes;
     // (in one piece: chunked uploads were slower, profiles/r05_h2d.md)
@@ -1808,8 +1863,9 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
       e = hipMemcpyAsync(hf.raw[slot][c], im[0].data, img_bytes * S, hipMemcpyHostToDevice, hf.strm);
     } else {
       for (int s = 0; s < S && e == hipSuccess; s++)
-        e = hipMemcpy2DAsync(hf.raw[slot][c] + (size_t)s * img_bytes, row, im[s].data, (size_t)im[s].pitch, row, h,
-                             hipMemcpyHostToDevice, hf.strm);
+        if (present(s))
+          e = hipMemcpy2DAsync(hf.raw[slot][c] + (size_t)s * img_bytes, row, im[s].data, (size_t)im[s].pitch, row, h,
+                               hipMemcpyHostToDevice, hf.strm);
     }
   }
   if (hf.timing && e == hipSuccess) {
@@ -1854,13 +1910,13 @@ int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis
     launch_bgr_to_gray(st, hf.raw[slot][1], ch1, hf.gray[slot][1], npix);
     d1 = hf.gray[slot][1];
   }
-  for (int s = 0; s < S; s++) hf.times[s] = h_img0[s].t;
+  for (int s = 0; s < S; s++) hf.times[s] = present(s) ? h_img0[s].t : 0.0;
   // one frame of lead in this mode: with two, the uploads' copies and events push the queued commands over what the HIP runtime
   // accepts without blocking the caller for milliseconds (measured: 16k vs 28k frames/s when that happened mid-run, profiles/r05_h2d.md)
   pl->host_lead_cap = 1;
   const auto th2 = std::chrono::steady_clock::now();
   pl->chain_continuous = wait_on_det && hf.mode == 2 && hf.last_call_frame == pl->frames_fed;  // (the previous frame was this entry's too)
-  const int rc = flvis_image_feed(ctx, d0, d1, hf.times.data(), h_out, with_local_map);
+  const int rc = flvis_image_feed_present(ctx, d0, d1, hf.times.data(), h_present, h_out, with_local_map);
   pl->chain_continuous = false;
   hf.last_call_frame = pl->frames_fed;
   pl->up_event = nullptr;
@@ -1895,6 +1951,12 @@ int flvis_imu_feed_all(flvis_ctx* ctx, const int* h_counts, const double* h_samp
 // resident in HBM -- a replay, bench.py's timed region, one rank of a multi-GPU job -- does not come back to its host language between
 // frames (eight Python interpreters on one host contending for cores are then not on the path).
 int flvis_run_steps(flvis_ctx* ctx, int n_steps, const flvis_step* steps, int with_local_map, double* h_call_ms) {
+  return flvis_run_steps_present(ctx, n_steps, steps, nullptr, with_local_map, h_call_ms);
+}
+
+// h_present (may be NULL: every stream in every step): [n_steps][n_streams], row k for step k as flvis_image_feed_present takes it
+int flvis_run_steps_present(flvis_ctx* ctx, int n_steps, const flvis_step* steps, const uint8_t* h_present, int with_local_map,
+                            double* h_call_ms) {
   if (!ctx || !ctx->pipe || n_steps < 0 || (n_steps > 0 && !steps)) return FLVIS_ERR_INVALID_ARG;
   for (int k = 0; k < n_steps; k++) {
     const flvis_step& f = steps[k];
@@ -1905,7 +1967,8 @@ int flvis_run_steps(flvis_ctx* ctx, int n_steps, const flvis_step* steps, int wi
     }
     ctx->pipe->defer_ba = k + 1 < n_steps;
     ctx->pipe->chain_continuous = k > 0;
-    const int rc = flvis_image_feed(ctx, f.d_img0, f.d_img1, f.h_times, nullptr, with_local_map);
+    const int rc = flvis_image_feed_present(ctx, f.d_img0, f.d_img1, f.h_times, h_present ? h_present + (size_t)k * ctx->pipe->S : nullptr,
+                                            nullptr, with_local_map);
     ctx->pipe->defer_ba = false;
     ctx->pipe->chain_continuous = false;
     if (rc != FLVIS_OK) return rc;
@@ -2213,7 +2276,7 @@ int flvis_write_imu_trajectory(const double* h_rows11, int n, const char* path, 
 int flvis_get_counters_n(flvis_ctx* ctx, int n, int64_t* h) {
   if (!ctx || !ctx->pipe || !h || n < 1 || n > 4) return FLVIS_ERR_INVALID_ARG;
   sync_all(ctx);
-  int64_t v[4] = {ctx->pipe->frames_fed * ctx->pipe->S, 0, 0, 0};
+  int64_t v[4] = {ctx->pipe->stream_frames, 0, 0, 0};
   for (Lane* L : ctx->pipe->lanes) {
     long long c[8];
     hipError_t e = hipMemcpy(c, L->pipe.counters, sizeof(c), hipMemcpyDeviceToHost);

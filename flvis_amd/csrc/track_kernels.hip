@@ -205,10 +205,28 @@ __global__ __launch_bounds__(AC_T) void k_apply_correction(Pipe p) {
 
 // ------------------------------------------------------------------------------------------------ frame begin
 __device__ inline void frame_begin_dev(const Pipe& p, int s, double time);
+// Per-stream presence (flvis_image_feed_present): a stream without a frame in this step.  Its frame never happens: frame_begin_dev does not
+// run (frame count, frame slots, skip window, rand() state and the slot of the next left image stay as the stream's last frame left them) and
+// the step plans nothing for it -- phase PH_IDLE (the per-step plan, which every frame_begin_dev rewrites first thing) and zero activity words,
+// so that every kernel of the step passes the stream by, as it passes an idle stream by.  k_frame_end writes nothing for it.
+__device__ __forceinline__ bool stream_present(const Pipe& p, int s) { return !p.present || p.present[s] != 0; }
+__device__ inline void frame_absent_dev(const Pipe& p, int s) {
+  p.st[s].phase = PH_IDLE;
+  p.act_img[s] = 0;
+  p.act_track[s] = 0;
+  p.det_mode[s] = 0;
+  p.gftt_act[s] = 0;
+  p.n_exist[s] = 0;
+  p.lk_count[s] = 0;
+}
+__device__ __forceinline__ void frame_step_dev(const Pipe& p, int s, double time) {
+  if (stream_present(p, s)) frame_begin_dev(p, s, time);
+  else frame_absent_dev(p, s);
+}
 __global__ void k_frame_begin(Pipe p, const double* __restrict__ frame_time) {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= p.S) return;
-  frame_begin_dev(p, s, frame_time[s]);
+  frame_step_dev(p, s, frame_time[s]);
 }
 // the head of a frame in one launch: the staged IMU samples (F2FTracking::imu_feed), then the frame set-up
 // One wavefront per stream: the integration itself is sequential (a sample's state follows from the previous one: lane 0 runs it), but
@@ -228,8 +246,8 @@ __device__ __forceinline__ void k_frame_head_body(const Pipe& p, const double* _
   const double t_frame = frame_time[s];
   __syncthreads();
   if (tid != 0) return;
-  imu_feed_dev(p, s, s_in);
-  frame_begin_dev(p, s, t_frame);
+  imu_feed_dev(p, s, s_in);  // (also for an absent stream: its IMU samples arrive without an image, as in imu_callback)
+  frame_step_dev(p, s, t_frame);
 }
 __global__ __launch_bounds__(64) void k_frame_head(Pipe p, const double* __restrict__ frame_time, long long* __restrict__ host_progress,
                                                    long long frame_no) {
@@ -378,7 +396,7 @@ __device__ __forceinline__ void k_frame_head_prepare_body(const Pipe& p, const d
   __syncthreads();
   if (tid == 0) {
     imu_feed_dev(p, s, s_in);
-    frame_begin_dev(p, s, t_frame);
+    frame_step_dev(p, s, t_frame);
   }
   __syncthreads();  // (workgroup-scope release / acquire: the stream's state as thread 0 left it)
   for (int i = tid; i < NMAX; i += 256) track_prepare_dev(p, s, i);
@@ -2710,7 +2728,9 @@ __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
 }
 __global__ __launch_bounds__(FE_T) void k_frame_end(Pipe p) {
   kj_wait(p.kj);
-  k_frame_end_body(p);
+  // a stream without a frame in this step: no output, trajectory row, feed count, next image slot or keyframe (its FrameOut stays its
+  // last frame's).  Uniform per workgroup; the join signal below is reached either way.
+  if (stream_present(p, blockIdx.x)) k_frame_end_body(p);
   kj_signal(p.kj);
 }
 

@@ -16,6 +16,7 @@ struct Pipe {
   const unsigned long long* seeds;  // [S] RANSAC seeds
   double* imu_in;           // [S][IMU_MAX][7]  (t, acc, gyro) in the FLVIS IMU frame
   int* n_imu;               // [S]
+  const int* present;       // [S] this step's presence (flvis_image_feed_present): 0 = the stream has no frame in it; nullptr: all present
   double* imu_out;          // [S][IMU_OUT_CAP][11]  F2FTracking::imu_feed's outputs per sample: (t, q_w_i wxyz, pos_w_i, vel_w_i)
   float* prev_pts;          // [S][NMAX][2]
   float* next_pts;          // [S][NMAX][2]

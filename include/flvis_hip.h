@@ -402,6 +402,32 @@ typedef struct flvis_image {
 int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, flvis_frame_out* h_out,
                           int with_local_map, int hold_buffers);
 
+/* Per-stream frame presence: the frame step advances only the streams that have a new frame (cameras at different rates, dropped
+ * frames, a camera that joins a running batch later).  h_present [n_streams]: nonzero = stream s has a frame in this step; NULL = every
+ * stream has one, exactly the entry point without _present.  Stream s under any presence schedule returns bit for bit what stream s of
+ * a tracker with the same configs, n_streams, seed_base and traj_capacity returns when it is fed only its present frames, each with the
+ * IMU samples that arrived since its previous present frame: per-frame outputs, trajectory rows (row j = its j-th present frame),
+ * landmarks, keyframe payloads, corrections, pose records, IMU-state rows and flvis_get_local_map_counts.  For a stream absent in a step:
+ *   - its images are not read (device slots [s] may hold anything; host entry: h_img0[s] / h_img1[s] are not looked at, their data may
+ *     be NULL, nothing of the stream is uploaded) and h_times[s] / h_img0[s].t is ignored;
+ *   - the IMU samples staged for it are integrated in the step (imu_callback without an image): its IMU-state rows are those of the run
+ *     fed its present frames alone;
+ *   - nothing else of it changes: frame count, skip_first_n_imgs (counted in its own present frames), the rand() state, its image slots
+ *     and template cache; no trajectory row, no keyframe.  Its h_out entry is its last frame's output (same frame_id: how a caller
+ *     tells presence), all zero before its first frame since tracker creation or its last reset;
+ *   - keyframes queued before keep being optimised.
+ * A step in which no stream is present is legal (only the IMU advances).  flvis_get_counters [0] counts the frames of present streams.
+ * A reset of an absent stream (flvis_reset_streams) takes effect in stream order: its next present frame is frame 0 of the new sequence.
+ * Works with several lanes and flvis_set_input_hold, also for a lane in which no stream is present.
+ * flvis_image_feed_host_present: a present stream with NULL data (or a size that does not match) returns FLVIS_ERR_INVALID_ARG before
+ * anything is enqueued.  flvis_run_steps_present: h_present [n_steps][n_streams], row k for step k (NULL: all present). */
+int flvis_image_feed_present(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
+                             const uint8_t* h_present, flvis_frame_out* h_out, int with_local_map);
+int flvis_image_feed_host_present(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, const uint8_t* h_present,
+                                  flvis_frame_out* h_out, int with_local_map, int hold_buffers);
+int flvis_run_steps_present(flvis_ctx* ctx, int n_steps, const flvis_step* steps, const uint8_t* h_present, int with_local_map,
+                            double* h_call_ms);
+
 /* Landmarks of curr_frame of one stream (host arrays of capacity cap): ids, raw pixel, rectified pixel, world point,
  * flags (bit0 has_3d, bit1 is_tracking_inlier).  Returns the landmark count (or <0). */
 int flvis_get_landmarks(flvis_ctx* ctx, int stream, int cap, int64_t* h_id, double* h_2d, double* h_2d_undist,
