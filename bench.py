@@ -9,8 +9,13 @@ frames, IMU samples) are resident in HBM / host memory before the timed region s
 
 Frame schedule (flvis_amd/bench_plan.py, tested on CPU): an UNTIMED pre-roll of skip_first_n_imgs + 12 frames brings every
 stream into the Tracking state (checked, more frames are fed while some stream is not there yet, the run fails loudly if
-that never happens), then --warmup untimed steps, then EXACTLY --steps timed steady-state steps, then 20 untimed steps with
-every stage bracketed by HIP events.
+that never happens), then --warmup untimed steps, then EXACTLY --steps timed steady-state steps.
+
+A plain run stops there: it prints the line of the timed region (value, ms_per_step, latency_ms, the k_lk_track roofline) and,
+with --dump-outputs, writes what the timed path computed.  --full adds everything else the benchmark measures or checks, after
+the timed region: 20 untimed steps with every stage bracketed by HIP events (stages_ms_per_step, roofline.kernels), the measured
+HBM copy bandwidth, the host-image leg (with_h2d), the CPU baselines and ATE against the CPU restatement (cpu_baseline, ate) and
+the EuRoC leg (euroc); --no-epilogue, --no-h2d, --cpu-frames, --cpu-mt-frames and --euroc select among them.
 
 --gpus N: one rank per GPU.  Under torchrun (WORLD_SIZE set) the rank joins the job; without it `bench.py --gpus N` spawns
 the N ranks itself (torch.distributed.run on 127.0.0.1) and fails loudly when fewer than N GPUs are visible.  Every rank
@@ -61,14 +66,16 @@ def parse_args(argv=None):
                     "untouched after it was handed over (flvis_set_input_hold); every frame of the run has its own buffer here")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--total-streams", type=int, default=512, help="fixed total for --scaling strong")
-    ap.add_argument("--cpu-frames", type=int, default=80, help="frames of the bounded single-thread CPU-baseline sample (0 = skip)")
-    ap.add_argument("--cpu-mt-frames", type=int, default=40, help="frames per stream of the one-thread-per-core CPU leg (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the per-stage epilogue, the copy-bandwidth "
+                    "probe, the host-image leg, the CPU baselines + ATE and the EuRoC leg (off: the timed region's line alone)")
+    ap.add_argument("--cpu-frames", type=int, default=80, help="--full: frames of the bounded single-thread CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-mt-frames", type=int, default=40, help="--full: frames per stream of the one-thread-per-core CPU leg (0 = skip)")
     ap.add_argument("--no-local-map", action="store_true")
-    ap.add_argument("--no-epilogue", action="store_true", help="skip the untimed per-stage epilogue")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-image (PCIe-inclusive) variant")
-    ap.add_argument("--euroc", default=os.environ.get("FLVIS_EUROC_DIR"), help="EuRoC ASL sequence folder (e.g. MH_05_difficult/mav0): BASELINE "
-                    "configs[0..1] -- the sequence through the HIP path and through the CPU restatement, ATE of each against the ground "
-                    "truth and of one against the other; absent: the line says \"dataset missing\" (SURVEY 8d)")
+    ap.add_argument("--no-epilogue", action="store_true", help="--full: skip the untimed per-stage epilogue")
+    ap.add_argument("--no-h2d", action="store_true", help="--full: skip the host-image (PCIe-inclusive) variant")
+    ap.add_argument("--euroc", default=os.environ.get("FLVIS_EUROC_DIR"), help="--full: EuRoC ASL sequence folder (e.g. MH_05_difficult/mav0): "
+                    "BASELINE configs[0..1] -- the sequence through the HIP path and through the CPU restatement, ATE of each against the "
+                    "ground truth and of one against the other; absent: the line says \"dataset missing\" (SURVEY 8d)")
     ap.add_argument("--pmc", action="store_true", help="collect FETCH_SIZE / WRITE_SIZE of k_lk_track under rocprofv3")
     ap.add_argument("--stub", action="store_true",
                     help="CPU test hook: no GPU work, gloo instead of RCCL; exercises rank spawning + result exchange only")
@@ -465,8 +472,9 @@ def main():
     open(ypath, "w").write(synth.D435I_STEREO_YAML)
     cfg = flvis_amd.load_config(ypath)
     skip = cfg.skip_first_n_imgs
-    epi = 0 if args.no_epilogue else plan.EPILOGUE
-    nmax = plan.max_frames(K, Wm, skip, epilogue=epi) + (0 if args.no_h2d else H2D_LEG_FRAMES + 4)   # (+ the host-image leg's own frames)
+    epi = plan.EPILOGUE if args.full and not args.no_epilogue else 0
+    with_h2d = args.full and not args.no_h2d
+    nmax = plan.max_frames(K, Wm, skip, epilogue=epi) + (H2D_LEG_FRAMES + 4 if with_h2d else 0)   # (+ the host-image leg's own frames)
     # multi-lane trackers run on their own streams: a private context stream keeps torch's (null) stream out of the frame loop;
     # the rendered inputs are synchronised explicitly below
     own_stream = int(os.environ.get("FLVIS_LANES", "1") or 1) > 1 or os.environ.get("FLVIS_BENCH_OWN_STREAM", "0") != "0"   # (A/B knob)
@@ -485,19 +493,25 @@ def main():
     SPF = 16
     imu = np.zeros((nmax, S, SPF, 7))
     imu_cnt = np.zeros((nmax, S), np.int32)
-    for i, s in enumerate(stream_ids):
-        t_prev = -1.0 / synth.FRAME_HZ
-        for f in range(nmax):
-            t = f / synth.FRAME_HZ
-            smp = synth.imu_samples(trajs[i], s, t_prev, t)
-            imu[f, i, :len(smp)] = smp
-            imu_cnt[f, i] = len(smp)
-            t_prev = t
+    imu_made = [0]
+
+    def make_imu(n):
+        """IMU samples of frames [0, n) of every stream (frame f: those in ((f - 1) / FRAME_HZ, f / FRAME_HZ]), made when first needed:
+        nmax bounds the longest pre-roll, a run usually feeds far fewer frames"""
+        for f in range(imu_made[0], n):
+            for i, s in enumerate(stream_ids):
+                smp = synth.imu_samples(trajs[i], s, (f - 1) / synth.FRAME_HZ, f / synth.FRAME_HZ)
+                imu[f, i, :len(smp)] = smp
+                imu_cnt[f, i] = len(smp)
+        imu_made[0] = max(imu_made[0], n)
+
+    if args.full:
+        make_imu(nmax)   # (the legs read the tables beyond the frames of the schedule)
     times = np.array([[f / synth.FRAME_HZ] * S for f in range(nmax)])
     n_mt = 0
-    if rank == 0 and args.cpu_mt_frames > 0:
+    if rank == 0 and args.full and args.cpu_mt_frames > 0:
         n_mt = min(S, os.cpu_count() or 1)
-    cpu_first, n_cpu = plan.cpu_sample(args.cpu_frames if rank == 0 else 0, plan.frame_schedule(K, Wm, skip, epilogue=epi))
+    cpu_first, n_cpu = plan.cpu_sample(args.cpu_frames if rank == 0 and args.full else 0, plan.frame_schedule(K, Wm, skip, epilogue=epi))
     n_keep = max(n_cpu, args.cpu_mt_frames if n_mt else 0)
     host_frames = {}   # frame -> (img0, img1) host copies of the first n_mt (>= 1) streams, for the CPU legs only
 
@@ -539,6 +553,7 @@ def main():
     f = 0
     while True:
         p_end = sched["preroll"][1]
+        make_imu(p_end)
         while f < p_end:
             feed(f, standin if f < skip else (standin if f == skip else render(f)), want_out=(f == p_end - 1))
             f += 1
@@ -554,7 +569,8 @@ def main():
         sched = plan.frame_schedule(K, Wm, skip, epilogue=epi, extra_settle=extra)
     tracking_at_start = n_tracking()
     t_pre = time.time() - t_pre
-    # ---- inputs of warm-up, timed region and epilogue: resident in HBM before the clock starts
+    # ---- inputs of warm-up, timed region and epilogue: resident in HBM (the images) and host memory (the IMU samples) before the clock starts
+    make_imu(sched["n_frames"])
     frames = {}
     for g in range(sched["warmup"][0], sched["n_frames"]):
         frames[g] = render(g)
@@ -710,7 +726,7 @@ def main():
             "config": {"workload": "%dxMI355X: batch of %d independent 640x480 synthetic stereo+IMU streams per GPU, full HIP "
                                    "front-end + batched Schur BA (BASELINE.json configs[%d])" % (world, S, 3 if world == 1 else 4),
                        "streams_per_gpu": S, "streams_total": world * S, "lanes_per_gpu": lib.flvis_tracker_lanes(ctx._h),
-                       "window_size": cfg.window_size, "local_map": bool(wlm),
+                       "window_size": cfg.window_size, "local_map": bool(wlm), "full": bool(args.full),
                        "preroll_frames": sched["preroll"][1], "streams_tracking_at_start": tracking_at_start,
                        "streams_tracking_at_end": int(csum[3]), "keyframes_in_run": int(csum[1]), "ba_runs_in_run": int(csum[2]),
                        "keyframes_in_timed_region": int(csum[4]), "ba_runs_in_timed_region": int(csum[5]),
@@ -737,10 +753,11 @@ def main():
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
                          "avg_launch_ms": round(dom_ms, 4), "algorithmic_bytes_per_launch": dom_bytes, "launches_per_step": 2},
         }
-        try:
-            out["roofline"]["hbm_copy_measured"] = measure_copy_bandwidth(dev)
-        except Exception as e:  # noqa: BLE001
-            out.setdefault("leg_errors", []).append("copy bandwidth: %s" % e)
+        if args.full:
+            try:
+                out["roofline"]["hbm_copy_measured"] = measure_copy_bandwidth(dev)
+            except Exception as e:  # noqa: BLE001
+                out.setdefault("leg_errors", []).append("copy bandwidth: %s" % e)
         if stages is not None:
             out["stages_ms_per_step"] = {k: round(v, 4) for k, v in stages.items()}
             out["stages_note"] = "per-stage times from %d untimed frames after the timed region (all stages bracketed by events)" % (epi - min(4, epi // 4))
@@ -791,7 +808,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out.setdefault("leg_errors", []).append("kernel table: %s: %s" % (type(e).__name__, e))
         # ---- legs that must never suppress the GPU line: host-image variant, CPU baselines, ATE
-        for leg in (leg_h2d, leg_cpu, leg_euroc):
+        for leg in (leg_h2d, leg_cpu, leg_euroc) if args.full else ():
             try:
                 leg(locals())
             except Exception as e:  # noqa: BLE001

@@ -17,7 +17,7 @@ tail -2 "$OUT/parity.log"
 cd /tmp || exit 1
 for i in 1 2; do
   for V in 0 1; do
-    FLVIS_EIG_WALK=0 FLVIS_EIG_STRIP=$V timeout 200 python "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --cpu-frames 0 --cpu-mt-frames 0 --no-h2d < /dev/null \
+    FLVIS_EIG_WALK=0 FLVIS_EIG_STRIP=$V timeout 200 python "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 --cpu-frames 0 --cpu-mt-frames 0 --no-h2d < /dev/null \
       > "$OUT/bench_strip${V}_run$i.json" 2> "$OUT/bench_strip${V}_run$i.err"
     python - "$OUT/bench_strip${V}_run$i.json" "$V" <<'PY'
 import json, sys

@@ -4,7 +4,7 @@
 #   scripts/collect_profiles.sh rNN
 # 1. `bench.py --pmc`: four separate rocprofv3 passes of the bench itself (kernel trace; SQ_INSTS_VALU; FETCH_SIZE; WRITE_SIZE) ->
 #    <tag>_kernel_pmc.json + <tag>_lk_pmc.json, which the bench lines below read back (source hash checked);
-# 2. the bench line with the driver's arguments and with the defaults;
+# 2. the full bench line (--full: every leg) with the driver's arguments and with the defaults;
 # 3. rocprofv3 --kernel-trace --stats of bench.py reduced to a summary + the kernel timeline of one frame.
 # Every step has its own timeout.
 set -u
@@ -16,8 +16,8 @@ export TMPDIR=/tmp
 cd /tmp || exit 1
 timeout 900 python "$R/bench.py" --pmc --steps 20 --warmup 10 < /dev/null > "$OUT/pmc.log" 2>&1
 cp "$R/gpurun_out/${TAG}_lk_pmc.json" "$R/gpurun_out/${TAG}_kernel_pmc.json" "$OUT/" 2>/dev/null
-timeout 300 python "$R/bench.py" --gpus 1 --steps 20 --warmup 5 < /dev/null > "$OUT/${TAG}_bench_line_driver_args.json" 2> "$OUT/bench_driver.err"
-timeout 400 python "$R/bench.py" < /dev/null > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench.err"
+timeout 300 python "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 < /dev/null > "$OUT/${TAG}_bench_line_driver_args.json" 2> "$OUT/bench_driver.err"
+timeout 400 python "$R/bench.py" --full < /dev/null > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench.err"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/cp_trace -o b -- python "$R/bench.py" --steps 60 --warmup 10 --cpu-frames 0 --cpu-mt-frames 0 --no-h2d --no-epilogue < /dev/null > "$OUT/trace.log" 2>&1
 T=$(find /tmp/cp_trace -name "*kernel_trace.csv" | head -1)
 S=$(find /tmp/cp_trace -name "*kernel_stats.csv" | head -1)

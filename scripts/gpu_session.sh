@@ -7,9 +7,9 @@
 #   env=<K=V> / unset=<K>        an environment variable for the steps that follow
 #   sh=<command line>            bash -c <command line>                                 -> sh_<n>.log
 #   lib=<path|->                 FLVIS_LIB_PATH for the steps that follow (a build of scripts/build_variant.sh; "-": the in-tree library)
-#   bench=<name>[,ENV=V...][,--flag...]  bench.py without the CPU / host-image legs (entries starting with -- go to bench.py) -> b_<name>.json
-#   benchh2d=<name>[,ENV=V...]   bench.py with the host-image leg, without the CPU legs -> b_<name>.json
-#   benchfull=<name>[,ENV=V...]  bench.py with every leg (the driver's arguments)       -> b_<name>.json
+#   bench=<name>[,ENV=V...][,--flag...]  bench.py --full without the CPU / host-image legs (entries starting with -- go to bench.py) -> b_<name>.json
+#   benchh2d=<name>[,ENV=V...]   bench.py --full with the host-image leg, without the CPU legs -> b_<name>.json
+#   benchfull=<name>[,ENV=V...]  bench.py --full with every leg (the driver's arguments) -> b_<name>.json
 #   baprof[=<frames>]            scripts/ba_prof.py (needs a -DFLVIS_BA_PROF variant selected by lib=)  -> ba_prof_<n>.txt
 #   py=<script and args>         python <script and args>                               -> py_<n>.log
 #   trace=<name>[,ENV=V...]      rocprofv3 --kernel-trace --stats of bench.py (60 steps) -> <name>_kernel_summary.md, <name>_timeline.txt
@@ -42,9 +42,9 @@ for step in "$@"; do
     bench|benchh2d|benchfull)
       split_env "$val"
       case "$key" in
-        bench) B="--no-h2d --cpu-frames 0 --cpu-mt-frames 0" ;;
-        benchh2d) B="--cpu-frames 0 --cpu-mt-frames 0" ;;
-        *) B="--gpus 1 --steps 20 --warmup 5" ;;
+        bench) B="--full --no-h2d --cpu-frames 0 --cpu-mt-frames 0" ;;
+        benchh2d) B="--full --cpu-frames 0 --cpu-mt-frames 0" ;;
+        *) B="--full --gpus 1 --steps 20 --warmup 5" ;;
       esac
       env "${envs[@]}" timeout 420 python bench.py $B "${xargs[@]}" < /dev/null > "$OUT/b_$name.json" 2> "$OUT/b_$name.err" || tail -3 "$OUT/b_$name.err" ;;
     baprof) timeout 600 python scripts/ba_prof.py ${val:-110} < /dev/null > "$OUT/ba_prof_$n.txt" 2>&1; cat "$OUT/ba_prof_$n.txt" ;;
@@ -63,7 +63,7 @@ for step in "$@"; do
       split_env "$val"
       rm -rf /tmp/gs_trace
       (cd /tmp && env "${envs[@]}" timeout 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/gs_trace -o b -- python "$R/bench.py" --steps 40 --warmup 10 \
-        --cpu-frames 0 --cpu-mt-frames 0 --no-epilogue < /dev/null > "$OUT/trace_$name.log" 2>&1)
+        --full --cpu-frames 0 --cpu-mt-frames 0 --no-epilogue < /dev/null > "$OUT/trace_$name.log" 2>&1)
       T=$(find /tmp/gs_trace -name "*kernel_trace.csv" | head -1); M=$(find /tmp/gs_trace -name "*memory_copy_trace.csv" | head -1)
       [ -n "$T" ] && [ -n "$M" ] && python scripts/h2d_kernel_compare.py "$T" "$M" < /dev/null > "$OUT/${name}_h2d_kernels.txt" 2>&1 && cat "$OUT/${name}_h2d_kernels.txt"
       [ -n "$T" ] && [ -n "$M" ] && python scripts/h2d_full_timeline.py "$T" "$M" 2 < /dev/null > "$OUT/${name}_h2d_timeline.txt" 2>&1 ;;
@@ -71,7 +71,7 @@ for step in "$@"; do
       split_env "$val"
       rm -rf /tmp/gs_trace
       (cd /tmp && env "${envs[@]}" timeout 400 rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d /tmp/gs_trace -o b -- python "$R/bench.py" --steps 20 --warmup 5 \
-        --cpu-frames 0 --cpu-mt-frames 0 --no-epilogue < /dev/null > "$OUT/trace_$name.log" 2>&1)
+        --full --cpu-frames 0 --cpu-mt-frames 0 --no-epilogue < /dev/null > "$OUT/trace_$name.log" 2>&1)
       A=$(find /tmp/gs_trace -name "*hip_api_trace.csv" | head -1); T=$(find /tmp/gs_trace -name "*kernel_trace.csv" | head -1); M=$(find /tmp/gs_trace -name "*memory_copy_trace.csv" | head -1)
       [ -n "$A" ] && python scripts/h2d_api_timeline.py "$A" "$T" "$M" < /dev/null > "$OUT/${name}_h2d_api.txt" 2>&1; head -80 "$OUT/${name}_h2d_api.txt" ;;
     evidence)

@@ -19,6 +19,14 @@ def test_euroc_leg_reports_a_missing_dataset():
         assert ("run_sequence.py" in out["euroc"]["would_run"]) and (d is None or d in out["euroc"]["looked_in"])
 
 
+def test_legs_run_only_under_full():
+    """A plain run times its steps and prints the line of the timed region; the epilogue and the legs are behind --full, whose
+    selectors keep their meaning there."""
+    assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    args = bench.parse_args(["--full", "--no-h2d", "--cpu-frames", "0"])
+    assert args.full and args.no_h2d and not args.no_epilogue and args.cpu_frames == 0 and args.cpu_mt_frames == 40
+
+
 def test_host_side_diagnostics_do_not_raise():
     a = np.zeros(1 << 16, np.uint8)
     a[:] = 1                                            # (touched: the pages exist)
