@@ -961,6 +961,10 @@ int flvis_hip_pgo_loop_closure(flvis_ctx* ctx, int n_graphs, const int* h_n_kf, 
       vkf.push_back((int)i);
       fixed.push_back((!later_end && (i == 0 || i == kf_prev)) ? 1 : 0);
     }
+    // a loop end outside min(earlier) .. max(later) has no vertex (e.g. [(5, 40), (50, 10)]), a self-loop has no edge: do not run
+    for (int k = 0; k < n_loops; k++)
+      if (vid[loops[2 * k]] < 0 || vid[loops[2 * k + 1]] < 0 || loops[2 * k] == loops[2 * k + 1]) valid = false;
+    if (!valid) continue;
     std::vector<int> ea, eb, eloop;
     for (long long i = kf_prev; i <= kf_curr; i++)
       for (long long j = i + 1; j <= std::min(kf_curr, i + 5); j++)

@@ -348,6 +348,7 @@ int ref_pgo_loop_closure(int n_kf, double* T_c_w7, const uint8_t* present, int n
   for (int k = 0; k < n_loops; k++) {
     const int a = loop_ids[2 * k], b = loop_ids[2 * k + 1];
     if (a < 0 || b < 0 || a >= n_kf || b >= n_kf || vid[a] < 0 || vid[b] < 0) return 0;  // (the reference dereferences a null vertex)
+    if (a == b) return 0;  // a self-loop: at(H, ...) would leave its profile row
     g.edges.push_back({vid[a], vid[b], ref::iso_inv(se3_of(loop_pose7 + 7 * k))});
   }
   if (use_initial_guess) g.initial_guess();
