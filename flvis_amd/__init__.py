@@ -372,6 +372,7 @@ class Context:
     def lc_keyframe_landmarks(self, img0, img1, cam_type, kps, desc, count, P0=None, P1=None, K4=None, in_place=False):
         """flvis_hip_lc_keyframe_landmarks (vo_loopclosing.cpp:255-372): kps float32 [n,cap,6], desc uint8 [n,cap,32], count int32 [n] as
         orb_detect_and_compute returns them; img0 uint8 [n,h,w]; img1 uint8 (stereo, cam_type 0) or int16/uint16 Z16 (depth, cam_type 2).
+        P0 / P1 [12] or K4 [4]: one camera for every image; [n,12] / [n,4]: one per image (flvis_hip_lc_keyframe_landmarks_rigs).
         Returns (lm_2d float32 [n,cap,2], lm_3d float64 [n,cap,3], lm_desc uint8 [n,cap,32], lm_count int32 [n])."""
         import numpy as np
         import torch
@@ -381,14 +382,16 @@ class Context:
         h, w = ref.shape[-2:]
         img0 = img0.contiguous() if img0 is not None else None
         img1 = img1.contiguous() if img1 is not None else None
-        dbl = lambda a, m: None if a is None else np.ascontiguousarray(a, np.float64).reshape(m)
+        rigs = any(a is not None and np.ndim(a) == 2 for a in (P0, P1, K4))
+        dbl = lambda a, m: None if a is None else np.ascontiguousarray(a, np.float64).reshape((n, m) if rigs else m)
         p0, p1, k4 = dbl(P0, 12), dbl(P1, 12), dbl(K4, 4)
+        fn = self._lib.flvis_hip_lc_keyframe_landmarks_rigs if rigs else self._lib.flvis_hip_lc_keyframe_landmarks
         hp = lambda a: _P(a, C.c_double) if a is not None else None
         lm2 = torch.zeros((n, cap, 2), dtype=torch.float32, device=kps.device)
         lm3 = torch.zeros((n, cap, 3), dtype=torch.float64, device=kps.device)
         lmd = desc if in_place else torch.zeros_like(desc)
         cnt = torch.zeros((n,), dtype=torch.int32, device=kps.device)
-        self._check(self._lib.flvis_hip_lc_keyframe_landmarks(
+        self._check(fn(
             self._h, _ptr(img0) if img0 is not None else C.c_void_p(0), _ptr(img1) if img1 is not None else C.c_void_p(0), w, h, n,
             int(cam_type), hp(p0), hp(p1), hp(k4), _ptr(kps), _ptr(desc), _ptr(count), cap, _ptr(lm2), _ptr(lm3), _ptr(lmd), _ptr(cnt)),
             "lc_keyframe_landmarks")
@@ -396,20 +399,21 @@ class Context:
 
     def pnp_ransac(self, p3d, p2d, count, K4, seeds, iterations=100, reproj_px=2.0, confidence=0.99):
         """flvis_hip_pnp_ransac: p3d float32 [n,cap,3], p2d float32 [n,cap,2], count int32 [n] (device) -> (pose7 [n,7], mask [n,cap],
-        n_inliers [n])."""
+        n_inliers [n]).  K4 [4]: one camera for every set; [n,4]: one per set (flvis_hip_pnp_ransac_rigs)."""
         import numpy as np
         import torch
         p3d, p2d = p3d.contiguous(), p2d.contiguous()
         n, cap, _ = p3d.shape
         K = np.ascontiguousarray(K4, np.float64)
         sd = np.ascontiguousarray(seeds, np.uint64)
-        assert len(sd) == n and len(K) == 4
+        rigs = K.ndim == 2
+        assert len(sd) == n and K.shape == ((n, 4) if rigs else (4,))
+        fn = self._lib.flvis_hip_pnp_ransac_rigs if rigs else self._lib.flvis_hip_pnp_ransac
         pose = torch.zeros((n, 7), dtype=torch.float64, device=p3d.device)
         mask = torch.zeros((n, cap), dtype=torch.uint8, device=p3d.device)
         ninl = torch.zeros((n,), dtype=torch.int32, device=p3d.device)
-        self._check(self._lib.flvis_hip_pnp_ransac(self._h, _ptr(p3d), _ptr(p2d), _ptr(count), cap, n, _P(K, C.c_double), int(iterations),
-                                                   C.c_double(reproj_px), C.c_double(confidence), _P(sd, C.c_uint64), _ptr(pose),
-                                                   _ptr(mask), _ptr(ninl)), "pnp_ransac")
+        self._check(fn(self._h, _ptr(p3d), _ptr(p2d), _ptr(count), cap, n, _P(K, C.c_double), int(iterations), C.c_double(reproj_px),
+                       C.c_double(confidence), _P(sd, C.c_uint64), _ptr(pose), _ptr(mask), _ptr(ninl)), "pnp_ransac")
         return pose, mask, ninl
 
     def debug_epnp(self, p3d, p2d, count, K4):
@@ -581,10 +585,19 @@ def load_lc_params(yaml_path):
 
 
 class LoopCloser:
-    """flvis_loop_closer: LoopClosingNodeletClass (vo_loopclosing.cpp) for n_streams sequences; the keyframe database stays on the GPU."""
+    """flvis_loop_closer: LoopClosingNodeletClass (vo_loopclosing.cpp) for n_streams sequences; the keyframe database stays on the GPU.
+
+    cfg: one config for every sequence, or a sequence of configs -- one camera per sequence (flvis_loop_closer_create_rigs: cam_type and
+    the image size must agree, FlvisError otherwise; n_streams is then their number).  self.cfg is sequence 0's."""
 
     def __init__(self, ctx, cfg, prm, n_streams=1, max_keyframes=2000, orb_pattern=None):
         import numpy as np
+        cfgs = None
+        if not isinstance(cfg, FlvisCfg):
+            cfgs = list(cfg)
+            if n_streams not in (1, len(cfgs)):
+                raise ValueError("LoopCloser: %d configs for %d streams" % (len(cfgs), n_streams))
+            n_streams, cfg = len(cfgs), cfgs[0]
         self._ctx, self._lib, self.n_streams = ctx, ctx._lib, n_streams
         self.cfg, self.max_keyframes = cfg, int(max_keyframes)
         if isinstance(prm, dict):
@@ -594,8 +607,16 @@ class LoopCloser:
             pat = np.ascontiguousarray(orb_pattern, np.int8)
             assert pat.size == 1024
         h = C.c_void_p(0)
-        ctx._check(self._lib.flvis_loop_closer_create(ctx._h, C.byref(cfg), C.byref(prm), int(n_streams), int(max_keyframes),
-                                                      C.c_void_p(pat.ctypes.data if pat is not None else 0), C.byref(h)), "loop_closer_create")
+        patp = C.c_void_p(pat.ctypes.data if pat is not None else 0)
+        if cfgs is None:
+            ctx._check(self._lib.flvis_loop_closer_create(ctx._h, C.byref(cfg), C.byref(prm), int(n_streams), int(max_keyframes), patp,
+                                                          C.byref(h)), "loop_closer_create")
+        else:
+            arr = (FlvisCfg * n_streams)(*cfgs)
+            self._lib.flvis_loop_closer_create_rigs.argtypes = [C.c_void_p, C.POINTER(FlvisCfg), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                                C.c_void_p]
+            ctx._check(self._lib.flvis_loop_closer_create_rigs(ctx._h, arr, C.byref(prm), int(n_streams), int(max_keyframes), patp,
+                                                               C.byref(h)), "loop_closer_create_rigs")
         self._h = h
         self._lib.flvis_loop_closer_destroy.argtypes = [C.c_void_p]
 
@@ -609,6 +630,30 @@ class LoopCloser:
             self.close()
         except Exception:
             pass
+
+    def reset(self, streams, cfgs=None):
+        """flvis_loop_closer_reset: the named sequences start over as sequences of a new closer (the others go on undisturbed).  cfgs: one
+        config per named sequence, whose camera it changes to (flvis_loop_closer_reset_rigs).  FlvisError, and nothing changes, for an
+        index out of range or listed twice or a config whose cam_type / image size is not the closer's."""
+        ids = [int(k) for k in streams]
+        arr = (C.c_int * max(1, len(ids)))(*ids)
+        if cfgs is None:
+            self._lib.flvis_loop_closer_reset.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+            self._ctx._check(self._lib.flvis_loop_closer_reset(self._h, len(ids), arr), "loop_closer_reset")
+            return
+        cfgs = [cfgs] if isinstance(cfgs, FlvisCfg) else list(cfgs)
+        if len(cfgs) != len(ids):
+            raise ValueError("LoopCloser.reset: %d configs for %d streams" % (len(cfgs), len(ids)))
+        carr = (FlvisCfg * max(1, len(ids)))(*cfgs)
+        self._lib.flvis_loop_closer_reset_rigs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(FlvisCfg)]
+        self._ctx._check(self._lib.flvis_loop_closer_reset_rigs(self._h, len(ids), arr, carr), "loop_closer_reset_rigs")
+
+    def stream_cfg(self, s):
+        """flvis_loop_closer_stream_cfg: the config sequence s runs on (as created, or as last reset with reset(..., cfgs))."""
+        out = FlvisCfg()
+        self._lib.flvis_loop_closer_stream_cfg.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlvisCfg)]
+        self._ctx._check(self._lib.flvis_loop_closer_stream_cfg(self._h, int(s), C.byref(out)), "loop_closer_stream_cfg")
+        return out
 
     def add_keyframes(self, streams, img0, img1, T_c_w_odom):
         """streams: the sequence of each keyframe (distinct); img0 uint8 [n,h,w], img1 uint8 / Z16 [n,h,w] (device); T_c_w_odom [n,7].

@@ -12,6 +12,11 @@
 // candidate three integers and a pose.  Integer / threshold logic stays on the host, as in the reference's pgoProcess thread.
 // That thread looks at whatever keyframe is newest whenever it comes round (a keyframe can be looked at twice or never); here
 // every keyframe is processed exactly once, in order (deterministic).  tf / path / image publishing is the ROS wrapper's business.
+//
+// A batch may hold one calibrated camera per sequence (flvis_loop_closer_create_rigs): the sequences' cameras are rows of one table
+// resident on the device, which the two kernels that read a camera index by the sequence of their keyframe / candidate; and a
+// sequence's slot can start over, also on another camera (flvis_loop_closer_reset[_rigs]) -- the host bookkeeping of Seq is all there
+// is to empty, the slot's database entries are unreachable once Seq::n is 0.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,11 +30,13 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "loop_kernels.hpp"
 
 namespace {
 
 constexpr int LCC_CAP = 1024;   // keypoints per keyframe (the reference extracts 1000) = correspondences per PnP set
 constexpr int LCC_VCAP = 1024;  // bag-of-words entries per keyframe
+constexpr size_t LCC_STAGE = 7 * sizeof(double) + 2 * sizeof(int);  // bytes per keyframe of an add call's one upload
 
 // ---- pose7 = tx ty tz qx qy qz qw on the host (Sophus::SE3 products of :377, :908) -------------------------------------------
 void q_mul(const double* a, const double* b, double* o) {  // Hamilton product, x y z w
@@ -59,12 +66,14 @@ void pose_mul(const double* a, const double* b, double* o) {  // T_a * T_b
 // copies the batch results of one add call into the keyframe slots of their sequences (slot = stream * maxkf + keyframe)
 __global__ __launch_bounds__(256) void k_lcc_store(const int* __restrict__ slot, const int* __restrict__ ids, const double* __restrict__ vals,
                                                    const int* __restrict__ nnz, const float* __restrict__ lm2, const double* __restrict__ lm3,
-                                                   const uint8_t* __restrict__ lmd, const int* __restrict__ lmc, int* db_ids, double* db_vals,
-                                                   int* db_nnz, float* db_lm2, double* db_lm3, uint8_t* db_lmd, int* db_lmc) {
+                                                   const uint8_t* __restrict__ lmd, const int* __restrict__ lmc, const double* __restrict__ T,
+                                                   int* db_ids, double* db_vals, int* db_nnz, float* db_lm2, double* db_lm3, uint8_t* db_lmd,
+                                                   int* db_lmc, double* db_T) {
   const int i = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;  // t: element of the keyframe's row, 0..1023
   const size_t s = (size_t)slot[i];
   if (t >= LCC_CAP) return;
   const int nv = nnz[i], nl = lmc[i];
+  if (t < 7) db_T[s * 7 + t] = T[(size_t)i * 7 + t];
   if (t < nv) {
     db_ids[s * LCC_VCAP + t] = ids[(size_t)i * LCC_VCAP + t];
     db_vals[s * LCC_VCAP + t] = vals[(size_t)i * LCC_VCAP + t];
@@ -115,6 +124,8 @@ __global__ __launch_bounds__(256) void k_lcc_correspondences(const int* __restri
   p2d[o * 2] = u, p2d[o * 2 + 1] = v;
 }
 
+using flvis::LcCam;
+
 struct Seq {
   int n = 0;
   bool fresh = false;
@@ -129,12 +140,14 @@ struct Seq {
 
 struct flvis_loop_closer {
   flvis_ctx* ctx = nullptr;
-  flvis_cfg cfg;
+  std::vector<flvis_cfg> cfgs;  // per sequence; cam_type / w / h below are batch-wide
   flvis_lc_params prm;
   flvis_orb_params orb{1000, 1.2f, 8, 20};  // :242
   std::vector<int8_t> pattern;
-  int S = 0, maxkf = 0, w = 0, h = 0, device = 0;
-  double K4[4];
+  int S = 0, maxkf = 0, w = 0, h = 0, cam_type = 0, device = 0;
+  // the sequences' cameras: [S] rows on the device, written in stream order from the pinned host copy (a reset does not wait)
+  LcCam* h_cams = nullptr;
+  LcCam* d_cams = nullptr;
   // keyframe database, [S * maxkf] slots
   int* db_ids = nullptr;
   double* db_vals = nullptr;
@@ -147,12 +160,14 @@ struct flvis_loop_closer {
   // per-call staging, [S] items
   float *kps = nullptr, *lm2 = nullptr, *p3d = nullptr, *p2d = nullptr;
   uint8_t *desc = nullptr, *da = nullptr, *db = nullptr, *mask = nullptr;
-  int *cnt = nullptr, *ovf = nullptr, *ids = nullptr, *nnz = nullptr, *lmc = nullptr, *slot_a = nullptr, *slot_b = nullptr, *na = nullptr,
+  int *cnt = nullptr, *ovf = nullptr, *ids = nullptr, *nnz = nullptr, *lmc = nullptr, *slot_a = nullptr, *na = nullptr,
       *nb = nullptr, *pairs = nullptr, *npairs = nullptr, *ninl = nullptr;
+  uint8_t* stage = nullptr;  // one upload per add call: [n][7] poses, [n] slots, [n] sequences
   double *vals = nullptr, *lm3 = nullptr, *rows = nullptr, *pose = nullptr, *loop_pose = nullptr, *drift = nullptr, *stats = nullptr, *pgo_T = nullptr;
   std::vector<void*> owned;
   std::vector<Seq> seq;
   std::vector<double> h_rows;
+  std::vector<uint8_t> h_stage;
 
   template <class T>
   bool alloc(T*& p, size_t count) {
@@ -209,10 +224,23 @@ int flvis_lc_params_load(const char* yaml_path, flvis_lc_params* prm, char* err,
   return FLVIS_OK;
 }
 
-int flvis_loop_closer_create(flvis_ctx* ctx, const flvis_cfg* cfg, const flvis_lc_params* prm, int n_streams, int max_keyframes,
-                             const int8_t* h_orb_pattern, flvis_loop_closer** out) {
+// the fields every sequence of a closer shares (they size buffers and pick the kernels' paths): null, or the name of the first that differs
+static const char* lc_batch_field_mismatch(const flvis_loop_closer* lc, const flvis_cfg& c) {
+  if (c.cam_type != lc->cam_type) return "cam_type";
+  if (c.image_width != lc->w) return "image_width";
+  if (c.image_height != lc->h) return "image_height";
+  return nullptr;
+}
+static void lc_cam_of_cfg(const flvis_cfg& c, LcCam* cam) {
+  memcpy(cam->P0, c.P0, sizeof(cam->P0));
+  memcpy(cam->P1, c.P1, sizeof(cam->P1));
+  cam->fx = c.P0[0], cam->fy = c.P0[5], cam->cx = c.P0[2], cam->cy = c.P0[6];  // dc.K0_rect (:670)
+}
+
+int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const flvis_lc_params* prm, int n_streams, int max_keyframes,
+                                  const int8_t* h_orb_pattern, flvis_loop_closer** out) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
-  if (!cfg || !prm || !out || n_streams <= 0 || max_keyframes <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_create: bad args");
+  if (!cfgs || !prm || !out || n_streams <= 0 || max_keyframes <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_create: bad args");
   *out = nullptr;
   if (ctx->voc_nodes < 2)
     return ctx->fail(FLVIS_ERR_CONFIG, "loop_closer_create: no vocabulary (flvis_hip_bow_load_vocabulary / flvis_hip_bow_set_vocabulary first)");
@@ -220,9 +248,15 @@ int flvis_loop_closer_create(flvis_ctx* ctx, const flvis_cfg* cfg, const flvis_l
     return ctx->fail(FLVIS_ERR_CAPACITY, "loop_closer_create: n_streams * max_keyframes is too large");
   hipSetDevice(ctx->device);
   flvis_loop_closer* lc = new flvis_loop_closer();
-  lc->ctx = ctx, lc->device = ctx->device, lc->cfg = *cfg, lc->prm = *prm, lc->S = n_streams, lc->maxkf = max_keyframes;
-  lc->w = cfg->image_width, lc->h = cfg->image_height;
-  lc->K4[0] = cfg->P0[0], lc->K4[1] = cfg->P0[5], lc->K4[2] = cfg->P0[2], lc->K4[3] = cfg->P0[6];  // dc.K0_rect (:670)
+  lc->ctx = ctx, lc->device = ctx->device, lc->prm = *prm, lc->S = n_streams, lc->maxkf = max_keyframes;
+  lc->w = cfgs[0].image_width, lc->h = cfgs[0].image_height, lc->cam_type = cfgs[0].cam_type;
+  for (int s = 1; s < n_streams; s++)
+    if (const char* f = lc_batch_field_mismatch(lc, cfgs[s])) {
+      delete lc;
+      return ctx->fail(FLVIS_ERR_CONFIG, "loop_closer_create_rigs: stream " + std::to_string(s) + ": batch-wide field " + f +
+                                             " differs from the closer's (stream 0)");
+    }
+  lc->cfgs.assign(cfgs, cfgs + n_streams);
   if (h_orb_pattern) lc->pattern.assign(h_orb_pattern, h_orb_pattern + 1024);
   const size_t slots = (size_t)n_streams * max_keyframes, S = (size_t)n_streams;
   bool ok = lc->alloc(lc->db_ids, slots * LCC_VCAP) && lc->alloc(lc->db_vals, slots * LCC_VCAP) && lc->alloc(lc->db_nnz, slots) &&
@@ -231,19 +265,87 @@ int flvis_loop_closer_create(flvis_ctx* ctx, const flvis_cfg* cfg, const flvis_l
             lc->alloc(lc->kps, S * LCC_CAP * 6) && lc->alloc(lc->desc, S * LCC_CAP * 32) && lc->alloc(lc->cnt, S) && lc->alloc(lc->ovf, S) &&
             lc->alloc(lc->ids, S * LCC_VCAP) && lc->alloc(lc->vals, S * LCC_VCAP) && lc->alloc(lc->nnz, S) &&
             lc->alloc(lc->lm2, S * LCC_CAP * 2) && lc->alloc(lc->lm3, S * LCC_CAP * 3) && lc->alloc(lc->lmc, S) &&
-            lc->alloc(lc->slot_a, S) && lc->alloc(lc->slot_b, S) && lc->alloc(lc->da, S * LCC_CAP * 32) &&
+            lc->alloc(lc->slot_a, S * 3) && lc->alloc(lc->da, S * LCC_CAP * 32) &&
             lc->alloc(lc->db, S * LCC_CAP * 32) && lc->alloc(lc->na, S) && lc->alloc(lc->nb, S) && lc->alloc(lc->pairs, S * LCC_CAP * 2) &&
             lc->alloc(lc->npairs, S) && lc->alloc(lc->p3d, S * LCC_CAP * 3) && lc->alloc(lc->p2d, S * LCC_CAP * 2) &&
             lc->alloc(lc->mask, S * LCC_CAP) && lc->alloc(lc->ninl, S) && lc->alloc(lc->pose, S * 7) && lc->alloc(lc->rows, slots) &&
-            lc->alloc(lc->loop_pose, slots * 7) && lc->alloc(lc->drift, S * 7) && lc->alloc(lc->stats, S * 5) && lc->alloc(lc->pgo_T, slots * 7);
+            lc->alloc(lc->loop_pose, slots * 7) && lc->alloc(lc->drift, S * 7) && lc->alloc(lc->stats, S * 5) && lc->alloc(lc->pgo_T, slots * 7) &&
+            lc->alloc(lc->stage, S * LCC_STAGE) && lc->alloc(lc->d_cams, S) &&
+            hipHostMalloc((void**)&lc->h_cams, S * sizeof(LcCam), hipHostMallocDefault) == hipSuccess;
+  if (ok) {
+    for (int s = 0; s < n_streams; s++) lc_cam_of_cfg(cfgs[s], &lc->h_cams[s]);
+    ok = hipMemcpyAsync(lc->d_cams, lc->h_cams, S * sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+  }
   if (!ok) {
+    (void)hipGetLastError();
+    hipStreamSynchronize(ctx->stream);
     for (void* p : lc->owned) hipFree(p);
+    if (lc->h_cams) hipHostFree(lc->h_cams);
     delete lc;
     return ctx->fail(FLVIS_ERR_HIP, "loop_closer_create: device allocation failed (76 KB per keyframe slot)");
   }
   lc->seq.resize(n_streams);
   lc->h_rows.resize(slots);
+  lc->h_stage.resize(S * LCC_STAGE);
   *out = lc;
+  return FLVIS_OK;
+}
+
+// one config for every sequence: the same call on n_streams copies
+int flvis_loop_closer_create(flvis_ctx* ctx, const flvis_cfg* cfg, const flvis_lc_params* prm, int n_streams, int max_keyframes,
+                             const int8_t* h_orb_pattern, flvis_loop_closer** out) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  if (!cfg || n_streams <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_create: bad args");
+  const std::vector<flvis_cfg> cfgs((size_t)n_streams, *cfg);
+  return flvis_loop_closer_create_rigs(ctx, cfgs.data(), prm, n_streams, max_keyframes, h_orb_pattern, out);
+}
+
+// Start over on the named sequences, each on cfgs[i] when cfgs is given.  Host bookkeeping plus, for a new camera, one row copy in
+// stream order from the closer's pinned table: nothing waits for the device.
+static int lc_reset(flvis_loop_closer* lc, int n, const int* streams, const flvis_cfg* cfgs, const char* what) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  if (n < 0 || (n > 0 && !streams)) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": bad args");
+  std::vector<char> named((size_t)lc->S, 0);
+  for (int i = 0; i < n; i++) {
+    const int s = streams[i];
+    if (s < 0 || s >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": stream out of range");
+    if (named[s]) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": stream " + std::to_string(s) + " is listed twice");
+    named[s] = 1;
+    if (cfgs)
+      if (const char* f = lc_batch_field_mismatch(lc, cfgs[i]))
+        return ctx->fail(FLVIS_ERR_CONFIG, std::string(what) + ": stream " + std::to_string(s) + ": batch-wide field " + f +
+                                               " differs from the closer's (stream 0)");
+  }
+  if (n == 0) return FLVIS_OK;
+  hipSetDevice(ctx->device);
+  for (int i = 0; i < n; i++) {
+    const int s = streams[i];
+    lc->seq[s] = Seq();  // n, the pending keyframe, T_odom_map, the loop list and last_pgo (the slot's database entries: unreachable with n = 0)
+    std::fill(lc->h_rows.begin() + (size_t)s * lc->maxkf, lc->h_rows.begin() + (size_t)(s + 1) * lc->maxkf, 0.0);
+    if (!cfgs) continue;
+    lc->cfgs[s] = cfgs[i];
+    // (a copy of this row that a previous reset queued has run: every call that reads the table returns synchronised, and with no such
+    //  call in between nothing has looked at the row the earlier reset wrote)
+    lc_cam_of_cfg(cfgs[i], &lc->h_cams[s]);
+    const hipError_t e = hipMemcpyAsync(lc->d_cams + s, lc->h_cams + s, sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return ctx->hip_fail(e, what);
+  }
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_reset(flvis_loop_closer* lc, int n, const int* streams) { return lc_reset(lc, n, streams, nullptr, "loop_closer_reset"); }
+
+int flvis_loop_closer_reset_rigs(flvis_loop_closer* lc, int n, const int* streams, const flvis_cfg* cfgs) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  if (n > 0 && !cfgs) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_reset_rigs: bad args");
+  return lc_reset(lc, n, streams, cfgs, "loop_closer_reset_rigs");
+}
+
+int flvis_loop_closer_stream_cfg(flvis_loop_closer* lc, int stream, flvis_cfg* out) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  if (stream < 0 || stream >= lc->S || !out) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_stream_cfg: bad args");
+  *out = lc->cfgs[stream];
   return FLVIS_OK;
 }
 
@@ -252,6 +354,7 @@ void flvis_loop_closer_destroy(flvis_loop_closer* lc) {
   hipSetDevice(lc->device);  // (the context may already be gone: nothing of it is touched here)
   hipDeviceSynchronize();
   for (void* p : lc->owned) hipFree(p);
+  hipHostFree(lc->h_cams);
   delete lc;
 }
 
@@ -269,31 +372,36 @@ int flvis_loop_closer_add_keyframes(flvis_loop_closer* lc, int n, const int* h_s
   }
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
+  // STEP 2's host part first (:374-383, T_c_w = T_c_w_odom * T_odom_map): the poses, the keyframes' slots and their sequences -- the
+  // index of each keyframe's camera -- go to the device in ONE copy, ahead of the kernels that read them
+  double* const T = reinterpret_cast<double*>(lc->h_stage.data());
+  int* const slot = reinterpret_cast<int*>(lc->h_stage.data() + 7 * sizeof(double) * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    const Seq& q = lc->seq[h_stream[i]];
+    slot[i] = h_stream[i] * lc->maxkf + q.n;
+    slot[n + i] = h_stream[i];
+    pose_mul(h_T_c_w_odom7 + 7 * i, q.T_odom_map, T + 7 * (size_t)i);
+  }
+  const double* const d_T = reinterpret_cast<const double*>(lc->stage);
+  const int* const d_slot = reinterpret_cast<const int*>(lc->stage + 7 * sizeof(double) * (size_t)n);
+  hipError_t e = hipMemcpyAsync(lc->stage, lc->h_stage.data(), LCC_STAGE * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_add_keyframes");
   // STEP 1.3 / 1.4 / 1.5 / 1.6 (:236-372): ORB, bag of words of ALL descriptors, 3-D positions, then the lists without the rest
   int rc = flvis_hip_orb_detect_and_compute(ctx, d_img0, lc->w, lc->h, n, &lc->orb, lc->pattern.empty() ? nullptr : lc->pattern.data(), lc->kps,
                                             lc->desc, lc->cnt, LCC_CAP, lc->ovf);
-  if (rc != FLVIS_OK) return rc;
-  rc = flvis_hip_bow_transform(ctx, lc->desc, lc->cnt, LCC_CAP, n, LCC_VCAP, lc->ids, lc->vals, lc->nnz);
-  if (rc != FLVIS_OK) return rc;
-  rc = flvis_hip_lc_keyframe_landmarks(ctx, d_img0, d_img1, lc->w, lc->h, n, lc->cfg.cam_type, lc->cfg.P0, lc->cfg.P1, lc->K4, lc->kps, lc->desc,
-                                       lc->cnt, LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
-  if (rc != FLVIS_OK) return rc;
-  // STEP 2 (:374-383): the keyframe joins its sequence's map with T_c_w = T_c_w_odom * T_odom_map
-  std::vector<int> slot((size_t)n);
-  std::vector<double> T((size_t)n * 7);
-  for (int i = 0; i < n; i++) {
-    Seq& q = lc->seq[h_stream[i]];
-    slot[i] = h_stream[i] * lc->maxkf + q.n;
-    pose_mul(h_T_c_w_odom7 + 7 * i, q.T_odom_map, &T[7 * (size_t)i]);
+  if (rc == FLVIS_OK) rc = flvis_hip_bow_transform(ctx, lc->desc, lc->cnt, LCC_CAP, n, LCC_VCAP, lc->ids, lc->vals, lc->nnz);
+  if (rc == FLVIS_OK)
+    rc = flvis::lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, lc->w, lc->h, n, lc->cam_type, lc->d_cams, d_slot + n, lc->kps, lc->desc, lc->cnt,
+                                          LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);  // (h_stage is reused by the next call)
+    return rc;
   }
-  hipError_t e = hipMemcpyAsync(lc->slot_a, slot.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st);
-  for (int i = 0; i < n && e == hipSuccess; i++)
-    e = hipMemcpyAsync(lc->db_T + (size_t)slot[i] * 7, &T[7 * (size_t)i], 7 * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_add_keyframes");
-  k_lcc_store<<<dim3(LCC_CAP / 256, n), 256, 0, st>>>(lc->slot_a, lc->ids, lc->vals, lc->nnz, lc->lm2, lc->lm3, lc->desc, lc->lmc, lc->db_ids,
-                                                       lc->db_vals, lc->db_nnz, lc->db_lm2, lc->db_lm3, lc->db_lmd, lc->db_lmc);
+  // STEP 2 on the device: the keyframe joins its sequence's map
+  k_lcc_store<<<dim3(LCC_CAP / 256, n), 256, 0, st>>>(d_slot, lc->ids, lc->vals, lc->nnz, lc->lm2, lc->lm3, lc->desc, lc->lmc, d_T, lc->db_ids,
+                                                       lc->db_vals, lc->db_nnz, lc->db_lm2, lc->db_lm3, lc->db_lmd, lc->db_lmc, lc->db_T);
   e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // slot / T are host temporaries of this call
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the batch is stored when the call returns (and h_stage is free again)
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_add_keyframes");
   for (int i = 0; i < n; i++) {
     Seq& q = lc->seq[h_stream[i]];
@@ -312,7 +420,7 @@ int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int
   flvis_ctx* ctx = lc->ctx;
   if (n <= 0 || n > lc->S || !h_img0 || !h_img1 || !h_stream || !h_T_c_w_odom7)
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: bad args");
-  const int bpp1 = lc->cfg.cam_type == 2 ? 2 : 1;
+  const int bpp1 = lc->cam_type == 2 ? 2 : 1;
   // every argument is checked BEFORE a copy is queued: the caller may free its images as soon as this call returns with an error
   for (int i = 0; i < n; i++) {
     const flvis_image &a = h_img0[i], &b = h_img1[i];
@@ -379,7 +487,7 @@ int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_process");
   // :453 + isLoopCandidate (:520-590) on the host
   std::vector<int> cand;  // sequences with a candidate
-  std::vector<int> sa, sb;
+  std::vector<int> sa, sb;  // the pair's database slots
   for (int s = 0; s < lc->S; s++) {
     Seq& q = lc->seq[s];
     if (!q.fresh) continue;
@@ -399,17 +507,21 @@ int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
   const int nc = (int)cand.size();
   if (nc == 0) return FLVIS_OK;
   // isLoopClosureKF (:593-686) for all candidates at once
-  e = hipMemcpyAsync(lc->slot_a, sa.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(lc->slot_b, sb.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, st);
+  // one copy: the earlier keyframes' slots, the later ones', the candidates' sequences (= their cameras' rows)
+  sa.insert(sa.end(), sb.begin(), sb.end());
+  sa.insert(sa.end(), cand.begin(), cand.end());
+  const int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + nc, *const cam_of = lc->slot_a + 2 * nc;
+  e = hipMemcpyAsync(lc->slot_a, sa.data(), sizeof(int) * 3 * (size_t)nc, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_process");
-  k_lcc_fetch<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(lc->slot_a, lc->slot_b, lc->db_lmd, lc->db_lmc, lc->da, lc->na, lc->db, lc->nb);
+  k_lcc_fetch<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->db_lmd, lc->db_lmc, lc->da, lc->na, lc->db, lc->nb);
   int rc = flvis_hip_orb_match(ctx, lc->da, lc->na, LCC_CAP, lc->db, lc->nb, LCC_CAP, nc, p.ratioMax, lc->pairs, lc->npairs);
   if (rc != FLVIS_OK) return rc;
-  k_lcc_correspondences<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(lc->slot_a, lc->slot_b, lc->pairs, lc->npairs, lc->db_lm3, lc->db_lm2, lc->p3d,
+  k_lcc_correspondences<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->pairs, lc->npairs, lc->db_lm3, lc->db_lm2, lc->p3d,
                                                                   lc->p2d);
   std::vector<uint64_t> seeds((size_t)nc);
   for (int i = 0; i < nc; i++) seeds[i] = ((uint64_t)(cand[i] + 1) << 32) + (uint64_t)lc->seq[cand[i]].n;  // (stream + 1) << 32 | kf_curr + 1
-  rc = flvis_hip_pnp_ransac(ctx, lc->p3d, lc->p2d, lc->npairs, LCC_CAP, nc, lc->K4, 100, 2.0, 0.99, seeds.data(), lc->pose, lc->mask, lc->ninl);
+  rc = flvis::pnp_ransac_dev(ctx, lc->p3d, lc->p2d, lc->npairs, LCC_CAP, nc, nullptr, &lc->d_cams[0].fx, flvis::LC_CAM_DOUBLES, cam_of, 100, 2.0,
+                             0.99, seeds.data(), lc->pose, lc->mask, lc->ninl);
   if (rc != FLVIS_OK) return rc;
   std::vector<int> h_np((size_t)nc), h_ni((size_t)nc);
   std::vector<double> h_pose((size_t)nc * 7);

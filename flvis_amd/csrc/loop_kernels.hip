@@ -26,6 +26,7 @@
 #include "dev_common.hpp"
 #include "dev_geom.hpp"
 #include "dev_math.hpp"
+#include "loop_kernels.hpp"
 #include "track_kernels.hpp"
 
 namespace flvis {
@@ -616,11 +617,7 @@ __global__ __launch_bounds__(PGO_T) void k_pgo(const PgoGraph* graphs) {
 
 
 // ---- 3-D positions of a keyframe's ORB keypoints (vo_loopclosing.cpp:255-372) ---------------------------------------------------
-struct LcCam {
-  double P0[12], P1[12];  // STEREO_RECT: the rectified projection matrices (dc.P0_, dc.P1_)
-  double fx, fy, cx, cy;  // DEPTH_D435
-  int cam_type, w, h;
-};
+// (LcCam, a keyframe's camera: loop_kernels.hpp)
 constexpr int LC_T = 1024;
 constexpr int LC_MAXF = 2048;
 
@@ -636,13 +633,16 @@ __global__ __launch_bounds__(256) void k_lc_points(const float* __restrict__ kps
   p0[o * 2 + 1] = p1[o * 2 + 1] = y;
 }
 
-// one workgroup per keyframe, two keypoints per thread: the mask of :280-349, then the ordered removal of :362-371
-__global__ __launch_bounds__(LC_T) void k_lc_landmarks(LcCam cam, const float* __restrict__ kps, const uint8_t* desc, const int* __restrict__ count,
+// one workgroup per keyframe, two keypoints per thread: the mask of :280-349, then the ordered removal of :362-371.  The keyframe's
+// camera is row cam_of[img] (cam_of null: row img) of a device table: the index depends on blockIdx.x alone, so the row's loads are scalar.
+__global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__ cams, const int* __restrict__ cam_of, int cam_type, int w, int h,
+                                                       const float* __restrict__ kps, const uint8_t* desc, const int* __restrict__ count,
                                                        int cap, const float* __restrict__ next_pts, const uint8_t* __restrict__ status,
                                                        const uint16_t* __restrict__ depth, float* lm_2d, double* lm_3d, uint8_t* lm_desc,
                                                        int* __restrict__ lm_count) {
   __shared__ int s_scan[LC_T / 64];
   const int img = blockIdx.x, t = threadIdx.x;
+  const LcCam& cam = cams[cam_of ? cam_of[img] : img];
   const int n = min(count[img], cap);
   bool keep[2] = {false, false};
   float xy[2][2];
@@ -657,7 +657,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(LcCam cam, const float* _
     xy[e][0] = x, xy[e][1] = y;
     const uint4* q = reinterpret_cast<const uint4*>(desc + o * 32);
     d[e][0] = q[0], d[e][1] = q[1];
-    if (cam.cam_type == 0) {
+    if (cam_type == 0) {
       if (status[o] == 1) {
         const V3 pc = triangulate_dlt((double)x, (double)y, (double)next_pts[o * 2], (double)next_pts[o * 2 + 1], cam.P0, cam.P1);
         if (!(pc.z < 0 || pc.z > (double)100.0f)) {  // trignaulationPtFromStereo, range = 100.0 (triangulation.h:24)
@@ -665,10 +665,10 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(LcCam cam, const float* _
           p3[e] = pc;
         }
       }
-    } else if (cam.cam_type == 2) {
+    } else if (cam_type == 2) {
       // img1.at<ushort>(Point2f): nearest-even rounding of the position; `ushort / 1000` is an integer division (:331)
-      const int ix = min(max(__float2int_rn(x), 0), cam.w - 1), iy = min(max(__float2int_rn(y), 0), cam.h - 1);
-      const double dm = (double)(depth[(size_t)img * cam.w * cam.h + (size_t)iy * cam.w + ix] / 1000);
+      const int ix = min(max(__float2int_rn(x), 0), w - 1), iy = min(max(__float2int_rn(y), 0), h - 1);
+      const double dm = (double)(depth[(size_t)img * w * h + (size_t)iy * w + ix] / 1000);
       if (dm >= 0.3 && dm <= 10) {
         keep[e] = true;
         p3[e] = V3{((double)x - cam.cx) / cam.fx * dm, ((double)y - cam.cy) / cam.fy * dm, dm};
@@ -769,49 +769,58 @@ int flvis_hip_bow_set_vocabulary(flvis_ctx* ctx, int n_nodes, const int* h_child
 
 // STEP 1.5 / 1.6 of the loop-closing keyframe (vo_loopclosing.cpp:255-372) for n_img keyframes: which ORB keypoints get a 3-D
 // position (stereo LK into img1 + DLT triangulation, or the depth image), and the keypoint / descriptor lists without the others.
+// The cameras are rows of a table on the device (flvis::lc_keyframe_landmarks_dev, after extern "C"): the loop closer keeps its
+// streams' table resident, the two entry points here upload the caller's rows.
+static int lc_landmarks_upload(flvis_ctx* ctx, int n_img, int cam_type, const double* h_P0, const double* h_P1, const double* h_K4, int row_stride,
+                               const LcCam** d_cams) {
+  *d_cams = nullptr;
+  if (cam_type != 0 && cam_type != 2) return FLVIS_OK;  // (bad values and the empty STEREO_UNRECT case are lc_keyframe_landmarks_dev's)
+  if (n_img <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: bad args");
+  if (cam_type == 0 && (!h_P0 || !h_P1)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: stereo needs img0, P0 and P1");
+  if (cam_type == 2 && !h_K4) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: the depth camera needs fx, fy, cx, cy");
+  std::vector<LcCam> rows((size_t)n_img);  // row_stride 0: one camera for every image
+  for (int i = 0; i < n_img; i++) {
+    LcCam& c = rows[i];
+    memset(&c, 0, sizeof(c));
+    if (cam_type == 0) {
+      memcpy(c.P0, h_P0 + (size_t)12 * row_stride * i, sizeof(c.P0));
+      memcpy(c.P1, h_P1 + (size_t)12 * row_stride * i, sizeof(c.P1));
+    } else {
+      const double* k = h_K4 + (size_t)4 * row_stride * i;
+      c.fx = k[0], c.fy = k[1], c.cx = k[2], c.cy = k[3];
+    }
+  }
+  hipSetDevice(ctx->device);
+  LcCam* d = (LcCam*)ctx->scratch("lc_cams", sizeof(LcCam) * (size_t)n_img);
+  if (!d) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks: scratch allocation failed");
+  hipError_t e = hipMemcpyAsync(d, rows.data(), sizeof(LcCam) * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the rows are a host temporary, the caller's arrays may go on return)
+  if (e != hipSuccess) return ctx->hip_fail(e, "lc_keyframe_landmarks");
+  *d_cams = d;
+  return FLVIS_OK;
+}
+
+int flvis_hip_lc_keyframe_landmarks_rigs(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
+                                         const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
+                                         const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+  CHECK_CTX(ctx);
+  const LcCam* cams = nullptr;
+  const int rc = lc_landmarks_upload(ctx, n_img, cam_type, h_P0, h_P1, h_K4, 1, &cams);
+  if (rc != FLVIS_OK) return rc;
+  return lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, w, h, n_img, cam_type, cams, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
+                                   d_lm_desc, d_lm_count);
+}
+
+// one camera for every keyframe: the same call on n_img equal rows
 int flvis_hip_lc_keyframe_landmarks(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
                                     const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
                                     const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
   CHECK_CTX(ctx);
-  if (!d_kps || !d_desc || !d_count || !d_lm_2d || !d_lm_3d || !d_lm_desc || !d_lm_count || n_img <= 0 || cap <= 0 || w <= 0 || h <= 0)
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: bad args");
-  if (cap > LC_MAXF) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_keyframe_landmarks: at most 2048 keypoints per keyframe");
-  if (cam_type < 0 || cam_type > 2) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: cam_type must be 0 (stereo rectified), 1 (stereo unrectified) or 2 (depth)");
-  // (d_lm_desc == d_desc is fine: every workgroup reads its keyframe's rows before the scan's barrier and writes after)
-  LcCam cam{};
-  cam.cam_type = cam_type, cam.w = w, cam.h = h;
-  hipStream_t st = ctx->stream;
-  if (cam_type == 1) {  // the reference's STEREO_UNRECT case is empty (:316-322): no keypoint gets a position
-    hipError_t e = hipMemsetAsync(d_lm_count, 0, sizeof(int) * (size_t)n_img, st);
-    if (e != hipSuccess) return ctx->hip_fail(e, "lc_keyframe_landmarks");
-    return FLVIS_OK;
-  }
-  if (!d_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: no second image");
-  const float* next = nullptr;
-  const uint8_t* status = nullptr;
-  if (cam_type == 0) {
-    if (!d_img0 || !h_P0 || !h_P1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: stereo needs img0, P0 and P1");
-    memcpy(cam.P0, h_P0, sizeof(cam.P0));
-    memcpy(cam.P1, h_P1, sizeof(cam.P1));
-    hipSetDevice(ctx->device);
-    const size_t np = (size_t)n_img * cap;
-    float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
-    float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
-    uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
-    if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks: scratch allocation failed");
-    k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, st>>>(d_kps, d_count, cap, p0, p1);
-    // calcOpticalFlowPyrLK(img0, img1, lm_img0, lm_img1, ., ., Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW)  (:274-278)
-    const int rc = flvis_hip_lk_track(ctx, d_img0, (const uint8_t*)d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
-    if (rc != FLVIS_OK) return rc;
-    next = p1, status = stt;
-  } else {
-    if (!h_K4) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: the depth camera needs fx, fy, cx, cy");
-    cam.fx = h_K4[0], cam.fy = h_K4[1], cam.cx = h_K4[2], cam.cy = h_K4[3];
-  }
-  k_lc_landmarks<<<n_img, LC_T, 0, st>>>(cam, d_kps, d_desc, d_count, cap, next, status, (const uint16_t*)d_img1, d_lm_2d, d_lm_3d, d_lm_desc,
-                                         d_lm_count);
-  CHECK_LAUNCH(ctx, "lc_keyframe_landmarks");
-  return FLVIS_OK;
+  const LcCam* cams = nullptr;
+  const int rc = lc_landmarks_upload(ctx, n_img, cam_type, h_P0, h_P1, h_K4, 0, &cams);
+  if (rc != FLVIS_OK) return rc;
+  return lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, w, h, n_img, cam_type, cams, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
+                                   d_lm_desc, d_lm_count);
 }
 
 int flvis_hip_bow_transform(flvis_ctx* ctx, const uint8_t* d_desc, const int* d_count, int dcap, int n_img, int vcap, int* d_ids,
@@ -873,20 +882,27 @@ int flvis_hip_pnp_ransac(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d,
                          int iterations, double reproj_px, double confidence, const uint64_t* h_seeds, double* d_pose7,
                          uint8_t* d_inlier_mask, int* d_n_inliers) {
   CHECK_CTX(ctx);
-  if (!d_p3d || !d_p2d || !d_count || !h_K4 || !h_seeds || !d_pose7 || !d_inlier_mask || !d_n_inliers || cap <= 0 || n_sets <= 0 ||
-      iterations <= 0 || !(reproj_px > 0) || !(confidence > 0 && confidence < 1))
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
-  if (cap > pnp_ransac_max_points()) return ctx->fail(FLVIS_ERR_CAPACITY, "pnp_ransac: at most 1024 correspondences per set");
+  if (!h_K4) return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
+  return pnp_ransac_dev(ctx, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, nullptr, 0, nullptr, iterations, reproj_px, confidence, h_seeds, d_pose7,
+                        d_inlier_mask, d_n_inliers);
+}
+
+// the same with one camera per set: the rows go to the device next to the seeds
+int flvis_hip_pnp_ransac_rigs(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
+                              int iterations, double reproj_px, double confidence, const uint64_t* h_seeds, double* d_pose7,
+                              uint8_t* d_inlier_mask, int* d_n_inliers) {
+  CHECK_CTX(ctx);
+  if (!h_K4 || n_sets <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
   hipSetDevice(ctx->device);
-  unsigned long long* seeds = (unsigned long long*)ctx->scratch("pnp_seeds", sizeof(unsigned long long) * (size_t)n_sets);
-  if (!seeds) return ctx->fail(FLVIS_ERR_HIP, "pnp_ransac: scratch allocation failed");
-  hipError_t e = hipMemcpyAsync(seeds, h_seeds, sizeof(unsigned long long) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (h_seeds is pageable caller memory)
-  if (e != hipSuccess) return ctx->hip_fail(e, "pnp_ransac seeds");
-  launch_pnp_ransac_sets(ctx->stream, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, 0, nullptr, seeds, iterations, reproj_px, confidence,
-                         d_pose7, d_inlier_mask, d_n_inliers);
-  CHECK_LAUNCH(ctx, "pnp_ransac");
-  return FLVIS_OK;
+  double* k4 = (double*)ctx->scratch("pnp_K4", sizeof(double) * 4 * (size_t)n_sets);
+  if (!k4) return ctx->fail(FLVIS_ERR_HIP, "pnp_ransac: scratch allocation failed");
+  // (pageable caller memory; pnp_ransac_dev waits for the stream after its seeds, before anything is launched)
+  const hipError_t e = hipMemcpyAsync(k4, h_K4, sizeof(double) * 4 * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, "pnp_ransac cameras");
+  const int rc = pnp_ransac_dev(ctx, d_p3d, d_p2d, d_count, cap, n_sets, nullptr, k4, 4, nullptr, iterations, reproj_px, confidence, h_seeds,
+                                d_pose7, d_inlier_mask, d_n_inliers);
+  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);  // (an argument refused before that wait: h_K4 may still be read)
+  return rc;
 }
 
 // cv::solvePnP(..., SOLVEPNP_EPNP) alone on n_sets correspondence sets (the solver inside flvis_hip_pnp_ransac and the tracker), with its
@@ -1110,3 +1126,66 @@ int flvis_loop_candidate(int g_size, const double* h_row, const uint8_t* h_prese
 }
 
 }  // extern "C"
+
+namespace flvis {
+
+int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type, const LcCam* d_cams,
+                              const int* d_cam_of, const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
+                              double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+  CHECK_CTX(ctx);
+  if (!d_kps || !d_desc || !d_count || !d_lm_2d || !d_lm_3d || !d_lm_desc || !d_lm_count || n_img <= 0 || cap <= 0 || w <= 0 || h <= 0)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: bad args");
+  if (cap > LC_MAXF) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_keyframe_landmarks: at most 2048 keypoints per keyframe");
+  if (cam_type < 0 || cam_type > 2) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: cam_type must be 0 (stereo rectified), 1 (stereo unrectified) or 2 (depth)");
+  // (d_lm_desc == d_desc is fine: every workgroup reads its keyframe's rows before the scan's barrier and writes after)
+  hipStream_t st = ctx->stream;
+  if (cam_type == 1) {  // the reference's STEREO_UNRECT case is empty (:316-322): no keypoint gets a position
+    hipError_t e = hipMemsetAsync(d_lm_count, 0, sizeof(int) * (size_t)n_img, st);
+    if (e != hipSuccess) return ctx->hip_fail(e, "lc_keyframe_landmarks");
+    return FLVIS_OK;
+  }
+  if (!d_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: no second image");
+  if (!d_cams) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: no camera table");
+  const float* next = nullptr;
+  const uint8_t* status = nullptr;
+  if (cam_type == 0) {
+    if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: stereo needs img0, P0 and P1");
+    hipSetDevice(ctx->device);
+    const size_t np = (size_t)n_img * cap;
+    float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
+    float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
+    uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
+    if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks: scratch allocation failed");
+    k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, st>>>(d_kps, d_count, cap, p0, p1);
+    // calcOpticalFlowPyrLK(img0, img1, lm_img0, lm_img1, ., ., Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW)  (:274-278)
+    const int rc = flvis_hip_lk_track(ctx, d_img0, (const uint8_t*)d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
+    if (rc != FLVIS_OK) return rc;
+    next = p1, status = stt;
+  }
+  k_lc_landmarks<<<n_img, LC_T, 0, st>>>(d_cams, d_cam_of, cam_type, w, h, d_kps, d_desc, d_count, cap, next, status, (const uint16_t*)d_img1,
+                                         d_lm_2d, d_lm_3d, d_lm_desc, d_lm_count);
+  CHECK_LAUNCH(ctx, "lc_keyframe_landmarks");
+  return FLVIS_OK;
+}
+
+int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
+                   const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
+                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers) {
+  CHECK_CTX(ctx);
+  if (!d_p3d || !d_p2d || !d_count || (!h_K4 && !d_K4) || !h_seeds || !d_pose7 || !d_inlier_mask || !d_n_inliers || cap <= 0 || n_sets <= 0 ||
+      iterations <= 0 || !(reproj_px > 0) || !(confidence > 0 && confidence < 1))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
+  if (cap > pnp_ransac_max_points()) return ctx->fail(FLVIS_ERR_CAPACITY, "pnp_ransac: at most 1024 correspondences per set");
+  hipSetDevice(ctx->device);
+  unsigned long long* seeds = (unsigned long long*)ctx->scratch("pnp_seeds", sizeof(unsigned long long) * (size_t)n_sets);
+  if (!seeds) return ctx->fail(FLVIS_ERR_HIP, "pnp_ransac: scratch allocation failed");
+  hipError_t e = hipMemcpyAsync(seeds, h_seeds, sizeof(unsigned long long) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (h_seeds is pageable caller memory)
+  if (e != hipSuccess) return ctx->hip_fail(e, "pnp_ransac seeds");
+  launch_pnp_ransac_sets(ctx->stream, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, d_K4, k4_stride, d_cam_of, 0, nullptr, seeds, iterations,
+                         reproj_px, confidence, d_pose7, d_inlier_mask, d_n_inliers);
+  CHECK_LAUNCH(ctx, "pnp_ransac");
+  return FLVIS_OK;
+}
+
+}  // namespace flvis

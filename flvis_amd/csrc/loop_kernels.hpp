@@ -1,0 +1,28 @@
+// flvis_amd: what loop_kernels.hip offers the loop closer (loop_closer.hip) beside the C ABI -- the two kernels that read a camera, on a
+// camera table that is already resident on the device.
+#pragma once
+#include <cstdint>
+
+#include "ctx.hpp"
+
+namespace flvis {
+
+// one camera of the loop closing (a row of the device table k_lc_landmarks and k_pnp_ransac_sets index)
+struct LcCam {
+  double P0[12], P1[12];  // STEREO_RECT: the rectified projection matrices (dc.P0_, dc.P1_)
+  double fx, fy, cx, cy;  // DEPTH_D435 back-projection and the K of solvePnPRansac (dc.K0_rect)
+};
+constexpr int LC_CAM_DOUBLES = 28;  // a row as doubles: the stride of &cams[0].fx for pnp_ransac_dev
+static_assert(sizeof(LcCam) == LC_CAM_DOUBLES * sizeof(double), "LcCam is a plain row of doubles");
+
+// flvis_hip_lc_keyframe_landmarks_rigs on a DEVICE table: image i uses d_cams[d_cam_of ? d_cam_of[i] : i].  Uploads nothing.
+int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type, const LcCam* d_cams,
+                              const int* d_cam_of, const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
+                              double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
+// flvis_hip_pnp_ransac_rigs on a DEVICE table: set i uses fx fy cx cy = d_K4 + k4_stride * (d_cam_of ? d_cam_of[i] : i) (k4_stride in
+// doubles).  d_K4 == nullptr: every set uses h_K4.  (h_seeds is uploaded as in flvis_hip_pnp_ransac.)
+int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
+                   const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
+                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
+
+}  // namespace flvis

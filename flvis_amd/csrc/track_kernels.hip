@@ -1822,10 +1822,12 @@ __global__ __launch_bounds__(64) void k_pnp_tail_cv(Pipe p) {
 
 // The same solver on caller-supplied correspondences: the geometric check of the loop closing, isLoopClosureKF
 // (vo_loopclosing.cpp:660-686: solvePnPRansac(p3d, p2d, K, Mat(), r, t, false, 100, 2.0, 0.99, inliers, SOLVEPNP_P3P)); one
-// workgroup per correspondence set.
+// workgroup per correspondence set.  cams != null: set b's fx fy cx cy are the four doubles at cams + cam_stride * (cam_of ? cam_of[b] : b)
+// -- a camera per set, e.g. a row of the loop closer's per-stream table (the index is wave-uniform: scalar loads); null: the arguments.
 constexpr int PNP_MAXN = 1024;
 __global__ __launch_bounds__(RP_T) void k_pnp_ransac_sets(const float* __restrict__ p3d, const float* __restrict__ p2d,
                                                           const int* __restrict__ count, int cap, double fx, double fy, double cx, double cy,
+                                                          const double* __restrict__ cams, int cam_stride, const int* __restrict__ cam_of,
                                                           int iterative, const double* __restrict__ guess7,
                                                           const unsigned long long* __restrict__ seeds, int max_iters, float t2, double conf,
                                                           double* __restrict__ pose7, unsigned char* __restrict__ mask,
@@ -1842,6 +1844,10 @@ __global__ __launch_bounds__(RP_T) void k_pnp_ransac_sets(const float* __restric
   __shared__ double gn[32];
   __shared__ epnp::Work ework[RP_T / 64];
   __shared__ short sinl[PNP_MAXN];
+  if (cams) {
+    const double* const k = cams + (size_t)cam_stride * (cam_of ? cam_of[b] : b);
+    fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+  }
   int np = count[b];
   np = np < 0 ? 0 : (np > cap ? cap : np);
   for (int i = tid; i < np; i += RP_T) {
@@ -2917,11 +2923,14 @@ void launch_pnp_tail_cv(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_pn
 int pnp_ransac_max_points() { return PNP_MAXN; }
 static hipError_t pnp_tables_init();
 void launch_pnp_ransac_sets(hipStream_t st, const float* p3d, const float* p2d, const int* count, int cap, int n_sets, const double* K4,
-                            int iterative, const double* guess7, const unsigned long long* seeds, int max_iters, double reproj_px,
-                            double conf, double* pose7, unsigned char* mask, int* n_inliers) {
+                            const double* d_cams, int cam_stride, const int* d_cam_of, int iterative, const double* guess7,
+                            const unsigned long long* seeds, int max_iters, double reproj_px, double conf, double* pose7, unsigned char* mask,
+                            int* n_inliers) {
   (void)pnp_tables_init();  // (the loop closing may use the solver without a tracker)
-  hipLaunchKernelGGL(k_pnp_ransac_sets, dim3(n_sets), dim3(RP_T), 0, st, p3d, p2d, count, cap, K4[0], K4[1], K4[2], K4[3], iterative,
-                     guess7, seeds, max_iters, (float)(reproj_px * reproj_px), conf, pose7, mask, n_inliers);
+  const double none[4] = {0, 0, 0, 0};
+  if (!K4) K4 = none;  // (not read when a device table is given)
+  hipLaunchKernelGGL(k_pnp_ransac_sets, dim3(n_sets), dim3(RP_T), 0, st, p3d, p2d, count, cap, K4[0], K4[1], K4[2], K4[3], d_cams, cam_stride,
+                     d_cam_of, iterative, guess7, seeds, max_iters, (float)(reproj_px * reproj_px), conf, pose7, mask, n_inliers);
 }
 void launch_track_post(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_track_post, dim3((p.S + 63) / 64), dim3(64), 0, st, p);

@@ -134,9 +134,11 @@ void launch_frame_begin(hipStream_t st, const Pipe& p, const double* d_time);
 int pnp_ransac_max_points();
 constexpr int EPNP_DBG_N = 160;  // doubles per set of launch_epnp_sets's output
 void launch_epnp_sets(hipStream_t st, const float* p3d, const float* p2d, const int* count, int cap, int n_sets, const double* K4, double* out);
+// K4: fx fy cx cy of every set (host); or d_cams (device, non-null): set b's four doubles at d_cams + cam_stride * (d_cam_of ? d_cam_of[b] : b)
 void launch_pnp_ransac_sets(hipStream_t st, const float* p3d, const float* p2d, const int* count, int cap, int n_sets, const double* K4,
-                            int iterative, const double* guess7, const unsigned long long* seeds, int max_iters, double reproj_px,
-                            double conf, double* pose7, unsigned char* mask, int* n_inliers);
+                            const double* d_cams, int cam_stride, const int* d_cam_of, int iterative, const double* guess7,
+                            const unsigned long long* seeds, int max_iters, double reproj_px, double conf, double* pose7, unsigned char* mask,
+                            int* n_inliers);
 void launch_store_progress(hipStream_t st, long long* host_word, long long v);  // stream-ordered store into host-mapped memory
 void launch_store_flag(hipStream_t st, long long* word, long long v);  // stream-ordered store of a sequence number into a device word
 void launch_wait_flag(hipStream_t st, const long long* flag, int n_words, long long seq, long long* err_word);  // stream-ordered wait for an upload's sequence block

@@ -18,8 +18,8 @@
  *   flvis_hip_orb_detect_and_compute / _hamming_knn2 / _orb_match  <- cv::ORB, cv::BFMatcher   src/backend/vo_loopclosing.cpp:242-243,601-639
  *   flvis_hip_bow_load_vocabulary / _set_vocabulary / _transform / _score / _score_jobs, flvis_loop_candidate
  *                                <- DBoW3::Vocabulary(file), ::transform, ::score; isLoopCandidate   vo_loopclosing.cpp:1097,249-253,417-437,520-590
- *   flvis_hip_lc_keyframe_landmarks  <- stereo LK + triangulation / depth lookup of the ORB keypoints   vo_loopclosing.cpp:255-372
- *   flvis_hip_pnp_ransac         <- cv::solvePnPRansac of isLoopClosureKF                             vo_loopclosing.cpp:660-686
+ *   flvis_hip_lc_keyframe_landmarks(_rigs)  <- stereo LK + triangulation / depth lookup of the ORB keypoints   vo_loopclosing.cpp:255-372
+ *   flvis_hip_pnp_ransac(_rigs)  <- cv::solvePnPRansac of isLoopClosureKF                             vo_loopclosing.cpp:660-686
  *   flvis_hip_pgo_loop_closure   <- loopClosureOnCovGraphG2ONew (g2o EdgeSE3 pose graph)              vo_loopclosing.cpp:742-944
  * Pipeline-level entry points (the nodelets' work for a batch of streams / sequences):
  *   flvis_config_load, flvis_tracker_create, flvis_imu_feed, flvis_image_feed(_host), flvis_get_*   <- TrackingNodeletClass / F2FTracking
@@ -177,6 +177,12 @@ int flvis_hip_bow_transform(flvis_ctx* ctx, const uint8_t* d_desc, const int* d_
 int flvis_hip_lc_keyframe_landmarks(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
                                     const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
                                     const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
+/* as flvis_hip_lc_keyframe_landmarks with one camera per image: h_P0 / h_P1 [n_img][12] (cam_type 0), h_K4 [n_img][4] (cam_type 2).  Image i
+ * gets bit for bit what the call above gives it alone with row i; w, h and cam_type hold for the whole call.  The host arrays may be freed
+ * when the call returns. */
+int flvis_hip_lc_keyframe_landmarks_rigs(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
+                                         const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
+                                         const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
 /* one row of the similarity matrix (vo_loopclosing.cpp:417-437): voc.score(query, db[j]) for j < n_db (ScoringObject.cpp:23-68);
  * the query is one vector on the device (d_q_nnz[0] entries), the database [n_db][vcap]; d_db_nnz[j] < 0 marks an absent keyframe
  * (kf_lc_tmp[j] == nullptr: score 0). */
@@ -203,6 +209,11 @@ int flvis_loop_candidate(int g_size, const double* h_row, const uint8_t* h_prese
 int flvis_hip_pnp_ransac(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
                          int iterations, double reproj_px, double confidence, const uint64_t* h_seeds, double* d_pose7,
                          uint8_t* d_inlier_mask, int* d_n_inliers);
+/* as flvis_hip_pnp_ransac with one camera per set: h_K4 [n_sets][4]; set i gets bit for bit what the call above gives it alone with row i.
+ * The host arrays may be freed when the call returns. */
+int flvis_hip_pnp_ransac_rigs(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets,
+                              const double* h_K4, int iterations, double reproj_px, double confidence, const uint64_t* h_seeds,
+                              double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
 /* Test hook: cv::solvePnP(..., SOLVEPNP_EPNP) alone (the solver inside flvis_hip_pnp_ransac and the tracker's PnP RANSAC) on n_sets
  * correspondence sets laid out as for flvis_hip_pnp_ransac (d_count[i] >= 4 points each), one wavefront per set.  d_out160 [n_sets][160]:
  * R (9, row-major) t (3) ok (1) | betas of the three approximations (12) | their mean reprojection errors (3) | the four eigenvectors of
@@ -296,7 +307,8 @@ int flvis_tracker_create(flvis_ctx* ctx, const flvis_cfg* cfg, int n_streams, ui
  * vifusion_para.  Batch-wide -- every config must match cfgs[0] exactly, as they size buffers and pick code paths: type_of_vi (and so
  * cam_type, imu_type), image_width, image_height, feature_para[0..5], window_size, skip_first_n_imgs, need_equal_hist.  A config that
  * differs in one of them returns FLVIS_ERR_CONFIG (flvis_last_error names the field and the stream) and creates nothing: a tracker the
- * context already holds is kept.  Every check of flvis_tracker_create applies to each config.  The loop closer keeps its single config. */
+ * context already holds is kept.  Every check of flvis_tracker_create applies to each config.  (The loop closer's counterpart:
+ * flvis_loop_closer_create_rigs.) */
 int flvis_tracker_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_streams, uint64_t seed_base, int traj_capacity);
 /* The config stream `stream` runs on: the one it was created or last reset with (flvis_reset_streams_rigs). */
 int flvis_get_stream_cfg(flvis_ctx* ctx, int stream, flvis_cfg* out);
@@ -613,7 +625,7 @@ int flvis_ba_push_keyframe_imu(flvis_ctx* ctx, int stream, int64_t frame_id, con
 /* ---- the loop-closing nodelet's control flow for a batch of independent sequences --------------------------------
  * LoopClosingNodeletClass (src/backend/vo_loopclosing.cpp:118-1119) without ROS: the keyframe database stays on the device.
  *   flvis_lc_params_load             <- onInit's LC_PARAS block                  :955-963
- *   flvis_loop_closer_create         <- onInit (camera from the same yaml, vocabulary already in the context: :1095-1101)
+ *   flvis_loop_closer_create(_rigs)  <- onInit (camera from the same yaml, vocabulary already in the context: :1095-1101)
  *   flvis_loop_closer_add_keyframes  <- frame_callback + kfmsgProcess            :178-391
  *   flvis_loop_closer_process        <- one pass of pgoProcess per new keyframe  :393-518 (+ :520-944)
  * The reference's pgoProcess thread polls the newest keyframe (a keyframe may be examined twice or never); here every keyframe is
@@ -639,6 +651,32 @@ int flvis_lc_params_load(const char* yaml_path, flvis_lc_params* prm, char* err,
  * flvis_hip_orb_detect_and_compute (NULL = the built-in pattern). */
 int flvis_loop_closer_create(flvis_ctx* ctx, const flvis_cfg* cfg, const flvis_lc_params* prm, int n_streams, int max_keyframes,
                              const int8_t* h_orb_pattern, flvis_loop_closer** out);
+/* The same with one finalized config per sequence (cfgs[0 .. n_streams)): a fleet of cameras that are calibrated each on its own, closed in
+ * one batch.  Sequence s behaves bit for bit as sequence s of flvis_loop_closer_create(ctx, &cfgs[s], ...); flvis_loop_closer_create is this
+ * call on n_streams copies of cfg.  Per sequence: what the closer reads from a config for geometry -- P0 and P1 (the stereo triangulation),
+ * and with them K = P0[0], P0[5], P0[2], P0[6] (the depth camera's back-projection and the solvePnPRansac of the geometric check).
+ * Batch-wide -- every config must match cfgs[0]: cam_type, image_width, image_height (they size buffers and pick the kernels' paths); so are
+ * prm and the ORB pattern.  A config that differs in one of them returns FLVIS_ERR_CONFIG (flvis_last_error names the field and the
+ * sequence) and creates nothing.  No other field is read.  depth_factor in particular is neither checked nor used: the depth camera's
+ * branch divides the Z16 value by 1000, an integer division, as the reference writes it (vo_loopclosing.cpp:331), whatever the yaml says. */
+int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const flvis_lc_params* prm, int n_streams, int max_keyframes,
+                                  const int8_t* h_orb_pattern, flvis_loop_closer** out);
+/* Start over on the named sequences (distinct indices in [0, n_streams)): from the next call on, each returns bit for bit what sequence 0
+ * of a closer just created on that sequence's config returns for the same keyframes -- keyframe ids from 0, events, similarity rows,
+ * flvis_loop_closer_keyframe contents, poses and drift.  Emptied: the keyframes (the slot's whole max_keyframes capacity is free again),
+ * T_odom_map (the identity), the loop list, the pose graph's trigger, the newest similarity row; a keyframe that was added and not yet
+ * processed is discarded (the next flvis_loop_closer_process reports kf_curr = -1 for the sequence).  Until the sequence's next keyframe
+ * flvis_loop_closer_poses and _similarity_row give *n_out = 0 and flvis_loop_closer_keyframe fails for every index.  The other sequences are
+ * not disturbed.  n == 0: no-op.  A stream out of range or listed twice: FLVIS_ERR_INVALID_ARG and nothing changes.  Returns without
+ * waiting for the device.
+ * _rigs: sequence streams[i] also changes to the camera of cfgs[i] (another unit taking over the slot; the table on the device is updated
+ * in stream order from memory the closer owns: cfgs may go away on return).  Every config is checked first against the closer's batch-wide
+ * fields as flvis_loop_closer_create_rigs checks it: one that differs returns FLVIS_ERR_CONFIG and nothing changes.  A tracker slot and
+ * its closer slot change hands together: flvis_reset_streams_rigs + flvis_loop_closer_reset_rigs. */
+int flvis_loop_closer_reset(flvis_loop_closer* lc, int n, const int* streams);
+int flvis_loop_closer_reset_rigs(flvis_loop_closer* lc, int n, const int* streams, const flvis_cfg* cfgs);
+/* The config sequence `stream` runs on: the one it was created or last reset with. */
+int flvis_loop_closer_stream_cfg(flvis_loop_closer* lc, int stream, flvis_cfg* out);
 /* (destroy it before the context it was created on: every other call runs on that context's stream) */
 void flvis_loop_closer_destroy(flvis_loop_closer* lc);
 /* one keyframe for each of the n sequences h_stream[i] (distinct): d_img0 [n][h][w] mono8, d_img1 [n][h][w] mono8 (stereo) or Z16

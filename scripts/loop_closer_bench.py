@@ -3,7 +3,10 @@
 Times add_keyframes (ORB + bag of words + 3-D landmarks + store) and process (similarity row, candidates, verification of all
 candidates at once, pose graphs) per batch with HIP events around the calls; prints one JSON line.
 
-usage: loop_closer_bench.py [n_streams=64] [n_keyframes=60]"""
+--rigs: a mixed fleet instead of one config -- sequence s runs on unit s % 4 of synth.rig_variant("d435i_stereo", .), rendered with that
+unit's rig, all in one closer (flvis_loop_closer_create_rigs).
+
+usage: loop_closer_bench.py [--rigs] [n_streams=64] [n_keyframes=60]"""
 import json
 import os
 import sys
@@ -22,19 +25,39 @@ import _loop_chain as LC
 import _pgo_synth as PS
 import _voc as V
 
-S = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 60
+RIGS = "--rigs" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--rigs"]
+S = int(args[0]) if len(args) > 0 else 64
+N = int(args[1]) if len(args) > 1 else 60
 PER = 50
+N_UNITS = 4
 
 ctx = flvis_amd.Context(0)
-p = os.path.join(tempfile.gettempdir(), "flvis_loop_closer_bench.yaml")
-open(p, "w").write(synth.D435I_STEREO_YAML)
-cfg = flvis_amd.load_config(p)
 trs = [LC.LoopTrajectory(phase=2 * np.pi * s / S) for s in range(S)]
-rnd = synth.Renderer("cuda")
 times = LC.keyframe_times(N, PER)
-frames = [rnd.stereo_frame(trs, t, i) for i, t in enumerate(times)]
-gt = [[G.pose7(*tr.T_c_w(t, rnd.rig)) for t in times] for tr in trs]
+if RIGS:
+    units = []
+    for k in range(N_UNITS):
+        rig, text = synth.rig_variant("d435i_stereo", k)
+        p = os.path.join(tempfile.gettempdir(), "flvis_loop_closer_bench_%d.yaml" % k)
+        open(p, "w").write(text)
+        units.append((synth.Renderer("cuda", rig=rig), flvis_amd.load_config(p)))
+    cfg = [units[s % N_UNITS][1] for s in range(S)]
+    rigs = [units[s % N_UNITS][0].rig for s in range(S)]
+    order = [s for k in range(N_UNITS) for s in range(k, S, N_UNITS)]   # every unit renders its own sequences; then back in sequence order
+    back = torch.tensor(np.argsort(order), device="cuda")
+    frames = []
+    for i, t in enumerate(times):
+        parts = [units[k][0].stereo_frame([trs[s] for s in range(k, S, N_UNITS)], t, i) for k in range(min(N_UNITS, S))]
+        frames.append(tuple(torch.cat([q[c] for q in parts])[back].contiguous() for c in range(2)))
+else:
+    p = os.path.join(tempfile.gettempdir(), "flvis_loop_closer_bench.yaml")
+    open(p, "w").write(synth.D435I_STEREO_YAML)
+    cfg = flvis_amd.load_config(p)
+    rnd = synth.Renderer("cuda")
+    rigs = [rnd.rig] * S
+    frames = [rnd.stereo_frame(trs, t, i) for i, t in enumerate(times)]
+gt = [[G.pose7(*trs[s].T_c_w(t, rigs[s])) for t in times] for s in range(S)]
 odom = [LC.drifted_odometry(gt[s], 100 + s, sigma_t=0.008, sigma_r=0.002) for s in range(S)]
 train = []
 for i in range(0, N, 6):
@@ -62,7 +85,7 @@ gap1 = np.mean([PS.loop_gap(lc.poses(s), np.array(gt[s]), 2, N - 1)[0] for s in 
 quiet = [i for i in range(5, N) if n_cand[i] == 0]
 busy = [i for i in range(N) if n_opt[i] > 0]
 print(json.dumps({
-    "n_streams": S, "n_keyframes": N,
+    "n_streams": S, "n_keyframes": N, "rig_units": N_UNITS if RIGS else 1,
     "add_keyframes_ms_per_batch": float(np.mean([t_add[i] for i in range(5, N)])),
     "process_ms_per_batch_no_candidate": float(np.mean([t_proc[i] for i in quiet])) if quiet else None,
     "process_ms_per_batch_with_pose_graphs": float(np.mean([t_proc[i] for i in busy])) if busy else None,
