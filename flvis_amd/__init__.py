@@ -574,6 +574,18 @@ class LcEvent(C.Structure):
                 ("chi2_before", C.c_double), ("chi2_after", C.c_double)]
 
 
+FLVIS_LC_FIX_CAND = 8
+
+
+class FlvisLcFix(C.Structure):
+    """flvis_lc_fix of include/flvis_hip.h: what flvis_loop_closer_localize reports for one query."""
+    _fields_ = [("n_landmarks", C.c_int), ("n_candidates", C.c_int), ("best", C.c_int), ("reserved", C.c_int),
+                ("cand_kf", C.c_int64 * FLVIS_LC_FIX_CAND), ("cand_score", C.c_double * FLVIS_LC_FIX_CAND),
+                ("cand_matches", C.c_int * FLVIS_LC_FIX_CAND), ("cand_inliers", C.c_int * FLVIS_LC_FIX_CAND),
+                ("cand_accepted", C.c_int * FLVIS_LC_FIX_CAND), ("cand_pose7", (C.c_double * 7) * FLVIS_LC_FIX_CAND),
+                ("T_c_map7", C.c_double * 7)]
+
+
 def load_lc_params(yaml_path):
     """flvis_lc_params_load: the loop-closing block of the reference's yaml files.  Host-only."""
     prm = LcParams()
@@ -701,6 +713,67 @@ class LoopCloser:
         return [dict(kf_prev=int(e.kf_prev), kf_curr=int(e.kf_curr), candidate=bool(e.candidate), n_matches=e.n_matches,
                      n_inliers=e.n_inliers, accepted=bool(e.loop_accepted), optimised=bool(e.optimised), pgo_iterations=e.pgo_iterations,
                      pose=[float(x) for x in e.loop_pose7], chi2_before=e.chi2_before, chi2_after=e.chi2_after) for e in ev]
+
+    @staticmethod
+    def _fixes(fix):
+        import numpy as np
+        out = []
+        for f in fix:
+            cands = [dict(kf=int(f.cand_kf[r]), score=float(f.cand_score[r]), n_matches=f.cand_matches[r], n_inliers=f.cand_inliers[r],
+                          accepted=bool(f.cand_accepted[r]), pose=np.array(f.cand_pose7[r][:])) for r in range(f.n_candidates)]
+            out.append(dict(n_landmarks=f.n_landmarks, candidates=cands, best=f.best, kf=cands[f.best]["kf"] if f.best >= 0 else -1,
+                            T_c_map=np.array(f.T_c_map7[:]) if f.best >= 0 else None))
+        return out
+
+    def localize(self, streams, img0, img1, n_best=4):
+        """flvis_loop_closer_localize: one query frame for each of the sequences `streams` (distinct), images as add_keyframes takes them;
+        nothing is stored.  -> one dict per query: n_landmarks, candidates (the up to n_best best-scoring keyframes of the sequence, each a
+        dict kf / score / n_matches / n_inliers / accepted / pose), best (index into candidates, -1: not localised), kf (its keyframe) and
+        T_c_map (the query camera's pose7 in the map frame, None when not localised)."""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        n = len(st)
+        img0 = img0.contiguous()
+        img1 = img1.contiguous() if img1 is not None else None
+        hw = (int(self.cfg.image_height), int(self.cfg.image_width))
+        assert img0.shape[0] == n and tuple(img0.shape[1:]) == hw, "img0 must be [n, image_height, image_width]"
+        if img1 is not None:                                 # a wrong-size tensor would be read out of bounds on the device
+            assert img1.shape[0] == n and tuple(img1.shape[1:]) == hw, "img1 must be [n, image_height, image_width]"
+            assert img1.element_size() == (2 if self.cfg.cam_type == 2 else 1), "img1: uint8 (stereo) or 16-bit depth (depth rig)"
+        fix = (FlvisLcFix * max(1, n))()
+        self._lib.flvis_loop_closer_localize.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,
+                                                         C.POINTER(FlvisLcFix)]
+        self._ctx._check(self._lib.flvis_loop_closer_localize(self._h, n, _P(st, C.c_int), _ptr(img0), _ptr(img1), int(n_best), fix),
+                         "loop_closer_localize")
+        return self._fixes(fix[:n])
+
+    def localize_host(self, streams, img0, img1, n_best=4):
+        """flvis_loop_closer_localize_host: localize on numpy images as add_keyframes_host takes them (rows may be padded)."""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        n = len(st)
+        a = (FlvisImage * max(1, n))()
+        b = (FlvisImage * max(1, n))()
+        keep = []
+        for i in range(n):
+            for arr, dst in ((img0[i], a), (img1[i], b)):
+                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
+                keep.append(arr)
+                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
+        fix = (FlvisLcFix * max(1, n))()
+        self._lib.flvis_loop_closer_localize_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(FlvisImage),
+                                                              C.POINTER(FlvisImage), C.c_int, C.POINTER(FlvisLcFix)]
+        self._ctx._check(self._lib.flvis_loop_closer_localize_host(self._h, n, _P(st, C.c_int), a, b, int(n_best), fix),
+                         "loop_closer_localize_host")
+        return self._fixes(fix[:n])
+
+    def set_drift(self, stream, T_odom_map):
+        """flvis_loop_closer_set_drift: the sequence's T_odom_map from now on (keyframes added afterwards get T_c_w_odom * T_odom_map).
+        After a tracker slot was reset: set_drift(s, mul(inv(T_c_odom), localize(...)["T_c_map"])) ties its new odometry frame to the map."""
+        import numpy as np
+        T = np.ascontiguousarray(T_odom_map, np.float64).reshape(7)
+        self._lib.flvis_loop_closer_set_drift.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        self._ctx._check(self._lib.flvis_loop_closer_set_drift(self._h, int(stream), _P(T, C.c_double)), "loop_closer_set_drift")
 
     def poses(self, stream=0, cap=None):
         import numpy as np

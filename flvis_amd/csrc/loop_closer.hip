@@ -6,6 +6,8 @@
 //   flvis_loop_closer_process        <- pgoProcess     :393-518   similarity row, the `size < 50` gate, isLoopCandidate (:520-590),
 //                                                      isLoopClosureKF (:593-735), the loop list, the PGO trigger (:488-497),
 //                                                      loopClosureOnCovGraphG2ONew (:742-944) and T_odom_map *= Tw1_w2 (:908)
+//   flvis_loop_closer_localize       (the project's own) a query frame against its sequence's whole database: isLoopClosureKF's check on
+//                                                      the n_best best-scoring keyframes, the camera's pose in the map frame; stores nothing
 //
 // The keyframe database (bag-of-words vectors, compacted ORB descriptors with their pixels and 3-D positions, T_c_w) lives in HBM
 // for the whole run -- 76 KB per keyframe -- and never returns to the host; per keyframe the host sees one similarity row, and per
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -37,6 +40,8 @@ namespace {
 constexpr int LCC_CAP = 1024;   // keypoints per keyframe (the reference extracts 1000) = correspondences per PnP set
 constexpr int LCC_VCAP = 1024;  // bag-of-words entries per keyframe
 constexpr size_t LCC_STAGE = 7 * sizeof(double) + 2 * sizeof(int);  // bytes per keyframe of an add call's one upload
+constexpr size_t LCC_QSTAGE = LCC_STAGE + sizeof(int);              // ... per query of a localize call's (the sequence's keyframe count too)
+constexpr int LCC_NBEST = FLVIS_LC_FIX_CAND;                        // candidates per query of a localize call
 
 // ---- pose7 = tx ty tz qx qy qz qw on the host (Sophus::SE3 products of :377, :908) -------------------------------------------
 void q_mul(const double* a, const double* b, double* o) {  // Hamilton product, x y z w
@@ -124,6 +129,69 @@ __global__ __launch_bounds__(256) void k_lcc_correspondences(const int* __restri
   p2d[o * 2] = u, p2d[o * 2 + 1] = v;
 }
 
+// What a localize call brings back in ONE copy: per set (= query * n_best + rank) the candidate and its pair check, per query the counts.
+// Laid out for the closer's capacity (ns_cap = n_streams * LCC_NBEST sets, q_cap = n_streams queries), whatever a call uses of it.
+struct LcFixOut {
+  double *score, *pose, *T_kf;  // [ns_cap], [ns_cap][7] the PnP pose, [ns_cap][7] the candidate's T_c_w in the database
+  int *kf, *npairs, *ninl;      // [ns_cap] keyframe index (-1: an empty rank), matches, inliers
+  int *ncand, *nlm;             // [q_cap] candidates, the query's kept landmarks
+  static size_t bytes(size_t ns_cap, size_t q_cap) { return ns_cap * (15 * sizeof(double) + 3 * sizeof(int)) + q_cap * 2 * sizeof(int); }
+  static LcFixOut at(void* base, size_t ns_cap, size_t q_cap) {
+    LcFixOut o;
+    o.score = (double*)base, o.pose = o.score + ns_cap, o.T_kf = o.pose + 7 * ns_cap;
+    o.kf = (int*)(o.T_kf + 7 * ns_cap), o.npairs = o.kf + ns_cap, o.ninl = o.npairs + ns_cap;
+    o.ncand = o.ninl + ns_cap, o.nlm = o.ncand + q_cap;
+    return o;
+  }
+};
+
+// The candidates of a localize call, one wave per query: the n_best keyframes of the query's sequence with the highest score (> 0 and
+// >= min_score), score descending, equal scores by keyframe index ascending.  Rank by rank: every lane scans its stride of the row for
+// the entry that comes next in that order after the previous pick, then the wave reduces with the same rule -- no LDS, no sort, any n.
+// Per set it writes what the pair check reads (the keyframe's slot, the query's slot, the camera row) and what the host gets back; a
+// rank without a candidate gets the closer's empty slot on both sides (landmark count 0): its set is empty from k_lcc_fetch on.
+__global__ __launch_bounds__(64) void k_lcc_select(const int* __restrict__ q_slot, const int* __restrict__ q_seq, const int* __restrict__ q_n,
+                                                   const double* __restrict__ rows, int maxkf, int n_best, double min_score, int empty_slot,
+                                                   const int* __restrict__ lmc, const double* __restrict__ db_T, int* slot_a, int* slot_b,
+                                                   int* cam_of, LcFixOut out) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const int s = q_seq[i], n = q_n[i];
+  const double* const row = rows + (size_t)s * maxkf;
+  double prev_sc = 0.0;
+  int prev_j = -1, cnt = 0;  // prev_j < 0: nothing picked yet
+  bool more = true;
+  for (int r = 0; r < n_best; r++) {
+    double b_sc = 0.0;
+    int b_j = INT_MAX;  // INT_MAX: none
+    if (more)
+      for (int j = lane; j < n; j += 64) {
+        const double sc = row[j];
+        if (!(sc > 0.0 && sc >= min_score)) continue;
+        if (prev_j >= 0 && !(sc < prev_sc || (sc == prev_sc && j > prev_j))) continue;  // picked already
+        if (b_j == INT_MAX || sc > b_sc) b_sc = sc, b_j = j;  // (j ascends within a lane: an equal score later in the stride loses)
+      }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const double o_sc = __shfl_xor(b_sc, d);
+      const int o_j = __shfl_xor(b_j, d);
+      if (o_j != INT_MAX && (b_j == INT_MAX || o_sc > b_sc || (o_sc == b_sc && o_j < b_j))) b_sc = o_sc, b_j = o_j;
+    }
+    more = b_j != INT_MAX;  // (wave-uniform: every lane holds the reduction's result)
+    const int set = i * n_best + r;
+    const int ks = more ? s * maxkf + b_j : empty_slot;
+    if (lane < 7) out.T_kf[(size_t)set * 7 + lane] = more ? db_T[(size_t)ks * 7 + lane] : (lane == 6 ? 1.0 : 0.0);
+    if (lane == 0) {
+      slot_a[set] = ks;
+      slot_b[set] = more ? q_slot[i] : empty_slot;
+      cam_of[set] = s;
+      out.kf[set] = more ? b_j : -1;
+      out.score[set] = more ? b_sc : 0.0;
+    }
+    if (more) prev_sc = b_sc, prev_j = b_j, cnt++;
+  }
+  if (lane == 0) out.ncand[i] = cnt, out.nlm[i] = lmc[i];
+}
+
 using flvis::LcCam;
 
 struct Seq {
@@ -148,7 +216,8 @@ struct flvis_loop_closer {
   // the sequences' cameras: [S] rows on the device, written in stream order from the pinned host copy (a reset does not wait)
   LcCam* h_cams = nullptr;
   LcCam* d_cams = nullptr;
-  // keyframe database, [S * maxkf] slots
+  // keyframe database, [S * maxkf] slots; behind them one query slot per sequence (what a localize call holds of its query, stream s at
+  // S * maxkf + s) and one slot that stays empty (S * maxkf + S: no landmarks, no words)
   int* db_ids = nullptr;
   double* db_vals = nullptr;
   int* db_nnz = nullptr;
@@ -164,6 +233,12 @@ struct flvis_loop_closer {
       *nb = nullptr, *pairs = nullptr, *npairs = nullptr, *ninl = nullptr;
   uint8_t* stage = nullptr;  // one upload per add call: [n][7] poses, [n] slots, [n] sequences
   double *vals = nullptr, *lm3 = nullptr, *rows = nullptr, *pose = nullptr, *loop_pose = nullptr, *drift = nullptr, *stats = nullptr, *pgo_T = nullptr;
+  // localize: the queries' score rows [S][maxkf] (`rows` is what similarity_row reports: not touched), the result block (LcFixOut) and
+  // its host copy; sets_cap: the pair-check buffers (slot_a .. mask) hold this many sets -- S until the first localize call
+  double* qrows = nullptr;
+  uint8_t* fix_out = nullptr;
+  std::vector<uint8_t> h_fix_out;
+  int sets_cap = 0;
   std::vector<void*> owned;
   std::vector<Seq> seq;
   std::vector<double> h_rows;
@@ -177,6 +252,17 @@ struct flvis_loop_closer {
     p = (T*)q;
     return true;
   }
+  // a larger buffer in place of p (contents dropped); the caller has waited for the stream
+  template <class T>
+  bool regrow(T*& p, size_t count) {
+    void* const old = (void*)p;
+    if (!alloc(p, count)) return false;
+    owned.erase(std::find(owned.begin(), owned.end(), old));
+    hipFree(old);
+    return true;
+  }
+  int query_slot(int s) const { return S * maxkf + s; }
+  int empty_slot() const { return S * maxkf + S; }
 };
 
 extern "C" {
@@ -244,7 +330,7 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
   *out = nullptr;
   if (ctx->voc_nodes < 2)
     return ctx->fail(FLVIS_ERR_CONFIG, "loop_closer_create: no vocabulary (flvis_hip_bow_load_vocabulary / flvis_hip_bow_set_vocabulary first)");
-  if ((long long)n_streams * max_keyframes > (1ll << 31) / LCC_CAP)
+  if ((long long)n_streams * (max_keyframes + 1) + 1 > (1ll << 31) / LCC_CAP)  // keyframe, query and empty slots: int indices * LCC_CAP
     return ctx->fail(FLVIS_ERR_CAPACITY, "loop_closer_create: n_streams * max_keyframes is too large");
   hipSetDevice(ctx->device);
   flvis_loop_closer* lc = new flvis_loop_closer();
@@ -258,10 +344,11 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
     }
   lc->cfgs.assign(cfgs, cfgs + n_streams);
   if (h_orb_pattern) lc->pattern.assign(h_orb_pattern, h_orb_pattern + 1024);
-  const size_t slots = (size_t)n_streams * max_keyframes, S = (size_t)n_streams;
-  bool ok = lc->alloc(lc->db_ids, slots * LCC_VCAP) && lc->alloc(lc->db_vals, slots * LCC_VCAP) && lc->alloc(lc->db_nnz, slots) &&
-            lc->alloc(lc->db_lm2, slots * LCC_CAP * 2) && lc->alloc(lc->db_lm3, slots * LCC_CAP * 3) &&
-            lc->alloc(lc->db_lmd, slots * LCC_CAP * 32) && lc->alloc(lc->db_lmc, slots) && lc->alloc(lc->db_T, slots * 7) &&
+  const size_t slots = (size_t)n_streams * max_keyframes, S = (size_t)n_streams, dbs = slots + S + 1;
+  bool ok = lc->alloc(lc->db_ids, dbs * LCC_VCAP) && lc->alloc(lc->db_vals, dbs * LCC_VCAP) && lc->alloc(lc->db_nnz, dbs) &&
+            lc->alloc(lc->db_lm2, dbs * LCC_CAP * 2) && lc->alloc(lc->db_lm3, dbs * LCC_CAP * 3) &&
+            lc->alloc(lc->db_lmd, dbs * LCC_CAP * 32) && lc->alloc(lc->db_lmc, dbs) && lc->alloc(lc->db_T, dbs * 7) &&
+            lc->alloc(lc->qrows, slots) && lc->alloc(lc->fix_out, LcFixOut::bytes(S * LCC_NBEST, S)) &&
             lc->alloc(lc->kps, S * LCC_CAP * 6) && lc->alloc(lc->desc, S * LCC_CAP * 32) && lc->alloc(lc->cnt, S) && lc->alloc(lc->ovf, S) &&
             lc->alloc(lc->ids, S * LCC_VCAP) && lc->alloc(lc->vals, S * LCC_VCAP) && lc->alloc(lc->nnz, S) &&
             lc->alloc(lc->lm2, S * LCC_CAP * 2) && lc->alloc(lc->lm3, S * LCC_CAP * 3) && lc->alloc(lc->lmc, S) &&
@@ -270,11 +357,14 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
             lc->alloc(lc->npairs, S) && lc->alloc(lc->p3d, S * LCC_CAP * 3) && lc->alloc(lc->p2d, S * LCC_CAP * 2) &&
             lc->alloc(lc->mask, S * LCC_CAP) && lc->alloc(lc->ninl, S) && lc->alloc(lc->pose, S * 7) && lc->alloc(lc->rows, slots) &&
             lc->alloc(lc->loop_pose, slots * 7) && lc->alloc(lc->drift, S * 7) && lc->alloc(lc->stats, S * 5) && lc->alloc(lc->pgo_T, slots * 7) &&
-            lc->alloc(lc->stage, S * LCC_STAGE) && lc->alloc(lc->d_cams, S) &&
+            lc->alloc(lc->stage, S * LCC_QSTAGE) && lc->alloc(lc->d_cams, S) &&
             hipHostMalloc((void**)&lc->h_cams, S * sizeof(LcCam), hipHostMallocDefault) == hipSuccess;
   if (ok) {
     for (int s = 0; s < n_streams; s++) lc_cam_of_cfg(cfgs[s], &lc->h_cams[s]);
     ok = hipMemcpyAsync(lc->d_cams, lc->h_cams, S * sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    // the empty slot: its two counts are all that is ever read of it
+    ok = ok && hipMemsetAsync(lc->db_lmc + slots + S, 0, sizeof(int), ctx->stream) == hipSuccess &&
+         hipMemsetAsync(lc->db_nnz + slots + S, 0, sizeof(int), ctx->stream) == hipSuccess;
   }
   if (!ok) {
     (void)hipGetLastError();
@@ -286,7 +376,9 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
   }
   lc->seq.resize(n_streams);
   lc->h_rows.resize(slots);
-  lc->h_stage.resize(S * LCC_STAGE);
+  lc->h_stage.resize(S * LCC_QSTAGE);
+  lc->h_fix_out.resize(LcFixOut::bytes(S * LCC_NBEST, S));
+  lc->sets_cap = n_streams;
   *out = lc;
   return FLVIS_OK;
 }
@@ -358,6 +450,19 @@ void flvis_loop_closer_destroy(flvis_loop_closer* lc) {
   delete lc;
 }
 
+// STEP 1.3 / 1.4 / 1.5 / 1.6 (:236-372) for n images into the per-call buffers: ORB, bag of words of ALL descriptors, 3-D positions with
+// the camera of each image's sequence (d_seq), then the lists without the rest -- a keyframe's, and a localize call's query's
+static int lc_features(flvis_loop_closer* lc, int n, const uint8_t* d_img0, const void* d_img1, const int* d_seq) {
+  flvis_ctx* ctx = lc->ctx;
+  int rc = flvis_hip_orb_detect_and_compute(ctx, d_img0, lc->w, lc->h, n, &lc->orb, lc->pattern.empty() ? nullptr : lc->pattern.data(), lc->kps,
+                                            lc->desc, lc->cnt, LCC_CAP, lc->ovf);
+  if (rc == FLVIS_OK) rc = flvis_hip_bow_transform(ctx, lc->desc, lc->cnt, LCC_CAP, n, LCC_VCAP, lc->ids, lc->vals, lc->nnz);
+  if (rc == FLVIS_OK)
+    rc = flvis::lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, lc->w, lc->h, n, lc->cam_type, lc->d_cams, d_seq, lc->kps, lc->desc, lc->cnt,
+                                          LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
+  return rc;
+}
+
 int flvis_loop_closer_add_keyframes(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1,
                                     const double* h_T_c_w_odom7, int64_t* h_kf_id) {
   if (!lc) return FLVIS_ERR_INVALID_ARG;
@@ -386,13 +491,7 @@ int flvis_loop_closer_add_keyframes(flvis_loop_closer* lc, int n, const int* h_s
   const int* const d_slot = reinterpret_cast<const int*>(lc->stage + 7 * sizeof(double) * (size_t)n);
   hipError_t e = hipMemcpyAsync(lc->stage, lc->h_stage.data(), LCC_STAGE * (size_t)n, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_add_keyframes");
-  // STEP 1.3 / 1.4 / 1.5 / 1.6 (:236-372): ORB, bag of words of ALL descriptors, 3-D positions, then the lists without the rest
-  int rc = flvis_hip_orb_detect_and_compute(ctx, d_img0, lc->w, lc->h, n, &lc->orb, lc->pattern.empty() ? nullptr : lc->pattern.data(), lc->kps,
-                                            lc->desc, lc->cnt, LCC_CAP, lc->ovf);
-  if (rc == FLVIS_OK) rc = flvis_hip_bow_transform(ctx, lc->desc, lc->cnt, LCC_CAP, n, LCC_VCAP, lc->ids, lc->vals, lc->nnz);
-  if (rc == FLVIS_OK)
-    rc = flvis::lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, lc->w, lc->h, n, lc->cam_type, lc->d_cams, d_slot + n, lc->kps, lc->desc, lc->cnt,
-                                          LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
+  int rc = lc_features(lc, n, d_img0, d_img1, d_slot + n);
   if (rc != FLVIS_OK) {
     hipStreamSynchronize(st);  // (h_stage is reused by the next call)
     return rc;
@@ -414,26 +513,30 @@ int flvis_loop_closer_add_keyframes(flvis_loop_closer* lc, int n, const int* h_s
 }
 
 // KeyFrameMsg::unpack (:206) hands the nodelet HOST images; this is the same call on host buffers: mono8 img0, mono8 or 16UC1 img1
-int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
-                                         const double* h_T_c_w_odom7, int64_t* h_kf_id) {
-  if (!lc) return FLVIS_ERR_INVALID_ARG;
+// the host images of an add_keyframes_host / localize_host call: first checked (nothing is queued), ...
+static int lc_host_images_check(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
+                                const std::string& what) {
   flvis_ctx* ctx = lc->ctx;
-  if (n <= 0 || n > lc->S || !h_img0 || !h_img1 || !h_stream || !h_T_c_w_odom7)
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: bad args");
   const int bpp1 = lc->cam_type == 2 ? 2 : 1;
-  // every argument is checked BEFORE a copy is queued: the caller may free its images as soon as this call returns with an error
   for (int i = 0; i < n; i++) {
     const flvis_image &a = h_img0[i], &b = h_img1[i];
-    if (h_stream[i] < 0 || h_stream[i] >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: bad stream index");
+    if (h_stream[i] < 0 || h_stream[i] >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": bad stream index");
     if (!a.data || !b.data || a.width != lc->w || a.height != lc->h || b.width != lc->w || b.height != lc->h || a.channels != 1 || b.channels != 1 ||
         a.pitch < lc->w || b.pitch < lc->w * bpp1)
-      return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: images must be mono8 (img1: 16UC1 on a depth rig) of the configured size");
+      return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": images must be mono8 (img1: 16UC1 on a depth rig) of the configured size");
   }
+  return FLVIS_OK;
+}
+// ... and queued for upload into the context's staging images (the caller waits for the stream before its images may go away)
+static int lc_host_images_stage(flvis_loop_closer* lc, int n, const flvis_image* h_img0, const flvis_image* h_img1, const std::string& what,
+                                uint8_t** d_img0, uint8_t** d_img1) {
+  flvis_ctx* ctx = lc->ctx;
+  const int bpp1 = lc->cam_type == 2 ? 2 : 1;
   const size_t px = (size_t)lc->w * lc->h;
   hipSetDevice(ctx->device);
   uint8_t* d0 = (uint8_t*)ctx->scratch("lc_host_img0", px * (size_t)lc->S);
   uint8_t* d1 = (uint8_t*)ctx->scratch("lc_host_img1", px * 2 * (size_t)lc->S);
-  if (!d0 || !d1) return ctx->fail(FLVIS_ERR_HIP, "loop_closer_add_keyframes_host: staging allocation failed");
+  if (!d0 || !d1) return ctx->fail(FLVIS_ERR_HIP, what + ": staging allocation failed");
   hipError_t e = hipSuccess;
   for (int i = 0; i < n && e == hipSuccess; i++) {
     const flvis_image &a = h_img0[i], &b = h_img1[i];
@@ -444,11 +547,53 @@ int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int
   }
   if (e != hipSuccess) {
     hipStreamSynchronize(ctx->stream);  // copies from the caller's images may still be in flight
-    return ctx->hip_fail(e, "loop_closer_add_keyframes_host");
+    return ctx->hip_fail(e, what.c_str());
   }
-  const int rc = flvis_loop_closer_add_keyframes(lc, n, h_stream, d0, d1, h_T_c_w_odom7, h_kf_id);  // (synchronises when it succeeds)
+  *d_img0 = d0, *d_img1 = d1;
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
+                                         const double* h_T_c_w_odom7, int64_t* h_kf_id) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_add_keyframes_host";
+  if (n <= 0 || n > lc->S || !h_img0 || !h_img1 || !h_stream || !h_T_c_w_odom7)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: bad args");
+  // every argument is checked BEFORE a copy is queued: the caller may free its images as soon as this call returns with an error
+  int rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
+  uint8_t *d0 = nullptr, *d1 = nullptr;
+  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
+  if (rc != FLVIS_OK) return rc;
+  rc = flvis_loop_closer_add_keyframes(lc, n, h_stream, d0, d1, h_T_c_w_odom7, h_kf_id);  // (synchronises when it succeeds)
   if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);  // ... and on its error paths the uploads are waited for here
   return rc;
+}
+
+// isLoopClosureKF (:593-686) on the device for nc pairs of database slots (a: the keyframe whose 3-D points are used, b: the one whose
+// pixels are; cam_of: the pair's camera row): mutual / ratio matches, the correspondences, solvePnPRansac in its P3P form (100 iterations,
+// 2.0 px, 0.99).  Leaves the matches, the pose and the inliers per pair in d_npairs / d_pose / d_ninl; a pair with a side that has no
+// landmarks runs through as an empty set (0 matches, the identity, 0 inliers).  nc <= lc->sets_cap.
+static int lc_pair_check(flvis_loop_closer* lc, int nc, const int* slot_a, const int* slot_b, const int* cam_of, const uint64_t* h_seeds,
+                         int* d_npairs, double* d_pose, int* d_ninl) {
+  flvis_ctx* ctx = lc->ctx;
+  hipStream_t st = ctx->stream;
+  k_lcc_fetch<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->db_lmd, lc->db_lmc, lc->da, lc->na, lc->db, lc->nb);
+  int rc = flvis_hip_orb_match(ctx, lc->da, lc->na, LCC_CAP, lc->db, lc->nb, LCC_CAP, nc, lc->prm.ratioMax, lc->pairs, d_npairs);
+  if (rc != FLVIS_OK) return rc;
+  k_lcc_correspondences<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->pairs, d_npairs, lc->db_lm3, lc->db_lm2, lc->p3d, lc->p2d);
+  return flvis::pnp_ransac_dev(ctx, lc->p3d, lc->p2d, d_npairs, LCC_CAP, nc, nullptr, &lc->d_cams[0].fx, flvis::LC_CAM_DOUBLES, cam_of, 100, 2.0,
+                               0.99, h_seeds, d_pose, lc->mask, d_ninl);
+}
+
+// ... and its verdict on the host (:666-686) from the matches m, the inliers and the PnP pose T: process' rule, and localize's
+static bool lc_pair_accepted(const flvis_lc_params& p, int m, int inl, const double* T) {
+  if (m < 5) return false;                                            // "p3d not enough" (:666)
+  if (inl * 1.0 / m < p.ratioRansac || inl < p.minPts) return false;  // :677
+  const double tn = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
+  const double vn = std::sqrt(T[3] * T[3] + T[4] * T[4] + T[5] * T[5]);
+  const double angle = 2.0 * std::atan2(vn, std::fabs(T[6]));  // |so3().log()|
+  return tn < 3 && angle < 1.5;                                // :686
 }
 
 int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
@@ -513,15 +658,9 @@ int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
   const int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + nc, *const cam_of = lc->slot_a + 2 * nc;
   e = hipMemcpyAsync(lc->slot_a, sa.data(), sizeof(int) * 3 * (size_t)nc, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_process");
-  k_lcc_fetch<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->db_lmd, lc->db_lmc, lc->da, lc->na, lc->db, lc->nb);
-  int rc = flvis_hip_orb_match(ctx, lc->da, lc->na, LCC_CAP, lc->db, lc->nb, LCC_CAP, nc, p.ratioMax, lc->pairs, lc->npairs);
-  if (rc != FLVIS_OK) return rc;
-  k_lcc_correspondences<<<dim3(LCC_CAP / 256, nc), 256, 0, st>>>(slot_a, slot_b, lc->pairs, lc->npairs, lc->db_lm3, lc->db_lm2, lc->p3d,
-                                                                  lc->p2d);
   std::vector<uint64_t> seeds((size_t)nc);
   for (int i = 0; i < nc; i++) seeds[i] = ((uint64_t)(cand[i] + 1) << 32) + (uint64_t)lc->seq[cand[i]].n;  // (stream + 1) << 32 | kf_curr + 1
-  rc = flvis::pnp_ransac_dev(ctx, lc->p3d, lc->p2d, lc->npairs, LCC_CAP, nc, nullptr, &lc->d_cams[0].fx, flvis::LC_CAM_DOUBLES, cam_of, 100, 2.0,
-                             0.99, seeds.data(), lc->pose, lc->mask, lc->ninl);
+  int rc = lc_pair_check(lc, nc, slot_a, slot_b, cam_of, seeds.data(), lc->npairs, lc->pose, lc->ninl);
   if (rc != FLVIS_OK) return rc;
   std::vector<int> h_np((size_t)nc), h_ni((size_t)nc);
   std::vector<double> h_pose((size_t)nc * 7);
@@ -541,11 +680,7 @@ int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
     if (m < 5) continue;  // "p3d not enough" (:666)
     ev.n_inliers = inl;
     memcpy(ev.loop_pose7, T, 7 * sizeof(double));
-    if (inl * 1.0 / m < p.ratioRansac || inl < p.minPts) continue;  // :677
-    const double tn = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
-    const double vn = std::sqrt(T[3] * T[3] + T[4] * T[4] + T[5] * T[5]);
-    const double angle = 2.0 * std::atan2(vn, std::fabs(T[6]));  // |so3().log()|
-    if (!(tn < 3 && angle < 1.5)) continue;                        // :686
+    if (!lc_pair_accepted(p, m, inl, T)) continue;
     ev.loop_accepted = 1;
     q.loop_ids.push_back((int)ev.kf_prev);
     q.loop_ids.push_back(q.n - 1);
@@ -606,6 +741,154 @@ int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events) {
     // (:922-925 re-derives the keyframes BEHIND the last optimised one from their odometry pose; the newest keyframe is the last
     //  optimised one here, so there is none)
   }
+  return FLVIS_OK;
+}
+
+// the arguments of a localize call that both forms share, checked before anything is queued
+static int lc_localize_check(flvis_loop_closer* lc, int n, const int* h_stream, int n_best, const flvis_lc_fix* h_fix, const std::string& what) {
+  flvis_ctx* ctx = lc->ctx;
+  if (n <= 0 || n > lc->S || !h_stream || !h_fix) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": bad args");
+  if (n_best < 1 || n_best > LCC_NBEST) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": n_best must be 1 .. " + std::to_string(LCC_NBEST));
+  std::vector<char> used((size_t)lc->S, 0);
+  for (int i = 0; i < n; i++) {
+    const int s = h_stream[i];
+    if (s < 0 || s >= lc->S || used[s]) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": one query per sequence and call");
+    used[s] = 1;
+  }
+  return FLVIS_OK;
+}
+
+// Relocalisation: where is this frame's camera in the map its sequence has built?  The query goes through a keyframe's steps into its
+// sequence's query slot, is scored against the sequence's whole database, the n_best best keyframes are chosen on the device
+// (k_lcc_select) and each (keyframe, query) pair goes through isLoopClosureKF's check as process runs it -- n * n_best sets, empty where
+// there is no candidate.  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.
+int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1, int n_best,
+                               flvis_lc_fix* h_fix) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_localize";
+  int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
+  if (rc != FLVIS_OK) return rc;
+  if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize: bad args");
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  const int ns_cap = lc->S * LCC_NBEST;
+  if (lc->sets_cap < ns_cap) {  // the first localize call: the pair-check buffers grow from one set per sequence to LCC_NBEST
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, what);
+    const size_t c = (size_t)ns_cap;
+    if (!(lc->regrow(lc->slot_a, c * 3) && lc->regrow(lc->da, c * LCC_CAP * 32) && lc->regrow(lc->db, c * LCC_CAP * 32) && lc->regrow(lc->na, c) &&
+          lc->regrow(lc->nb, c) && lc->regrow(lc->pairs, c * LCC_CAP * 2) && lc->regrow(lc->p3d, c * LCC_CAP * 3) &&
+          lc->regrow(lc->p2d, c * LCC_CAP * 2) && lc->regrow(lc->mask, c * LCC_CAP))) {
+      (void)hipGetLastError();
+      // (a buffer that did not grow keeps its size, and sets_cap its value: process goes on, the next localize call tries again)
+      return ctx->fail(FLVIS_ERR_HIP, "loop_closer_localize: device allocation failed");
+    }
+    lc->sets_cap = ns_cap;
+  }
+  // one upload: identity poses for k_lcc_store, the queries' slots, their sequences (= camera rows), the sequences' keyframe counts
+  double* const T = reinterpret_cast<double*>(lc->h_stage.data());
+  int* const hq = reinterpret_cast<int*>(lc->h_stage.data() + 7 * sizeof(double) * (size_t)n);
+  std::vector<int> jobs;
+  for (int i = 0; i < n; i++) {
+    const int s = h_stream[i], nk = lc->seq[s].n;
+    for (int k = 0; k < 7; k++) T[7 * (size_t)i + k] = k == 6 ? 1.0 : 0.0;
+    hq[i] = lc->query_slot(s), hq[n + i] = s, hq[2 * n + i] = nk;
+    if (nk > 0) jobs.insert(jobs.end(), {lc->query_slot(s), s * lc->maxkf, nk});
+  }
+  const double* const d_T = reinterpret_cast<const double*>(lc->stage);
+  const int* const d_q = reinterpret_cast<const int*>(lc->stage + 7 * sizeof(double) * (size_t)n);
+  e = hipMemcpyAsync(lc->stage, lc->h_stage.data(), LCC_QSTAGE * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  rc = lc_features(lc, n, d_img0, d_img1, d_q + n);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);  // (h_stage is reused by the next call)
+    return rc;
+  }
+  k_lcc_store<<<dim3(LCC_CAP / 256, n), 256, 0, st>>>(d_q, lc->ids, lc->vals, lc->nnz, lc->lm2, lc->lm3, lc->desc, lc->lmc, d_T, lc->db_ids,
+                                                       lc->db_vals, lc->db_nnz, lc->db_lm2, lc->db_lm3, lc->db_lmd, lc->db_lmc, lc->db_T);
+  e = hipGetLastError();
+  if (e != hipSuccess) {
+    hipStreamSynchronize(st);
+    return ctx->hip_fail(e, what);
+  }
+  // the queries' score rows (flvis_hip_bow_score's scores: the same kernel body), then the candidates
+  if (!jobs.empty()) rc = flvis_hip_bow_score_jobs(ctx, (int)(jobs.size() / 3), jobs.data(), lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP, lc->qrows);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  const int ns = n * n_best;
+  int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
+  const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)lc->S);
+  k_lcc_select<<<n, 64, 0, st>>>(d_q, d_q + n, d_q + 2 * n, lc->qrows, lc->maxkf, n_best, lc->prm.minScore, lc->empty_slot(), lc->lmc, lc->db_T,
+                                 slot_a, slot_b, cam_of, out);
+  std::vector<uint64_t> seeds((size_t)ns);
+  for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(h_stream[i / n_best] + 1) << 32) + (uint64_t)(i % n_best + 1);  // (stream + 1) << 32 | rank + 1
+  rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  e = hipMemcpyAsync(lc->h_fix_out.data(), lc->fix_out, lc->h_fix_out.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)lc->S);
+  for (int i = 0; i < n; i++) {
+    flvis_lc_fix& f = h_fix[i];
+    memset(&f, 0, sizeof(f));
+    f.n_landmarks = h.nlm[i];
+    f.n_candidates = h.ncand[i];
+    f.best = -1;
+    f.T_c_map7[6] = 1.0;
+    for (int r = 0; r < LCC_NBEST; r++) f.cand_kf[r] = -1, f.cand_pose7[r][6] = 1.0;
+    for (int r = 0; r < f.n_candidates; r++) {
+      const int set = i * n_best + r, m = h.npairs[set];
+      f.cand_kf[r] = h.kf[set];
+      f.cand_score[r] = h.score[set];
+      f.cand_matches[r] = m;
+      if (m < 5) continue;  // "p3d not enough" (:666): no inliers, the identity, as in an event
+      const double* const P = h.pose + 7 * (size_t)set;
+      f.cand_inliers[r] = h.ninl[set];
+      memcpy(f.cand_pose7[r], P, 7 * sizeof(double));
+      f.cand_accepted[r] = lc_pair_accepted(lc->prm, m, h.ninl[set], P) ? 1 : 0;
+      if (f.cand_accepted[r] && (f.best < 0 || f.cand_inliers[r] > f.cand_inliers[f.best])) f.best = r;
+    }
+    if (f.best >= 0) pose_mul(f.cand_pose7[f.best], h.T_kf + 7 * (size_t)(i * n_best + f.best), f.T_c_map7);
+  }
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
+                                    int n_best, flvis_lc_fix* h_fix) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_localize_host";
+  int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
+  if (rc != FLVIS_OK) return rc;
+  if (!h_img0 || !h_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_host: bad args");
+  rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
+  uint8_t *d0 = nullptr, *d1 = nullptr;
+  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
+  if (rc != FLVIS_OK) return rc;
+  rc = flvis_loop_closer_localize(lc, n, h_stream, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
+  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
+int flvis_loop_closer_set_drift(flvis_loop_closer* lc, int stream, const double* h_T_odom_map7) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  if (stream < 0 || stream >= lc->S || !h_T_odom_map7) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_set_drift: bad args");
+  const double* const T = h_T_odom_map7;
+  for (int k = 0; k < 7; k++)
+    if (!std::isfinite(T[k])) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_set_drift: the pose is not finite");
+  const double qn = std::sqrt(T[3] * T[3] + T[4] * T[4] + T[5] * T[5] + T[6] * T[6]);
+  if (!(qn > 0) || !std::isfinite(qn)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_set_drift: zero quaternion");
+  double* const M = lc->seq[stream].T_odom_map;
+  for (int k = 0; k < 3; k++) M[k] = T[k];
+  for (int k = 3; k < 7; k++) M[k] = T[k] / qn;
   return FLVIS_OK;
 }
 

@@ -699,6 +699,49 @@ int flvis_loop_closer_keyframe(flvis_loop_closer* lc, int stream, int kf, int ca
 int flvis_loop_closer_drift(flvis_loop_closer* lc, int stream, double* h_T_odom_map7);
 /* the newest row of the sequence's similarity matrix as the last flvis_loop_closer_process computed it */
 int flvis_loop_closer_similarity_row(flvis_loop_closer* lc, int stream, double* h_row, int cap, int* n_out);
+/* Relocalisation: where is a frame's camera in the map its sequence has built?  (The reference has no such call: a tracker that lost its
+ * pose restarts at the identity and nothing ties the new odometry frame to the old map.  What follows is the reference's own pair check,
+ * isLoopClosureKF :593-686, applied to (database keyframe, query) around a candidate choice that is this project's definition.)
+ * Query: one image pair for each of the n sequences h_stream[i] (distinct), in the layout and types of flvis_loop_closer_add_keyframes.  It
+ * goes through a keyframe's steps -- ORB, the bag of words of all descriptors, the landmarks with the sequence's own camera, the kept lists
+ * -- and is NOT stored.  Database: everything add_keyframes has stored for the sequence, processed or not; an empty sequence gives
+ * n_candidates = 0 and best = -1, not an error.
+ * Candidates: the n_best (1 .. FLVIS_LC_FIX_CAND) keyframes with the highest L1 score against the query (flvis_hip_bow_score's value, bit
+ * for bit) among those with score > 0 and score >= prm.minScore, by score descending and, for equal scores, keyframe index ascending;
+ * n_candidates may be smaller than n_best.  No temporal exclusion (lcKFDist / lcKFMaxDist) and no 50-keyframe gate.
+ * Pair check per candidate, exactly as flvis_loop_closer_process does it: mutual / ratio matches with prm.ratioMax; the keyframe's 3-D
+ * point with the query's pixel; solvePnPRansac in its P3P form (100 iterations, 2.0 px, 0.99) with the sequence's K; cand_accepted by the
+ * reference's rule: m >= 5, inl / m >= ratioRansac, inl >= minPts, |t| < 3, |log R| < 1.5.  With m < 5: cand_inliers = 0 and cand_pose7 the
+ * identity, as in an event.  Entries from n_candidates on: cand_kf = -1, zeros, the identity.
+ * best: the accepted candidate with the most inliers, the earlier one in candidate order on a tie; then
+ * T_c_map7 = cand_pose7[best] * T_c_w(cand_kf[best]) with the database's current pose (the one a pose graph corrected).  best = -1: the
+ * identity.
+ * No side effect a caller can observe: every later add_keyframes, process, poses, drift, similarity_row or keyframe call returns bit for
+ * bit what it returns on a closer that never saw the query; a keyframe that was added and not yet processed stays pending.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: n_best outside 1 .. FLVIS_LC_FIX_CAND, a stream out of range or listed twice, n <= 0,
+ * h_fix == NULL, a NULL closer; in the _host form (the checks and the staging of flvis_loop_closer_add_keyframes_host) wrong image shapes. */
+#define FLVIS_LC_FIX_CAND 8
+typedef struct flvis_lc_fix {
+  int n_landmarks;   /* the query's kept ORB landmarks: what add_keyframes would have stored for it */
+  int n_candidates;  /* <= n_best */
+  int best;          /* index into cand_*; -1: not localised */
+  int reserved;
+  int64_t cand_kf[FLVIS_LC_FIX_CAND];
+  double  cand_score[FLVIS_LC_FIX_CAND];
+  int     cand_matches[FLVIS_LC_FIX_CAND], cand_inliers[FLVIS_LC_FIX_CAND], cand_accepted[FLVIS_LC_FIX_CAND];
+  double  cand_pose7[FLVIS_LC_FIX_CAND][7]; /* as flvis_lc_event.loop_pose7: the query camera from keyframe cand_kf's camera */
+  double  T_c_map7[7];                      /* best >= 0: the query camera's T_c_w in the map frame */
+} flvis_lc_fix;
+int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1,
+                               int n_best, flvis_lc_fix* h_fix /* [n] */);
+int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0,
+                                    const flvis_image* h_img1, int n_best, flvis_lc_fix* h_fix);
+/* Replaces the sequence's T_odom_map (the quaternion is normalised).  It enters the keyframes added afterwards
+ * (T_c_w = T_c_w_odom * T_odom_map); stored poses, loops and the pose graph's trigger do not change, and a reset puts it back to the
+ * identity.  A value that is not finite or a zero quaternion: FLVIS_ERR_INVALID_ARG and nothing changes.
+ * The use it is for: after flvis_reset_streams on a tracker slot, localize the slot's first frame (tracker pose T_c_odom), set
+ * T_odom_map = inv(T_c_odom) * T_c_map, and keep adding the slot's keyframes: they land in the map the sequence already has. */
+int flvis_loop_closer_set_drift(flvis_loop_closer* lc, int stream, const double* h_T_odom_map7);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,12 @@ candidates at once, pose graphs) per batch with HIP events around the calls; pri
 --rigs: a mixed fleet instead of one config -- sequence s runs on unit s % 4 of synth.rig_variant("d435i_stereo", .), rendered with that
 unit's rig, all in one closer (flvis_loop_closer_create_rigs).
 
-usage: loop_closer_bench.py [--rigs] [n_streams=64] [n_keyframes=60]"""
+--localize: after the tour, one flvis_loop_closer_localize call for all sequences (a frame rendered between two keyframes of each) at
+n_best = 1, 4 and 8: ms per call, and per stage -- the query's features timed through the separate entry points on the same batch (ORB,
+bag of words, landmarks), the rest of the call (store, scores, candidate selection, n_streams * n_best pair checks, the result copy) as the
+difference -- next to this run's add_keyframes + process time for one batch; a second JSON line.
+
+usage: loop_closer_bench.py [--rigs] [--localize] [n_streams=64] [n_keyframes=60]"""
 import json
 import os
 import sys
@@ -26,7 +31,8 @@ import _pgo_synth as PS
 import _voc as V
 
 RIGS = "--rigs" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a != "--rigs"]
+LOCALIZE = "--localize" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--rigs", "--localize")]
 S = int(args[0]) if len(args) > 0 else 64
 N = int(args[1]) if len(args) > 1 else 60
 PER = 50
@@ -93,3 +99,37 @@ print(json.dumps({
     "candidates": int(sum(n_cand)), "loops_accepted": int(sum(n_acc)), "pose_graph_runs": int(sum(n_opt)),
     "mean_loop_gap_m_odometry": float(gap0), "mean_loop_gap_m_after": float(gap1),
     "timing": "host wall clock around calls that return synchronised"}))
+
+if LOCALIZE:
+    tq = 0.5 * (times[N // 2] + times[N // 2 + 1])                    # between two keyframes of the tour
+    if RIGS:
+        parts = [units[k][0].stereo_frame([trs[s] for s in range(k, S, N_UNITS)], tq, N) for k in range(min(N_UNITS, S))]
+        q0, q1 = (torch.cat([q[c] for q in parts])[back].contiguous() for c in range(2))
+    else:
+        q0, q1 = rnd.stereo_frame(trs, tq, N)
+    cfg0 = cfg[0] if RIGS else cfg
+    P0, P1 = np.array(list(cfg0.P0)), np.array(list(cfg0.P1))
+
+    def timed(f, reps=5):
+        f()                                                            # warm-up (the first localize call also grows the pair-check buffers)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            r = f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / reps, r
+
+    t_orb, (kps, desc, cnt, _) = timed(lambda: ctx.orb_detect_and_compute(q0, cap=1024))
+    t_bow, _ = timed(lambda: ctx.bow_transform(desc, cnt, vcap=1024))
+    t_lm, _ = timed(lambda: ctx.lc_keyframe_landmarks(q0, q1, 0, kps, desc, cnt, P0=P0, P1=P1))
+    out = {"n_streams": S, "n_keyframes": N, "rig_units": N_UNITS if RIGS else 1,
+           "query_orb_ms": t_orb, "query_bow_ms": t_bow, "query_landmarks_ms": t_lm,
+           "add_keyframes_plus_process_ms_per_batch": float(np.mean([t_add[i] + t_proc[i] for i in range(5, N)]))}
+    for n_best in (1, 4, 8):
+        ms, fix = timed(lambda: lc.localize(streams, q0, q1, n_best=n_best))
+        out["localize_ms_n_best_%d" % n_best] = ms
+        out["select_and_pair_checks_ms_n_best_%d" % n_best] = ms - (t_orb + t_bow + t_lm)
+        out["localised_n_best_%d" % n_best] = int(sum(f["best"] >= 0 for f in fix))
+        out["candidates_n_best_%d" % n_best] = int(sum(len(f["candidates"]) for f in fix))
+    out["timing"] = "host wall clock around synchronised calls, mean of 5 after a warm-up; stages: separate entry points on the same batch"
+    print(json.dumps(out))
