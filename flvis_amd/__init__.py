@@ -369,6 +369,38 @@ class Context:
                     "bow_score_jobs")
         return scores
 
+    def bow_score_jobs_at(self, jobs, ids, vals, nnz, n_out):
+        """flvis_hip_bow_score_jobs_at: jobs [(query vector, first database vector, n database vectors, first output index)] over one store
+        ids / vals [n_vectors, vcap], nnz [n_vectors] (device) -> scores float64 [n_out] (entries no job writes stay -1)."""
+        import numpy as np
+        import torch
+        j = np.ascontiguousarray(jobs, np.int32).reshape(-1, 4)
+        assert all(0 <= o and o + n <= n_out for _, _, n, o in j), "a job writes outside the output"
+        assert all(0 <= q < ids.shape[0] and 0 <= f and f + n <= ids.shape[0] for q, f, n, _ in j), "a job reads outside the store"
+        vcap = ids.shape[1]
+        scores = torch.full((int(n_out),), -1.0, dtype=torch.float64, device=ids.device)
+        self._check(self._lib.flvis_hip_bow_score_jobs_at(self._h, len(j), _P(j, C.c_int), _ptr(ids), _ptr(vals), _ptr(nnz), vcap,
+                                                          _ptr(scores)), "bow_score_jobs_at")
+        return scores
+
+    def lc_select_maps(self, scores, seg_n, maps, n_best, min_score):
+        """flvis_hip_lc_select_maps: scores float64 [n_q, n_seg, seg_len], seg_n int32 [n_seg], maps int32 [n_q] (a segment, or -1: all),
+        device tensors -> (idx int32 [n_q, n_best] global index seg * seg_len + j or -1, score float64 [n_q, n_best], count int32 [n_q])."""
+        import torch
+        scores = scores.contiguous()
+        n_q, n_seg, seg_len = scores.shape
+        assert scores.dtype == torch.float64 and seg_n.dtype == torch.int32 and maps.dtype == torch.int32
+        assert seg_n.numel() == n_seg and maps.numel() == n_q
+        idx = torch.full((n_q, int(n_best)), -2, dtype=torch.int32, device=scores.device)
+        sc = torch.full((n_q, int(n_best)), -1.0, dtype=torch.float64, device=scores.device)
+        cnt = torch.full((n_q,), -1, dtype=torch.int32, device=scores.device)
+        self._lib.flvis_hip_lc_select_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self._lib.flvis_hip_lc_select_maps(self._h, n_q, _ptr(scores), n_seg, seg_len, _ptr(seg_n.contiguous()),
+                                                       _ptr(maps.contiguous()), int(n_best), float(min_score), _ptr(idx), _ptr(sc), _ptr(cnt)),
+                    "lc_select_maps")
+        return idx, sc, cnt
+
     def lc_keyframe_landmarks(self, img0, img1, cam_type, kps, desc, count, P0=None, P1=None, K4=None, in_place=False):
         """flvis_hip_lc_keyframe_landmarks (vo_loopclosing.cpp:255-372): kps float32 [n,cap,6], desc uint8 [n,cap,32], count int32 [n] as
         orb_detect_and_compute returns them; img0 uint8 [n,h,w]; img1 uint8 (stereo, cam_type 0) or int16/uint16 Z16 (depth, cam_type 2).
@@ -586,6 +618,14 @@ class FlvisLcFix(C.Structure):
                 ("T_c_map7", C.c_double * 7)]
 
 
+FLVIS_LC_ALL_MAPS = -1
+
+
+class FlvisLcFixIn(C.Structure):
+    """flvis_lc_fix_in of include/flvis_hip.h: what flvis_loop_closer_localize_in reports for one query."""
+    _fields_ = [("fix", FlvisLcFix), ("cand_seq", C.c_int * FLVIS_LC_FIX_CAND), ("map", C.c_int), ("reserved", C.c_int)]
+
+
 def load_lc_params(yaml_path):
     """flvis_lc_params_load: the loop-closing block of the reference's yaml files.  Host-only."""
     prm = LcParams()
@@ -766,6 +806,61 @@ class LoopCloser:
         self._ctx._check(self._lib.flvis_loop_closer_localize_host(self._h, n, _P(st, C.c_int), a, b, int(n_best), fix),
                          "loop_closer_localize_host")
         return self._fixes(fix[:n])
+
+    @classmethod
+    def _fixes_in(cls, fix):
+        out = cls._fixes([f.fix for f in fix])
+        for d, f in zip(out, fix):
+            for r, c in enumerate(d["candidates"]):
+                c["seq"] = int(f.cand_seq[r])
+            d["map"] = int(f.map)
+        return out
+
+    def localize_in(self, streams, maps, img0, img1, n_best=4):
+        """flvis_loop_closer_localize_in: localize with the searched database named per query -- maps[i] is the sequence whose keyframe map
+        query i (taken by the camera of sequence streams[i]) is looked for in, FLVIS_LC_ALL_MAPS (-1) every sequence's.  -> localize's
+        dicts, each candidate with seq (kf is an index within that sequence), plus map (the sequence whose map frame T_c_map is in, -1
+        when not localised)."""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        mp = np.ascontiguousarray(maps, np.int32)
+        n = len(st)
+        assert len(mp) == n, "one map per query"
+        img0 = img0.contiguous()
+        img1 = img1.contiguous() if img1 is not None else None
+        hw = (int(self.cfg.image_height), int(self.cfg.image_width))
+        assert img0.shape[0] == n and tuple(img0.shape[1:]) == hw, "img0 must be [n, image_height, image_width]"
+        if img1 is not None:                                 # a wrong-size tensor would be read out of bounds on the device
+            assert img1.shape[0] == n and tuple(img1.shape[1:]) == hw, "img1 must be [n, image_height, image_width]"
+            assert img1.element_size() == (2 if self.cfg.cam_type == 2 else 1), "img1: uint8 (stereo) or 16-bit depth (depth rig)"
+        fix = (FlvisLcFixIn * max(1, n))()
+        self._lib.flvis_loop_closer_localize_in.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                                            C.c_int, C.POINTER(FlvisLcFixIn)]
+        self._ctx._check(self._lib.flvis_loop_closer_localize_in(self._h, n, _P(st, C.c_int), _P(mp, C.c_int), _ptr(img0), _ptr(img1),
+                                                                 int(n_best), fix), "loop_closer_localize_in")
+        return self._fixes_in(fix[:n])
+
+    def localize_in_host(self, streams, maps, img0, img1, n_best=4):
+        """flvis_loop_closer_localize_in_host: localize_in on numpy images as add_keyframes_host takes them (rows may be padded)."""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        mp = np.ascontiguousarray(maps, np.int32)
+        n = len(st)
+        assert len(mp) == n, "one map per query"
+        a = (FlvisImage * max(1, n))()
+        b = (FlvisImage * max(1, n))()
+        keep = []
+        for i in range(n):
+            for arr, dst in ((img0[i], a), (img1[i], b)):
+                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
+                keep.append(arr)
+                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
+        fix = (FlvisLcFixIn * max(1, n))()
+        self._lib.flvis_loop_closer_localize_in_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                                 C.POINTER(FlvisImage), C.POINTER(FlvisImage), C.c_int, C.POINTER(FlvisLcFixIn)]
+        self._ctx._check(self._lib.flvis_loop_closer_localize_in_host(self._h, n, _P(st, C.c_int), _P(mp, C.c_int), a, b, int(n_best), fix),
+                         "loop_closer_localize_in_host")
+        return self._fixes_in(fix[:n])
 
     def set_drift(self, stream, T_odom_map):
         """flvis_loop_closer_set_drift: the sequence's T_odom_map from now on (keyframes added afterwards get T_c_w_odom * T_odom_map).

@@ -8,6 +8,8 @@
 //                                                      loopClosureOnCovGraphG2ONew (:742-944) and T_odom_map *= Tw1_w2 (:908)
 //   flvis_loop_closer_localize       (the project's own) a query frame against its sequence's whole database: isLoopClosureKF's check on
 //                                                      the n_best best-scoring keyframes, the camera's pose in the map frame; stores nothing
+//   flvis_loop_closer_localize_in    (the project's own) the same against ANOTHER sequence's database, or all of them: the candidates are
+//                                                      ranked across maps (flvis_hip_lc_select_maps), PnP runs with the query's camera
 //
 // The keyframe database (bag-of-words vectors, compacted ORB descriptors with their pixels and 3-D positions, T_c_w) lives in HBM
 // for the whole run -- 76 KB per keyframe -- and never returns to the host; per keyframe the host sees one similarity row, and per
@@ -192,6 +194,31 @@ __global__ __launch_bounds__(64) void k_lcc_select(const int* __restrict__ q_slo
   if (lane == 0) out.ncand[i] = cnt, out.nlm[i] = lmc[i];
 }
 
+// k_lcc_select's writes for a localize_in call, whose candidates k_lc_select_maps (loop_kernels.hip) has chosen across maps: sel_idx is
+// the candidate's database slot (sequence * maxkf + keyframe; -1: an empty rank) and goes to the host as it is.  Side a is the candidate's
+// slot, side b the query's, the camera row the QUERY's sequence: solvePnPRansac needs the K of the camera that saw the pixels.
+__global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ q_slot, const int* __restrict__ q_seq, const int* __restrict__ sel_idx,
+                                                        const double* __restrict__ sel_score, const int* __restrict__ sel_cnt, int n_best,
+                                                        int empty_slot, const int* __restrict__ lmc, const double* __restrict__ db_T, int* slot_a,
+                                                        int* slot_b, int* cam_of, LcFixOut out) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  for (int r = 0; r < n_best; r++) {
+    const int set = i * n_best + r;
+    const int g = sel_idx[set];
+    const bool more = g >= 0;
+    const int ks = more ? g : empty_slot;
+    if (lane < 7) out.T_kf[(size_t)set * 7 + lane] = more ? db_T[(size_t)ks * 7 + lane] : (lane == 6 ? 1.0 : 0.0);
+    if (lane == 0) {
+      slot_a[set] = ks;
+      slot_b[set] = more ? q_slot[i] : empty_slot;
+      cam_of[set] = q_seq[i];
+      out.kf[set] = g;
+      out.score[set] = sel_score[set];
+    }
+  }
+  if (lane == 0) out.ncand[i] = sel_cnt[i], out.nlm[i] = lmc[i];
+}
+
 using flvis::LcCam;
 
 struct Seq {
@@ -239,6 +266,14 @@ struct flvis_loop_closer {
   uint8_t* fix_out = nullptr;
   std::vector<uint8_t> h_fix_out;
   int sets_cap = 0;
+  // localize_in, all allocated by its first call: the queries' score rows ([S][maxkf], one searched map per query; [S][S * maxkf] from
+  // the first call that searches all maps on; mrows_cap: doubles), the searched maps and the sequences' keyframe counts ([2 S], one
+  // upload from h_in_stage), and what k_lc_select_maps leaves per set / per query
+  double* mrows = nullptr;
+  size_t mrows_cap = 0;
+  int *in_stage = nullptr, *sel_idx = nullptr, *sel_cnt = nullptr;
+  double* sel_score = nullptr;
+  std::vector<int> h_in_stage;
   std::vector<void*> owned;
   std::vector<Seq> seq;
   std::vector<double> h_rows;
@@ -762,14 +797,15 @@ static int lc_localize_check(flvis_loop_closer* lc, int n, const int* h_stream, 
 // sequence's query slot, is scored against the sequence's whole database, the n_best best keyframes are chosen on the device
 // (k_lcc_select) and each (keyframe, query) pair goes through isLoopClosureKF's check as process runs it -- n * n_best sets, empty where
 // there is no candidate.  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.
-int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1, int n_best,
-                               flvis_lc_fix* h_fix) {
-  if (!lc) return FLVIS_ERR_INVALID_ARG;
+//
+// h_map == nullptr: localize (every query against its own sequence's database: qrows, k_lcc_select).  Otherwise localize_in: query i
+// against the database of sequence h_map[i], or of every sequence (< 0) -- the score rows in mrows, one launch for all (query, map) jobs,
+// the candidates across maps by k_lc_select_maps, then k_lcc_select's writes; h.kf comes back as a slot index, not a keyframe index.
+// The fix of query i is written at fix_base + i * fix_stride (cand_kf: what h.kf holds).
+static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
+                           int n_best, char* fix_base, size_t fix_stride, const char* what) {
   flvis_ctx* ctx = lc->ctx;
-  const char* const what = "loop_closer_localize";
-  int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
-  if (rc != FLVIS_OK) return rc;
-  if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize: bad args");
+  int rc = FLVIS_OK;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
   hipError_t e = hipSuccess;
@@ -783,9 +819,29 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
           lc->regrow(lc->p2d, c * LCC_CAP * 2) && lc->regrow(lc->mask, c * LCC_CAP))) {
       (void)hipGetLastError();
       // (a buffer that did not grow keeps its size, and sets_cap its value: process goes on, the next localize call tries again)
-      return ctx->fail(FLVIS_ERR_HIP, "loop_closer_localize: device allocation failed");
+      return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
     }
     lc->sets_cap = ns_cap;
+  }
+  bool all_maps = false;
+  if (h_map) {
+    for (int i = 0; i < n; i++) all_maps = all_maps || h_map[i] < 0;
+    const size_t S = (size_t)lc->S, need = (all_maps ? S * S : S) * (size_t)lc->maxkf;
+    if (need > (size_t)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, std::string(what) + ": n_streams^2 * max_keyframes is too large");
+    if (lc->mrows_cap < need || !lc->sel_cnt) {  // the first call, and the first that searches all maps
+      e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return ctx->hip_fail(e, what);
+      bool ok = lc->mrows ? lc->regrow(lc->mrows, need) : lc->alloc(lc->mrows, need);
+      if (ok) lc->mrows_cap = need;
+      ok = ok && (lc->in_stage || lc->alloc(lc->in_stage, 2 * S)) && (lc->sel_idx || lc->alloc(lc->sel_idx, S * LCC_NBEST)) &&
+           (lc->sel_score || lc->alloc(lc->sel_score, S * LCC_NBEST)) && (lc->sel_cnt || lc->alloc(lc->sel_cnt, S));
+      if (!ok) {
+        (void)hipGetLastError();
+        // (the rows keep the size they had: calls that need no more go on, the next one that does tries again)
+        return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation of the score rows failed");
+      }
+      lc->h_in_stage.resize(2 * S);
+    }
   }
   // one upload: identity poses for k_lcc_store, the queries' slots, their sequences (= camera rows), the sequences' keyframe counts
   double* const T = reinterpret_cast<double*>(lc->h_stage.data());
@@ -795,7 +851,7 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
     const int s = h_stream[i], nk = lc->seq[s].n;
     for (int k = 0; k < 7; k++) T[7 * (size_t)i + k] = k == 6 ? 1.0 : 0.0;
     hq[i] = lc->query_slot(s), hq[n + i] = s, hq[2 * n + i] = nk;
-    if (nk > 0) jobs.insert(jobs.end(), {lc->query_slot(s), s * lc->maxkf, nk});
+    if (!h_map && nk > 0) jobs.insert(jobs.end(), {lc->query_slot(s), s * lc->maxkf, nk});
   }
   const double* const d_T = reinterpret_cast<const double*>(lc->stage);
   const int* const d_q = reinterpret_cast<const int*>(lc->stage + 7 * sizeof(double) * (size_t)n);
@@ -813,17 +869,49 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
     hipStreamSynchronize(st);
     return ctx->hip_fail(e, what);
   }
-  // the queries' score rows (flvis_hip_bow_score's scores: the same kernel body), then the candidates
-  if (!jobs.empty()) rc = flvis_hip_bow_score_jobs(ctx, (int)(jobs.size() / 3), jobs.data(), lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP, lc->qrows);
-  if (rc != FLVIS_OK) {
-    hipStreamSynchronize(st);
-    return rc;
-  }
   const int ns = n * n_best;
   int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
   const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)lc->S);
-  k_lcc_select<<<n, 64, 0, st>>>(d_q, d_q + n, d_q + 2 * n, lc->qrows, lc->maxkf, n_best, lc->prm.minScore, lc->empty_slot(), lc->lmc, lc->db_T,
-                                 slot_a, slot_b, cam_of, out);
+  if (!h_map) {
+    // the queries' score rows (flvis_hip_bow_score's scores: the same kernel body), then the candidates
+    if (!jobs.empty()) rc = flvis_hip_bow_score_jobs(ctx, (int)(jobs.size() / 3), jobs.data(), lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP, lc->qrows);
+    if (rc != FLVIS_OK) {
+      hipStreamSynchronize(st);
+      return rc;
+    }
+    k_lcc_select<<<n, 64, 0, st>>>(d_q, d_q + n, d_q + 2 * n, lc->qrows, lc->maxkf, n_best, lc->prm.minScore, lc->empty_slot(), lc->lmc, lc->db_T,
+                                   slot_a, slot_b, cam_of, out);
+  } else {
+    // one job per (query, searched map that holds keyframes); a query's row is one segment per sequence, or, when no query of the call
+    // searches all maps, the one segment it searches
+    const size_t stride = (size_t)(all_maps ? lc->S : 1) * lc->maxkf;
+    int* const hm = lc->h_in_stage.data();
+    for (int m = 0; m < lc->S; m++) hm[n + m] = lc->seq[m].n;
+    for (int i = 0; i < n; i++) {
+      hm[i] = h_map[i] < 0 ? -1 : h_map[i];
+      for (int m = h_map[i] < 0 ? 0 : h_map[i]; m < (h_map[i] < 0 ? lc->S : h_map[i] + 1); m++)
+        if (lc->seq[m].n > 0)
+          jobs.insert(jobs.end(), {lc->query_slot(h_stream[i]), m * lc->maxkf, lc->seq[m].n, (int)(stride * i + (all_maps ? (size_t)m * lc->maxkf : 0))});
+    }
+    e = hipMemcpyAsync(lc->in_stage, hm, sizeof(int) * (size_t)(n + lc->S), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+      hipStreamSynchronize(st);
+      return ctx->hip_fail(e, what);
+    }
+    const int n_jobs = (int)(jobs.size() / 4);
+    for (int j0 = 0; j0 < n_jobs && rc == FLVIS_OK; j0 += 65535)  // (a launch takes 65535 jobs: one launch up to 255 sequences)
+      rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
+                                       lc->mrows);
+    if (rc == FLVIS_OK)
+      rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, lc->S, lc->maxkf, lc->in_stage + n, lc->in_stage, !all_maps, n_best, lc->prm.minScore,
+                                     lc->sel_idx, lc->sel_score, lc->sel_cnt);
+    if (rc != FLVIS_OK) {
+      hipStreamSynchronize(st);
+      return rc;
+    }
+    k_lcc_select_sets<<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->lmc, lc->db_T, slot_a,
+                                        slot_b, cam_of, out);
+  }
   std::vector<uint64_t> seeds((size_t)ns);
   for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(h_stream[i / n_best] + 1) << 32) + (uint64_t)(i % n_best + 1);  // (stream + 1) << 32 | rank + 1
   rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
@@ -836,7 +924,7 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
   if (e != hipSuccess) return ctx->hip_fail(e, what);
   const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)lc->S);
   for (int i = 0; i < n; i++) {
-    flvis_lc_fix& f = h_fix[i];
+    flvis_lc_fix& f = *reinterpret_cast<flvis_lc_fix*>(fix_base + fix_stride * (size_t)i);
     memset(&f, 0, sizeof(f));
     f.n_landmarks = h.nlm[i];
     f.n_candidates = h.ncand[i];
@@ -860,6 +948,17 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
   return FLVIS_OK;
 }
 
+int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1, int n_best,
+                               flvis_lc_fix* h_fix) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_localize";
+  const int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
+  if (rc != FLVIS_OK) return rc;
+  if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize: bad args");
+  return lc_localize_run(lc, n, h_stream, nullptr, d_img0, d_img1, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix), what);
+}
+
 int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
                                     int n_best, flvis_lc_fix* h_fix) {
   if (!lc) return FLVIS_ERR_INVALID_ARG;
@@ -873,6 +972,60 @@ int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_s
   if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
   if (rc != FLVIS_OK) return rc;
   rc = flvis_loop_closer_localize(lc, n, h_stream, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
+  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
+// the arguments of a localize_in call that both forms share, checked before anything is queued
+static int lc_localize_in_check(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, int n_best, const flvis_lc_fix_in* h_fix,
+                                const std::string& what) {
+  flvis_ctx* ctx = lc->ctx;
+  if (!h_map || !h_fix) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": bad args");
+  const int rc = lc_localize_check(lc, n, h_stream, n_best, &h_fix->fix, what);
+  if (rc != FLVIS_OK) return rc;
+  for (int i = 0; i < n; i++)
+    if (h_map[i] < FLVIS_LC_ALL_MAPS || h_map[i] >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": no such map");
+  return FLVIS_OK;
+}
+
+// Where is this frame's camera in the map ANOTHER sequence has built, or in whichever map knows the place?  localize's run with the
+// searched database named per query; the candidates come back as database slots and are split into (sequence, keyframe) here.
+int flvis_loop_closer_localize_in(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
+                                  int n_best, flvis_lc_fix_in* h_fix) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_localize_in";
+  int rc = lc_localize_in_check(lc, n, h_stream, h_map, n_best, h_fix, what);
+  if (rc != FLVIS_OK) return rc;
+  if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_in: bad args");
+  rc = lc_localize_run(lc, n, h_stream, h_map, d_img0, d_img1, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix_in), what);
+  if (rc != FLVIS_OK) return rc;
+  for (int i = 0; i < n; i++) {
+    flvis_lc_fix_in& f = h_fix[i];
+    for (int r = 0; r < LCC_NBEST; r++) {
+      const int64_t g = f.fix.cand_kf[r];
+      f.cand_seq[r] = g < 0 ? -1 : (int)(g / lc->maxkf);
+      if (g >= 0) f.fix.cand_kf[r] = g % lc->maxkf;
+    }
+    f.map = f.fix.best >= 0 ? f.cand_seq[f.fix.best] : -1;
+    f.reserved = 0;
+  }
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const flvis_image* h_img0,
+                                       const flvis_image* h_img1, int n_best, flvis_lc_fix_in* h_fix) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_localize_in_host";
+  int rc = lc_localize_in_check(lc, n, h_stream, h_map, n_best, h_fix, what);
+  if (rc != FLVIS_OK) return rc;
+  if (!h_img0 || !h_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_in_host: bad args");
+  rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
+  uint8_t *d0 = nullptr, *d1 = nullptr;
+  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
+  if (rc != FLVIS_OK) return rc;
+  rc = flvis_loop_closer_localize_in(lc, n, h_stream, h_map, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
   if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
   return rc;
 }

@@ -249,6 +249,83 @@ __global__ __launch_bounds__(256) void k_bow_score_jobs(const int* __restrict__ 
   if (lane == 0) scores[v] = sc;
 }
 
+// ... and with an output position per job: job = (query vector, first database vector, number of database vectors, first output index),
+// scores[out + j] -- several queries may score the same database range, each into a row of its own
+__global__ __launch_bounds__(256) void k_bow_score_jobs_at(const int* __restrict__ jobs, const int* __restrict__ ids, const double* __restrict__ vals,
+                                                           const int* __restrict__ nnz, int vcap, double* __restrict__ scores) {
+  __shared__ double s_term[4][64];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = jobs[4 * blockIdx.y], first = jobs[4 * blockIdx.y + 1], n_db = jobs[4 * blockIdx.y + 2], out = jobs[4 * blockIdx.y + 3];
+  const int j = blockIdx.x * 4 + wv;
+  if (j >= n_db) return;
+  const size_t v = (size_t)first + j;
+  const int nd = nnz[v], nq = nnz[q];
+  double sc = 0.0;
+  if (nd >= 0 && nq >= 0) sc = bow_score_wave(ids + (size_t)q * vcap, vals + (size_t)q * vcap, nq, ids + v * vcap, vals + v * vcap, nd, s_term[wv], lane);
+  if (lane == 0) scores[(size_t)out + j] = sc;
+}
+
+// The best entries of a score row that is cut into n_seg segments of seg_len entries (the loop closer: one segment per sequence's map),
+// of which the first seg_n[s] count: per query the n_best entries with the highest score (> 0 and >= min_score; a NaN fails both) of
+// segment map[q], or of all segments (map[q] < 0), score descending, equal scores by global index s * seg_len + j ascending.
+// One workgroup per query, rank by rank: the waves share out the row in chunks of 64 entries (a chunk beyond its segment's count costs
+// one scalar compare), every lane keeps the entry of its chunks that comes next in that order after the previous pick, the wave reduces
+// by shuffles and the workgroup through LDS with the same rule -- no sort, any row length; n_best passes over a row the cache holds.
+// compact: the row holds segment map[q] alone (seg_len entries; map[q] >= 0 for every query) -- the indices reported are the same.
+constexpr int LSM_T = 1024, LSM_W = LSM_T / 64;
+__device__ inline bool lsm_before(double a_sc, int a_g, double b_sc, int b_g) {  // a comes before b in the order (INT_MAX: no entry)
+  return a_g != INT_MAX && (b_g == INT_MAX || a_sc > b_sc || (a_sc == b_sc && a_g < b_g));
+}
+__global__ __launch_bounds__(LSM_T) void k_lc_select_maps(const double* __restrict__ scores, int n_seg, int seg_len, const int* __restrict__ seg_n,
+                                                          const int* __restrict__ map, int compact, int n_best, double min_score,
+                                                          int* __restrict__ idx, double* __restrict__ score, int* __restrict__ count) {
+  __shared__ double s_sc[LSM_W];
+  __shared__ int s_g[LSM_W];
+  const int q = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int m = map[q];
+  const int s0 = m < 0 ? 0 : m, ns = m < 0 ? n_seg : (m < n_seg ? 1 : 0);  // the segments searched: s0 .. s0 + ns - 1 (no such segment: none)
+  const int cps = (seg_len + 63) >> 6;                   // chunks per segment
+  const double* const row = scores + (size_t)q * (compact ? (size_t)seg_len : (size_t)n_seg * seg_len);
+  double prev_sc = 0.0;
+  int prev_g = -1, cnt = 0;  // prev_g < 0: nothing picked yet
+  bool more = true;
+  for (int r = 0; r < n_best; r++) {
+    double b_sc = 0.0;
+    int b_g = INT_MAX;
+    if (more)
+      for (int item = wv; item < ns * cps; item += LSM_W) {
+        const int s = s0 + item / cps, j = (item % cps) * 64 + lane;
+        const int n = min(seg_n[s], seg_len);
+        if (j >= n) continue;
+        const double sc = row[(compact ? (size_t)0 : (size_t)s * seg_len) + j];
+        const int g = s * seg_len + j;
+        if (!(sc > 0.0 && sc >= min_score)) continue;
+        if (prev_g >= 0 && !(sc < prev_sc || (sc == prev_sc && g > prev_g))) continue;  // picked already
+        if (lsm_before(sc, g, b_sc, b_g)) b_sc = sc, b_g = g;
+      }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const double o_sc = __shfl_xor(b_sc, d);
+      const int o_g = __shfl_xor(b_g, d);
+      if (lsm_before(o_sc, o_g, b_sc, b_g)) b_sc = o_sc, b_g = o_g;
+    }
+    if (lane == 0) s_sc[wv] = b_sc, s_g[wv] = b_g;
+    __syncthreads();
+    b_sc = s_sc[0], b_g = s_g[0];
+#pragma unroll
+    for (int w = 1; w < LSM_W; w++)
+      if (lsm_before(s_sc[w], s_g[w], b_sc, b_g)) b_sc = s_sc[w], b_g = s_g[w];
+    __syncthreads();         // (s_sc / s_g are written again in the next rank)
+    more = b_g != INT_MAX;  // (uniform over the workgroup: every thread folded the same LSM_W entries)
+    if (threadIdx.x == 0) {
+      idx[(size_t)q * n_best + r] = more ? b_g : -1;
+      score[(size_t)q * n_best + r] = more ? b_sc : 0.0;
+    }
+    if (more) prev_sc = b_sc, prev_g = b_g, cnt++;
+  }
+  if (threadIdx.x == 0) count[q] = cnt;
+}
+
 
 // ------------------------------------------------------------------------------------------------ pose-graph optimisation
 // loopClosureOnCovGraphG2ONew (vo_loopclosing.cpp:742-944): vertices kf_prev..kf_curr (g2o VertexSE3, estimate T_w_c), EdgeSE3 to
@@ -875,6 +952,35 @@ int flvis_hip_bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs3, con
   return FLVIS_OK;
 }
 
+int flvis_hip_bow_score_jobs_at(flvis_ctx* ctx, int n_jobs, const int* h_jobs4, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
+                                double* d_scores) {
+  CHECK_CTX(ctx);
+  if (n_jobs <= 0 || n_jobs > 65535 || !h_jobs4 || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs_at: bad args");
+  int max_n = 0;
+  for (int i = 0; i < n_jobs; i++) {
+    const int* const j = h_jobs4 + 4 * (size_t)i;
+    if (j[0] < 0 || j[1] < 0 || j[2] < 0 || j[3] < 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs_at: negative index");
+    max_n = std::max(max_n, j[2]);
+  }
+  if (max_n == 0) return FLVIS_OK;
+  hipSetDevice(ctx->device);
+  int* jobs = (int*)ctx->scratch("bow_jobs_at", sizeof(int) * 4 * (size_t)n_jobs);
+  if (!jobs) return ctx->fail(FLVIS_ERR_HIP, "bow_score_jobs_at: scratch allocation failed");
+  hipError_t e = hipMemcpyAsync(jobs, h_jobs4, sizeof(int) * 4 * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h_jobs4 is the caller's: done with it before returning
+  if (e != hipSuccess) return ctx->hip_fail(e, "bow_score_jobs_at");
+  k_bow_score_jobs_at<<<dim3((max_n + 3) / 4, n_jobs), 256, 0, ctx->stream>>>(jobs, d_ids, d_vals, d_nnz, vcap, d_scores);
+  CHECK_LAUNCH(ctx, "bow_score_jobs_at");
+  return FLVIS_OK;
+}
+
+int flvis_hip_lc_select_maps(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
+                             int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
+  CHECK_CTX(ctx);
+  return flvis::lc_select_maps_dev(ctx, n_q, d_scores, n_seg, seg_len, d_seg_n, d_map, false, n_best, min_score, d_idx, d_score, d_count);
+}
+
 // isLoopClosureKF's geometric check (vo_loopclosing.cpp:660-686) for n_sets candidate pairs: solvePnPRansac on the matched
 // (3-D point of the earlier keyframe, pixel in the current keyframe) correspondences -- the tracker's solver (track_kernels.hip),
 // P3P hypotheses, on caller arrays.
@@ -1165,6 +1271,19 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
   k_lc_landmarks<<<n_img, LC_T, 0, st>>>(d_cams, d_cam_of, cam_type, w, h, d_kps, d_desc, d_count, cap, next, status, (const uint16_t*)d_img1,
                                          d_lm_2d, d_lm_3d, d_lm_desc, d_lm_count);
   CHECK_LAUNCH(ctx, "lc_keyframe_landmarks");
+  return FLVIS_OK;
+}
+
+int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map, bool compact,
+                       int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
+  if (n_q <= 0 || !d_scores || n_seg <= 0 || seg_len <= 0 || !d_seg_n || !d_map || n_best < 1 || n_best > FLVIS_LC_FIX_CAND || !d_idx ||
+      !d_score || !d_count)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_select_maps: bad args");
+  if ((long long)n_seg * seg_len > (long long)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_select_maps: n_seg * seg_len is too large");
+  hipSetDevice(ctx->device);
+  k_lc_select_maps<<<n_q, LSM_T, 0, ctx->stream>>>(d_scores, n_seg, seg_len, d_seg_n, d_map, compact ? 1 : 0, n_best, min_score, d_idx, d_score,
+                                                    d_count);
+  CHECK_LAUNCH(ctx, "lc_select_maps");
   return FLVIS_OK;
 }
 

@@ -24,5 +24,9 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
 int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
                    const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
                    const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
+// flvis_hip_lc_select_maps, and with compact its form for rows that hold segment d_map[q] alone ([n_q][seg_len], every d_map[q] >= 0): the
+// loop closer's layout for a call in which no query searches all maps
+int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map, bool compact,
+                       int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
 
 }  // namespace flvis

@@ -193,6 +193,18 @@ int flvis_hip_bow_score(flvis_ctx* ctx, const int* d_q_ids, const double* d_q_va
  * closer's rows of all sequences that got a keyframe. */
 int flvis_hip_bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs3, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
                              double* d_scores);
+/* the same with an output position per job: job i = h_jobs4[4i..4i+3] = (query vector, first database vector, number of database vectors,
+ * first output index); d_scores[out + j] = score(query, first + j), flvis_hip_bow_score's value bit for bit.  Two queries may score the
+ * same database range, each into a row of its own: what flvis_loop_closer_localize_in needs.  At most 65535 jobs. */
+int flvis_hip_bow_score_jobs_at(flvis_ctx* ctx, int n_jobs, const int* h_jobs4, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
+                                double* d_scores);
+/* The candidate choice of flvis_loop_closer_localize_in.  A score row is cut into n_seg segments of seg_len entries (the closer: one segment
+ * per sequence's map), of which the first d_seg_n[s] count and the rest is never read.  Per query q: the n_best (1 .. 8) entries with the
+ * highest score among those with score > 0 and score >= min_score (a NaN is never picked), in segment d_map[q] or, with d_map[q] = -1, in
+ * all segments; score descending, equal scores by global index s * seg_len + j ascending.  d_idx [n_q][n_best]: the global index, -1 for
+ * an empty rank; d_score: the entry's score, 0 there; d_count [n_q]: the ranks filled.  n_seg * seg_len < 2^31. */
+int flvis_hip_lc_select_maps(flvis_ctx* ctx, int n_q, const double* d_scores /* [n_q][n_seg * seg_len] */, int n_seg, int seg_len,
+                             const int* d_seg_n, const int* d_map, int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
 /* isLoopCandidate (vo_loopclosing.cpp:520-590) on the newest keyframe's row h_row[i] = sim_matrix[i][g_size-1] (host control
  * logic, as in the reference's pgoProcess thread).  Returns 1 and *kf_prev_idx when there is a candidate, 0 when not. */
 int flvis_loop_candidate(int g_size, const double* h_row, const uint8_t* h_present, int lcKFDist, int lcKFMaxDist, int lcNKFClosest,
@@ -736,6 +748,38 @@ int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream
                                int n_best, flvis_lc_fix* h_fix /* [n] */);
 int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0,
                                     const flvis_image* h_img1, int n_best, flvis_lc_fix* h_fix);
+/* Localisation in ANOTHER sequence's map, or in all of them: flvis_loop_closer_localize with the searched database named per query.  (The
+ * project's own, as localize is: the reference runs one sequence.)
+ * Query: as in localize -- h_stream[i] (distinct) names the sequence whose camera took query i; the query goes through a keyframe's steps
+ * with THAT sequence's camera (its P0 / P1 for the landmarks) into that sequence's query slot, and is not stored.
+ * Searched map: h_map[i] is the sequence whose database is searched, FLVIS_LC_ALL_MAPS every sequence's, the query's own included.  Several
+ * queries may name the same map.  An empty searched map gives n_candidates = 0, best = -1, map = -1, not an error.
+ * Candidates: the n_best (1 .. FLVIS_LC_FIX_CAND) keyframes of the searched databases with score > 0 and >= prm.minScore, score descending,
+ * equal scores by sequence ascending, then keyframe index ascending (flvis_hip_lc_select_maps' order: the global slot index).  No temporal
+ * exclusion, no 50-keyframe gate.  Candidate r is keyframe fix.cand_kf[r] of sequence cand_seq[r].
+ * Pair check per candidate: localize's, with side a the candidate's slot (its 3-D points, in the frame of the camera that stored it), side b
+ * the query's slot (its pixels), and solvePnPRansac with the K of the QUERY's sequence -- the camera that saw the pixels.  The PnP seeds are
+ * localize's ((h_stream[i] + 1) << 32 | rank + 1): with h_map[i] = h_stream[i] the result is localize's bit for bit.
+ * Result: fix.best and ties as in localize; fix.T_c_map7 = cand_pose7[best] * T_c_w(cand_seq[best], cand_kf[best]), the query camera's pose
+ * in the frame of map `map` = cand_seq[best].  Two uses: tying two maps, T_mapq_mapm = inv(T_c_mapq) * T_c_mapm from one frame localised
+ * in both; joining a map, flvis_loop_closer_set_drift(q, inv(T_c_odom) * T_c_mapm).
+ * No side effect a caller can observe on any sequence, as in localize.
+ * Score rows: a device buffer of the call's own, [n_streams][max_keyframes] doubles from the first call on and
+ * [n_streams][n_streams * max_keyframes] from the first call with FLVIS_LC_ALL_MAPS on (about 65 MB at 64 x 2000); when that allocation
+ * fails the call returns FLVIS_ERR_HIP and the closer stays usable.  A closer that never makes the call allocates none of it.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: n_best outside 1 .. FLVIS_LC_FIX_CAND, a stream out of range or listed twice, an
+ * h_map[i] outside -1 .. n_streams - 1, n <= 0, a NULL h_map, h_fix or closer; in the _host form wrong image shapes. */
+#define FLVIS_LC_ALL_MAPS (-1)
+typedef struct flvis_lc_fix_in {
+  flvis_lc_fix fix;                /* as flvis_loop_closer_localize fills it; cand_kf[r] is an index within sequence cand_seq[r] */
+  int cand_seq[FLVIS_LC_FIX_CAND]; /* the sequence whose database holds candidate r; -1 from n_candidates on */
+  int map;                         /* cand_seq[fix.best]; -1 when not localised */
+  int reserved;
+} flvis_lc_fix_in;
+int flvis_loop_closer_localize_in(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0,
+                                  const void* d_img1, int n_best, flvis_lc_fix_in* h_fix /* [n] */);
+int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const flvis_image* h_img0,
+                                       const flvis_image* h_img1, int n_best, flvis_lc_fix_in* h_fix);
 /* Replaces the sequence's T_odom_map (the quaternion is normalised).  It enters the keyframes added afterwards
  * (T_c_w = T_c_w_odom * T_odom_map); stored poses, loops and the pose graph's trigger do not change, and a reset puts it back to the
  * identity.  A value that is not finite or a zero quaternion: FLVIS_ERR_INVALID_ARG and nothing changes.

@@ -11,7 +11,13 @@ n_best = 1, 4 and 8: ms per call, and per stage -- the query's features timed th
 bag of words, landmarks), the rest of the call (store, scores, candidate selection, n_streams * n_best pair checks, the result copy) as the
 difference -- next to this run's add_keyframes + process time for one batch; a second JSON line.
 
-usage: loop_closer_bench.py [--rigs] [--localize] [n_streams=64] [n_keyframes=60]"""
+--localize-in: after the tour, flvis_loop_closer_localize_in for all sequences on the same frame, next to localize in the same run, at
+n_best = 1, 4 and 8: with every query in its own map (the same kernels as localize apart from the selection), in its neighbour's map
+(sequence s in the map of s + 1), and in all maps (n_streams x n_streams score jobs, candidates ranked across the maps); ms per call, the
+calls taken in turns; the size of the score rows; a further JSON line.  --localize-in=all: only the all-maps calls at n_best = 8 (a run
+under a profiler then holds nothing else of the new kernels).  max_keyframes sizes the databases and the score rows (default: n_keyframes).
+
+usage: loop_closer_bench.py [--rigs] [--localize] [--localize-in[=all]] [n_streams=64] [n_keyframes=60] [max_keyframes]"""
 import json
 import os
 import sys
@@ -32,9 +38,11 @@ import _voc as V
 
 RIGS = "--rigs" in sys.argv[1:]
 LOCALIZE = "--localize" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--rigs", "--localize")]
+LOCALIZE_IN = [a for a in sys.argv[1:] if a.split("=")[0] == "--localize-in"]
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(args[0]) if len(args) > 0 else 64
 N = int(args[1]) if len(args) > 1 else 60
+MAXKF = int(args[2]) if len(args) > 2 else N
 PER = 50
 N_UNITS = 4
 
@@ -70,7 +78,7 @@ for i in range(0, N, 6):
     k, d, c, _ = ctx.orb_detect_and_compute(frames[i][0][0:1], cap=1024)
     train.append(d[0, :int(c[0])].cpu().numpy())
 ctx.bow_set_vocabulary(*V.build_vocabulary(train, k=8, depth=3))
-lc = flvis_amd.LoopCloser(ctx, cfg, LC.LC_PARAMS, n_streams=S, max_keyframes=N)
+lc = flvis_amd.LoopCloser(ctx, cfg, LC.LC_PARAMS, n_streams=S, max_keyframes=MAXKF)
 streams = list(range(S))
 t_add, t_proc, n_cand, n_acc, n_opt = [], [], [], [], []
 torch.cuda.synchronize()
@@ -100,7 +108,7 @@ print(json.dumps({
     "mean_loop_gap_m_odometry": float(gap0), "mean_loop_gap_m_after": float(gap1),
     "timing": "host wall clock around calls that return synchronised"}))
 
-if LOCALIZE:
+if LOCALIZE or LOCALIZE_IN:
     tq = 0.5 * (times[N // 2] + times[N // 2 + 1])                    # between two keyframes of the tour
     if RIGS:
         parts = [units[k][0].stereo_frame([trs[s] for s in range(k, S, N_UNITS)], tq, N) for k in range(min(N_UNITS, S))]
@@ -119,6 +127,7 @@ if LOCALIZE:
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / reps, r
 
+if LOCALIZE:
     t_orb, (kps, desc, cnt, _) = timed(lambda: ctx.orb_detect_and_compute(q0, cap=1024))
     t_bow, _ = timed(lambda: ctx.bow_transform(desc, cnt, vcap=1024))
     t_lm, _ = timed(lambda: ctx.lc_keyframe_landmarks(q0, q1, 0, kps, desc, cnt, P0=P0, P1=P1))
@@ -132,4 +141,29 @@ if LOCALIZE:
         out["localised_n_best_%d" % n_best] = int(sum(f["best"] >= 0 for f in fix))
         out["candidates_n_best_%d" % n_best] = int(sum(len(f["candidates"]) for f in fix))
     out["timing"] = "host wall clock around synchronised calls, mean of 5 after a warm-up; stages: separate entry points on the same batch"
+    print(json.dumps(out))
+
+if LOCALIZE_IN:
+    only_all = LOCALIZE_IN[-1].endswith("=all")
+    ALL = flvis_amd.FLVIS_LC_ALL_MAPS
+    legs = {"all_maps": [ALL] * S} if only_all else {"localize": None, "own_map": streams, "next_map": [(s + 1) % S for s in streams], "all_maps": [ALL] * S}
+    call = lambda maps, n_best: lc.localize(streams, q0, q1, n_best=n_best) if maps is None else lc.localize_in(streams, maps, q0, q1, n_best=n_best)
+    out = {"n_streams": S, "n_keyframes": N, "max_keyframes": MAXKF, "rig_units": N_UNITS if RIGS else 1,
+           "score_rows_bytes_one_map": 8 * S * MAXKF, "score_rows_bytes_all_maps": 8 * S * S * MAXKF}
+    for n_best in ((8,) if only_all else (1, 4, 8)):
+        ms = {k: [] for k in legs}
+        for k, maps in legs.items():
+            call(maps, n_best)                                         # warm-up (the first calls also allocate and grow buffers)
+        for _ in range(3 if only_all else 7):                          # the legs in turns: a drift of the clocks hits all alike
+            for k, maps in legs.items():
+                ms[k].append(timed(lambda: call(maps, n_best), reps=3)[0])
+        for k, maps in legs.items():
+            fix = call(maps, n_best)
+            out["%s_ms_n_best_%d" % (k, n_best)] = float(np.median(ms[k]))
+            out["%s_ms_min_max_n_best_%d" % (k, n_best)] = [float(min(ms[k])), float(max(ms[k]))]
+            out["%s_localised_n_best_%d" % (k, n_best)] = int(sum(f["best"] >= 0 for f in fix))
+            out["%s_candidates_n_best_%d" % (k, n_best)] = int(sum(len(f["candidates"]) for f in fix))
+            if maps is not None and maps[0] == ALL:
+                out["all_maps_found_in_own_map_n_best_%d" % n_best] = int(sum(f["map"] == s for s, f in zip(streams, fix)))
+    out["timing"] = "host wall clock around synchronised calls: median (and min, max) of 7 rounds of 3 calls, the legs in turns, each round after a warm-up call"
     print(json.dumps(out))
