@@ -626,6 +626,26 @@ class FlvisLcFixIn(C.Structure):
     _fields_ = [("fix", FlvisLcFix), ("cand_seq", C.c_int * FLVIS_LC_FIX_CAND), ("map", C.c_int), ("reserved", C.c_int)]
 
 
+class FlvisLcLink(C.Structure):
+    """flvis_lc_link of include/flvis_hip.h: keyframe kf_from of sequence seq_from seen from keyframe kf_to of sequence seq_to (pose7: the
+    `to` camera from the `from` camera)."""
+    _fields_ = [("seq_from", C.c_int), ("seq_to", C.c_int), ("kf_from", C.c_int64), ("kf_to", C.c_int64), ("pose7", C.c_double * 7)]
+
+
+class FlvisLcMerge(C.Structure):
+    """flvis_lc_merge of include/flvis_hip.h: what flvis_loop_closer_merge reports for one group."""
+    _fields_ = [("optimised", C.c_int), ("n_vertices", C.c_int), ("n_edges", C.c_int), ("iterations", C.c_int),
+                ("chi2_before", C.c_double), ("chi2_after", C.c_double)]
+
+
+def links_from_fix(fix, stream, kf):
+    """The links a localize_in result yields when its query frame is also stored as keyframe `kf` of sequence `stream`: one per accepted
+    candidate, from (candidate's sequence, candidate's keyframe) to (stream, kf) with the candidate's PnP pose.  -> list of dicts
+    (seq_from, kf_from, seq_to, kf_to, pose) for LoopCloser.merge."""
+    return [dict(seq_from=int(c["seq"]), kf_from=int(c["kf"]), seq_to=int(stream), kf_to=int(kf), pose=[float(x) for x in c["pose"]])
+            for c in fix["candidates"] if c["accepted"]]
+
+
 def load_lc_params(yaml_path):
     """flvis_lc_params_load: the loop-closing block of the reference's yaml files.  Host-only."""
     prm = LcParams()
@@ -869,6 +889,29 @@ class LoopCloser:
         T = np.ascontiguousarray(T_odom_map, np.float64).reshape(7)
         self._lib.flvis_loop_closer_set_drift.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         self._ctx._check(self._lib.flvis_loop_closer_set_drift(self._h, int(stream), _P(T, C.c_double)), "loop_closer_set_drift")
+
+    def merge(self, groups, links, iterations=100):
+        """flvis_loop_closer_merge: the maps of each group's sequences become one map in the frame of the group's first sequence, by one
+        joint pose graph per group in which `links` (dicts seq_from / kf_from / seq_to / kf_to / pose, as links_from_fix makes them, or
+        FlvisLcLink) tie keyframes of different sequences.  groups: lists of at least two sequences, disjoint.  -> (one dict per group:
+        optimised / n_vertices / n_edges / iterations / chi2_before / chi2_after, drift [sequences in the groups' order, 7]: what each
+        sequence's T_odom_map was multiplied by).  FlvisError, and nothing changes, for arguments the call refuses."""
+        import numpy as np
+        groups = [[int(s) for s in g] for g in groups]
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(g) for g in groups])]), np.int32)
+        seqs = np.ascontiguousarray([s for g in groups for s in g], np.int32)
+        arr = (FlvisLcLink * max(1, len(links)))()
+        for k, l in enumerate(links):
+            arr[k] = l if isinstance(l, FlvisLcLink) else FlvisLcLink(int(l["seq_from"]), int(l["seq_to"]), int(l["kf_from"]), int(l["kf_to"]),
+                                                                     (C.c_double * 7)(*[float(x) for x in l["pose"]]))
+        out = (FlvisLcMerge * max(1, len(groups)))()
+        drift = np.zeros((max(1, len(seqs)), 7))
+        self._lib.flvis_loop_closer_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(FlvisLcLink),
+                                                      C.c_int, C.POINTER(FlvisLcMerge), C.POINTER(C.c_double)]
+        self._ctx._check(self._lib.flvis_loop_closer_merge(self._h, len(groups), _P(ptr, C.c_int), _P(seqs, C.c_int), len(links), arr,
+                                                           int(iterations), out, _P(drift, C.c_double)), "loop_closer_merge")
+        return ([dict(optimised=bool(o.optimised), n_vertices=o.n_vertices, n_edges=o.n_edges, iterations=o.iterations,
+                      chi2_before=o.chi2_before, chi2_after=o.chi2_after) for o in out[:len(groups)]], drift[:len(seqs)].copy())
 
     def poses(self, stream=0, cap=None):
         import numpy as np

@@ -10,6 +10,8 @@
 //                                                      the n_best best-scoring keyframes, the camera's pose in the map frame; stores nothing
 //   flvis_loop_closer_localize_in    (the project's own) the same against ANOTHER sequence's database, or all of them: the candidates are
 //                                                      ranked across maps (flvis_hip_lc_select_maps), PnP runs with the query's camera
+//   flvis_loop_closer_merge          (the project's own) several sequences' maps into one: loopClosureOnCovGraphG2ONew on the sequences'
+//                                                      keyframes side by side, tied by links between keyframes of different sequences
 //
 // The keyframe database (bag-of-words vectors, compacted ORB descriptors with their pixels and 3-D positions, T_c_w) lives in HBM
 // for the whole run -- 76 KB per keyframe -- and never returns to the host; per keyframe the host sees one similarity row, and per
@@ -220,6 +222,7 @@ __global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ 
 }
 
 using flvis::LcCam;
+using flvis::LcMergeSeq;
 
 struct Seq {
   int n = 0;
@@ -274,6 +277,14 @@ struct flvis_loop_closer {
   int *in_stage = nullptr, *sel_idx = nullptr, *sel_cnt = nullptr;
   double* sel_score = nullptr;
   std::vector<int> h_in_stage;
+  // merge, all allocated by its first call and regrown by a call that needs more: the batch of virtual sequences (mg_V_cap doubles), the
+  // call's one upload (loop poses, row table, LcMergeSeq table; mg_stage_cap bytes) and what comes back in one copy (per group k_pgo's
+  // drift [7] and stats [5], then per sequence its drift [7]; mg_out_cap doubles)
+  double *mg_V = nullptr, *mg_out = nullptr;
+  uint8_t* mg_stage = nullptr;
+  size_t mg_V_cap = 0, mg_stage_cap = 0, mg_out_cap = 0;
+  std::vector<uint8_t> h_mg_stage;
+  std::vector<double> h_mg_out;
   std::vector<void*> owned;
   std::vector<Seq> seq;
   std::vector<double> h_rows;
@@ -294,6 +305,14 @@ struct flvis_loop_closer {
     if (!alloc(p, count)) return false;
     owned.erase(std::find(owned.begin(), owned.end(), old));
     hipFree(old);
+    return true;
+  }
+  // a buffer of at least `count` items, allocated on its first use (contents dropped); the caller has waited for the stream
+  template <class T>
+  bool reserve(T*& p, size_t& cap, size_t count) {
+    if (cap >= count) return true;
+    if (!(p ? regrow(p, count) : alloc(p, count))) return false;
+    cap = count;
     return true;
   }
   int query_slot(int s) const { return S * maxkf + s; }
@@ -1042,6 +1061,165 @@ int flvis_loop_closer_set_drift(flvis_loop_closer* lc, int stream, const double*
   double* const M = lc->seq[stream].T_odom_map;
   for (int k = 0; k < 3; k++) M[k] = T[k];
   for (int k = 3; k < 7; k++) M[k] = T[k] / qn;
+  return FLVIS_OK;
+}
+
+// Several sequences' maps into one map per group (include/flvis_hip.h has the definition).  Host: the checks, the virtual sequences' row
+// table, loop lists and the sequences' vertex ranges; device: the rows out of the pose database (one launch), k_pgo through
+// flvis_hip_pgo_loop_closure (one workgroup per group), the rows back with the tails and the drifts (one launch).  No pose but the
+// sequences' drifts crosses to the host.
+int flvis_loop_closer_merge(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, int n_links, const flvis_lc_link* h_links,
+                            int iterations, flvis_lc_merge* h_out, double* h_drift7) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_merge: " + m); };
+  if (!h_group_ptr || !h_seq || !h_links || !h_out || n_groups <= 0 || n_links < 0 || iterations < 0) return bad("bad args");
+  if (h_group_ptr[0] != 0) return bad("h_group_ptr must start at 0");
+  // ---- the groups: grp_of / pos_of per sequence of the closer (-1: in no group)
+  std::vector<int> grp_of((size_t)lc->S, -1), pos_of((size_t)lc->S, -1);
+  for (int g = 0; g < n_groups; g++) {
+    const int b = h_group_ptr[g], e = h_group_ptr[g + 1];
+    if (e < b || e - b < 2) return bad("a group needs at least two sequences");
+    if (e > lc->S) return bad("the groups list more sequences than the closer has");
+    for (int i = b; i < e; i++) {
+      const int s = h_seq[i];
+      if (s < 0 || s >= lc->S) return bad("sequence out of range");
+      if (grp_of[s] >= 0) return bad("sequence " + std::to_string(s) + " is listed twice");
+      if (lc->seq[s].n == 0) return bad("sequence " + std::to_string(s) + " is empty");
+      grp_of[s] = g, pos_of[s] = i - b;
+    }
+  }
+  // ---- the links; `root` joins the sequences a link ties (every non-anchor sequence must end up with its anchor)
+  std::vector<int> root((size_t)lc->S);
+  for (int s = 0; s < lc->S; s++) root[s] = s;
+  auto find = [&](int s) {
+    while (root[s] != s) s = root[s] = root[root[s]];
+    return s;
+  };
+  std::vector<double> qnorm((size_t)n_links);  // |quaternion| per link: the pose is normalised as set_drift normalises its own
+  for (int k = 0; k < n_links; k++) {
+    const flvis_lc_link& l = h_links[k];
+    const std::string lk = "link " + std::to_string(k);
+    if (l.seq_from < 0 || l.seq_from >= lc->S || l.seq_to < 0 || l.seq_to >= lc->S) return bad(lk + ": sequence out of range");
+    if (l.seq_from == l.seq_to) return bad(lk + ": both ends are in one sequence");
+    if (grp_of[l.seq_from] < 0 || grp_of[l.seq_from] != grp_of[l.seq_to]) return bad(lk + ": its sequences are not both in one group");
+    if (pos_of[l.seq_from] > pos_of[l.seq_to]) return bad(lk + ": its `from` sequence comes after its `to` sequence in the group");
+    if (l.kf_from < 0 || l.kf_from >= lc->seq[l.seq_from].n || l.kf_to < 0 || l.kf_to >= lc->seq[l.seq_to].n) return bad(lk + ": no such keyframe");
+    for (int c = 0; c < 7; c++)
+      if (!std::isfinite(l.pose7[c])) return bad(lk + ": the pose is not finite");
+    const double* const P = l.pose7;
+    const double qn = std::sqrt(P[3] * P[3] + P[4] * P[4] + P[5] * P[5] + P[6] * P[6]);
+    if (!(qn > 0) || !std::isfinite(qn)) return bad(lk + ": zero quaternion");
+    qnorm[k] = qn;
+    root[find(l.seq_from)] = find(l.seq_to);
+  }
+  const int NS = h_group_ptr[n_groups];
+  for (int g = 0; g < n_groups; g++)
+    for (int i = h_group_ptr[g] + 1; i < h_group_ptr[g + 1]; i++)
+      if (find(h_seq[i]) != find(h_seq[h_group_ptr[g]]))
+        return bad("no chain of links connects sequence " + std::to_string(h_seq[i]) + " to its group's anchor");
+  // ---- the virtual sequences: rows (src: database slot, -1 absent), present flags, loop lists; per sequence its vertex range
+  std::vector<int> n_kf((size_t)n_groups), n_loops((size_t)n_groups), ids, src, ran((size_t)n_groups, 0), v_off((size_t)NS);
+  std::vector<uint8_t> present;
+  std::vector<double> lp;
+  std::vector<LcMergeSeq> tab((size_t)NS);
+  std::vector<std::vector<int>> glinks((size_t)n_groups);  // a group's links, in the caller's order
+  for (int k = 0; k < n_links; k++) glinks[grp_of[h_links[k].seq_from]].push_back(k);
+  for (int g = 0; g < n_groups; g++) {
+    const int b = h_group_ptr[g], e = h_group_ptr[g + 1];
+    const size_t row0 = src.size(), loop0 = ids.size();
+    for (int i = b; i < e; i++) {
+      const int s = h_seq[i];
+      const Seq& q = lc->seq[s];
+      if (i > b) {  // five absent keyframes in a row cut the odometry chain (its edges reach the next five keyframes)
+        src.insert(src.end(), 5, -1);
+        present.insert(present.end(), 5, 0);
+      }
+      v_off[i] = (int)(src.size() - row0);
+      tab[i] = LcMergeSeq{s * lc->maxkf, (int)src.size(), 0, q.n - 1, q.n};
+      for (int k = 0; k < q.n; k++) src.push_back(s * lc->maxkf + k);
+      present.insert(present.end(), (size_t)q.n, 1);
+      for (int v : q.loop_ids) ids.push_back(v_off[i] + v);
+      lp.insert(lp.end(), q.loop_poses.begin(), q.loop_poses.end());
+    }
+    for (int k : glinks[g]) {
+      const flvis_lc_link& l = h_links[k];
+      const double* const P = l.pose7;
+      const double qn = qnorm[k];
+      ids.push_back(v_off[b + pos_of[l.seq_from]] + (int)l.kf_from);
+      ids.push_back(v_off[b + pos_of[l.seq_to]] + (int)l.kf_to);
+      for (int c = 0; c < 7; c++) lp.push_back(c < 3 ? P[c] : P[c] / qn);
+    }
+    n_kf[g] = (int)(src.size() - row0);
+    n_loops[g] = (int)((ids.size() - loop0) / 2);
+    // the vertices run from min(earlier) to max(later) (vo_loopclosing.cpp:747-756).  Every link runs from an earlier to a later
+    // sequence and every sequence hangs on the anchor, so the anchor starts some link and the last sequence ends one: min(earlier) is a
+    // keyframe of the anchor, max(later) one of the last sequence, and every sequence has a vertex
+    int kf_prev = INT_MAX, kf_curr = 0;
+    for (size_t k = loop0; k < ids.size(); k += 2) kf_prev = std::min(kf_prev, ids[k]), kf_curr = std::max(kf_curr, ids[k + 1]);
+    tab[b].first = kf_prev;
+    tab[e - 1].v_s = kf_curr - v_off[e - 1];
+  }
+  // ---- buffers, on the first call and when a call needs more
+  const size_t n_rows = src.size(), lp_bytes = sizeof(double) * lp.size(), src_bytes = sizeof(int) * n_rows;
+  const size_t stage_bytes = lp_bytes + src_bytes + sizeof(LcMergeSeq) * (size_t)NS, n_out = (size_t)n_groups * 12 + (size_t)NS * 7;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  if (lc->mg_V_cap < n_rows * 7 || lc->mg_stage_cap < stage_bytes || lc->mg_out_cap < n_out) {
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_merge");
+    if (!(lc->reserve(lc->mg_V, lc->mg_V_cap, n_rows * 7) && lc->reserve(lc->mg_stage, lc->mg_stage_cap, stage_bytes) &&
+          lc->reserve(lc->mg_out, lc->mg_out_cap, n_out))) {
+      (void)hipGetLastError();
+      // (a buffer that did not grow keeps its size: a call that needs no more goes on, the next one that does tries again)
+      return ctx->fail(FLVIS_ERR_HIP, "loop_closer_merge: device allocation failed");
+    }
+  }
+  // ---- the call's one upload: loop poses | row table | sequence table
+  lc->h_mg_stage.resize(stage_bytes);
+  memcpy(lc->h_mg_stage.data(), lp.data(), lp_bytes);
+  memcpy(lc->h_mg_stage.data() + lp_bytes, src.data(), src_bytes);
+  memcpy(lc->h_mg_stage.data() + lp_bytes + src_bytes, tab.data(), sizeof(LcMergeSeq) * (size_t)NS);
+  const double* const d_lp = reinterpret_cast<const double*>(lc->mg_stage);
+  const int* const d_src = reinterpret_cast<const int*>(lc->mg_stage + lp_bytes);
+  const LcMergeSeq* const d_tab = reinterpret_cast<const LcMergeSeq*>(lc->mg_stage + lp_bytes + src_bytes);
+  double *const d_gdrift = lc->mg_out, *const d_stats = d_gdrift + 7 * (size_t)n_groups, *const d_drift = d_stats + 5 * (size_t)n_groups;
+  e = hipMemcpyAsync(lc->mg_stage, lc->h_mg_stage.data(), stage_bytes, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_merge");
+  int rc = flvis::lc_merge_gather_dev(ctx, d_src, (int)n_rows, lc->db_T, lc->mg_V);
+  if (rc == FLVIS_OK)
+    rc = flvis_hip_pgo_loop_closure(ctx, n_groups, n_kf.data(), lc->mg_V, present.data(), n_loops.data(), ids.data(), d_lp, iterations, 1, d_gdrift,
+                                    d_stats, ran.data());
+  // (a graph runs for every group that passed the checks: its loop ends are present keyframes inside min(earlier) .. max(later) and no
+  //  loop ties a keyframe to itself.  A group that did not run would keep its gathered rows: the apply kernel then writes back what it
+  //  read, with the identity as drift)
+  if (rc == FLVIS_OK) rc = flvis::lc_merge_apply_dev(ctx, d_tab, NS, lc->mg_V, lc->db_T, d_drift);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);  // (h_mg_stage is reused by the next call)
+    return rc;
+  }
+  lc->h_mg_out.resize(n_out);
+  e = hipMemcpyAsync(lc->h_mg_out.data(), lc->mg_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_merge");
+  const double *const stats = lc->h_mg_out.data() + 7 * (size_t)n_groups, *const drift = stats + 5 * (size_t)n_groups;
+  for (int g = 0; g < n_groups; g++) {
+    flvis_lc_merge& o = h_out[g];
+    o.optimised = ran[g];
+    o.iterations = (int)stats[5 * (size_t)g];
+    o.chi2_before = stats[5 * (size_t)g + 1];
+    o.chi2_after = stats[5 * (size_t)g + 2];
+    o.n_vertices = (int)stats[5 * (size_t)g + 3];
+    o.n_edges = (int)stats[5 * (size_t)g + 4];
+  }
+  for (int i = 0; i < NS; i++) {
+    Seq& q = lc->seq[h_seq[i]];
+    double m2[7];
+    pose_mul(q.T_odom_map, drift + 7 * (size_t)i, m2);  // T_odom_map = T_odom_map * Tw1_w2 (:908), for every sequence of the group
+    memcpy(q.T_odom_map, m2, sizeof(m2));
+  }
+  if (h_drift7) memcpy(h_drift7, drift, sizeof(double) * 7 * (size_t)NS);
   return FLVIS_OK;
 }
 

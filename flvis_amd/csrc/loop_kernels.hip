@@ -693,6 +693,36 @@ __global__ __launch_bounds__(PGO_T) void k_pgo(const PgoGraph* graphs) {
 }
 
 
+// ---- joint pose graph of several sequences (flvis_loop_closer_merge): the two kernels around k_pgo ------------------------------------
+// The batch of virtual sequences [a | 5 absent | b | ...] out of the pose database: row r is database slot src[r], or absent (< 0), which
+// k_pgo never reads and which gets the identity.  One thread per double.
+__global__ __launch_bounds__(256) void k_lc_merge_gather(const int* __restrict__ src, int n_rows, const double* __restrict__ db_T,
+                                                         double* __restrict__ V) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= 7LL * n_rows) return;
+  const int r = (int)(i / 7), c = (int)(i % 7);
+  const int s = src[r];
+  V[i] = s >= 0 ? db_T[(size_t)s * 7 + c] : (c == 6 ? 1.0 : 0.0);
+}
+
+// The optimised virtual sequences back into the pose database, one workgroup per sequence of every group: rows first .. v_s are vertices
+// and get the optimised pose, the rows behind v_s get T_c_w_old * drift (vo_loopclosing.cpp:922-925) with
+// drift = inv(T_c_w_old(v_s)) * T_c_w_new(v_s), which also goes out for the host's T_odom_map.  Row v_s is read (old) and written (new)
+// here: every thread forms the drift from the old row BEFORE the barrier, every store to the database comes after it, and no other
+// workgroup touches this sequence's rows.
+__global__ __launch_bounds__(256) void k_lc_merge_apply(const LcMergeSeq* __restrict__ seqs, const double* __restrict__ V, double* db_T,
+                                                        double* __restrict__ drift7) {
+  const LcMergeSeq q = seqs[blockIdx.x];
+  double* const T = db_T + (size_t)q.db_base * 7;
+  const double* const Vs = V + (size_t)q.v_base * 7;
+  const SE3d drift = iso_mul(iso_inv(load_pose7(T + 7 * (size_t)q.v_s)), load_pose7(Vs + 7 * (size_t)q.v_s));
+  __syncthreads();
+  for (int k = q.first + (int)threadIdx.x; k < q.n; k += 256)
+    store_pose7(T + 7 * (size_t)k, k <= q.v_s ? load_pose7(Vs + 7 * (size_t)k) : iso_mul(load_pose7(T + 7 * (size_t)k), drift));
+  if (threadIdx.x == 0) store_pose7(drift7 + 7 * (size_t)blockIdx.x, drift);
+}
+
+
 // ---- 3-D positions of a keyframe's ORB keypoints (vo_loopclosing.cpp:255-372) ---------------------------------------------------
 // (LcCam, a keyframe's camera: loop_kernels.hpp)
 constexpr int LC_T = 1024;
@@ -1284,6 +1314,22 @@ int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_se
   k_lc_select_maps<<<n_q, LSM_T, 0, ctx->stream>>>(d_scores, n_seg, seg_len, d_seg_n, d_map, compact ? 1 : 0, n_best, min_score, d_idx, d_score,
                                                     d_count);
   CHECK_LAUNCH(ctx, "lc_select_maps");
+  return FLVIS_OK;
+}
+
+int lc_merge_gather_dev(flvis_ctx* ctx, const int* d_src, int n_rows, const double* d_db_T, double* d_V) {
+  if (!d_src || n_rows <= 0 || !d_db_T || !d_V) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_merge_gather: bad args");
+  hipSetDevice(ctx->device);
+  k_lc_merge_gather<<<(unsigned)((7LL * n_rows + 255) / 256), 256, 0, ctx->stream>>>(d_src, n_rows, d_db_T, d_V);
+  CHECK_LAUNCH(ctx, "lc_merge_gather");
+  return FLVIS_OK;
+}
+
+int lc_merge_apply_dev(flvis_ctx* ctx, const LcMergeSeq* d_seqs, int n_seqs, const double* d_V, double* d_db_T, double* d_drift7) {
+  if (!d_seqs || n_seqs <= 0 || !d_V || !d_db_T || !d_drift7) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_merge_apply: bad args");
+  hipSetDevice(ctx->device);
+  k_lc_merge_apply<<<n_seqs, 256, 0, ctx->stream>>>(d_seqs, d_V, d_db_T, d_drift7);
+  CHECK_LAUNCH(ctx, "lc_merge_apply");
   return FLVIS_OK;
 }
 

@@ -29,4 +29,14 @@ int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const
 int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map, bool compact,
                        int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
 
+// flvis_loop_closer_merge's two kernels.  A sequence of a group, as the apply kernel sees it: its keyframes are database slots db_base ..
+// db_base + n - 1 and rows v_base .. v_base + n - 1 of the batch of virtual sequences; keyframes first .. v_s are vertices of the joint graph.
+struct LcMergeSeq {
+  int db_base, v_base, first, v_s, n;
+};
+// d_V[r] = d_db_T[d_src[r]], or the identity pose for an absent row (d_src[r] < 0): every group's virtual sequence in one launch
+int lc_merge_gather_dev(flvis_ctx* ctx, const int* d_src, int n_rows, const double* d_db_T, double* d_V);
+// the optimised rows back into d_db_T, the rows behind a sequence's last vertex times its drift, the drifts into d_drift7 [n_seqs][7]
+int lc_merge_apply_dev(flvis_ctx* ctx, const LcMergeSeq* d_seqs, int n_seqs, const double* d_V, double* d_db_T, double* d_drift7);
+
 }  // namespace flvis

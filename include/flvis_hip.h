@@ -786,6 +786,47 @@ int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* 
  * The use it is for: after flvis_reset_streams on a tracker slot, localize the slot's first frame (tracker pose T_c_odom), set
  * T_odom_map = inv(T_c_odom) * T_c_map, and keep adding the slot's keyframes: they land in the map the sequence already has. */
 int flvis_loop_closer_set_drift(flvis_loop_closer* lc, int stream, const double* h_T_odom_map7);
+/* Merging sequences' maps: ONE pose graph over the keyframes of several sequences that have seen the same place.  (The project's own: the
+ * reference runs one sequence.)
+ * Link: ties keyframe kf_from of sequence seq_from to keyframe kf_to of sequence seq_to; pose7 is the `to` camera from the `from` camera, the
+ * form of flvis_lc_event.loop_pose7 and flvis_lc_fix.cand_pose7 (its quaternion is normalised here).  An accepted candidate r of a
+ * localize_in fix whose query frame was also stored as keyframe k of sequence q is the link (cand_seq[r], cand_kf[r]) -> (q, k), cand_pose7[r].
+ * Group: the sequences h_seq[h_group_ptr[g] .. h_group_ptr[g + 1]), at least two, distinct; the first is the anchor, whose frame is the
+ * merged map's.  Several disjoint groups go in one call and are optimised by one launch, one workgroup per group.
+ * Joint graph of a group: flvis_hip_pgo_loop_closure with use_initial_guess = 1 on the virtual sequence
+ *   rows:  the current T_c_w of every keyframe of the first sequence, 5 absent rows, every keyframe of the second sequence, 5 absent rows, ...
+ *   loops: per sequence in group order its recorded loops in recorded order, shifted by the sequence's offset in the rows; then the group's
+ *          links in the caller's order as (offset_from + kf_from, offset_to + kf_to).
+ * Five absent rows cut the odometry chain, so only links tie the sequences; vertices, the fixed vertex, the edge order and the Cauchy /
+ * Levenberg schedule are that call's.
+ * Result per sequence s of a group, v_s its last keyframe that is a vertex (its last keyframe; in the group's last sequence the one at
+ * max(later)): vertex rows get the optimised T_c_w, drift_s = inv(T_c_w_old(v_s)) * T_c_w_new(v_s), every keyframe behind v_s gets
+ * T_c_w_old * drift_s (vo_loopclosing.cpp:922-925), and the sequence's T_odom_map becomes T_odom_map * drift_s: keyframes added afterwards
+ * land in the merged frame.  Keyframes of the anchor before the first vertex stay as they are.  Nothing else changes: loop lists, the
+ * pose-graph trigger, a pending unprocessed keyframe, similarity rows, the landmark database, and every sequence outside the groups.
+ * The call keeps no links: the caller passes the whole list every time, and a second merge is another run on the current poses.
+ * h_out[g]: whether group g's graph ran (always, for arguments that pass the checks), its vertices, edges, iterations and chi2 before / after.
+ * h_drift7 (may be NULL): drift_s in the order of h_seq.
+ * Buffers: the virtual sequences and the loop poses get device buffers of the call's own on its first use (and larger ones when a later call
+ * needs them); when that allocation fails the call returns FLVIS_ERR_HIP and the closer stays usable.  A closer that never merges allocates none.
+ * FLVIS_ERR_INVALID_ARG before anything is queued, and nothing changes: a NULL closer, h_group_ptr, h_seq, h_links or h_out; n_groups <= 0;
+ * h_group_ptr that does not start at 0; a group of fewer than two sequences; a sequence out of range, or listed twice within or across groups;
+ * an empty sequence in a group; a link whose sequences are not both in one group, whose two ends are in the same sequence, or whose `from`
+ * sequence does not come before its `to` sequence in the group's order (the caller orders the group, no pose is inverted here); a keyframe
+ * index outside its sequence; a pose7 that is not finite or has a zero quaternion; a non-anchor sequence that no chain of links connects to
+ * the anchor; n_links < 0; iterations < 0. */
+typedef struct flvis_lc_link {
+  int seq_from, seq_to;
+  int64_t kf_from, kf_to;
+  double pose7[7];
+} flvis_lc_link;
+typedef struct flvis_lc_merge {
+  int optimised, n_vertices, n_edges, iterations;
+  double chi2_before, chi2_after;
+} flvis_lc_merge;
+int flvis_loop_closer_merge(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr /* [n_groups + 1] */, const int* h_seq,
+                            int n_links, const flvis_lc_link* h_links, int iterations /* 100: the reference's */,
+                            flvis_lc_merge* h_out /* [n_groups] */, double* h_drift7 /* [h_group_ptr[n_groups]][7], may be NULL */);
 
 #ifdef __cplusplus
 }
