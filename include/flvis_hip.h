@@ -111,7 +111,26 @@ int flvis_hip_feature_dem_redetect(flvis_ctx* ctx, const uint8_t* d_img, int w, 
  * (OpenCV's order is an artefact of std::nth_element); d_kps rows are (x, y, size, angle_deg, response, octave).
  * h_pattern: host table of the 256 test pairs as int8 [512][2] (x, y), e.g. OpenCV's learned bit_pattern_31_ when the
  * descriptors must be compatible with a DBoW vocabulary; NULL selects OpenCV's generator makeRandomPattern(31, ., 512)
- * (flvis_orb_default_pattern).  d_overflow (optional, [n_img]) is set non-zero where a capacity truncated the result. */
+ * (flvis_orb_default_pattern).  d_overflow (optional, [n_img]) is set non-zero where a capacity truncated the result.
+ *
+ * Capacities and what survives them.  Both retainBest cuts keep, as OpenCV does, everything >= the n-th best, so a class of equal
+ * scores / equal Harris responses (integer sums: periodic imagery ties exactly) that straddles a cut is kept whole and a level can
+ * return more than its budget nfeat[l] (orb.cpp's geometric split of nfeatures).  Three capacities bound that, each per image:
+ *   1. candidates: at most 8192 survivors of the FAST-score cut (>= the (2 nfeat[l])-th best score) per level.  Beyond that the
+ *      first 8192 in raster order go on, and the Harris cut of that level is taken among them alone: the level's list is then
+ *      some valid keypoints of the level, not necessarily a prefix of the untruncated list.
+ *   2. per level: at most lvl_cap = m + m / 4 + 64 keypoints with m = max_l nfeat[l] (335 for the reference's parameters).  The
+ *      Harris threshold is still the one over all candidates; the first lvl_cap keypoints >= it in raster order survive.
+ *   3. the caller's cap: of the level-major concatenation of the level lists the first cap rows survive, d_count = min(total, cap).
+ * Every truncation sets d_overflow of its image (the flags of all n_img images are cleared at the start of each call) and
+ * touches nothing else: the other images of the batch, the levels that did not overflow, and the rows [d_count, cap) of d_kps /
+ * d_desc, which are never written.  Without truncation the result is complete and d_overflow is 0.
+ * Refused before anything is launched or written: w or h < 64 or > 32767, nlevels outside 1 .. 12, scale_factor <= 1,
+ * nfeatures < 1, fast_threshold outside 1 .. 254, a level smaller than 8 px (FLVIS_ERR_INVALID_ARG), and 2 m > 6144
+ * (FLVIS_ERR_CAPACITY: the candidate buffer must hold retainBest(2 m) with room for ties).  A level of 62 px or less in either
+ * direction has no border box and yields no keypoints.
+ * flvis_loop_closer calls this with nfeatures 1000 and cap 1024 and does not read the flag: a keyframe with more than 1024
+ * keypoints (ties make that possible) is stored from its first 1024 rows, silently. */
 typedef struct flvis_orb_params {
   int nfeatures;       /* 1000 in the reference */
   float scale_factor;  /* 1.2f */
@@ -130,11 +149,14 @@ int flvis_hip_fast_score(flvis_ctx* ctx, const uint8_t* d_img, int w, int h, int
 int flvis_hip_gaussian_blur7(flvis_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n_img);
 /* cv::BFMatcher(cv::NORM_HAMMING, false).knnMatch(query, train, matches, 2) (vo_loopclosing.cpp:601-613) for n_pairs
  * independent (query, train) sets of 32-byte descriptors: d_query [n_pairs][qcap][32], d_nq [n_pairs], likewise train.
- * d_idx / d_dist: [n_pairs][qcap][2], ascending distance, ties keep the lower train index; -1 / INT_MAX when absent. */
+ * d_idx / d_dist: [n_pairs][qcap][2], ascending distance, ties keep the lower train index; -1 / INT_MAX when absent.
+ * A count above its capacity is read as the capacity, a negative one as 0; rows [count, qcap) of d_idx / d_dist are not written. */
 int flvis_hip_hamming_knn2(flvis_ctx* ctx, const uint8_t* d_query, const int* d_nq, int qcap, const uint8_t* d_train,
                            const int* d_nt, int tcap, int n_pairs, int* d_idx, int* d_dist);
 /* the mutual-best + ratio test of vo_loopclosing.cpp:603-639 (knnMatch both ways, keep i when the best match of its best
- * match is i and d0/d1 < ratio_max), pairs (index in a, index in b) in ascending a order: d_pairs [n_pairs][acap][2]. */
+ * match is i and d0/d1 < ratio_max), pairs (index in a, index in b) in ascending a order: d_pairs [n_pairs][acap][2].
+ * Counts are clamped as in flvis_hip_hamming_knn2; a set of fewer than 2 descriptors gives no pair (knnMatch has no second
+ * neighbour), and so does d0 = d1 = 0 (exact duplicates in b: 0/0 is not < ratio_max).  Rows [d_npairs, acap) are not written. */
 int flvis_hip_orb_match(flvis_ctx* ctx, const uint8_t* d_a, const int* d_na, int acap, const uint8_t* d_b, const int* d_nb,
                         int bcap, int n_pairs, double ratio_max, int* d_pairs, int* d_npairs);
 
