@@ -14,9 +14,19 @@ void equalize_hist(const uint8_t* src, uint8_t* dst, int w, int h);
 void cvt_bgr_to_gray(const uint8_t* src, int channels, uint8_t* dst, int w, int h);
 void pyr_down(const uint8_t* src, int w, int h, uint8_t* dst);
 int lk_num_levels(int w, int h, int win, int max_level);
+// Opt-in trace of calc_optical_flow_pyr_lk for the tests that aim inputs at the tracker's edges: what happened at each (level, point)
+// visit.  visit is [levels + 1][n][6], sums [levels + 1][n][4], zeroed by the caller (a visit that never happened stays 0).
+//   visit: iterations run, exit cause (LkCause), largest |inx - inx_first|, largest |iny - iny_first| over the level's iterations,
+//          inx_first, iny_first (the search window's start at the level's first iteration; 0 when none ran)
+//   sums:  |iA11|, |iA22| of the template, largest |ib1|, largest |ib2| over the level's iterations
+enum LkCause { LK_NOT_VISITED = 0, LK_CONVERGED = 1, LK_OSCILLATION = 2, LK_EXHAUSTED = 3, LK_LEFT_IMAGE = 4, LK_FLAT = 5, LK_TEMPLATE_OUTSIDE = 6 };
+struct LkTrace {
+  int32_t* visit;
+  int64_t* sums;
+};
 void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts,
                               float* next_pts, uint8_t* status, int n, int win, int max_level, int max_iter,
-                              double eps, int use_initial_flow, float min_eig_thr);
+                              double eps, int use_initial_flow, float min_eig_thr, const LkTrace* trace = nullptr);
 void min_eigen_map(const uint8_t* img, int w, int h, float* eig);
 int good_features_to_track(const uint8_t* img, int w, int h, int max_corners, double quality, double min_distance,
                            float* out_xy);

@@ -151,7 +151,7 @@ static void build_pyramid(const uint8_t* img, int w, int h, int levels, std::vec
 // cv::calcOpticalFlowPyrLK restated (LKTrackerInvoker::operator()).  next_pts is in/out (OPTFLOW_USE_INITIAL_FLOW).
 void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts,
                               float* next_pts, uint8_t* status, int n, int win, int max_level, int max_iter,
-                              double eps, int use_initial_flow, float min_eig_thr) {
+                              double eps, int use_initial_flow, float min_eig_thr, const LkTrace* trace) {
   const int levels = lk_num_levels(w, h, win, max_level);
   std::vector<Level> P, N;
   build_pyramid(prev, w, h, levels, P);
@@ -171,6 +171,9 @@ void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, i
     const Level& I = P[level];
     const Level& J = N[level];
     for (int p = 0; p < n; p++) {
+      // opt-in trace of this (level, point) visit: written on every way out of it, read by nothing here
+      int32_t* const tr_v = trace ? trace->visit + ((size_t)level * n + p) * 6 : nullptr;
+      int64_t* const tr_s = trace ? trace->sums + ((size_t)level * n + p) * 4 : nullptr;
       float ppx = prev_pts[2 * p] * (float)(1. / (1 << level));
       float ppy = prev_pts[2 * p + 1] * (float)(1. / (1 << level));
       float npx, npy;
@@ -194,6 +197,7 @@ void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, i
       int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
       if (ipx < -win || ipx >= I.w || ipy < -win || ipy >= I.h) {
         if (level == 0) status[p] = 0;
+        if (tr_v) tr_v[1] = LK_TEMPLATE_OUTSIDE;
         continue;
       }
       float a = ppx - ipx, b = ppy - ipy;
@@ -226,19 +230,29 @@ void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, i
       float A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
       float D = A11 * A22 - A12 * A12;
       float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
+      if (tr_s) tr_s[0] = iA11, tr_s[1] = iA22;
       if (minEig < min_eig_thr || D < 1.1920929e-07f /*FLT_EPSILON*/) {
         if (level == 0) status[p] = 0;
+        if (tr_v) tr_v[1] = LK_FLAT;
         continue;
       }
       D = 1.f / D;
       npx -= halfWin;
       npy -= halfWin;
       float pdx = 0, pdy = 0;
+      int tr_cause = LK_EXHAUSTED, tr_iters = 0, tr_inx0 = 0, tr_iny0 = 0;
       for (int j = 0; j < max_iter; j++) {
         int inx = (int)floorf(npx), iny = (int)floorf(npy);
         if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
           if (level == 0) status[p] = 0;
+          tr_cause = LK_LEFT_IMAGE;
           break;
+        }
+        if (tr_v) {
+          if (j == 0) tr_inx0 = tr_v[4] = inx, tr_iny0 = tr_v[5] = iny;
+          tr_iters = j + 1;
+          tr_v[2] = std::max(tr_v[2], std::abs(inx - tr_inx0));
+          tr_v[3] = std::max(tr_v[3], std::abs(iny - tr_iny0));
         }
         a = npx - inx;
         b = npy - iny;
@@ -258,6 +272,7 @@ void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, i
             ib2 += (int64_t)diff * dIWin[((size_t)y * win + x) * 2 + 1];
           }
         }
+        if (tr_s) tr_s[2] = std::max(tr_s[2], (int64_t)std::llabs(ib1)), tr_s[3] = std::max(tr_s[3], (int64_t)std::llabs(ib2));
         float b1 = (float)ib1 * FLT_SCALE, b2 = (float)ib2 * FLT_SCALE;
         float dx = (A12 * b2 - A22 * b1) * D;
         float dy = (A12 * b1 - A11 * b2) * D;
@@ -265,15 +280,20 @@ void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, i
         npy += dy;
         next_pts[2 * p] = npx + halfWin;
         next_pts[2 * p + 1] = npy + halfWin;
-        if ((double)dx * dx + (double)dy * dy <= eps2) break;
+        if ((double)dx * dx + (double)dy * dy <= eps2) {
+          tr_cause = LK_CONVERGED;
+          break;
+        }
         if (j > 0 && std::fabs(dx + pdx) < 0.01 && std::fabs(dy + pdy) < 0.01) {
           next_pts[2 * p] -= dx * 0.5f;
           next_pts[2 * p + 1] -= dy * 0.5f;
+          tr_cause = LK_OSCILLATION;
           break;
         }
         pdx = dx;
         pdy = dy;
       }
+      if (tr_v) tr_v[0] = tr_iters, tr_v[1] = tr_cause;
       // error stage (the reference passes an err vector, so the final in-bounds test is live)
       if (status[p] && level == 0) {
         float fx = next_pts[2 * p] - halfWin, fy = next_pts[2 * p + 1] - halfWin;
@@ -512,6 +532,16 @@ void ref_calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int 
                                   double eps, int use_initial_flow, float min_eig_thr) {
   ref::calc_optical_flow_pyr_lk(prev, next, w, h, prev_pts, next_pts, status, n, win, max_level, max_iter, eps,
                                 use_initial_flow, min_eig_thr);
+}
+// The same call with the per-visit trace: visit int32 [levels + 1][n][6], sums int64 [levels + 1][n][4] (LkTrace in ref_api.h), zeroed by the
+// caller; returns the number of the top level.  The results are those of ref_calc_optical_flow_pyr_lk, bit for bit.
+int ref_calc_optical_flow_pyr_lk_trace(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts, float* next_pts,
+                                       uint8_t* status, int n, int win, int max_level, int max_iter, double eps, int use_initial_flow,
+                                       float min_eig_thr, int32_t* visit, int64_t* sums) {
+  const ref::LkTrace tr{visit, sums};
+  ref::calc_optical_flow_pyr_lk(prev, next, w, h, prev_pts, next_pts, status, n, win, max_level, max_iter, eps, use_initial_flow,
+                                min_eig_thr, &tr);
+  return ref::lk_num_levels(w, h, win, max_level);
 }
 void ref_min_eigen_map(const uint8_t* img, int w, int h, float* eig) { ref::min_eigen_map(img, w, h, eig); }
 int ref_good_features_to_track(const uint8_t* img, int w, int h, int max_corners, double q, double min_dist,

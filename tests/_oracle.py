@@ -81,6 +81,37 @@ def lk(prev, nxt, prev_pts, next_pts, win=31, max_level=10, max_iter=30, eps=1e-
     return npts, st
 
 
+LK_CAUSES = ("not_visited", "converged", "oscillation", "exhausted", "left_image", "flat", "template_outside")      # LkCause of oracle/ref_api.h
+
+
+def lk_trace(prev, nxt, prev_pts, next_pts, win=31, max_level=10, max_iter=30, eps=1e-3, use_initial=True, min_eig=1e-4):
+    """O.lk with the oracle's per-visit trace -> (next_pts, status, trace).  trace: levels (the top level's number) and, each
+    [levels + 1, n]: iters, cause (an index into LK_CAUSES), move_x / move_y (largest |inx - inx_first| / |iny - iny_first| over the
+    level's iterations), first_x / first_y (inx / iny of the level's first iteration), a11 / a22 (the template's Hessian sums), b1 / b2 (the largest |ib1| / |ib2| over the level's iterations)."""
+    prev = np.ascontiguousarray(prev, np.uint8)
+    nxt = np.ascontiguousarray(nxt, np.uint8)
+    pp = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+    npts = np.ascontiguousarray(next_pts, np.float32).reshape(-1, 2).copy()
+    n = pp.shape[0]
+    st = np.zeros(n, np.uint8)
+    g = lib().ref_lk_num_levels
+    g.argtypes = [C.c_int] * 4
+    levels = g(prev.shape[1], prev.shape[0], win, max_level)
+    visit = np.zeros((levels + 1, n, 6), np.int32)
+    sums = np.zeros((levels + 1, n, 4), np.int64)
+    f = lib().ref_calc_optical_flow_pyr_lk_trace
+    f.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_float),
+                  C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                  C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    got = f(_p(prev, C.c_uint8), _p(nxt, C.c_uint8), prev.shape[1], prev.shape[0], _p(pp, C.c_float), _p(npts, C.c_float),
+            _p(st, C.c_uint8), n, win, max_level, max_iter, eps, int(use_initial), min_eig, _p(visit, C.c_int32), _p(sums, C.c_int64))
+    assert got == levels
+    tr = dict(levels=levels, iters=visit[..., 0], cause=visit[..., 1], move_x=visit[..., 2], move_y=visit[..., 3],
+              first_x=visit[..., 4], first_y=visit[..., 5],
+              a11=sums[..., 0], a22=sums[..., 1], b1=sums[..., 2], b2=sums[..., 3])
+    return npts, st, tr
+
+
 def min_eigen_map(img):
     img = np.ascontiguousarray(img, np.uint8)
     out = np.empty(img.shape, np.float32)
