@@ -332,6 +332,21 @@ class Context:
         self._check(self._lib.flvis_hip_bow_set_vocabulary(self._h, n, _P(cp, C.c_int), _P(ci, C.c_int), _P(ds, C.c_uint8),
                                                            _P(wt, C.c_double), _P(wi, C.c_int)), "bow_set_vocabulary")
 
+    def voc_train(self, desc, count, k=10, L=5, seed=1, weighting=0, max_iters=0, small_node_max=0):
+        """flvis_hip_voc_train: DBoW3's Vocabulary::create on the device.  desc uint8 [n,cap,32], count int32 [n] (device tensors, as
+        orb_detect_and_compute returns them) -> TrainedVocabulary."""
+        import torch
+        desc = desc.contiguous()
+        assert desc.dtype == torch.uint8 and desc.is_cuda and desc.dim() == 3 and desc.shape[2] == 32
+        assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.numel() == desc.shape[0]
+        prm = VocTrainParams(int(k), int(L), int(weighting), int(seed) & 0xFFFFFFFF, int(max_iters), int(small_node_max))
+        h = C.c_void_p(0)
+        stats = (C.c_int64 * 8)()
+        self._lib.flvis_hip_voc_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self._lib.flvis_hip_voc_train(self._h, _ptr(desc), _ptr(count), desc.shape[1], desc.shape[0], C.byref(prm), C.byref(h),
+                                                  stats), "voc_train")
+        return TrainedVocabulary(self._lib, h, list(stats))
+
     def bow_load_vocabulary(self, path):
         """flvis_hip_bow_load_vocabulary: `Vocabulary voc(path)` of vo_loopclosing.cpp:1097 (.dbow3 / .txt / .yml / .yml.gz)."""
         self._check(self._lib.flvis_hip_bow_load_vocabulary(self._h, C.c_char_p(os.fsencode(path))), "bow_load_vocabulary")
@@ -518,21 +533,111 @@ def read_vocabulary_file(path):
     if rc != FLVIS_OK:
         raise FlvisError("flvis_voc_file_open(%s): %s" % (path, err.value.decode(errors="replace") or rc))
     try:
-        info = (C.c_int * 8)()
-        lib.flvis_voc_file_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        lib.flvis_voc_file_info(h, info)
-        n, n_words, k, L, scoring, weighting, n_edges, layout = list(info)
-        ptrs = [C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_double)(), C.POINTER(C.c_int)()]
-        lib.flvis_voc_file_arrays.argtypes = [C.c_void_p] + [C.c_void_p] * 5
-        lib.flvis_voc_file_arrays(h, *[C.byref(q) for q in ptrs])
-        take = lambda q, cnt, dt: np.ctypeslib.as_array(q, shape=(cnt,)).astype(dt, copy=True) if cnt else np.zeros(0, dt)
-        return {"child_ptr": take(ptrs[0], n + 1, np.int32), "child_idx": take(ptrs[1], n_edges, np.int32),
-                "desc": take(ptrs[2], n * 32, np.uint8).reshape(n, 32), "weight": take(ptrs[3], n, np.float64),
-                "word_id": take(ptrs[4], n, np.int32), "k": k, "L": L, "scoring": scoring, "weighting": weighting,
-                "n_words": n_words, "layout": ["binary", "binary-quicklz", "text", "yaml"][layout]}
+        return _voc_handle_dict(lib, h)
     finally:
         lib.flvis_voc_file_close.argtypes = [C.c_void_p]
         lib.flvis_voc_file_close(h)
+
+
+_VOC_LAYOUTS = ["binary", "binary-quicklz", "text", "yaml", "trained"]
+
+
+def _voc_handle_dict(lib, h):
+    """the content of a flvis_voc_file handle, copied out"""
+    import numpy as np
+    info = (C.c_int * 8)()
+    lib.flvis_voc_file_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.flvis_voc_file_info(h, info)
+    n, n_words, k, L, scoring, weighting, n_edges, layout = list(info)
+    ptrs = [C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_double)(), C.POINTER(C.c_int)()]
+    lib.flvis_voc_file_arrays.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.flvis_voc_file_arrays(h, *[C.byref(q) for q in ptrs])
+    take = lambda q, cnt, dt: np.ctypeslib.as_array(q, shape=(cnt,)).astype(dt, copy=True) if cnt else np.zeros(0, dt)
+    return {"child_ptr": take(ptrs[0], n + 1, np.int32), "child_idx": take(ptrs[1], n_edges, np.int32),
+            "desc": take(ptrs[2], n * 32, np.uint8).reshape(n, 32), "weight": take(ptrs[3], n, np.float64),
+            "word_id": take(ptrs[4], n, np.int32), "k": k, "L": L, "scoring": scoring, "weighting": weighting,
+            "n_words": n_words, "layout": _VOC_LAYOUTS[layout]}
+
+
+def save_vocabulary_file(path, arrays, k, L, scoring=0, weighting=0):
+    """flvis_voc_file_save_arrays (host only): the flat arrays (child_ptr, child_idx, desc [n,32], weight, word_id) as an uncompressed
+    binary .dbow3 file, byte for byte what DBoW3's Vocabulary::save(path, false) writes."""
+    import numpy as np
+    lib = load_library()
+    cp = np.ascontiguousarray(arrays[0], np.int32)
+    ci = np.ascontiguousarray(arrays[1], np.int32)
+    ds = np.ascontiguousarray(arrays[2], np.uint8)
+    wt = np.ascontiguousarray(arrays[3], np.float64)
+    wi = np.ascontiguousarray(arrays[4], np.int32)
+    n = len(cp) - 1
+    if ds.shape != (n, 32) or len(wt) != n or len(wi) != n or len(ci) != n - 1:
+        raise FlvisError("save_vocabulary_file: the arrays do not describe one tree of %d nodes" % n)
+    lib.flvis_voc_file_save_arrays.argtypes = [C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4
+    rc = lib.flvis_voc_file_save_arrays(os.fsencode(path), 0, n, cp.ctypes.data, ci.ctypes.data, ds.ctypes.data, wt.ctypes.data,
+                                        wi.ctypes.data, int(k), int(L), int(scoring), int(weighting))
+    if rc != FLVIS_OK:
+        raise FlvisError("flvis_voc_file_save_arrays(%s) failed (%d)" % (path, rc))
+
+
+def convert_vocabulary_file(src, dst):
+    """flvis_voc_file_open + flvis_voc_file_save (host only): any readable vocabulary file rewritten as an uncompressed .dbow3."""
+    lib = load_library()
+    h = C.c_void_p(0)
+    err = C.create_string_buffer(512)
+    lib.flvis_voc_file_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
+    rc = lib.flvis_voc_file_open(os.fsencode(src), C.byref(h), err, 512)
+    if rc != FLVIS_OK:
+        raise FlvisError("flvis_voc_file_open(%s): %s" % (src, err.value.decode(errors="replace") or rc))
+    try:
+        lib.flvis_voc_file_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        rc = lib.flvis_voc_file_save(h, os.fsencode(dst), 0)
+        if rc != FLVIS_OK:
+            raise FlvisError("flvis_voc_file_save(%s) failed (%d)" % (dst, rc))
+    finally:
+        lib.flvis_voc_file_close.argtypes = [C.c_void_p]
+        lib.flvis_voc_file_close(h)
+
+
+class VocTrainParams(C.Structure):
+    """flvis_voc_train_params of include/flvis_hip.h."""
+    _fields_ = [("k", C.c_int), ("L", C.c_int), ("weighting", C.c_int), ("seed", C.c_uint), ("max_iters", C.c_int),
+                ("small_node_max", C.c_int)]
+
+
+class TrainedVocabulary:
+    """What Context.voc_train returns: .arrays (child_ptr, child_idx, desc, weight, word_id with 0 on inner nodes -- the 5-tuple
+    Context.bow_set_vocabulary takes), .info (the dict read_vocabulary_file returns, word_id -1 on inner nodes), .stats (descriptors,
+    nodes, words, passes, capped, empty, trivial, launches), .save(path), .close()."""
+    STATS = ("descriptors", "nodes", "words", "passes", "capped", "empty", "trivial", "launches")
+
+    def __init__(self, lib, h, stats):
+        import numpy as np
+        self._lib, self._h = lib, h
+        self.info = _voc_handle_dict(lib, h)
+        self.stats = dict(zip(self.STATS, [int(x) for x in stats]))
+        i = self.info
+        self.arrays = (i["child_ptr"], i["child_idx"], i["desc"], i["weight"], np.maximum(i["word_id"], 0).astype(np.int32))
+
+    def save(self, path):
+        """flvis_voc_file_save: an uncompressed binary .dbow3 file"""
+        if not self._h:
+            raise FlvisError("TrainedVocabulary.save: closed")
+        self._lib.flvis_voc_file_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        rc = self._lib.flvis_voc_file_save(self._h, os.fsencode(path), 0)
+        if rc != FLVIS_OK:
+            raise FlvisError("flvis_voc_file_save(%s) failed (%d)" % (path, rc))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.flvis_voc_file_close.argtypes = [C.c_void_p]
+            self._lib.flvis_voc_file_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class OrbParams(C.Structure):

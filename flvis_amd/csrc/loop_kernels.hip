@@ -28,22 +28,12 @@
 #include "dev_math.hpp"
 #include "loop_kernels.hpp"
 #include "track_kernels.hpp"
+#include "voc_descent.hpp"
 
 namespace flvis {
 
 constexpr int BOW_T = 1024;
 constexpr int BOW_MAXF = 2048;  // descriptors per keyframe (the reference extracts 1000)
-
-struct VocDev {
-  const int* child_ptr;
-  const int* child_idx;
-  const uint8_t* desc;      // [n_nodes][32]
-  const int* word_id;       // per node (leaves)
-  const double* weight;     // per node (leaves: idf)
-  const double* word_weight;  // per word id
-  int n_nodes, n_words;
-  int depth;  // levels below the root (bounds the descent of k_bow_words)
-};
 
 // exclusive prefix sum of one int per thread over the workgroup (NW waves); total = the sum
 template <int NW>
@@ -69,13 +59,6 @@ __device__ inline int block_exclusive_scan(int v, int* s_part, int& total) {
   return off + inc - v;
 }
 
-__device__ inline int hamming256(const uint4 a0, const uint4 a1, const uint8_t* b) {
-  const uint4* q = reinterpret_cast<const uint4*>(b);
-  const uint4 b0 = q[0], b1 = q[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-         __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // word of every descriptor: d_words[img][r] = word id, or INT_MAX when r >= count or the word is stopped (weight <= 0)
 __global__ __launch_bounds__(256) void k_bow_words(VocDev v, const uint8_t* __restrict__ desc, const int* __restrict__ count, int dcap,
                                                    int* __restrict__ words) {
@@ -85,27 +68,8 @@ __global__ __launch_bounds__(256) void k_bow_words(VocDev v, const uint8_t* __re
   if (r < min(count[img], dcap)) {
     const uint4* f = reinterpret_cast<const uint4*>(desc + ((size_t)img * dcap + r) * 32);
     const uint4 f0 = f[0], f1 = f[1];
-    int node = 0;
-    // (flvis_hip_bow_set_vocabulary only accepts trees, so the descent ends after at most `depth` levels; the bound keeps a
-    // corrupted table from hanging the GPU: it then yields no word)
-    bool leaf = false;
-    for (int level = 0; level <= v.depth; level++) {
-      const int c0 = v.child_ptr[node], c1 = v.child_ptr[node + 1];
-      if (c0 == c1) {
-        leaf = true;
-        break;
-      }
-      int best_d = INT_MAX, best = node;
-      for (int c = c0; c < c1; c++) {
-        const int id = v.child_idx[c];
-        const int d = hamming256(f0, f1, v.desc + (size_t)id * 32);
-        if (d < best_d) {
-          best_d = d;
-          best = id;
-        }
-      }
-      node = best;
-    }
+    bool leaf;
+    const int node = voc_descend(v, f0, f1, leaf);
     if (leaf && v.weight[node] > 0) out = v.word_id[node];
   }
   words[(size_t)img * dcap + r] = out;

@@ -18,6 +18,7 @@
 // stored weight per feature), scoring L1_NORM.  Anything else is refused with a message, never approximated.
 #include <zlib.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -31,14 +32,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
-
-struct flvis_voc_file {
-  int k = 0, L = 0, scoring = 0, weighting = 0, format = 0;
-  int n_nodes = 0, n_words = 0;
-  std::vector<int> child_ptr, child_idx, word_id;
-  std::vector<uint8_t> desc;
-  std::vector<double> weight;
-};
+#include "voc_file.hpp"
 
 namespace {
 
@@ -518,6 +512,71 @@ std::vector<uint8_t> read_file(const char* path) {  // through zlib: FileStorage
   return data;
 }
 
+// ---- the writer: Vocabulary::toStream(out, false) (Vocabulary.cpp:1180-1256) -------------------------------------------------
+// header (magic, compressed = 0, node count), k, L, scoring, weighting, one 60-byte record per non-root node in the order of
+// toStream's parent stack (the children of the parent popped last, in their order; a child with children is pushed), then the
+// word table in ascending word id.
+template <class T>
+void put(std::vector<uint8_t>& b, T v) {
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(&v);
+  b.insert(b.end(), p, p + sizeof(T));
+}
+
+int write_binary(const char* path, int n_nodes, const int* child_ptr, const int* child_idx, const uint8_t* desc, const double* weight,
+                 const int* word_id, int k, int L, int scoring, int weighting) {
+  if (n_nodes < 2 || child_ptr[0] != 0) return FLVIS_ERR_INVALID_ARG;
+  for (int n = 0; n < n_nodes; n++)
+    if (child_ptr[n + 1] < child_ptr[n]) return FLVIS_ERR_INVALID_ARG;
+  if (child_ptr[n_nodes] != n_nodes - 1) return FLVIS_ERR_INVALID_ARG;  // a tree of n nodes has n - 1 child links
+  for (int c = 0; c < n_nodes - 1; c++)
+    if (child_idx[c] <= 0 || child_idx[c] >= n_nodes) return FLVIS_ERR_INVALID_ARG;
+  std::vector<uint8_t> b;
+  b.reserve(13 + 16 + (size_t)(n_nodes - 1) * 68 + 4);
+  put<uint64_t>(b, kMagic);
+  put<uint8_t>(b, 0);
+  put<uint32_t>(b, (uint32_t)n_nodes);
+  put<int32_t>(b, k);
+  put<int32_t>(b, L);
+  put<int32_t>(b, scoring);
+  put<int32_t>(b, weighting);
+  std::vector<int> parents{0};
+  size_t written = 0;
+  while (!parents.empty()) {
+    const int pid = parents.back();
+    parents.pop_back();
+    for (int c = child_ptr[pid]; c < child_ptr[pid + 1]; c++) {
+      const int id = child_idx[c];
+      if (++written > (size_t)(n_nodes - 1)) return FLVIS_ERR_INVALID_ARG;  // the links do not form a tree
+      put<uint32_t>(b, (uint32_t)id);
+      put<uint32_t>(b, (uint32_t)pid);
+      put<double>(b, weight[id]);
+      put<int32_t>(b, 32);  // cv::Mat header: cols, rows, type CV_8U
+      put<int32_t>(b, 1);
+      put<int32_t>(b, 0);
+      b.insert(b.end(), desc + (size_t)id * 32, desc + (size_t)id * 32 + 32);
+      if (child_ptr[id + 1] > child_ptr[id]) parents.push_back(id);
+    }
+  }
+  if (written != (size_t)(n_nodes - 1)) return FLVIS_ERR_INVALID_ARG;
+  std::vector<std::pair<int, int>> words;  // (word id, node id)
+  for (int n = 1; n < n_nodes; n++)
+    if (child_ptr[n + 1] == child_ptr[n]) {
+      if (word_id[n] < 0) return FLVIS_ERR_INVALID_ARG;
+      words.push_back({word_id[n], n});
+    }
+  std::sort(words.begin(), words.end());
+  put<uint32_t>(b, (uint32_t)words.size());
+  for (auto& w : words) {
+    put<uint32_t>(b, (uint32_t)w.first);
+    put<uint32_t>(b, (uint32_t)w.second);
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return FLVIS_ERR_CONFIG;
+  const size_t done = fwrite(b.data(), 1, b.size(), f);
+  const int rc = fclose(f);
+  return (done == b.size() && rc == 0) ? FLVIS_OK : FLVIS_ERR_CONFIG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -571,6 +630,19 @@ int flvis_voc_file_arrays(const flvis_voc_file* v, const int** child_ptr, const 
 }
 
 void flvis_voc_file_close(flvis_voc_file* v) { delete v; }
+
+int flvis_voc_file_save_arrays(const char* path, int layout, int n_nodes, const int* child_ptr, const int* child_idx, const uint8_t* desc,
+                               const double* weight, const int* word_id, int k, int L, int scoring, int weighting) {
+  if (!path || !child_ptr || !child_idx || !desc || !weight || !word_id) return FLVIS_ERR_INVALID_ARG;
+  if (layout != 0) return FLVIS_ERR_INVALID_ARG;  // the QuickLZ, text and yaml writers do not exist
+  return write_binary(path, n_nodes, child_ptr, child_idx, desc, weight, word_id, k, L, scoring, weighting);
+}
+
+int flvis_voc_file_save(const flvis_voc_file* v, const char* path, int layout) {
+  if (!v || !path) return FLVIS_ERR_INVALID_ARG;
+  return flvis_voc_file_save_arrays(path, layout, v->n_nodes, v->child_ptr.data(), v->child_idx.data(), v->desc.data(), v->weight.data(),
+                                    v->word_id.data(), v->k, v->L, v->scoring, v->weighting);
+}
 
 int flvis_hip_bow_load_vocabulary(flvis_ctx* ctx, const char* path) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;

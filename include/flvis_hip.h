@@ -18,6 +18,7 @@
  *   flvis_hip_orb_detect_and_compute / _hamming_knn2 / _orb_match  <- cv::ORB, cv::BFMatcher   src/backend/vo_loopclosing.cpp:242-243,601-639
  *   flvis_hip_bow_load_vocabulary / _set_vocabulary / _transform / _score / _score_jobs, flvis_loop_candidate
  *                                <- DBoW3::Vocabulary(file), ::transform, ::score; isLoopCandidate   vo_loopclosing.cpp:1097,249-253,417-437,520-590
+ *   flvis_hip_voc_train, flvis_voc_file_save / _save_arrays   <- DBoW3::Vocabulary::create, ::save   3rdPartLib/DBow3/src/Vocabulary.cpp:142-569,1180-1256
  *   flvis_hip_lc_keyframe_landmarks(_rigs)  <- stereo LK + triangulation / depth lookup of the ORB keypoints   vo_loopclosing.cpp:255-372
  *   flvis_hip_pnp_ransac(_rigs)  <- cv::solvePnPRansac of isLoopClosureKF                             vo_loopclosing.cpp:660-686
  *   flvis_hip_pgo_loop_closure   <- loopClosureOnCovGraphG2ONew (g2o EdgeSE3 pose graph)              vo_loopclosing.cpp:742-944
@@ -174,13 +175,45 @@ int flvis_hip_bow_set_vocabulary(flvis_ctx* ctx, int n_nodes, const int* h_child
 int flvis_hip_bow_load_vocabulary(flvis_ctx* ctx, const char* path);
 /* the file reader on its own (host only, no device needed): the flat arrays flvis_hip_bow_set_vocabulary takes, owned by the
  * handle until flvis_voc_file_close.  info8 = {n_nodes, n_words, k, L, scoringType, weightingType, n_edges, layout}, layout
- * 0 binary, 1 binary QuickLZ, 2 text, 3 yaml.  word_id is -1 on inner nodes. */
+ * 0 binary, 1 binary QuickLZ, 2 text, 3 yaml, 4 trained by flvis_hip_voc_train (not from a file).  word_id is -1 on inner nodes. */
 typedef struct flvis_voc_file flvis_voc_file;
 int flvis_voc_file_open(const char* path, flvis_voc_file** out, char* err, int errlen);
 int flvis_voc_file_info(const flvis_voc_file* voc, int* info8);
 int flvis_voc_file_arrays(const flvis_voc_file* voc, const int** child_ptr, const int** child_idx, const uint8_t** desc,
                           const double** weight, const int** word_id);
 void flvis_voc_file_close(flvis_voc_file* voc);
+/* Vocabulary::save for the binary layout (host only): layout 0 writes the uncompressed .dbow3 stream of Vocabulary::toStream(out,
+ * false) (Vocabulary.cpp:1180-1256), byte for byte; layouts 1 .. 3 (QuickLZ, text, yaml) have no writer and return
+ * FLVIS_ERR_INVALID_ARG, as do null arguments and links that do not form a tree below node 0; FLVIS_ERR_CONFIG when the file cannot
+ * be written.  flvis_voc_file_save takes any handle -- trained, or opened from any readable layout, which makes it the converter
+ * to .dbow3 --, flvis_voc_file_save_arrays the flat arrays themselves (word_id is read on the leaves only). */
+int flvis_voc_file_save(const flvis_voc_file* voc, const char* path, int layout);
+int flvis_voc_file_save_arrays(const char* path, int layout, int n_nodes, const int* child_ptr, const int* child_idx,
+                               const uint8_t* desc, const double* weight, const int* word_id, int k, int L, int scoring,
+                               int weighting);
+/* Vocabulary::create (3rdPartLib/DBow3/src/Vocabulary.cpp:142-569) on the device, for the descriptors this library's ORB extractor
+ * leaves in d_desc [n_img][cap][32] / d_count [n_img] (a count above cap reads as cap, a negative one as 0; an image without
+ * descriptors still counts as a document): hierarchical k-means with k-means++ seeding and bit-majority means, then the idf
+ * weights from every training descriptor sent down the finished tree.  Two departures from DBoW3: each
+ * split node draws from its own glibc stream srand(seed + node id) and nodes are numbered breadth-first (so L = 1 is exactly
+ * Vocabulary::create after srand(seed)); a node's k-means ends after max_iters association passes.  Integer arithmetic throughout:
+ * two runs give the same tree bit for bit, whatever small_node_max.
+ * *out: a handle as flvis_voc_file_open returns it (info8.layout = 4), to be passed to flvis_voc_file_arrays / _save / _close.
+ * stats8 (may be null) = {descriptors, nodes, words, association passes in total, nodes that hit max_iters, children created
+ * without a descriptor (empty clusters kept), nodes split trivially (n <= k), kernel launches}.
+ * FLVIS_ERR_INVALID_ARG, before anything is launched: null pointers, k outside 2 .. 64, L outside 1 .. 10, weighting other than
+ * 0 / 1, max_iters or small_node_max negative, cap <= 0 or > 2048, n_img <= 0, no descriptor at all.
+ * FLVIS_ERR_CAPACITY, also before anything is launched: more than 65535 images, or more than 2^25 (33 554 432) descriptors. */
+typedef struct flvis_voc_train_params {
+  int k, L;           /* branching factor 2 .. 64, depth 1 .. 10 */
+  int weighting;      /* 0 TF_IDF, 1 TF (every word weight 1) */
+  unsigned seed;
+  int max_iters;      /* association passes per node; 0 = 100 */
+  int small_node_max; /* nodes of at most this many descriptors are clustered by one workgroup in LDS; 0 = 2048; values above what
+                         LDS holds are clamped */
+} flvis_voc_train_params;
+int flvis_hip_voc_train(flvis_ctx* ctx, const uint8_t* d_desc, const int* d_count, int cap, int n_img,
+                        const flvis_voc_train_params* params, flvis_voc_file** out, int64_t* stats8);
 /* voc.transform(kf.lm_descriptor, kf_bv) (vo_loopclosing.cpp:249-253; Vocabulary.cpp:628-688) for n_img keyframes:
  * d_desc [n_img][dcap][32] + d_count [n_img] as flvis_hip_orb_detect_and_compute leaves them (dcap <= 2048);
  * out: d_ids / d_vals [n_img][vcap] ascending word ids and L1-normalised values, d_nnz [n_img]; vcap >= min(dcap, words of the
