@@ -416,6 +416,32 @@ class Context:
                     "lc_select_maps")
         return idx, sc, cnt
 
+    def lc_select_maps_skip(self, scores, seg_n, maps, skip, n_best, min_score):
+        """flvis_hip_lc_select_maps_skip: lc_select_maps with skip int32 [n_q, 2] = (lo, hi) per query -- the global indices lo <= g < hi
+        are never candidates and are not read.  scores [n_q, n_seg, seg_len], or [n_q, seg_len]: the compact rows that hold segment
+        maps[q] alone (flvis_hip_lc_select_maps_skip_compact; seg_n then tells the number of segments, and skip may be None)."""
+        import torch
+        scores = scores.contiguous()
+        compact = scores.dim() == 2
+        n_q, n_seg, seg_len = (scores.shape[0], seg_n.numel(), scores.shape[1]) if compact else scores.shape
+        assert scores.dtype == torch.float64 and seg_n.dtype == torch.int32 and maps.dtype == torch.int32
+        assert seg_n.numel() == n_seg and maps.numel() == n_q
+        assert skip is not None or compact
+        if skip is not None:
+            skip = skip.contiguous()
+            assert skip.dtype == torch.int32 and tuple(skip.shape) == (n_q, 2)
+        if compact:                                      # a map outside the segments would index seg_n out of bounds on the device
+            assert bool(((maps >= 0) & (maps < n_seg)).all()), "compact rows: every query names its segment"
+        idx = torch.full((n_q, int(n_best)), -2, dtype=torch.int32, device=scores.device)
+        sc = torch.full((n_q, int(n_best)), -1.0, dtype=torch.float64, device=scores.device)
+        cnt = torch.full((n_q,), -1, dtype=torch.int32, device=scores.device)
+        fn = self._lib.flvis_hip_lc_select_maps_skip_compact if compact else self._lib.flvis_hip_lc_select_maps_skip
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                       C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, n_q, _ptr(scores), n_seg, seg_len, _ptr(seg_n.contiguous()), _ptr(maps.contiguous()), _ptr(skip), int(n_best),
+                       float(min_score), _ptr(idx), _ptr(sc), _ptr(cnt)), "lc_select_maps_skip")
+        return idx, sc, cnt
+
     def lc_keyframe_landmarks(self, img0, img1, cam_type, kps, desc, count, P0=None, P1=None, K4=None, in_place=False):
         """flvis_hip_lc_keyframe_landmarks (vo_loopclosing.cpp:255-372): kps float32 [n,cap,6], desc uint8 [n,cap,32], count int32 [n] as
         orb_detect_and_compute returns them; img0 uint8 [n,h,w]; img1 uint8 (stereo, cam_type 0) or int16/uint16 Z16 (depth, cam_type 2).
@@ -746,9 +772,38 @@ class FlvisLcMerge(C.Structure):
 def links_from_fix(fix, stream, kf):
     """The links a localize_in result yields when its query frame is also stored as keyframe `kf` of sequence `stream`: one per accepted
     candidate, from (candidate's sequence, candidate's keyframe) to (stream, kf) with the candidate's PnP pose.  -> list of dicts
-    (seq_from, kf_from, seq_to, kf_to, pose) for LoopCloser.merge."""
+    (seq_from, kf_from, seq_to, kf_to, pose) for LoopCloser.merge.  (C callers have flvis_lc_links_from_fix.)"""
     return [dict(seq_from=int(c["seq"]), kf_from=int(c["kf"]), seq_to=int(stream), kf_to=int(kf), pose=[float(x) for x in c["pose"]])
             for c in fix["candidates"] if c["accepted"]]
+
+
+class FlvisLcLinkQuery(C.Structure):
+    """flvis_lc_link_query of include/flvis_hip.h: a stored keyframe as the query of flvis_loop_closer_link."""
+    _fields_ = [("stream", C.c_int), ("map", C.c_int), ("kf", C.c_int64), ("own_gap", C.c_int64)]
+
+
+def _link_dict(l):
+    return dict(seq_from=int(l.seq_from), kf_from=int(l.kf_from), seq_to=int(l.seq_to), kf_to=int(l.kf_to), pose=[float(x) for x in l.pose7])
+
+
+def _link_struct(l):
+    return l if isinstance(l, FlvisLcLink) else FlvisLcLink(int(l["seq_from"]), int(l["seq_to"]), int(l["kf_from"]), int(l["kf_to"]),
+                                                             (C.c_double * 7)(*[float(x) for x in l["pose"]]))
+
+
+def links_reverse(links):
+    """flvis_lc_link_reverse on each link (dicts as links_from_fix makes them, or FlvisLcLink): the ends swapped and the pose inverted --
+    what LoopCloser.merge needs for links whose `from` sequence comes after their `to` sequence in the group.  -> list of dicts.  Host-only."""
+    lib = load_library()
+    lib.flvis_lc_link_reverse.argtypes = [C.POINTER(FlvisLcLink), C.POINTER(FlvisLcLink)]
+    out = []
+    for l in links:
+        a, b = _link_struct(l), FlvisLcLink()
+        rc = lib.flvis_lc_link_reverse(C.byref(a), C.byref(b))
+        if rc != FLVIS_OK:
+            raise FlvisError("flvis_lc_link_reverse failed (%d): a pose that is not finite, or a zero quaternion" % rc)
+        out.append(_link_dict(b))
+    return out
 
 
 def load_lc_params(yaml_path):
@@ -987,6 +1042,28 @@ class LoopCloser:
                          "loop_closer_localize_in_host")
         return self._fixes_in(fix[:n])
 
+    def link(self, queries, n_best=4):
+        """flvis_loop_closer_link: localize_in with STORED keyframes as the queries.  queries: FlvisLcLinkQuery, dicts or tuples
+        (stream, map, kf, own_gap) -- keyframe kf of sequence stream (-1: its newest) is looked for in the map of sequence `map`
+        (FLVIS_LC_ALL_MAPS: every map), without what own_gap names of its own sequence (-1 all of it, g >= 0 the keyframes within g of
+        kf).  Any number of queries, a sequence any number of times.  -> (localize_in's dicts, one per query; the links of the accepted
+        candidates in OTHER sequences as LoopCloser.merge takes them)."""
+        qs = []
+        for q in queries:
+            if isinstance(q, dict):
+                q = (q["stream"], q["map"], q.get("kf", -1), q.get("own_gap", -1))
+            qs.append(q if isinstance(q, FlvisLcLinkQuery) else FlvisLcLinkQuery(*[int(v) for v in q]))
+        n = len(qs)
+        arr = (FlvisLcLinkQuery * max(1, n))(*qs)
+        fix = (FlvisLcFixIn * max(1, n))()
+        cap = max(1, n) * FLVIS_LC_FIX_CAND                  # (no call yields more)
+        links = (FlvisLcLink * cap)()
+        cnt = C.c_int(0)
+        self._lib.flvis_loop_closer_link.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlvisLcLinkQuery), C.c_int, C.POINTER(FlvisLcFixIn), C.c_int,
+                                                     C.POINTER(FlvisLcLink), C.POINTER(C.c_int)]
+        self._ctx._check(self._lib.flvis_loop_closer_link(self._h, n, arr, int(n_best), fix, cap, links, C.byref(cnt)), "loop_closer_link")
+        return self._fixes_in(fix[:n]), [_link_dict(l) for l in links[:cnt.value]]
+
     def set_drift(self, stream, T_odom_map):
         """flvis_loop_closer_set_drift: the sequence's T_odom_map from now on (keyframes added afterwards get T_c_w_odom * T_odom_map).
         After a tracker slot was reset: set_drift(s, mul(inv(T_c_odom), localize(...)["T_c_map"])) ties its new odometry frame to the map."""
@@ -1007,8 +1084,7 @@ class LoopCloser:
         seqs = np.ascontiguousarray([s for g in groups for s in g], np.int32)
         arr = (FlvisLcLink * max(1, len(links)))()
         for k, l in enumerate(links):
-            arr[k] = l if isinstance(l, FlvisLcLink) else FlvisLcLink(int(l["seq_from"]), int(l["seq_to"]), int(l["kf_from"]), int(l["kf_to"]),
-                                                                     (C.c_double * 7)(*[float(x) for x in l["pose"]]))
+            arr[k] = _link_struct(l)
         out = (FlvisLcMerge * max(1, len(groups)))()
         drift = np.zeros((max(1, len(seqs)), 7))
         self._lib.flvis_loop_closer_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(FlvisLcLink),

@@ -10,6 +10,8 @@
 //                                                      the n_best best-scoring keyframes, the camera's pose in the map frame; stores nothing
 //   flvis_loop_closer_localize_in    (the project's own) the same against ANOTHER sequence's database, or all of them: the candidates are
 //                                                      ranked across maps (flvis_hip_lc_select_maps), PnP runs with the query's camera
+//   flvis_loop_closer_link           (the project's own) localize_in with a STORED keyframe as the query: its database slot takes the query
+//                                                      slot's place, no feature kernel runs; any number of queries, its own keyframes left out
 //   flvis_loop_closer_merge          (the project's own) several sequences' maps into one: loopClosureOnCovGraphG2ONew on the sequences'
 //                                                      keyframes side by side, tied by links between keyframes of different sequences
 //
@@ -199,6 +201,8 @@ __global__ __launch_bounds__(64) void k_lcc_select(const int* __restrict__ q_slo
 // k_lcc_select's writes for a localize_in call, whose candidates k_lc_select_maps (loop_kernels.hip) has chosen across maps: sel_idx is
 // the candidate's database slot (sequence * maxkf + keyframe; -1: an empty rank) and goes to the host as it is.  Side a is the candidate's
 // slot, side b the query's, the camera row the QUERY's sequence: solvePnPRansac needs the K of the camera that saw the pixels.
+// lmc: the queries' landmark counts, per query (the call's feature buffers) or, BY_SLOT, per database slot (a link call's stored queries).
+template <bool BY_SLOT>
 __global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ q_slot, const int* __restrict__ q_seq, const int* __restrict__ sel_idx,
                                                         const double* __restrict__ sel_score, const int* __restrict__ sel_cnt, int n_best,
                                                         int empty_slot, const int* __restrict__ lmc, const double* __restrict__ db_T, int* slot_a,
@@ -218,7 +222,7 @@ __global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ 
       out.score[set] = sel_score[set];
     }
   }
-  if (lane == 0) out.ncand[i] = sel_cnt[i], out.nlm[i] = lmc[i];
+  if (lane == 0) out.ncand[i] = sel_cnt[i], out.nlm[i] = lmc[BY_SLOT ? q_slot[i] : i];
 }
 
 using flvis::LcCam;
@@ -812,20 +816,10 @@ static int lc_localize_check(flvis_loop_closer* lc, int n, const int* h_stream, 
   return FLVIS_OK;
 }
 
-// Relocalisation: where is this frame's camera in the map its sequence has built?  The query goes through a keyframe's steps into its
-// sequence's query slot, is scored against the sequence's whole database, the n_best best keyframes are chosen on the device
-// (k_lcc_select) and each (keyframe, query) pair goes through isLoopClosureKF's check as process runs it -- n * n_best sets, empty where
-// there is no candidate.  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.
-//
-// h_map == nullptr: localize (every query against its own sequence's database: qrows, k_lcc_select).  Otherwise localize_in: query i
-// against the database of sequence h_map[i], or of every sequence (< 0) -- the score rows in mrows, one launch for all (query, map) jobs,
-// the candidates across maps by k_lc_select_maps, then k_lcc_select's writes; h.kf comes back as a slot index, not a keyframe index.
-// The fix of query i is written at fix_base + i * fix_stride (cand_kf: what h.kf holds).
-static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
-                           int n_best, char* fix_base, size_t fix_stride, const char* what) {
+// the buffers of a localize / localize_in / link call beyond what create allocates, grown by the first call that needs them: the pair-check
+// buffers for LCC_NBEST sets per sequence, and (in_maps) localize_in's score rows and selection buffers -- all_maps: rows for all segments
+static int lc_localize_reserve(flvis_loop_closer* lc, bool in_maps, bool all_maps, const char* what) {
   flvis_ctx* ctx = lc->ctx;
-  int rc = FLVIS_OK;
-  hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
   hipError_t e = hipSuccess;
   const int ns_cap = lc->S * LCC_NBEST;
@@ -842,9 +836,7 @@ static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, co
     }
     lc->sets_cap = ns_cap;
   }
-  bool all_maps = false;
-  if (h_map) {
-    for (int i = 0; i < n; i++) all_maps = all_maps || h_map[i] < 0;
+  if (in_maps) {
     const size_t S = (size_t)lc->S, need = (all_maps ? S * S : S) * (size_t)lc->maxkf;
     if (need > (size_t)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, std::string(what) + ": n_streams^2 * max_keyframes is too large");
     if (lc->mrows_cap < need || !lc->sel_cnt) {  // the first call, and the first that searches all maps
@@ -862,6 +854,64 @@ static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, co
       lc->h_in_stage.resize(2 * S);
     }
   }
+  return FLVIS_OK;
+}
+
+// the host's part of a fix: query i of a call with n_best ranks per query from the result block h (cand_kf: what h.kf holds)
+static void lc_fix_fill(const flvis_loop_closer* lc, const LcFixOut& h, int i, int n_best, flvis_lc_fix& f) {
+  memset(&f, 0, sizeof(f));
+  f.n_landmarks = h.nlm[i];
+  f.n_candidates = h.ncand[i];
+  f.best = -1;
+  f.T_c_map7[6] = 1.0;
+  for (int r = 0; r < LCC_NBEST; r++) f.cand_kf[r] = -1, f.cand_pose7[r][6] = 1.0;
+  for (int r = 0; r < f.n_candidates; r++) {
+    const int set = i * n_best + r, m = h.npairs[set];
+    f.cand_kf[r] = h.kf[set];
+    f.cand_score[r] = h.score[set];
+    f.cand_matches[r] = m;
+    if (m < 5) continue;  // "p3d not enough" (:666): no inliers, the identity, as in an event
+    const double* const P = h.pose + 7 * (size_t)set;
+    f.cand_inliers[r] = h.ninl[set];
+    memcpy(f.cand_pose7[r], P, 7 * sizeof(double));
+    f.cand_accepted[r] = lc_pair_accepted(lc->prm, m, h.ninl[set], P) ? 1 : 0;
+    if (f.cand_accepted[r] && (f.best < 0 || f.cand_inliers[r] > f.cand_inliers[f.best])) f.best = r;
+  }
+  if (f.best >= 0) pose_mul(f.cand_pose7[f.best], h.T_kf + 7 * (size_t)(i * n_best + f.best), f.T_c_map7);
+}
+
+// ... and of a localize_in fix: the candidates come back as database slots and are split into (sequence, keyframe)
+static void lc_fix_in_split(const flvis_loop_closer* lc, flvis_lc_fix_in& f) {
+  for (int r = 0; r < LCC_NBEST; r++) {
+    const int64_t g = f.fix.cand_kf[r];
+    f.cand_seq[r] = g < 0 ? -1 : (int)(g / lc->maxkf);
+    if (g >= 0) f.fix.cand_kf[r] = g % lc->maxkf;
+  }
+  f.map = f.fix.best >= 0 ? f.cand_seq[f.fix.best] : -1;
+  f.reserved = 0;
+}
+
+// Relocalisation: where is this frame's camera in the map its sequence has built?  The query goes through a keyframe's steps into its
+// sequence's query slot, is scored against the sequence's whole database, the n_best best keyframes are chosen on the device
+// (k_lcc_select) and each (keyframe, query) pair goes through isLoopClosureKF's check as process runs it -- n * n_best sets, empty where
+// there is no candidate.  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.
+//
+// h_map == nullptr: localize (every query against its own sequence's database: qrows, k_lcc_select).  Otherwise localize_in: query i
+// against the database of sequence h_map[i], or of every sequence (< 0) -- the score rows in mrows, one launch for all (query, map) jobs,
+// the candidates across maps by k_lc_select_maps, then k_lcc_select's writes; h.kf comes back as a slot index, not a keyframe index.
+// The fix of query i is written at fix_base + i * fix_stride (cand_kf: what h.kf holds).
+static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
+                           int n_best, char* fix_base, size_t fix_stride, const char* what) {
+  flvis_ctx* ctx = lc->ctx;
+  int rc = FLVIS_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  const int ns_cap = lc->S * LCC_NBEST;
+  bool all_maps = false;
+  for (int i = 0; h_map && i < n; i++) all_maps = all_maps || h_map[i] < 0;
+  rc = lc_localize_reserve(lc, h_map != nullptr, all_maps, what);
+  if (rc != FLVIS_OK) return rc;
   // one upload: identity poses for k_lcc_store, the queries' slots, their sequences (= camera rows), the sequences' keyframe counts
   double* const T = reinterpret_cast<double*>(lc->h_stage.data());
   int* const hq = reinterpret_cast<int*>(lc->h_stage.data() + 7 * sizeof(double) * (size_t)n);
@@ -922,14 +972,14 @@ static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, co
       rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
                                        lc->mrows);
     if (rc == FLVIS_OK)
-      rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, lc->S, lc->maxkf, lc->in_stage + n, lc->in_stage, !all_maps, n_best, lc->prm.minScore,
+      rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, lc->S, lc->maxkf, lc->in_stage + n, lc->in_stage, nullptr, !all_maps, n_best, lc->prm.minScore,
                                      lc->sel_idx, lc->sel_score, lc->sel_cnt);
     if (rc != FLVIS_OK) {
       hipStreamSynchronize(st);
       return rc;
     }
-    k_lcc_select_sets<<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->lmc, lc->db_T, slot_a,
-                                        slot_b, cam_of, out);
+    k_lcc_select_sets<false><<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->lmc, lc->db_T,
+                                               slot_a, slot_b, cam_of, out);
   }
   std::vector<uint64_t> seeds((size_t)ns);
   for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(h_stream[i / n_best] + 1) << 32) + (uint64_t)(i % n_best + 1);  // (stream + 1) << 32 | rank + 1
@@ -942,28 +992,7 @@ static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, co
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return ctx->hip_fail(e, what);
   const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)lc->S);
-  for (int i = 0; i < n; i++) {
-    flvis_lc_fix& f = *reinterpret_cast<flvis_lc_fix*>(fix_base + fix_stride * (size_t)i);
-    memset(&f, 0, sizeof(f));
-    f.n_landmarks = h.nlm[i];
-    f.n_candidates = h.ncand[i];
-    f.best = -1;
-    f.T_c_map7[6] = 1.0;
-    for (int r = 0; r < LCC_NBEST; r++) f.cand_kf[r] = -1, f.cand_pose7[r][6] = 1.0;
-    for (int r = 0; r < f.n_candidates; r++) {
-      const int set = i * n_best + r, m = h.npairs[set];
-      f.cand_kf[r] = h.kf[set];
-      f.cand_score[r] = h.score[set];
-      f.cand_matches[r] = m;
-      if (m < 5) continue;  // "p3d not enough" (:666): no inliers, the identity, as in an event
-      const double* const P = h.pose + 7 * (size_t)set;
-      f.cand_inliers[r] = h.ninl[set];
-      memcpy(f.cand_pose7[r], P, 7 * sizeof(double));
-      f.cand_accepted[r] = lc_pair_accepted(lc->prm, m, h.ninl[set], P) ? 1 : 0;
-      if (f.cand_accepted[r] && (f.best < 0 || f.cand_inliers[r] > f.cand_inliers[f.best])) f.best = r;
-    }
-    if (f.best >= 0) pose_mul(f.cand_pose7[f.best], h.T_kf + 7 * (size_t)(i * n_best + f.best), f.T_c_map7);
-  }
+  for (int i = 0; i < n; i++) lc_fix_fill(lc, h, i, n_best, *reinterpret_cast<flvis_lc_fix*>(fix_base + fix_stride * (size_t)i));
   return FLVIS_OK;
 }
 
@@ -1019,16 +1048,7 @@ int flvis_loop_closer_localize_in(flvis_loop_closer* lc, int n, const int* h_str
   if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_in: bad args");
   rc = lc_localize_run(lc, n, h_stream, h_map, d_img0, d_img1, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix_in), what);
   if (rc != FLVIS_OK) return rc;
-  for (int i = 0; i < n; i++) {
-    flvis_lc_fix_in& f = h_fix[i];
-    for (int r = 0; r < LCC_NBEST; r++) {
-      const int64_t g = f.fix.cand_kf[r];
-      f.cand_seq[r] = g < 0 ? -1 : (int)(g / lc->maxkf);
-      if (g >= 0) f.fix.cand_kf[r] = g % lc->maxkf;
-    }
-    f.map = f.fix.best >= 0 ? f.cand_seq[f.fix.best] : -1;
-    f.reserved = 0;
-  }
+  for (int i = 0; i < n; i++) lc_fix_in_split(lc, h_fix[i]);
   return FLVIS_OK;
 }
 
@@ -1047,6 +1067,150 @@ int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* 
   rc = flvis_loop_closer_localize_in(lc, n, h_stream, h_map, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
   if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
   return rc;
+}
+
+// One pass of a link call: n <= n_streams queries (kf resolved), localize_in's run from the score jobs on with the query keyframe's own
+// database slot where localize_in has the sequence's query slot, and k_lc_select_maps' excluded range.  all_maps: the call's row layout.
+static int lc_link_pass(flvis_loop_closer* lc, int n, const flvis_lc_link_query* q, bool all_maps, int n_best, flvis_lc_fix_in* h_fix,
+                        const char* what) {
+  flvis_ctx* ctx = lc->ctx;
+  hipStream_t st = ctx->stream;
+  const int S = lc->S, maxkf = lc->maxkf, ns = n * n_best, ns_cap = S * LCC_NBEST;
+  // two uploads: the queries' slots, their sequences (= camera rows) and excluded ranges; the searched maps and the sequences' counts
+  int* const hq = reinterpret_cast<int*>(lc->h_stage.data());
+  int* const hm = lc->h_in_stage.data();
+  const size_t stride = (size_t)(all_maps ? S : 1) * maxkf;
+  std::vector<int> jobs;
+  for (int m = 0; m < S; m++) hm[n + m] = lc->seq[m].n;
+  for (int i = 0; i < n; i++) {
+    const int s = q[i].stream, kf = (int)q[i].kf, nk = lc->seq[s].n;
+    const int g = (int)std::min<int64_t>(q[i].own_gap, maxkf);
+    hq[i] = s * maxkf + kf, hq[n + i] = s;
+    hq[2 * n + 2 * i] = s * maxkf + (g < 0 ? 0 : std::max(0, kf - g));
+    hq[2 * n + 2 * i + 1] = g < 0 ? (s + 1) * maxkf : s * maxkf + std::min(nk, kf + g + 1);
+    hm[i] = q[i].map < 0 ? -1 : q[i].map;
+    for (int m = q[i].map < 0 ? 0 : q[i].map; m < (q[i].map < 0 ? S : q[i].map + 1); m++)
+      if (lc->seq[m].n > 0 && !(m == s && g < 0))  // (the own segment wholly excluded: its part of the row is never written, and never read)
+        jobs.insert(jobs.end(), {hq[i], m * maxkf, lc->seq[m].n, (int)(stride * i + (all_maps ? (size_t)m * maxkf : 0))});
+  }
+  const int* const d_q = reinterpret_cast<const int*>(lc->stage);
+  hipError_t e = hipMemcpyAsync(lc->stage, hq, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(lc->in_stage, hm, sizeof(int) * (size_t)(n + S), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    hipStreamSynchronize(st);  // (h_stage is reused by the next call)
+    return ctx->hip_fail(e, what);
+  }
+  int rc = FLVIS_OK;
+  const int n_jobs = (int)(jobs.size() / 4);
+  for (int j0 = 0; j0 < n_jobs && rc == FLVIS_OK; j0 += 65535)
+    rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
+                                     lc->mrows);
+  if (rc == FLVIS_OK)
+    rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, S, maxkf, lc->in_stage + n, lc->in_stage, d_q + 2 * n, !all_maps, n_best, lc->prm.minScore,
+                                   lc->sel_idx, lc->sel_score, lc->sel_cnt);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
+  const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)S);
+  k_lcc_select_sets<true><<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->db_lmc, lc->db_T,
+                                            slot_a, slot_b, cam_of, out);
+  std::vector<uint64_t> seeds((size_t)ns);
+  for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(q[i / n_best].stream + 1) << 32) + (uint64_t)(i % n_best + 1);  // localize's
+  rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  e = hipMemcpyAsync(lc->h_fix_out.data(), lc->fix_out, lc->h_fix_out.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)S);
+  for (int i = 0; i < n; i++) {
+    lc_fix_fill(lc, h, i, n_best, h_fix[i].fix);
+    lc_fix_in_split(lc, h_fix[i]);
+  }
+  return FLVIS_OK;
+}
+
+int flvis_lc_links_from_fix(const flvis_lc_fix_in* fix, int stream, int64_t kf, int cap, flvis_lc_link* out) {
+  if (!fix || cap < 0 || (cap > 0 && !out)) return -1;
+  int cnt = 0;
+  for (int r = 0; r < fix->fix.n_candidates && r < LCC_NBEST; r++) {
+    if (!fix->fix.cand_accepted[r]) continue;
+    if (cnt < cap) {
+      flvis_lc_link& l = out[cnt];
+      l.seq_from = fix->cand_seq[r], l.seq_to = stream, l.kf_from = fix->fix.cand_kf[r], l.kf_to = kf;
+      memcpy(l.pose7, fix->fix.cand_pose7[r], sizeof(l.pose7));
+    }
+    cnt++;
+  }
+  return cnt;
+}
+
+int flvis_lc_link_reverse(const flvis_lc_link* in, flvis_lc_link* out) {
+  if (!in || !out) return FLVIS_ERR_INVALID_ARG;
+  double n2 = 0.0;
+  for (int k = 0; k < 7; k++) {
+    if (!std::isfinite(in->pose7[k])) return FLVIS_ERR_INVALID_ARG;
+    if (k >= 3) n2 += in->pose7[k] * in->pose7[k];
+  }
+  const double nq = std::sqrt(n2);
+  if (!(nq > 0.0) || !std::isfinite(nq)) return FLVIS_ERR_INVALID_ARG;
+  // inv(q, t) = (conj(q), -R(conj(q)) t), as the device's iso_inv
+  const double qi[4] = {-in->pose7[3] / nq, -in->pose7[4] / nq, -in->pose7[5] / nq, in->pose7[6] / nq};
+  const double mt[3] = {-in->pose7[0], -in->pose7[1], -in->pose7[2]};
+  flvis_lc_link o;
+  o.seq_from = in->seq_to, o.seq_to = in->seq_from, o.kf_from = in->kf_to, o.kf_to = in->kf_from;
+  q_rot(qi, mt, o.pose7);
+  memcpy(o.pose7 + 3, qi, sizeof(qi));
+  *out = o;
+  return FLVIS_OK;
+}
+
+// Links and loops from stored keyframes: the arguments are checked before anything is queued, then the queries run in passes of n_streams
+// (what the buffers are laid out for); the links are made on the host from the fixes.
+int flvis_loop_closer_link(flvis_loop_closer* lc, int n, const flvis_lc_link_query* h_q, int n_best, flvis_lc_fix_in* h_fix, int link_cap,
+                           flvis_lc_link* h_links, int* n_links) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* const what = "loop_closer_link";
+  if (n <= 0 || !h_q || !h_fix || !n_links || link_cap < 0 || (link_cap > 0 && !h_links))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: bad args");
+  if (n_best < 1 || n_best > LCC_NBEST) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: n_best must be 1 .. " + std::to_string(LCC_NBEST));
+  std::vector<flvis_lc_link_query> q(h_q, h_q + n);
+  bool all_maps = false;
+  for (int i = 0; i < n; i++) {
+    if (q[i].stream < 0 || q[i].stream >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: no such sequence");
+    if (q[i].map < FLVIS_LC_ALL_MAPS || q[i].map >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: no such map");
+    const int nk = lc->seq[q[i].stream].n;
+    if (q[i].kf < -1 || q[i].kf >= nk || nk == 0)  // (-1 on an empty sequence names no keyframe: its slot was never written)
+      return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: no such keyframe");
+    if (q[i].own_gap < -1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_link: own_gap must be -1 or >= 0");
+    if (q[i].kf < 0) q[i].kf = nk - 1;
+    all_maps = all_maps || q[i].map < 0;
+  }
+  hipSetDevice(ctx->device);
+  int rc = lc_localize_reserve(lc, true, all_maps, what);
+  if (rc != FLVIS_OK) return rc;
+  for (int i0 = 0; i0 < n; i0 += lc->S) {
+    rc = lc_link_pass(lc, std::min(lc->S, n - i0), q.data() + i0, all_maps, n_best, h_fix + i0, what);
+    if (rc != FLVIS_OK) return rc;
+  }
+  int cnt = 0;
+  for (int i = 0; i < n; i++)
+    for (int r = 0; r < h_fix[i].fix.n_candidates; r++) {
+      if (!h_fix[i].fix.cand_accepted[r] || h_fix[i].cand_seq[r] == q[i].stream) continue;  // (its own sequence's: a loop, not a link)
+      if (cnt < link_cap) {
+        flvis_lc_link& l = h_links[cnt];
+        l.seq_from = h_fix[i].cand_seq[r], l.seq_to = q[i].stream, l.kf_from = h_fix[i].fix.cand_kf[r], l.kf_to = q[i].kf;
+        memcpy(l.pose7, h_fix[i].fix.cand_pose7[r], sizeof(l.pose7));
+      }
+      cnt++;
+    }
+  *n_links = cnt;
+  return FLVIS_OK;
 }
 
 int flvis_loop_closer_set_drift(flvis_loop_closer* lc, int stream, const double* h_T_odom_map7) {

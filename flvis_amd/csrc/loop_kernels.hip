@@ -240,13 +240,24 @@ constexpr int LSM_T = 1024, LSM_W = LSM_T / 64;
 __device__ inline bool lsm_before(double a_sc, int a_g, double b_sc, int b_g) {  // a comes before b in the order (INT_MAX: no entry)
   return a_g != INT_MAX && (b_g == INT_MAX || a_sc > b_sc || (a_sc == b_sc && a_g < b_g));
 }
+// SKIP: the global indices skip[2q] <= g < skip[2q + 1] are no candidates of query q, whatever the row holds there (it is not read): a chunk
+// that lies wholly in the range goes the way of a chunk beyond its segment's count, on one wave-uniform compare; lo >= hi excludes nothing.
+// The range table comes as the LAST argument and, without SKIP, as an empty struct: the arguments before it lie where they lay before it
+// came, and that instantiation is the kernel as it was.
+struct LsmNoSkip {};
+struct LsmSkip {
+  const int* range;  // [n_q][2]
+};
+template <bool SKIP, class Skip>
 __global__ __launch_bounds__(LSM_T) void k_lc_select_maps(const double* __restrict__ scores, int n_seg, int seg_len, const int* __restrict__ seg_n,
                                                           const int* __restrict__ map, int compact, int n_best, double min_score,
-                                                          int* __restrict__ idx, double* __restrict__ score, int* __restrict__ count) {
+                                                          int* __restrict__ idx, double* __restrict__ score, int* __restrict__ count, Skip skip) {
   __shared__ double s_sc[LSM_W];
   __shared__ int s_g[LSM_W];
   const int q = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = map[q];
+  int lo = 0, hi = 0;
+  if constexpr (SKIP) lo = skip.range[2 * q], hi = skip.range[2 * q + 1];
   const int s0 = m < 0 ? 0 : m, ns = m < 0 ? n_seg : (m < n_seg ? 1 : 0);  // the segments searched: s0 .. s0 + ns - 1 (no such segment: none)
   const int cps = (seg_len + 63) >> 6;                   // chunks per segment
   const double* const row = scores + (size_t)q * (compact ? (size_t)seg_len : (size_t)n_seg * seg_len);
@@ -260,7 +271,13 @@ __global__ __launch_bounds__(LSM_T) void k_lc_select_maps(const double* __restri
       for (int item = wv; item < ns * cps; item += LSM_W) {
         const int s = s0 + item / cps, j = (item % cps) * 64 + lane;
         const int n = min(seg_n[s], seg_len);
+        if constexpr (SKIP) {
+          const int g0 = s * seg_len + (item % cps) * 64;  // the chunk's first index, and the end of what it holds of its segment
+          if (g0 >= lo && min(g0 + 64, (s + 1) * seg_len) <= hi) continue;
+        }
         if (j >= n) continue;
+        if constexpr (SKIP)
+          if (s * seg_len + j >= lo && s * seg_len + j < hi) continue;  // (in front of the load: what lies there is not read)
         const double sc = row[(compact ? (size_t)0 : (size_t)s * seg_len) + j];
         const int g = s * seg_len + j;
         if (!(sc > 0.0 && sc >= min_score)) continue;
@@ -972,7 +989,21 @@ int flvis_hip_bow_score_jobs_at(flvis_ctx* ctx, int n_jobs, const int* h_jobs4, 
 int flvis_hip_lc_select_maps(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
                              int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
   CHECK_CTX(ctx);
-  return flvis::lc_select_maps_dev(ctx, n_q, d_scores, n_seg, seg_len, d_seg_n, d_map, false, n_best, min_score, d_idx, d_score, d_count);
+  return flvis::lc_select_maps_dev(ctx, n_q, d_scores, n_seg, seg_len, d_seg_n, d_map, nullptr, false, n_best, min_score, d_idx, d_score, d_count);
+}
+
+int flvis_hip_lc_select_maps_skip(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
+                                  const int* d_skip, int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
+  CHECK_CTX(ctx);
+  if (!d_skip) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_select_maps_skip: bad args");
+  return flvis::lc_select_maps_dev(ctx, n_q, d_scores, n_seg, seg_len, d_seg_n, d_map, d_skip, false, n_best, min_score, d_idx, d_score, d_count);
+}
+
+int flvis_hip_lc_select_maps_skip_compact(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n,
+                                          const int* d_map, const int* d_skip, int n_best, double min_score, int* d_idx, double* d_score,
+                                          int* d_count) {
+  CHECK_CTX(ctx);
+  return flvis::lc_select_maps_dev(ctx, n_q, d_scores, n_seg, seg_len, d_seg_n, d_map, d_skip, true, n_best, min_score, d_idx, d_score, d_count);
 }
 
 // isLoopClosureKF's geometric check (vo_loopclosing.cpp:660-686) for n_sets candidate pairs: solvePnPRansac on the matched
@@ -1268,15 +1299,19 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
   return FLVIS_OK;
 }
 
-int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map, bool compact,
-                       int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
+int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
+                       const int* d_skip, bool compact, int n_best, double min_score, int* d_idx, double* d_score, int* d_count) {
   if (n_q <= 0 || !d_scores || n_seg <= 0 || seg_len <= 0 || !d_seg_n || !d_map || n_best < 1 || n_best > FLVIS_LC_FIX_CAND || !d_idx ||
       !d_score || !d_count)
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_select_maps: bad args");
   if ((long long)n_seg * seg_len > (long long)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_select_maps: n_seg * seg_len is too large");
   hipSetDevice(ctx->device);
-  k_lc_select_maps<<<n_q, LSM_T, 0, ctx->stream>>>(d_scores, n_seg, seg_len, d_seg_n, d_map, compact ? 1 : 0, n_best, min_score, d_idx, d_score,
-                                                    d_count);
+  if (d_skip)
+    k_lc_select_maps<true, LsmSkip><<<n_q, LSM_T, 0, ctx->stream>>>(d_scores, n_seg, seg_len, d_seg_n, d_map, compact ? 1 : 0, n_best, min_score,
+                                                                     d_idx, d_score, d_count, LsmSkip{d_skip});
+  else
+    k_lc_select_maps<false, LsmNoSkip><<<n_q, LSM_T, 0, ctx->stream>>>(d_scores, n_seg, seg_len, d_seg_n, d_map, compact ? 1 : 0, n_best, min_score,
+                                                                        d_idx, d_score, d_count, LsmNoSkip{});
   CHECK_LAUNCH(ctx, "lc_select_maps");
   return FLVIS_OK;
 }

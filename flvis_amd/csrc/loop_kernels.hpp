@@ -25,9 +25,10 @@ int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const
                    const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
                    const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
 // flvis_hip_lc_select_maps, and with compact its form for rows that hold segment d_map[q] alone ([n_q][seg_len], every d_map[q] >= 0): the
-// loop closer's layout for a call in which no query searches all maps
-int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map, bool compact,
-                       int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
+// loop closer's layout for a call in which no query searches all maps.  d_skip: flvis_hip_lc_select_maps_skip's excluded ranges [n_q][2] in
+// global indices (both row forms), or nullptr: none, the kernel without the range test
+int lc_select_maps_dev(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
+                       const int* d_skip, bool compact, int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
 
 // flvis_loop_closer_merge's two kernels.  A sequence of a group, as the apply kernel sees it: its keyframes are database slots db_base ..
 // db_base + n - 1 and rows v_base .. v_base + n - 1 of the batch of virtual sequences; keyframes first .. v_s are vertices of the joint graph.

@@ -260,6 +260,19 @@ int flvis_hip_bow_score_jobs_at(flvis_ctx* ctx, int n_jobs, const int* h_jobs4, 
  * an empty rank; d_score: the entry's score, 0 there; d_count [n_q]: the ranks filled.  n_seg * seg_len < 2^31. */
 int flvis_hip_lc_select_maps(flvis_ctx* ctx, int n_q, const double* d_scores /* [n_q][n_seg * seg_len] */, int n_seg, int seg_len,
                              const int* d_seg_n, const int* d_map, int n_best, double min_score, int* d_idx, double* d_score, int* d_count);
+/* flvis_hip_lc_select_maps with an excluded range per query, the candidate choice of flvis_loop_closer_link: d_skip [n_q][2] = (lo, hi), and
+ * the global indices lo <= s * seg_len + j < hi are never candidates of query q, whatever bits the row holds there (NaN, stale scores,
+ * memory never written: those entries are not read).  lo >= hi excludes nothing, and the result is then flvis_hip_lc_select_maps' bit for
+ * bit.  Order, predicate, tie rule, empty ranks and counts are that call's. */
+int flvis_hip_lc_select_maps_skip(flvis_ctx* ctx, int n_q, const double* d_scores /* [n_q][n_seg * seg_len] */, int n_seg, int seg_len,
+                                  const int* d_seg_n, const int* d_map, const int* d_skip /* [n_q][2] */, int n_best, double min_score,
+                                  int* d_idx, double* d_score, int* d_count);
+/* ... on the closer's compact rows, the layout of a call in which no query searches all maps: d_scores [n_q][seg_len] holds segment d_map[q]
+ * alone (every d_map[q] in 0 .. n_seg - 1; the caller sees to that).  Indices reported, and d_skip, are global as above.  d_skip may be NULL: no
+ * range. */
+int flvis_hip_lc_select_maps_skip_compact(flvis_ctx* ctx, int n_q, const double* d_scores /* [n_q][seg_len] */, int n_seg, int seg_len,
+                                          const int* d_seg_n, const int* d_map, const int* d_skip, int n_best, double min_score, int* d_idx,
+                                          double* d_score, int* d_count);
 /* isLoopCandidate (vo_loopclosing.cpp:520-590) on the newest keyframe's row h_row[i] = sim_matrix[i][g_size-1] (host control
  * logic, as in the reference's pgoProcess thread).  Returns 1 and *kf_prev_idx when there is a candidate, 0 when not. */
 int flvis_loop_candidate(int g_size, const double* h_row, const uint8_t* h_present, int lcKFDist, int lcKFMaxDist, int lcNKFClosest,
@@ -882,6 +895,45 @@ typedef struct flvis_lc_merge {
 int flvis_loop_closer_merge(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr /* [n_groups + 1] */, const int* h_seq,
                             int n_links, const flvis_lc_link* h_links, int iterations /* 100: the reference's */,
                             flvis_lc_merge* h_out /* [n_groups] */, double* h_drift7 /* [h_group_ptr[n_groups]][7], may be NULL */);
+/* Links and loops from STORED keyframes: flvis_loop_closer_localize_in with a keyframe of the database as the query instead of images.  (The
+ * project's own.)
+ * Query: keyframe kf of sequence `stream` (-1: its newest).  Its own database slot is the query: no image, no feature kernel, nothing is
+ * stored.  n >= 1 with no upper limit, and a sequence may appear any number of times (several of its keyframes, or one keyframe against
+ * several maps).  A keyframe that was added and not yet processed is a valid query and stays pending.
+ * Candidates: localize_in's rule over the searched map(s) -- `map`, or FLVIS_LC_ALL_MAPS -- minus what own_gap leaves out of the query's OWN
+ * sequence: -1 all of it (with FLVIS_LC_ALL_MAPS: "all other maps"; with map == stream nothing is searched and n_candidates = 0, not an
+ * error); g >= 0 its keyframes kf - g .. kf + g (0: only the query itself).  Keyframes of other sequences are never left out.
+ * Pair check, acceptance, best, T_c_map7, map, cand_seq: localize_in's, with side a the candidate's slot, side b the query keyframe's slot,
+ * the K of the QUERY's sequence and the PnP seeds (stream + 1) << 32 | rank + 1.  So for a keyframe that was stored from images I, a query
+ * with map = m and own_gap = -1 returns bit for bit the fix that localize_in(stream, m, I) returns on the same closer.  T_c_map7 uses the
+ * candidate's T_c_w as the database holds it at the time of the call (after merges and pose-graph runs).
+ * Links: for every query in order and every accepted candidate r in rank order with cand_seq[r] != stream, the link {seq_from = cand_seq[r],
+ * kf_from = cand_kf[r], seq_to = stream, kf_to = kf, pose7 = cand_pose7[r]} -- flvis_lc_links_from_fix's, ready for flvis_loop_closer_merge.
+ * *n_links is the full count, at most link_cap are written (h_links may be NULL when link_cap = 0).  Accepted candidates in the query's own
+ * sequence are loops, not links: they are in the fix only, and the sequence's loop list is not touched.
+ * Any n: the queries run in passes of n_streams; a query's result does not depend on what else the call holds or on the call's order.
+ * No side effect a caller can observe on any sequence, as in localize; the query slots of localize are not used.
+ * Score rows: localize_in's buffer, allocated or grown as there; when that fails the call returns FLVIS_ERR_HIP and the closer stays usable.
+ * FLVIS_ERR_INVALID_ARG before anything is queued, and nothing changes: n_best outside 1 .. FLVIS_LC_FIX_CAND, n <= 0, a stream or map out
+ * of range, kf outside -1 .. count - 1 (so any kf on an empty sequence), own_gap < -1, link_cap < 0, link_cap > 0 with a NULL h_links, a
+ * NULL h_q, h_fix, n_links or closer. */
+typedef struct flvis_lc_link_query {
+  int     stream;  /* the sequence that holds the query keyframe */
+  int     map;     /* the sequence whose database is searched, or FLVIS_LC_ALL_MAPS */
+  int64_t kf;      /* keyframe index in `stream`; -1: its newest */
+  int64_t own_gap; /* what of the query's OWN sequence is left out: -1 all of it; g >= 0 the keyframes j with |j - kf| <= g */
+} flvis_lc_link_query;
+int flvis_loop_closer_link(flvis_loop_closer* lc, int n, const flvis_lc_link_query* h_q, int n_best, flvis_lc_fix_in* h_fix /* [n] */,
+                           int link_cap, flvis_lc_link* h_links, int* n_links);
+/* The links a localize_in (or link) fix yields when its query frame is keyframe kf of sequence `stream`: one per accepted candidate r in rank
+ * order, {cand_seq[r], cand_kf[r]} -> {stream, kf} with cand_pose7[r]; candidates of sequence `stream` itself included (localize_in does
+ * not leave them out).  Returns the count; at most cap are written (out may be NULL when cap = 0).  -1 for a NULL fix, cap < 0, or
+ * cap > 0 with a NULL out.  Host only. */
+int flvis_lc_links_from_fix(const flvis_lc_fix_in* fix, int stream, int64_t kf, int cap, flvis_lc_link* out);
+/* The same link seen from its other end: the sequences and keyframes swapped, pose7 inverted (the quaternion is normalised first) -- what
+ * flvis_loop_closer_merge needs when a link's `from` sequence comes after its `to` sequence in the group's order.  in == out is allowed.
+ * FLVIS_ERR_INVALID_ARG for a NULL argument, a pose that is not finite or a zero quaternion.  Host only. */
+int flvis_lc_link_reverse(const flvis_lc_link* in, flvis_lc_link* out);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,14 @@ n_best = 1, 4 and 8: with every query in its own map (the same kernels as locali
 calls taken in turns; the size of the score rows; a further JSON line.  --localize-in=all: only the all-maps calls at n_best = 8 (a run
 under a profiler then holds nothing else of the new kernels).  max_keyframes sizes the databases and the score rows (default: n_keyframes).
 
-usage: loop_closer_bench.py [--rigs] [--localize] [--localize-in[=all]] [n_streams=64] [n_keyframes=60] [max_keyframes]"""
+--link: after the tour, flvis_loop_closer_link with the NEWEST stored keyframe of every sequence as the query, next to
+flvis_loop_closer_localize_in on the images that keyframe was stored from, at n_best = 1, 4 and 8: into the neighbour's map (sequence s in
+the map of s + 1; link with own_gap = -1) and into all maps (localize_in: all maps, its own included -- it has no exclusion; link: all
+OTHER maps); ms per call, the calls taken in turns; then every keyframe of sequence s against map s + 1 in ONE link call (n_streams *
+n_keyframes queries, n_best = 4): ms per call and per query; a further JSON line.  With a library that has no flvis_loop_closer_link
+(FLVIS_LIB_PATH: the parent commit's) only the localize_in legs run: the same script then gives the parent's figures.
+
+usage: loop_closer_bench.py [--rigs] [--localize] [--localize-in[=all]] [--link] [n_streams=64] [n_keyframes=60] [max_keyframes]"""
 import json
 import os
 import sys
@@ -39,6 +46,7 @@ import _voc as V
 RIGS = "--rigs" in sys.argv[1:]
 LOCALIZE = "--localize" in sys.argv[1:]
 LOCALIZE_IN = [a for a in sys.argv[1:] if a.split("=")[0] == "--localize-in"]
+LINK = "--link" in sys.argv[1:]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(args[0]) if len(args) > 0 else 64
 N = int(args[1]) if len(args) > 1 else 60
@@ -108,7 +116,7 @@ print(json.dumps({
     "mean_loop_gap_m_odometry": float(gap0), "mean_loop_gap_m_after": float(gap1),
     "timing": "host wall clock around calls that return synchronised"}))
 
-if LOCALIZE or LOCALIZE_IN:
+if LOCALIZE or LOCALIZE_IN or LINK:
     tq = 0.5 * (times[N // 2] + times[N // 2 + 1])                    # between two keyframes of the tour
     if RIGS:
         parts = [units[k][0].stereo_frame([trs[s] for s in range(k, S, N_UNITS)], tq, N) for k in range(min(N_UNITS, S))]
@@ -166,4 +174,47 @@ if LOCALIZE_IN:
             if maps is not None and maps[0] == ALL:
                 out["all_maps_found_in_own_map_n_best_%d" % n_best] = int(sum(f["map"] == s for s, f in zip(streams, fix)))
     out["timing"] = "host wall clock around synchronised calls: median (and min, max) of 7 rounds of 3 calls, the legs in turns, each round after a warm-up call"
+    print(json.dumps(out))
+
+if LINK:
+    ALL = flvis_amd.FLVIS_LC_ALL_MAPS
+    has_link = hasattr(flvis_amd.load_library(), "flvis_loop_closer_link")
+    k0, k1 = frames[N - 1]                                             # what the newest keyframe of every sequence was stored from
+    nxt = [(s + 1) % S for s in streams]
+    legs = {"localize_in_next_map": lambda nb: lc.localize_in(streams, nxt, k0, k1, n_best=nb),
+            "localize_in_all_maps": lambda nb: lc.localize_in(streams, [ALL] * S, k0, k1, n_best=nb)}
+    if has_link:
+        legs["link_next_map"] = lambda nb: lc.link([(s, nxt[s], -1, -1) for s in streams], n_best=nb)[0]
+        legs["link_all_other_maps"] = lambda nb: lc.link([(s, ALL, -1, -1) for s in streams], n_best=nb)[0]
+    out = {"n_streams": S, "n_keyframes": N, "max_keyframes": MAXKF, "rig_units": N_UNITS if RIGS else 1, "library_has_link": has_link}
+    for n_best in (1, 4, 8):
+        ms = {k: [] for k in legs}
+        for k, f in legs.items():
+            f(n_best)                                                  # warm-up (the first calls also allocate and grow buffers)
+        for _ in range(7):                                             # the legs in turns: a drift of the clocks hits all alike
+            for k, f in legs.items():
+                ms[k].append(timed(lambda: f(n_best), reps=3)[0])
+        for k, f in legs.items():
+            fix = f(n_best)
+            out["%s_ms_n_best_%d" % (k, n_best)] = float(np.median(ms[k]))
+            out["%s_ms_min_max_n_best_%d" % (k, n_best)] = [float(min(ms[k])), float(max(ms[k]))]
+            out["%s_localised_n_best_%d" % (k, n_best)] = int(sum(f_["best"] >= 0 for f_ in fix))
+            out["%s_accepted_n_best_%d" % (k, n_best)] = int(sum(c["accepted"] for f_ in fix for c in f_["candidates"]))
+        if has_link:                                                   # the same stored frames: link's fix is localize_in's
+            a, b = legs["localize_in_next_map"](n_best), legs["link_next_map"](n_best)
+            out["link_equals_localize_in_n_best_%d" % n_best] = bool(all(
+                x["best"] == y["best"] and [(c["seq"], c["kf"], c["n_inliers"]) for c in x["candidates"]] ==
+                [(c["seq"], c["kf"], c["n_inliers"]) for c in y["candidates"]] for x, y in zip(a, b)))
+    if has_link:
+        whole = [(s, nxt[s], k, -1) for s in streams for k in range(N)]
+        ms = [timed(lambda: lc.link(whole, n_best=4), reps=1)[0] for _ in range(3)]
+        fixes, links = lc.link(whole, n_best=4)
+        out["whole_map_queries"] = len(whole)
+        out["whole_map_ms_n_best_4"] = float(np.median(ms))
+        out["whole_map_ms_min_max_n_best_4"] = [float(min(ms)), float(max(ms))]
+        out["whole_map_us_per_query_n_best_4"] = float(np.median(ms)) * 1e3 / len(whole)
+        out["whole_map_links_n_best_4"] = len(links)
+        out["whole_map_localised_n_best_4"] = int(sum(f_["best"] >= 0 for f_ in fixes))
+    out["timing"] = ("host wall clock around synchronised calls: median (and min, max) of 7 rounds of 3 calls, the legs in turns, each round "
+                     "after a warm-up call; whole map: median of 3 single calls, each after a warm-up call")
     print(json.dumps(out))
