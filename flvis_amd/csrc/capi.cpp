@@ -312,8 +312,7 @@ int flvis_hip_stereo_depth(flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* 
 }
 
 static int gftt_scratch(flvis_ctx* ctx, int w, int h, int n_img, GfttScratch& sc) {
-  int cap = 1;
-  while (cap < (w / 2 + 1) * (h / 2 + 1)) cap <<= 1;  // strict 3x3 local maxima cannot exceed ~w*h/4
+  const int cap = gftt_key_cap(w, h);
   sc.cap = cap;
   sc.maxenc = (unsigned*)ctx->scratch("gftt_max", sizeof(unsigned) * n_img);
   sc.nkeys = (int*)ctx->scratch("gftt_nkeys", sizeof(int) * n_img);
@@ -355,6 +354,8 @@ static int dem_common(flvis_ctx* ctx, const uint8_t* d_img, int w, int h, int n_
   int gftt_num = (int)f_para[3];
   int maxc = mode == 1 ? 2 * gftt_num : gftt_num;
   if (maxc <= 0 || maxc > 4096) return ctx->fail(FLVIS_ERR_CAPACITY, "feature_dem: gftt_num out of range (<=2048)");
+  if (!(f_para[0] <= (double)dem_max_region_features()))
+    return ctx->fail(FLVIS_ERR_CAPACITY, "feature_dem: max_region_feature_num (f_para[0]) must be <= " + std::to_string(dem_max_region_features()));
   GfttScratch sc;
   int rc = gftt_scratch(ctx, w, h, n_img, sc);
   if (rc) return rc;

@@ -911,7 +911,13 @@ __global__ __launch_bounds__(SORT_T) void k_gftt_pick(unsigned long long* __rest
 // Reproduces feature_dem.cpp including calHarrisR's quirks, integer cv::Point rounding in redetect, the cross-shaped
 // spacing test and the "push then check size" region cap.  std::sort ties are resolved stably (GFTT rank order).
 constexpr int DEM_MAXC = 4096;   // max GFTT corners per call (2*gftt_num; KITTI.yaml asks for 2 x 2000); candidate arrays in dynamic LDS
-constexpr int DEM_MAXR = 192;    // max entries kept per region (existing + new)
+// Entries of a region held in LDS (existing + new).  New ones never exceed max_region_feature_num, which the callers keep <= DEM_MAXR
+// (dem_max_region_features).  Existing ones are the caller's: a region that gets DEM_MAXR of them or more is at or above
+// max_region_feature_num already, so the reference's "push, then check the size" lets it take ONE more point at most -- the first
+// candidate clear of every existing point of the region.  k_feature_dem finds that one against the existing points in global memory
+// (kover below), the reference's answer whatever their number.
+constexpr int DEM_MAXR = 192;
+int dem_max_region_features() { return DEM_MAXR; }
 
 __device__ __forceinline__ float dem_harris(const uint8_t* __restrict__ img, int pitch, float ptx, float pty) {
   int xx = (int)ptx, yy = (int)pty;
@@ -1080,10 +1086,10 @@ __device__ __forceinline__ void k_feature_dem_body(int w, int h, DemParams prm, 
   float* cy = cx + cmax;
   __shared__ int roff[17];
   __shared__ float kx[16][DEM_MAXR], ky[16][DEM_MAXR];
-  __shared__ int kcount[16], knew0[16], ooff[17];
+  __shared__ int kcount[16], knew0[16], ooff[17], kover[16];
   __shared__ int wcnt[DEM_T / 64][16];
   if (tid < 17) roff[tid] = region_off[(size_t)s * 17 + tid];
-  if (tid < 16) kcount[tid] = 0;
+  if (tid < 16) kcount[tid] = 0, kover[tid] = 0;
   __syncthreads();
   {
     const float* const SX = sorted_xy + (size_t)s * corner_cap * 2;
@@ -1129,6 +1135,7 @@ __device__ __forceinline__ void k_feature_dem_body(int w, int h, DemParams prm, 
         int k = kcount[tid];
         for (int v = 0; v < DEM_T / 64; v++) k += wcnt[v][tid];
         kcount[tid] = k < DEM_MAXR ? k : DEM_MAXR;
+        if (k >= DEM_MAXR) kover[tid] = 1;  // (at DEM_MAXR too: no slot is left for the one new point)
       }
       __syncthreads();
     }
@@ -1143,6 +1150,37 @@ __device__ __forceinline__ void k_feature_dem_body(int w, int h, DemParams prm, 
     int kept = kcount[r];
     unsigned count = 0;
     const int j0 = roff[r], j1 = roff[r + 1];
+    if (md == 2 && kover[r]) {
+      // DEM_MAXR existing points or more: the region is full (DEM_MAXR >= max_region_feature_num), the first candidate clear of
+      // ALL its existing points is pushed and the walk ends.  The existing points are read again, the 16 lanes splitting the stream's list.
+      int ne = nexist[s];
+      if (ne > exist_cap) ne = exist_cap;
+      const double* E = exist_xy + (size_t)s * exist_cap * 2;
+      int found = 0;
+      for (int j = j0; j < j1 && !found; j++) {
+        const float px = (float)__float2int_rn(cx[j]), py = (float)__float2int_rn(cy[j]);
+        int bad = 0;
+        for (int i = sub; i < ne; i += 16) {
+          const float ex = (float)E[2 * i], ey = (float)E[2 * i + 1];
+          if (!(ex >= 3 && ex < (w - 3) && ey >= 3 && ey < (h - 3))) continue;
+          if ((int)(4.f * floorf(ey / (float)prm.regionHeight) + ex / (float)prm.regionWidth) != r) continue;
+          if (fabsf(px - ex) <= (float)bd || fabsf(py - ey) <= (float)bd) bad = 1;
+        }
+        bad = (int)((__ballot(bad != 0) >> (lane & 48)) & 0xFFFFull);
+        if (!bad) {
+          if (sub == 0) {
+            kx[r][0] = px;
+            ky[r][0] = py;
+          }
+          found = 1;
+        }
+      }
+      // (the existing entries of kx / ky are not read again: slot 0 is the region's output)
+      if (sub == 0) {
+        knew0[r] = 0;
+        kcount[r] = found;
+      }
+    } else {
     for (int j = j0; j < j1; j++) {
       float px = cx[j], py = cy[j];
       if (md == 2) {  // cv::Point pt = Point2f (rounds), feature_dem.cpp:174
@@ -1175,6 +1213,7 @@ __device__ __forceinline__ void k_feature_dem_body(int w, int h, DemParams prm, 
       }
     }
     if (sub == 0) kcount[r] = kept < DEM_MAXR ? kept : DEM_MAXR;
+    }
   }
   __syncthreads();
   // output: new points, regions in order 0..15, per region in acceptance order

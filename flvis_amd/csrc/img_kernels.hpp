@@ -103,6 +103,14 @@ struct GfttScratch {
   unsigned long long* keys;  // [S][cap]
   int cap;                   // power of two
 };
+// Keys per stream of the GFTT scratch.  A candidate is an interior pixel with e > 0 && !(neighbour > e) -- not a strict maximum: on a
+// plateau of equal positive response (block patterns, saturated patches) every pixel is one, so only the interior (w - 2)(h - 2) bounds
+// their number.  A power of two: sort_keys_global pads to one inside the capacity.
+inline int gftt_key_cap(int w, int h) {
+  int cap = 1;
+  while ((long long)cap < (long long)(w - 2) * (h - 2)) cap <<= 1;
+  return cap;
+}
 
 hipError_t img_kernels_init();
 void launch_equalize_hist(hipStream_t st, ImgSel src, ImgSel dst, int w, int h, int spitch, int dpitch, size_t sstride,
@@ -143,6 +151,7 @@ void launch_corner_response(hipStream_t st, int variant, int rows, ImgSel src, i
 void launch_sqrt_check(hipStream_t st, unsigned first_bits, unsigned n, unsigned long long* mismatches);  // test aid, eig_walk.hip
 // FeatureDEM in two launches: what depends on the corners and the image only (regions, Harris scores, per-region order) -> sorted_xy
 // [S][corner_cap][2], region_off [S][17]; then the part that needs the existing landmarks (fill, greedy spacing, output)
+int dem_max_region_features();  // largest DemParams::max_region_feature_num the FeatureDEM kernels hold (callers refuse more)
 void launch_feature_dem_prep(hipStream_t st, ImgSel src, int w, int h, int pitch, size_t sstride, int S, DemParams prm,
                              const float* corners, const int* ncorners, int corner_cap, const int* active, float* sorted_xy,
                              int* region_off, const KJoin* kj = nullptr);

@@ -631,8 +631,7 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
     }
   }
   // GFTT scratch
-  int cap = 1;
-  while (cap < (w / 2 + 1) * (h / 2 + 1)) cap <<= 1;
+  const int cap = gftt_key_cap(w, h);
   L->gftt.cap = cap;
   ok = ok && ((L->gftt.maxenc = dalloc<unsigned>(L->allocs, S)) != nullptr);
   ok = ok && ((L->gftt.nkeys = dalloc<int>(L->allocs, S)) != nullptr);
