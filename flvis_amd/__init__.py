@@ -398,6 +398,45 @@ class Context:
                                                           _ptr(scores)), "bow_score_jobs_at")
         return scores
 
+    def voxel_cloud(self, p3, count, T_c_w, clouds, leaf=0.08, min_points=1, cap=None, want_npts=True):
+        """flvis_hip_voxel_cloud: p3 float64 [n_rows, pcap, 3] (camera frame), count int32 [n_rows], T_c_w float64 [n_rows, 7], device
+        tensors; clouds: per cloud a list of (first row, row count) ranges.  cap: output rows per cloud (default: every input slot of the
+        largest cloud, so nothing is cut).  -> (xyz [n_clouds] of float32 [k, 3], npts [n_clouds] of int32 [k] or None, n_out int64
+        [n_clouds] the full counts, n_dropped int64 [n_clouds]) as numpy arrays; k = min(n_out, cap)."""
+        import numpy as np
+        import torch
+        assert p3.dtype == torch.float64 and p3.is_cuda and p3.is_contiguous() and p3.dim() == 3 and p3.shape[2] == 3
+        assert count.dtype == torch.int32 and count.is_contiguous() and T_c_w.dtype == torch.float64 and T_c_w.is_contiguous()
+        n_rows, pcap = int(p3.shape[0]), int(p3.shape[1])
+        assert count.numel() == n_rows and tuple(T_c_w.shape) == (n_rows, 7)
+        clouds = [[(int(a), int(b)) for a, b in c] for c in clouds]
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) for c in clouds])]), np.int32)
+        rng = np.ascontiguousarray([r for c in clouds for r in c], np.int32).reshape(-1, 2)
+        if cap is None:
+            cap = max([sum(max(b, 0) for _, b in c) for c in clouds] + [0]) * pcap
+        cap, nc = int(cap), len(clouds)
+        xyz = torch.empty((max(nc, 1), max(cap, 0), 3), dtype=torch.float32, device=p3.device)
+        npts = torch.empty((max(nc, 1), max(cap, 0)), dtype=torch.int32, device=p3.device) if want_npts else None
+        n_out, n_drop = np.zeros(max(nc, 1), np.int64), np.zeros(max(nc, 1), np.int64)
+        fn = self._lib.flvis_hip_voxel_cloud
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                       C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self._check(fn(self._h, _ptr(p3), _ptr(count), _ptr(T_c_w), n_rows, pcap, nc, _P(ptr, C.c_int), _P(rng, C.c_int), float(leaf),
+                       int(min_points), cap, _ptr(xyz), _ptr(npts), _P(n_out, C.c_int64), _P(n_drop, C.c_int64)), "voxel_cloud")
+        k = [int(min(n, cap)) for n in n_out[:nc]]
+        hx = xyz.cpu().numpy()
+        hn = npts.cpu().numpy() if want_npts else None
+        return ([hx[c, :k[c]].copy() for c in range(nc)], [hn[c, :k[c]].copy() for c in range(nc)] if want_npts else None,
+                n_out[:nc].copy(), n_drop[:nc].copy())
+
+    def voxel_cloud_stats(self):
+        """flvis_hip_voxel_cloud_stats: dict(passes_run, passes_skipped, workspace_bytes, input_points) of the context's last call"""
+        import numpy as np
+        st = np.zeros(4, np.int64)
+        self._lib.flvis_hip_voxel_cloud_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self._check(self._lib.flvis_hip_voxel_cloud_stats(self._h, _P(st, C.c_int64)), "voxel_cloud_stats")
+        return dict(passes_run=int(st[0]), passes_skipped=int(st[1]), workspace_bytes=int(st[2]), input_points=int(st[3]))
+
     def lc_select_maps(self, scores, seg_n, maps, n_best, min_score):
         """flvis_hip_lc_select_maps: scores float64 [n_q, n_seg, seg_len], seg_n int32 [n_seg], maps int32 [n_q] (a segment, or -1: all),
         device tensors -> (idx int32 [n_q, n_best] global index seg * seg_len + j or -1, score float64 [n_q, n_best], count int32 [n_q])."""
@@ -527,6 +566,16 @@ class Context:
             res.append(out[o:o + k].copy())
             o += k
         return res, drift.cpu().numpy(), stats.cpu().numpy(), ran
+
+
+def voxel_cloud_info():
+    """flvis_hip_voxel_cloud_info: dict(sort_tile, workgroup, bytes_per_point, bytes_per_row) -- constants of the build, no device needed"""
+    lib = load_library()
+    info = (C.c_int * 4)()
+    lib.flvis_hip_voxel_cloud_info.argtypes = [C.POINTER(C.c_int)]
+    if lib.flvis_hip_voxel_cloud_info(info) != FLVIS_OK:
+        raise FlvisError("voxel_cloud_info failed")
+    return dict(sort_tile=info[0], workgroup=info[1], bytes_per_point=info[2], bytes_per_row=info[3])
 
 
 def loop_candidate(row, present, lcKFDist, lcKFMaxDist, lcNKFClosest, minScore):
@@ -1093,6 +1142,44 @@ class LoopCloser:
                                                            int(iterations), out, _P(drift, C.c_double)), "loop_closer_merge")
         return ([dict(optimised=bool(o.optimised), n_vertices=o.n_vertices, n_edges=o.n_edges, iterations=o.iterations,
                       chi2_before=o.chi2_before, chi2_after=o.chi2_after) for o in out[:len(groups)]], drift[:len(seqs)].copy())
+
+    def map_cloud(self, groups, leaf=0.08, min_points=1, cap=None, host=False):
+        """flvis_loop_closer_map_cloud: the landmarks of every stored keyframe of each group's sequences, in the map frame (the T_c_w the
+        database holds now), one point per voxel of `leaf` metres that holds min_points points or more; leaf = 0: every landmark.  groups:
+        lists of sequences as merge takes them (a single sequence is a group too).  cap: rows per group (default: what the largest
+        group yields, found by a call of its own).  host=True goes through the _host entry.  -> (xyz [n_groups] of float32 [k, 3], npts [n_groups] of int32
+        [k], n_out int64 [n_groups] the full counts, n_dropped int64 [n_groups])."""
+        import numpy as np
+        import torch
+        groups = [[int(s) for s in g] for g in groups]
+        ng = len(groups)
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(g) for g in groups])]), np.int32)
+        seqs = np.ascontiguousarray([s for g in groups for s in g] + [0], np.int32)
+        if cap is None:                                      # a first call for the counts alone: the buffers then fit what comes
+            cap = int(max(list(self.map_cloud(groups, leaf, min_points, cap=0, host=host)[2]) + [0]))
+        cap = int(cap)
+        n_out, n_drop = np.zeros(max(ng, 1), np.int64), np.zeros(max(ng, 1), np.int64)
+        shape = (max(ng, 1), max(cap, 0))
+        args = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int]
+        if host:
+            hx, hn = np.zeros(shape + (3,), np.float32), np.zeros(shape, np.int32)
+            fn = self._lib.flvis_loop_closer_map_cloud_host
+            fn.argtypes = args + [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            rc = fn(self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), float(leaf), int(min_points), cap, _P(hx, C.c_float), _P(hn, C.c_int),
+                    _P(n_out, C.c_int64), _P(n_drop, C.c_int64))
+            self._ctx._check(rc, "loop_closer_map_cloud_host")
+        else:
+            xyz = torch.empty(shape + (3,), dtype=torch.float32, device=self._ctx.device)
+            npts = torch.empty(shape, dtype=torch.int32, device=self._ctx.device)
+            fn = self._lib.flvis_loop_closer_map_cloud
+            fn.argtypes = args + [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            rc = fn(self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), float(leaf), int(min_points), cap, _ptr(xyz), _ptr(npts),
+                    _P(n_out, C.c_int64), _P(n_drop, C.c_int64))
+            self._ctx._check(rc, "loop_closer_map_cloud")
+            kmax = int(min(max(n_out[:ng].max() if ng else 0, 0), cap))
+            hx, hn = xyz[:, :kmax].cpu().numpy(), npts[:, :kmax].cpu().numpy()
+        k = [int(min(n, cap)) for n in n_out[:ng]]
+        return ([hx[g, :k[g]].copy() for g in range(ng)], [hn[g, :k[g]].copy() for g in range(ng)], n_out[:ng].copy(), n_drop[:ng].copy())
 
     def poses(self, stream=0, cap=None):
         import numpy as np

@@ -25,6 +25,7 @@ struct flvis_ctx {
   std::map<std::string, Buf> bufs;  // named scratch buffers, grown on demand (never inside a steady-state loop)
   flvis::Pipeline* pipe = nullptr;
   int voc_nodes = 0, voc_words = 0, voc_depth = 0;  // the DBoW3 vocabulary resident in the `voc_*` scratch buffers (flvis_hip_bow_set_vocabulary)
+  int64_t mc_stats[4] = {0, 0, 0, 0};  // the last flvis_hip_voxel_cloud call: sort passes run / skipped, workspace bytes, input points
   std::string orb_pattern;  // the BRIEF pattern currently resident in the `orb_pattern` scratch buffer (1024 bytes) or empty
 
   // returns a device buffer of at least `bytes` bytes (contents undefined after growth)

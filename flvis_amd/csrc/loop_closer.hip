@@ -1387,6 +1387,78 @@ int flvis_loop_closer_merge(flvis_loop_closer* lc, int n_groups, const int* h_gr
   return FLVIS_OK;
 }
 
+// The maps as voxel clouds (include/flvis_hip.h): one row range per sequence over the landmark and pose databases, then
+// flvis_hip_voxel_cloud.  Reads the database and writes nothing of the closer's.
+static int lc_map_cloud_ranges(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int64_t* h_n_out,
+                               std::vector<int>& range2) {
+  flvis_ctx* ctx = lc->ctx;
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_map_cloud: " + m); };
+  if (!h_group_ptr || !h_seq || !h_n_out || n_groups <= 0) return bad("bad args");
+  if (h_group_ptr[0] != 0) return bad("h_group_ptr must start at 0");
+  std::vector<int> seen((size_t)lc->S, -1);  // the last group that listed the sequence
+  for (int g = 0; g < n_groups; g++) {
+    if (h_group_ptr[g + 1] < h_group_ptr[g]) return bad("h_group_ptr decreases");
+    for (int i = h_group_ptr[g]; i < h_group_ptr[g + 1]; i++) {
+      const int s = h_seq[i];
+      if (s < 0 || s >= lc->S) return bad("sequence out of range");
+      if (seen[s] == g) return bad("sequence " + std::to_string(s) + " is listed twice in group " + std::to_string(g));
+      seen[s] = g;
+      range2.push_back(s * lc->maxkf);
+      range2.push_back(lc->seq[s].n);
+    }
+  }
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_map_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, double leaf, int min_points,
+                                int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  std::vector<int> range2;
+  const int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
+  if (rc != FLVIS_OK) return rc;
+  return flvis_hip_voxel_cloud(lc->ctx, lc->db_lm3, lc->db_lmc, lc->db_T, lc->S * lc->maxkf, LCC_CAP, n_groups, h_group_ptr, range2.data(), leaf,
+                               min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped);
+}
+
+int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, double leaf, int min_points,
+                                     int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  std::vector<int> range2;
+  int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
+  if (rc != FLVIS_OK) return rc;
+  if (!h_xyz && out_cap > 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_map_cloud_host: NULL h_xyz");
+  float* d_xyz = nullptr;
+  int* d_npts = nullptr;
+  if (out_cap > 0) {  // rows and counts of every group in one staging buffer of the context
+    const size_t rows = (size_t)n_groups * (size_t)out_cap;
+    d_xyz = (float*)ctx->scratch("mc_host_rows", rows * (3 * sizeof(float) + sizeof(int)));
+    if (!d_xyz) {
+      (void)hipGetLastError();
+      return ctx->fail(FLVIS_ERR_HIP, "loop_closer_map_cloud_host: device allocation failed");
+    }
+    d_npts = (int*)(d_xyz + 3 * rows);
+  }
+  rc = flvis_hip_voxel_cloud(ctx, lc->db_lm3, lc->db_lmc, lc->db_T, lc->S * lc->maxkf, LCC_CAP, n_groups, h_group_ptr, range2.data(), leaf,
+                             min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr, h_n_out, h_n_dropped);
+  if (rc != FLVIS_OK) return rc;
+  hipError_t e = hipSuccess;
+  bool any = false;
+  for (int g = 0; g < n_groups && e == hipSuccess; g++) {
+    const size_t n = (size_t)std::min<int64_t>(h_n_out[g], out_cap), at = (size_t)g * (size_t)out_cap;
+    if (n == 0) continue;
+    any = true;
+    e = hipMemcpyAsync(h_xyz + 3 * at, d_xyz + 3 * at, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && h_npts) e = hipMemcpyAsync(h_npts + at, d_npts + at, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  if (any || e != hipSuccess) {
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_map_cloud_host");
+  return FLVIS_OK;
+}
+
 int flvis_loop_closer_poses(flvis_loop_closer* lc, int stream, double* h_T_c_w7, int cap, int* n_out) {
   if (!lc) return FLVIS_ERR_INVALID_ARG;
   flvis_ctx* ctx = lc->ctx;

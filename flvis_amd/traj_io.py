@@ -301,3 +301,58 @@ def camera_to_body(positions_w_c, quats_wxyz_w_c, T_imu_cam44):
         pos.append(R @ T_c_i[:3, 3] + p)
         quat.append(rot_to_quat(R @ T_c_i[:3, :3]))
     return np.array(pos), np.array(quat)
+
+
+def write_ply(path, xyz, npts=None):
+    """A point cloud as ASCII PLY: float x y z per vertex and, with npts, an int property `npts` (the points a voxel held).  Coordinates
+    are written with 9 significant digits: a float32 reads back as the same bits.  (A viewer's exchange format, not a map file.)"""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    if npts is not None:
+        npts = np.asarray(npts, np.int64).reshape(-1)
+        if len(npts) != len(xyz):
+            raise ValueError("write_ply: %d points, %d counts" % (len(xyz), len(npts)))
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\ncomment flvis_amd map cloud\nelement vertex %d\n" % len(xyz))
+        f.write("property float x\nproperty float y\nproperty float z\n")
+        if npts is not None:
+            f.write("property int npts\n")
+        f.write("end_header\n")
+        for i, p in enumerate(xyz):
+            row = "%.9g %.9g %.9g" % (p[0], p[1], p[2])
+            f.write(row + (" %d\n" % npts[i] if npts is not None else "\n"))
+
+
+def read_ply(path):
+    """-> (xyz float32 [n, 3], npts int32 [n] or None) of an ASCII PLY whose vertices carry x y z (and optionally npts), as write_ply
+    writes it; other vertex properties are skipped, other elements must follow the vertices."""
+    with open(path) as f:
+        if f.readline().strip() != "ply":
+            raise ValueError("read_ply: %s is not a PLY file" % path)
+        n, props, in_vertex = None, [], False
+        for line in f:
+            w = line.split()
+            if not w or w[0] == "comment":
+                continue
+            if w[0] == "format":
+                if w[1] != "ascii":
+                    raise ValueError("read_ply: only ASCII PLY is read")
+            elif w[0] == "element":
+                in_vertex = w[1] == "vertex"
+                if in_vertex:
+                    n = int(w[2])
+            elif w[0] == "property" and in_vertex:
+                props.append(w[-1])
+            elif w[0] == "end_header":
+                break
+        if n is None or not all(k in props for k in "xyz"):
+            raise ValueError("read_ply: no vertex element with x y z")
+        col = [props.index(k) for k in "xyz"]
+        xyz, npts = np.zeros((n, 3), np.float32), np.zeros(n, np.int32) if "npts" in props else None
+        for i in range(n):
+            w = f.readline().split()
+            if len(w) < len(props):
+                raise ValueError("read_ply: vertex %d is short" % i)
+            xyz[i] = [np.float32(w[c]) for c in col]
+            if npts is not None:
+                npts[i] = int(w[props.index("npts")])
+    return xyz, npts

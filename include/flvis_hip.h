@@ -935,6 +935,67 @@ int flvis_lc_links_from_fix(const flvis_lc_fix_in* fix, int stream, int64_t kf, 
  * FLVIS_ERR_INVALID_ARG for a NULL argument, a pose that is not finite or a zero quaternion.  Host only. */
 int flvis_lc_link_reverse(const flvis_lc_link* in, flvis_lc_link* out);
 
+/* ---- a map as points: landmarks of many keyframes in the map frame, one point per occupied voxel ---------------------------------------
+ * (LocalMapNodeletClass publishes /map_cloud, vo_localmap.cpp:335-377 and :458-461, and sets up a pcl::VoxelGrid with an 0.08 m leaf that it
+ * never runs: the raw cloud goes out.  leaf = 0 is that output; leaf > 0 is the filter, by this project's own rule.)
+ * Input: n_rows rows of up to cap points.  d_p3 [n_rows][cap][3] doubles in the row's camera frame; d_count [n_rows] (a negative count is
+ * read as 0, one above cap as cap); d_T_c_w7 [n_rows][7] tx ty tz qx qy qz qw, the row's T_c_w.  A cloud is the concatenation of row
+ * ranges: h_range2 [h_cloud_ptr[n_clouds]][2] = (first row, row count), cloud c owns the ranges h_cloud_ptr[c] .. h_cloud_ptr[c + 1].
+ * A row may be in several ranges and several clouds.
+ * Canonical order of a cloud's points: its ranges in the caller's order, rows ascending within a range, landmark index ascending.
+ * Map-frame point: p = q_rotate(q_conj(q), p_c - t) on the pose as stored (dev_math.hpp; no normalisation), fp64 without contraction.  An
+ *   identity pose returns p_c bit for bit (a zero coordinate comes out as +0).
+ * Voxel index per axis: i = floor(p / leaf) in fp64 -- one correctly rounded division, then floor.  (PCL multiplies by a float inverse
+ *   relative to the cloud's minimum: a point's voxel would depend on the other points.)
+ * Dropped: a point with a coordinate that is not finite or an index outside -2^20 <= i < 2^20; counted in h_n_dropped.
+ * Key: (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20).
+ * leaf > 0: one output row per voxel that holds at least min_points points, rows ascending by key.  Per axis the row is the fp64 sum of the
+ *   voxel's points -- the first point, then the others added one after another in canonical order -- divided by the count as a double and
+ *   rounded once to float; d_npts is the count.
+ * leaf == 0: no filter: every kept point in canonical order, rounded to float, d_npts = 1; min_points is not used.
+ * Output: d_xyz [n_clouds][out_cap][3], d_npts [n_clouds][out_cap] (may be NULL), h_n_out [n_clouds] the FULL row counts -- at most out_cap
+ *   rows are written per cloud, the first ones in output order; h_n_dropped [n_clouds] (may be NULL).  Rows from h_n_out on are not written.
+ * Several clouds in one call give, cloud for cloud, the bits of as many single calls; a second run gives the same bits.
+ * The call waits for its own counts (three times: the input points, which key bytes vary, the row counts) and for nothing else; d_xyz and
+ *   d_npts are complete on the context's stream when it returns.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: leaf < 0 or not finite, min_points < 1, out_cap < 0, n_rows <= 0, cap <= 0, a range
+ *   outside [0, n_rows), an h_cloud_ptr that does not start at 0 or decreases, n_clouds <= 0, a NULL d_p3, d_count, d_T_c_w7, h_cloud_ptr,
+ *   h_range2 or h_n_out, a NULL d_xyz with out_cap > 0.  flvis_voxel_cloud_check is the host part of these checks on its own (no context).
+ * FLVIS_ERR_CAPACITY: the clouds of the call hold 2^31 input points or more together (so: also a single cloud that does).
+ * Workspace: the context's, grown on demand and kept: 48 bytes per input point of the call (two buffers of 64-bit keys and of 32-bit
+ *   indices for the sort's passes, the fp64 map-frame point), 16 per listed row, 24 per cloud and a fixed 2.1 MB.  A failed allocation
+ *   returns FLVIS_ERR_HIP and leaves the context usable.
+ * Sort: stable LSD radix passes over 8-bit digits of (cloud index | key) in tiles of info[0] elements; a digit with one value in the
+ *   whole call is skipped, and the cloud digits are skipped when no key digit ran or one cloud holds every point.
+ * flvis_hip_voxel_cloud_info: h_info4 = sort tile (elements), workgroup size, workspace bytes per input point, per listed row.  Host only.
+ * flvis_hip_voxel_cloud_stats: of the context's last call that got as far as the sort: passes run, passes skipped, workspace bytes the
+ *   call needed, input points. */
+int flvis_hip_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const double* d_T_c_w7, int n_rows, int cap, int n_clouds,
+                          const int* h_cloud_ptr /* [n_clouds + 1] */, const int* h_range2, double leaf, int min_points, int out_cap,
+                          float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped);
+int flvis_voxel_cloud_check(int n_rows, int cap, int n_clouds, const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points,
+                            int out_cap);
+int flvis_hip_voxel_cloud_info(int* h_info4);
+int flvis_hip_voxel_cloud_stats(flvis_ctx* ctx, int64_t* h_stats4);
+/* The maps of a closer as voxel clouds: cloud g is flvis_hip_voxel_cloud over every stored keyframe of the sequences
+ * h_seq[h_group_ptr[g] .. h_group_ptr[g + 1]) in that order, keyframes ascending -- one range per sequence over the landmark database
+ * (camera-frame positions, counts) and the pose database.  Groups are written as flvis_loop_closer_merge takes them, but a group of one
+ * sequence is allowed, a sequence may be in several groups, and only within a group the sequences must be distinct.
+ * "Stored": everything add_keyframes has stored, processed or not (localize's database).  Each keyframe enters with the T_c_w the database
+ * holds at the time of the call: after a merge of the same group the cloud is in the anchor's frame.  An empty sequence contributes
+ * nothing; a group of empty sequences gives h_n_out = 0.
+ * leaf, min_points, out_cap, d_xyz [n_groups][out_cap][3], d_npts (may be NULL), h_n_out, h_n_dropped (may be NULL): that call's.
+ * _host: h_xyz / h_npts (may be NULL) are host arrays of the same shapes; the rows below min(h_n_out, out_cap) are written.
+ * The call waits for its own counts (the _host form: and for its rows) and for nothing else.
+ * No side effect a caller can observe: poses, drift, loops, similarity rows and events afterwards are bit for bit those of a closer that
+ * never made the call; a keyframe that was added and not yet processed stays pending; the query slots of localize are not touched.
+ * FLVIS_ERR_INVALID_ARG, and nothing changes: a NULL closer, h_group_ptr, h_seq or h_n_out; n_groups <= 0; an h_group_ptr that does not
+ * start at 0 or decreases; a sequence out of range or twice in one group; the argument errors of flvis_hip_voxel_cloud. */
+int flvis_loop_closer_map_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, double leaf, int min_points,
+                                int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped);
+int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, double leaf,
+                                     int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped);
+
 #ifdef __cplusplus
 }
 #endif

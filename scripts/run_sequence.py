@@ -3,7 +3,7 @@
 (`stamp x y z qw qx qy qz`, camera pose T_w_c); with ground truth present, prints the Umeyama-aligned ATE.
 
   run_sequence.py <sequence folder> <config yaml> <out.txt> [--backend hip|cpu] [--frames N] [--local-map] [--imu-out <est.txt>]
-                  [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>]]
+                  [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]]
 
 --imu-out : rigs with an IMU: additionally the IMU-rate trajectory of F2FTracking::imu_feed's outputs (pos_w_i, q_w_i per sample) -- the
 /imu_pose topic, which is what the reference's EuRoC launch file records as est.txt (launch/flvis_euroc_mav.launch:83-103) and scores;
@@ -16,7 +16,11 @@ Comparing the two output files with flvis_amd.traj_io.ate_from_files gives the m
 --loop-closing : the tracker's keyframes additionally go through the loop closing (vo_loopclosing.cpp: the third nodelet of the launch
 files) with the vocabulary of --voc (.dbow3 / .txt / .yml[.gz]) and the lcKF* / ratio* / min* block of the yaml; the keyframe path it
 maintains (T_w_c of every keyframe, corrected by the pose graph whenever a loop closes) is written to --lc-out in the same format.
-hip: flvis_loop_closer; cpu: the same control flow assembled from the oracle's functions (tests/_loop_chain.py)."""
+hip: flvis_loop_closer; cpu: the same control flow assembled from the oracle's functions (tests/_loop_chain.py).
+
+--map-cloud : (hip) the corrected map next to the corrected keyframe path: the landmarks of every keyframe in the map frame, one point per
+voxel of --leaf metres (0: every landmark, what the reference's /map_cloud carries), as ASCII PLY with the voxels' point counts
+(flvis_loop_closer_map_cloud, flvis_amd.traj_io.write_ply)."""
 import argparse
 import json
 import os
@@ -40,9 +44,13 @@ def main():
     ap.add_argument("--voc", default=None)
     ap.add_argument("--lc-out", default=None)
     ap.add_argument("--imu-out", default=None)
+    ap.add_argument("--map-cloud", default=None)
+    ap.add_argument("--leaf", type=float, default=0.08)
     args = ap.parse_args()
     if args.loop_closing and not args.voc:
         ap.error("--loop-closing needs --voc <vocabulary file>")
+    if args.map_cloud and not (args.loop_closing and args.backend == "hip"):
+        ap.error("--map-cloud needs --loop-closing and --backend hip")
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -114,6 +122,11 @@ def main():
         if args.imu_out and len(imu_rows):
             trk.write_imu_trajectory(imu_rows, args.imu_out)
         kf_T_c_w = closer.poses(0) if closer is not None else None
+        map_cloud = None
+        if args.map_cloud:
+            xyz, npts, n_out, n_drop = closer.map_cloud([[0]], leaf=args.leaf)
+            traj_io.write_ply(args.map_cloud, xyz[0], npts[0])
+            map_cloud = {"points": int(n_out[0]), "dropped": int(n_drop[0]), "leaf": args.leaf}
         T_imu_cam = np.array(list(cfg.T_imu_cam0)).reshape(4, 4)
         stamps, pos, quat = traj_io.read_stamped(args.out)
     out = {"backend": args.backend, "frames": len(seq) if args.frames is None else args.frames, "tracked": len(stamps)}
@@ -128,6 +141,8 @@ def main():
         out["loop_closing"] = {"keyframes": len(kf_stamps), "candidates": int(sum(bool(e["candidate"]) for e in lc_events)),
                                "loops_accepted": int(sum(bool(e["accepted"]) for e in lc_events)),
                                "pose_graph_runs": int(sum(bool(e["optimised"]) for e in lc_events))}
+        if args.map_cloud:
+            out["loop_closing"]["map_cloud"] = map_cloud
     if seq.groundtruth is not None and len(stamps) >= 3:
         gt_t, gt_p, _ = seq.groundtruth
         if kitti:   # KITTI ground truth is the camera itself
