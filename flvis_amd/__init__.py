@@ -528,6 +528,25 @@ class Context:
                        C.c_double(confidence), _P(sd, C.c_uint64), _ptr(pose), _ptr(mask), _ptr(ninl)), "pnp_ransac")
         return pose, mask, ninl
 
+    def debug_pnp_ransac_iterative(self, p3d, p2d, count, K4, guess7, iterations=100, reproj_px=3.0, confidence=0.99):
+        """flvis_hip_debug_pnp_ransac_iterative: the tracker's branch of the PnP RANSAC (5-point EPnP hypotheses, Gauss-Newton on the inliers;
+        its parameters are the defaults) on the arrays of pnp_ransac, guess7 float64 [n,7] (host) -> (pose7 [n,7], mask [n,cap],
+        n_inliers [n]); a set without a model gets its guess back."""
+        import numpy as np
+        import torch
+        p3d, p2d = p3d.contiguous(), p2d.contiguous()
+        n, cap, _ = p3d.shape
+        K = np.ascontiguousarray(K4, np.float64)
+        g7 = np.ascontiguousarray(guess7, np.float64)
+        assert K.shape == (4,) and g7.shape == (n, 7)
+        pose = torch.zeros((n, 7), dtype=torch.float64, device=p3d.device)
+        mask = torch.zeros((n, cap), dtype=torch.uint8, device=p3d.device)
+        ninl = torch.zeros((n,), dtype=torch.int32, device=p3d.device)
+        self._check(self._lib.flvis_hip_debug_pnp_ransac_iterative(
+            self._h, _ptr(p3d), _ptr(p2d), _ptr(count), cap, n, _P(K, C.c_double), int(iterations), C.c_double(reproj_px),
+            C.c_double(confidence), _P(g7, C.c_double), _ptr(pose), _ptr(mask), _ptr(ninl)), "debug_pnp_ransac_iterative")
+        return pose, mask, ninl
+
     def debug_epnp(self, p3d, p2d, count, K4):
         """flvis_hip_debug_epnp: EPnP alone on correspondence sets (p3d float32 [n,cap,3], p2d float32 [n,cap,2], count int32 [n], device)
         -> float64 [n,160] (layout in include/flvis_hip.h)."""

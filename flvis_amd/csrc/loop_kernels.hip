@@ -778,6 +778,17 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__
   if (t == 0) lm_count[img] = tot;
 }
 
+// what every entry point of the PnP RANSAC on caller arrays refuses, before anything is uploaded or launched
+static int pnp_ransac_check(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, bool have_K4,
+                            int iterations, double reproj_px, double confidence, const double* d_pose7, const uint8_t* d_inlier_mask,
+                            const int* d_n_inliers) {
+  if (!d_p3d || !d_p2d || !d_count || !have_K4 || !d_pose7 || !d_inlier_mask || !d_n_inliers || cap <= 0 || n_sets <= 0 || iterations <= 0 ||
+      !(reproj_px > 0) || !(confidence > 0 && confidence < 1))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
+  if (cap > pnp_ransac_max_points()) return ctx->fail(FLVIS_ERR_CAPACITY, "pnp_ransac: at most 1024 correspondences per set");
+  return FLVIS_OK;
+}
+
 }  // namespace flvis
 
 using namespace flvis;
@@ -1033,6 +1044,28 @@ int flvis_hip_pnp_ransac_rigs(flvis_ctx* ctx, const float* d_p3d, const float* d
   const int rc = pnp_ransac_dev(ctx, d_p3d, d_p2d, d_count, cap, n_sets, nullptr, k4, 4, nullptr, iterations, reproj_px, confidence, h_seeds,
                                 d_pose7, d_inlier_mask, d_n_inliers);
   if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);  // (an argument refused before that wait: h_K4 may still be read)
+  return rc;
+}
+
+// The tracker's branch of the same solver (cv::solvePnPRansac(..., SOLVEPNP_ITERATIVE): 5-point EPnP hypotheses, a pose to fall back on,
+// Gauss-Newton on the inliers) on caller arrays: k_pnp_ransac_sets with iterative = 1.  The guesses go to the device as the seeds do.
+int flvis_hip_debug_pnp_ransac_iterative(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets,
+                                         const double* h_K4, int iterations, double reproj_px, double confidence, const double* h_guess7,
+                                         double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers) {
+  CHECK_CTX(ctx);
+  if (!h_guess7) return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
+  const int bad = pnp_ransac_check(ctx, d_p3d, d_p2d, d_count, cap, n_sets, h_K4 != nullptr, iterations, reproj_px, confidence, d_pose7,
+                                   d_inlier_mask, d_n_inliers);
+  if (bad != FLVIS_OK) return bad;
+  hipSetDevice(ctx->device);
+  double* g7 = (double*)ctx->scratch("pnp_guess7", sizeof(double) * 7 * (size_t)n_sets);
+  if (!g7) return ctx->fail(FLVIS_ERR_HIP, "pnp_ransac: scratch allocation failed");
+  // (pageable caller memory; pnp_ransac_dev waits for the stream after its seeds, before anything is launched)
+  const hipError_t e = hipMemcpyAsync(g7, h_guess7, sizeof(double) * 7 * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, "pnp_ransac guesses");
+  const int rc = pnp_ransac_dev(ctx, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, nullptr, 0, nullptr, iterations, reproj_px, confidence, nullptr,
+                                d_pose7, d_inlier_mask, d_n_inliers, true, g7);
+  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);  // (an argument refused before that wait: h_guess7 may still be read)
   return rc;
 }
 
@@ -1334,20 +1367,22 @@ int lc_merge_apply_dev(flvis_ctx* ctx, const LcMergeSeq* d_seqs, int n_seqs, con
 
 int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
                    const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
-                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers) {
+                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers, bool iterative, const double* d_guess7) {
   CHECK_CTX(ctx);
-  if (!d_p3d || !d_p2d || !d_count || (!h_K4 && !d_K4) || !h_seeds || !d_pose7 || !d_inlier_mask || !d_n_inliers || cap <= 0 || n_sets <= 0 ||
-      iterations <= 0 || !(reproj_px > 0) || !(confidence > 0 && confidence < 1))
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
-  if (cap > pnp_ransac_max_points()) return ctx->fail(FLVIS_ERR_CAPACITY, "pnp_ransac: at most 1024 correspondences per set");
+  if ((!h_seeds && !iterative) || (iterative && !d_guess7)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "pnp_ransac: bad args");
+  const int bad = pnp_ransac_check(ctx, d_p3d, d_p2d, d_count, cap, n_sets, h_K4 || d_K4, iterations, reproj_px, confidence, d_pose7,
+                                   d_inlier_mask, d_n_inliers);
+  if (bad != FLVIS_OK) return bad;
   hipSetDevice(ctx->device);
   unsigned long long* seeds = (unsigned long long*)ctx->scratch("pnp_seeds", sizeof(unsigned long long) * (size_t)n_sets);
   if (!seeds) return ctx->fail(FLVIS_ERR_HIP, "pnp_ransac: scratch allocation failed");
-  hipError_t e = hipMemcpyAsync(seeds, h_seeds, sizeof(unsigned long long) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream);
+  // (the kernel reads a seed per set whatever the branch: zeros where the caller has none)
+  hipError_t e = h_seeds ? hipMemcpyAsync(seeds, h_seeds, sizeof(unsigned long long) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream)
+                         : hipMemsetAsync(seeds, 0, sizeof(unsigned long long) * (size_t)n_sets, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (h_seeds is pageable caller memory)
   if (e != hipSuccess) return ctx->hip_fail(e, "pnp_ransac seeds");
-  launch_pnp_ransac_sets(ctx->stream, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, d_K4, k4_stride, d_cam_of, 0, nullptr, seeds, iterations,
-                         reproj_px, confidence, d_pose7, d_inlier_mask, d_n_inliers);
+  launch_pnp_ransac_sets(ctx->stream, d_p3d, d_p2d, d_count, cap, n_sets, h_K4, d_K4, k4_stride, d_cam_of, iterative ? 1 : 0,
+                         iterative ? d_guess7 : nullptr, seeds, iterations, reproj_px, confidence, d_pose7, d_inlier_mask, d_n_inliers);
   CHECK_LAUNCH(ctx, "pnp_ransac");
   return FLVIS_OK;
 }

@@ -20,10 +20,12 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
                               const int* d_cam_of, const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
                               double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
 // flvis_hip_pnp_ransac_rigs on a DEVICE table: set i uses fx fy cx cy = d_K4 + k4_stride * (d_cam_of ? d_cam_of[i] : i) (k4_stride in
-// doubles).  d_K4 == nullptr: every set uses h_K4.  (h_seeds is uploaded as in flvis_hip_pnp_ransac.)
+// doubles).  d_K4 == nullptr: every set uses h_K4.  (h_seeds is uploaded as in flvis_hip_pnp_ransac.)  iterative: the tracker's branch
+// (flvis_hip_debug_pnp_ransac_iterative) with set i's fallback pose at d_guess7 + 7 i, on the device; h_seeds may then be nullptr.
 int pnp_ransac_dev(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
                    const double* d_K4, int k4_stride, const int* d_cam_of, int iterations, double reproj_px, double confidence,
-                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
+                   const uint64_t* h_seeds, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers, bool iterative = false,
+                   const double* d_guess7 = nullptr);
 // flvis_hip_lc_select_maps, and with compact its form for rows that hold segment d_map[q] alone ([n_q][seg_len], every d_map[q] >= 0): the
 // loop closer's layout for a call in which no query searches all maps.  d_skip: flvis_hip_lc_select_maps_skip's excluded ranges [n_q][2] in
 // global indices (both row forms), or nullptr: none, the kernel without the range test

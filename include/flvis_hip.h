@@ -300,6 +300,15 @@ int flvis_hip_pnp_ransac_rigs(flvis_ctx* ctx, const float* d_p3d, const float* d
  * MtM (48) | L (60) | rho (6) | the eigenvalues of MtM (12) | unused (6). */
 int flvis_hip_debug_epnp(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, const double* h_K4,
                          double* d_out160);
+/* Test hook: the tracker's branch of the same solver on caller arrays -- cv::solvePnPRansac(..., SOLVEPNP_ITERATIVE) as
+ * LKORBTracking::tracking calls it (lkorb_tracking.cpp:170-177, there with iterations = 100, reprojectionError = 3.0, confidence = 0.99):
+ * 5-point subsets, EPnP hypotheses, Gauss-Newton on the winning model's inliers.  Arguments as for flvis_hip_pnp_ransac, with h_guess7
+ * [n_sets][7] (tx ty tz qx qy qz qw, unit quaternion) in place of the seeds: the pose a set gets back when no model is found (as a
+ * rotation matrix turned into a quaternion again), with n_inliers 0 and an all-zero mask.  The host arrays may be freed when the call
+ * returns. */
+int flvis_hip_debug_pnp_ransac_iterative(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets,
+                                         const double* h_K4, int iterations, double reproj_px, double confidence,
+                                         const double* h_guess7 /* [n_sets][7] */, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
 /* loopClosureOnCovGraphG2ONew (vo_loopclosing.cpp:742-944) for n_graphs independent sequences in one launch (one workgroup per
  * pose graph): graph g has h_n_kf[g] keyframes with T_c_w (device, 7 doubles each: tx ty tz qx qy qz qw, graphs concatenated, in/out)
  * and presence flags (host, concatenated; 0 = kf_map_lc[i] == nullptr), h_n_loops[g] recorded loops (host ids: earlier, later
