@@ -169,10 +169,12 @@ class Context:
         self._check(self._lib.flvis_hip_rand_seed(self._h, C.c_uint32(seed), _ptr(st), n_sets), "rand_seed")
         return st
 
-    def stereo_depth(self, cfg, img0, img1, pt2d_plane, pt2d_undistort, pt3d_w, has_depth, count, poses7, rng, rand_state):
+    def stereo_depth(self, cfg, img0, img1, pt2d_plane, pt2d_undistort, pt3d_w, has_depth, count, poses7, rng, rand_state, out=None, mask=None):
         """flvis_hip_stereo_depth = CameraFrame::recover3DPts_c_FromStereo (camera_frame.cpp:93-180) for n_sets frames in one call.
         img0 / img1 uint8 [n,h,w]; pt2d_* float32 [n,cap,2]; pt3d_w float32 [n,cap,3]; has_depth uint8 [n,cap]; count int32 [n] (all on
-        the device); poses7 host [n,7]; rand_state from rand_seed() (updated in place).  Returns (pt3ds float64 [n,cap,3], mask uint8)."""
+        the device); poses7 host [n,7]; rand_state from rand_seed() (updated in place).  Returns (pt3ds float64 [n,cap,3], mask uint8):
+        out / mask when the caller passes its own (the call writes the first min(count, cap) slots of a set and no other), else new
+        zero-filled tensors."""
         import numpy as np
         import torch
         n, cap = pt2d_plane.shape[0], pt2d_plane.shape[1]
@@ -180,8 +182,12 @@ class Context:
                       (count, torch.int32), (img0, torch.uint8), (img1, torch.uint8), (rand_state, torch.int32)):
             assert a.is_cuda and a.is_contiguous() and a.dtype == dt
         T = np.ascontiguousarray(poses7, np.float64).reshape(n, 7)
-        out = torch.zeros((n, cap, 3), dtype=torch.float64, device=self.device)
-        mask = torch.zeros((n, cap), dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.zeros((n, cap, 3), dtype=torch.float64, device=self.device)
+        if mask is None:
+            mask = torch.zeros((n, cap), dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (n, cap, 3)
+        assert mask.is_cuda and mask.is_contiguous() and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, cap)
         self._lib.flvis_hip_stereo_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
