@@ -515,6 +515,36 @@ class Context:
             "lc_keyframe_landmarks")
         return lm2, lm3, lmd, cnt
 
+    def lc_keyframe_landmarks_unrect(self, img0, img1, cfgs, kps, desc, count, in_place=False, out=None):
+        """flvis_hip_lc_keyframe_landmarks_unrect: the STEREO_UNRECT case (the reference's is empty) by this project's rule -- LK from the
+        keypoints of the raw img0 into the raw img1, both ends through undistortPoints, DLT with P0 / P1.  img0 / img1 uint8 [n,h,w]; cfgs: a
+        finalized FlvisCfg (one rig for every image) or a sequence of n (one per image); kps / desc / count as orb_detect_and_compute returns
+        them.  Returns (lm_2d float32 [n,cap,2] in the RECTIFIED plane, lm_3d float64 [n,cap,3] in the rectified camera-0 frame, lm_desc,
+        lm_count) as lc_keyframe_landmarks does; out: these four tensors from the caller (a test's sentinel-filled ones) instead of new ones."""
+        import torch
+        kps, desc, img0, img1 = kps.contiguous(), desc.contiguous(), img0.contiguous(), img1.contiguous()
+        n, cap, _ = kps.shape
+        h, w = img0.shape[-2:]
+        assert tuple(img0.shape) == tuple(img1.shape) == (n, h, w) and img0.dtype == img1.dtype == torch.uint8
+        cfgs = [cfgs] if isinstance(cfgs, FlvisCfg) else list(cfgs)
+        arr = (FlvisCfg * max(1, len(cfgs)))(*cfgs)
+        if out is not None:
+            lm2, lm3, lmd, cnt = out
+            assert (lm2.dtype, lm3.dtype, lmd.dtype, cnt.dtype) == (torch.float32, torch.float64, torch.uint8, torch.int32)
+            assert tuple(lm2.shape) == (n, cap, 2) and tuple(lm3.shape) == (n, cap, 3) and tuple(lmd.shape) == (n, cap, 32) and cnt.numel() == n
+            assert all(t.is_contiguous() for t in out)
+        else:
+            lm2 = torch.zeros((n, cap, 2), dtype=torch.float32, device=kps.device)
+            lm3 = torch.zeros((n, cap, 3), dtype=torch.float64, device=kps.device)
+            lmd = desc if in_place else torch.zeros_like(desc)
+            cnt = torch.zeros((n,), dtype=torch.int32, device=kps.device)
+        fn = self._lib.flvis_hip_lc_keyframe_landmarks_unrect
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FlvisCfg), C.c_int, C.c_void_p, C.c_void_p,
+                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, _ptr(img0), _ptr(img1), w, h, n, arr, len(cfgs), _ptr(kps), _ptr(desc), _ptr(count), cap, _ptr(lm2), _ptr(lm3),
+                       _ptr(lmd), _ptr(cnt)), "lc_keyframe_landmarks_unrect")
+        return lm2, lm3, lmd, cnt
+
     def pnp_ransac(self, p3d, p2d, count, K4, seeds, iterations=100, reproj_px=2.0, confidence=0.99):
         """flvis_hip_pnp_ransac: p3d float32 [n,cap,3], p2d float32 [n,cap,2], count int32 [n] (device) -> (pose7 [n,7], mask [n,cap],
         n_inliers [n]).  K4 [4]: one camera for every set; [n,4]: one per set (flvis_hip_pnp_ransac_rigs)."""
@@ -960,6 +990,13 @@ class LoopCloser:
         self._lib.flvis_loop_closer_stream_cfg.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlvisCfg)]
         self._ctx._check(self._lib.flvis_loop_closer_stream_cfg(self._h, int(s), C.byref(out)), "loop_closer_stream_cfg")
         return out
+
+    def set_stereo_unrect(self, enable):
+        """flvis_loop_closer_set_stereo_unrect: on a STEREO_UNRECT closer (cam_type 1, the EuRoC camera) keyframes and queries get their
+        landmarks by this project's rule (Context.lc_keyframe_landmarks_unrect) instead of the reference's empty case.  Pixels and poses
+        are then of the rectified camera 0.  FlvisError on another cam_type, and while any sequence holds a keyframe."""
+        self._lib.flvis_loop_closer_set_stereo_unrect.argtypes = [C.c_void_p, C.c_int]
+        self._ctx._check(self._lib.flvis_loop_closer_set_stereo_unrect(self._h, 1 if enable else 0), "loop_closer_set_stereo_unrect")
 
     def add_keyframes(self, streams, img0, img1, T_c_w_odom):
         """streams: the sequence of each keyframe (distinct); img0 uint8 [n,h,w], img1 uint8 / Z16 [n,h,w] (device); T_c_w_odom [n,7].

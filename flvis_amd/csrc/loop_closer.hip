@@ -226,6 +226,9 @@ __global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ 
 }
 
 using flvis::LcCam;
+using flvis::LcCamUnrect;
+using flvis::lc_cam_of_cfg;
+using flvis::lc_cam_unrect_of_cfg;
 using flvis::LcMergeSeq;
 
 struct Seq {
@@ -250,6 +253,11 @@ struct flvis_loop_closer {
   // the sequences' cameras: [S] rows on the device, written in stream order from the pinned host copy (a reset does not wait)
   LcCam* h_cams = nullptr;
   LcCam* d_cams = nullptr;
+  // ... and, on a STEREO_UNRECT closer alone, the rows the opt-in rule reads beside them (flvis_loop_closer_set_stereo_unrect), kept like
+  // the first table: the switch may be thrown at any time the database is empty
+  LcCamUnrect* h_ucams = nullptr;
+  LcCamUnrect* d_ucams = nullptr;
+  bool stereo_unrect = false;
   // keyframe database, [S * maxkf] slots; behind them one query slot per sequence (what a localize call holds of its query, stream s at
   // S * maxkf + s) and one slot that stays empty (S * maxkf + S: no landmarks, no words)
   int* db_ids = nullptr;
@@ -375,11 +383,6 @@ static const char* lc_batch_field_mismatch(const flvis_loop_closer* lc, const fl
   if (c.image_height != lc->h) return "image_height";
   return nullptr;
 }
-static void lc_cam_of_cfg(const flvis_cfg& c, LcCam* cam) {
-  memcpy(cam->P0, c.P0, sizeof(cam->P0));
-  memcpy(cam->P1, c.P1, sizeof(cam->P1));
-  cam->fx = c.P0[0], cam->fy = c.P0[5], cam->cx = c.P0[2], cam->cy = c.P0[6];  // dc.K0_rect (:670)
-}
 
 int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const flvis_lc_params* prm, int n_streams, int max_keyframes,
                                   const int8_t* h_orb_pattern, flvis_loop_closer** out) {
@@ -417,9 +420,15 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
             lc->alloc(lc->loop_pose, slots * 7) && lc->alloc(lc->drift, S * 7) && lc->alloc(lc->stats, S * 5) && lc->alloc(lc->pgo_T, slots * 7) &&
             lc->alloc(lc->stage, S * LCC_QSTAGE) && lc->alloc(lc->d_cams, S) &&
             hipHostMalloc((void**)&lc->h_cams, S * sizeof(LcCam), hipHostMallocDefault) == hipSuccess;
+  if (ok && lc->cam_type == 1)
+    ok = lc->alloc(lc->d_ucams, S) && hipHostMalloc((void**)&lc->h_ucams, S * sizeof(LcCamUnrect), hipHostMallocDefault) == hipSuccess;
   if (ok) {
     for (int s = 0; s < n_streams; s++) lc_cam_of_cfg(cfgs[s], &lc->h_cams[s]);
     ok = hipMemcpyAsync(lc->d_cams, lc->h_cams, S * sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok && lc->h_ucams) {
+      for (int s = 0; s < n_streams; s++) lc_cam_unrect_of_cfg(cfgs[s], &lc->h_ucams[s]);
+      ok = hipMemcpyAsync(lc->d_ucams, lc->h_ucams, S * sizeof(LcCamUnrect), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    }
     // the empty slot: its two counts are all that is ever read of it
     ok = ok && hipMemsetAsync(lc->db_lmc + slots + S, 0, sizeof(int), ctx->stream) == hipSuccess &&
          hipMemsetAsync(lc->db_nnz + slots + S, 0, sizeof(int), ctx->stream) == hipSuccess;
@@ -429,6 +438,7 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
     hipStreamSynchronize(ctx->stream);
     for (void* p : lc->owned) hipFree(p);
     if (lc->h_cams) hipHostFree(lc->h_cams);
+    if (lc->h_ucams) hipHostFree(lc->h_ucams);
     delete lc;
     return ctx->fail(FLVIS_ERR_HIP, "loop_closer_create: device allocation failed (76 KB per keyframe slot)");
   }
@@ -478,7 +488,11 @@ static int lc_reset(flvis_loop_closer* lc, int n, const int* streams, const flvi
     // (a copy of this row that a previous reset queued has run: every call that reads the table returns synchronised, and with no such
     //  call in between nothing has looked at the row the earlier reset wrote)
     lc_cam_of_cfg(cfgs[i], &lc->h_cams[s]);
-    const hipError_t e = hipMemcpyAsync(lc->d_cams + s, lc->h_cams + s, sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(lc->d_cams + s, lc->h_cams + s, sizeof(LcCam), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && lc->h_ucams) {
+      lc_cam_unrect_of_cfg(cfgs[i], &lc->h_ucams[s]);
+      e = hipMemcpyAsync(lc->d_ucams + s, lc->h_ucams + s, sizeof(LcCamUnrect), hipMemcpyHostToDevice, ctx->stream);
+    }
     if (e != hipSuccess) return ctx->hip_fail(e, what);
   }
   return FLVIS_OK;
@@ -505,7 +519,24 @@ void flvis_loop_closer_destroy(flvis_loop_closer* lc) {
   hipDeviceSynchronize();
   for (void* p : lc->owned) hipFree(p);
   hipHostFree(lc->h_cams);
+  if (lc->h_ucams) hipHostFree(lc->h_ucams);
   delete lc;
+}
+
+// The reference's STEREO_UNRECT case is empty: a keyframe of such a rig stores no landmark (the default here).  enable != 0 fills it with
+// this project's rule (k_lc_landmarks_unrect) for every frame that goes through a keyframe's steps from now on.  The switch belongs to the
+// whole database -- a map of keyframes with and without landmarks, in raw and in rectified pixels, would be neither -- so it is refused
+// while any sequence holds a keyframe.
+int flvis_loop_closer_set_stereo_unrect(flvis_loop_closer* lc, int enable) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  if (lc->cam_type != 1) return ctx->fail(FLVIS_ERR_CONFIG, "loop_closer_set_stereo_unrect: the closer's rig is not STEREO_UNRECT (cam_type 1)");
+  for (int s = 0; s < lc->S; s++)
+    if (lc->seq[s].n > 0)
+      return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_set_stereo_unrect: sequence " + std::to_string(s) +
+                                                  " holds keyframes (reset every sequence first)");
+  lc->stereo_unrect = enable != 0;
+  return FLVIS_OK;
 }
 
 // STEP 1.3 / 1.4 / 1.5 / 1.6 (:236-372) for n images into the per-call buffers: ORB, bag of words of ALL descriptors, 3-D positions with
@@ -515,7 +546,10 @@ static int lc_features(flvis_loop_closer* lc, int n, const uint8_t* d_img0, cons
   int rc = flvis_hip_orb_detect_and_compute(ctx, d_img0, lc->w, lc->h, n, &lc->orb, lc->pattern.empty() ? nullptr : lc->pattern.data(), lc->kps,
                                             lc->desc, lc->cnt, LCC_CAP, lc->ovf);
   if (rc == FLVIS_OK) rc = flvis_hip_bow_transform(ctx, lc->desc, lc->cnt, LCC_CAP, n, LCC_VCAP, lc->ids, lc->vals, lc->nnz);
-  if (rc == FLVIS_OK)
+  if (rc == FLVIS_OK && lc->stereo_unrect)
+    rc = flvis::lc_keyframe_landmarks_unrect_dev(ctx, d_img0, (const uint8_t*)d_img1, lc->w, lc->h, n, lc->d_cams, lc->d_ucams, d_seq, lc->kps,
+                                                 lc->desc, lc->cnt, LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
+  else if (rc == FLVIS_OK)
     rc = flvis::lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, lc->w, lc->h, n, lc->cam_type, lc->d_cams, d_seq, lc->kps, lc->desc, lc->cnt,
                                           LCC_CAP, lc->lm2, lc->lm3, lc->desc, lc->lmc);
   return rc;

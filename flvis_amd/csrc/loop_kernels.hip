@@ -778,6 +778,60 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__
   if (t == 0) lm_count[img] = tot;
 }
 
+// The STEREO_UNRECT case, which the reference leaves empty (:318-324, "track to another image / go to undistor plane / triangulation"):
+// this project's rule is the STEREO_RECT case with the tracker's undistortion in front of the DLT (recover3DPts_c_FromStereo, k_sd_post).
+// A kernel of its own: the two undistortions' registers stay off k_lc_landmarks' two paths.  Same shape otherwise -- one workgroup per
+// keyframe, two keypoints per thread, the ordered removal -- and the kept pixel is the one in the rectified plane, which is where the
+// pair check's K = P0[0], P0[5], P0[2], P0[6] without distortion holds.
+__global__ __launch_bounds__(LC_T) void k_lc_landmarks_unrect(const LcCam* __restrict__ cams, const LcCamUnrect* __restrict__ ucams,
+                                                              const int* __restrict__ cam_of, const float* __restrict__ kps, const uint8_t* desc,
+                                                              const int* __restrict__ count, int cap, const float* __restrict__ next_pts,
+                                                              const uint8_t* __restrict__ status, float* lm_2d, double* lm_3d, uint8_t* lm_desc,
+                                                              int* __restrict__ lm_count) {
+  __shared__ int s_scan[LC_T / 64];
+  const int img = blockIdx.x, t = threadIdx.x;
+  const int row = cam_of ? cam_of[img] : img;
+  const LcCam& cam = cams[row];
+  const LcCamUnrect& uc = ucams[row];
+  const int n = min(count[img], cap);
+  bool keep[2] = {false, false};
+  float xy[2][2];
+  V3 p3[2];
+  uint4 d[2][2];
+#pragma unroll
+  for (int e = 0; e < 2; e++) {
+    const int i = 2 * t + e;
+    if (i >= n) continue;
+    const size_t o = (size_t)img * cap + i;
+    const uint4* q = reinterpret_cast<const uint4*>(desc + o * 32);
+    d[e][0] = q[0], d[e][1] = q[1];
+    if (status[o] != 1) continue;
+    const float src0[2] = {kps[o * 6], kps[o * 6 + 1]}, src1[2] = {next_pts[o * 2], next_pts[o * 2 + 1]};
+    float u0[2], u1[2];  // (floats: cv::undistortPoints returns Point2f)
+    undistort_point(src0, uc.K0, uc.D0, uc.R0, cam.P0, u0);
+    undistort_point(src1, uc.K1, uc.D1, uc.R1, cam.P1, u1);
+    const V3 pc = triangulate_dlt((double)u0[0], (double)u0[1], (double)u1[0], (double)u1[1], cam.P0, cam.P1);
+    if (!(pc.z < 0 || pc.z > (double)100.0f)) {  // the STEREO_RECT rule (range = 100.0, triangulation.h:24)
+      keep[e] = true;
+      p3[e] = pc;
+      xy[e][0] = u0[0], xy[e][1] = u0[1];
+    }
+  }
+  int tot;
+  int k = block_exclusive_scan<LC_T / 64>((int)keep[0] + (int)keep[1], s_scan, tot);  // (its barriers also order the in-place case)
+#pragma unroll
+  for (int e = 0; e < 2; e++) {
+    if (!keep[e]) continue;
+    const size_t o = (size_t)img * cap + k;
+    lm_2d[o * 2] = xy[e][0], lm_2d[o * 2 + 1] = xy[e][1];
+    lm_3d[o * 3] = p3[e].x, lm_3d[o * 3 + 1] = p3[e].y, lm_3d[o * 3 + 2] = p3[e].z;
+    uint4* q = reinterpret_cast<uint4*>(lm_desc + o * 32);
+    q[0] = d[e][0], q[1] = d[e][1];
+    k++;
+  }
+  if (t == 0) lm_count[img] = tot;
+}
+
 // what every entry point of the PnP RANSAC on caller arrays refuses, before anything is uploaded or launched
 static int pnp_ransac_check(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets, bool have_K4,
                             int iterations, double reproj_px, double confidence, const double* d_pose7, const uint8_t* d_inlier_mask,
@@ -920,6 +974,40 @@ int flvis_hip_lc_keyframe_landmarks(flvis_ctx* ctx, const uint8_t* d_img0, const
   if (rc != FLVIS_OK) return rc;
   return lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, w, h, n_img, cam_type, cams, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
                                    d_lm_desc, d_lm_count);
+}
+
+// the STEREO_UNRECT rule (k_lc_landmarks_unrect) on caller arrays: the rigs are finalized configs, one for every image or one per image
+int flvis_hip_lc_keyframe_landmarks_unrect(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int w, int h, int n_img,
+                                           const flvis_cfg* h_cfgs, int n_cfgs, const float* d_kps, const uint8_t* d_desc, const int* d_count,
+                                           int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+  CHECK_CTX(ctx);
+  if (!d_img0 || !d_img1 || !h_cfgs || !d_kps || !d_desc || !d_count || !d_lm_2d || !d_lm_3d || !d_lm_desc || !d_lm_count || n_img <= 0 ||
+      cap <= 0 || w <= 0 || h <= 0 || (n_cfgs != 1 && n_cfgs != n_img))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks_unrect: bad args (n_cfgs is 1 or n_img)");
+  if (cap > LC_MAXF) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_keyframe_landmarks_unrect: at most 2048 keypoints per keyframe");
+  for (int i = 0; i < n_cfgs; i++) {
+    if (h_cfgs[i].cam_type != 1)
+      return ctx->fail(FLVIS_ERR_CONFIG, "lc_keyframe_landmarks_unrect: config " + std::to_string(i) + " is not a STEREO_UNRECT rig (cam_type 1)");
+    if (h_cfgs[i].image_width != w || h_cfgs[i].image_height != h)
+      return ctx->fail(FLVIS_ERR_CONFIG, "lc_keyframe_landmarks_unrect: config " + std::to_string(i) + " is for another image size");
+  }
+  std::vector<LcCam> rows((size_t)n_img);
+  std::vector<LcCamUnrect> urows((size_t)n_img);
+  for (int i = 0; i < n_img; i++) {
+    const flvis_cfg& c = h_cfgs[n_cfgs == 1 ? 0 : i];
+    lc_cam_of_cfg(c, &rows[i]);
+    lc_cam_unrect_of_cfg(c, &urows[i]);
+  }
+  hipSetDevice(ctx->device);
+  LcCam* d = (LcCam*)ctx->scratch("lc_cams", sizeof(LcCam) * (size_t)n_img);
+  LcCamUnrect* du = (LcCamUnrect*)ctx->scratch("lc_ucams", sizeof(LcCamUnrect) * (size_t)n_img);
+  if (!d || !du) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks_unrect: scratch allocation failed");
+  hipError_t e = hipMemcpyAsync(d, rows.data(), sizeof(LcCam) * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(du, urows.data(), sizeof(LcCamUnrect) * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the rows are host temporaries)
+  if (e != hipSuccess) return ctx->hip_fail(e, "lc_keyframe_landmarks_unrect");
+  return lc_keyframe_landmarks_unrect_dev(ctx, d_img0, d_img1, w, h, n_img, d, du, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
+                                          d_lm_desc, d_lm_count);
 }
 
 int flvis_hip_bow_transform(flvis_ctx* ctx, const uint8_t* d_desc, const int* d_count, int dcap, int n_img, int vcap, int* d_ids,
@@ -1329,6 +1417,47 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
   k_lc_landmarks<<<n_img, LC_T, 0, st>>>(d_cams, d_cam_of, cam_type, w, h, d_kps, d_desc, d_count, cap, next, status, (const uint16_t*)d_img1,
                                          d_lm_2d, d_lm_3d, d_lm_desc, d_lm_count);
   CHECK_LAUNCH(ctx, "lc_keyframe_landmarks");
+  return FLVIS_OK;
+}
+
+void lc_cam_of_cfg(const flvis_cfg& c, LcCam* cam) {
+  memcpy(cam->P0, c.P0, sizeof(cam->P0));
+  memcpy(cam->P1, c.P1, sizeof(cam->P1));
+  cam->fx = c.P0[0], cam->fy = c.P0[5], cam->cx = c.P0[2], cam->cy = c.P0[6];  // dc.K0_rect (:670)
+}
+
+void lc_cam_unrect_of_cfg(const flvis_cfg& c, LcCamUnrect* cam) {  // (the fields the tracker's rig takes: rig_from_cfg)
+  memcpy(cam->K0, c.cam0_intrinsics, sizeof(cam->K0));
+  memcpy(cam->D0, c.cam0_distortion, sizeof(cam->D0));
+  memcpy(cam->R0, c.R0, sizeof(cam->R0));
+  memcpy(cam->K1, c.cam1_intrinsics, sizeof(cam->K1));
+  memcpy(cam->D1, c.cam1_distortion, sizeof(cam->D1));
+  memcpy(cam->R1, c.R1, sizeof(cam->R1));
+}
+
+int lc_keyframe_landmarks_unrect_dev(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int w, int h, int n_img, const LcCam* d_cams,
+                                     const LcCamUnrect* d_ucams, const int* d_cam_of, const float* d_kps, const uint8_t* d_desc,
+                                     const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+  CHECK_CTX(ctx);
+  if (!d_img0 || !d_img1 || !d_cams || !d_ucams || !d_kps || !d_desc || !d_count || !d_lm_2d || !d_lm_3d || !d_lm_desc || !d_lm_count ||
+      n_img <= 0 || cap <= 0 || w <= 0 || h <= 0)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks_unrect: bad args");
+  if (cap > LC_MAXF) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_keyframe_landmarks_unrect: at most 2048 keypoints per keyframe");
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const size_t np = (size_t)n_img * cap;
+  float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
+  float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
+  uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
+  if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks_unrect: scratch allocation failed");
+  k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, st>>>(d_kps, d_count, cap, p0, p1);
+  // the STEREO_RECT case's matcher, on the raw pair: Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW  (:274-278)
+  const int rc = flvis_hip_lk_track(ctx, d_img0, d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
+  if (rc != FLVIS_OK) return rc;
+  // (d_lm_desc == d_desc is fine: every workgroup reads its keyframe's rows before the scan's barrier and writes after)
+  k_lc_landmarks_unrect<<<n_img, LC_T, 0, st>>>(d_cams, d_ucams, d_cam_of, d_kps, d_desc, d_count, cap, p1, stt, d_lm_2d, d_lm_3d, d_lm_desc,
+                                                 d_lm_count);
+  CHECK_LAUNCH(ctx, "lc_keyframe_landmarks_unrect");
   return FLVIS_OK;
 }
 

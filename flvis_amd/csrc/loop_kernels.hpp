@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 
+#include "../../include/flvis_hip.h"
 #include "ctx.hpp"
 
 namespace flvis {
@@ -19,6 +20,19 @@ static_assert(sizeof(LcCam) == LC_CAM_DOUBLES * sizeof(double), "LcCam is a plai
 int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type, const LcCam* d_cams,
                               const int* d_cam_of, const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
                               double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
+// what flvis_hip_lc_keyframe_landmarks_unrect reads of a STEREO_UNRECT rig beside its row's P0 / P1: both raw cameras' pinhole + radtan
+// models and rectifying rotations.  A table of its own with the same row index, so that LcCam -- and with it every load of the
+// STEREO_RECT / DEPTH_D435 kernel and of the PnP RANSAC -- stays as it is.
+struct LcCamUnrect {
+  double K0[4], D0[4], R0[9], K1[4], D1[4], R1[9];
+};
+// flvis_hip_lc_keyframe_landmarks_unrect on DEVICE tables: image i uses row d_cam_of ? d_cam_of[i] : i of both.  Uploads nothing.
+int lc_keyframe_landmarks_unrect_dev(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int w, int h, int n_img, const LcCam* d_cams,
+                                     const LcCamUnrect* d_ucams, const int* d_cam_of, const float* d_kps, const uint8_t* d_desc,
+                                     const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
+// the two rows of a finalized config
+void lc_cam_of_cfg(const flvis_cfg& c, LcCam* cam);
+void lc_cam_unrect_of_cfg(const flvis_cfg& c, LcCamUnrect* cam);
 // flvis_hip_pnp_ransac_rigs on a DEVICE table: set i uses fx fy cx cy = d_K4 + k4_stride * (d_cam_of ? d_cam_of[i] : i) (k4_stride in
 // doubles).  d_K4 == nullptr: every set uses h_K4.  (h_seeds is uploaded as in flvis_hip_pnp_ransac.)  iterative: the tracker's branch
 // (flvis_hip_debug_pnp_ransac_iterative) with set i's fallback pose at d_guess7 + 7 i, on the device; h_seeds may then be nullptr.

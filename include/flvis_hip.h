@@ -20,6 +20,7 @@
  *                                <- DBoW3::Vocabulary(file), ::transform, ::score; isLoopCandidate   vo_loopclosing.cpp:1097,249-253,417-437,520-590
  *   flvis_hip_voc_train, flvis_voc_file_save / _save_arrays   <- DBoW3::Vocabulary::create, ::save   3rdPartLib/DBow3/src/Vocabulary.cpp:142-569,1180-1256
  *   flvis_hip_lc_keyframe_landmarks(_rigs)  <- stereo LK + triangulation / depth lookup of the ORB keypoints   vo_loopclosing.cpp:255-372
+ *   flvis_hip_lc_keyframe_landmarks_unrect  <- the STEREO_UNRECT case the reference leaves empty (:318-324), filled in: this project's rule
  *   flvis_hip_pnp_ransac(_rigs)  <- cv::solvePnPRansac of isLoopClosureKF                             vo_loopclosing.cpp:660-686
  *   flvis_hip_pgo_loop_closure   <- loopClosureOnCovGraphG2ONew (g2o EdgeSE3 pose graph)              vo_loopclosing.cpp:742-944
  * Pipeline-level entry points (the nodelets' work for a batch of streams / sequences):
@@ -38,6 +39,7 @@ extern "C" {
 #endif
 
 typedef struct flvis_ctx flvis_ctx;
+struct flvis_cfg; /* (defined with the pipeline-level entry points below) */
 
 typedef enum flvis_status {
   FLVIS_OK = 0,
@@ -238,6 +240,26 @@ int flvis_hip_lc_keyframe_landmarks(flvis_ctx* ctx, const uint8_t* d_img0, const
 int flvis_hip_lc_keyframe_landmarks_rigs(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
                                          const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
                                          const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
+/* The STEREO_UNRECT case (the EuRoC camera), which the reference leaves as three comments -- "track to another image / go to undistor
+ * plane / triangulation" -- and a break (vo_loopclosing.cpp:318-324).  The two calls above keep that empty case (every count 0); this
+ * one fills it in, as an addition of this project: the STEREO_RECT case with the tracker's undistortion in front of the DLT
+ * (CameraFrame::recover3DPts_c_FromStereo, camera_frame.cpp:124-147).  Per keypoint (x, y) of the RAW img0: the match in the RAW img1 by
+ * calcOpticalFlowPyrLK(Size(31,31), 5, 30 / 0.001, USE_INITIAL_FLOW) seeded at the same pixel; where its status is 1,
+ * u0 = undistortPoints((x, y), K0, D0, R0, P0), u1 = undistortPoints(match, K1, D1, R1, P1) (Point2f, as OpenCV returns them) and
+ * pc = Triangulation::triangulationPt(u0, u1, P0, P1); kept unless pc.z < 0 or pc.z > 100.
+ * Out, order kept: d_lm_2d = u0, the pixel in the RECTIFIED plane (where K = P0[0], P0[5], P0[2], P0[6] without distortion -- the K of
+ * the pair check's solvePnPRansac -- holds); d_lm_3d = pc in the RECTIFIED camera-0 frame (the frame of the tracker's T_c_w on this rig);
+ * the descriptor.  Outputs, aliasing (d_lm_desc == d_desc), count clamping and "rows from d_lm_count on are never written" are those of
+ * flvis_hip_lc_keyframe_landmarks; cap <= 2048.
+ * h_cfgs: finalized configs (flvis_config_load), read during the call (they may be freed on return): K, D of both cameras, R0 / R1 /
+ * P0 / P1.  n_cfgs = 1: one rig for every image; n_cfgs = n_img: one per image, and image i gets bit for bit what the call gives it alone
+ * with h_cfgs[i].
+ * Refused before anything is launched or written: a config whose cam_type is not 1 or whose image size is not w x h
+ * (FLVIS_ERR_CONFIG); n_cfgs other than 1 or n_img, null pointers (FLVIS_ERR_INVALID_ARG); cap > 2048 (FLVIS_ERR_CAPACITY). */
+int flvis_hip_lc_keyframe_landmarks_unrect(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int w, int h, int n_img,
+                                           const struct flvis_cfg* h_cfgs, int n_cfgs /* 1: one rig for every image; n_img: one per image */,
+                                           const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
+                                           double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count);
 /* one row of the similarity matrix (vo_loopclosing.cpp:417-437): voc.score(query, db[j]) for j < n_db (ScoringObject.cpp:23-68);
  * the query is one vector on the device (d_q_nnz[0] entries), the database [n_db][vcap]; d_db_nnz[j] < 0 marks an absent keyframe
  * (kf_lc_tmp[j] == nullptr: score 0). */
@@ -766,6 +788,16 @@ int flvis_loop_closer_reset(flvis_loop_closer* lc, int n, const int* streams);
 int flvis_loop_closer_reset_rigs(flvis_loop_closer* lc, int n, const int* streams, const flvis_cfg* cfgs);
 /* The config sequence `stream` runs on: the one it was created or last reset with. */
 int flvis_loop_closer_stream_cfg(flvis_loop_closer* lc, int stream, flvis_cfg* out);
+/* Loop closing on a STEREO_UNRECT rig (cam_type 1, the EuRoC camera).  By default (0) such a closer is the reference's: its case is empty,
+ * a keyframe stores no landmark, and process / localize / link never verify a pair.  enable != 0 makes every frame that goes through a
+ * keyframe's steps -- add_keyframes(_host) and the queries of localize(_host) and localize_in(_host) -- use the rule of
+ * flvis_hip_lc_keyframe_landmarks_unrect with the rig of the frame's sequence (the configs of create_rigs / reset_rigs, which
+ * flvis_loop_closer_stream_cfg returns: K, D of both cameras, R0, R1, P0, P1 per sequence).  An addition of this project, hence opt-in.
+ * On such a closer flvis_loop_closer_keyframe returns pixels of the RECTIFIED plane, and every pose (loop_pose7, cand_pose7, T_c_map7,
+ * flvis_loop_closer_poses; and so the T_c_w_odom7 a caller hands in) is of the RECTIFIED camera-0 frame -- the tracker's T_c_w on this rig.
+ * The switch belongs to the whole database: FLVIS_ERR_INVALID_ARG while any sequence holds a keyframe (allowed again once every sequence
+ * has been reset) and for a NULL closer; FLVIS_ERR_CONFIG on a closer whose cam_type is not 1.  Closers of cam_type 0 and 2 are untouched. */
+int flvis_loop_closer_set_stereo_unrect(flvis_loop_closer* lc, int enable);
 /* (destroy it before the context it was created on: every other call runs on that context's stream) */
 void flvis_loop_closer_destroy(flvis_loop_closer* lc);
 /* one keyframe for each of the n sequences h_stream[i] (distinct): d_img0 [n][h][w] mono8, d_img1 [n][h][w] mono8 (stereo) or Z16

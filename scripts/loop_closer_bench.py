@@ -24,7 +24,12 @@ OTHER maps); ms per call, the calls taken in turns; then every keyframe of seque
 n_keyframes queries, n_best = 4): ms per call and per query; a further JSON line.  With a library that has no flvis_loop_closer_link
 (FLVIS_LIB_PATH: the parent commit's) only the localize_in legs run: the same script then gives the parent's figures.
 
-usage: loop_closer_bench.py [--rigs] [--localize] [--localize-in[=all]] [--link] [n_streams=64] [n_keyframes=60] [max_keyframes]"""
+--unrect: instead of all the above, what the opt-in landmarks of an unrectified stereo rig cost (flvis_loop_closer_set_stereo_unrect): S
+sequences on the EuRoC-like rig (752 x 480), add_keyframes per call with the switch on against the switch off -- off is the same ORB and
+bag of words without landmarks, so the difference is the feature's own cost -- the two closers taken in turns on the same frames; beside
+them, as an indication only (another image size), the rectified-stereo case of the D435i rig (640 x 480) in the same turns; one JSON line.
+
+usage: loop_closer_bench.py [--rigs] [--localize] [--localize-in[=all]] [--link] [--unrect] [n_streams=64] [n_keyframes=60] [max_keyframes]"""
 import json
 import os
 import sys
@@ -55,6 +60,47 @@ PER = 50
 N_UNITS = 4
 
 ctx = flvis_amd.Context(0)
+if "--unrect" in sys.argv[1:]:
+    trs = [LC.LoopTrajectory(phase=2 * np.pi * s / S) for s in range(S)]
+    times = LC.keyframe_times(N, PER)
+    ident = np.tile(np.array([0, 0, 0, 0, 0, 0, 1.0]), (S, 1))
+    legs, frames = {}, {}
+    for name, rig, text in (("euroc", synth.euroc_rig(), synth.EUROC_LIKE_YAML), ("d435i", synth.d435_rig(), synth.D435I_STEREO_YAML)):
+        p = os.path.join(tempfile.gettempdir(), "flvis_loop_closer_bench_%s.yaml" % name)
+        open(p, "w").write(text)
+        rnd = synth.Renderer("cuda", rig=rig)
+        frames[name] = [rnd.stereo_frame(trs, t, i) for i, t in enumerate(times)]
+        legs[name] = flvis_amd.load_config(p)
+    train = []
+    for i in range(0, N, 6):
+        k, d, c, _ = ctx.orb_detect_and_compute(frames["euroc"][i][0][0:1], cap=1024)
+        train.append(d[0, :int(c[0])].cpu().numpy())
+    ctx.bow_set_vocabulary(*V.build_vocabulary(train, k=8, depth=3))
+    closers = {"unrect_off": ("euroc", flvis_amd.LoopCloser(ctx, legs["euroc"], LC.LC_PARAMS, n_streams=S, max_keyframes=MAXKF)),
+               "unrect_on": ("euroc", flvis_amd.LoopCloser(ctx, legs["euroc"], LC.LC_PARAMS, n_streams=S, max_keyframes=MAXKF)),
+               "rect_d435i": ("d435i", flvis_amd.LoopCloser(ctx, legs["d435i"], LC.LC_PARAMS, n_streams=S, max_keyframes=MAXKF))}
+    closers["unrect_on"][1].set_stereo_unrect(True)
+    ms = {k: [] for k in closers}
+    streams = list(range(S))
+    torch.cuda.synchronize()
+    for i in range(N):                                                     # the legs in turns: a drift of the clocks hits all alike
+        for k, (rig, lc) in closers.items():
+            t0 = time.perf_counter()
+            lc.add_keyframes(streams, frames[rig][i][0], frames[rig][i][1], ident)      # returns after the batch is stored (it synchronises)
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    out = {"n_streams": S, "n_keyframes": N, "image_size": {"unrect": [752, 480], "rect_d435i": [640, 480]}}
+    for k, (rig, lc) in closers.items():
+        v = np.array(ms[k][5:])                                            # (the first calls also allocate and load code objects)
+        out["add_keyframes_ms_%s" % k] = {"median": float(np.median(v)), "mean": float(v.mean()), "min": float(v.min()), "max": float(v.max())}
+        out["landmarks_per_keyframe_%s" % k] = float(np.mean([len(lc.keyframe(s, N - 1)["lm2"]) for s in range(0, S, max(1, S // 8))]))
+    d = np.array(ms["unrect_on"][5:]) - np.array(ms["unrect_off"][5:])
+    out["unrect_landmarks_cost_ms_per_call"] = {"median": float(np.median(d)), "mean": float(d.mean()), "min": float(d.min()), "max": float(d.max())}
+    out["timing"] = "host wall clock around calls that return synchronised, calls 5 .. n_keyframes - 1, the three closers in turns"
+    print(json.dumps(out))
+    for _, lc in closers.values():
+        lc.close()
+    ctx.close()
+    sys.exit(0)
 trs = [LC.LoopTrajectory(phase=2 * np.pi * s / S) for s in range(S)]
 times = LC.keyframe_times(N, PER)
 if RIGS:

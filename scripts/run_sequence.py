@@ -3,7 +3,8 @@
 (`stamp x y z qw qx qy qz`, camera pose T_w_c); with ground truth present, prints the Umeyama-aligned ATE.
 
   run_sequence.py <sequence folder> <config yaml> <out.txt> [--backend hip|cpu] [--frames N] [--local-map] [--imu-out <est.txt>]
-                  [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]]
+                  [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]
+                   [--lc-stereo-unrect]]
 
 --imu-out : rigs with an IMU: additionally the IMU-rate trajectory of F2FTracking::imu_feed's outputs (pos_w_i, q_w_i per sample) -- the
 /imu_pose topic, which is what the reference's EuRoC launch file records as est.txt (launch/flvis_euroc_mav.launch:83-103) and scores;
@@ -17,6 +18,11 @@ Comparing the two output files with flvis_amd.traj_io.ate_from_files gives the m
 files) with the vocabulary of --voc (.dbow3 / .txt / .yml[.gz]) and the lcKF* / ratio* / min* block of the yaml; the keyframe path it
 maintains (T_w_c of every keyframe, corrected by the pose graph whenever a loop closes) is written to --lc-out in the same format.
 hip: flvis_loop_closer; cpu: the same control flow assembled from the oracle's functions (tests/_loop_chain.py).
+
+--lc-stereo-unrect : unrectified stereo rigs (cam_type 1: EuRoC).  The reference's loop closing leaves their case empty -- no keyframe gets a
+landmark and no loop is ever verified, which stays the default here.  With this switch the keyframes' landmarks come from this project's
+rule: LK into the raw second image, both ends undistorted into the rectified plane, DLT (hip: flvis_loop_closer_set_stereo_unrect; cpu:
+the checker composed from the oracle's functions, tests/_lc_unrect.py).
 
 --map-cloud : (hip) the corrected map next to the corrected keyframe path: the landmarks of every keyframe in the map frame, one point per
 voxel of --leaf metres (0: every landmark, what the reference's /map_cloud carries), as ASCII PLY with the voxels' point counts
@@ -46,7 +52,10 @@ def main():
     ap.add_argument("--imu-out", default=None)
     ap.add_argument("--map-cloud", default=None)
     ap.add_argument("--leaf", type=float, default=0.08)
+    ap.add_argument("--lc-stereo-unrect", action="store_true")
     args = ap.parse_args()
+    if args.lc_stereo_unrect and not args.loop_closing:
+        ap.error("--lc-stereo-unrect needs --loop-closing")
     if args.loop_closing and not args.voc:
         ap.error("--loop-closing needs --voc <vocabulary file>")
     if args.map_cloud and not (args.loop_closing and args.backend == "hip"):
@@ -72,6 +81,11 @@ def main():
             P0, P1 = np.array(list(cfg.P0)), np.array(list(cfg.P1))
             K4 = np.array([P0[0], P0[5], P0[2], P0[6]])
             closer = LC.RefLoopCloser(K4, {k: getattr(prm, k) for k, _ in prm._fields_})
+            if args.lc_stereo_unrect:
+                if cfg.cam_type != 1:
+                    ap.error("--lc-stereo-unrect: the config's rig is not unrectified stereo (cam_type 1)")
+                import _lc_unrect as U
+                unrect_cam = U.cam_of(cfg)
         for t, i0, i1, imu in seq.frames(0, args.frames):
             for r in imu:
                 a, g = traj_io.sensor_to_flvis_imu(imu_type, r[4:7], r[1:4])
@@ -79,7 +93,12 @@ def main():
             res = trk.image(t, i0, i1)
             if closer is not None and res["new_keyframe"]:
                 k, d = O.orb_detect_and_compute(i0)
-                lm2, lm3, lmd = O.lc_keyframe_landmarks(i0, i1, cfg.cam_type, k, d, P0, P1, K4)
+                if args.lc_stereo_unrect:
+                    k, d = k[:1024], d[:1024]                                  # (the closer's keyframe capacity)
+                    f = U.check(i0, i1, k, d, unrect_cam)
+                    lm2, lm3, lmd = f["lm2"], f["lm3"], f["lmd"]
+                else:
+                    lm2, lm3, lmd = O.lc_keyframe_landmarks(i0, i1, cfg.cam_type, k, d, P0, P1, K4)
                 closer.add(dict(bow=rv.transform(d), lm2=lm2, lm3=lm3, lmd=lmd), res["pose7"])
                 lc_events.append(closer.process())
                 kf_stamps.append(t)
@@ -95,6 +114,7 @@ def main():
             traj_io.write_stamped(args.imu_out, imu_rows[:, 0], imu_rows[:, 5:8], imu_rows[:, 1:5])
         T_imu_cam = np.array(list(cfg.T_imu_cam0)).reshape(4, 4)
         kf_T_c_w = np.array(closer.T_c_w).reshape(-1, 7) if closer is not None else None
+        kf_landmarks = [len(f["lm2"]) for f in closer.kfs] if closer is not None else []
     else:
         import torch
         import flvis_amd
@@ -106,6 +126,8 @@ def main():
         if args.loop_closing:
             ctx.bow_load_vocabulary(args.voc)                                  # Vocabulary voc(path), vo_loopclosing.cpp:1097
             closer = flvis_amd.LoopCloser(ctx, cfg, flvis_amd.load_lc_params(args.config), n_streams=1, max_keyframes=max(n, 1))
+            if args.lc_stereo_unrect:
+                closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
         for t, i0, i1, imu in seq.frames(0, n):
             for r in imu:
                 trk.imu_feed_sensor(0, r[0], r[4:7], r[1:4])                   # the library applies the axis remap
@@ -122,6 +144,7 @@ def main():
         if args.imu_out and len(imu_rows):
             trk.write_imu_trajectory(imu_rows, args.imu_out)
         kf_T_c_w = closer.poses(0) if closer is not None else None
+        kf_landmarks = [len(closer.keyframe(0, i)["lm2"]) for i in range(len(kf_stamps))] if args.lc_stereo_unrect else []
         map_cloud = None
         if args.map_cloud:
             xyz, npts, n_out, n_drop = closer.map_cloud([[0]], leaf=args.leaf)
@@ -141,6 +164,8 @@ def main():
         out["loop_closing"] = {"keyframes": len(kf_stamps), "candidates": int(sum(bool(e["candidate"]) for e in lc_events)),
                                "loops_accepted": int(sum(bool(e["accepted"]) for e in lc_events)),
                                "pose_graph_runs": int(sum(bool(e["optimised"]) for e in lc_events))}
+        if args.lc_stereo_unrect:
+            out["loop_closing"]["stereo_unrect_landmarks"] = int(sum(kf_landmarks))
         if args.map_cloud:
             out["loop_closing"]["map_cloud"] = map_cloud
     if seq.groundtruth is not None and len(stamps) >= 3:
