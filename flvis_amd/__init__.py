@@ -13,6 +13,7 @@ _LIB = None
 FLVIS_OK = 0
 FLVIS_ERR_INVALID_ARG = -1
 FLVIS_ERR_NO_DEVICE = -2
+FLVIS_ERR_CAPACITY = -4
 
 
 class FlvisError(RuntimeError):
@@ -582,6 +583,77 @@ class Context:
             self._h, _ptr(p3d), _ptr(p2d), _ptr(count), cap, n, _P(K, C.c_double), int(iterations), C.c_double(reproj_px),
             C.c_double(confidence), _P(g7, C.c_double), _ptr(pose), _ptr(mask), _ptr(ninl)), "debug_pnp_ransac_iterative")
         return pose, mask, ninl
+
+    def find_fundamental_ransac(self, m1, m2, count, thr_px=5.0, confidence=0.99, mask=None, n_inliers=None):
+        """flvis_hip_find_fundamental_ransac = cv::findFundamentalMat(FM_RANSAC, thr_px, confidence) (lkorb_tracking.cpp:134), the mask only:
+        m1, m2 float32 [n,cap,2], count int32 [n] (device) -> (mask uint8 [n,cap], n_inliers int32 [n]).  mask / n_inliers: the caller's
+        output tensors (rows from a set's count on are left as they are); default: new zeroed ones."""
+        import torch
+        m1, m2 = m1.contiguous(), m2.contiguous()
+        n, cap, _ = m1.shape
+        assert m1.dtype == torch.float32 and m2.dtype == torch.float32 and m2.shape == m1.shape and count.dtype == torch.int32
+        mask = torch.zeros((n, cap), dtype=torch.uint8, device=m1.device) if mask is None else mask
+        n_inliers = torch.zeros((n,), dtype=torch.int32, device=m1.device) if n_inliers is None else n_inliers
+        assert mask.is_contiguous() and mask.shape == (n, cap) and mask.dtype == torch.uint8 and n_inliers.dtype == torch.int32
+        self._check(self._lib.flvis_hip_find_fundamental_ransac(self._h, _ptr(m1), _ptr(m2), _ptr(count), cap, n, C.c_double(thr_px),
+                                                                C.c_double(confidence), _ptr(mask), _ptr(n_inliers)),
+                    "find_fundamental_ransac")
+        return mask, n_inliers
+
+    def optimize_in_frame(self, lm_3d_w, lm_2d_undistort, lm_id, count, K4, pose7, ok=None):
+        """flvis_hip_optimize_in_frame = OptimizeInFrame::optimize (optimize_in_frame.cpp:10-91): lm_3d_w float64 [n,cap,3], lm_2d_undistort
+        float64 [n,cap,2], lm_id int64 [n,cap], count int32 [n], pose7 float64 [n,7] (device; T_c_w, updated IN PLACE where ok) ->
+        (pose7, ok uint8 [n]).  K4 [4]: one camera for every set; [n,4]: one per set."""
+        import numpy as np
+        import torch
+        lm_3d_w, lm_2d_undistort, lm_id = lm_3d_w.contiguous(), lm_2d_undistort.contiguous(), lm_id.contiguous()
+        n, cap, _ = lm_3d_w.shape
+        K = np.ascontiguousarray(K4, np.float64)
+        assert K.shape in ((4,), (n, 4)) and pose7.is_contiguous() and pose7.shape == (n, 7) and pose7.dtype == torch.float64
+        assert lm_3d_w.dtype == torch.float64 and lm_2d_undistort.dtype == torch.float64 and lm_id.dtype == torch.int64
+        assert lm_2d_undistort.shape == (n, cap, 2) and lm_id.shape == (n, cap) and count.dtype == torch.int32
+        ok = torch.zeros((n,), dtype=torch.uint8, device=lm_3d_w.device) if ok is None else ok
+        self._check(self._lib.flvis_hip_optimize_in_frame(self._h, _ptr(lm_3d_w), _ptr(lm_2d_undistort), _ptr(lm_id), _ptr(count), cap, n,
+                                                          _P(K, C.c_double), 1 if K.ndim == 1 else n, _ptr(pose7), _ptr(ok)),
+                    "optimize_in_frame")
+        return pose7, ok
+
+    def undistort_points(self, src, count, K4, D4, R, P, dst=None):
+        """flvis_hip_undistort_points = cv::undistortPoints(src, dst, K, D, R, P): src float32 [n,cap,2], count int32 [n] (device) -> dst
+        float32 [n,cap,2] (the caller's, or a new zeroed one).  K4 [4] / D4 [4] / R [3,3] / P [3,4]: one camera; with a leading [n]: one
+        per set."""
+        import numpy as np
+        import torch
+        src = src.contiguous()
+        n, cap, _ = src.shape
+        K, D = np.ascontiguousarray(K4, np.float64), np.ascontiguousarray(D4, np.float64)
+        R, P = np.ascontiguousarray(R, np.float64), np.ascontiguousarray(P, np.float64)
+        n_cam = 1 if K.ndim == 1 else n
+        assert K.size == 4 * n_cam and D.size == 4 * n_cam and R.size == 9 * n_cam and P.size == 12 * n_cam
+        assert src.dtype == torch.float32 and count.dtype == torch.int32
+        dst = torch.zeros_like(src) if dst is None else dst
+        assert dst.is_contiguous() and dst.shape == src.shape and dst.dtype == torch.float32
+        self._check(self._lib.flvis_hip_undistort_points(self._h, _ptr(src), _ptr(count), cap, n, _P(K, C.c_double), _P(D, C.c_double),
+                                                         _P(R, C.c_double), _P(P, C.c_double), n_cam, _ptr(dst)), "undistort_points")
+        return dst
+
+    def project_points(self, p3d, count, pose7, K4, D4, dst=None):
+        """flvis_hip_project_points = cv::projectPoints: p3d float32 [n,cap,3], count int32 [n] (device), pose7 float64 [n,7] (host: the pose
+        each set is projected with) -> dst float32 [n,cap,2] (the caller's, or a new zeroed one).  K4 / D4 [4]: one camera; [n,4]: one per set."""
+        import numpy as np
+        import torch
+        p3d = p3d.contiguous()
+        n, cap, _ = p3d.shape
+        K, D = np.ascontiguousarray(K4, np.float64), np.ascontiguousarray(D4, np.float64)
+        T = np.ascontiguousarray(pose7, np.float64)
+        n_cam = 1 if K.ndim == 1 else n
+        assert K.size == 4 * n_cam and D.size == 4 * n_cam and T.shape == (n, 7)
+        assert p3d.dtype == torch.float32 and count.dtype == torch.int32
+        dst = torch.zeros((n, cap, 2), dtype=torch.float32, device=p3d.device) if dst is None else dst
+        assert dst.is_contiguous() and dst.shape == (n, cap, 2) and dst.dtype == torch.float32
+        self._check(self._lib.flvis_hip_project_points(self._h, _ptr(p3d), _ptr(count), cap, n, _P(T, C.c_double), _P(K, C.c_double),
+                                                       _P(D, C.c_double), n_cam, _ptr(dst)), "project_points")
+        return dst
 
     def debug_epnp(self, p3d, p2d, count, K4):
         """flvis_hip_debug_epnp: EPnP alone on correspondence sets (p3d float32 [n,cap,3], p2d float32 [n,cap,2], count int32 [n], device)

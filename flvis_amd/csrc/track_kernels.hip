@@ -547,25 +547,51 @@ __device__ unsigned long long g_f_rng7[F_TAB_N][F_TAB_B];
 #define FLVIS_RF_T 1024
 #endif
 constexpr int RF_T = FLVIS_RF_T;  // (A/B knob: 256 or 512 threads leave room for the detection stream's waves on the workgroup's CU)
-template <bool COLLECT>
-__device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
-  chain_priority();
+// One body for the tracker's kernels (k_ransac_f / k_collect_ransac_f) and the call on caller arrays (k_fund_ransac_sets,
+// flvis_hip_find_fundamental_ransac).  What differs between them -- where the correspondences come from, threshold and confidence, where
+// the winning mask goes, OpenCV's dispatch below eight points -- is chosen by the compile-time SETS: the tracker's instantiations keep
+// their own prologue (the collect, the stream's state) and epilogue (the mirrored-index write into to[i].inlier, f_cnt, st.ok) and the
+// literals 5.0 / 0.99, and compile to the instruction stream they had before the call existed (a core function with the prologue and
+// epilogue handed in as functors was tried first: same arithmetic, but another register allocation with 50 more scratch reloads, and
+// 0.7 % of the tracker's frame rate).
+struct FundSets {  // the arguments of k_fund_ransac_sets; unused (and empty) in the tracker's instantiations
+  const float* m1;   // [n_sets][cap][2]
+  const float* m2;
+  const int* count;  // [n_sets], clamped to 0 .. cap
+  int cap;           // <= NMAX
+  double thr_px, confidence;
+  unsigned char* mask;  // [n_sets][cap]: rows below the count are written
+  int* n_inliers;       // [n_sets]
+};
+template <bool COLLECT, bool SETS>
+__device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a) {
+  if (!SETS) chain_priority();
   const int s = blockIdx.x;
-  StreamState& st = p.st[s];
-  if (COLLECT) {  // k_track_collect's work as this launch's prologue: the survivors, m1 / m2, the stream's counts
-    __shared__ int s_cnt[NMAX / 64 + 1];
-    track_collect_dev<RF_T>(p, s, s_cnt);
-    __syncthreads();  // (workgroup scope: what thread 0 and the copying lanes stored is what everybody reads below)
+  StreamState* const stp = SETS ? nullptr : p.st + s;
+  if (!SETS) {
+    if (COLLECT) {  // k_track_collect's work as this launch's prologue: the survivors, m1 / m2, the stream's counts
+      __shared__ int s_cnt[NMAX / 64 + 1];
+      track_collect_dev<RF_T>(p, s, s_cnt);
+      __syncthreads();  // (workgroup scope: what thread 0 and the copying lanes stored is what everybody reads below)
+    }
+    if (stp->phase != PH_TRACK || !stp->ok) return;
   }
-  if (st.phase != PH_TRACK || !st.ok) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #ifdef FLVIS_RANSAC_PROF
   long long tlast_ = (long long)wall_clock64();
   long long tlast2_ = tlast_;
   if (tid == 0 && p.counters) atomicAdd((unsigned long long*)&p.counters[24 + 7], 1ull);
 #endif
-  const int n = st.n_surv;
+  int n_ = 0;
+  if (SETS) {
+    n_ = a.count[s];
+    n_ = n_ < 0 ? 0 : (n_ > a.cap ? a.cap : n_);
+  } else {
+    n_ = stp->n_surv;
+  }
+  const int n = n_;
   __shared__ float sm1[NMAX * 2], sm2[NMAX * 2];
+  __shared__ unsigned char smask[SETS ? NMAX : 1];  // the winning mask of a caller's set
   __shared__ double Fm[64 * 3][9];
 #ifdef FLVIS_SOLVERS_PRODUCT
   __shared__ double spw[63 * 64];  // 7-point workspaces of the 64 hypothesis lanes (element-major: conflict-free)
@@ -583,8 +609,8 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
   __shared__ int s_sub[64][8];  // the batch's subsets (7 indices each)
   __shared__ double bestF[9];
   __shared__ int ctl[4];  // niters, maxGood, best_iter, best_model
-  const float* gm1 = p.m1 + (size_t)s * NMAX * 2;
-  const float* gm2 = p.m2 + (size_t)s * NMAX * 2;
+  const float* gm1 = SETS ? a.m1 + (size_t)s * a.cap * 2 : p.m1 + (size_t)s * NMAX * 2;
+  const float* gm2 = SETS ? a.m2 + (size_t)s * a.cap * 2 : p.m2 + (size_t)s * NMAX * 2;
   for (int i = tid; i < 2 * n; i += RF_T) {
     sm1[i] = gm1[i];
     sm2[i] = gm2[i];
@@ -596,8 +622,11 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
     ctl[3] = 0;
   }
   __syncthreads();
-  const float thr2 = 25.0f;
-  Landmark* to = lm_ptr(p, st.cur, s);
+  const float thr2 = SETS ? (float)(a.thr_px * a.thr_px) : 25.0f;
+  const double confidence = SETS ? a.confidence : 0.99;
+  Landmark* to = SETS ? nullptr : lm_ptr(p, stp->cur, s);
+  // (where the mask goes: the tracker applies it with the reference's mirrored index -- mask index i to to.landmarks[i] (descending
+  // order): quirk A1; a caller's set gets it through smask)
   RPROF(24, 0);
   CvRng rng = cv_rng_init();  // RNG rng((uint64)-1) of RANSACPointSetRegistrator::run / LMeDSPointSetRegistrator::run
   const ModC mc = mod_c_make((uint32_t)(n > 0 ? n : 1));
@@ -697,13 +726,15 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
-  if (n > 7 && n < 15) {
+  if (SETS && n <= 7) {  // OpenCV's dispatch below eight points (the tracker never gets here): < 7 nothing, exactly 7 all points kept
+    for (int i = tid; i < n; i += RF_T) smask[i] = n == 7 ? 1 : 0;
+  } else if (n > 7 && n < 15) {
     // ---- LMeDSPointSetRegistrator::run: max(RANSACUpdateNumIters(0.99, 0.45, 7, 1000), 3) subsets, the model with the smallest
     // median error wins, the inliers are the points within sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median) (>= 0.001) of it.
     // n <= 14: a lane scores its own models (errors, insertion sort, median); thread 0 replays the running minimum in order.
     __shared__ double s_med[64 * 3];
     __shared__ double s_lm[2];
-    int niters = ransac_update_num_iters(0.99, 0.45, 7, 1000);
+    int niters = ransac_update_num_iters(confidence, 0.45, 7, 1000);
     niters = niters > 3 ? niters : 3;
     if (tid == 0) {
       s_lm[0] = 1.7976931348623157e308;  // minMedian
@@ -854,10 +885,14 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
       const float tl = (float)(sigma * sigma);
       for (int i = tid; i < n; i += RF_T) {
         bool in = f_error(bestF, sm1[2 * i], sm1[2 * i + 1], sm2[2 * i], sm2[2 * i + 1]) <= tl;
-        if (!in) to[i].inlier = 0;  // mask index i applied to to.landmarks[i] (descending order): quirk A1
+        if (SETS) smask[i] = in ? 1 : 0;
+        else if (!in) to[i].inlier = 0;
       }
     } else {
-      for (int i = tid; i < n; i += RF_T) to[i].inlier = 0;
+      for (int i = tid; i < n; i += RF_T) {
+        if (SETS) smask[i] = 0;
+        else to[i].inlier = 0;
+      }
     }
   } else if (n > 7) {
     for (int base = 0, B = 16; base < ctl[0]; base += B, B = 64) {
@@ -1058,7 +1093,7 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
               ctl[2] = base + k;
               ctl[3] = hmodel[k];
               for (int j = 0; j < 9; j++) bestF[j] = Fm[k * 3 + hmodel[k]][j];
-              niters = ransac_update_num_iters(0.99, (double)(n - good) / n, 7, niters);
+              niters = ransac_update_num_iters(confidence, (double)(n - good) / n, 7, niters);
             }
           }
           ctl[0] = niters;
@@ -1068,37 +1103,63 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p) {
       }
       RPROF(24, 3);
     }
-    // apply the winning model's mask with the reference's mirrored index
+    // the winning model's mask
     if (ctl[2] >= 0) {
       for (int i = tid; i < n; i += RF_T) {
         bool in = f_error(bestF, sm1[2 * i], sm1[2 * i + 1], sm2[2 * i], sm2[2 * i + 1]) <= thr2;
-        if (!in) to[i].inlier = 0;  // mask index i applied to to.landmarks[i] (descending order): quirk A1
+        if (SETS) smask[i] = in ? 1 : 0;
+        else if (!in) to[i].inlier = 0;
       }
     } else {
-      for (int i = tid; i < n; i += RF_T) to[i].inlier = 0;  // no model: all-zero mask
+      for (int i = tid; i < n; i += RF_T) {  // no model: all-zero mask
+        if (SETS) smask[i] = 0;
+        else to[i].inlier = 0;
+      }
     }
   }
   __syncthreads();
-  if (wv == 0) {
+  if (SETS) {
+    unsigned char* const gm = a.mask + (size_t)s * a.cap;
+    for (int i = tid; i < n; i += RF_T) gm[i] = smask[i];
+    if (wv == 0) {
+      int c = 0;
+      for (int i = lane; i < n; i += 64) c += smask[i];
+      c = wave_sum_i32(c);
+      if (lane == 0) a.n_inliers[s] = c;
+    }
+  } else if (wv == 0) {
     int fc = 0;
     for (int i = lane; i < n; i += 64) fc += to[i].inlier ? 1 : 0;
     fc = wave_sum_i32(fc);
     if (lane == 0) {
-      st.f_cnt = fc;
-      if (fc < 10) st.ok = 0;
+      stp->f_cnt = fc;
+      if (fc < 10) stp->ok = 0;
     }
   }
   RPROF(24, 4);
 }
 __global__ __launch_bounds__(RF_T) void k_ransac_f(Pipe p) {
   kj_wait(p.kj);
-  k_ransac_f_body<false>(p);
+  k_ransac_f_body<false, false>(p, FundSets{});
   kj_signal(p.kj);
 }
 __global__ __launch_bounds__(RF_T) void k_collect_ransac_f(Pipe p) {
   kj_wait(p.kj);
-  k_ransac_f_body<true>(p);
+  k_ransac_f_body<true, false>(p, FundSets{});
   kj_signal(p.kj);
+}
+
+// The same search on caller arrays (flvis_hip_find_fundamental_ransac): cv::findFundamentalMat(m1, m2, FM_RANSAC, thr_px, confidence,
+// mask) for n_sets independent correspondence sets, one workgroup per set.  m1 / m2 [n_sets][cap][2], count [n_sets] (clamped to
+// 0 .. cap; cap <= NMAX is the caller's check), mask [n_sets][cap]: rows below the count are written, the others are left alone;
+// n_inliers [n_sets] the ones of each mask.  k_ransac_f_body's SETS instantiation: the tracker's search, and on top of it OpenCV's
+// dispatch below eight points, which the tracker never meets -- fewer than 7 give an all-zero mask, exactly 7 all ones (the 7-point
+// solver alone; the reference discards its matrices).
+__global__ __launch_bounds__(RF_T) void k_fund_ransac_sets(const float* __restrict__ m1, const float* __restrict__ m2,
+                                                           const int* __restrict__ count, int cap, double thr_px, double confidence,
+                                                           unsigned char* __restrict__ mask, int* __restrict__ n_inliers) {
+  const Pipe none{};  // (the body reads no field of it in this instantiation but, in a profile build, the null `counters`)
+  k_ransac_f_body<false, true>(none, FundSets{m1, m2, count, cap, thr_px, confidence, mask, n_inliers});
 }
 
 // ------------------------------------------------------------------------------------------------ PnP RANSAC
@@ -2201,6 +2262,71 @@ __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
 #endif
 }
 
+// OptimizeInFrame::optimize on caller arrays (flvis_hip_optimize_in_frame), one workgroup per set: the arrays getValidInliersPair hands
+// the reference -- lm3d [n_sets][cap][3] world points, lm2d [n_sets][cap][2] undistorted pixels, lm_id [n_sets][cap] -- and pose7
+// [n_sets][7] (T_c_w, in / out); count clamped to 0 .. cap (cap <= PL_EMAX is the caller's check).  K: set b's fx fy cx cy at
+// K4 + k_stride * b (k_stride 0: one camera).  ok[b] = 1 and the optimised pose, or ok[b] = 0 and the pose untouched (fewer than 10
+// edges, before or after the chi2 cull).  The tracker's own ids are unique; a caller's need not be: the active-edge order is ascending
+// id with equal ids in input order (the checker's std::stable_sort), so the rank counts (id, index) pairs.
+__global__ __launch_bounds__(PL_T) void k_pose_lm_sets(const double* __restrict__ lm3d, const double* __restrict__ lm2d,
+                                                       const long long* __restrict__ lm_id, const int* __restrict__ count, int cap,
+                                                       const double* __restrict__ K4, int k_stride, double* __restrict__ pose7,
+                                                       unsigned char* __restrict__ okflag) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  PoseLMShared& sh = *reinterpret_cast<PoseLMShared*>(pl_smem);
+  long long* ids = reinterpret_cast<long long*>(sh.terms);
+  int n = count[b];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  bool ok = n >= 10;
+  if (ok) {  // (n is workgroup-uniform: so are the barriers below)
+    const long long* const gid = lm_id + (size_t)b * cap;
+    const double* const P = lm3d + (size_t)b * cap * 3;
+    const double* const Z = lm2d + (size_t)b * cap * 2;
+    for (int k = tid; k < n; k += PL_T) ids[k] = gid[k];
+    __syncthreads();
+    for (int k = tid; k < n; k += PL_T) {
+      const long long id = ids[k];
+      int rank = 0;
+      for (int j = 0; j < n; j++) rank += (ids[j] < id) || (ids[j] == id && j < k);
+      sh.pw[0][rank] = P[3 * k];
+      sh.pw[1][rank] = P[3 * k + 1];
+      sh.pw[2][rank] = P[3 * k + 2];
+      sh.zu[rank] = Z[2 * k];
+      sh.zv[rank] = Z[2 * k + 1];
+      sh.alive[rank] = 1;
+    }
+    __syncthreads();
+    const double* const k4 = K4 + (size_t)k_stride * b;
+    const double fx = k4[0], fy = k4[1], cx = k4[2], cy = k4[3];
+    const SE3d T0 = load_pose7(pose7 + 7 * b);
+    SE3d T = g2o_from_mat(q_to_mat(T0.q), T0.t);
+    pose_lm_optimize(T, sh, n, 2, fx, fy, cx, cy);
+    __shared__ int s_alive[PL_T / 64];
+    int alive = 0;
+    for (int base = 0; base < n; base += PL_T) {
+      const int e = base + tid;
+      bool keep = false;
+      if (e < n) {
+        double er[2];
+        proj_edge(T, V3{sh.pw[0][e], sh.pw[1][e], sh.pw[2][e]}, sh.zu[e], sh.zv[e], fx, fy, cx, cy, er, nullptr);
+        keep = !(er[0] * er[0] + er[1] * er[1] > 3.0);
+        if (!keep) sh.alive[e] = 0;
+      }
+      int tot;
+      block_rank<PL_T / 64>(keep, s_alive, tot);
+      alive += tot;
+    }
+    __syncthreads();
+    if (alive < 10) {
+      ok = false;
+    } else {
+      pose_lm_optimize(T, sh, n, 2, fx, fy, cx, cy);
+      if (tid == 0) store_pose7(pose7 + 7 * b, se3_from_mat(q_to_mat(T.q), T.t));
+    }
+  }
+  if (tid == 0) okflag[b] = ok ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------ reprojection filter
 // calReprjInlierOutlier(1.5) + eraseReprjOutlier + viCorrectionFromVision; prepares the redetect inputs.
 // One workgroup of NMAX threads per stream, one landmark per thread.
@@ -2932,8 +3058,23 @@ void launch_pnp_ransac_sets(hipStream_t st, const float* p3d, const float* p2d, 
   hipLaunchKernelGGL(k_pnp_ransac_sets, dim3(n_sets), dim3(RP_T), 0, st, p3d, p2d, count, cap, K4[0], K4[1], K4[2], K4[3], d_cams, cam_stride,
                      d_cam_of, iterative, guess7, seeds, max_iters, (float)(reproj_px * reproj_px), conf, pose7, mask, n_inliers);
 }
+void launch_fund_ransac_sets(hipStream_t st, const float* m1, const float* m2, const int* count, int cap, int n_sets, double thr_px,
+                             double conf, unsigned char* mask, int* n_inliers) {
+  (void)pnp_tables_init();  // (g_f_sub7: a context without a tracker has no tables otherwise)
+  hipLaunchKernelGGL(k_fund_ransac_sets, dim3(n_sets), dim3(RF_T), 0, st, m1, m2, count, cap, thr_px, conf, mask, n_inliers);
+}
+int fund_ransac_max_points() { return NMAX; }
 void launch_track_post(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_track_post, dim3((p.S + 63) / 64), dim3(64), 0, st, p);
+}
+int pose_lm_max_edges() { return PL_EMAX; }
+hipError_t launch_pose_lm_sets(hipStream_t st, const double* lm3d, const double* lm2d, const long long* lm_id, const int* count, int cap,
+                               int n_sets, const double* d_K4, int k_stride, double* pose7, unsigned char* ok) {
+  // (a context without a tracker has not gone through track_kernels_init)
+  const hipError_t e = hipFuncSetAttribute((const void*)k_pose_lm_sets, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PoseLMShared));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pose_lm_sets, dim3(n_sets), dim3(PL_T), sizeof(PoseLMShared), st, lm3d, lm2d, lm_id, count, cap, d_K4, k_stride, pose7, ok);
+  return hipSuccess;
 }
 void launch_pose_lm(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_pose_lm, dim3(p.S), dim3(PL_T), sizeof(PoseLMShared), st, p); }
 // the tabulated first batches of the PnP RANSAC (see g_pnp_sub5): once per device, before the first launch that reads them

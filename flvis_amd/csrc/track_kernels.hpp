@@ -139,6 +139,21 @@ void launch_pnp_ransac_sets(hipStream_t st, const float* p3d, const float* p2d, 
                             const double* d_cams, int cam_stride, const int* d_cam_of, int iterative, const double* guess7,
                             const unsigned long long* seeds, int max_iters, double reproj_px, double conf, double* pose7, unsigned char* mask,
                             int* n_inliers);
+// cv::findFundamentalMat(FM_RANSAC) on caller arrays (one workgroup per set; cap <= fund_ransac_max_points())
+int fund_ransac_max_points();
+void launch_fund_ransac_sets(hipStream_t st, const float* m1, const float* m2, const int* count, int cap, int n_sets, double thr_px,
+                             double conf, unsigned char* mask, int* n_inliers);
+// OptimizeInFrame::optimize on caller arrays (one workgroup per set; cap <= pose_lm_max_edges()); set b's camera at d_K4 + k_stride * b
+int pose_lm_max_edges();
+hipError_t launch_pose_lm_sets(hipStream_t st, const double* lm3d, const double* lm2d, const long long* lm_id, const int* count, int cap,
+                               int n_sets, const double* d_K4, int k_stride, double* pose7, unsigned char* ok);
+// cv::undistortPoints / cv::projectPoints on caller arrays (geom_calls.hip), one thread per point; d_cam: [n_cam][GEOM_CAM_N] doubles
+// K (4) D (4) R (9) P (12), cam_stride GEOM_CAM_N or 0 (one camera); d_pose7 [n_sets][7]
+constexpr int GEOM_CAM_N = 29;
+void launch_undistort_points_sets(hipStream_t st, const float* src, const int* count, int cap, int n_sets, const double* d_cam, int cam_stride,
+                                  float* dst);
+void launch_project_points_sets(hipStream_t st, const float* p3d, const int* count, int cap, int n_sets, const double* d_pose7,
+                                const double* d_cam, int cam_stride, float* dst);
 void launch_store_progress(hipStream_t st, long long* host_word, long long v);  // stream-ordered store into host-mapped memory
 void launch_store_flag(hipStream_t st, long long* word, long long v);  // stream-ordered store of a sequence number into a device word
 void launch_wait_flag(hipStream_t st, const long long* flag, int n_words, long long seq, long long* err_word);  // stream-ordered wait for an upload's sequence block

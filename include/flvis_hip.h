@@ -13,6 +13,11 @@
  *   flvis_hip_lk_track           <- cv::calcOpticalFlowPyrLK    src/processing/lkorb_tracking.cpp:64-73,
  *                                                               src/processing/camera_frame.cpp:124-128
  *   flvis_hip_gftt               <- cv::goodFeaturesToTrack     src/processing/feature_dem.cpp:160,221
+ *   flvis_hip_find_fundamental_ransac <- cv::findFundamentalMat(FM_RANSAC, 5.0, 0.99)   src/processing/lkorb_tracking.cpp:134
+ *   flvis_hip_optimize_in_frame  <- OptimizeInFrame::optimize   src/processing/optimize_in_frame.cpp:10-91 (lkorb_tracking.cpp:199)
+ *   flvis_hip_undistort_points   <- cv::undistortPoints(K, D, R, P)   src/processing/lkorb_tracking.cpp:87, src/frontend/f2f_tracking.cpp:301,425,
+ *                                                               src/processing/camera_frame.cpp:130
+ *   flvis_hip_project_points     <- cv::projectPoints           src/processing/lkorb_tracking.cpp:58, src/processing/camera_frame.cpp:116
  *   flvis_hip_feature_dem_detect / _redetect <- FeatureDEM::detect / ::redetect   src/processing/feature_dem.cpp:124-266
  *                                              (include/feature_dem.h:40-50)
  *   flvis_hip_orb_detect_and_compute / _hamming_knn2 / _orb_match  <- cv::ORB, cv::BFMatcher   src/backend/vo_loopclosing.cpp:242-243,601-639
@@ -331,6 +336,38 @@ int flvis_hip_debug_epnp(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d,
 int flvis_hip_debug_pnp_ransac_iterative(flvis_ctx* ctx, const float* d_p3d, const float* d_p2d, const int* d_count, int cap, int n_sets,
                                          const double* h_K4, int iterations, double reproj_px, double confidence,
                                          const double* h_guess7 /* [n_sets][7] */, double* d_pose7, uint8_t* d_inlier_mask, int* d_n_inliers);
+/* ---- the solver calls of LKORBTracking::tracking (lkorb_tracking.cpp:9-202) and OptimizeInFrame::optimize on caller arrays ----
+ * Common to the four calls below: they are batched over n_sets independent sets (a set is one frame, as in flvis_hip_stereo_depth), arrays
+ * are [n_sets][cap]..., and they work on the context's stream.  d_count [n_sets]: a count above cap reads as cap, a negative one as 0;
+ * rows from the count on are never written.  Argument errors (a null pointer, cap <= 0, n_sets <= 0, what each call names) are refused
+ * before anything is launched or written.  The host arrays may be freed when the call returns.
+ *
+ * cv::findFundamentalMat(m1, m2, FM_RANSAC, thr_px, confidence, mask) (lkorb_tracking.cpp:134: 5.0, 0.99) -- the mask only, which is
+ * all the reference uses.  d_m1 / d_m2 [n_sets][cap][2] float (cv::Point2f), d_mask [n_sets][cap], d_n_inliers [n_sets] = the ones of
+ * each set's mask.  OpenCV's dispatch: fewer than 7 points give an all-zero mask, exactly 7 all ones, 8 .. 14 the LMedS registrator, from
+ * 15 on the RANSAC registrator (1000 iterations at most); both draw their 7-point subsets from cv::RNG((uint64)-1) in getSubset's order
+ * with FMEstimatorCallback::checkSubset, so a set's mask is a function of its points alone.  The tracker's own search on caller arrays.
+ * FLVIS_ERR_CAPACITY for cap > 1024; FLVIS_ERR_INVALID_ARG for thr_px <= 0 or confidence outside (0, 1). */
+int flvis_hip_find_fundamental_ransac(flvis_ctx* ctx, const float* d_m1, const float* d_m2, const int* d_count, int cap, int n_sets,
+                                      double thr_px, double confidence, uint8_t* d_mask, int* d_n_inliers);
+/* OptimizeInFrame::optimize (optimize_in_frame.cpp:10-91): g2o Levenberg on one free pose over EdgeSE3ProjectXYZOnlyPose edges with
+ * Huber(1).  Inputs are the arrays getValidInliersPair hands the reference: d_lm_3d_w [n_sets][cap][3], d_lm_2d_undistort [n_sets][cap][2],
+ * d_lm_id [n_sets][cap] (the edge ids); h_K4 fx fy cx cy, [n_K][4] with n_K = 1 (every set) or n_sets (one camera per set); d_pose7
+ * [n_sets][7] T_c_w as tx ty tz qx qy qz qw, in / out; d_ok [n_sets].  Fewer than 10 edges: ok = 0, the pose untouched.  Otherwise the
+ * active edges are taken in ascending id, equal ids in input order; two iterations; edges with chi2 > 3 are dropped; fewer than 10 left:
+ * ok = 0, the pose untouched; two more iterations, the pose written, ok = 1.
+ * FLVIS_ERR_CAPACITY for cap > 512 (the batched tracker truncates a frame there; a call refuses). */
+int flvis_hip_optimize_in_frame(flvis_ctx* ctx, const double* d_lm_3d_w, const double* d_lm_2d_undistort, const int64_t* d_lm_id,
+                                const int* d_count, int cap, int n_sets, const double* h_K4, int n_K /* 1 or n_sets */,
+                                double* d_pose7 /* in/out */, uint8_t* d_ok);
+/* cv::undistortPoints(src, dst, K, D, R, P) (k1 k2 p1 p2, five iterations) and cv::projectPoints(p3d, rvec(T), tvec(T), K, D, dst), one
+ * thread per point: d_src / d_dst [n_sets][cap][2] float, d_p3d [n_sets][cap][3] float.  h_K4 / h_D4 / h_R9 / h_P12 (row-major 3x3 and
+ * 3x4): [n_cam][...] with n_cam = 1 (every set) or n_sets; h_pose7 [n_sets][7] (tx ty tz qx qy qz qw) the pose each set is projected with.
+ * A point at z = 0 is projected with 1 / z taken as 1, as OpenCV does.  n_sets <= 65535. */
+int flvis_hip_undistort_points(flvis_ctx* ctx, const float* d_src, const int* d_count, int cap, int n_sets, const double* h_K4,
+                               const double* h_D4, const double* h_R9, const double* h_P12, int n_cam /* 1 or n_sets */, float* d_dst);
+int flvis_hip_project_points(flvis_ctx* ctx, const float* d_p3d, const int* d_count, int cap, int n_sets,
+                             const double* h_pose7 /* [n_sets][7] */, const double* h_K4, const double* h_D4, int n_cam, float* d_dst);
 /* loopClosureOnCovGraphG2ONew (vo_loopclosing.cpp:742-944) for n_graphs independent sequences in one launch (one workgroup per
  * pose graph): graph g has h_n_kf[g] keyframes with T_c_w (device, 7 doubles each: tx ty tz qx qy qz qw, graphs concatenated, in/out)
  * and presence flags (host, concatenated; 0 = kf_map_lc[i] == nullptr), h_n_loops[g] recorded loops (host ids: earlier, later
