@@ -14,6 +14,7 @@ FLVIS_OK = 0
 FLVIS_ERR_INVALID_ARG = -1
 FLVIS_ERR_NO_DEVICE = -2
 FLVIS_ERR_CAPACITY = -4
+FLVIS_ERR_CONFIG = -5
 
 
 class FlvisError(RuntimeError):
@@ -197,6 +198,46 @@ class Context:
                                                      T.ctypes.data, C.c_float(rng), _ptr(rand_state), _ptr(out), _ptr(mask)),
                     "stereo_depth")
         return out, mask
+
+    def lkorb_tracking(self, cfg, img_from, img_to, from_2d_plane, from_2d_undistort, from_3d_w, from_flags, count, guess7=None,
+                       use_guess=None, pose7=None, out=None):
+        """flvis_hip_lkorb_tracking = LKORBTracking::tracking (lkorb_tracking.cpp:9-202) for n_sets frames in one call, on any cam_type.
+        img_from / img_to uint8 [n,h,w]; from_2d_* float32 [n,cap,2]; from_3d_w float32 [n,cap,3]; from_flags uint8 [n,cap] (bit 0 has_3d,
+        bit 1 is_tracking_inlier); count int32 [n] (all on the device); guess7 host [n,7] (tx ty tz qx qy qz qw) and use_guess host [n],
+        or None: no set has a guess.  pose7: float64 [n,7] on the device, in / out (None: a new tensor of identities); only the sets that
+        reach the PnP write theirs.  out: a dict of the caller's own output tensors (any of to_from int32 [n,cap], to_2d_plane /
+        to_2d_undistort float32 [n,cap,2], to_flags uint8 [n,cap], mask_F uint8 [n,cap], counts4 int32 [n,4], ret uint8 [n]); the call
+        writes the rows below each set's of_inlier_cnt and no other; what is missing is created zero-filled.
+        Returns the dict of the outputs, with "pose7"."""
+        import numpy as np
+        import torch
+        n, cap = from_2d_plane.shape[0], from_2d_plane.shape[1]
+        for a, dt in ((img_from, torch.uint8), (img_to, torch.uint8), (from_2d_plane, torch.float32), (from_2d_undistort, torch.float32),
+                      (from_3d_w, torch.float32), (from_flags, torch.uint8), (count, torch.int32)):
+            assert a.is_cuda and a.is_contiguous() and a.dtype == dt
+        assert tuple(img_from.shape) == tuple(img_to.shape) == (n, cfg.image_height, cfg.image_width)
+        g = None if guess7 is None else np.ascontiguousarray(guess7, np.float64).reshape(n, 7)
+        u = None if use_guess is None else np.ascontiguousarray(use_guess, np.uint8).reshape(n)
+        if pose7 is None:
+            pose7 = torch.zeros((n, 7), dtype=torch.float64, device=self.device)
+            pose7[:, 6] = 1.0
+        o = dict(out or {})
+        spec = (("to_from", torch.int32, (n, cap)), ("to_2d_plane", torch.float32, (n, cap, 2)), ("to_2d_undistort", torch.float32, (n, cap, 2)),
+                ("to_flags", torch.uint8, (n, cap)), ("mask_F", torch.uint8, (n, cap)), ("counts4", torch.int32, (n, 4)), ("ret", torch.uint8, (n,)))
+        for name, dt, shape in spec:
+            if o.get(name) is None:
+                o[name] = torch.zeros(shape, dtype=dt, device=self.device)
+            t = o[name]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape, name
+        assert pose7.is_cuda and pose7.is_contiguous() and pose7.dtype == torch.float64 and tuple(pose7.shape) == (n, 7)
+        o["pose7"] = pose7
+        f = self._lib.flvis_hip_lkorb_tracking
+        f.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10
+        self._check(f(self._h, C.byref(cfg), _ptr(img_from), _ptr(img_to), n, _ptr(from_2d_plane), _ptr(from_2d_undistort), _ptr(from_3d_w),
+                      _ptr(from_flags), _ptr(count), cap, None if g is None else g.ctypes.data, None if u is None else u.ctypes.data,
+                      _ptr(o["to_from"]), _ptr(o["to_2d_plane"]), _ptr(o["to_2d_undistort"]), _ptr(o["to_flags"]), _ptr(o["mask_F"]),
+                      _ptr(o["counts4"]), _ptr(pose7), _ptr(o["ret"])), "lkorb_tracking")
+        return o
 
     def gftt(self, img, max_corners, quality, min_distance):
         import torch

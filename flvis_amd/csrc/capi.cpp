@@ -39,6 +39,61 @@ void* flvis_ctx::scratch(const std::string& name, size_t bytes, bool zero_on_all
     if (e__ != hipSuccess) return (ctx)->hip_fail(e__, what);    \
   } while (0)
 
+// (shared with tracking_call.hip: ctx.hpp)
+int flvis::lk_pyr_levels(int w, int h, int win, int max_level) {
+  int level = 0;
+  for (; level <= max_level; ++level) {
+    w = (w + 1) / 2;
+    h = (h + 1) / 2;
+    if (w <= win || h <= win) return level;
+  }
+  return max_level;
+}
+
+// builds levels 1..L of `img` ([n][h][w]) into scratch `name`, fills `pyr`
+int flvis::build_pyramid(flvis_ctx* ctx, const char* name, const uint8_t* d_img, int w, int h, int n_img, int L, PyrSel& pyr) {
+  pyr.levels = L;
+  pyr.lvl[0] = img_plain(d_img);
+  pyr.w[0] = w;
+  pyr.h[0] = h;
+  pyr.pitch[0] = w;
+  pyr.stride[0] = (size_t)w * h;
+  if (w & 3) {
+    // rows that are not dword aligned (KITTI's 1241 x 376, tightly packed): level 0 is copied into a pitch-aligned buffer first, as
+    // the tracker's ingest does
+    const int pitch0 = align_up(w, 16);
+    const size_t stride0 = (size_t)pitch0 * h;
+    uint8_t* l0 = (uint8_t*)ctx->scratch(std::string(name) + "_l0", stride0 * n_img + 256);
+    if (!l0) return ctx->fail(FLVIS_ERR_HIP, "pyramid scratch allocation failed");
+    launch_copy_image_any(ctx->stream, img_plain(d_img), img_plain(l0), w, h, w, pitch0, (size_t)w * h, stride0, n_img, nullptr);
+    pyr.lvl[0] = img_plain(l0);
+    pyr.pitch[0] = pitch0;
+    pyr.stride[0] = stride0;
+  }
+  size_t total = 0;
+  size_t off[LK_MAX_LEVELS] = {0};
+  int lw = w, lh = h;
+  for (int l = 1; l <= L; l++) {
+    lw = (lw + 1) / 2;
+    lh = (lh + 1) / 2;
+    pyr.w[l] = lw;
+    pyr.h[l] = lh;
+    pyr.pitch[l] = align_up(lw, 16);
+    pyr.stride[l] = (size_t)pyr.pitch[l] * lh;
+    off[l] = total;
+    total += pyr.stride[l] * n_img + 256;
+    total = (total + 255) / 256 * 256;
+  }
+  uint8_t* base = (uint8_t*)ctx->scratch(name, total + 256);
+  if (!base && L > 0) return ctx->fail(FLVIS_ERR_HIP, "pyramid scratch allocation failed");
+  for (int l = 1; l <= L; l++) {
+    pyr.lvl[l] = img_plain(base + off[l]);
+    launch_pyr_down(ctx->stream, pyr.lvl[l - 1], pyr.w[l - 1], pyr.h[l - 1], pyr.pitch[l - 1], pyr.stride[l - 1],
+                    pyr.lvl[l], pyr.pitch[l], pyr.stride[l], n_img, nullptr);
+  }
+  return FLVIS_OK;
+}
+
 extern "C" {
 
 const char* flvis_version(void) { return "flvis_hip 0.1 (gfx950)"; }
@@ -166,61 +221,6 @@ int flvis_hip_pyr_down(flvis_ctx* ctx, const uint8_t* d_src, int w, int h, int s
   return FLVIS_OK;
 }
 
-static int lk_levels(int w, int h, int win, int max_level) {
-  int level = 0;
-  for (; level <= max_level; ++level) {
-    w = (w + 1) / 2;
-    h = (h + 1) / 2;
-    if (w <= win || h <= win) return level;
-  }
-  return max_level;
-}
-
-// builds levels 1..L of `img` ([n][h][w]) into scratch `name`, fills `pyr`
-static int build_pyramid(flvis_ctx* ctx, const char* name, const uint8_t* d_img, int w, int h, int n_img, int L,
-                         PyrSel& pyr) {
-  pyr.levels = L;
-  pyr.lvl[0] = img_plain(d_img);
-  pyr.w[0] = w;
-  pyr.h[0] = h;
-  pyr.pitch[0] = w;
-  pyr.stride[0] = (size_t)w * h;
-  if (w & 3) {
-    // rows that are not dword aligned (KITTI's 1241 x 376, tightly packed): level 0 is copied into a pitch-aligned buffer first, as
-    // the tracker's ingest does
-    const int pitch0 = align_up(w, 16);
-    const size_t stride0 = (size_t)pitch0 * h;
-    uint8_t* l0 = (uint8_t*)ctx->scratch(std::string(name) + "_l0", stride0 * n_img + 256);
-    if (!l0) return ctx->fail(FLVIS_ERR_HIP, "pyramid scratch allocation failed");
-    launch_copy_image_any(ctx->stream, img_plain(d_img), img_plain(l0), w, h, w, pitch0, (size_t)w * h, stride0, n_img, nullptr);
-    pyr.lvl[0] = img_plain(l0);
-    pyr.pitch[0] = pitch0;
-    pyr.stride[0] = stride0;
-  }
-  size_t total = 0;
-  size_t off[LK_MAX_LEVELS] = {0};
-  int lw = w, lh = h;
-  for (int l = 1; l <= L; l++) {
-    lw = (lw + 1) / 2;
-    lh = (lh + 1) / 2;
-    pyr.w[l] = lw;
-    pyr.h[l] = lh;
-    pyr.pitch[l] = align_up(lw, 16);
-    pyr.stride[l] = (size_t)pyr.pitch[l] * lh;
-    off[l] = total;
-    total += pyr.stride[l] * n_img + 256;
-    total = (total + 255) / 256 * 256;
-  }
-  uint8_t* base = (uint8_t*)ctx->scratch(name, total + 256);
-  if (!base && L > 0) return ctx->fail(FLVIS_ERR_HIP, "pyramid scratch allocation failed");
-  for (int l = 1; l <= L; l++) {
-    pyr.lvl[l] = img_plain(base + off[l]);
-    launch_pyr_down(ctx->stream, pyr.lvl[l - 1], pyr.w[l - 1], pyr.h[l - 1], pyr.pitch[l - 1], pyr.stride[l - 1],
-                    pyr.lvl[l], pyr.pitch[l], pyr.stride[l], n_img, nullptr);
-  }
-  return FLVIS_OK;
-}
-
 int flvis_hip_lk_track(flvis_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_next, int w, int h, int n_img,
                        const float* d_prev_pts, float* d_next_pts, uint8_t* d_status, const int* d_count, int nmax,
                        int max_level, int max_iter, double eps, int use_initial_flow) {
@@ -228,7 +228,7 @@ int flvis_hip_lk_track(flvis_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_n
   if (!d_prev || !d_next || !d_prev_pts || !d_next_pts || !d_status || !d_count || w < 32 || h < 32 || n_img <= 0 || nmax <= 0 ||
       max_level < 0)
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "lk_track: bad args");
-  int L = lk_levels(w, h, 31, max_level);
+  int L = lk_pyr_levels(w, h, 31, max_level);
   if (L >= LK_MAX_LEVELS) L = LK_MAX_LEVELS - 1;
   PyrSel pp, pn;
   int rc = build_pyramid(ctx, "lk_pyr_prev", d_prev, w, h, n_img, L, pp);
@@ -292,7 +292,7 @@ int flvis_hip_stereo_depth(flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* 
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the caller's pose array may be reused when this call returns)
   if (e != hipSuccess) return ctx->hip_fail(e, "stereo_depth pose upload");
   launch_stereo_depth_seeds(ctx->stream, cam, d_pt2d_plane, d_pt3d_w, d_has_depth, d_count, cap, n_sets, d_T, seeds);
-  int L = lk_levels(w, h, 31, 5);
+  int L = lk_pyr_levels(w, h, 31, 5);
   if (L >= LK_MAX_LEVELS) L = LK_MAX_LEVELS - 1;
   PyrSel pp, pn;
   int rc = build_pyramid(ctx, "lk_pyr_prev", d_img0, w, h, n_sets, L, pp);

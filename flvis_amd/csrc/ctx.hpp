@@ -41,3 +41,10 @@ struct flvis_ctx {
 };
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+namespace flvis {
+// the pyramids of the kernel-level LK calls (capi.cpp; flvis_hip_lk_track, flvis_hip_stereo_depth, flvis_hip_lkorb_tracking): the highest level
+// cv::calcOpticalFlowPyrLK builds for a w x h image, and levels 1 .. L of `d_img` ([n_img][h][w]) built into the scratch buffer `name`
+int lk_pyr_levels(int w, int h, int win, int max_level);
+int build_pyramid(flvis_ctx* ctx, const char* name, const uint8_t* d_img, int w, int h, int n_img, int L, PyrSel& pyr);
+}  // namespace flvis

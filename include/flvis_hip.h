@@ -10,6 +10,7 @@
  *   flvis_hip_equalize_hist      <- cv::equalizeHist            src/frontend/f2f_tracking.cpp:127,143-144
  *   flvis_hip_pyr_down           <- pyramid level of cv::calcOpticalFlowPyrLK (buildOpticalFlowPyramid)
  *   flvis_hip_stereo_depth       <- CameraFrame::recover3DPts_c_FromStereo   src/processing/camera_frame.cpp:93-180
+ *   flvis_hip_lkorb_tracking     <- LKORBTracking::tracking     src/processing/lkorb_tracking.cpp:9-202 (the whole step, one call)
  *   flvis_hip_lk_track           <- cv::calcOpticalFlowPyrLK    src/processing/lkorb_tracking.cpp:64-73,
  *                                                               src/processing/camera_frame.cpp:124-128
  *   flvis_hip_gftt               <- cv::goodFeaturesToTrack     src/processing/feature_dem.cpp:160,221
@@ -445,6 +446,37 @@ int flvis_hip_stereo_depth(flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* 
                            const float* d_pt2d_plane, const float* d_pt2d_undistort, const float* d_pt3d_w, const uint8_t* d_has_depth,
                            const int* d_count, int cap, const double* h_T_c_w7, float range, int32_t* d_rand_state35, double* d_pt3d_c,
                            uint8_t* d_mask_has_3d);
+
+/* LKORBTracking::tracking(from, to, T_c_w_guess, use_guess, ...) (src/processing/lkorb_tracking.cpp:9-202) in ONE call, for n_sets independent
+ * frames (a set is one frame) and every cam_type of cfg: no host step between the optical flow and the pose.
+ * In, per set s and landmark i < d_count[s] (arrays [n_sets][cap]...; a count above cap reads as cap, a negative one as 0): d_img_from /
+ * d_img_to [n_sets][h][w] mono8 of cfg's image size (from.img0 / to.img0); d_from_2d_plane / d_from_2d_undistort / d_from_3d_w what
+ * getAll2dPlaneUndistort3d_cvPf hands the reference (cv::Point2f / Point3f); d_from_flags bit 0 has_3d, bit 1 is_tracking_inlier of
+ * from.landmarks[i] (the copy `lm = from.landmarks.at(i)` carries the flag over and the F step only ever clears it, so it is an input);
+ * h_guess7 [n_sets][7] (tx ty tz qx qy qz qw) and h_use_guess [n_sets], host, per set and freely mixed; h_use_guess NULL: no set has a guess
+ * (h_guess7 may then be NULL too).
+ * Steps: the seeds -- from_2d_plane, or with a guess cv::projectPoints(K0, D0) on stereo rigs and, on CAM_DEPTH, camera2pixel of the
+ * float-narrowed landmark (:41-58) --; cv::calcOpticalFlowPyrLK(31 x 31, maxLevel 10, 30 / 0.001, OPTFLOW_USE_INITIAL_FLOW, minEig 1e-4) with the
+ * pyramids of flvis_hip_lk_track; on STEREO_UNRECT cv::undistortPoints(K0, D0, R0, P0) of the tracked points (the other rigs use the plane
+ * coordinates on both sides, whatever d_from_2d_undistort holds); the survivors (status 1, 0 < x < w - 1, 0 < y < h - 1) into `to` in
+ * DESCENDING index order; fewer than 10: ret 0.  cv::findFundamentalMat(FM_RANSAC, 5.0, 0.99) on the ascending pairs; mask[i] == 0 clears
+ * is_tracking_inlier of to.landmarks[i] (the reference's mirrored index, kept); fewer than 10 flags left: ret 0, the pose untouched.  The pairs
+ * has_3d && is_tracking_inlier in `to` order go to cv::solvePnPRansac(100, 3.0, 0.99) with the rectified K (P0) -- SOLVEPNP_ITERATIVE from the
+ * guess, SOLVEPNP_P3P without --, CameraFrame::updateLMState clears the flag of the pairs outside its mask, ret = inliers >= 10.
+ * Out: to.landmarks as d_to_from [n_sets][cap] (index in `from` of the j-th landmark of `to`), d_to_2d_plane / d_to_2d_undistort, d_to_flags;
+ * d_mask_F [n_sets][cap] (may be NULL) the F mask by ascending survivor rank; d_counts4 [n_sets][4] = of_inlier_cnt, F_inlier_cnt, the pairs
+ * handed to the PnP, pnp_inlier_cnt (0 for a stage not reached); d_pose7 [n_sets][7] in / out: written by the sets that reach the PnP (when it
+ * finds no model: the guess as a rotation matrix turned into a quaternion again, or the identity), left alone by the others; d_ret [n_sets].
+ * Rows of `to` from of_inlier_cnt on are never written.  A set's result is a function of that set alone; the host arrays may be freed when the
+ * call returns.
+ * Refused before anything is launched or written: null pointers, n_sets <= 0 or > 65535, cap <= 0, a non-zero h_use_guess entry with h_guess7
+ * NULL (FLVIS_ERR_INVALID_ARG); cap > 1024 (FLVIS_ERR_CAPACITY: the F search and the PnP hold 1024 points; the call never truncates); an
+ * image below 32 x 32 or a configuration that did not go through flvis_config_finalize (FLVIS_ERR_CONFIG).  One flvis_cfg per call. */
+int flvis_hip_lkorb_tracking(flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* d_img_from, const uint8_t* d_img_to, int n_sets,
+                             const float* d_from_2d_plane, const float* d_from_2d_undistort, const float* d_from_3d_w,
+                             const uint8_t* d_from_flags, const int* d_count, int cap, const double* h_guess7, const uint8_t* h_use_guess,
+                             int* d_to_from, float* d_to_2d_plane, float* d_to_2d_undistort, uint8_t* d_to_flags, uint8_t* d_mask_F,
+                             int* d_counts4, double* d_pose7, uint8_t* d_ret);
 
 /* Creates the batched tracker (and local map) for n_streams independent streams inside `ctx`.  seed_base + stream is the
  * RANSAC seed of each stream.  traj_capacity > 0 keeps a device-side trajectory of that many frames per stream. */
