@@ -895,9 +895,17 @@ int flvis_hip_bow_set_vocabulary(flvis_ctx* ctx, int n_nodes, const int* h_child
     }
     if (reached != (size_t)n_nodes) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_set_vocabulary: nodes that are not reachable from the root");
   }
+  // one leaf per word id: word_weight has one entry per id, while k_bow_words filters by the weight of the node it ended at
   std::vector<double> ww((size_t)n_words, 0.0);
-  for (int n = 0; n < n_nodes; n++)
-    if (h_child_ptr[n + 1] == h_child_ptr[n]) ww[h_word_id[n]] = h_weight[n];
+  {
+    std::vector<char> seen((size_t)n_words, 0);
+    for (int n = 0; n < n_nodes; n++)
+      if (h_child_ptr[n + 1] == h_child_ptr[n]) {
+        if (seen[h_word_id[n]]) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_set_vocabulary: duplicate word id");
+        seen[h_word_id[n]] = 1;
+        ww[h_word_id[n]] = h_weight[n];
+      }
+  }
   hipSetDevice(ctx->device);
   int* cp = (int*)ctx->scratch("voc_child_ptr", sizeof(int) * (size_t)(n_nodes + 1));
   int* ci = (int*)ctx->scratch("voc_child_idx", sizeof(int) * (size_t)std::max(n_edges, 1));
@@ -1044,7 +1052,8 @@ int flvis_hip_bow_score(flvis_ctx* ctx, const int* d_q_ids, const double* d_q_va
 int flvis_hip_bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs3, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
                              double* d_scores) {
   CHECK_CTX(ctx);
-  if (n_jobs <= 0 || !h_jobs3 || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs: bad args");
+  if (n_jobs <= 0 || n_jobs > 65535 || !h_jobs3 || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs: bad args");
   int max_n = 0;
   for (int i = 0; i < n_jobs; i++) {
     if (h_jobs3[3 * i] < 0 || h_jobs3[3 * i + 1] < 0 || h_jobs3[3 * i + 2] < 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs: negative index");

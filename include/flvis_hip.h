@@ -173,7 +173,8 @@ int flvis_hip_orb_match(flvis_ctx* ctx, const uint8_t* d_a, const int* d_na, int
  * The vocabulary is handed over as flat arrays (the reference loads a DBoW3 file that is not shipped with it,
  * vo_loopclosing.cpp:1097): node 0 is the root, the children of node n are h_child_idx[h_child_ptr[n] .. h_child_ptr[n+1]) in
  * DBoW3's order (3rdPartLib/DBow3/src/Vocabulary.h m_nodes[n].children), a node without children is a word with id h_word_id[n]
- * and weight h_weight[n] (idf); h_desc: 32 bytes per node.  Weighting TF_IDF, scoring L1_NORM (DBoW3's defaults). */
+ * and weight h_weight[n] (idf), no two words with the same id; h_desc: 32 bytes per node.  Weighting TF_IDF, scoring L1_NORM (DBoW3's
+ * defaults). */
 int flvis_hip_bow_set_vocabulary(flvis_ctx* ctx, int n_nodes, const int* h_child_ptr, const int* h_child_idx, const uint8_t* h_desc,
                                  const double* h_weight, const int* h_word_id);
 /* `Vocabulary vocTmp(vocFile)` (vo_loopclosing.cpp:1095-1099; Vocabulary::load, 3rdPartLib/DBow3/src/Vocabulary.cpp:1082-1096):
@@ -273,7 +274,7 @@ int flvis_hip_bow_score(flvis_ctx* ctx, const int* d_q_ids, const double* d_q_va
                         const double* d_db_vals, const int* d_db_nnz, int vcap, int n_db, double* d_scores);
 /* several rows in one launch over ONE store of vectors (d_ids / d_vals [n_vectors][vcap], d_nnz [n_vectors]): job i = h_jobs3[3i..3i+2]
  * = (query vector, first database vector, number of database vectors); d_scores[first + j] = score(query, first + j).  The loop
- * closer's rows of all sequences that got a keyframe. */
+ * closer's rows of all sequences that got a keyframe.  At most 65535 jobs. */
 int flvis_hip_bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs3, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
                              double* d_scores);
 /* the same with an output position per job: job i = h_jobs4[4i..4i+3] = (query vector, first database vector, number of database vectors,

@@ -132,6 +132,11 @@ void ref_voc_words(void* h, int n, const uint8_t* desc, int* words) {
     ref::word_of(v, desc + (size_t)r * 32, words[r], w);
   }
 }
+// ... and the weight of the word each descriptor ends at (what BowVector::addWeight is asked to add; <= 0: a stop word)
+void ref_voc_words_weights(void* h, int n, const uint8_t* desc, int* words, double* weights) {
+  const ref::Vocabulary& v = *(ref::Vocabulary*)h;
+  for (int r = 0; r < n; r++) ref::word_of(v, desc + (size_t)r * 32, words[r], weights[r]);
+}
 // BoW vector of n descriptors: ascending word ids + L1-normalised values; returns the number of entries
 int ref_voc_transform(void* h, int n, const uint8_t* desc, int cap, int* ids, double* vals) {
   std::map<int, double> bow;

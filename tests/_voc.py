@@ -5,10 +5,13 @@ training (its k-means++ seeding draws random numbers); only the SHAPE of what it
 import numpy as np
 
 
+_POPCOUNT = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.uint8)
+
+
 def hamming(a, b):
     """a [n,32] uint8, b [m,32] uint8 -> [n,m] int"""
     x = np.bitwise_xor(a[:, None, :], b[None, :, :])
-    return np.unpackbits(x, axis=2).sum(2).astype(np.int64)
+    return _POPCOUNT[x].sum(2, dtype=np.int64)
 
 
 def majority(d):

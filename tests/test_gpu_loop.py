@@ -4,6 +4,7 @@ run in DBoW3's order on both sides)."""
 import numpy as np
 import pytest
 
+import _bow_edges as E
 import _oracle as O
 import _voc as V
 from test_oracle_bow import RefVoc, ref_score
@@ -33,8 +34,8 @@ def _batch(kfs, dcap):
 
 def test_bow_transform_parity_bit_exact(ctx):
     kfs = V.make_keyframes(3, n_img=20)
-    voc = V.build_vocabulary(kfs[:12])
-    assert (voc[3][voc[4] >= 0] == 0).sum() >= 0
+    voc = V.build_vocabulary(kfs[:8])                                       # eight training images: some words occur in all of them
+    assert (voc[3][voc[4] >= 0] == 0).sum() == 6                            # stop words (idf log(8/8) = 0)
     rv = RefVoc(voc)
     ctx.bow_set_vocabulary(*voc)
     # edge cases: an empty keyframe, one descriptor repeated (a single word), a keyframe that fills the capacity exactly
@@ -42,6 +43,8 @@ def test_bow_transform_parity_bit_exact(ctx):
     desc, cnt = _batch(kfs, 512)
     ids, vals, nnz = ctx.bow_transform(desc, cnt, vcap=512)
     ids, vals, nnz = ids.cpu().numpy(), vals.cpu().numpy(), nnz.cpu().numpy()
+    stopped = sum(int((~(E.ref_words(rv, k[:512])[1] > 0)).sum()) for k in kfs)
+    assert stopped == 1248, stopped                                          # descriptors of the batch that end in a stop word, by the oracle
     for i, k in enumerate(kfs):
         wi, wv = rv.transform(k[:512])
         assert nnz[i] == len(wi), i
@@ -345,6 +348,9 @@ def test_loop_entry_points_reject_bad_input(ctx):
         ctx.bow_set_vocabulary(np.array([0, 2, 4, 4, 4, 4], np.int32), np.array([1, 2, 1, 3], np.int32), ds5, wt5, wi5)
     with pytest.raises(flvis_amd.FlvisError):      # node 3 is the child of two nodes
         ctx.bow_set_vocabulary(np.array([0, 2, 4, 4, 4, 4], np.int32), np.array([1, 3, 3, 4], np.int32), ds5, wt5, wi5)
+    with pytest.raises(flvis_amd.FlvisError) as e:  # two leaves with the same word id (one entry of the per-word weights for both)
+        ctx.bow_set_vocabulary(np.array([0, 2, 4, 4, 4, 4], np.int32), np.array([1, 2, 3, 4], np.int32), ds5, wt5, np.array([-1, -1, 0, 1, 1], np.int32))
+    assert "duplicate word id" in str(e.value) and "(-1)" in str(e.value)
     with pytest.raises(flvis_amd.FlvisError):      # nodes 3 and 4 form a cycle that the root does not reach
         ctx.bow_set_vocabulary(np.array([0, 2, 2, 2, 3, 4], np.int32), np.array([1, 2, 4, 3], np.int32), ds5,
                                np.array([0.0, 1.0, 1.0, 0.0, 0.0]), np.array([-1, 0, 1, -1, -1], np.int32))
