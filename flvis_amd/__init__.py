@@ -1111,13 +1111,8 @@ class LoopCloser:
         self._lib.flvis_loop_closer_set_stereo_unrect.argtypes = [C.c_void_p, C.c_int]
         self._ctx._check(self._lib.flvis_loop_closer_set_stereo_unrect(self._h, 1 if enable else 0), "loop_closer_set_stereo_unrect")
 
-    def add_keyframes(self, streams, img0, img1, T_c_w_odom):
-        """streams: the sequence of each keyframe (distinct); img0 uint8 [n,h,w], img1 uint8 / Z16 [n,h,w] (device); T_c_w_odom [n,7].
-        Returns the keyframes' indices in their sequences."""
-        import numpy as np
-        st = np.ascontiguousarray(streams, np.int32)
-        n = len(st)
-        T = np.ascontiguousarray(T_c_w_odom, np.float64).reshape(n, 7)
+    def _device_images(self, img0, img1, n):
+        """the device images of an add_keyframes / localize call, contiguous and of the configured size"""
         img0 = img0.contiguous()
         img1 = img1.contiguous() if img1 is not None else None
         hw = (int(self.cfg.image_height), int(self.cfg.image_width))
@@ -1125,6 +1120,29 @@ class LoopCloser:
         if img1 is not None:                                 # a wrong-size tensor would be read out of bounds on the device
             assert img1.shape[0] == n and tuple(img1.shape[1:]) == hw, "img1 must be [n, image_height, image_width]"
             assert img1.element_size() == (2 if self.cfg.cam_type == 2 else 1), "img1: uint8 (stereo) or 16-bit depth (depth rig)"
+        return img0, img1
+
+    @staticmethod
+    def _host_images(img0, img1, n):
+        """the numpy images of a _host call as two FlvisImage arrays (and the arrays they point into, to be kept until the call returns)"""
+        a = (FlvisImage * max(1, n))()
+        b = (FlvisImage * max(1, n))()
+        keep = []
+        for i in range(n):
+            for arr, dst in ((img0[i], a), (img1[i], b)):
+                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
+                keep.append(arr)
+                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
+        return a, b, keep
+
+    def add_keyframes(self, streams, img0, img1, T_c_w_odom):
+        """streams: the sequence of each keyframe (distinct); img0 uint8 [n,h,w], img1 uint8 / Z16 [n,h,w] (device); T_c_w_odom [n,7].
+        Returns the keyframes' indices in their sequences."""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        n = len(st)
+        T = np.ascontiguousarray(T_c_w_odom, np.float64).reshape(n, 7)
+        img0, img1 = self._device_images(img0, img1, n)
         ids = np.zeros(n, np.int64)
         self._ctx._check(self._lib.flvis_loop_closer_add_keyframes(self._h, n, _P(st, C.c_int), _ptr(img0), _ptr(img1), _P(T, C.c_double),
                                                                    _P(ids, C.c_int64)), "loop_closer_add_keyframes")
@@ -1138,14 +1156,7 @@ class LoopCloser:
         n = len(st)
         T = np.ascontiguousarray(T_c_w_odom, np.float64).reshape(n, 7)
         ids = np.zeros(n, np.int64)
-        a = (FlvisImage * n)()
-        b = (FlvisImage * n)()
-        keep = []
-        for i in range(n):
-            for arr, dst in ((img0[i], a), (img1[i], b)):
-                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
-                keep.append(arr)
-                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
+        a, b, keep = self._host_images(img0, img1, n)
         self._ctx._check(self._lib.flvis_loop_closer_add_keyframes_host(self._h, n, _P(st, C.c_int), a, b, _P(T, C.c_double), _P(ids, C.c_int64)),
                          "loop_closer_add_keyframes_host")
         return ids
@@ -1169,48 +1180,6 @@ class LoopCloser:
                             T_c_map=np.array(f.T_c_map7[:]) if f.best >= 0 else None))
         return out
 
-    def localize(self, streams, img0, img1, n_best=4):
-        """flvis_loop_closer_localize: one query frame for each of the sequences `streams` (distinct), images as add_keyframes takes them;
-        nothing is stored.  -> one dict per query: n_landmarks, candidates (the up to n_best best-scoring keyframes of the sequence, each a
-        dict kf / score / n_matches / n_inliers / accepted / pose), best (index into candidates, -1: not localised), kf (its keyframe) and
-        T_c_map (the query camera's pose7 in the map frame, None when not localised)."""
-        import numpy as np
-        st = np.ascontiguousarray(streams, np.int32)
-        n = len(st)
-        img0 = img0.contiguous()
-        img1 = img1.contiguous() if img1 is not None else None
-        hw = (int(self.cfg.image_height), int(self.cfg.image_width))
-        assert img0.shape[0] == n and tuple(img0.shape[1:]) == hw, "img0 must be [n, image_height, image_width]"
-        if img1 is not None:                                 # a wrong-size tensor would be read out of bounds on the device
-            assert img1.shape[0] == n and tuple(img1.shape[1:]) == hw, "img1 must be [n, image_height, image_width]"
-            assert img1.element_size() == (2 if self.cfg.cam_type == 2 else 1), "img1: uint8 (stereo) or 16-bit depth (depth rig)"
-        fix = (FlvisLcFix * max(1, n))()
-        self._lib.flvis_loop_closer_localize.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,
-                                                         C.POINTER(FlvisLcFix)]
-        self._ctx._check(self._lib.flvis_loop_closer_localize(self._h, n, _P(st, C.c_int), _ptr(img0), _ptr(img1), int(n_best), fix),
-                         "loop_closer_localize")
-        return self._fixes(fix[:n])
-
-    def localize_host(self, streams, img0, img1, n_best=4):
-        """flvis_loop_closer_localize_host: localize on numpy images as add_keyframes_host takes them (rows may be padded)."""
-        import numpy as np
-        st = np.ascontiguousarray(streams, np.int32)
-        n = len(st)
-        a = (FlvisImage * max(1, n))()
-        b = (FlvisImage * max(1, n))()
-        keep = []
-        for i in range(n):
-            for arr, dst in ((img0[i], a), (img1[i], b)):
-                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
-                keep.append(arr)
-                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
-        fix = (FlvisLcFix * max(1, n))()
-        self._lib.flvis_loop_closer_localize_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(FlvisImage),
-                                                              C.POINTER(FlvisImage), C.c_int, C.POINTER(FlvisLcFix)]
-        self._ctx._check(self._lib.flvis_loop_closer_localize_host(self._h, n, _P(st, C.c_int), a, b, int(n_best), fix),
-                         "loop_closer_localize_host")
-        return self._fixes(fix[:n])
-
     @classmethod
     def _fixes_in(cls, fix):
         out = cls._fixes([f.fix for f in fix])
@@ -1220,51 +1189,50 @@ class LoopCloser:
             d["map"] = int(f.map)
         return out
 
+    def _localize(self, fn, streams, maps, img0, img1, n_best, host):
+        """the four localize calls through their entry point fn: maps None: localize (FlvisLcFix), otherwise localize_in (FlvisLcFixIn);
+        host: numpy images"""
+        import numpy as np
+        st = np.ascontiguousarray(streams, np.int32)
+        n = len(st)
+        args, types = [_P(st, C.c_int)], [C.POINTER(C.c_int)]
+        if maps is not None:
+            mp = np.ascontiguousarray(maps, np.int32)
+            assert len(mp) == n, "one map per query"
+            args, types = args + [_P(mp, C.c_int)], types + [C.POINTER(C.c_int)]
+        if host:
+            a, b, keep = self._host_images(img0, img1, n)
+            args, types = args + [a, b], types + [C.POINTER(FlvisImage), C.POINTER(FlvisImage)]
+        else:
+            img0, img1 = self._device_images(img0, img1, n)
+            args, types = args + [_ptr(img0), _ptr(img1)], types + [C.c_void_p, C.c_void_p]
+        Fix = FlvisLcFix if maps is None else FlvisLcFixIn
+        fix = (Fix * max(1, n))()
+        fn.argtypes = [C.c_void_p, C.c_int] + types + [C.c_int, C.POINTER(Fix)]
+        self._ctx._check(fn(self._h, n, *args, int(n_best), fix), fn.__name__[len("flvis_"):])
+        return self._fixes(fix[:n]) if maps is None else self._fixes_in(fix[:n])
+
+    def localize(self, streams, img0, img1, n_best=4):
+        """flvis_loop_closer_localize: one query frame for each of the sequences `streams` (distinct), images as add_keyframes takes them;
+        nothing is stored.  -> one dict per query: n_landmarks, candidates (the up to n_best best-scoring keyframes of the sequence, each a
+        dict kf / score / n_matches / n_inliers / accepted / pose), best (index into candidates, -1: not localised), kf (its keyframe) and
+        T_c_map (the query camera's pose7 in the map frame, None when not localised)."""
+        return self._localize(self._lib.flvis_loop_closer_localize, streams, None, img0, img1, n_best, host=False)
+
+    def localize_host(self, streams, img0, img1, n_best=4):
+        """flvis_loop_closer_localize_host: localize on numpy images as add_keyframes_host takes them (rows may be padded)."""
+        return self._localize(self._lib.flvis_loop_closer_localize_host, streams, None, img0, img1, n_best, host=True)
+
     def localize_in(self, streams, maps, img0, img1, n_best=4):
         """flvis_loop_closer_localize_in: localize with the searched database named per query -- maps[i] is the sequence whose keyframe map
         query i (taken by the camera of sequence streams[i]) is looked for in, FLVIS_LC_ALL_MAPS (-1) every sequence's.  -> localize's
         dicts, each candidate with seq (kf is an index within that sequence), plus map (the sequence whose map frame T_c_map is in, -1
         when not localised)."""
-        import numpy as np
-        st = np.ascontiguousarray(streams, np.int32)
-        mp = np.ascontiguousarray(maps, np.int32)
-        n = len(st)
-        assert len(mp) == n, "one map per query"
-        img0 = img0.contiguous()
-        img1 = img1.contiguous() if img1 is not None else None
-        hw = (int(self.cfg.image_height), int(self.cfg.image_width))
-        assert img0.shape[0] == n and tuple(img0.shape[1:]) == hw, "img0 must be [n, image_height, image_width]"
-        if img1 is not None:                                 # a wrong-size tensor would be read out of bounds on the device
-            assert img1.shape[0] == n and tuple(img1.shape[1:]) == hw, "img1 must be [n, image_height, image_width]"
-            assert img1.element_size() == (2 if self.cfg.cam_type == 2 else 1), "img1: uint8 (stereo) or 16-bit depth (depth rig)"
-        fix = (FlvisLcFixIn * max(1, n))()
-        self._lib.flvis_loop_closer_localize_in.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
-                                                            C.c_int, C.POINTER(FlvisLcFixIn)]
-        self._ctx._check(self._lib.flvis_loop_closer_localize_in(self._h, n, _P(st, C.c_int), _P(mp, C.c_int), _ptr(img0), _ptr(img1),
-                                                                 int(n_best), fix), "loop_closer_localize_in")
-        return self._fixes_in(fix[:n])
+        return self._localize(self._lib.flvis_loop_closer_localize_in, streams, maps, img0, img1, n_best, host=False)
 
     def localize_in_host(self, streams, maps, img0, img1, n_best=4):
         """flvis_loop_closer_localize_in_host: localize_in on numpy images as add_keyframes_host takes them (rows may be padded)."""
-        import numpy as np
-        st = np.ascontiguousarray(streams, np.int32)
-        mp = np.ascontiguousarray(maps, np.int32)
-        n = len(st)
-        assert len(mp) == n, "one map per query"
-        a = (FlvisImage * max(1, n))()
-        b = (FlvisImage * max(1, n))()
-        keep = []
-        for i in range(n):
-            for arr, dst in ((img0[i], a), (img1[i], b)):
-                assert arr.ndim == 2 and arr.strides[1] == arr.itemsize
-                keep.append(arr)
-                dst[i] = FlvisImage(C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(C.c_uint8)), arr.shape[1], arr.shape[0], arr.strides[0], 1, 0.0)
-        fix = (FlvisLcFixIn * max(1, n))()
-        self._lib.flvis_loop_closer_localize_in_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                                 C.POINTER(FlvisImage), C.POINTER(FlvisImage), C.c_int, C.POINTER(FlvisLcFixIn)]
-        self._ctx._check(self._lib.flvis_loop_closer_localize_in_host(self._h, n, _P(st, C.c_int), _P(mp, C.c_int), a, b, int(n_best), fix),
-                         "loop_closer_localize_in_host")
-        return self._fixes_in(fix[:n])
+        return self._localize(self._lib.flvis_loop_closer_localize_in_host, streams, maps, img0, img1, n_best, host=True)
 
     def link(self, queries, n_best=4):
         """flvis_loop_closer_link: localize_in with STORED keyframes as the queries.  queries: FlvisLcLinkQuery, dicts or tuples

@@ -6,12 +6,14 @@
 //   flvis_loop_closer_process        <- pgoProcess     :393-518   similarity row, the `size < 50` gate, isLoopCandidate (:520-590),
 //                                                      isLoopClosureKF (:593-735), the loop list, the PGO trigger (:488-497),
 //                                                      loopClosureOnCovGraphG2ONew (:742-944) and T_odom_map *= Tw1_w2 (:908)
-//   flvis_loop_closer_localize       (the project's own) a query frame against its sequence's whole database: isLoopClosureKF's check on
-//                                                      the n_best best-scoring keyframes, the camera's pose in the map frame; stores nothing
-//   flvis_loop_closer_localize_in    (the project's own) the same against ANOTHER sequence's database, or all of them: the candidates are
-//                                                      ranked across maps (flvis_hip_lc_select_maps), PnP runs with the query's camera
+//   flvis_loop_closer_localize_in    (the project's own) a query frame against a sequence's whole database, or all of them: the candidates
+//                                                      are ranked across maps (flvis_hip_lc_select_maps), isLoopClosureKF's check on the n_best
+//                                                      best-scoring keyframes with the query's camera, its pose in the map frame; stores nothing
+//   flvis_loop_closer_localize       (the project's own) localize_in on the query's own sequence's map
 //   flvis_loop_closer_link           (the project's own) localize_in with a STORED keyframe as the query: its database slot takes the query
 //                                                      slot's place, no feature kernel runs; any number of queries, its own keyframes left out
+//                                                      -- the three are one candidate search (lc_search) on queries that differ in where they
+//                                                      come from
 //   flvis_loop_closer_merge          (the project's own) several sequences' maps into one: loopClosureOnCovGraphG2ONew on the sequences'
 //                                                      keyframes side by side, tied by links between keyframes of different sequences
 //
@@ -33,6 +35,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -45,8 +48,7 @@ namespace {
 
 constexpr int LCC_CAP = 1024;   // keypoints per keyframe (the reference extracts 1000) = correspondences per PnP set
 constexpr int LCC_VCAP = 1024;  // bag-of-words entries per keyframe
-constexpr size_t LCC_STAGE = 7 * sizeof(double) + 2 * sizeof(int);  // bytes per keyframe of an add call's one upload
-constexpr size_t LCC_QSTAGE = LCC_STAGE + sizeof(int);              // ... per query of a localize call's (the sequence's keyframe count too)
+constexpr size_t LCC_STAGE = 7 * sizeof(double) + 2 * sizeof(int);  // bytes per keyframe of an add call's one upload, per query of a localize call's
 constexpr int LCC_NBEST = FLVIS_LC_FIX_CAND;                        // candidates per query of a localize call
 
 // ---- pose7 = tx ty tz qx qy qz qw on the host (Sophus::SE3 products of :377, :908) -------------------------------------------
@@ -151,56 +153,11 @@ struct LcFixOut {
   }
 };
 
-// The candidates of a localize call, one wave per query: the n_best keyframes of the query's sequence with the highest score (> 0 and
-// >= min_score), score descending, equal scores by keyframe index ascending.  Rank by rank: every lane scans its stride of the row for
-// the entry that comes next in that order after the previous pick, then the wave reduces with the same rule -- no LDS, no sort, any n.
-// Per set it writes what the pair check reads (the keyframe's slot, the query's slot, the camera row) and what the host gets back; a
-// rank without a candidate gets the closer's empty slot on both sides (landmark count 0): its set is empty from k_lcc_fetch on.
-__global__ __launch_bounds__(64) void k_lcc_select(const int* __restrict__ q_slot, const int* __restrict__ q_seq, const int* __restrict__ q_n,
-                                                   const double* __restrict__ rows, int maxkf, int n_best, double min_score, int empty_slot,
-                                                   const int* __restrict__ lmc, const double* __restrict__ db_T, int* slot_a, int* slot_b,
-                                                   int* cam_of, LcFixOut out) {
-  const int i = blockIdx.x, lane = threadIdx.x;
-  const int s = q_seq[i], n = q_n[i];
-  const double* const row = rows + (size_t)s * maxkf;
-  double prev_sc = 0.0;
-  int prev_j = -1, cnt = 0;  // prev_j < 0: nothing picked yet
-  bool more = true;
-  for (int r = 0; r < n_best; r++) {
-    double b_sc = 0.0;
-    int b_j = INT_MAX;  // INT_MAX: none
-    if (more)
-      for (int j = lane; j < n; j += 64) {
-        const double sc = row[j];
-        if (!(sc > 0.0 && sc >= min_score)) continue;
-        if (prev_j >= 0 && !(sc < prev_sc || (sc == prev_sc && j > prev_j))) continue;  // picked already
-        if (b_j == INT_MAX || sc > b_sc) b_sc = sc, b_j = j;  // (j ascends within a lane: an equal score later in the stride loses)
-      }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const double o_sc = __shfl_xor(b_sc, d);
-      const int o_j = __shfl_xor(b_j, d);
-      if (o_j != INT_MAX && (b_j == INT_MAX || o_sc > b_sc || (o_sc == b_sc && o_j < b_j))) b_sc = o_sc, b_j = o_j;
-    }
-    more = b_j != INT_MAX;  // (wave-uniform: every lane holds the reduction's result)
-    const int set = i * n_best + r;
-    const int ks = more ? s * maxkf + b_j : empty_slot;
-    if (lane < 7) out.T_kf[(size_t)set * 7 + lane] = more ? db_T[(size_t)ks * 7 + lane] : (lane == 6 ? 1.0 : 0.0);
-    if (lane == 0) {
-      slot_a[set] = ks;
-      slot_b[set] = more ? q_slot[i] : empty_slot;
-      cam_of[set] = s;
-      out.kf[set] = more ? b_j : -1;
-      out.score[set] = more ? b_sc : 0.0;
-    }
-    if (more) prev_sc = b_sc, prev_j = b_j, cnt++;
-  }
-  if (lane == 0) out.ncand[i] = cnt, out.nlm[i] = lmc[i];
-}
-
-// k_lcc_select's writes for a localize_in call, whose candidates k_lc_select_maps (loop_kernels.hip) has chosen across maps: sel_idx is
-// the candidate's database slot (sequence * maxkf + keyframe; -1: an empty rank) and goes to the host as it is.  Side a is the candidate's
-// slot, side b the query's, the camera row the QUERY's sequence: solvePnPRansac needs the K of the camera that saw the pixels.
+// The sets of a candidate search, one wave per query, from the candidates k_lc_select_maps (loop_kernels.hip) has chosen across maps: per
+// set (= query * n_best + rank) what the pair check reads (side a the candidate's slot, side b the query's, the camera row the QUERY's
+// sequence: solvePnPRansac needs the K of the camera that saw the pixels) and what the host gets back.  sel_idx is the candidate's database
+// slot (sequence * maxkf + keyframe; -1: an empty rank) and goes to the host as it is; an empty rank gets the closer's empty slot on both
+// sides (landmark count 0): its set is empty from k_lcc_fetch on.
 // lmc: the queries' landmark counts, per query (the call's feature buffers) or, BY_SLOT, per database slot (a link call's stored queries).
 template <bool BY_SLOT>
 __global__ __launch_bounds__(64) void k_lcc_select_sets(const int* __restrict__ q_slot, const int* __restrict__ q_seq, const int* __restrict__ sel_idx,
@@ -275,15 +232,14 @@ struct flvis_loop_closer {
       *nb = nullptr, *pairs = nullptr, *npairs = nullptr, *ninl = nullptr;
   uint8_t* stage = nullptr;  // one upload per add call: [n][7] poses, [n] slots, [n] sequences
   double *vals = nullptr, *lm3 = nullptr, *rows = nullptr, *pose = nullptr, *loop_pose = nullptr, *drift = nullptr, *stats = nullptr, *pgo_T = nullptr;
-  // localize: the queries' score rows [S][maxkf] (`rows` is what similarity_row reports: not touched), the result block (LcFixOut) and
-  // its host copy; sets_cap: the pair-check buffers (slot_a .. mask) hold this many sets -- S until the first localize call
-  double* qrows = nullptr;
+  // a candidate search (localize, localize_in, link): the result block (LcFixOut) and its host copy; sets_cap: the pair-check buffers
+  // (slot_a .. mask) hold this many sets -- S until the first search
   uint8_t* fix_out = nullptr;
   std::vector<uint8_t> h_fix_out;
   int sets_cap = 0;
-  // localize_in, all allocated by its first call: the queries' score rows ([S][maxkf], one searched map per query; [S][S * maxkf] from
-  // the first call that searches all maps on; mrows_cap: doubles), the searched maps and the sequences' keyframe counts ([2 S], one
-  // upload from h_in_stage), and what k_lc_select_maps leaves per set / per query
+  // ... all allocated by the first search: the queries' score rows ([S][maxkf], one searched map per query; [S][S * maxkf] from the first
+  // call that searches all maps on; mrows_cap: doubles -- `rows` is what similarity_row reports: not touched), the searched maps and the
+  // sequences' keyframe counts ([2 S], one upload from h_in_stage), and what k_lc_select_maps leaves per set / per query
   double* mrows = nullptr;
   size_t mrows_cap = 0;
   int *in_stage = nullptr, *sel_idx = nullptr, *sel_cnt = nullptr;
@@ -409,7 +365,7 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
   bool ok = lc->alloc(lc->db_ids, dbs * LCC_VCAP) && lc->alloc(lc->db_vals, dbs * LCC_VCAP) && lc->alloc(lc->db_nnz, dbs) &&
             lc->alloc(lc->db_lm2, dbs * LCC_CAP * 2) && lc->alloc(lc->db_lm3, dbs * LCC_CAP * 3) &&
             lc->alloc(lc->db_lmd, dbs * LCC_CAP * 32) && lc->alloc(lc->db_lmc, dbs) && lc->alloc(lc->db_T, dbs * 7) &&
-            lc->alloc(lc->qrows, slots) && lc->alloc(lc->fix_out, LcFixOut::bytes(S * LCC_NBEST, S)) &&
+            lc->alloc(lc->fix_out, LcFixOut::bytes(S * LCC_NBEST, S)) &&
             lc->alloc(lc->kps, S * LCC_CAP * 6) && lc->alloc(lc->desc, S * LCC_CAP * 32) && lc->alloc(lc->cnt, S) && lc->alloc(lc->ovf, S) &&
             lc->alloc(lc->ids, S * LCC_VCAP) && lc->alloc(lc->vals, S * LCC_VCAP) && lc->alloc(lc->nnz, S) &&
             lc->alloc(lc->lm2, S * LCC_CAP * 2) && lc->alloc(lc->lm3, S * LCC_CAP * 3) && lc->alloc(lc->lmc, S) &&
@@ -418,7 +374,7 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
             lc->alloc(lc->npairs, S) && lc->alloc(lc->p3d, S * LCC_CAP * 3) && lc->alloc(lc->p2d, S * LCC_CAP * 2) &&
             lc->alloc(lc->mask, S * LCC_CAP) && lc->alloc(lc->ninl, S) && lc->alloc(lc->pose, S * 7) && lc->alloc(lc->rows, slots) &&
             lc->alloc(lc->loop_pose, slots * 7) && lc->alloc(lc->drift, S * 7) && lc->alloc(lc->stats, S * 5) && lc->alloc(lc->pgo_T, slots * 7) &&
-            lc->alloc(lc->stage, S * LCC_QSTAGE) && lc->alloc(lc->d_cams, S) &&
+            lc->alloc(lc->stage, S * LCC_STAGE) && lc->alloc(lc->d_cams, S) &&
             hipHostMalloc((void**)&lc->h_cams, S * sizeof(LcCam), hipHostMallocDefault) == hipSuccess;
   if (ok && lc->cam_type == 1)
     ok = lc->alloc(lc->d_ucams, S) && hipHostMalloc((void**)&lc->h_ucams, S * sizeof(LcCamUnrect), hipHostMallocDefault) == hipSuccess;
@@ -444,7 +400,7 @@ int flvis_loop_closer_create_rigs(flvis_ctx* ctx, const flvis_cfg* cfgs, const f
   }
   lc->seq.resize(n_streams);
   lc->h_rows.resize(slots);
-  lc->h_stage.resize(S * LCC_QSTAGE);
+  lc->h_stage.resize(S * LCC_STAGE);
   lc->h_fix_out.resize(LcFixOut::bytes(S * LCC_NBEST, S));
   lc->sets_cap = n_streams;
   *out = lc;
@@ -644,6 +600,19 @@ static int lc_host_images_stage(flvis_loop_closer* lc, int n, const flvis_image*
   *d_img0 = d0, *d_img1 = d1;
   return FLVIS_OK;
 }
+// ... around the device-image call of the same name: call(d_img0, d_img1) synchronises when it succeeds, and on its error paths the uploads
+// are waited for here.  Every argument is checked BEFORE a copy is queued (the caller has checked its own): the caller may free its images
+// as soon as the call returns with an error.
+static int lc_on_host_images(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
+                             const std::string& what, const std::function<int(const uint8_t*, const uint8_t*)>& call) {
+  int rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
+  uint8_t *d0 = nullptr, *d1 = nullptr;
+  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
+  if (rc != FLVIS_OK) return rc;
+  rc = call(d0, d1);
+  if (rc != FLVIS_OK) hipStreamSynchronize(lc->ctx->stream);
+  return rc;
+}
 
 int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int* h_stream, const flvis_image* h_img0, const flvis_image* h_img1,
                                          const double* h_T_c_w_odom7, int64_t* h_kf_id) {
@@ -652,14 +621,9 @@ int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int
   const char* const what = "loop_closer_add_keyframes_host";
   if (n <= 0 || n > lc->S || !h_img0 || !h_img1 || !h_stream || !h_T_c_w_odom7)
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_add_keyframes_host: bad args");
-  // every argument is checked BEFORE a copy is queued: the caller may free its images as soon as this call returns with an error
-  int rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
-  uint8_t *d0 = nullptr, *d1 = nullptr;
-  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
-  if (rc != FLVIS_OK) return rc;
-  rc = flvis_loop_closer_add_keyframes(lc, n, h_stream, d0, d1, h_T_c_w_odom7, h_kf_id);  // (synchronises when it succeeds)
-  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);  // ... and on its error paths the uploads are waited for here
-  return rc;
+  return lc_on_host_images(lc, n, h_stream, h_img0, h_img1, what, [&](const uint8_t* d0, const uint8_t* d1) {
+    return flvis_loop_closer_add_keyframes(lc, n, h_stream, d0, d1, h_T_c_w_odom7, h_kf_id);
+  });
 }
 
 // isLoopClosureKF (:593-686) on the device for nc pairs of database slots (a: the keyframe whose 3-D points are used, b: the one whose
@@ -850,14 +814,14 @@ static int lc_localize_check(flvis_loop_closer* lc, int n, const int* h_stream, 
   return FLVIS_OK;
 }
 
-// the buffers of a localize / localize_in / link call beyond what create allocates, grown by the first call that needs them: the pair-check
-// buffers for LCC_NBEST sets per sequence, and (in_maps) localize_in's score rows and selection buffers -- all_maps: rows for all segments
-static int lc_localize_reserve(flvis_loop_closer* lc, bool in_maps, bool all_maps, const char* what) {
+// the buffers of a candidate search beyond what create allocates, grown by the first call that needs them: the pair-check buffers for
+// LCC_NBEST sets per sequence, the score rows and the selection buffers -- all_maps: rows for all segments
+static int lc_search_reserve(flvis_loop_closer* lc, bool all_maps, const char* what) {
   flvis_ctx* ctx = lc->ctx;
   hipStream_t st = ctx->stream;
   hipError_t e = hipSuccess;
   const int ns_cap = lc->S * LCC_NBEST;
-  if (lc->sets_cap < ns_cap) {  // the first localize call: the pair-check buffers grow from one set per sequence to LCC_NBEST
+  if (lc->sets_cap < ns_cap) {  // the first search: the pair-check buffers grow from one set per sequence to LCC_NBEST
     e = hipStreamSynchronize(st);
     if (e != hipSuccess) return ctx->hip_fail(e, what);
     const size_t c = (size_t)ns_cap;
@@ -865,28 +829,26 @@ static int lc_localize_reserve(flvis_loop_closer* lc, bool in_maps, bool all_map
           lc->regrow(lc->nb, c) && lc->regrow(lc->pairs, c * LCC_CAP * 2) && lc->regrow(lc->p3d, c * LCC_CAP * 3) &&
           lc->regrow(lc->p2d, c * LCC_CAP * 2) && lc->regrow(lc->mask, c * LCC_CAP))) {
       (void)hipGetLastError();
-      // (a buffer that did not grow keeps its size, and sets_cap its value: process goes on, the next localize call tries again)
+      // (a buffer that did not grow keeps its size, and sets_cap its value: process goes on, the next search tries again)
       return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
     }
     lc->sets_cap = ns_cap;
   }
-  if (in_maps) {
-    const size_t S = (size_t)lc->S, need = (all_maps ? S * S : S) * (size_t)lc->maxkf;
-    if (need > (size_t)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, std::string(what) + ": n_streams^2 * max_keyframes is too large");
-    if (lc->mrows_cap < need || !lc->sel_cnt) {  // the first call, and the first that searches all maps
-      e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return ctx->hip_fail(e, what);
-      bool ok = lc->mrows ? lc->regrow(lc->mrows, need) : lc->alloc(lc->mrows, need);
-      if (ok) lc->mrows_cap = need;
-      ok = ok && (lc->in_stage || lc->alloc(lc->in_stage, 2 * S)) && (lc->sel_idx || lc->alloc(lc->sel_idx, S * LCC_NBEST)) &&
-           (lc->sel_score || lc->alloc(lc->sel_score, S * LCC_NBEST)) && (lc->sel_cnt || lc->alloc(lc->sel_cnt, S));
-      if (!ok) {
-        (void)hipGetLastError();
-        // (the rows keep the size they had: calls that need no more go on, the next one that does tries again)
-        return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation of the score rows failed");
-      }
-      lc->h_in_stage.resize(2 * S);
+  const size_t S = (size_t)lc->S, need = (all_maps ? S * S : S) * (size_t)lc->maxkf;
+  if (need > (size_t)INT_MAX - 64) return ctx->fail(FLVIS_ERR_CAPACITY, std::string(what) + ": n_streams^2 * max_keyframes is too large");
+  if (lc->mrows_cap < need || !lc->sel_cnt) {  // the first search, and the first that searches all maps
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, what);
+    bool ok = lc->mrows ? lc->regrow(lc->mrows, need) : lc->alloc(lc->mrows, need);
+    if (ok) lc->mrows_cap = need;
+    ok = ok && (lc->in_stage || lc->alloc(lc->in_stage, 2 * S)) && (lc->sel_idx || lc->alloc(lc->sel_idx, S * LCC_NBEST)) &&
+         (lc->sel_score || lc->alloc(lc->sel_score, S * LCC_NBEST)) && (lc->sel_cnt || lc->alloc(lc->sel_cnt, S));
+    if (!ok) {
+      (void)hipGetLastError();
+      // (the rows keep the size they had: calls that need no more go on, the next one that does tries again)
+      return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation of the score rows failed");
     }
+    lc->h_in_stage.resize(2 * S);
   }
   return FLVIS_OK;
 }
@@ -925,109 +887,117 @@ static void lc_fix_in_split(const flvis_loop_closer* lc, flvis_lc_fix_in& f) {
   f.reserved = 0;
 }
 
-// Relocalisation: where is this frame's camera in the map its sequence has built?  The query goes through a keyframe's steps into its
-// sequence's query slot, is scored against the sequence's whole database, the n_best best keyframes are chosen on the device
-// (k_lcc_select) and each (keyframe, query) pair goes through isLoopClosureKF's check as process runs it -- n * n_best sets, empty where
-// there is no candidate.  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.
-//
-// h_map == nullptr: localize (every query against its own sequence's database: qrows, k_lcc_select).  Otherwise localize_in: query i
-// against the database of sequence h_map[i], or of every sequence (< 0) -- the score rows in mrows, one launch for all (query, map) jobs,
-// the candidates across maps by k_lc_select_maps, then k_lcc_select's writes; h.kf comes back as a slot index, not a keyframe index.
-// The fix of query i is written at fix_base + i * fix_stride (cand_kf: what h.kf holds).
+// The queries of a candidate search, per query: the database slot that stands for it (its sequence's query slot, or a stored keyframe's
+// own slot), its sequence (= its camera's row), the searched map (< 0: every map) and, skip != null, the slots [skip[2i], skip[2i + 1]) that
+// are no candidates of it.  slot, seq and skip are host arrays and the same on the device, in the one upload the caller has queued.
+struct LcQueries {
+  const int *slot, *seq, *skip, *map;  // host
+  const int *d_slot, *d_seq, *d_skip;  // device
+};
+
+// The candidate search of localize, localize_in and link for n <= n_streams queries: every query is scored against the keyframes of its
+// searched maps -- one launch for all (query, map that holds candidates) jobs, a row per query of one segment per sequence (all_maps) or of
+// the one segment it searches --, k_lc_select_maps picks the n_best best across the maps, and each (keyframe, query) pair goes through
+// isLoopClosureKF's check as process runs it: n * n_best sets, empty where there is no candidate.  One copy brings the results back; fix i
+// is written at fix_base + i * fix_stride, a flvis_lc_fix_in (fix_in: the candidates split into sequence and keyframe) or a flvis_lc_fix
+// (the keyframe alone).  by_slot: the queries are stored keyframes (their landmark counts are the database's, not the call's feature
+// buffers').  Nothing of the sequences' state is written: not Seq, not the database's keyframe slots, not `rows`.  The one exit waits for
+// the stream when the search fails: h_stage, which the caller filled, is reused by the next call.
+static int lc_search(flvis_loop_closer* lc, int n, const LcQueries& q, bool all_maps, bool by_slot, int n_best, char* fix_base, size_t fix_stride,
+                     bool fix_in, const char* what) {
+  flvis_ctx* ctx = lc->ctx;
+  hipStream_t st = ctx->stream;
+  const int S = lc->S, maxkf = lc->maxkf, ns = n * n_best, ns_cap = S * LCC_NBEST;
+  auto hip = [&](hipError_t e) { return e == hipSuccess ? (int)FLVIS_OK : ctx->hip_fail(e, what); };
+  // the searched maps and the sequences' keyframe counts (one upload); one job per (query, searched map that holds candidates)
+  const size_t stride = (size_t)(all_maps ? S : 1) * maxkf;
+  int* const hm = lc->h_in_stage.data();
+  std::vector<int> jobs;
+  for (int m = 0; m < S; m++) hm[n + m] = lc->seq[m].n;
+  for (int i = 0; i < n; i++) {
+    hm[i] = q.map[i] < 0 ? -1 : q.map[i];
+    for (int m = hm[i] < 0 ? 0 : hm[i]; m < (hm[i] < 0 ? S : hm[i] + 1); m++) {
+      const int first = m * maxkf, nk = lc->seq[m].n;
+      // (a map wholly excluded: its part of the row is never written, and never read)
+      if (nk > 0 && !(q.skip && q.skip[2 * i] <= first && first + nk <= q.skip[2 * i + 1]))
+        jobs.insert(jobs.end(), {q.slot[i], first, nk, (int)(stride * i + (all_maps ? (size_t)first : 0))});
+    }
+  }
+  int rc = hip(hipMemcpyAsync(lc->in_stage, hm, sizeof(int) * (size_t)(n + S), hipMemcpyHostToDevice, st));
+  const int n_jobs = (int)(jobs.size() / 4);
+  for (int j0 = 0; j0 < n_jobs && rc == FLVIS_OK; j0 += 65535)  // (a launch takes 65535 jobs: one launch up to 255 sequences)
+    rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
+                                     lc->mrows);
+  if (rc == FLVIS_OK)
+    rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, S, maxkf, lc->in_stage + n, lc->in_stage, q.d_skip, !all_maps, n_best, lc->prm.minScore,
+                                   lc->sel_idx, lc->sel_score, lc->sel_cnt);
+  int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
+  const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)S);
+  if (rc == FLVIS_OK) {
+    if (by_slot)
+      k_lcc_select_sets<true><<<n, 64, 0, st>>>(q.d_slot, q.d_seq, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->db_lmc,
+                                                lc->db_T, slot_a, slot_b, cam_of, out);
+    else
+      k_lcc_select_sets<false><<<n, 64, 0, st>>>(q.d_slot, q.d_seq, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->lmc,
+                                                 lc->db_T, slot_a, slot_b, cam_of, out);
+    std::vector<uint64_t> seeds((size_t)ns);
+    for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(q.seq[i / n_best] + 1) << 32) + (uint64_t)(i % n_best + 1);  // (stream + 1) << 32 | rank + 1
+    rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
+  }
+  if (rc == FLVIS_OK) rc = hip(hipMemcpyAsync(lc->h_fix_out.data(), lc->fix_out, lc->h_fix_out.size(), hipMemcpyDeviceToHost, st));
+  if (rc == FLVIS_OK) rc = hip(hipStreamSynchronize(st));
+  if (rc != FLVIS_OK) {
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)S);
+  for (int i = 0; i < n; i++) {
+    flvis_lc_fix& f = *reinterpret_cast<flvis_lc_fix*>(fix_base + fix_stride * (size_t)i);
+    lc_fix_fill(lc, h, i, n_best, f);  // (cand_kf: database slots)
+    if (fix_in) lc_fix_in_split(lc, *reinterpret_cast<flvis_lc_fix_in*>(&f));
+    else
+      for (int r = 0; r < f.n_candidates; r++) f.cand_kf[r] %= maxkf;
+  }
+  return FLVIS_OK;
+}
+
+// Relocalisation: where is this frame's camera in the map of sequence h_map[i], or in whichever map knows the place (< 0)?  h_map ==
+// nullptr is localize: every query in the map its own sequence has built.  What is this run's own comes before the search: the queries go
+// through a keyframe's steps into their sequences' query slots, so that the kernels which take database slots address them as they address
+// a keyframe.  The fix of query i is written at fix_base + i * fix_stride (lc_search).
 static int lc_localize_run(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
                            int n_best, char* fix_base, size_t fix_stride, const char* what) {
   flvis_ctx* ctx = lc->ctx;
-  int rc = FLVIS_OK;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
-  hipError_t e = hipSuccess;
-  const int ns_cap = lc->S * LCC_NBEST;
   bool all_maps = false;
   for (int i = 0; h_map && i < n; i++) all_maps = all_maps || h_map[i] < 0;
-  rc = lc_localize_reserve(lc, h_map != nullptr, all_maps, what);
+  int rc = lc_search_reserve(lc, all_maps, what);
   if (rc != FLVIS_OK) return rc;
-  // one upload: identity poses for k_lcc_store, the queries' slots, their sequences (= camera rows), the sequences' keyframe counts
+  // one upload: identity poses for k_lcc_store, the queries' slots, their sequences (= camera rows)
   double* const T = reinterpret_cast<double*>(lc->h_stage.data());
   int* const hq = reinterpret_cast<int*>(lc->h_stage.data() + 7 * sizeof(double) * (size_t)n);
-  std::vector<int> jobs;
   for (int i = 0; i < n; i++) {
-    const int s = h_stream[i], nk = lc->seq[s].n;
     for (int k = 0; k < 7; k++) T[7 * (size_t)i + k] = k == 6 ? 1.0 : 0.0;
-    hq[i] = lc->query_slot(s), hq[n + i] = s, hq[2 * n + i] = nk;
-    if (!h_map && nk > 0) jobs.insert(jobs.end(), {lc->query_slot(s), s * lc->maxkf, nk});
+    hq[i] = lc->query_slot(h_stream[i]), hq[n + i] = h_stream[i];
   }
   const double* const d_T = reinterpret_cast<const double*>(lc->stage);
   const int* const d_q = reinterpret_cast<const int*>(lc->stage + 7 * sizeof(double) * (size_t)n);
-  e = hipMemcpyAsync(lc->stage, lc->h_stage.data(), LCC_QSTAGE * (size_t)n, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(lc->stage, lc->h_stage.data(), LCC_STAGE * (size_t)n, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return ctx->hip_fail(e, what);
   rc = lc_features(lc, n, d_img0, d_img1, d_q + n);
+  if (rc == FLVIS_OK) {
+    k_lcc_store<<<dim3(LCC_CAP / 256, n), 256, 0, st>>>(d_q, lc->ids, lc->vals, lc->nnz, lc->lm2, lc->lm3, lc->desc, lc->lmc, d_T, lc->db_ids,
+                                                         lc->db_vals, lc->db_nnz, lc->db_lm2, lc->db_lm3, lc->db_lmd, lc->db_lmc, lc->db_T);
+    e = hipGetLastError();
+    if (e != hipSuccess) rc = ctx->hip_fail(e, what);
+  }
   if (rc != FLVIS_OK) {
     hipStreamSynchronize(st);  // (h_stage is reused by the next call)
     return rc;
   }
-  k_lcc_store<<<dim3(LCC_CAP / 256, n), 256, 0, st>>>(d_q, lc->ids, lc->vals, lc->nnz, lc->lm2, lc->lm3, lc->desc, lc->lmc, d_T, lc->db_ids,
-                                                       lc->db_vals, lc->db_nnz, lc->db_lm2, lc->db_lm3, lc->db_lmd, lc->db_lmc, lc->db_T);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    hipStreamSynchronize(st);
-    return ctx->hip_fail(e, what);
-  }
-  const int ns = n * n_best;
-  int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
-  const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)lc->S);
-  if (!h_map) {
-    // the queries' score rows (flvis_hip_bow_score's scores: the same kernel body), then the candidates
-    if (!jobs.empty()) rc = flvis_hip_bow_score_jobs(ctx, (int)(jobs.size() / 3), jobs.data(), lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP, lc->qrows);
-    if (rc != FLVIS_OK) {
-      hipStreamSynchronize(st);
-      return rc;
-    }
-    k_lcc_select<<<n, 64, 0, st>>>(d_q, d_q + n, d_q + 2 * n, lc->qrows, lc->maxkf, n_best, lc->prm.minScore, lc->empty_slot(), lc->lmc, lc->db_T,
-                                   slot_a, slot_b, cam_of, out);
-  } else {
-    // one job per (query, searched map that holds keyframes); a query's row is one segment per sequence, or, when no query of the call
-    // searches all maps, the one segment it searches
-    const size_t stride = (size_t)(all_maps ? lc->S : 1) * lc->maxkf;
-    int* const hm = lc->h_in_stage.data();
-    for (int m = 0; m < lc->S; m++) hm[n + m] = lc->seq[m].n;
-    for (int i = 0; i < n; i++) {
-      hm[i] = h_map[i] < 0 ? -1 : h_map[i];
-      for (int m = h_map[i] < 0 ? 0 : h_map[i]; m < (h_map[i] < 0 ? lc->S : h_map[i] + 1); m++)
-        if (lc->seq[m].n > 0)
-          jobs.insert(jobs.end(), {lc->query_slot(h_stream[i]), m * lc->maxkf, lc->seq[m].n, (int)(stride * i + (all_maps ? (size_t)m * lc->maxkf : 0))});
-    }
-    e = hipMemcpyAsync(lc->in_stage, hm, sizeof(int) * (size_t)(n + lc->S), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-      hipStreamSynchronize(st);
-      return ctx->hip_fail(e, what);
-    }
-    const int n_jobs = (int)(jobs.size() / 4);
-    for (int j0 = 0; j0 < n_jobs && rc == FLVIS_OK; j0 += 65535)  // (a launch takes 65535 jobs: one launch up to 255 sequences)
-      rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
-                                       lc->mrows);
-    if (rc == FLVIS_OK)
-      rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, lc->S, lc->maxkf, lc->in_stage + n, lc->in_stage, nullptr, !all_maps, n_best, lc->prm.minScore,
-                                     lc->sel_idx, lc->sel_score, lc->sel_cnt);
-    if (rc != FLVIS_OK) {
-      hipStreamSynchronize(st);
-      return rc;
-    }
-    k_lcc_select_sets<false><<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->lmc, lc->db_T,
-                                               slot_a, slot_b, cam_of, out);
-  }
-  std::vector<uint64_t> seeds((size_t)ns);
-  for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(h_stream[i / n_best] + 1) << 32) + (uint64_t)(i % n_best + 1);  // (stream + 1) << 32 | rank + 1
-  rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
-  if (rc != FLVIS_OK) {
-    hipStreamSynchronize(st);
-    return rc;
-  }
-  e = hipMemcpyAsync(lc->h_fix_out.data(), lc->fix_out, lc->h_fix_out.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return ctx->hip_fail(e, what);
-  const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)lc->S);
-  for (int i = 0; i < n; i++) lc_fix_fill(lc, h, i, n_best, *reinterpret_cast<flvis_lc_fix*>(fix_base + fix_stride * (size_t)i));
-  return FLVIS_OK;
+  const LcQueries q{hq, hq + n, nullptr, h_map ? h_map : h_stream, d_q, d_q + n, nullptr};
+  return lc_search(lc, n, q, all_maps, false, n_best, fix_base, fix_stride, h_map != nullptr, what);
 }
 
 int flvis_loop_closer_localize(flvis_loop_closer* lc, int n, const int* h_stream, const uint8_t* d_img0, const void* d_img1, int n_best,
@@ -1046,16 +1016,12 @@ int flvis_loop_closer_localize_host(flvis_loop_closer* lc, int n, const int* h_s
   if (!lc) return FLVIS_ERR_INVALID_ARG;
   flvis_ctx* ctx = lc->ctx;
   const char* const what = "loop_closer_localize_host";
-  int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
+  const int rc = lc_localize_check(lc, n, h_stream, n_best, h_fix, what);
   if (rc != FLVIS_OK) return rc;
   if (!h_img0 || !h_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_host: bad args");
-  rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
-  uint8_t *d0 = nullptr, *d1 = nullptr;
-  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
-  if (rc != FLVIS_OK) return rc;
-  rc = flvis_loop_closer_localize(lc, n, h_stream, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
-  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return lc_on_host_images(lc, n, h_stream, h_img0, h_img1, what, [&](const uint8_t* d0, const uint8_t* d1) {
+    return flvis_loop_closer_localize(lc, n, h_stream, d0, d1, n_best, h_fix);
+  });
 }
 
 // the arguments of a localize_in call that both forms share, checked before anything is queued
@@ -1070,8 +1036,7 @@ static int lc_localize_in_check(flvis_loop_closer* lc, int n, const int* h_strea
   return FLVIS_OK;
 }
 
-// Where is this frame's camera in the map ANOTHER sequence has built, or in whichever map knows the place?  localize's run with the
-// searched database named per query; the candidates come back as database slots and are split into (sequence, keyframe) here.
+// Where is this frame's camera in the map ANOTHER sequence has built, or in whichever map knows the place?
 int flvis_loop_closer_localize_in(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const uint8_t* d_img0, const void* d_img1,
                                   int n_best, flvis_lc_fix_in* h_fix) {
   if (!lc) return FLVIS_ERR_INVALID_ARG;
@@ -1080,10 +1045,7 @@ int flvis_loop_closer_localize_in(flvis_loop_closer* lc, int n, const int* h_str
   int rc = lc_localize_in_check(lc, n, h_stream, h_map, n_best, h_fix, what);
   if (rc != FLVIS_OK) return rc;
   if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_in: bad args");
-  rc = lc_localize_run(lc, n, h_stream, h_map, d_img0, d_img1, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix_in), what);
-  if (rc != FLVIS_OK) return rc;
-  for (int i = 0; i < n; i++) lc_fix_in_split(lc, h_fix[i]);
-  return FLVIS_OK;
+  return lc_localize_run(lc, n, h_stream, h_map, d_img0, d_img1, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix_in), what);
 }
 
 int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* h_stream, const int* h_map, const flvis_image* h_img0,
@@ -1091,81 +1053,35 @@ int flvis_loop_closer_localize_in_host(flvis_loop_closer* lc, int n, const int* 
   if (!lc) return FLVIS_ERR_INVALID_ARG;
   flvis_ctx* ctx = lc->ctx;
   const char* const what = "loop_closer_localize_in_host";
-  int rc = lc_localize_in_check(lc, n, h_stream, h_map, n_best, h_fix, what);
+  const int rc = lc_localize_in_check(lc, n, h_stream, h_map, n_best, h_fix, what);
   if (rc != FLVIS_OK) return rc;
   if (!h_img0 || !h_img1) return ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_localize_in_host: bad args");
-  rc = lc_host_images_check(lc, n, h_stream, h_img0, h_img1, what);
-  uint8_t *d0 = nullptr, *d1 = nullptr;
-  if (rc == FLVIS_OK) rc = lc_host_images_stage(lc, n, h_img0, h_img1, what, &d0, &d1);
-  if (rc != FLVIS_OK) return rc;
-  rc = flvis_loop_closer_localize_in(lc, n, h_stream, h_map, d0, d1, n_best, h_fix);  // (synchronises when it succeeds, and on its device error paths)
-  if (rc != FLVIS_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return lc_on_host_images(lc, n, h_stream, h_img0, h_img1, what, [&](const uint8_t* d0, const uint8_t* d1) {
+    return flvis_loop_closer_localize_in(lc, n, h_stream, h_map, d0, d1, n_best, h_fix);
+  });
 }
 
-// One pass of a link call: n <= n_streams queries (kf resolved), localize_in's run from the score jobs on with the query keyframe's own
-// database slot where localize_in has the sequence's query slot, and k_lc_select_maps' excluded range.  all_maps: the call's row layout.
+// One pass of a link call: n <= n_streams queries (kf resolved), each the search's query by its keyframe's own database slot, with
+// own_gap as a range of excluded slots.  all_maps: the call's row layout.
 static int lc_link_pass(flvis_loop_closer* lc, int n, const flvis_lc_link_query* q, bool all_maps, int n_best, flvis_lc_fix_in* h_fix,
                         const char* what) {
   flvis_ctx* ctx = lc->ctx;
-  hipStream_t st = ctx->stream;
-  const int S = lc->S, maxkf = lc->maxkf, ns = n * n_best, ns_cap = S * LCC_NBEST;
-  // two uploads: the queries' slots, their sequences (= camera rows) and excluded ranges; the searched maps and the sequences' counts
+  const int maxkf = lc->maxkf;
+  // one upload: the queries' slots, their sequences (= camera rows) and excluded ranges
   int* const hq = reinterpret_cast<int*>(lc->h_stage.data());
-  int* const hm = lc->h_in_stage.data();
-  const size_t stride = (size_t)(all_maps ? S : 1) * maxkf;
-  std::vector<int> jobs;
-  for (int m = 0; m < S; m++) hm[n + m] = lc->seq[m].n;
+  std::vector<int> map((size_t)n);
   for (int i = 0; i < n; i++) {
-    const int s = q[i].stream, kf = (int)q[i].kf, nk = lc->seq[s].n;
+    const int s = q[i].stream, kf = (int)q[i].kf;
     const int g = (int)std::min<int64_t>(q[i].own_gap, maxkf);
-    hq[i] = s * maxkf + kf, hq[n + i] = s;
+    hq[i] = s * maxkf + kf, hq[n + i] = s, map[i] = q[i].map;
     hq[2 * n + 2 * i] = s * maxkf + (g < 0 ? 0 : std::max(0, kf - g));
-    hq[2 * n + 2 * i + 1] = g < 0 ? (s + 1) * maxkf : s * maxkf + std::min(nk, kf + g + 1);
-    hm[i] = q[i].map < 0 ? -1 : q[i].map;
-    for (int m = q[i].map < 0 ? 0 : q[i].map; m < (q[i].map < 0 ? S : q[i].map + 1); m++)
-      if (lc->seq[m].n > 0 && !(m == s && g < 0))  // (the own segment wholly excluded: its part of the row is never written, and never read)
-        jobs.insert(jobs.end(), {hq[i], m * maxkf, lc->seq[m].n, (int)(stride * i + (all_maps ? (size_t)m * maxkf : 0))});
+    hq[2 * n + 2 * i + 1] = g < 0 ? (s + 1) * maxkf : s * maxkf + std::min(lc->seq[s].n, kf + g + 1);
   }
   const int* const d_q = reinterpret_cast<const int*>(lc->stage);
-  hipError_t e = hipMemcpyAsync(lc->stage, hq, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(lc->in_stage, hm, sizeof(int) * (size_t)(n + S), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) {
-    hipStreamSynchronize(st);  // (h_stage is reused by the next call)
-    return ctx->hip_fail(e, what);
-  }
-  int rc = FLVIS_OK;
-  const int n_jobs = (int)(jobs.size() / 4);
-  for (int j0 = 0; j0 < n_jobs && rc == FLVIS_OK; j0 += 65535)
-    rc = flvis_hip_bow_score_jobs_at(ctx, std::min(65535, n_jobs - j0), jobs.data() + 4 * (size_t)j0, lc->db_ids, lc->db_vals, lc->db_nnz, LCC_VCAP,
-                                     lc->mrows);
-  if (rc == FLVIS_OK)
-    rc = flvis::lc_select_maps_dev(ctx, n, lc->mrows, S, maxkf, lc->in_stage + n, lc->in_stage, d_q + 2 * n, !all_maps, n_best, lc->prm.minScore,
-                                   lc->sel_idx, lc->sel_score, lc->sel_cnt);
-  if (rc != FLVIS_OK) {
-    hipStreamSynchronize(st);
-    return rc;
-  }
-  int *const slot_a = lc->slot_a, *const slot_b = lc->slot_a + ns, *const cam_of = lc->slot_a + 2 * ns;
-  const LcFixOut out = LcFixOut::at(lc->fix_out, (size_t)ns_cap, (size_t)S);
-  k_lcc_select_sets<true><<<n, 64, 0, st>>>(d_q, d_q + n, lc->sel_idx, lc->sel_score, lc->sel_cnt, n_best, lc->empty_slot(), lc->db_lmc, lc->db_T,
-                                            slot_a, slot_b, cam_of, out);
-  std::vector<uint64_t> seeds((size_t)ns);
-  for (int i = 0; i < ns; i++) seeds[i] = ((uint64_t)(q[i / n_best].stream + 1) << 32) + (uint64_t)(i % n_best + 1);  // localize's
-  rc = lc_pair_check(lc, ns, slot_a, slot_b, cam_of, seeds.data(), out.npairs, out.pose, out.ninl);
-  if (rc != FLVIS_OK) {
-    hipStreamSynchronize(st);
-    return rc;
-  }
-  e = hipMemcpyAsync(lc->h_fix_out.data(), lc->fix_out, lc->h_fix_out.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const hipError_t e = hipMemcpyAsync(lc->stage, hq, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return ctx->hip_fail(e, what);
-  const LcFixOut h = LcFixOut::at(lc->h_fix_out.data(), (size_t)ns_cap, (size_t)S);
-  for (int i = 0; i < n; i++) {
-    lc_fix_fill(lc, h, i, n_best, h_fix[i].fix);
-    lc_fix_in_split(lc, h_fix[i]);
-  }
-  return FLVIS_OK;
+  const LcQueries lq{hq, hq + n, hq + 2 * n, map.data(), d_q, d_q + n, d_q + 2 * n};
+  return lc_search(lc, n, lq, all_maps, true, n_best, reinterpret_cast<char*>(h_fix), sizeof(flvis_lc_fix_in), true, what);
 }
 
 int flvis_lc_links_from_fix(const flvis_lc_fix_in* fix, int stream, int64_t kf, int cap, flvis_lc_link* out) {
@@ -1226,7 +1142,7 @@ int flvis_loop_closer_link(flvis_loop_closer* lc, int n, const flvis_lc_link_que
     all_maps = all_maps || q[i].map < 0;
   }
   hipSetDevice(ctx->device);
-  int rc = lc_localize_reserve(lc, true, all_maps, what);
+  int rc = lc_search_reserve(lc, all_maps, what);
   if (rc != FLVIS_OK) return rc;
   for (int i0 = 0; i0 < n; i0 += lc->S) {
     rc = lc_link_pass(lc, std::min(lc->S, n - i0), q.data() + i0, all_maps, n_best, h_fix + i0, what);

@@ -197,29 +197,17 @@ __global__ __launch_bounds__(256) void k_bow_score(const int* __restrict__ q_ids
   if (lane == 0) scores[j] = sc;
 }
 
-// the same for several (query, database range) jobs of one vector store in one launch: job = (query vector, first database vector,
-// number of database vectors), all indices into the store; scores[first + j]
+// the same for several (query, database range) jobs of one vector store in one launch.  W = 3: job = (query vector, first database
+// vector, number of database vectors), all indices into the store; scores[first + j].  W = 4: the job's fourth int is its first output
+// index, scores[out + j] -- several queries may score the same database range, each into a row of its own
+template <int W>
 __global__ __launch_bounds__(256) void k_bow_score_jobs(const int* __restrict__ jobs, const int* __restrict__ ids, const double* __restrict__ vals,
                                                         const int* __restrict__ nnz, int vcap, double* __restrict__ scores) {
+  static_assert(W == 3 || W == 4, "a job is (query, first, n) or (query, first, n, out)");
   __shared__ double s_term[4][64];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = jobs[3 * blockIdx.y], first = jobs[3 * blockIdx.y + 1], n_db = jobs[3 * blockIdx.y + 2];
-  const int j = blockIdx.x * 4 + wv;
-  if (j >= n_db) return;
-  const size_t v = (size_t)first + j;
-  const int nd = nnz[v], nq = nnz[q];
-  double sc = 0.0;
-  if (nd >= 0 && nq >= 0) sc = bow_score_wave(ids + (size_t)q * vcap, vals + (size_t)q * vcap, nq, ids + v * vcap, vals + v * vcap, nd, s_term[wv], lane);
-  if (lane == 0) scores[v] = sc;
-}
-
-// ... and with an output position per job: job = (query vector, first database vector, number of database vectors, first output index),
-// scores[out + j] -- several queries may score the same database range, each into a row of its own
-__global__ __launch_bounds__(256) void k_bow_score_jobs_at(const int* __restrict__ jobs, const int* __restrict__ ids, const double* __restrict__ vals,
-                                                           const int* __restrict__ nnz, int vcap, double* __restrict__ scores) {
-  __shared__ double s_term[4][64];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = jobs[4 * blockIdx.y], first = jobs[4 * blockIdx.y + 1], n_db = jobs[4 * blockIdx.y + 2], out = jobs[4 * blockIdx.y + 3];
+  const int q = jobs[W * blockIdx.y], first = jobs[W * blockIdx.y + 1], n_db = jobs[W * blockIdx.y + 2];
+  const int out = W == 4 ? jobs[W * blockIdx.y + 3] : first;
   const int j = blockIdx.x * 4 + wv;
   if (j >= n_db) return;
   const size_t v = (size_t)first + j;
@@ -721,6 +709,30 @@ __global__ __launch_bounds__(256) void k_lc_points(const float* __restrict__ kps
   p0[o * 2 + 1] = p1[o * 2 + 1] = y;
 }
 
+// What the two landmark kernels share, around their own rule for which keypoint gets a position: a keypoint's descriptor into registers ...
+__device__ __forceinline__ void lc_load_desc(const uint8_t* desc, size_t o, uint4 (&d)[2]) {
+  const uint4* q = reinterpret_cast<const uint4*>(desc + o * 32);
+  d[0] = q[0], d[1] = q[1];
+}
+// ... and the ordered removal of :362-371: the kept keypoints of a thread's two go behind those of the threads before it, then the count
+__device__ __forceinline__ void lc_store_kept(int img, int cap, const bool (&keep)[2], const float (&xy)[2][2], const V3 (&p3)[2],
+                                              const uint4 (&d)[2][2], int* s_scan, float* lm_2d, double* lm_3d, uint8_t* lm_desc,
+                                              int* __restrict__ lm_count) {
+  int tot;
+  int k = block_exclusive_scan<LC_T / 64>((int)keep[0] + (int)keep[1], s_scan, tot);  // (its barriers also order the in-place case)
+#pragma unroll
+  for (int e = 0; e < 2; e++) {
+    if (!keep[e]) continue;
+    const size_t o = (size_t)img * cap + k;
+    lm_2d[o * 2] = xy[e][0], lm_2d[o * 2 + 1] = xy[e][1];
+    lm_3d[o * 3] = p3[e].x, lm_3d[o * 3 + 1] = p3[e].y, lm_3d[o * 3 + 2] = p3[e].z;
+    uint4* q = reinterpret_cast<uint4*>(lm_desc + o * 32);
+    q[0] = d[e][0], q[1] = d[e][1];
+    k++;
+  }
+  if (threadIdx.x == 0) lm_count[img] = tot;
+}
+
 // one workgroup per keyframe, two keypoints per thread: the mask of :280-349, then the ordered removal of :362-371.  The keyframe's
 // camera is row cam_of[img] (cam_of null: row img) of a device table: the index depends on blockIdx.x alone, so the row's loads are scalar.
 __global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__ cams, const int* __restrict__ cam_of, int cam_type, int w, int h,
@@ -743,8 +755,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__
     const size_t o = (size_t)img * cap + i;
     const float x = kps[o * 6], y = kps[o * 6 + 1];
     xy[e][0] = x, xy[e][1] = y;
-    const uint4* q = reinterpret_cast<const uint4*>(desc + o * 32);
-    d[e][0] = q[0], d[e][1] = q[1];
+    lc_load_desc(desc, o, d[e]);
     if (cam_type == 0) {
       if (status[o] == 1) {
         const V3 pc = triangulate_dlt((double)x, (double)y, (double)next_pts[o * 2], (double)next_pts[o * 2 + 1], cam.P0, cam.P1);
@@ -763,19 +774,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks(const LcCam* __restrict__
       }
     }
   }
-  int tot;
-  int k = block_exclusive_scan<LC_T / 64>((int)keep[0] + (int)keep[1], s_scan, tot);  // (its barriers also order the in-place case)
-#pragma unroll
-  for (int e = 0; e < 2; e++) {
-    if (!keep[e]) continue;
-    const size_t o = (size_t)img * cap + k;
-    lm_2d[o * 2] = xy[e][0], lm_2d[o * 2 + 1] = xy[e][1];
-    lm_3d[o * 3] = p3[e].x, lm_3d[o * 3 + 1] = p3[e].y, lm_3d[o * 3 + 2] = p3[e].z;
-    uint4* q = reinterpret_cast<uint4*>(lm_desc + o * 32);
-    q[0] = d[e][0], q[1] = d[e][1];
-    k++;
-  }
-  if (t == 0) lm_count[img] = tot;
+  lc_store_kept(img, cap, keep, xy, p3, d, s_scan, lm_2d, lm_3d, lm_desc, lm_count);
 }
 
 // The STEREO_UNRECT case, which the reference leaves empty (:318-324, "track to another image / go to undistor plane / triangulation"):
@@ -803,8 +802,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks_unrect(const LcCam* __res
     const int i = 2 * t + e;
     if (i >= n) continue;
     const size_t o = (size_t)img * cap + i;
-    const uint4* q = reinterpret_cast<const uint4*>(desc + o * 32);
-    d[e][0] = q[0], d[e][1] = q[1];
+    lc_load_desc(desc, o, d[e]);
     if (status[o] != 1) continue;
     const float src0[2] = {kps[o * 6], kps[o * 6 + 1]}, src1[2] = {next_pts[o * 2], next_pts[o * 2 + 1]};
     float u0[2], u1[2];  // (floats: cv::undistortPoints returns Point2f)
@@ -817,19 +815,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_landmarks_unrect(const LcCam* __res
       xy[e][0] = u0[0], xy[e][1] = u0[1];
     }
   }
-  int tot;
-  int k = block_exclusive_scan<LC_T / 64>((int)keep[0] + (int)keep[1], s_scan, tot);  // (its barriers also order the in-place case)
-#pragma unroll
-  for (int e = 0; e < 2; e++) {
-    if (!keep[e]) continue;
-    const size_t o = (size_t)img * cap + k;
-    lm_2d[o * 2] = xy[e][0], lm_2d[o * 2 + 1] = xy[e][1];
-    lm_3d[o * 3] = p3[e].x, lm_3d[o * 3 + 1] = p3[e].y, lm_3d[o * 3 + 2] = p3[e].z;
-    uint4* q = reinterpret_cast<uint4*>(lm_desc + o * 32);
-    q[0] = d[e][0], q[1] = d[e][1];
-    k++;
-  }
-  if (t == 0) lm_count[img] = tot;
+  lc_store_kept(img, cap, keep, xy, p3, d, s_scan, lm_2d, lm_3d, lm_desc, lm_count);
 }
 
 // what every entry point of the PnP RANSAC on caller arrays refuses, before anything is uploaded or launched
@@ -854,6 +840,32 @@ using namespace flvis;
     hipError_t e_ = hipGetLastError();                  \
     if (e_ != hipSuccess) return (c)->hip_fail(e_, what); \
   } while (0)
+
+// the two job calls: W ints per job (k_bow_score_jobs<W>), `name` in front of the messages, a scratch buffer per width
+template <int W>
+static int bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
+                          double* d_scores, const char* name, const char* scratch) {
+  CHECK_CTX(ctx);
+  const std::string what = name;
+  if (n_jobs <= 0 || n_jobs > 65535 || !h_jobs || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": bad args");
+  int max_n = 0;
+  for (int i = 0; i < n_jobs; i++) {
+    const int* const j = h_jobs + W * (size_t)i;
+    if (*std::min_element(j, j + W) < 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, what + ": negative index");
+    max_n = std::max(max_n, j[2]);
+  }
+  if (max_n == 0) return FLVIS_OK;
+  hipSetDevice(ctx->device);
+  int* jobs = (int*)ctx->scratch(scratch, sizeof(int) * W * (size_t)n_jobs);
+  if (!jobs) return ctx->fail(FLVIS_ERR_HIP, what + ": scratch allocation failed");
+  hipError_t e = hipMemcpyAsync(jobs, h_jobs, sizeof(int) * W * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h_jobs is the caller's: done with it before returning
+  if (e != hipSuccess) return ctx->hip_fail(e, name);
+  k_bow_score_jobs<W><<<dim3((max_n + 3) / 4, n_jobs), 256, 0, ctx->stream>>>(jobs, d_ids, d_vals, d_nnz, vcap, d_scores);
+  CHECK_LAUNCH(ctx, name);
+  return FLVIS_OK;
+}
 
 extern "C" {
 
@@ -961,27 +973,31 @@ static int lc_landmarks_upload(flvis_ctx* ctx, int n_img, int cam_type, const do
   return FLVIS_OK;
 }
 
-int flvis_hip_lc_keyframe_landmarks_rigs(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
-                                         const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
-                                         const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+// row_stride 1: a camera per keyframe; 0: one camera for every keyframe, the same call on n_img equal rows
+static int lc_keyframe_landmarks_rows(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
+                                      const double* h_P0, const double* h_P1, const double* h_K4, int row_stride, const float* d_kps,
+                                      const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc,
+                                      int* d_lm_count) {
   CHECK_CTX(ctx);
   const LcCam* cams = nullptr;
-  const int rc = lc_landmarks_upload(ctx, n_img, cam_type, h_P0, h_P1, h_K4, 1, &cams);
+  const int rc = lc_landmarks_upload(ctx, n_img, cam_type, h_P0, h_P1, h_K4, row_stride, &cams);
   if (rc != FLVIS_OK) return rc;
   return lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, w, h, n_img, cam_type, cams, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
                                    d_lm_desc, d_lm_count);
 }
 
-// one camera for every keyframe: the same call on n_img equal rows
+int flvis_hip_lc_keyframe_landmarks_rigs(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
+                                         const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
+                                         const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
+  return lc_keyframe_landmarks_rows(ctx, d_img0, d_img1, w, h, n_img, cam_type, h_P0, h_P1, h_K4, 1, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
+                                    d_lm_desc, d_lm_count);
+}
+
 int flvis_hip_lc_keyframe_landmarks(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type,
                                     const double* h_P0, const double* h_P1, const double* h_K4, const float* d_kps, const uint8_t* d_desc,
                                     const int* d_count, int cap, float* d_lm_2d, double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
-  CHECK_CTX(ctx);
-  const LcCam* cams = nullptr;
-  const int rc = lc_landmarks_upload(ctx, n_img, cam_type, h_P0, h_P1, h_K4, 0, &cams);
-  if (rc != FLVIS_OK) return rc;
-  return lc_keyframe_landmarks_dev(ctx, d_img0, d_img1, w, h, n_img, cam_type, cams, nullptr, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
-                                   d_lm_desc, d_lm_count);
+  return lc_keyframe_landmarks_rows(ctx, d_img0, d_img1, w, h, n_img, cam_type, h_P0, h_P1, h_K4, 0, d_kps, d_desc, d_count, cap, d_lm_2d, d_lm_3d,
+                                    d_lm_desc, d_lm_count);
 }
 
 // the STEREO_UNRECT rule (k_lc_landmarks_unrect) on caller arrays: the rigs are finalized configs, one for every image or one per image
@@ -1051,47 +1067,12 @@ int flvis_hip_bow_score(flvis_ctx* ctx, const int* d_q_ids, const double* d_q_va
 
 int flvis_hip_bow_score_jobs(flvis_ctx* ctx, int n_jobs, const int* h_jobs3, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
                              double* d_scores) {
-  CHECK_CTX(ctx);
-  if (n_jobs <= 0 || n_jobs > 65535 || !h_jobs3 || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0)
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs: bad args");
-  int max_n = 0;
-  for (int i = 0; i < n_jobs; i++) {
-    if (h_jobs3[3 * i] < 0 || h_jobs3[3 * i + 1] < 0 || h_jobs3[3 * i + 2] < 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs: negative index");
-    max_n = std::max(max_n, h_jobs3[3 * i + 2]);
-  }
-  if (max_n == 0) return FLVIS_OK;
-  hipSetDevice(ctx->device);
-  int* jobs = (int*)ctx->scratch("bow_jobs", sizeof(int) * 3 * (size_t)n_jobs);
-  if (!jobs) return ctx->fail(FLVIS_ERR_HIP, "bow_score_jobs: scratch allocation failed");
-  hipError_t e = hipMemcpyAsync(jobs, h_jobs3, sizeof(int) * 3 * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h_jobs3 is the caller's: done with it before returning
-  if (e != hipSuccess) return ctx->hip_fail(e, "bow_score_jobs");
-  k_bow_score_jobs<<<dim3((max_n + 3) / 4, n_jobs), 256, 0, ctx->stream>>>(jobs, d_ids, d_vals, d_nnz, vcap, d_scores);
-  CHECK_LAUNCH(ctx, "bow_score_jobs");
-  return FLVIS_OK;
+  return bow_score_jobs<3>(ctx, n_jobs, h_jobs3, d_ids, d_vals, d_nnz, vcap, d_scores, "bow_score_jobs", "bow_jobs");
 }
 
 int flvis_hip_bow_score_jobs_at(flvis_ctx* ctx, int n_jobs, const int* h_jobs4, const int* d_ids, const double* d_vals, const int* d_nnz, int vcap,
                                 double* d_scores) {
-  CHECK_CTX(ctx);
-  if (n_jobs <= 0 || n_jobs > 65535 || !h_jobs4 || !d_ids || !d_vals || !d_nnz || !d_scores || vcap <= 0)
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs_at: bad args");
-  int max_n = 0;
-  for (int i = 0; i < n_jobs; i++) {
-    const int* const j = h_jobs4 + 4 * (size_t)i;
-    if (j[0] < 0 || j[1] < 0 || j[2] < 0 || j[3] < 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "bow_score_jobs_at: negative index");
-    max_n = std::max(max_n, j[2]);
-  }
-  if (max_n == 0) return FLVIS_OK;
-  hipSetDevice(ctx->device);
-  int* jobs = (int*)ctx->scratch("bow_jobs_at", sizeof(int) * 4 * (size_t)n_jobs);
-  if (!jobs) return ctx->fail(FLVIS_ERR_HIP, "bow_score_jobs_at: scratch allocation failed");
-  hipError_t e = hipMemcpyAsync(jobs, h_jobs4, sizeof(int) * 4 * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h_jobs4 is the caller's: done with it before returning
-  if (e != hipSuccess) return ctx->hip_fail(e, "bow_score_jobs_at");
-  k_bow_score_jobs_at<<<dim3((max_n + 3) / 4, n_jobs), 256, 0, ctx->stream>>>(jobs, d_ids, d_vals, d_nnz, vcap, d_scores);
-  CHECK_LAUNCH(ctx, "bow_score_jobs_at");
-  return FLVIS_OK;
+  return bow_score_jobs<4>(ctx, n_jobs, h_jobs4, d_ids, d_vals, d_nnz, vcap, d_scores, "bow_score_jobs_at", "bow_jobs_at");
 }
 
 int flvis_hip_lc_select_maps(flvis_ctx* ctx, int n_q, const double* d_scores, int n_seg, int seg_len, const int* d_seg_n, const int* d_map,
@@ -1390,6 +1371,22 @@ int flvis_loop_candidate(int g_size, const double* h_row, const uint8_t* h_prese
 
 namespace flvis {
 
+// The keypoints of n_img keyframes tracked into their second images, for both stereo rules: calcOpticalFlowPyrLK(img0, img1, lm_img0,
+// lm_img1, ., ., Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW) with lm_img1 = lm_img0 (:270-278).  The points in
+// img1 and the status bytes stay in the context's scratch.
+static int lc_stereo_track(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int w, int h, int n_img, const float* d_kps,
+                           const int* d_count, int cap, const std::string& what, const float** next, const uint8_t** status) {
+  hipSetDevice(ctx->device);
+  const size_t np = (size_t)n_img * cap;
+  float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
+  float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
+  uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
+  if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, what + ": scratch allocation failed");
+  k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, ctx->stream>>>(d_kps, d_count, cap, p0, p1);
+  *next = p1, *status = stt;
+  return flvis_hip_lk_track(ctx, d_img0, d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
+}
+
 int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void* d_img1, int w, int h, int n_img, int cam_type, const LcCam* d_cams,
                               const int* d_cam_of, const float* d_kps, const uint8_t* d_desc, const int* d_count, int cap, float* d_lm_2d,
                               double* d_lm_3d, uint8_t* d_lm_desc, int* d_lm_count) {
@@ -1411,17 +1408,8 @@ int lc_keyframe_landmarks_dev(flvis_ctx* ctx, const uint8_t* d_img0, const void*
   const uint8_t* status = nullptr;
   if (cam_type == 0) {
     if (!d_img0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks: stereo needs img0, P0 and P1");
-    hipSetDevice(ctx->device);
-    const size_t np = (size_t)n_img * cap;
-    float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
-    float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
-    uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
-    if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks: scratch allocation failed");
-    k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, st>>>(d_kps, d_count, cap, p0, p1);
-    // calcOpticalFlowPyrLK(img0, img1, lm_img0, lm_img1, ., ., Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW)  (:274-278)
-    const int rc = flvis_hip_lk_track(ctx, d_img0, (const uint8_t*)d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
+    const int rc = lc_stereo_track(ctx, d_img0, (const uint8_t*)d_img1, w, h, n_img, d_kps, d_count, cap, "lc_keyframe_landmarks", &next, &status);
     if (rc != FLVIS_OK) return rc;
-    next = p1, status = stt;
   }
   k_lc_landmarks<<<n_img, LC_T, 0, st>>>(d_cams, d_cam_of, cam_type, w, h, d_kps, d_desc, d_count, cap, next, status, (const uint16_t*)d_img1,
                                          d_lm_2d, d_lm_3d, d_lm_desc, d_lm_count);
@@ -1452,20 +1440,14 @@ int lc_keyframe_landmarks_unrect_dev(flvis_ctx* ctx, const uint8_t* d_img0, cons
       n_img <= 0 || cap <= 0 || w <= 0 || h <= 0)
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "lc_keyframe_landmarks_unrect: bad args");
   if (cap > LC_MAXF) return ctx->fail(FLVIS_ERR_CAPACITY, "lc_keyframe_landmarks_unrect: at most 2048 keypoints per keyframe");
-  hipSetDevice(ctx->device);
-  hipStream_t st = ctx->stream;
-  const size_t np = (size_t)n_img * cap;
-  float* p0 = (float*)ctx->scratch("lc_pts0", sizeof(float) * 2 * np);
-  float* p1 = (float*)ctx->scratch("lc_pts1", sizeof(float) * 2 * np);
-  uint8_t* stt = (uint8_t*)ctx->scratch("lc_status", np);
-  if (!p0 || !p1 || !stt) return ctx->fail(FLVIS_ERR_HIP, "lc_keyframe_landmarks_unrect: scratch allocation failed");
-  k_lc_points<<<dim3((cap + 255) / 256, n_img), 256, 0, st>>>(d_kps, d_count, cap, p0, p1);
-  // the STEREO_RECT case's matcher, on the raw pair: Size(31,31), 5, (COUNT+EPS, 30, 0.001), OPTFLOW_USE_INITIAL_FLOW  (:274-278)
-  const int rc = flvis_hip_lk_track(ctx, d_img0, d_img1, w, h, n_img, p0, p1, stt, d_count, cap, 5, 30, 0.001, 1);
+  const float* next = nullptr;
+  const uint8_t* status = nullptr;
+  // the STEREO_RECT case's matcher, on the raw pair
+  const int rc = lc_stereo_track(ctx, d_img0, d_img1, w, h, n_img, d_kps, d_count, cap, "lc_keyframe_landmarks_unrect", &next, &status);
   if (rc != FLVIS_OK) return rc;
   // (d_lm_desc == d_desc is fine: every workgroup reads its keyframe's rows before the scan's barrier and writes after)
-  k_lc_landmarks_unrect<<<n_img, LC_T, 0, st>>>(d_cams, d_ucams, d_cam_of, d_kps, d_desc, d_count, cap, p1, stt, d_lm_2d, d_lm_3d, d_lm_desc,
-                                                 d_lm_count);
+  k_lc_landmarks_unrect<<<n_img, LC_T, 0, ctx->stream>>>(d_cams, d_ucams, d_cam_of, d_kps, d_desc, d_count, cap, next, status, d_lm_2d, d_lm_3d,
+                                                          d_lm_desc, d_lm_count);
   CHECK_LAUNCH(ctx, "lc_keyframe_landmarks_unrect");
   return FLVIS_OK;
 }

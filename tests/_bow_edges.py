@@ -1,5 +1,5 @@
 """Inputs that drive the bag-of-words transform (k_bow_words / voc_descend, k_bow_vector) and the L1 score kernels (bow_score_wave in
-k_bow_score, k_bow_score_jobs, k_bow_score_jobs_at) to their edges.  No GPU is needed here: tests/test_bow_edges_inputs.py checks every
+k_bow_score, k_bow_score_jobs<3> and <4>) to their edges.  No GPU is needed here: tests/test_bow_edges_inputs.py checks every
 recipe with the CPU oracle (oracle/ref_bow.cpp) and the plain-Python restatements of tests/_voc.py, and shows by restated alternative
 rules which mistake each recipe would catch; tests/test_gpu_bow_edges.py compares the kernels against what is built here.
 

@@ -273,6 +273,22 @@ def test_score_jobs_at_bit_exact(ctx, stores):
     assert np.array_equal(got, np.concatenate([w, w[1:]]))
 
 
+def test_score_jobs_is_score_jobs_at_with_out_first(ctx, stores):
+    """the two job calls are one kernel body at two job widths: (query, first, n) and (query, first, n, out = first) leave the same score
+    array bit for bit -- whole ranges, ranges of one, an empty range among others, every job empty"""
+    for name, ds in stores.items():
+        st = ds.st
+        nv = len(st.vectors)
+        whole = [(q,) + tuple(st.db[qn]) for qn, q in st.queries.items()]
+        ones = [(q, first + n - 1, 1) for q, first, n in whole]
+        empty = [(q, first, 0) for q, first, n in whole]
+        for jobs in (whole + empty[:1], ones, empty[-1:] + ones[:1], whole[:1], empty):
+            a = ctx.bow_score_jobs(jobs, ds.ids, ds.vals, ds.nnz).cpu().numpy()
+            b = ctx.bow_score_jobs_at([j + (j[1],) for j in jobs], ds.ids, ds.vals, ds.nnz, nv).cpu().numpy()
+            assert np.array_equal(a, b) and np.array_equal(_bits(a), _bits(b)), (name, jobs, np.nonzero(a != b)[0])
+            assert bool((a != -1.0).any()) == any(n for _, _, n in jobs), (name, jobs)
+
+
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------
 class RawOut:
     """sentinel-filled outputs of a raw flvis_hip_bow_transform call, GUARD entries behind their ends"""
