@@ -931,6 +931,19 @@ def load_config(yaml_path):
     return cfg
 
 
+def config_get_bool(yaml_path, key):
+    """flvis_config_get_bool: one boolean key of a yaml file as getBoolVariableFromYaml reads it (y/n, yes/no, true/false, on/off; lower,
+    Capitalised or UPPER).  FlvisError for a missing key or any other value.  Host-only."""
+    lib = load_library()
+    out = C.c_int(0)
+    err = C.create_string_buffer(256)
+    lib.flvis_config_get_bool.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    rc = lib.flvis_config_get_bool(yaml_path.encode(), key.encode(), C.byref(out), err, 256)
+    if rc != FLVIS_OK:
+        raise FlvisError("flvis_config_get_bool(%s, %s) failed (%d): %s" % (yaml_path, key, rc, err.value.decode()))
+    return bool(out.value)
+
+
 def _P(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -1748,6 +1761,67 @@ class Tracker:
     def local_map_reset(self, streams):
         """flvis_local_map_reset: KFMSG_CMD_RESET_LM for the named streams' local maps (what is queued ahead is processed first)."""
         self._stream_list(streams, "flvis_local_map_reset")
+
+    def local_map_cloud_enable(self, max_points):
+        """flvis_local_map_cloud_enable: keep every optimisation's multi-view landmarks on the device, max_points per stream (<= 0: off)."""
+        self.lib.flvis_local_map_cloud_enable.argtypes = [C.c_void_p, C.c_int64]
+        self.ctx._check(self.lib.flvis_local_map_cloud_enable(self.ctx._h, int(max_points)), "local_map_cloud_enable")
+
+    def local_map_cloud_clear(self, streams):
+        """flvis_local_map_cloud_clear: empties the named streams' records."""
+        self._stream_list(streams, "flvis_local_map_cloud_clear")
+
+    def local_map_cloud_info(self, stream):
+        """flvis_local_map_cloud_info -> dict(points, runs, dropped, capacity) of the stream's record."""
+        v = (C.c_int64 * 4)()
+        self.lib.flvis_local_map_cloud_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        self.ctx._check(self.lib.flvis_local_map_cloud_info(self.ctx._h, int(stream), v), "local_map_cloud_info")
+        return dict(points=int(v[0]), runs=int(v[1]), dropped=int(v[2]), capacity=int(v[3]))
+
+    def local_map_cloud(self, streams, mode="all", leaf=0.0, min_points=1, cap=None, host=False, ids=False):
+        """flvis_local_map_cloud: the named streams' recorded map clouds.  mode "all": every recorded entry in record order (the
+        reference's /map_cloud); "latest": one entry per landmark id, from the newest optimisation that lists it.  leaf = 0: every point
+        rounded to float; leaf > 0: one point per voxel of `leaf` metres holding min_points points or more (flvis_hip_voxel_cloud's rule).
+        cap: rows per stream (default: what the largest cloud yields, found by a call of its own).  host=True goes through the _host
+        entry.  ids=True (leaf 0 only): the rows' landmark ids.
+        -> (xyz [n] of float32 [k, 3], npts [n] of int32 [k], n_out int64 [n], n_dropped int64 [n]) and, with ids, ids [n] of int64 [k]."""
+        import numpy as np
+        import torch
+        modes = {"all": 0, "latest": 1}
+        m = modes[mode] if mode in modes else int(mode)
+        sl = [int(s) for s in streams]
+        n = len(sl)
+        arr = np.ascontiguousarray(sl + [0], np.int32)
+        if cap is None:
+            cap = int(max(list(self.local_map_cloud(sl, m, leaf, min_points, cap=0, host=host)[2]) + [0]))
+        cap = int(cap)
+        n_out, n_drop = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        shape = (max(n, 1), max(cap, 0))
+        args = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int]
+        head = (self.ctx._h, n, _P(arr, C.c_int), m, float(leaf), int(min_points), cap)
+        if host:
+            hx, hn, hi = np.zeros(shape + (3,), np.float32), np.zeros(shape, np.int32), np.zeros(shape, np.int64)
+            fn = self.lib.flvis_local_map_cloud_host
+            fn.argtypes = args + [C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            rc = fn(*head, _P(hx, C.c_float), _P(hn, C.c_int), _P(hi, C.c_int64) if ids else None, _P(n_out, C.c_int64), _P(n_drop, C.c_int64))
+            self.ctx._check(rc, "local_map_cloud_host")
+        else:
+            dev = self.ctx.device
+            xyz = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+            npts = torch.empty(shape, dtype=torch.int32, device=dev)
+            did = torch.empty(shape, dtype=torch.int64, device=dev) if ids else None
+            fn = self.lib.flvis_local_map_cloud
+            fn.argtypes = args + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            rc = fn(*head, _ptr(xyz), _ptr(npts), _ptr(did) if ids else None, _P(n_out, C.c_int64), _P(n_drop, C.c_int64))
+            self.ctx._check(rc, "local_map_cloud")
+            kmax = int(min(max(n_out[:n].max() if n else 0, 0), cap))
+            hx, hn = xyz[:, :kmax].cpu().numpy(), npts[:, :kmax].cpu().numpy()
+            hi = did[:, :kmax].cpu().numpy() if ids else None
+        k = [int(min(c, cap)) for c in n_out[:n]]
+        out = ([hx[g, :k[g]].copy() for g in range(n)], [hn[g, :k[g]].copy() for g in range(n)], n_out[:n].copy(), n_drop[:n].copy())
+        if ids:
+            out = out + ([hi[g, :k[g]].copy() for g in range(n)],)
+        return out
 
     def dropped_keyframes(self):
         """keyframes that met a full keyframe queue (flvis_get_counters_n [3]; 0 under the tracker's back-pressure)"""

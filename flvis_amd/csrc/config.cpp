@@ -4,6 +4,7 @@
 //   flvis_config_finalize  derives what TrackingNodeletClass::onInit derives (src/frontend/vo_tracking.cpp:155-306): camera
 //                          type, skip/equalise flags and the rectification R0,R1,P0,P1 of cv::stereoRectify(CALIB_ZERO_DISPARITY,
 //                          alpha = 0) restated from OpenCV 3.x's cvStereoRectify (external dependency of the reference).
+#include <cctype>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -477,4 +478,58 @@ extern "C" int flvis_config_load(const char* path, flvis_cfg* c, char* err, int 
   int rc = flvis_config_finalize(c);
   if (rc != FLVIS_OK) return fail("unsupported type_of_vi for this path");
   return FLVIS_OK;
+}
+
+// getBoolVariableFromYaml (yamlRead.h): YAML::LoadFile(path)[key].as<bool>() with yaml-cpp 0.6.2, whose convert<bool>::decode accepts the
+// scalars y/n, yes/no, true/false, on/off when they are entirely lower case, Capitalised or entirely UPPER case (IsFlexibleCase) and
+// throws on anything else.  The files are flat maps of "key: scalar" lines with '#' comments, as flvis_config_load reads them, and
+// this is a reader for such files, not yaml-cpp: a key matches at any indentation (a nested key would match too), and a line is cut
+// at its first '#' even inside quotes.
+extern "C" int flvis_config_get_bool(const char* path, const char* key, int* out, char* err, int errlen) {
+  auto fail = [&](const std::string& m) {
+    if (err && errlen > 0) snprintf(err, errlen, "%s", m.c_str());
+    return (int)FLVIS_ERR_CONFIG;
+  };
+  if (!path || !key || !out) return FLVIS_ERR_INVALID_ARG;
+  std::ifstream f(path);
+  if (!f) return fail(std::string("cannot open ") + path);
+  std::string line;
+  while (std::getline(f, line)) {
+    const size_t h = line.find('#');
+    if (h != std::string::npos) line = line.substr(0, h);
+    const size_t col = line.find(':');
+    if (col == std::string::npos) continue;
+    std::string k = line.substr(0, col);
+    const size_t a = k.find_first_not_of(" \t");
+    if (a == std::string::npos) continue;
+    k = k.substr(a);
+    k.erase(k.find_last_not_of(" \t") + 1);
+    if (k != key) continue;
+    std::string v = line.substr(col + 1);
+    const size_t b = v.find_first_not_of(" \t\r");
+    if (b == std::string::npos) return fail(std::string("yaml key ") + key + " has no value");
+    v = v.substr(b);
+    v.erase(v.find_last_not_of(" \t\r") + 1);
+    if (v.size() >= 2 && (v.front() == '"' || v.front() == '\'') && v.back() == v.front()) v = v.substr(1, v.size() - 2);
+    // IsFlexibleCase: lower, Capitalised (first upper, rest lower) or UPPER
+    auto all = [&](size_t from, int (*is)(int)) {
+      for (size_t i = from; i < v.size(); i++)
+        if (!is((unsigned char)v[i])) return false;
+      return true;
+    };
+    const bool flexible = !v.empty() && (all(0, islower) || all(0, isupper) || (isupper((unsigned char)v[0]) && all(1, islower)));
+    if (flexible) {
+      std::string low = v;
+      for (char& ch : low) ch = (char)tolower((unsigned char)ch);
+      static const char* names[4][2] = {{"y", "n"}, {"yes", "no"}, {"true", "false"}, {"on", "off"}};
+      for (auto& n : names)
+        for (int side = 0; side < 2; side++)
+          if (low == n[side]) {
+            *out = side == 0 ? 1 : 0;
+            return FLVIS_OK;
+          }
+    }
+    return fail(std::string("yaml key ") + key + ": '" + v + "' is not a boolean (y/n, yes/no, true/false, on/off)");
+  }
+  return fail(std::string("yaml key missing: ") + key);
 }

@@ -1,7 +1,9 @@
 // flvis_amd: a map's landmarks as one voxel-filtered point cloud (flvis_hip_voxel_cloud; include/flvis_hip.h has the definition).
 //
 // The reference's LocalMapNodeletClass publishes /map_cloud (vo_localmap.cpp:335-377, :458-461) and sets up a pcl::VoxelGrid of 0.08 m that it
-// never runs; this is that output for the loop closer's device-resident database, with the filter.
+// never runs.  The local map's own cloud is flvis_local_map_cloud (lm_cloud.hip), which ends in this call; the loop closer's database goes
+// through it as flvis_loop_closer_map_cloud.  The radix passes (mc_sort) and the call with landmark ids (mc_voxel_cloud) are shared with
+// lm_cloud.hip through map_cloud.hpp.
 //
 // Steps of one call (every cloud of the call goes through each of them together):
 //   k_mc_counts, k_mc_scan     the listed rows' clamped counts and their running sum: where each row's points start in canonical order
@@ -26,6 +28,7 @@
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
 #include "dev_math.hpp"
+#include "map_cloud.hpp"
 
 namespace {
 
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(256) void k_mc_cloud_starts(const long long* __rest
 __global__ __launch_bounds__(256) void k_mc_keys(const int* __restrict__ rows, const int* __restrict__ cnt, const long long* __restrict__ off,
                                                  const double* __restrict__ p3, const double* __restrict__ T7, int cap, double leaf,
                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, double* __restrict__ pts,
-                                                 int* __restrict__ occ) {
+                                                 int* __restrict__ occ, const long long* __restrict__ id_rows, long long* __restrict__ idc) {
   __shared__ uint8_t seen[MC_KEY_DIGITS * 256];
   const int tid = threadIdx.x;
   const int e = blockIdx.x, n = cnt[e];
@@ -163,6 +166,7 @@ __global__ __launch_bounds__(256) void k_mc_keys(const int* __restrict__ rows, c
     keys[i] = key;
     idx[i] = (uint32_t)i;
     pts[3 * i] = p.x, pts[3 * i + 1] = p.y, pts[3 * i + 2] = p.z;
+    if (id_rows) idc[i] = id_rows[(size_t)row * cap + lm];  // (mc_voxel_cloud: the points' ids, in canonical order like the points)
     if (key == MC_DROPPED) {
       seen[7 * 256 + 0x80] = 1;  // (a dropped point counts in the top byte alone: it must end up behind the voxels, nothing else)
     } else {
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(256) void k_mc_cloud_rank(McOut o, int n, const int
 
 __global__ __launch_bounds__(256) void k_mc_emit(McOut o, int n, const uint32_t* __restrict__ I, const double* __restrict__ pts,
                                                  const int* __restrict__ bpre, const int* __restrict__ cg, int out_cap, float* __restrict__ xyz,
-                                                 int* __restrict__ npts) {
+                                                 int* __restrict__ npts, const long long* __restrict__ idc, long long* __restrict__ id_out) {
   __shared__ int sc[256];
   const int tid = threadIdx.x;
   const long long base = (long long)blockIdx.x * MC_RB + tid * (MC_RB / 256);
@@ -363,6 +367,7 @@ __global__ __launch_bounds__(256) void k_mc_emit(McOut o, int n, const uint32_t*
     const double d = (double)cnt;
     xyz[3 * at] = (float)(sx / d), xyz[3 * at + 1] = (float)(sy / d), xyz[3 * at + 2] = (float)(sz / d);
     if (npts) npts[at] = cnt;
+    if (id_out) id_out[at] = idc[I[i]];  // (raw rows only: mc_voxel_cloud)
   }
 }
 
@@ -391,41 +396,74 @@ int mc_check(int n_rows, int cap, int n_clouds, const int* h_cloud_ptr, const in
   return FLVIS_OK;
 }
 
+void mc_tiling(int N, int& tiles_per_blk, int& nblk) {
+  const int n_tiles = (N + MC_TILE - 1) / MC_TILE;
+  tiles_per_blk = (n_tiles + MC_MAX_BLK - 1) / MC_MAX_BLK;
+  nblk = (n_tiles + tiles_per_blk - 1) / tiles_per_blk;
+}
+
 }  // namespace
 
-extern "C" {
+namespace flvis {
 
-int flvis_hip_voxel_cloud_info(int* h_info4) {
-  if (!h_info4) return FLVIS_ERR_INVALID_ARG;
-  h_info4[0] = MC_TILE;
-  h_info4[1] = MC_T;
-  h_info4[2] = MC_BYTES_PER_POINT;
-  h_info4[3] = MC_BYTES_PER_ROW;
+size_t mc_sort_table_ints(int N) {
+  int tiles_per_blk, nblk;
+  mc_tiling(N, tiles_per_blk, nblk);
+  return 256 * (size_t)nblk + 257;
+}
+
+// the passes: a key byte with two values or more; then, if any ran, the bytes of the cloud index that tell two non-empty clouds apart
+int mc_sort(flvis_ctx* ctx, const int* occ, uint64_t* const d_keys[2], uint32_t* const d_idx[2], int N, int n_clouds, const int* d_cstart,
+            const long long* cs, uint32_t* d_hist, int* cur_out, int* n_passes, int* n_cloud_digits) {
+  hipStream_t st = ctx->stream;
+  int tiles_per_blk, nblk;
+  mc_tiling(N, tiles_per_blk, nblk);
+  uint32_t* const d_tot = d_hist + 256 * (size_t)nblk;  // [257]
+  std::vector<McDigit> passes;
+  for (int d = 0; d < MC_KEY_DIGITS; d++) {
+    int used = 0;
+    for (int v = 0; v < 256; v++) used += occ[d * 256 + v] ? 1 : 0;
+    if (used > 1) passes.push_back(McDigit{8 * d, 0, n_clouds, d_cstart});
+  }
+  int cloud_digits = 0;
+  while (cloud_digits < 4 && ((long long)(n_clouds - 1) >> (8 * cloud_digits)) > 0) cloud_digits++;
+  if (!passes.empty())
+    for (int d = 0; d < cloud_digits; d++) {
+      int first = -1;
+      bool two = false;
+      for (int c = 0; c < n_clouds && !two; c++) {
+        if (cs[c + 1] == cs[c]) continue;
+        const int v = (c >> (8 * d)) & 255;
+        if (first < 0) first = v;
+        else two = v != first;
+      }
+      if (two) passes.push_back(McDigit{8 * d, 1, n_clouds, d_cstart});
+    }
+  int cur = 0;
+  for (const McDigit& g : passes) {
+    k_mc_hist<<<nblk, MC_T, 0, st>>>(d_keys[cur], d_idx[cur], N, tiles_per_blk, g, d_hist, nblk);
+    k_mc_scan_rows<<<256, 1024, 0, st>>>(d_hist, nblk, d_tot);
+    k_mc_scan<uint32_t, uint32_t><<<1, 1024, 0, st>>>(d_tot, 256LL, d_tot);
+    k_mc_scatter<<<nblk, MC_T, 0, st>>>(d_keys[cur], d_idx[cur], N, tiles_per_blk, g, d_hist, d_tot, nblk, d_keys[cur ^ 1], d_idx[cur ^ 1]);
+    MC_LAUNCH(ctx, "voxel_cloud: sort");
+    cur ^= 1;
+  }
+  *cur_out = cur;
+  if (n_passes) *n_passes = (int)passes.size();
+  if (n_cloud_digits) *n_cloud_digits = cloud_digits;
   return FLVIS_OK;
 }
 
-int flvis_voxel_cloud_check(int n_rows, int cap, int n_clouds, const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points,
-                            int out_cap) {
-  std::string why;
-  return mc_check(n_rows, cap, n_clouds, h_cloud_ptr, h_range2, leaf, min_points, out_cap, why);
-}
-
-int flvis_hip_voxel_cloud_stats(flvis_ctx* ctx, int64_t* h_stats4) {
-  if (!ctx) return FLVIS_ERR_INVALID_ARG;
-  if (!h_stats4) return ctx->fail(FLVIS_ERR_INVALID_ARG, "voxel_cloud_stats: NULL output");
-  memcpy(h_stats4, ctx->mc_stats, sizeof(ctx->mc_stats));
-  return FLVIS_OK;
-}
-
-int flvis_hip_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const double* d_T_c_w7, int n_rows, int cap, int n_clouds,
-                          const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
-                          int64_t* h_n_out, int64_t* h_n_dropped) {
+int mc_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const double* d_T_c_w7, int n_rows, int cap, int n_clouds,
+                   const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                   const long long* d_id_rows, long long* d_id_out, int64_t* h_n_out, int64_t* h_n_dropped) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
   if (!d_p3 || !d_count || !d_T_c_w7 || !h_n_out || (!d_xyz && out_cap != 0))
     return ctx->fail(FLVIS_ERR_INVALID_ARG, "voxel_cloud: a NULL required pointer");
   std::string why;
   int rc = mc_check(n_rows, cap, n_clouds, h_cloud_ptr, h_range2, leaf, min_points, out_cap, why);
   if (rc != FLVIS_OK) return ctx->fail(rc, "voxel_cloud: " + why);
+  if (d_id_out && (leaf != 0 || !d_id_rows)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "voxel_cloud: ids go with leaf == 0 only");
   // ---- the listed rows, cloud after cloud in the caller's order: [eptr (n_clouds + 1) | rows (R)]
   long long R64 = 0;
   for (int r = 0; r < h_cloud_ptr[n_clouds]; r++) R64 += h_range2[2 * r + 1];
@@ -498,49 +536,28 @@ int flvis_hip_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count
   int* const d_bsum = (int*)(d_tot + 257);
   e = hipMemsetAsync(d_occ, 0, sizeof(int) * MC_KEY_DIGITS * 256, st);
   if (e != hipSuccess) return ctx->hip_fail(e, "voxel_cloud");
-  k_mc_keys<<<R, 256, 0, st>>>(d_rows, d_cnt, d_off, d_p3, d_T_c_w7, cap, leaf, d_keys[0], d_idx[0], d_pts, d_occ);
+  long long* d_idc = nullptr;  // the points' ids in canonical order (only for a caller that wants the rows' ids)
+  if (d_id_out) {
+    d_idc = (long long*)ctx->scratch("mc_ids", sizeof(long long) * (size_t)N);
+    if (!d_idc) return no_mem();
+  }
+  k_mc_keys<<<R, 256, 0, st>>>(d_rows, d_cnt, d_off, d_p3, d_T_c_w7, cap, leaf, d_keys[0], d_idx[0], d_pts, d_occ, d_idc ? d_id_rows : nullptr,
+                               d_idc);
   MC_LAUNCH(ctx, "voxel_cloud: keys");
   int occ[MC_KEY_DIGITS * 256];
   e = hipMemcpyAsync(occ, d_occ, sizeof(occ), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return ctx->hip_fail(e, "voxel_cloud: keys");
-  // ---- the passes: a key byte with two values or more; then, if any ran, the bytes of the cloud index that tell two non-empty clouds apart
-  std::vector<McDigit> passes;
-  for (int d = 0; d < MC_KEY_DIGITS; d++) {
-    int used = 0;
-    for (int v = 0; v < 256; v++) used += occ[d * 256 + v] ? 1 : 0;
-    if (used > 1) passes.push_back(McDigit{8 * d, 0, n_clouds, d_cstart});
-  }
-  int cloud_digits = 0;
-  while (cloud_digits < 4 && ((long long)(n_clouds - 1) >> (8 * cloud_digits)) > 0) cloud_digits++;
-  if (!passes.empty())
-    for (int d = 0; d < cloud_digits; d++) {
-      int first = -1;
-      bool two = false;
-      for (int c = 0; c < n_clouds && !two; c++) {
-        if (cs[c + 1] == cs[c]) continue;
-        const int v = (c >> (8 * d)) & 255;
-        if (first < 0) first = v;
-        else two = v != first;
-      }
-      if (two) passes.push_back(McDigit{8 * d, 1, n_clouds, d_cstart});
-    }
-  int cur = 0;
-  for (const McDigit& g : passes) {
-    k_mc_hist<<<nblk, MC_T, 0, st>>>(d_keys[cur], d_idx[cur], N, tiles_per_blk, g, d_hist, nblk);
-    k_mc_scan_rows<<<256, 1024, 0, st>>>(d_hist, nblk, d_tot);
-    k_mc_scan<uint32_t, uint32_t><<<1, 1024, 0, st>>>(d_tot, 256LL, d_tot);
-    k_mc_scatter<<<nblk, MC_T, 0, st>>>(d_keys[cur], d_idx[cur], N, tiles_per_blk, g, d_hist, d_tot, nblk, d_keys[cur ^ 1], d_idx[cur ^ 1]);
-    MC_LAUNCH(ctx, "voxel_cloud: sort");
-    cur ^= 1;
-  }
+  int cur = 0, n_passes = 0, cloud_digits = 0;
+  rc = mc_sort(ctx, occ, d_keys, d_idx, N, n_clouds, d_cstart, cs.data(), d_hist, &cur, &n_passes, &cloud_digits);
+  if (rc != FLVIS_OK) return rc;
   // ---- the rows
   const McOut o{d_keys[cur], d_cstart, d_kend, n_clouds, leaf == 0 ? 1 : 0, min_points};
   k_mc_bounds<<<(n_clouds + 255) / 256, 256, 0, st>>>(d_keys[cur], d_cstart, n_clouds, d_kend);
   k_mc_flags<<<n_chunks, 256, 0, st>>>(o, N, d_bsum);
   k_mc_scan<int, int><<<1, 1024, 0, st>>>(d_bsum, (long long)n_chunks, d_bsum);
   k_mc_cloud_rank<<<NC1, 256, 0, st>>>(o, N, d_bsum, d_cg);
-  if (out_cap > 0) k_mc_emit<<<n_chunks, 256, 0, st>>>(o, N, d_idx[cur], d_pts, d_bsum, d_cg, out_cap, d_xyz, d_npts);
+  if (out_cap > 0) k_mc_emit<<<n_chunks, 256, 0, st>>>(o, N, d_idx[cur], d_pts, d_bsum, d_cg, out_cap, d_xyz, d_npts, d_idc, d_id_out);
   MC_LAUNCH(ctx, "voxel_cloud: rows");
   std::vector<int> back(2 * (size_t)NC1);  // kend | cg (adjacent on the device)
   e = hipMemcpyAsync(back.data(), d_kend, sizeof(int) * back.size(), hipMemcpyDeviceToHost, st);
@@ -550,10 +567,42 @@ int flvis_hip_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count
     h_n_out[c] = (int64_t)back[(size_t)NC1 + c + 1] - back[(size_t)NC1 + c];
     if (h_n_dropped) h_n_dropped[c] = cs[c + 1] - back[c];
   }
-  ctx->mc_stats[0] = (int64_t)passes.size();
-  ctx->mc_stats[1] = MC_KEY_DIGITS + cloud_digits - (int64_t)passes.size();
+  ctx->mc_stats[0] = n_passes;
+  ctx->mc_stats[1] = MC_KEY_DIGITS + cloud_digits - n_passes;
   ctx->mc_stats[2] = (int64_t)(pt_bytes + rows_bytes + sizeof(int) * tab_ints);
   ctx->mc_stats[3] = N;
   return FLVIS_OK;
+}
+
+}  // namespace flvis
+extern "C" {
+
+int flvis_hip_voxel_cloud_info(int* h_info4) {
+  if (!h_info4) return FLVIS_ERR_INVALID_ARG;
+  h_info4[0] = MC_TILE;
+  h_info4[1] = MC_T;
+  h_info4[2] = MC_BYTES_PER_POINT;
+  h_info4[3] = MC_BYTES_PER_ROW;
+  return FLVIS_OK;
+}
+
+int flvis_voxel_cloud_check(int n_rows, int cap, int n_clouds, const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points,
+                            int out_cap) {
+  std::string why;
+  return mc_check(n_rows, cap, n_clouds, h_cloud_ptr, h_range2, leaf, min_points, out_cap, why);
+}
+
+int flvis_hip_voxel_cloud_stats(flvis_ctx* ctx, int64_t* h_stats4) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  if (!h_stats4) return ctx->fail(FLVIS_ERR_INVALID_ARG, "voxel_cloud_stats: NULL output");
+  memcpy(h_stats4, ctx->mc_stats, sizeof(ctx->mc_stats));
+  return FLVIS_OK;
+}
+
+int flvis_hip_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const double* d_T_c_w7, int n_rows, int cap, int n_clouds,
+                          const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                          int64_t* h_n_out, int64_t* h_n_dropped) {
+  return flvis::mc_voxel_cloud(ctx, d_p3, d_count, d_T_c_w7, n_rows, cap, n_clouds, h_cloud_ptr, h_range2, leaf, min_points, out_cap, d_xyz, d_npts,
+                               nullptr, nullptr, h_n_out, h_n_dropped);
 }
 }

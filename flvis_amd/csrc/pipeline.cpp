@@ -25,6 +25,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "lm_cloud.hpp"
 #include "track_kernels.hpp"
 
 namespace flvis {
@@ -118,6 +119,7 @@ struct Lane {
   // frame counts at which any stream of the lane had one appended, for the back-pressure (lane_backpressure_depth)
   std::vector<long long> cmd_frame;
   std::vector<long long> cmd_steps;
+  int lmc_cmds = 0;              // reset calls that appended a command since the lane's last local-map launch (local_map_work)
   bool cmd_since_frame = false;  // a command was appended since the lane's last frame (a frame without the local map applies it: k_kfq_drop)
 };
 
@@ -208,6 +210,10 @@ struct Pipeline {
   bool flag_joins = false;                    // FLVIS_JOIN=flag
   bool fold_joins = false;                    // FLVIS_JOIN_FOLD: the chain's own kernels wait for / store the words (KJoin)
   bool chain_continuous = false;              // this frame follows the previous one on the main stream with nothing of the caller's in between
+  // flvis_local_map_cloud_enable: the streams' map-cloud records (cap 0: off, and no k_lm_cloud_append is launched) and the event that
+  // orders the context's stream behind the tracker's for a fetch
+  LmCloudRec lmc{};
+  hipEvent_t lmc_ev = nullptr;
   Lane& lane_of(int stream, int& local) {
     const int k = stream / lane_size;
     local = stream - k * lane_size;
@@ -396,6 +402,13 @@ extern "C" long long flvis_pipeline_ba_overflow_internal(flvis_ctx* ctx) {
   return v;
 }
 
+static void lm_cloud_free(Pipeline* pl) {
+  if (pl->lmc.hdr) hipFree(pl->lmc.hdr);
+  if (pl->lmc.ids) hipFree(pl->lmc.ids);
+  if (pl->lmc.pts) hipFree(pl->lmc.pts);
+  pl->lmc = LmCloudRec{};
+}
+
 extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
   if (!ctx || !ctx->pipe) return;
   Pipeline* pl = ctx->pipe;
@@ -423,6 +436,8 @@ extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
       if (fp) hipHostFree(fp);
   }
   if (pl->ev_in) hipEventDestroy(pl->ev_in);
+  if (pl->lmc_ev) hipEventDestroy(pl->lmc_ev);
+  lm_cloud_free(pl);
   for (void* p : pl->allocs) hipFree(p);
   delete pl;
   ctx->pipe = nullptr;
@@ -1181,6 +1196,37 @@ static bool fold_post(Pipeline* pl, Lane* L, hipEvent_t ev, KJoin& kj) {
   return true;
 }
 
+// the lane's part of the map-cloud record, and its append kernel behind a local-map launch of the lane on `bs`
+static LmCloudRec lane_lmc(const Pipeline* pl, const Lane* L) {
+  LmCloudRec r = pl->lmc;
+  r.hdr += (size_t)L->s0 * LMC_HDR;
+  r.ids += (size_t)L->s0 * r.cap;
+  r.pts += (size_t)L->s0 * r.cap * 3;
+  return r;
+}
+// The worker of one local-map launch on `bs`.  Record off: k_ba_worker as ever.  Record on: every optimisation must be looked at
+// before the next one of its stream overwrites the correction, and k_lm_cloud_append can only run between two kernels.  So a worker
+// then takes ONE queue entry per stream (ba_drain 1: at most one optimisation) with the append kernel behind it, `pairs` times -- as
+// many entries as the one launch would have taken -- and nothing else of the lane's local map runs meanwhile (launch_local_map orders
+// the lane's launches one behind the other; the other callers wait on the host).  An owner still stays past its share at KFQ / 2
+// waiting entries, the back-pressure's last resort; that is out of reach here: a launch takes what the frames since the previous
+// launch can have queued.
+static void local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int slot, int pairs, hipEvent_t prof_end) {
+  if (pl->lmc.cap <= 0) {
+    launch_ba_worker(bs, L->pipe, slot, ++L->ba_tag);
+    if (prof_end) hipEventRecord(prof_end, bs);
+    return;
+  }
+  Pipe one = L->pipe;
+  one.ba_drain = 1;
+  const LmCloudRec r = lane_lmc(pl, L);
+  for (int k = 0; k < pairs; k++) {
+    launch_ba_worker(bs, one, slot, ++L->ba_tag);
+    if (prof_end && k == 0) hipEventRecord(prof_end, bs);
+    launch_lm_cloud_append(bs, one, r);
+  }
+}
+
 static void launch_local_map(Pipeline* pl, Lane* L, hipEvent_t ev, bool record, hipEvent_t* prof_begin_end) {
   const int bi = (L->idx * pl->nba_lane + (int)(L->ba_launches % pl->nba_lane)) % pl->nba;
   hipStream_t bs = pl->ba_stream[bi];
@@ -1191,9 +1237,13 @@ static void launch_local_map(Pipeline* pl, Lane* L, hipEvent_t ev, bool record, 
   }
   if (record) join_signal(pl, L, ev, L->st);
   join_wait(pl, L, bs, ev);
+  // record on: behind the lane's previous launch and its append kernel (it ran on the lane's other local-map stream)
+  const bool rec_on = pl->lmc.cap > 0;
+  if (rec_on && L->ba_launches > 0) join_wait(pl, L, bs, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
   if (prof_begin_end) hipEventRecord(prof_begin_end[0], bs);
-  launch_ba_worker(bs, L->pipe, bi, ++L->ba_tag);
-  if (prof_begin_end) hipEventRecord(prof_begin_end[1], bs);
+  // (a reset command takes a queue entry like a keyframe, at most one per stream and frame)
+  local_map_work(pl, L, bs, bi, pl->ba_every + std::min(L->lmc_cmds, pl->ba_every), prof_begin_end ? prof_begin_end[1] : nullptr);
+  L->lmc_cmds = 0;
   join_signal(pl, L, L->ev_ba_done[L->ba_launches % Lane::BAQ], bs);
   L->ba_launches++;
   L->ba_pending = false;
@@ -1228,7 +1278,7 @@ static void sync_all(flvis_ctx* ctx) {
       bool pending = false;
       for (int i = 0; i < L->S; i++) pending = pending || hd[i] != tl[i];
       if (!pending) break;
-      launch_ba_worker(pl->ba_stream[0], L->pipe, 0, ++L->ba_tag);
+      local_map_work(pl, L, pl->ba_stream[0], 0, 1, nullptr);
       hipStreamSynchronize(pl->ba_stream[0]);
     }
   }
@@ -2355,6 +2405,7 @@ static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, c
     }
     if (todo.empty()) continue;
     if (new_cmd) {
+      L->lmc_cmds++;
       // the command takes a queue entry: the back-pressure of a keyframe append, counting it (lane_backpressure_depth)
       if (L->cmd_steps.empty() || L->cmd_steps.back() != L->frames_uploaded) L->cmd_steps.push_back(L->frames_uploaded);
       L->cmd_since_frame = true;
@@ -2395,6 +2446,99 @@ int flvis_reset_streams_rigs(flvis_ctx* ctx, int n, const int* streams, const fl
 }
 
 int flvis_local_map_reset(flvis_ctx* ctx, int n, const int* streams) { return reset_impl(ctx, n, streams, false, "local_map_reset"); }
+
+// ---- the local map's sparse map cloud: the record (include/flvis_hip.h; the kernels and the fetch are lm_cloud.hip's)
+int flvis_local_map_cloud_enable(flvis_ctx* ctx, int64_t max_points) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  Pipeline* pl = ctx->pipe;
+  if (!pl) return ctx->fail(FLVIS_ERR_INVALID_ARG, "local_map_cloud_enable: no tracker (flvis_tracker_create)");
+  if (max_points > (int64_t)INT_MAX) return ctx->fail(FLVIS_ERR_CAPACITY, "local_map_cloud_enable: max_points >= 2^31");
+  hipSetDevice(ctx->device);
+  sync_all(ctx);  // (no append kernel is in flight when its record goes away)
+  lm_cloud_free(pl);
+  if (max_points <= 0) return FLVIS_OK;
+  const size_t S = (size_t)pl->S, cap = (size_t)max_points;
+  LmCloudRec r{};
+  r.cap = (long long)max_points;
+  if (hipMalloc((void**)&r.hdr, sizeof(long long) * LMC_HDR * S) != hipSuccess || hipMalloc((void**)&r.ids, sizeof(long long) * S * cap) != hipSuccess ||
+      hipMalloc((void**)&r.pts, sizeof(double) * 3 * S * cap) != hipSuccess) {
+    (void)hipGetLastError();
+    pl->lmc = r;
+    lm_cloud_free(pl);
+    return ctx->fail(FLVIS_ERR_HIP, "local_map_cloud_enable: device allocation failed");
+  }
+  pl->lmc = r;
+  for (Lane* L : pl->lanes) launch_lm_cloud_init(ctx->stream, L->pipe, lane_lmc(pl, L), 0, L->S);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, "local_map_cloud_enable");
+  return FLVIS_OK;
+}
+
+int flvis_local_map_cloud_clear(flvis_ctx* ctx, int n, const int* streams) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  Pipeline* pl = ctx->pipe;
+  if (!pl || pl->lmc.cap <= 0) return ctx->fail(FLVIS_ERR_INVALID_ARG, "local_map_cloud_clear: no tracker, or its record is off");
+  if (n < 0 || (n > 0 && !streams)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "local_map_cloud_clear: bad stream list");
+  for (int i = 0; i < n; i++)
+    if (streams[i] < 0 || streams[i] >= pl->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, "local_map_cloud_clear: stream out of range");
+  if (n == 0) return FLVIS_OK;
+  hipSetDevice(ctx->device);
+  sync_all(ctx);
+  for (int i = 0; i < n; i++) {
+    int ls;
+    Lane& L = pl->lane_of(streams[i], ls);
+    launch_lm_cloud_init(ctx->stream, L.pipe, lane_lmc(pl, &L), ls, 1);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, "local_map_cloud_clear");
+  return FLVIS_OK;
+}
+
+}  // extern "C"
+namespace flvis {
+// what == nullptr: the checks alone
+int lm_cloud_settle(flvis_ctx* ctx, const char* what, LmCloudRec& rec, int& S) {
+  Pipeline* pl = ctx->pipe;
+  if (!pl || pl->lmc.cap <= 0) return FLVIS_ERR_INVALID_ARG;
+  rec = pl->lmc;
+  S = pl->S;
+  if (!what) return FLVIS_OK;
+  for (Lane* L : pl->lanes)
+    if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a launch deferred into the next frame: there is none)
+  if (!pl->lmc_ev && hipEventCreateWithFlags(&pl->lmc_ev, Pipeline::ev_flags) != hipSuccess) return ctx->hip_fail(hipGetLastError(), what);
+  // the context's stream behind the lanes' tracking streams (a reset's kernel) and the local-map streams (the workers, their append kernels)
+  auto behind = [&](hipStream_t s) {
+    if (!s || s == ctx->stream) return;
+    hipEventRecord(pl->lmc_ev, s);
+    hipStreamWaitEvent(ctx->stream, pl->lmc_ev, 0);
+  };
+  for (Lane* L : pl->lanes) behind(L->st);
+  for (int k = 0; k < Pipeline::NBA; k++) behind(pl->ba_stream[k]);
+  // what the last launches left unrecorded (a window that was owned when its append kernel looked), and a reset not yet applied
+  for (Lane* L : pl->lanes) launch_lm_cloud_append(ctx->stream, L->pipe, lane_lmc(pl, L));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  return FLVIS_OK;
+}
+}  // namespace flvis
+extern "C" {
+
+int flvis_local_map_cloud_info(flvis_ctx* ctx, int stream, int64_t* h_info4) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  LmCloudRec rec{};
+  int S = 0;
+  if (!h_info4 || lm_cloud_settle(ctx, nullptr, rec, S) != FLVIS_OK || stream < 0 || stream >= S)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, "local_map_cloud_info: no tracker, its record is off, or bad arguments");
+  hipSetDevice(ctx->device);
+  const int rc = lm_cloud_settle(ctx, "local_map_cloud_info", rec, S);
+  if (rc != FLVIS_OK) return rc;
+  long long h[LMC_HDR];
+  hipError_t e = hipMemcpyAsync(h, rec.hdr + (size_t)stream * LMC_HDR, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, "local_map_cloud_info");
+  h_info4[0] = h[LMC_POINTS], h_info4[1] = h[LMC_RUNS], h_info4[2] = h[LMC_DROPPED], h_info4[3] = rec.cap;
+  return FLVIS_OK;
+}
 
 // test aid: the tracker's pyramid construction on its own (see include/flvis_hip.h for the layout of d_out)
 int flvis_debug_pyramid(flvis_ctx* ctx, const uint8_t* d_src, int w, int h, int n_img, int levels, int bx, int by, int ingest, uint8_t* d_out,
@@ -2618,7 +2762,7 @@ static int ba_push_impl(flvis_ctx* ctx, int stream, int64_t frame_id, const doub
   L.cmd_frame[ls] = -1;  // (a reset command queued before this keyframe is no longer the last entry)
   hipMemcpy(L.pipe.kfq_kf + ls, &tl, sizeof(unsigned), hipMemcpyHostToDevice);
   hipMemcpy(&L.pipe.corr[ls].valid, &zero, sizeof(int), hipMemcpyHostToDevice);
-  launch_ba_worker(pl->ba_stream[0], L.pipe, 0, ++L.ba_tag);
+  local_map_work(pl, &L, pl->ba_stream[0], 0, 1, nullptr);
   hipError_t e = hipStreamSynchronize(pl->ba_stream[0]);
   if (e != hipSuccess) return ctx->hip_fail(e, "ba_push_keyframe");
   sync_all(ctx);

@@ -426,6 +426,12 @@ typedef struct flvis_frame_out {
 
 int flvis_config_load(const char* yaml_path, flvis_cfg* cfg, char* err, int errlen);
 int flvis_config_finalize(flvis_cfg* cfg);
+/* One boolean key of the same yaml file, as getBoolVariableFromYaml reads it (yamlRead.h: yaml-cpp 0.6.2 as<bool>): the plain scalars
+ * y / n, yes / no, true / false, on / off, each all lower case, Capitalised or all UPPER case.  *out = 1 or 0.  The keys the nodelets read
+ * this way and flvis_cfg does not carry: output_sparse_map (vo_localmap.cpp: flvis_local_map_cloud is that output), is_lite_version.
+ * FLVIS_ERR_CONFIG with a message in err: the file cannot be opened, the key is missing, the value is anything else (mixed case, a number,
+ * nothing).  FLVIS_ERR_INVALID_ARG: a NULL path, key or out.  Host only. */
+int flvis_config_get_bool(const char* yaml_path, const char* key, int* out, char* err, int errlen);
 
 /* CameraFrame::recover3DPts_c_FromStereo (src/processing/camera_frame.cpp:93-180) in ONE call -- the kernel-level drop-in a
  * configs[1] integrator (the reference's own frame loop, HIP pieces underneath) puts in its place: the stereo matcher's seeds
@@ -717,6 +723,62 @@ int flvis_reset_streams_rigs(flvis_ctx* ctx, int n, const int* streams, const fl
  * The keyframe getters still return the stream's last keyframe.  Enqueued in stream order, in order with the keyframes; does not
  * wait for the device.  Arguments and errors as flvis_reset_streams. */
 int flvis_local_map_reset(flvis_ctx* ctx, int n, const int* streams);
+/* ---- the local map's sparse map cloud (/map_cloud, vo_localmap.cpp:329-377, :454-461; yaml key output_sparse_map) ----------------------
+ * With output_sparse_map set the reference appends the optimised position of every multi-view landmark (bag->getMultiViewLMs(lms, 4)) to
+ * `map` after each window optimisation and publishes the growing cloud.  Those are the lm_id / lm_3d of the CorrectionInf, which the next
+ * optimisation overwrites (flvis_get_correction returns the last one).  The record keeps them on the device, per stream, without the host:
+ * a small kernel behind every local-map launch (frame path, flvis_ba_push_keyframe*, the drains) appends the correction of a stream whose
+ * window has optimised since the kernel last looked.  Opt-in: with the record off nothing is launched and nothing changes.
+ * With the record on, every optimisation is looked at before the stream's next one overwrites it: a local-map launch then consists of
+ * workers that take one keyframe per stream, each with the append kernel behind it (as many as the one worker would have taken
+ * keyframes: FLVIS_BA_EVERY), and a lane's launches run one behind the other instead of overlapping on its two HIP streams.  That
+ * order, not the kernel, is what the record costs: 6.8 % of the frame rate at 64 streams (profiles/r22_local_map_cloud.md).
+ *
+ * flvis_local_map_cloud_enable: after flvis_tracker_create(_rigs).  Room for max_points entries per stream (landmark id int64 + position
+ *   3 doubles, the optimiser's own values: 32 bytes) and a header per stream.  max_points <= 0 switches the record off and frees it;
+ *   enabling again, with the same capacity or another, starts empty.  Corrections from before the call are not recorded.  Waits for the
+ *   device.  FLVIS_ERR_INVALID_ARG without a tracker, FLVIS_ERR_CAPACITY for max_points >= 2^31, FLVIS_ERR_HIP if the allocation fails
+ *   (the record is then off).
+ * A stream's record is at any time the concatenation of (lm_id[i], lm_3d[i]), i < lm_count, over a prefix of the stream's optimisations
+ *   in order: what flvis_get_correction would have returned after each, in getMultiViewLMs order -- the reference's map->points.push_back
+ *   order, duplicates across optimisations included.  An optimisation whose points do not fit whole is not recorded at all and counted as
+ *   dropped; after the first dropped one nothing more is recorded until the stream is cleared (every later optimisation counts as
+ *   dropped).  Capacity is the only cause.  (Should the kernel ever find that a window ran twice between two looks -- the launch
+ *   order above excludes it -- it counts those runs as dropped too rather than leave a silent gap.)
+ * flvis_local_map_reset (KFMSG_CMD_RESET_LM, which leaves `map` alone) leaves the record as it is, later optimisations append behind it.
+ *   flvis_reset_streams(_rigs) empties the record of each named stream, and of no other, in order with the reset: nothing the old
+ *   sequence's window still finishes is recorded.
+ * flvis_local_map_cloud_clear: empties the named streams' records (points, runs, dropped).  Waits for the device.  Errors as
+ *   flvis_reset_streams, and FLVIS_ERR_INVALID_ARG with the record off.
+ * flvis_local_map_cloud_info: h_info4 = points recorded, optimisations recorded, optimisations dropped, capacity.  Waits for what is
+ *   queued; does not drain the keyframe queues (flvis_get_local_map_counts does).
+ *
+ * flvis_local_map_cloud: the records of the n listed streams as n clouds.
+ *   mode FLVIS_LM_CLOUD_ALL: every recorded entry, in record order -- the reference's cloud.  FLVIS_LM_CLOUD_LATEST: one entry per landmark
+ *   id, the one from the newest recorded optimisation that lists the id, the survivors in record order (ids recur, and not in adjacent
+ *   optimisations only: a landmark's view count falls below 4 and rises again).
+ *   The selected entries of stream h_stream[c] are cloud c of flvis_hip_voxel_cloud: one row of fp64 points in canonical (record) order
+ *   under an identity pose.  leaf, min_points, out_cap, d_xyz [n][out_cap][3], d_npts [n][out_cap] (may be NULL), h_n_out [n] (full
+ *   counts; the first out_cap rows are written), h_n_dropped [n] (may be NULL: points that are not finite or outside the voxel range) and
+ *   the rounding to float are that call's, bit for bit.  leaf == 0 is the reference's raw output: every point, rounded once to float.
+ *   d_id [n][out_cap] (may be NULL; leaf == 0 only): the landmark id of each row.
+ *   Several streams in one call give, stream for stream, the bits of single calls; a second call gives the same bits.  A stream with an
+ *   empty record gives h_n_out = 0.  The call waits for its own counts (the _host form: and for its rows) and for nothing else; the
+ *   tracker's and the local map's queued work is ordered ahead of it on the device.  No effect a caller can observe on tracking,
+ *   corrections or the record.
+ *   _host: h_xyz / h_npts / h_id are host arrays of the same shapes; the rows below min(h_n_out, out_cap) are written.
+ *   FLVIS_ERR_INVALID_ARG before anything is queued: no tracker or the record is off; n <= 0; a NULL h_stream or h_n_out; a stream out of
+ *   range or listed twice; an unknown mode; d_id with leaf > 0; leaf < 0 or not finite, min_points < 1, out_cap < 0, NULL rows with
+ *   out_cap > 0.  FLVIS_ERR_CAPACITY: the listed records hold 2^31 entries or more together. */
+#define FLVIS_LM_CLOUD_ALL    0
+#define FLVIS_LM_CLOUD_LATEST 1
+int flvis_local_map_cloud_enable(flvis_ctx* ctx, int64_t max_points);
+int flvis_local_map_cloud_clear(flvis_ctx* ctx, int n, const int* streams);
+int flvis_local_map_cloud_info(flvis_ctx* ctx, int stream, int64_t* h_info4);
+int flvis_local_map_cloud(flvis_ctx* ctx, int n, const int* h_stream, int mode, double leaf, int min_points, int out_cap, float* d_xyz,
+                          int* d_npts, int64_t* d_id, int64_t* h_n_out, int64_t* h_n_dropped);
+int flvis_local_map_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, int mode, double leaf, int min_points, int out_cap, float* h_xyz,
+                               int* h_npts, int64_t* h_id, int64_t* h_n_out, int64_t* h_n_dropped);
 /* Counters: [0] frames fed, [1] keyframes, [2] BA runs.  Cumulative over the context's work: a stream reset does not take them back. */
 int flvis_get_counters(flvis_ctx* ctx, int64_t* h_counters3);
 /* The first n (1 .. 4) of: [0] frames fed, [1] keyframes, [2] BA runs, [3] keyframes dropped at a full keyframe queue -- what the
@@ -1048,7 +1110,9 @@ int flvis_lc_link_reverse(const flvis_lc_link* in, flvis_lc_link* out);
 
 /* ---- a map as points: landmarks of many keyframes in the map frame, one point per occupied voxel ---------------------------------------
  * (LocalMapNodeletClass publishes /map_cloud, vo_localmap.cpp:335-377 and :458-461, and sets up a pcl::VoxelGrid with an 0.08 m leaf that it
- * never runs: the raw cloud goes out.  leaf = 0 is that output; leaf > 0 is the filter, by this project's own rule.)
+ * never runs: the raw cloud goes out.  leaf = 0 is that rounding; leaf > 0 is the filter, by this project's own rule.  This call is the
+ * filter on caller arrays.  The local map's own cloud is flvis_local_map_cloud, which ends in this call; the loop closer's ORB landmarks
+ * go through it as flvis_loop_closer_map_cloud -- a different map, of a nodelet the EuRoC launch does not load.)
  * Input: n_rows rows of up to cap points.  d_p3 [n_rows][cap][3] doubles in the row's camera frame; d_count [n_rows] (a negative count is
  * read as 0, one above cap as cap); d_T_c_w7 [n_rows][7] tx ty tz qx qy qz qw, the row's T_c_w.  A cloud is the concatenation of row
  * ranges: h_range2 [h_cloud_ptr[n_clouds]][2] = (first row, row count), cloud c owns the ranges h_cloud_ptr[c] .. h_cloud_ptr[c + 1].

@@ -5,6 +5,7 @@
   run_sequence.py <sequence folder> <config yaml> <out.txt> [--backend hip|cpu] [--frames N] [--local-map] [--imu-out <est.txt>]
                   [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]
                    [--lc-stereo-unrect]]
+                  [--local-map --lm-cloud <cloud.ply> [--lm-cloud-mode all|latest] [--leaf 0.08]]
 
 --imu-out : rigs with an IMU: additionally the IMU-rate trajectory of F2FTracking::imu_feed's outputs (pos_w_i, q_w_i per sample) -- the
 /imu_pose topic, which is what the reference's EuRoC launch file records as est.txt (launch/flvis_euroc_mav.launch:83-103) and scores;
@@ -26,7 +27,15 @@ the checker composed from the oracle's functions, tests/_lc_unrect.py).
 
 --map-cloud : (hip) the corrected map next to the corrected keyframe path: the landmarks of every keyframe in the map frame, one point per
 voxel of --leaf metres (0: every landmark, what the reference's /map_cloud carries), as ASCII PLY with the voxels' point counts
-(flvis_loop_closer_map_cloud, flvis_amd.traj_io.write_ply)."""
+(flvis_loop_closer_map_cloud, flvis_amd.traj_io.write_ply).
+
+--lm-cloud : (hip, with --local-map) the local map's own /map_cloud, which the reference publishes when the yaml says
+output_sparse_map: True (vo_localmap.cpp:329-377): the optimised multi-view landmarks of every window optimisation, kept on the device
+(flvis_local_map_cloud_enable) and fetched once at the end (flvis_local_map_cloud), as ASCII PLY.  --lm-cloud-mode all: every recorded
+estimate, the reference's cloud; latest: each landmark's newest estimate.  --leaf is shared with --map-cloud and defaults to 0.08: the
+file is then the voxel-filtered cloud; the reference's raw /map_cloud, point for point, is --lm-cloud-mode all --leaf 0.
+--lm-cloud-points: the record's capacity in points (32 bytes each; default 2^22), which the device record needs up front; a run that
+outgrows it is reported as runs_dropped in the JSON line.  When the yaml sets the key and no file is named, the JSON line says so."""
 import argparse
 import json
 import os
@@ -53,6 +62,9 @@ def main():
     ap.add_argument("--map-cloud", default=None)
     ap.add_argument("--leaf", type=float, default=0.08)
     ap.add_argument("--lc-stereo-unrect", action="store_true")
+    ap.add_argument("--lm-cloud", default=None)
+    ap.add_argument("--lm-cloud-mode", choices=["all", "latest"], default="all")
+    ap.add_argument("--lm-cloud-points", type=int, default=1 << 22)
     args = ap.parse_args()
     if args.lc_stereo_unrect and not args.loop_closing:
         ap.error("--lc-stereo-unrect needs --loop-closing")
@@ -60,6 +72,8 @@ def main():
         ap.error("--loop-closing needs --voc <vocabulary file>")
     if args.map_cloud and not (args.loop_closing and args.backend == "hip"):
         ap.error("--map-cloud needs --loop-closing and --backend hip")
+    if args.lm_cloud and not (args.local_map and args.backend == "hip"):
+        ap.error("--lm-cloud needs --local-map and --backend hip")
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -122,6 +136,8 @@ def main():
         ctx = flvis_amd.Context(0)
         n = len(seq) if args.frames is None else min(len(seq), args.frames)
         trk = flvis_amd.Tracker(ctx, cfg, 1, traj_capacity=n)
+        if args.lm_cloud:
+            trk.local_map_cloud_enable(args.lm_cloud_points)
         closer, lc_events, kf_stamps = None, [], []
         if args.loop_closing:
             ctx.bow_load_vocabulary(args.voc)                                  # Vocabulary voc(path), vo_loopclosing.cpp:1097
@@ -150,9 +166,27 @@ def main():
             xyz, npts, n_out, n_drop = closer.map_cloud([[0]], leaf=args.leaf)
             traj_io.write_ply(args.map_cloud, xyz[0], npts[0])
             map_cloud = {"points": int(n_out[0]), "dropped": int(n_drop[0]), "leaf": args.leaf}
+        lm_cloud = None
+        if args.lm_cloud:
+            trk.local_map_counts()                                             # (drains the keyframe queue: the last optimisations too)
+            xyz, npts, n_out, n_drop = trk.local_map_cloud([0], args.lm_cloud_mode, leaf=args.leaf)
+            traj_io.write_ply(args.lm_cloud, xyz[0], npts[0])
+            info = trk.local_map_cloud_info(0)
+            lm_cloud = {"points": int(n_out[0]), "dropped": int(n_drop[0]), "leaf": args.leaf, "mode": args.lm_cloud_mode,
+                        "recorded_points": info["points"], "runs": info["runs"], "runs_dropped": info["dropped"]}
         T_imu_cam = np.array(list(cfg.T_imu_cam0)).reshape(4, 4)
         stamps, pos, quat = traj_io.read_stamped(args.out)
     out = {"backend": args.backend, "frames": len(seq) if args.frames is None else args.frames, "tracked": len(stamps)}
+    if args.backend == "hip":
+        import flvis_amd
+        try:
+            wants_cloud = flvis_amd.config_get_bool(args.config, "output_sparse_map")
+        except flvis_amd.FlvisError:
+            wants_cloud = False                                                # (a yaml without the key: the reference would refuse it)
+        if args.lm_cloud:
+            out["local_map_cloud"] = lm_cloud
+        elif wants_cloud:
+            out["local_map_cloud"] = "output_sparse_map is set in the yaml: --local-map --lm-cloud <file.ply> writes the cloud"
     if args.loop_closing:
         kf_pos, kf_quat = [], []
         for p7 in kf_T_c_w:
