@@ -23,218 +23,17 @@
 #include <limits>
 #include <vector>
 
-#include "../../include/flvis_hip.h"
-#include "ctx.hpp"
-#include "lm_cloud.hpp"
-#include "track_kernels.hpp"
+#include "pipeline_host.hpp"
 
-namespace flvis {
+using namespace flvis;
 
-constexpr int PROF_STAGES = 20;  // every stage has its own (begin, end) event pair on the stream it runs on
 static const char* kStageNames[PROF_STAGES] = {
     "imu_feed+frame_begin", "ingest(equalize)", "pyr_down(left)", "track_prepare", "lk_track(temporal)", "track_collect",
     "ransac_f", "ransac_pnp", "track_post+pose_lm", "reproj_filter", "gftt:eig_cand", "gftt:(merged)", "gftt:pick",
     "feature_dem+add_new", "depth_prepare", "lk_track(stereo)", "depth_innovate", "frame_end",
     "ba_worker(launch)", "frame(chain)"};
 
-// One sub-batch of streams [s0, s0 + S): all device state of those streams and the HIP streams their frames run on.
-struct Lane {
-  int s0 = 0, S = 0;
-  Pipe pipe;
-  hipStream_t st = nullptr;  // tracking chain (the context's stream when the tracker has a single lane)
-  bool own_st = false;
-  // images
-  uint8_t* pyr0[2][LK_MAX_LEVELS] = {};
-  uint8_t* pyr1[LK_MAX_LEVELS] = {};
-  uint32_t* tc = nullptr;  // LK template cache [S][pipe.tc_cap][tc_stride dwords] (LKParams::tc), or nullptr
-  int tc_stride = 0;
-  GfttScratch gftt;
-  float* gftt_xy = nullptr;
-  float* dem_sorted = nullptr;  // [S][2 gftt_num][2] FeatureDEM: the corners in region-major, score-sorted order (k_feature_dem_prep)
-  int* dem_roff = nullptr;      // [S][17] ... and the offset of every region in that list
-  int* gftt_n = nullptr;
-  unsigned* eq_hist = nullptr;
-  uint8_t* eq_lut = nullptr;
-  // per-frame inputs of the lane, uploaded as ONE block: [times S][imu S*IMU_MAX*7][input image bases 2][n_imu S][present S]
-  uint8_t* d_inputs = nullptr;
-  double* d_time = nullptr;
-  const uint8_t** d_tab = nullptr;
-  size_t input_bytes = 0;
-  std::vector<double> h_imu;  // [S][IMU_MAX][7] staged between two frames
-  std::vector<int> h_nimu;
-  std::vector<long long> imu_read;  // [S] rows of the stream's IMU-state ring the caller has fetched (flvis_get_imu_states)
-  // Host staging: a ring of pinned slots, each guarded by an event recorded after its upload, so that image_feed never
-  // waits for the previous frame -- the host runs several frames ahead of the GPU and a frame's launches are already queued
-  // when the GPU gets to them.
-  static constexpr int PIN_RING = 4;
-  void* pinned[PIN_RING] = {};      // page-locked staging of a frame's inputs (host view) ...
-  uint8_t* pinned_dev[PIN_RING] = {};  // ... and the same memory as the device sees it (k_frame_head reads it in place)
-  const uint8_t* h_tab[2] = {nullptr, nullptr};  // the image bases of the last frame fed (host copy of the table)
-  size_t in_off_imu = 0, in_off_tab = 0, in_off_n = 0, in_off_pres = 0;
-  // the slot of frame n may be refilled once frame n's upload is done: k_frame_head (the first kernel after the upload) stores the
-  // frame number into this host-mapped word and the host polls it.  (hipEventSynchronize on an event recorded after the upload
-  // returned only when EVERYTHING enqueued so far had finished -- measured: the host then slept through four queued frames and the
-  // GPU ran dry once per burst, a 0.9 ms hole in every fifth frame.)
-  volatile long long* h_progress = nullptr;  // host view
-  long long* d_progress = nullptr;           // device view of the same word
-  long long frames_uploaded = 0;             // frames this lane has enqueued
-  std::vector<void*> allocs;
-  std::vector<hipEvent_t> prof_ev;  // optional per-stage HIP-event timing (flvis_prof_enable)
-  std::vector<unsigned char> prof18_rec;  // per armed step: the local-map launch's event pair (stage 18) was recorded -- a deferred launch
-                                          // (Pipeline::defer_ba) belongs to the NEXT step, the first step of a batch has none, the last one two
-  // corner detection on its own HIP stream: goodFeaturesToTrack only needs the new image, so it runs beside the temporal
-  // tracking chain (LK -> RANSACs -> pose LM) and joins before FeatureDEM consumes the corners
-  hipStream_t det_stream = nullptr;
-  hipEvent_t ev_img = nullptr, ev_det = nullptr, ev_gftt = nullptr, ev_fe = nullptr, ev_lm = nullptr, ev_tri = nullptr, ev_head = nullptr;
-  hipEvent_t ev_endf = nullptr;  // "k_frame_end has finished": the next frame's ingest and an immediate local-map launch wait for it (folded joins)
-  // templates ahead of the stereo matcher (FLVIS_TPL_AHEAD, round 6): k_lk_templates_ahead on a low-priority stream of its own, beside the
-  // one-workgroup-per-stream geometry kernels of the frame's chain; ev_tpl: "the frame's templates are in the cache" (k_depth_seeds waits)
-  hipStream_t tpl_stream = nullptr;
-  hipEvent_t ev_tpl = nullptr;
-  bool endf_valid = false;       // the last k_frame_end carried that signal
-  int idx = 0;  // position in Pipeline::lanes
-  // multi-lane trackers: ev_end[n % HOLD_RING] follows the lane's n-th frame (the context's stream waits for the frame whose
-  // input buffers the caller may reuse next, see flvis_set_input_hold); ev_stagger follows the temporal LK of the lane's first
-  // processed frame (the next lane starts its first frame there, so that the lanes run out of phase)
-  static constexpr int HOLD_RING = 8;
-  hipEvent_t ev_end[HOLD_RING] = {};
-  hipEvent_t ev_stagger = nullptr;
-  // back-pressure on the keyframe queues in stream order: ev_ba_done[i % BAQ] follows the lane's i-th local-map launch; the
-  // tracking stream waits for the launches of KFQ-3 frames ago before it appends new keyframes (see lane_frame)
-  static constexpr int BAQ = 64;
-  hipEvent_t ev_ba_done[BAQ] = {};
-  // FLVIS_JOIN (round 6; "flag" is the default, "event" the form of rounds 1-5): the joins between the lane's streams as device words instead of events -- the producing stream stores a
-  // sequence number behind its last kernel (k_store_flag), the consuming stream waits for it with one sleeping lane (k_wait_flag).  An
-  // event record is a system-scope barrier packet and a wait a barrier packet that polls the record's signal for as long as it is pending
-  // (and slows the queues beside it, profiles/r06_h2d.md); a word in HBM costs two one-lane launches.
-  static constexpr int JOIN_IDS = 9 + BAQ;
-  long long* d_join = nullptr;             // [JOIN_IDS] words, 64 bytes apart
-  unsigned* d_join_cnt = nullptr;          // [JOIN_IDS] arrival counters of the launches that signal a word themselves (KJoin)
-  long long join_seq[JOIN_IDS] = {};
-  long long ba_launches = 0;
-  bool ba_pending = false;       // the local-map launch for the last frame's keyframes has not been enqueued yet (Pipeline::defer_ba)
-  unsigned ba_tag = 0;           // tag of the lane's last local-map launch (k_ba_worker's stream list is valid for one tag; 0 is never used)
-  // reset commands in the keyframe queues (flvis_reset_streams / flvis_local_map_reset): per stream, the lane frame count when its last
-  // command was appended (-1: none, or keyframes pushed behind it) -- a second request before the next frame adds no entry; and the lane
-  // frame counts at which any stream of the lane had one appended, for the back-pressure (lane_backpressure_depth)
-  std::vector<long long> cmd_frame;
-  std::vector<long long> cmd_steps;
-  int lmc_cmds = 0;              // reset calls that appended a command since the lane's last local-map launch (local_map_work)
-  bool cmd_since_frame = false;  // a command was appended since the lane's last frame (a frame without the local map applies it: k_kfq_drop)
-};
-
-struct Pipeline {
-  int S = 0;
-  flvis_cfg cfg;                 // the batch-wide fields every stream shares (stream 0's config)
-  std::vector<flvis_cfg> cfgs;   // [S] the config each stream runs on (flvis_get_stream_cfg) ...
-  std::vector<RigParams> rigs;   // [S] ... and its rig as the device has it (host mirror of the lanes' Pipe::rig)
-  int lane_size = 0;
-  std::vector<Lane*> lanes;
-  int levels_t = 0, levels_s = 0, levels = 0;
-  int lw[LK_MAX_LEVELS], lh[LK_MAX_LEVELS], lpitch[LK_MAX_LEVELS];
-  size_t lstride[LK_MAX_LEVELS];
-  int lbx = 0, lby = 0;  // physical border of every pyramid level (columns / rows on each side)
-  int max_pts = 0;  // bound on the landmarks of a frame (16 regions x max_region_feature_num): sizes the LK grid
-  // The environment knobs the tracker honours, read once when it is created (read_knobs; INTEGRATION.md lists them)
-  int n_lanes_req = 1;  // FLVIS_LANES: sub-batches of streams (1 .. 16)
-  bool lk_border = true;  // FLVIS_LK_BORDER: pyramid levels with a physical border
-  bool lk_tcache = true;  // FLVIS_LK_TCACHE: the LK template cache between a frame's stereo and the next frame's temporal LK
-  bool tpl_ahead = false;  // FLVIS_TPL_AHEAD: the stereo matcher's templates computed ahead, on a stream of their own
-  int tpl_start = 1;  // FLVIS_TPL_START: where k_lk_templates_ahead starts (lane_frame)
-  int chain_merge = 3;  // FLVIS_CHAIN_MERGE: launches of the frame's chain folded into their neighbours (lane_frame)
-  bool head_prepare = true;  // FLVIS_HEAD_PREPARE: k_frame_head and k_track_prepare as one launch
-  bool ba_mfma = false, ba_balance = false, kf_check = false;  // FLVIS_BA_MFMA, FLVIS_BA_BALANCE, FLVIS_KF_CHECK (Pipe fields)
-  bool pnp_tail_cv = false;  // FLVIS_PNP_TAIL=cv
-  unsigned prof_scope = 0;  // FLVIS_PROF_EVENT_SCOPE: release scope of the stage-timing events
-  long long frames_fed = 0;
-  long long stream_frames = 0;  // stream-frames fed (flvis_get_counters [0]): frames_fed * S unless steps left streams absent
-  std::vector<void*> allocs;  // context-level device allocations (host-feed staging)
-  int prof_cap = 0, prof_step = 0;
-  unsigned long long prof_mask = ~0ull;  // stages that record events (an event record costs a few us on the GPU queue)
-  // The local map runs beside the front-end: k_frame_end appends KeyFrame payloads to per-stream queues, k_ba_worker (one
-  // launch per lane and frame on one of the shared local-map streams, round-robin) drains them.  Its output is never fed
-  // back into the tracker in the reference (src/frontend/vo_tracking.cpp:373-385).
-  static constexpr int NBA = 8;
-  static_assert(NBA == BA_PLAN_SLOTS, "one stream list per local-map HIP stream");
-  int nba = 2;                   // local-map streams in use: 2 per lane (profiles/r04_local_map_and_streams_ab.md) ...
-  int nba_lane = 2;              // ... of which every lane uses its own nba_lane
-  int host_lead = 3;             // frames the host may run ahead of the GPU (FLVIS_HOST_LEAD, 1 .. PIN_RING; 2 until round 6: a host thread that is held up for a millisecond then leaves the GPU dry)
-  int host_lead_cap = 4;         // (flvis_image_feed_host lowers it to 1 for its call: its copies and events add to the queued commands)
-  int input_hold = 0;            // flvis_set_input_hold: frames the caller keeps its input buffers untouched after handing them over
-  double host_ms_total = 0, host_ms_wait = 0;  // host time inside flvis_image_feed / of it blocked on the pinned ring
-  bool sync_each_frame = false;  // FLVIS_SYNC_EACH_FRAME=1: image_feed waits for the previous frame (tuning knob)
-  int ba_every = 1;              // launch the local-map worker every n-th frame (FLVIS_BA_EVERY)
-  bool lk_stats = false;         // flvis_debug_lk_stats: the LK launches count their iterations per level into counters[36 .. 59]
-  hipStream_t ba_stream[NBA] = {};
-  std::vector<hipStream_t> pad_streams;  // idle streams in front of the lanes' template streams (tracker_create_impl)
-  long long ba_rr = 0;           // round-robin counter over the local-map streams
-  hipEvent_t ev_in = nullptr;    // the caller's inputs are ready (recorded on the context's stream)
-  bool defer_ba = false;         // inside flvis_run_steps, not its last step: the local-map launch of this frame waits for the next frame (lane_frame)
-  bool feedback_used = false;    // flvis_correction_feed was called: k_apply_correction runs after every frame_begin
-  // flvis_image_feed_host: double-buffered device staging filled by async H2D copies on a copy stream, so that the upload of
-  // frame N+1 overlaps the kernels of frame N (allocated by the first call)
-  struct HostFeed {
-    hipStream_t strm = nullptr;
-    static constexpr int SLOTS = 3;   // (mode 2 cycles through three staging slots, mode 1 through two)
-    uint8_t* raw[SLOTS][2] = {};   // [slot][camera]: the images as handed over (tightly packed rows of w * bytes-per-pixel)
-    uint8_t* gray[SLOTS][2] = {};  // [slot][camera]: cvtColor output for 3/4-channel input
-    // mode 2 (round 6, default): nothing but copies on the copy stream.  Behind the images of a call the copy engine writes a block of
-    // sequence numbers (FLAG_WORDS x the call's number, from a page-locked ring: large enough not to be turned into a blit kernel);
-    // k_wait_flag on the stream that ingests the images waits for it; the host learns that the uploads are done from hipStreamQuery
-    // and that a slot is free from the frame-progress word.  No event, no kernel, no AQL barrier packet on the copy stream's queue.
-    int mode = 2;  // FLVIS_H2D_MODE
-    static constexpr int FLAG_WORDS = 4096, FLAG_RING = 4;
-    long long* h_flag[FLAG_RING] = {};
-    long long* d_flag = nullptr;
-    long long slot_frame[SLOTS] = {0, 0, 0};  // the lane frame number (frames_uploaded) that read the slot last
-    long long last_call_frame = -1;           // frames_fed behind this entry's last call (another entry in between: the chain is not continuous)
-    size_t raw_bytes[2] = {}, gray_bytes = 0;
-    hipEvent_t ev_done[2] = {}, ev_free[2] = {};
-    long long n = 0;
-    volatile long long* h_up = nullptr;  // host-mapped: number of calls whose uploads have finished (stored by the copy stream)
-    long long* d_up = nullptr;
-    std::vector<double> times;
-    double ms_wait_uploads = 0, ms_issue = 0, ms_feed = 0;  // host time of the calls: blocked on the previous uploads, issuing, in flvis_image_feed
-    // flvis_debug_host_feed_timing: the uploads of a call bracketed by two timing events on the copy stream (their own durations, what
-    // bench.py's with_h2d.upload_GBs is made of); read back when the slot comes round again
-    bool timing = false;
-    hipEvent_t ev_t0[2] = {}, ev_t1[2] = {};
-    bool timed[2] = {false, false};
-    size_t timed_bytes[2] = {0, 0};
-    double up_ms = 0, up_bytes = 0, up_calls = 0;
-  } hf;
-  hipEvent_t up_event = nullptr;  // set by flvis_image_feed_host for its flvis_image_feed call: the upload's event, waited for on the stream that ingests the images
-  const long long* up_flag = nullptr;  // ... or (mode 2) the sequence block the copy engine writes behind the images, and the number to wait for
-  long long up_seq = 0;
-  static constexpr unsigned ev_flags = hipEventDisableTiming;  // flags of every event of the pipeline (system scope: profiles/r06_h2d.md)
-  bool flag_joins = false;                    // FLVIS_JOIN=flag
-  bool fold_joins = false;                    // FLVIS_JOIN_FOLD: the chain's own kernels wait for / store the words (KJoin)
-  bool chain_continuous = false;              // this frame follows the previous one on the main stream with nothing of the caller's in between
-  // flvis_local_map_cloud_enable: the streams' map-cloud records (cap 0: off, and no k_lm_cloud_append is launched) and the event that
-  // orders the context's stream behind the tracker's for a fetch
-  LmCloudRec lmc{};
-  hipEvent_t lmc_ev = nullptr;
-  Lane& lane_of(int stream, int& local) {
-    const int k = stream / lane_size;
-    local = stream - k * lane_size;
-    return *lanes[k];
-  }
-};
-
-}  // namespace flvis
-
-using namespace flvis;
-
 namespace {
-
-template <typename T>
-T* dalloc(std::vector<void*>& allocs, size_t n, bool zero = true) {
-  void* p = nullptr;
-  if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
-  if (zero) hipMemset(p, 0, n * sizeof(T));
-  allocs.push_back(p);
-  return (T*)p;
-}
 
 int lk_levels(int w, int h, int win, int max_level) {
   int level = 0;
@@ -344,13 +143,12 @@ static void lane_destroy(Lane* L) {
     hipStreamSynchronize(L->tpl_stream);
     hipStreamDestroy(L->tpl_stream);
   }
-  if (L->ev_tpl) hipEventDestroy(L->ev_tpl);
   if (L->own_st && L->st) hipStreamDestroy(L->st);
-  for (hipEvent_t e : {L->ev_img, L->ev_det, L->ev_gftt, L->ev_fe, L->ev_lm, L->ev_tri, L->ev_head, L->ev_endf, L->ev_stagger, L->ev_end[0], L->ev_end[1], L->ev_end[2], L->ev_end[3],
-                       L->ev_end[4], L->ev_end[5], L->ev_end[6], L->ev_end[7]})
+  for (Join& j : L->join)
+    if (j.ev) hipEventDestroy(j.ev);
+  if (L->ev_stagger) hipEventDestroy(L->ev_stagger);
+  for (hipEvent_t e : L->ev_end)
     if (e) hipEventDestroy(e);
-  for (int k = 0; k < Lane::BAQ; k++)
-    if (L->ev_ba_done[k]) hipEventDestroy(L->ev_ba_done[k]);
   for (void* p : L->allocs) hipFree(p);
   for (hipEvent_t e : L->prof_ev) hipEventDestroy(e);
   for (int k = 0; k < Lane::PIN_RING; k++)
@@ -359,7 +157,6 @@ static void lane_destroy(Lane* L) {
   delete L;
 }
 
-static void sync_all(flvis_ctx* ctx);
 extern "C" void flvis_pipeline_sync_internal(flvis_ctx* ctx) {
   if (ctx && ctx->pipe) sync_all(ctx);
 }
@@ -657,9 +454,10 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   ok = ok && ((L->dem_roff = dalloc<int>(L->allocs, (size_t)S * 17)) != nullptr);
   ok = ok && ((L->eq_hist = dalloc<unsigned>(L->allocs, (size_t)S * 256)) != nullptr);
   ok = ok && ((L->eq_lut = dalloc<uint8_t>(L->allocs, (size_t)S * 256)) != nullptr);
-  ok = ok && ((L->d_join = dalloc<long long>(L->allocs, (size_t)Lane::JOIN_IDS * 8)) != nullptr);
-  ok = ok && ((L->d_join_cnt = dalloc<unsigned>(L->allocs, (size_t)Lane::JOIN_IDS)) != nullptr);
+  ok = ok && ((L->d_join = dalloc<long long>(L->allocs, (size_t)JOIN_IDS * 8)) != nullptr);
+  ok = ok && ((L->d_join_cnt = dalloc<unsigned>(L->allocs, (size_t)JOIN_IDS)) != nullptr);
   if (!ok) return false;
+  for (int id = 0; id < JOIN_IDS; id++) L->join[id].word = L->d_join + 8 * id, L->join[id].cnt = L->d_join_cnt + id;
   // initial per-stream state (F2FTracking::init, VIMOTION ctor, landmark id counter 100, glibc rand seed 1): the kernel flvis_reset_streams
   // runs, so that a reset stream and a new one cannot differ (tracker_create synchronises the device before it returns)
   for (int b = 0; b < S; b += RESET_LIST) {
@@ -705,13 +503,10 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   }
   // (the detection stream at the default priority; the lowest was measured no faster: DESIGN.md section 4)
   bool evok = hipStreamCreateWithFlags(&L->det_stream, hipStreamNonBlocking) == hipSuccess;
-  if (L->pipe.tpl_ahead) evok = evok && hipEventCreateWithFlags(&L->ev_tpl, pl->ev_flags) == hipSuccess;  // (its stream: flvis_tracker_create)
-  static_assert(Lane::HOLD_RING == 8, "event list below");  // (ev_endf included)
-  for (hipEvent_t* e : {&L->ev_img, &L->ev_det, &L->ev_gftt, &L->ev_fe, &L->ev_lm, &L->ev_tri, &L->ev_head, &L->ev_endf, &L->ev_stagger, &L->ev_end[0], &L->ev_end[1], &L->ev_end[2],
-                        &L->ev_end[3], &L->ev_end[4], &L->ev_end[5], &L->ev_end[6], &L->ev_end[7]})
-    evok = evok && hipEventCreateWithFlags(e, pl->ev_flags) == hipSuccess;
-  for (int k = 0; k < Lane::BAQ && evok; k++)
-    evok = hipEventCreateWithFlags(&L->ev_ba_done[k], pl->ev_flags) == hipSuccess;
+  for (int id = 0; id < JOIN_IDS && evok; id++)  // (J_TPL only with templates ahead; its stream: flvis_tracker_create)
+    if (id != J_TPL || L->pipe.tpl_ahead) evok = hipEventCreateWithFlags(&L->join[id].ev, pl->ev_flags) == hipSuccess;
+  evok = evok && hipEventCreateWithFlags(&L->ev_stagger, pl->ev_flags) == hipSuccess;
+  for (hipEvent_t& e : L->ev_end) evok = evok && hipEventCreateWithFlags(&e, pl->ev_flags) == hipSuccess;
   return evok;
 }
 
@@ -1064,967 +859,6 @@ int flvis_imu_feed_out(flvis_ctx* ctx, int stream, double t, const double* acc3,
   return FLVIS_OK;
 }
 
-
-}  // extern "C"
-
-static void fill_pyr(Pipeline* pl, PyrSel& ps, uint8_t* const* l0, uint8_t* const* l1, const int* cur, int flip, int levels) {
-  ps.levels = levels;
-  for (int l = 0; l <= levels; l++) {
-    ps.lvl[l] = ImgSel{{l0[l], l1 ? l1[l] : l0[l]}, cur, flip, nullptr};
-    ps.w[l] = pl->lw[l];
-    ps.h[l] = pl->lh[l];
-    ps.pitch[l] = pl->lpitch[l];
-    ps.stride[l] = pl->lstride[l];
-    ps.bx[l] = pl->lbx;
-    ps.by[l] = pl->lby;
-  }
-}
-
-// Levels 1 .. levels of the pyramid `pyr` (level 0 too when `ingest` is set: the copy of the caller's image src0).  Level 0 is read from
-// src0 (the caller's image when ingest or in place, else pyr.lvl[0] itself, which another kernel wrote).  The levels' physical borders are
-// written by the kernel that produces the level wherever it can; the return value is the mask of the levels whose border is still to
-// fill (k_pyr_border).  level0_todo: level 0 has a border that nobody has written yet (equalizeHist / the unaligned copy made it).
-// Walking kernels (pyr_walk.hip) where the geometry allows -- 16-pixel lanes: widths that are multiples of 16 up to 1024 --, else the
-// LDS-tile kernels level by level.
-static unsigned pyramid_levels(hipStream_t ds, bool bordered, ImgSel src0, int spitch0, size_t sstride0, bool ingest, bool level0_is_buffer,
-                               const PyrSel& pyr, int S, const int* active) {
-  const int levels = pyr.levels;
-  unsigned border_left = bordered ? (1u << (levels + 1)) - 1u : 0u;
-  if (!level0_is_buffer && !ingest) border_left &= ~1u;  // (level 0 is the caller's buffer: no border to fill)
-  // levels per walking launch: one, then two ("12": the fastest for 640-pixel rows; other plans: profiles/r04_lk_ab.md) -- unless level 1
-  // is not a whole number of 16-pixel lanes while level 0 is (752-pixel rows: 376): then the first launch takes two levels ("21") and only
-  // the last one is left to the tile kernels
-  const char* plan = (pyr.w[0] & 15) == 0 && (((pyr.w[0] + 1) >> 1) & 15) != 0 ? "21" : "12";
-  int step = 0, l = 0;
-  while (l < levels) {
-    int nout = plan[step] ? plan[step] - '0' : 1;
-    if (plan[step]) step++;
-    if (nout > levels - l) nout = levels - l;
-    const bool from0 = l == 0 && (ingest || !level0_is_buffer);
-    ImgSel src = from0 ? src0 : pyr.lvl[l];
-    const int spitch = from0 ? spitch0 : pyr.pitch[l];
-    const size_t sstride = from0 ? sstride0 : pyr.stride[l];
-    const bool copy0 = l == 0 && ingest;
-    PyrSel q = pyr;
-    for (int j = 0; j <= nout; j++)  // a level too small to mirror into its border in one pass keeps it for k_pyr_border
-      if (!(bordered && pyr_border_fusable(pyr.w[l + j], pyr.h[l + j], pyr.bx[l + j], pyr.by[l + j]))) q.bx[l + j] = q.by[l + j] = 0;
-    if (pyr_walk_ok(pyr.w[l], pyr.h[l], nout, q.bx + l, q.by + l, copy0)) {
-      launch_pyr_walk(ds, src, pyr.w[l], pyr.h[l], spitch, sstride, q, l, nout, copy0, S, active);
-      for (int j = copy0 ? 0 : 1; j <= nout; j++)
-        if (q.bx[l + j]) border_left &= ~(1u << (l + j));
-      l += nout;
-      continue;
-    }
-    // one level by the tile kernels
-    const int d = l + 1;
-    if (copy0) {
-      const bool f = q.bx[0] && q.bx[1];
-      launch_pyr_down_ingest(ds, src, pyr.w[0], pyr.h[0], spitch, sstride, pyr.lvl[0], pyr.pitch[0], pyr.stride[0], pyr.lvl[1], pyr.pitch[1],
-                             pyr.stride[1], S, active, f ? pyr.bx[1] : 0, f ? pyr.by[1] : 0);
-      if (f) border_left &= ~3u;
-    } else {
-      const bool f = q.bx[d] != 0;
-      const bool sf = !from0 && bordered && !((border_left >> l) & 1u);  // (the source level's border is complete)
-      launch_pyr_down(ds, src, pyr.w[l], pyr.h[l], spitch, sstride, pyr.lvl[d], pyr.pitch[d], pyr.stride[d], S, active, f ? pyr.bx[d] : 0,
-                      f ? pyr.by[d] : 0, sf ? pyr.bx[l] : 0, sf ? pyr.by[l] : 0);
-      if (f) border_left &= ~(1u << d);
-    }
-    l = d;
-  }
-  return border_left;
-}
-
-// One local-map launch for the lane (a workgroup per stream takes the stream's next keyframe): on the lane's next local-map HIP stream,
-// behind `ev` of the tracking stream (recorded here when `record` is set), its completion event kept for the back-pressure.
-static int join_id(const Lane* L, hipEvent_t ev) {
-  if (ev == L->ev_img) return 0;
-  if (ev == L->ev_det) return 1;
-  if (ev == L->ev_gftt) return 2;
-  if (ev == L->ev_fe) return 3;
-  if (ev == L->ev_lm) return 4;
-  if (ev == L->ev_tri) return 5;
-  if (ev == L->ev_head) return 6;
-  if (ev == L->ev_endf) return 7;
-  if (ev == L->ev_tpl) return 8;
-  for (int k = 0; k < Lane::BAQ; k++)
-    if (ev == L->ev_ba_done[k]) return 9 + k;
-  return -1;
-}
-// "stream s has reached this point" / "stream s goes on when that point has been reached": an event, or (FLVIS_JOIN=flag) a device word
-static void join_signal(Pipeline* pl, Lane* L, hipEvent_t ev, hipStream_t s) {
-  const int id = pl->flag_joins ? join_id(L, ev) : -1;
-  if (id < 0) {
-    hipEventRecord(ev, s);
-    return;
-  }
-  launch_store_flag(s, L->d_join + 8 * id, ++L->join_seq[id]);
-}
-static void join_wait(Pipeline* pl, Lane* L, hipStream_t s, hipEvent_t ev) {
-  const int id = pl->flag_joins ? join_id(L, ev) : -1;
-  if (id < 0) {
-    hipStreamWaitEvent(s, ev, 0);
-    return;
-  }
-  launch_wait_flag(s, L->d_join + 8 * id, 1, L->join_seq[id], L->d_progress + 2);
-}
-
-// folded forms (KJoin): the NEXT launch that is handed `kj` stores the word behind its last workgroup / waits for it in front of its first
-static bool fold_signal(Pipeline* pl, Lane* L, hipEvent_t ev, KJoin& kj) {
-  const int id = pl->fold_joins ? join_id(L, ev) : -1;
-  if (id < 0) return false;
-  kj.sig = L->d_join + 8 * id;
-  kj.sig_seq = ++L->join_seq[id];
-  kj.sig_cnt = L->d_join_cnt + id;
-  return true;
-}
-static bool fold_wait(Pipeline* pl, Lane* L, hipEvent_t ev, KJoin& kj, int slot) {
-  const int id = pl->fold_joins ? join_id(L, ev) : -1;
-  if (id < 0) return false;
-  kj.wait[slot] = L->d_join + 8 * id;
-  kj.wait_seq[slot] = L->join_seq[id];
-  kj.err = L->d_progress + 2;
-  return true;
-}
-
-// ... or keeps the launch from ENDING before the word is there (KJoin::post): the launch behind it needs no wait of its own
-static bool fold_post(Pipeline* pl, Lane* L, hipEvent_t ev, KJoin& kj) {
-  const int id = pl->fold_joins ? join_id(L, ev) : -1;
-  if (id < 0) return false;
-  kj.post = L->d_join + 8 * id;
-  kj.post_seq = L->join_seq[id];
-  kj.err = L->d_progress + 2;
-  return true;
-}
-
-// the lane's part of the map-cloud record, and its append kernel behind a local-map launch of the lane on `bs`
-static LmCloudRec lane_lmc(const Pipeline* pl, const Lane* L) {
-  LmCloudRec r = pl->lmc;
-  r.hdr += (size_t)L->s0 * LMC_HDR;
-  r.ids += (size_t)L->s0 * r.cap;
-  r.pts += (size_t)L->s0 * r.cap * 3;
-  return r;
-}
-// The worker of one local-map launch on `bs`.  Record off: k_ba_worker as ever.  Record on: every optimisation must be looked at
-// before the next one of its stream overwrites the correction, and k_lm_cloud_append can only run between two kernels.  So a worker
-// then takes ONE queue entry per stream (ba_drain 1: at most one optimisation) with the append kernel behind it, `pairs` times -- as
-// many entries as the one launch would have taken -- and nothing else of the lane's local map runs meanwhile (launch_local_map orders
-// the lane's launches one behind the other; the other callers wait on the host).  An owner still stays past its share at KFQ / 2
-// waiting entries, the back-pressure's last resort; that is out of reach here: a launch takes what the frames since the previous
-// launch can have queued.
-static void local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int slot, int pairs, hipEvent_t prof_end) {
-  if (pl->lmc.cap <= 0) {
-    launch_ba_worker(bs, L->pipe, slot, ++L->ba_tag);
-    if (prof_end) hipEventRecord(prof_end, bs);
-    return;
-  }
-  Pipe one = L->pipe;
-  one.ba_drain = 1;
-  const LmCloudRec r = lane_lmc(pl, L);
-  for (int k = 0; k < pairs; k++) {
-    launch_ba_worker(bs, one, slot, ++L->ba_tag);
-    if (prof_end && k == 0) hipEventRecord(prof_end, bs);
-    launch_lm_cloud_append(bs, one, r);
-  }
-}
-
-static void launch_local_map(Pipeline* pl, Lane* L, hipEvent_t ev, bool record, hipEvent_t* prof_begin_end) {
-  const int bi = (L->idx * pl->nba_lane + (int)(L->ba_launches % pl->nba_lane)) % pl->nba;
-  hipStream_t bs = pl->ba_stream[bi];
-  if (prof_begin_end) {  // (one timed launch per armed step: the first; a second one in the same step keeps its hands off the pair)
-    unsigned char& rec = L->prof18_rec[(size_t)pl->prof_step];
-    if (rec) prof_begin_end = nullptr;
-    else rec = 1;
-  }
-  if (record) join_signal(pl, L, ev, L->st);
-  join_wait(pl, L, bs, ev);
-  // record on: behind the lane's previous launch and its append kernel (it ran on the lane's other local-map stream)
-  const bool rec_on = pl->lmc.cap > 0;
-  if (rec_on && L->ba_launches > 0) join_wait(pl, L, bs, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
-  if (prof_begin_end) hipEventRecord(prof_begin_end[0], bs);
-  // (a reset command takes a queue entry like a keyframe, at most one per stream and frame)
-  local_map_work(pl, L, bs, bi, pl->ba_every + std::min(L->lmc_cmds, pl->ba_every), prof_begin_end ? prof_begin_end[1] : nullptr);
-  L->lmc_cmds = 0;
-  join_signal(pl, L, L->ev_ba_done[L->ba_launches % Lane::BAQ], bs);
-  L->ba_launches++;
-  L->ba_pending = false;
-}
-
-static void sync_streams(flvis_ctx* ctx) {
-  hipStreamSynchronize(ctx->stream);
-  Pipeline* pl = ctx->pipe;
-  if (!pl) return;
-  for (Lane* L : pl->lanes) {
-    hipStreamSynchronize(L->st);
-    hipStreamSynchronize(L->det_stream);
-    if (L->tpl_stream) hipStreamSynchronize(L->tpl_stream);
-  }
-  for (int k = 0; k < Pipeline::NBA; k++)
-    if (pl->ba_stream[k]) hipStreamSynchronize(pl->ba_stream[k]);
-}
-// waits for everything that was enqueued AND for the local map to have consumed every queued keyframe (a keyframe that
-// slipped in while a worker workgroup was releasing its window is picked up by one more worker launch)
-static void sync_all(flvis_ctx* ctx) {
-  if (ctx->pipe)
-    for (Lane* L : ctx->pipe->lanes)
-      if (L->ba_pending) launch_local_map(ctx->pipe, L, L->ev_fe, true, nullptr);  // (a launch deferred into the next frame: there is none)
-  sync_streams(ctx);
-  Pipeline* pl = ctx->pipe;
-  if (!pl) return;
-  for (Lane* L : pl->lanes) {
-    std::vector<unsigned> hd(L->S), tl(L->S);
-    for (int guard = 0; guard < 64; guard++) {
-      hipMemcpy(hd.data(), L->pipe.kfq_head, sizeof(unsigned) * L->S, hipMemcpyDeviceToHost);
-      hipMemcpy(tl.data(), L->pipe.kfq_tail, sizeof(unsigned) * L->S, hipMemcpyDeviceToHost);
-      bool pending = false;
-      for (int i = 0; i < L->S; i++) pending = pending || hd[i] != tl[i];
-      if (!pending) break;
-      local_map_work(pl, L, pl->ba_stream[0], 0, 1, nullptr);
-      hipStreamSynchronize(pl->ba_stream[0]);
-    }
-  }
-}
-
-// How many local-map launches back the tracking stream waits before it appends to the keyframe queues (lane_frame).  A reset command
-// (k_stream_reset) takes a queue entry like a keyframe: every lane frame with a command among the frames the bound counts moves the wait
-// one launch closer.  Without commands: the depth of rounds 1-6.
-static long long lane_backpressure_depth(Pipeline* pl, Lane* L) {
-  long long D = std::max(0, KFQ / 2 / pl->ba_every - 3);  // (-2, and -1 because a deferred launch is one frame late)
-  if (L->cmd_steps.empty()) return D;
-  const long long window = (D + pl->nba_lane + 2) * pl->ba_every;
-  std::vector<long long>& c = L->cmd_steps;
-  c.erase(std::remove_if(c.begin(), c.end(), [&](long long f) { return L->frames_uploaded - f > window; }), c.end());
-  return std::max(0LL, D - (long long)c.size());
-}
-
-// One frame of one lane: stages the lane's host inputs, uploads them as one block and enqueues the fixed kernel sequence
-// on the lane's streams.  d_img0 / d_img1 already point at the lane's first stream.
-// present: the lane's slice of the step's presence bytes (flvis_image_feed_present), nullptr when every stream has a frame.
-static void lane_frame(flvis_ctx* ctx, Pipeline* pl, Lane* L, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
-                       const uint8_t* present, int with_local_map) {
-  Pipe& p = L->pipe;
-  const int S = L->S;
-  hipStream_t st = L->st;
-  const int w = pl->cfg.image_width, h = pl->cfg.image_height;
-  // ---- stage host inputs (pinned) and upload: [times][imu][input image bases][n_imu]
-  const long long frame_no = ++L->frames_uploaded;  // 1-based count of the frames this lane has been fed
-  const int pslot = (int)((frame_no - 1) % Lane::PIN_RING);
-  uint8_t* pin = (uint8_t*)L->pinned[pslot];
-  if (pl->sync_each_frame) hipStreamSynchronize(st);
-  // run at most host_lead frames ahead of the GPU (<= PIN_RING: the staging slot of frame N - PIN_RING must be free).  Not further:
-  // beyond ~5 queued frames (~300 commands) the HIP runtime itself blocks the enqueuing thread for 7-9 ms at a time and the GPU
-  // then runs dry while the queue is refilled (measured)
-  // (zero-copy inputs: k_frame_head publishes its progress word when it STARTS, while its other workgroups may still be reading the
-  // slot -- one slot of slack, so that the slot the host refills belongs to a frame whose successor has started, i.e. that is over)
-  const long long lead = std::min(std::min(pl->host_lead, pl->host_lead_cap), (int)Lane::PIN_RING - 1);
-  if (frame_no > lead && *L->h_progress < frame_no - lead) {
-    const auto tw = std::chrono::steady_clock::now();
-    int polls = 0;
-    while (*L->h_progress < frame_no - lead) {
-      if ((++polls & 255) == 0 && hipStreamQuery(st) == hipSuccess && *L->h_progress < frame_no - lead) break;  // (idle stream: a failed launch)
-      std::this_thread::sleep_for(std::chrono::microseconds(30));
-    }
-    pl->host_ms_wait += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-  }
-  double* pt = (double*)pin;
-  double* pi = pt + S;
-  const uint8_t** ptab = (const uint8_t**)(pi + (size_t)S * IMU_MAX * 7);
-  int* pn = (int*)(ptab + 2);
-  int* ppres = (int*)((uint8_t*)pin + L->in_off_pres);
-  // presence: the stream's word in the table (read by k_frame_head, k_frame_end and the left image's ingest); a lane whose streams all
-  // have a frame passes nullptr, the form of a plain flvis_image_feed
-  int n_present = S;
-  if (present) {
-    n_present = 0;
-    for (int s = 0; s < S; s++) n_present += (ppres[s] = present[s] ? 1 : 0);
-  }
-  const bool all_present = n_present == S, none_present = n_present == 0;
-  memcpy(pt, h_times, sizeof(double) * S);
-  // only the staged samples travel (the block keeps its layout: [S][IMU_MAX][7])
-  int max_n = 0;
-  for (int s = 0; s < S; s++) max_n = std::max(max_n, L->h_nimu[s]);
-  for (int s = 0; s < S; s++)
-    memcpy(pi + (size_t)s * IMU_MAX * 7, &L->h_imu[(size_t)s * IMU_MAX * 7], sizeof(double) * 7 * L->h_nimu[s]);
-  (void)max_n;
-  ptab[0] = d_img0;
-  ptab[1] = d_img1;
-  memcpy(pn, L->h_nimu.data(), sizeof(int) * S);
-  std::fill(L->h_nimu.begin(), L->h_nimu.end(), 0);
-  // a reset command appended since the lane's last frame (flvis_reset_streams / flvis_local_map_reset)
-  const bool cmd_pending = L->cmd_since_frame;
-  L->cmd_since_frame = false;
-  // No copy: k_frame_head reads the block where the host staged it (page-locked, mapped into the device's address space: a few KB per
-  // stream over PCIe, in parallel over the streams), and the image bases travel as kernel arguments.  A staging slot is rewritten PIN_RING
-  // frames later, when the frame that read it is long over (the host-lead wait above).  Copying forms: profiles/r04_lk_ab.md.  (The copy
-  // below only serves a runtime that maps no device pointer for the staging slot.)
-  const bool zerocopy = L->pinned_dev[pslot] != nullptr;
-  L->h_tab[0] = d_img0, L->h_tab[1] = d_img1;
-  p.in_img1 = d_img1;
-  {
-    uint8_t* din = zerocopy ? L->pinned_dev[pslot] : L->d_inputs;
-    L->d_time = reinterpret_cast<double*>(din);
-    p.imu_in = reinterpret_cast<double*>(din + L->in_off_imu);
-    p.n_imu = reinterpret_cast<int*>(din + L->in_off_n);
-    p.present = all_present ? nullptr : reinterpret_cast<const int*>(din + L->in_off_pres);
-  }
-  if (!zerocopy) hipMemcpyAsync(L->d_inputs, pin, L->input_bytes, hipMemcpyHostToDevice, st);
-  // ---- fixed kernel sequence
-  const bool prof = pl->prof_cap > 0 && pl->prof_step < pl->prof_cap;
-  hipEvent_t* pev = prof ? &L->prof_ev[(size_t)pl->prof_step * (2 * PROF_STAGES)] : nullptr;
-#define PB(i, strm) \
-  if (prof && ((pl->prof_mask >> (i)) & 1ull)) hipEventRecord(pev[2 * (i)], strm)
-#define PE(i, strm) \
-  if (prof && ((pl->prof_mask >> (i)) & 1ull)) hipEventRecord(pev[2 * (i) + 1], strm)
-  PB(19, st);  // the whole main-stream chain of this frame: per-frame GPU latency (p50/p99 in bench.py)
-  // The local-map launch for the keyframes of frame n is enqueued inside frame n + 1, behind its PnP RANSAC, where the ~0.3 ms in which two
-  // launches hold CUs fall on the one-workgroup-per-stream geometry kernels (other placements: profiles/r05_local_map_cost.md).  Only
-  // between the steps of one flvis_run_steps call -- the next frame is known to follow at once; a per-frame caller (the ROS wrapper) gets
-  // its local-map launch when its frame ends, and so does the last step of a batch.
-  hipEvent_t* prof18 = (prof && ((pl->prof_mask >> 18) & 1ull)) ? &pev[2 * 18] : nullptr;
-  const bool skipped = pl->frames_fed < (long long)pl->cfg.skip_first_n_imgs;
-  // a step in which no stream of the lane has a frame runs as a skipped one (the IMU, and k_frame_end, which writes nothing for an absent
-  // stream) -- plus the local map, which goes on with the keyframes queued before.  (While frames_fed < skip_first_n_imgs every stream that
-  // has a frame is in its skip window, whichever steps it was absent from: the skipped form holds with presence too.)
-  const bool idle_step = skipped || none_present;
-  const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;  // the second image is the Z16 depth map, read in place
-  const bool eq = pl->cfg.need_equal_hist != 0;
-  // rows of whole 16-byte lanes at 16-byte aligned bases (the walking kernels' dwordx4 loads); otherwise (KITTI: 1241 x 376 tightly packed
-  // rows, or a caller's buffer at an odd offset) both images are copied into pitch-aligned level 0
-  const bool aligned = (w & 15) == 0 && !(((uintptr_t)d_img0 | (depth_cam ? (uintptr_t)0 : (uintptr_t)d_img1)) & 15);
-  // the left image on the detection stream, k_frame_head on the main one (the two swapped: profiles/r05_local_map_cost.md)
-  hipStream_t ds = L->det_stream;
-  ImgSel in0 = img_plain(d_img0), in1 = img_plain(d_img1);  // (kernel arguments: no graph is captured)
-  ImgSel l0cur{{L->pyr0[0][0], L->pyr0[1][0]}, p.img_slot, 0, nullptr};
-  if (!idle_step) {
-    // left image -> level 0 of the slot this frame is going to use (+ the pyramid), on the detection stream BESIDE k_frame_head: the
-    // slot was fixed when the previous frame ended (img_slot_in), so the image work does not wait for the IMU integration and the
-    // state machine (one thread per stream, 45 us).  Every present stream's image is ingested, also that of a stream this frame leaves
-    // idle.  Without equalizeHist the first pyrDown reads the caller's image and writes level 0 and level 1 in one pass; with it the
-    // equalised image is level 0.
-    ImgSel l0in{{L->pyr0[0][0], L->pyr0[1][0]}, p.img_slot_in, 0, nullptr};
-    // what the detection stream needs from the main one here is k_frame_end of the previous frame (the slot the image goes to) and, in
-    // the copying mode, the upload of the input table: a signal of its own -- or, folded, the word the last k_frame_end stored itself
-    // (only where nothing can have been enqueued on the main stream since that k_frame_end: between the steps of one flvis_run_steps call,
-    // and for host images that arrive through the copy stream -- a caller of flvis_image_feed may have produced its images on this stream)
-    if (pl->fold_joins && zerocopy && L->endf_valid && pl->chain_continuous) {
-      join_wait(pl, L, ds, L->ev_endf);
-    } else {
-      join_signal(pl, L, L->ev_lm, st);  // (the frame's input table has been uploaded)
-      join_wait(pl, L, ds, L->ev_lm);
-    }
-    // host images (flvis_image_feed_host, single-lane stereo): the upload's signal is waited for by the stream that ingests the left image; the
-    // main stream only sees the joins it has anyway (left pyramid in front of the temporal LK, right pyramid in front of the stereo LK)
-    if (pl->up_event) hipStreamWaitEvent(ds, pl->up_event, 0);
-    if (pl->up_flag) launch_wait_flag(ds, pl->up_flag, Pipeline::HostFeed::FLAG_WORDS, pl->up_seq, L->d_progress + 2);
-    PB(1, ds);
-    // (an absent stream's workgroups retire at once: its image is not read, the slots of its pyramid are not written)
-    const int* pg = p.present;
-    if (eq) launch_equalize_hist(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, pg);
-    else if (!aligned) launch_copy_image_any(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, pg);
-    PE(1, ds);
-    PB(2, ds);
-    // the borders of the levels: written by the pyrDown kernel that produces the level (every pixel also goes to the border positions
-    // that mirror it); k_pyr_border only for what is left (level 0 when another kernel makes it, levels smaller than the border)
-    PyrSel pyl;
-    fill_pyr(pl, pyl, L->pyr0[0], L->pyr0[1], p.img_slot_in, 0, pl->levels);
-    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in0, w, (size_t)w * h, !eq && aligned, true, pyl, S, pg);
-    if (pl->levels == 0 && !eq && aligned) launch_copy_image(ds, in0, l0in, w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, pg);
-    if (border_left) launch_pyr_border(ds, pyl, S, pg, border_left);
-    PE(2, ds);
-    join_signal(pl, L, L->ev_img, ds);
-  }
-  PB(0, st);
-  // the staged IMU samples, then frame_begin -- and, unless the local-map feedback has to be applied in between, the temporal tracker's
-  // inputs in the same launch (FLVIS_HEAD_PREPARE=0, A/B knob: two launches)
-  const bool head_prepare = pl->head_prepare && !pl->feedback_used && !idle_step;
-  const bool head_signals = !pl->feedback_used && fold_signal(pl, L, L->ev_head, p.kj);  // (the head kernel is the last one in front of the signal)
-  // ... and it does not end before the left pyramid is there (the temporal LK follows it, directly or behind k_track_prepare)
-  const bool head_posts = !idle_step && fold_post(pl, L, L->ev_img, p.kj);
-  if (head_prepare) launch_frame_head_prepare(st, p, L->d_time, L->d_progress, frame_no);
-  else launch_frame_head(st, p, L->d_time, L->d_progress, frame_no);
-  p.kj = KJoin{};
-  if (pl->feedback_used) launch_apply_correction(st, p);  // STEP1 of the Tracking case (local-map feedback, opt-in)
-  PE(0, st);
-  // the detection stream's kernels that read what k_frame_head decides (act_img, gftt_act, gftt_maxc, img_slot) wait for this event:
-  // the corner detection and the right pyramid (they start behind the F-RANSAC anyway)
-  if (!head_signals) join_signal(pl, L, L->ev_head, st);
-  // behind k_frame_end: the local-map launch for the lane (or, without a local map, the keyframe queues' drop); `timed`: stage 18's pair
-  auto local_map_tail = [&](hipEvent_t* p18, bool timed) {
-    if (with_local_map && (pl->frames_fed % pl->ba_every) == 0) {
-      if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a deferred launch this frame had no place for: skipped frames)
-      if (pl->defer_ba) L->ba_pending = true;
-      else if (L->endf_valid) launch_local_map(pl, L, L->ev_endf, false, p18);  // (k_frame_end has stored the word itself)
-      else launch_local_map(pl, L, L->ev_fe, true, p18);
-    } else if (!with_local_map) {
-      // without a local map nobody consumes the keyframe queue: drop what frame_end appended (and apply a reset command queued since the
-      // last frame: k_kfq_drop)
-      // (a reset command is applied to the window here: behind the lane's last local-map launch, so that no workgroup of it owns the window)
-      if (cmd_pending) {
-        if (L->ba_launches > 0) join_wait(pl, L, st, L->ev_ba_done[(L->ba_launches - 1) % Lane::BAQ]);
-        launch_kfq_drop(st, p);
-      } else hipMemcpyAsync(p.kfq_head, p.kfq_tail, sizeof(unsigned) * S, hipMemcpyDeviceToDevice, st);
-      if (timed) {
-        PB(18, st);
-        PE(18, st);
-        L->prof18_rec[(size_t)pl->prof_step] = 1;
-      }
-    }
-  };
-  if (idle_step) {
-    // the reference drops the first skip_first_n_imgs frames before any processing (vo_tracking.cpp image callback): every
-    // stream is idle for this frame, so only the IMU filter, the frame counter and the per-frame outputs are advanced
-    PB(17, st);
-    L->endf_valid = fold_signal(pl, L, L->ev_endf, p.kj);
-    launch_frame_end(st, p);
-    p.kj = KJoin{};
-    PE(17, st);
-    PE(19, st);
-    if (prof)
-      for (int i = 1; i < PROF_STAGES; i++)
-        if (i != 17 && i != 19) {
-          PB(i, st);
-          PE(i, st);
-        }
-    // no stream of the lane has a frame: the keyframes queued before this step keep being optimised (the skip window's steps come before
-    // any keyframe)
-    if (!skipped) local_map_tail(nullptr, false);
-    return;
-  }
-  // lanes out of phase: a lane's first processed frame starts when the previous lane has finished the temporal LK of its own, so
-  // that from then on the image kernels of one lane overlap the one-workgroup-per-stream geometry chain of another
-  const bool first_processed = pl->frames_fed == (long long)pl->cfg.skip_first_n_imgs;
-  if (first_processed && L->idx > 0) hipStreamWaitEvent(st, pl->lanes[L->idx - 1]->ev_stagger, 0);
-  // (the guesses of the temporal tracker only need the state frame_begin left)
-  PB(3, st);
-  if (!head_prepare) launch_track_prepare(st, p);
-  PE(3, st);
-  if (!head_posts) join_wait(pl, L, st, L->ev_img);  // join: the left pyramid
-  // The right image is only read within this frame: without equalizeHist the caller's buffer IS level 0 of the right pyramid (no copy;
-  // that level then has no border, and the few stereo search regions that leave the image at level 0 are staged by the kernel's
-  // index-reflecting path; a bordered copy: DESIGN.md section 4).
-  const bool r_in_place = !eq && aligned;
-  ImgSel r0 = r_in_place ? in1 : img_plain(L->pyr1[0]);
-  const int r0pitch = r_in_place ? w : pl->lpitch[0];
-  const size_t r0stride = r_in_place ? (size_t)w * h : pl->lstride[0];
-  // temporal tracking
-  PB(4, st);
-  {
-    PyrSel prev, next;
-    fill_pyr(pl, prev, L->pyr0[0], L->pyr0[1], p.img_slot, 1, pl->levels_t);
-    fill_pyr(pl, next, L->pyr0[0], L->pyr0[1], p.img_slot, 0, pl->levels_t);
-    LKParams prm{30, 1e-3 * 1e-3, 1e-4f, 1};
-    if (pl->lk_stats) prm.stats = reinterpret_cast<unsigned long long*>(p.counters) + 36;  // temporal: counters[36 .. 47]
-    if (pl->lk_stats) prm.stats_tc = reinterpret_cast<unsigned long long*>(p.counters) + 61;  // both launches: counters[61 .. 63]
-    if (L->tc) {  // templates the stereo matcher of the previous frame stored (same image, same pixel): taken instead of computed
-      prm.tc = L->tc;
-      prm.tc_mode = 2;
-      prm.tc_cap = p.tc_cap;
-      prm.tc_stride = L->tc_stride;
-      prm.tc_slot = p.lk_slot;
-      prm.tc_tag = p.lk_tag;
-    }
-    prm.dbg_slot = (int)(pl->frames_fed & 7);
-    launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, prm, p.act_track, pl->max_pts, 1);
-  }
-  PE(4, st);
-  // templates ahead of the stereo matcher (lane_create: FLVIS_TPL_AHEAD): the survivors' pixels are known when k_track_collect has run.
-  // FLVIS_TPL_START (A/B knob): 1 (default) the kernel starts with the corner detection, behind the F-RANSAC, on that join's word;
-  // 0 behind k_track_collect, beside the F-RANSAC, on a word of its own (one more one-lane launch on the chain)
-  const int tpl_start = pl->tpl_start;
-  auto templates_ahead = [&] {
-    hipStream_t ts = L->tpl_stream;
-    join_wait(pl, L, ts, tpl_start == 1 ? L->ev_lm : L->ev_tpl);
-    PyrSel img;
-    fill_pyr(pl, img, L->pyr0[0], L->pyr0[1], p.img_slot, 0, pl->levels_s);
-    launch_lk_templates_ahead(ts, img, p.tpl_pts, p.tpl_count, NMAX, S, L->tc, p.tc_cap, L->tc_stride, p.tpl_tag, pl->max_pts);
-    join_signal(pl, L, L->ev_tpl, ts);
-  };
-  // FLVIS_CHAIN_MERGE (round 6; bits, default 3): launches of the frame's chain folded into their neighbours -- every launch on the chain is
-  // ~8 us of dispatch, ramp and drain whatever it computes.  Bit 0: k_add_new + k_depth_seeds as one launch (a barrier between them);
-  // bit 1: k_track_collect as the prologue of k_ransac_f (and by sixteen waves instead of one).  0: rounds 1-5's launches.
-  const int chain_merge = pl->chain_merge;
-  const bool merge_collect = (chain_merge & 2) && !(p.tpl_ahead && tpl_start == 0);
-  PB(5, st);
-  if (!merge_collect) launch_track_collect(st, p);
-  PE(5, st);
-  if (p.tpl_ahead && tpl_start == 0) {
-    join_signal(pl, L, L->ev_tpl, st);
-    templates_ahead();
-  }
-  if (first_processed && pl->lanes.size() > 1) hipEventRecord(L->ev_stagger, st);
-  PB(6, st);
-  const bool rf_signals = fold_signal(pl, L, L->ev_lm, p.kj);
-  launch_ransac_f(st, p, merge_collect);
-  p.kj = KJoin{};
-  PE(6, st);
-  if (!rf_signals) join_signal(pl, L, L->ev_lm, st);
-  if (p.tpl_ahead && tpl_start == 1) templates_ahead();
-  // fork, behind the F-RANSAC: the corner detection of the new left image (speculative for tracking frames: used only if tracking
-  // succeeds), then the right pyramid (first used by the stereo matcher), on the detection stream beside the PnP RANSAC / pose
-  // optimisation -- latency chains on 64 CUs that leave the rest of the chip to the detection (other placements and orders:
-  // profiles/r03_stream_structure_ab.md)
-  join_wait(pl, L, ds, L->ev_lm);
-  join_wait(pl, L, ds, L->ev_head);
-  launch_gftt(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, L->gftt, nullptr, p.cam.gftt_ql, p.gftt_maxc, p.cam.gftt_num,
-              (double)p.cam.gftt_dis, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num, p.gftt_act,
-              (prof && ((pl->prof_mask >> 10) & 7ull) == 7ull) ? &pev[2 * 10] : nullptr, false);
-  {  // FeatureDEM's image part (regions, Harris scores, per-region order of the corners) follows at once, off the critical path
-    KJoin prep_kj{};
-    const bool prep_signals = fold_signal(pl, L, L->ev_gftt, prep_kj);
-    launch_feature_dem_prep(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, p.cam.dem, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num,
-                            p.gftt_act, L->dem_sorted, L->dem_roff, &prep_kj);
-    if (!prep_signals) join_signal(pl, L, L->ev_gftt, ds);
-  }
-  join_wait(pl, L, ds, L->ev_head);
-  if (!depth_cam) {
-    if (eq) launch_equalize_hist(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, p.act_img);
-    else if (!aligned) launch_copy_image_any(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, p.act_img);
-    PyrSel pyr_r;
-    fill_pyr(pl, pyr_r, L->pyr1, nullptr, nullptr, 0, pl->levels);
-    unsigned border_left = pyramid_levels(ds, pl->lbx != 0, in1, w, (size_t)w * h, false, !r_in_place, pyr_r, S, p.act_img);
-    if (border_left) launch_pyr_border(ds, pyr_r, S, p.act_img, border_left);
-  }
-  join_signal(pl, L, L->ev_det, ds);
-  PB(7, st);
-  const bool ba_here = L->ba_pending;
-  const bool pnp_signals = ba_here && fold_signal(pl, L, L->ev_fe, p.kj);  // (the deferred local-map launch starts behind this kernel)
-  launch_ransac_pnp(st, p);
-  p.kj = KJoin{};
-  if (p.pnp_tail_cv) launch_pnp_tail_cv(st, p);
-  PE(7, st);
-  if (ba_here) launch_local_map(pl, L, L->ev_fe, !pnp_signals, prof18);
-  PB(8, st);
-  launch_pose_lm(st, p);  // (with k_track_post's work in its prologue)
-  PE(8, st);
-  PB(9, st);
-  const bool rp_signals = fold_signal(pl, L, L->ev_lm, p.kj);
-  launch_reproj_filter(st, p);
-  p.kj = KJoin{};
-  PE(9, st);
-  // the IMU filter's correction from this frame's pose: on the detection stream (joined with the triangulation before the depth innovation)
-  if (!rp_signals) join_signal(pl, L, L->ev_lm, st);
-  join_wait(pl, L, ds, L->ev_lm);
-  launch_vi_correction(ds, p);
-  // join: FeatureDEM (init: detect, tracking: redetect) consumes the corners; the right pyramid is joined before the stereo LK
-  KJoin dem_kj{};
-  if (!fold_wait(pl, L, L->ev_gftt, dem_kj, 0)) join_wait(pl, L, st, L->ev_gftt);
-  PB(13, st);
-  launch_feature_dem(st, w, h, S, p.cam.dem, L->dem_sorted, L->dem_roff, 2 * p.cam.gftt_num, p.det_mode, p.exist_xy, p.n_exist, NMAX,
-                     p.new_xy, p.n_new, NEW_MAX, &dem_kj);
-  // k_add_new (one wave per stream) stores the word the two-view triangulation waits for: that kernel reads the landmarks as k_add_new leaves
-  // them and nothing k_depth_seeds writes
-  const bool an_signals = fold_signal(pl, L, L->ev_lm, p.kj);
-  const bool merge_seeds = (chain_merge & 1) != 0;  // (k_add_new_seeds carries both launches' joins)
-  if (!merge_seeds) {
-    launch_add_new(st, p);
-    p.kj = KJoin{};
-  }
-  PE(13, st);
-  // depth innovation: stereo LK img0 -> img1 + DLT + IIR
-  PB(14, st);
-  // (k_depth_seeds and k_depth_triangulate store no word themselves: 256 workgroups each -- every workgroup's release is a write-back of its
-  // XCD's L2, and beside the stereo LK's template stores the kernels doubled their time: 5.9 -> 12.7 us, 87 -> 180 us)
-  const bool ds_signals = an_signals;
-  // ... and k_depth_seeds does not end before the right pyramid is there (the stereo LK follows it)
-  const bool seeds_post = fold_post(pl, L, L->ev_det, p.kj);
-  // ... and with templates ahead it looks them up: they must be there
-  if (p.tpl_ahead && !fold_wait(pl, L, L->ev_tpl, p.kj, 0)) join_wait(pl, L, st, L->ev_tpl);
-  if (merge_seeds) launch_add_new_seeds(st, p);
-  else launch_depth_seeds(st, p);
-  p.kj = KJoin{};
-  PE(14, st);
-  // the two-view triangulation that k_depth_innovate consumes: on the detection stream (idle by now), under the stereo LK
-  if (!ds_signals) join_signal(pl, L, L->ev_lm, st);
-  join_wait(pl, L, ds, L->ev_lm);
-  launch_depth_triangulate(ds, p);
-  join_signal(pl, L, L->ev_tri, ds);
-  if (!seeds_post) join_wait(pl, L, st, L->ev_det);
-  PB(15, st);
-  if (!depth_cam) {
-    PyrSel prev, next;
-    fill_pyr(pl, prev, L->pyr0[0], L->pyr0[1], p.img_slot, 0, pl->levels_s);
-    fill_pyr(pl, next, L->pyr1, nullptr, nullptr, 0, pl->levels_s);
-    next.lvl[0] = r0;
-    next.pitch[0] = r0pitch;
-    next.stride[0] = r0stride;
-    if (r_in_place) next.bx[0] = next.by[0] = 0;  // the caller's buffer has no border
-    LKParams prm{30, 1e-3 * 1e-3, 1e-4f, 1};
-    if (pl->lk_stats) prm.stats = reinterpret_cast<unsigned long long*>(p.counters) + 48;  // stereo: counters[48 .. 59]
-    if (pl->lk_stats) prm.stats_tc = reinterpret_cast<unsigned long long*>(p.counters) + 61;
-    if (L->tc) {  // ... which stores its templates for the next frame's temporal tracker
-      prm.tc = L->tc;
-      prm.tc_mode = p.tpl_ahead ? 3 : 1;  // (3: takes those k_lk_templates_ahead made, k_depth_seeds has looked the slots up)
-      prm.tc_cap = p.tc_cap;
-      prm.tc_stride = L->tc_stride;
-      prm.tc_tag = p.lk_tag;
-      prm.tc_slot = p.lk_slot;
-    }
-    prm.dbg_slot = (int)(pl->frames_fed & 7);
-    prm.order = 1;  // the frame's new landmarks, which have no depth to start from, first (profiles/r06_chain_ab.md)
-    launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, prm, p.det_mode, pl->max_pts,
-                    L->tc && p.tpl_ahead ? 4 : 2);
-  }
-  PE(15, st);
-  const bool inn_waits = fold_wait(pl, L, L->ev_tri, p.kj, 0);
-  if (!inn_waits) join_wait(pl, L, st, L->ev_tri);
-  PB(16, st);
-  launch_depth_innovate(st, p);
-  p.kj = KJoin{};
-  PE(16, st);
-  if (with_local_map) {
-    // Keyframe-queue back-pressure, expressed in stream order (never by spinning inside a kernel).  Once every local-map launch of
-    // this lane up to index j has finished, less than ba_backlog = KFQ / 2 keyframes of the frames up to j * ba_every are left in any
-    // queue: the last workgroup that owned the stream's window among those launches stayed until fewer were waiting (k_ba_worker),
-    // and every launch behind it found the queue empty.  The frames since then add at most (D + nba_lane) * ba_every keyframes, so
-    // waiting for the launches of D frames ago (the last one on each of the lane's local-map streams) keeps a queue at
-    // KFQ / 2 - 1 + (D + 2) * ba_every < KFQ when k_frame_end appends: no keyframe is dropped, whatever the optimiser's pace.
-    // (ba_every <= KFQ / 4, flvis_tracker_create.)
-    // (a reset command counts as a keyframe: lane_backpressure_depth)
-    const long long D = lane_backpressure_depth(pl, L);
-    for (int k = 0; k < pl->nba_lane; k++) {
-      const long long j = L->ba_launches - 1 - D - k;
-      if (j >= 0 && L->ba_launches - j <= Lane::BAQ) {
-        if (!(k < 2 && fold_wait(pl, L, L->ev_ba_done[j % Lane::BAQ], p.kj, k))) join_wait(pl, L, st, L->ev_ba_done[j % Lane::BAQ]);
-      }
-    }
-  }
-  PB(17, st);
-  L->endf_valid = fold_signal(pl, L, L->ev_endf, p.kj);
-  launch_frame_end(st, p);
-  p.kj = KJoin{};
-  PE(17, st);
-  PE(19, st);
-  local_map_tail(prof18, prof);
-#undef PB
-#undef PE
-}
-
-extern "C" {
-
-int flvis_image_feed(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times,
-                     flvis_frame_out* h_out, int with_local_map) {
-  return flvis_image_feed_present(ctx, d_img0, d_img1, h_times, nullptr, h_out, with_local_map);
-}
-
-// h_present (may be NULL: every stream): the streams that have a frame in this step (include/flvis_hip.h)
-int flvis_image_feed_present(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times, const uint8_t* h_present,
-                             flvis_frame_out* h_out, int with_local_map) {
-  if (!ctx || !ctx->pipe || !d_img0 || !d_img1 || !h_times) return FLVIS_ERR_INVALID_ARG;
-  Pipeline* pl = ctx->pipe;
-  if (h_present) {
-    bool all = true;
-    for (int s = 0; s < pl->S && all; s++) all = h_present[s] != 0;
-    if (all) h_present = nullptr;  // (the plain step)
-  }
-  hipSetDevice(ctx->device);
-  const size_t img_px = (size_t)pl->cfg.image_width * pl->cfg.image_height;
-  const size_t img1_bytes = img_px * (pl->cfg.cam_type == CAM_DEPTH ? 2 : 1);
-  const bool multi = pl->lanes.size() > 1;
-  const auto t_host0 = std::chrono::steady_clock::now();
-  // the caller's images were produced on the context's stream; lanes with their own streams wait for them, and the
-  // context's stream waits for the lanes afterwards, so that the caller may recycle its buffers in stream order -- the buffers
-  // of THIS frame by default, those handed over input_hold frames ago when the caller cycles through more buffers
-  // (flvis_set_input_hold): only then can the lanes drift apart by more than a frame
-  if (multi) hipEventRecord(pl->ev_in, ctx->stream);
-  for (Lane* L : pl->lanes) {
-    if (multi) hipStreamWaitEvent(L->st, pl->ev_in, 0);
-    lane_frame(ctx, pl, L, d_img0 + (size_t)L->s0 * img_px, d_img1 + (size_t)L->s0 * img1_bytes, h_times + L->s0,
-               h_present ? h_present + L->s0 : nullptr, with_local_map);
-    if (multi) {
-      hipEventRecord(L->ev_end[pl->frames_fed % Lane::HOLD_RING], L->st);
-      const long long rel = pl->frames_fed - pl->input_hold;
-      if (rel >= 0) hipStreamWaitEvent(ctx->stream, L->ev_end[rel % Lane::HOLD_RING], 0);
-    }
-  }
-  pl->host_ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  const bool prof = pl->prof_cap > 0 && pl->prof_step < pl->prof_cap;
-  if (prof) pl->prof_step++;
-  pl->frames_fed++;
-  if (h_present) {
-    for (int s = 0; s < pl->S; s++) pl->stream_frames += h_present[s] != 0;
-  } else {
-    pl->stream_frames += pl->S;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->hip_fail(e, "image_feed launch");
-  if (h_out) {
-    static_assert(sizeof(flvis_frame_out) == sizeof(FrameOut), "FrameOut layout");
-    for (Lane* L : pl->lanes) {
-      e = hipMemcpyAsync(h_out + L->s0, L->pipe.out, sizeof(FrameOut) * L->S, hipMemcpyDeviceToHost, L->st);
-      if (e != hipSuccess) return ctx->hip_fail(e, "image_feed readback");
-    }
-    for (Lane* L : pl->lanes) {
-      e = hipStreamSynchronize(L->st);
-      if (e != hipSuccess) return ctx->hip_fail(e, "image_feed readback");
-    }
-  }
-  return FLVIS_OK;
-}
-
-// TrackingNodeletClass::image_input_callback (src/frontend/vo_tracking.cpp:396-430) hands F2FTracking::image_feed two HOST
-// cv::Mat (mono8, or 3/4 channels converted by cvtColor, f2f_tracking.cpp:74-111; depth rigs: img1 = 16UC1 depth): the same
-// hand-over with plain structs.  Uploads run on a copy stream into double-buffered device staging.
-int flvis_image_feed_host(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, flvis_frame_out* h_out,
-                          int with_local_map, int hold_buffers) {
-  return flvis_image_feed_host_present(ctx, h_img0, h_img1, nullptr, h_out, with_local_map, hold_buffers);
-}
-
-// h_present (may be NULL: every stream): an absent stream's two flvis_image entries are not looked at and nothing of it is uploaded
-int flvis_image_feed_host_present(flvis_ctx* ctx, const flvis_image* h_img0, const flvis_image* h_img1, const uint8_t* h_present,
-                                  flvis_frame_out* h_out, int with_local_map, int hold_buffers) {
-  if (!ctx || !ctx->pipe || !h_img0 || !h_img1) return FLVIS_ERR_INVALID_ARG;
-  Pipeline* pl = ctx->pipe;
-  const int S = pl->S, w = pl->cfg.image_width, h = pl->cfg.image_height;
-  const bool depth_cam = pl->cfg.cam_type == CAM_DEPTH;
-  auto present = [&](int s) { return !h_present || h_present[s] != 0; };
-  int first = 0;  // the first stream with a frame: its images set the channel counts every other one must match
-  while (first < S && !present(first)) first++;
-  const bool any = first < S;
-  const int ch0 = any ? h_img0[first].channels : 1, ch1 = any ? h_img1[first].channels : 1;
-  if ((ch0 != 1 && ch0 != 3 && ch0 != 4) || (ch1 != 1 && ch1 != 3 && ch1 != 4) || (depth_cam && ch1 != 1))
-    return ctx->fail(FLVIS_ERR_INVALID_ARG, "image_feed_host: channels must be 1, 3 or 4 (depth image: 1)");
-  const size_t bpp[2] = {(size_t)ch0, depth_cam ? (size_t)2 : (size_t)ch1};  // bytes per pixel as handed over
-  for (int s = 0; s < S; s++) {
-    if (!present(s)) continue;
-    const flvis_image* im[2] = {&h_img0[s], &h_img1[s]};
-    for (int c = 0; c < 2; c++)
-      if (!im[c]->data || im[c]->width != w || im[c]->height != h || im[c]->channels != (c ? ch1 : ch0) ||
-          (size_t)im[c]->pitch < (size_t)w * bpp[c])
-        return ctx->fail(FLVIS_ERR_INVALID_ARG, "image_feed_host: image size/channels/pitch do not match the configuration");
-  }
-  hipSetDevice(ctx->device);
-  Pipeline::HostFeed& hf = pl->hf;
-  if (!hf.strm) {
-    bool ok = hipStreamCreateWithFlags(&hf.strm, hipStreamNonBlocking) == hipSuccess;
-    for (int k = 0; k < 2 && ok; k++)
-      ok = hipEventCreateWithFlags(&hf.ev_done[k], pl->ev_flags) == hipSuccess &&
-           hipEventCreateWithFlags(&hf.ev_free[k], pl->ev_flags) == hipSuccess && hipEventCreate(&hf.ev_t0[k]) == hipSuccess &&
-           hipEventCreate(&hf.ev_t1[k]) == hipSuccess;
-    if (!ok) return ctx->fail(FLVIS_ERR_HIP, "image_feed_host: cannot create the copy stream");
-    void* hp = nullptr;
-    void* dp = nullptr;
-    if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess)
-      return ctx->fail(FLVIS_ERR_HIP, "image_feed_host: cannot map the progress word");
-    hf.h_up = (volatile long long*)hp;
-    hf.d_up = (long long*)dp;
-    *hf.h_up = 0;
-    hf.times.assign(S, 0.0);
-    if (hf.mode == 2) {
-      // (fine-grained device memory: the copy engine writes it past the XCDs' L2 caches, the waiting wave must never see a cached line)
-      void* dfp = nullptr;
-      bool fok = hipExtMallocWithFlags(&dfp, sizeof(long long) * Pipeline::HostFeed::FLAG_WORDS, hipDeviceMallocFinegrained) == hipSuccess;
-      if (fok) {
-        hipMemset(dfp, 0, sizeof(long long) * Pipeline::HostFeed::FLAG_WORDS);
-        pl->allocs.push_back(dfp);
-        hf.d_flag = (long long*)dfp;
-      }
-      for (int k = 0; k < Pipeline::HostFeed::FLAG_RING && fok; k++) {
-        void* fp = nullptr;
-        fok = hipHostMalloc(&fp, sizeof(long long) * Pipeline::HostFeed::FLAG_WORDS, hipHostMallocDefault) == hipSuccess;
-        hf.h_flag[k] = (long long*)fp;
-      }
-      if (!fok) return ctx->fail(FLVIS_ERR_HIP, "image_feed_host: cannot allocate the sequence blocks");
-    }
-  }
-  const int n_slots = hf.mode == 2 ? Pipeline::HostFeed::SLOTS : 2;
-  const size_t npix = (size_t)S * w * h;
-  for (int c = 0; c < 2; c++) {
-    const size_t need = npix * bpp[c] + 256;
-    if (hf.raw_bytes[c] < need) {
-      hipStreamSynchronize(hf.strm);
-      hipStreamSynchronize(ctx->stream);
-      for (Lane* L : pl->lanes) hipStreamSynchronize(L->det_stream);
-      for (int k = 0; k < n_slots; k++)
-        if (!(hf.raw[k][c] = dalloc<uint8_t>(pl->allocs, need, false))) return ctx->fail(FLVIS_ERR_HIP, "image_feed_host: device allocation failed");
-      hf.raw_bytes[c] = need;
-    }
-  }
-  if ((ch0 > 1 || (ch1 > 1 && !depth_cam)) && hf.gray_bytes < npix + 256) {
-    for (int k = 0; k < n_slots; k++)
-      for (int c = 0; c < 2; c++)
-        if (!(hf.gray[k][c] = dalloc<uint8_t>(pl->allocs, npix + 256, false))) return ctx->fail(FLVIS_ERR_HIP, "image_feed_host: device allocation failed");
-    hf.gray_bytes = npix + 256;
-  }
-  const int slot = (int)(hf.n % n_slots), tslot = (int)(hf.n & 1);
-  // hold_buffers contract: the previous call's buffers are free when this call returns -- its uploads must be done.
-  // Mode 1: polled on a host-mapped counter a kernel of the copy stream stores after the uploads (hipEventSynchronize on its event also
-  // waited for the KERNELS of the previous frame, so uploads and frames never overlapped: measured 2.25 ms per step = upload + frame).
-  // Mode 2: hipStreamQuery on the copy stream, which holds nothing but the copies (the host reads the last copy's signal; no packet).
-  auto wait_uploads = [&](long long calls) {
-    int polls = 0;
-    if (hf.mode == 2) {
-      while (hipStreamQuery(hf.strm) == hipErrorNotReady) {
-        if (++polls > 16) std::this_thread::sleep_for(std::chrono::microseconds(20));
-      }
-      (void)hipGetLastError();
-      return;
-    }
-    while (*hf.h_up < calls) {
-      if ((++polls & 255) == 0 && hipStreamQuery(hf.strm) == hipSuccess && *hf.h_up < calls) break;  // (idle copy stream: a failed copy)
-      std::this_thread::sleep_for(std::chrono::microseconds(30));
-    }
-  };
-  const auto th0 = std::chrono::steady_clock::now();
-  if (hf.n >= 1) wait_uploads(hf.n);
-  const auto th1 = std::chrono::steady_clock::now();
-  // the frame that used this slot has been consumed.  (NOT implied by the host lead: the uploads are issued before this call waits for the
-  // previous frame to start, i.e. while the frame before that may still be reading the slot -- without this wait the leg's poses differ from
-  // the resident run's, bench.py's check caught it in round 5)
-  // Mode 1: the copy stream waits for an event recorded behind that frame.  Mode 2: the HOST looks at the lanes' progress words -- the slot
-  // was read by lane frame slot_frame[slot]; once a later frame of every lane has started (k_frame_head publishes its number when it
-  // starts, behind k_frame_end of its predecessor and the joins in front of that), or the lane's stream has run dry, nothing reads it any
-  // more.  With three slots the frame in question lies three calls back: the test is true when it is made.
-  if (hf.mode == 2) {
-    const long long need = hf.slot_frame[slot] + 1;
-    if (hf.slot_frame[slot] > 0)
-      for (Lane* L : pl->lanes) {
-        int polls = 0;
-        while (*L->h_progress < need) {
-          if ((++polls & 63) == 0 && hipStreamQuery(L->st) == hipSuccess) break;  // (an idle stream: the frame is over, or its launch failed)
-          std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-      }
-  } else if (hf.n >= 2) {
-    hipStreamWaitEvent(hf.strm, hf.ev_free[slot], 0);
-  }
-  if (hf.timed[tslot]) {  // the uploads of two calls ago: done (the previous call's are, and the copy stream is in order)
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, hf.ev_t0[tslot], hf.ev_t1[tslot]) == hipSuccess) hf.up_ms += ms, hf.up_bytes += (double)hf.timed_bytes[tslot], hf.up_calls += 1;
-    else (void)hipGetLastError();
-    hf.timed[tslot] = false;
-  }
-  if (hf.timing) hipEventRecord(hf.ev_t0[tslot], hf.strm);
-  // (Measured in round 4, profiles/r04_h2d_full_timeline_*.txt: beside an SDMA upload the chain's latency-bound kernels run 2-3 x slower,
-  // the LK launches do not.  Gating the uploads under LK launches -- left image under the previous frame's stereo LK, right image under
-  // the frame's own head / temporal LK -- made the leg slower, 40k -> 31k frames/s: k_frame_head / k_track_prepare are latency-bound too
-  // and the later start of the copies costs host lead.  A copy KERNEL of 8 .. 128 workgroups reading the caller's page-locked buffer over
-  // PCIe instead of the SDMA engine: 19-34k frames/s against 35.3k (profiles/r04_lk_ab.md).  The uploads start as soon as their
-  // staging slot is free, on the SDMA engine.  Round 6: what slowed the chain was not the copy but the barrier packets that waited for
-  // it on the copy stream's hardware queue -- mode 2 has none, profiles/r06_h2d.md.)
-  hipError_t e = hipSuccess;
-  for (int c = 0; c < 2 && e == hipSuccess; c++) {
-    const flvis_image* im = c ? h_img1 : h_img0;
-    const size_t row = (size_t)w * bpp[c], img_bytes = row * h;
-    bool contiguous = !h_present;  // one block [S][h][w*bpp]: a single copy (every stream's image)
-    for (int s = 0; s < S && contiguous; s++)
-      contiguous = (size_t)im[s].pitch == row && im[s].data == im[0].data + (size_t)s * img_bytes;
-    // (in one piece: chunked uploads were slower, profiles/r05_h2d.md)
-    if (contiguous) {
-      e = hipMemcpyAsync(hf.raw[slot][c], im[0].data, img_bytes * S, hipMemcpyHostToDevice, hf.strm);
-    } else {
-      for (int s = 0; s < S && e == hipSuccess; s++)
-        if (present(s))
-          e = hipMemcpy2DAsync(hf.raw[slot][c] + (size_t)s * img_bytes, row, im[s].data, (size_t)im[s].pitch, row, h,
-                               hipMemcpyHostToDevice, hf.strm);
-    }
-  }
-  if (hf.timing && e == hipSuccess) {
-    hipEventRecord(hf.ev_t1[tslot], hf.strm);
-    hf.timed[tslot] = true;
-    hf.timed_bytes[tslot] = (size_t)w * h * S * (bpp[0] + bpp[1]);
-  }
-  const long long seq = hf.n + 1;
-  if (hf.mode == 2) {
-    // the sequence block behind the images (page-locked ring of FLAG_RING blocks: the block of call n is rewritten by call n + FLAG_RING,
-    // whose predecessors' uploads the host has seen finish)
-    long long* fb = hf.h_flag[hf.n % Pipeline::HostFeed::FLAG_RING];
-    for (int k = 0; k < Pipeline::HostFeed::FLAG_WORDS; k++) fb[k] = seq;
-    if (e == hipSuccess) e = hipMemcpyAsync(hf.d_flag, fb, sizeof(long long) * Pipeline::HostFeed::FLAG_WORDS, hipMemcpyHostToDevice, hf.strm);
-    if (e != hipSuccess) return ctx->hip_fail(e, "image_feed_host upload");
-  } else {
-    if (e == hipSuccess) e = hipEventRecord(hf.ev_done[slot], hf.strm);
-    if (e != hipSuccess) return ctx->hip_fail(e, "image_feed_host upload");
-    launch_store_progress(hf.strm, hf.d_up, seq);
-  }
-  hipStream_t st = ctx->stream;
-  // Which stream waits for the uploads.  In mode 2 the detection stream, in front of the left image's ingest: every reader of the staged
-  // images is ordered behind that stream already -- the left pyramid's join in front of the temporal LK, the right pyramid's in front of
-  // the stereo LK, which reads the right image in place.  Only for single-channel stereo input on a single lane past the skipped start-up
-  // frames; otherwise, and in mode 1, the main stream waits, in front of the frame (rounds 1-5: always; profiles/r06_h2d.md).
-  const bool wait_on_det = hf.mode == 2 && ch0 == 1 && ch1 == 1 && !depth_cam && pl->lanes.size() == 1 &&
-                           pl->frames_fed >= (long long)pl->cfg.skip_first_n_imgs;
-  if (hf.mode == 2) {
-    if (wait_on_det) pl->up_flag = hf.d_flag, pl->up_seq = seq;
-    else launch_wait_flag(st, hf.d_flag, Pipeline::HostFeed::FLAG_WORDS, seq, pl->lanes[0]->d_progress + 2);
-  } else {
-    if (wait_on_det) pl->up_event = hf.ev_done[slot];
-    else hipStreamWaitEvent(st, hf.ev_done[slot], 0);
-  }
-  const uint8_t* d0 = hf.raw[slot][0];
-  const uint8_t* d1 = hf.raw[slot][1];
-  if (ch0 > 1) {
-    launch_bgr_to_gray(st, hf.raw[slot][0], ch0, hf.gray[slot][0], npix);
-    d0 = hf.gray[slot][0];
-  }
-  if (ch1 > 1 && !depth_cam) {
-    launch_bgr_to_gray(st, hf.raw[slot][1], ch1, hf.gray[slot][1], npix);
-    d1 = hf.gray[slot][1];
-  }
-  for (int s = 0; s < S; s++) hf.times[s] = present(s) ? h_img0[s].t : 0.0;
-  // one frame of lead in this mode: with two, the uploads' copies and events push the queued commands over what the HIP runtime
-  // accepts without blocking the caller for milliseconds (measured: 16k vs 28k frames/s when that happened mid-run, profiles/r05_h2d.md)
-  pl->host_lead_cap = 1;
-  const auto th2 = std::chrono::steady_clock::now();
-  pl->chain_continuous = wait_on_det && hf.mode == 2 && hf.last_call_frame == pl->frames_fed;  // (the previous frame was this entry's too)
-  const int rc = flvis_image_feed_present(ctx, d0, d1, hf.times.data(), h_present, h_out, with_local_map);
-  pl->chain_continuous = false;
-  hf.last_call_frame = pl->frames_fed;
-  pl->up_event = nullptr;
-  pl->up_flag = nullptr;
-  const auto th3 = std::chrono::steady_clock::now();
-  hf.ms_wait_uploads += std::chrono::duration<double, std::milli>(th1 - th0).count();
-  hf.ms_issue += std::chrono::duration<double, std::milli>(th2 - th1).count();
-  hf.ms_feed += std::chrono::duration<double, std::milli>(th3 - th2).count();
-  pl->host_lead_cap = 4;
-  if (hf.mode == 2) hf.slot_frame[slot] = pl->lanes[0]->frames_uploaded;
-  else hipEventRecord(hf.ev_free[slot], st);
-  hf.n++;
-  if (rc != FLVIS_OK) return rc;
-  if (!hold_buffers) wait_uploads(hf.n);  // the caller may reuse its buffers at once: wait for the uploads (not for the frame)
-  return FLVIS_OK;
-}
-
-
-int flvis_imu_feed_all(flvis_ctx* ctx, const int* h_counts, const double* h_samples, int samples_per_stream) {
-  if (!ctx || !ctx->pipe || !h_counts || !h_samples || samples_per_stream <= 0) return FLVIS_ERR_INVALID_ARG;
-  Pipeline* pl = ctx->pipe;
-  for (int s = 0; s < pl->S; s++) {
-    int n = h_counts[s];
-    if (n < 0 || n > samples_per_stream) return ctx->fail(FLVIS_ERR_INVALID_ARG, "imu_feed_all: bad count");
-    int rc = flvis_imu_feed_flvis_frame(ctx, s, n, h_samples + (size_t)s * samples_per_stream * 7);
-    if (rc) return rc;
-  }
-  return FLVIS_OK;
-}
-
-// The caller's per-frame loop (IMU samples, then the stereo pair) for n_steps frames in ONE call: a driver that feeds frames already
-// resident in HBM -- a replay, bench.py's timed region, one rank of a multi-GPU job -- does not come back to its host language between
-// frames (eight Python interpreters on one host contending for cores are then not on the path).
-int flvis_run_steps(flvis_ctx* ctx, int n_steps, const flvis_step* steps, int with_local_map, double* h_call_ms) {
-  return flvis_run_steps_present(ctx, n_steps, steps, nullptr, with_local_map, h_call_ms);
-}
-
-// h_present (may be NULL: every stream in every step): [n_steps][n_streams], row k for step k as flvis_image_feed_present takes it
-int flvis_run_steps_present(flvis_ctx* ctx, int n_steps, const flvis_step* steps, const uint8_t* h_present, int with_local_map,
-                            double* h_call_ms) {
-  if (!ctx || !ctx->pipe || n_steps < 0 || (n_steps > 0 && !steps)) return FLVIS_ERR_INVALID_ARG;
-  for (int k = 0; k < n_steps; k++) {
-    const flvis_step& f = steps[k];
-    const auto t0 = std::chrono::steady_clock::now();
-    if (f.h_imu_counts) {
-      const int rc = flvis_imu_feed_all(ctx, f.h_imu_counts, f.h_imu_samples, f.imu_samples_per_stream);
-      if (rc != FLVIS_OK) return rc;
-    }
-    ctx->pipe->defer_ba = k + 1 < n_steps;
-    ctx->pipe->chain_continuous = k > 0;
-    const int rc = flvis_image_feed_present(ctx, f.d_img0, f.d_img1, f.h_times, h_present ? h_present + (size_t)k * ctx->pipe->S : nullptr,
-                                            nullptr, with_local_map);
-    ctx->pipe->defer_ba = false;
-    ctx->pipe->chain_continuous = false;
-    if (rc != FLVIS_OK) return rc;
-    if (h_call_ms) h_call_ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return FLVIS_OK;
-}
 
 int flvis_prof_enable(flvis_ctx* ctx, int max_steps) { return flvis_prof_enable_stages(ctx, max_steps, ~0ull); }
 
@@ -2406,14 +1240,10 @@ static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, c
     if (todo.empty()) continue;
     if (new_cmd) {
       L->lmc_cmds++;
-      // the command takes a queue entry: the back-pressure of a keyframe append, counting it (lane_backpressure_depth)
+      // the command takes a queue entry: the back-pressure of a keyframe append, counting it (lane_backpressure_wait)
       if (L->cmd_steps.empty() || L->cmd_steps.back() != L->frames_uploaded) L->cmd_steps.push_back(L->frames_uploaded);
       L->cmd_since_frame = true;
-      const long long D = lane_backpressure_depth(pl, L);
-      for (int k = 0; k < pl->nba_lane; k++) {
-        const long long j = L->ba_launches - 1 - D - k;
-        if (j >= 0 && L->ba_launches - j <= Lane::BAQ) join_wait(pl, L, L->st, L->ev_ba_done[j % Lane::BAQ]);
-      }
+      lane_backpressure_wait(pl, L, nullptr);
     }
     if (cfgs) {
       for (const auto& e : todo) {
@@ -2504,7 +1334,7 @@ int lm_cloud_settle(flvis_ctx* ctx, const char* what, LmCloudRec& rec, int& S) {
   S = pl->S;
   if (!what) return FLVIS_OK;
   for (Lane* L : pl->lanes)
-    if (L->ba_pending) launch_local_map(pl, L, L->ev_fe, true, nullptr);  // (a launch deferred into the next frame: there is none)
+    if (L->ba_pending) launch_local_map(pl, L, J_FE, true, nullptr);  // (a launch deferred into the next frame: there is none)
   if (!pl->lmc_ev && hipEventCreateWithFlags(&pl->lmc_ev, Pipeline::ev_flags) != hipSuccess) return ctx->hip_fail(hipGetLastError(), what);
   // the context's stream behind the lanes' tracking streams (a reset's kernel) and the local-map streams (the workers, their append kernels)
   auto behind = [&](hipStream_t s) {

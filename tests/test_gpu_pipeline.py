@@ -1139,58 +1139,16 @@ def _assert_same_run(a, b, what):
     assert na == nb_, (what, na, nb_)
 
 
-def test_stream_join_forms_leave_the_same_results(ctx, monkeypatch):
-    """Round 6: the joins between a lane's streams are device words (k_store_flag / k_wait_flag) and, where the chain's own kernels can
-    carry them, folded into those kernels (KJoin) -- instead of hipEventRecord / hipStreamWaitEvent.  FLVIS_JOIN=event (rounds 1-5),
-    flag joins without folding and the default must leave the same trajectories, landmarks, CorrectionInf and counters, bit for bit --
-    frame by frame (per-frame callers: the explicit frame-start join) and in batches (flvis_run_steps: the folded one, the deferred
-    local-map launch behind k_ransac_pnp)."""
+def _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, streams, ref_name):
+    """Runs 50 + 36 frames of 8 streams under every (name, environment) form, frame by frame and in batches, and compares every run
+    with the frame-by-frame run of the form `ref_name`, bit for bit."""
     import flvis_amd
     cfg, _ = _cfgs()
     S, nframes = 8, 50 + 36
-    frames = _mode_frames(S, nframes, [3 + 7 * i for i in range(S)])
+    frames = _mode_frames(S, nframes, streams)
+    knobs = sorted({k for _, env in forms for k in env})
     res = {}
-    for name, env in (("event", {"FLVIS_JOIN": "event"}), ("flag", {"FLVIS_JOIN_FOLD": "0"}), ("default", {})):
-        for k in ("FLVIS_JOIN", "FLVIS_JOIN_FOLD"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        for feed in ("frames", "batches"):
-            trk = flvis_amd.Tracker(ctx, cfg, S, seed_base=0xF1715, traj_capacity=nframes)
-            if feed == "frames":
-                for (i0, i1, ts, cnt, blk) in frames:
-                    for i in range(S):
-                        trk.imu_feed_flvis(i, blk[i, :cnt[i]])
-                    trk.image_feed(i0, i1, ts, want_out=False, with_local_map=True)
-            else:
-                f = 0
-                for nb in (50, 1, 5, 2, nframes):
-                    nb = min(nb, nframes - f)
-                    if nb > 0:
-                        trk.run_steps(frames[f:f + nb], with_local_map=True)
-                    f += nb
-            res[(name, feed)] = _mode_result(trk, ctx, S, nframes)
-            del trk
-    ref = res[("event", "frames")]
-    assert np.all((ref[0][:, 50:, 8].astype(int) & 15) == 1) and ref[4].sum() > 2 * S and ref[5].sum() >= 1
-    for key, r in res.items():
-        _assert_same_run(ref, r, key)
-
-
-def test_templates_ahead_leave_the_same_results(ctx, monkeypatch):
-    """Round 6: the stereo matcher's templates of the landmarks the temporal tracker has followed into the frame are computed AHEAD, by
-    k_lk_templates_ahead on a stream of its own beside the frame's geometry kernels, and the stereo launch takes them from the cache
-    (FLVIS_TPL_AHEAD=1, an opt-in knob: measured, not faster -- profiles/r06_templates_ahead.md).  With them, with the kernel started behind
-    k_track_collect instead of behind the F-RANSAC (FLVIS_TPL_START=0), with event joins, and without them (the default: rounds 4-5) a
-    run must leave the same trajectories, landmarks, CorrectionInf and counters, bit for bit -- frame by frame and in batches."""
-    import flvis_amd
-    cfg, _ = _cfgs()
-    S, nframes = 8, 50 + 36
-    frames = _mode_frames(S, nframes, [5 + 3 * i for i in range(S)])
-    res = {}
-    knobs = ("FLVIS_TPL_AHEAD", "FLVIS_TPL_START", "FLVIS_JOIN")
-    for name, env in (("off", {}), ("ahead", {"FLVIS_TPL_AHEAD": "1"}), ("start0", {"FLVIS_TPL_AHEAD": "1", "FLVIS_TPL_START": "0"}),
-                      ("event", {"FLVIS_TPL_AHEAD": "1", "FLVIS_JOIN": "event"})):
+    for name, env in forms:
         for k in knobs:
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
@@ -1213,46 +1171,39 @@ def test_templates_ahead_leave_the_same_results(ctx, monkeypatch):
             del trk
     for k in knobs:
         monkeypatch.delenv(k, raising=False)
-    ref = res[("off", "frames")]
+    ref = res[(ref_name, "frames")]
     assert np.all((ref[0][:, 50:, 8].astype(int) & 15) == 1) and ref[4].sum() > 2 * S and ref[5].sum() >= 1
     for key, r in res.items():
         _assert_same_run(ref, r, key)
+
+
+def test_stream_join_forms_leave_the_same_results(ctx, monkeypatch):
+    """Round 6: the joins between a lane's streams are device words (k_store_flag / k_wait_flag) and, where the chain's own kernels can
+    carry them, folded into those kernels (KJoin) -- instead of hipEventRecord / hipStreamWaitEvent.  FLVIS_JOIN=event (rounds 1-5),
+    flag joins without folding and the default must leave the same trajectories, landmarks, CorrectionInf and counters, bit for bit --
+    frame by frame (per-frame callers: the explicit frame-start join) and in batches (flvis_run_steps: the folded one, the deferred
+    local-map launch behind k_ransac_pnp)."""
+    forms = (("event", {"FLVIS_JOIN": "event"}), ("flag", {"FLVIS_JOIN_FOLD": "0"}), ("default", {}))
+    _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, [3 + 7 * i for i in range(8)], "event")
+
+
+def test_templates_ahead_leave_the_same_results(ctx, monkeypatch):
+    """Round 6: the stereo matcher's templates of the landmarks the temporal tracker has followed into the frame are computed AHEAD, by
+    k_lk_templates_ahead on a stream of its own beside the frame's geometry kernels, and the stereo launch takes them from the cache
+    (FLVIS_TPL_AHEAD=1, an opt-in knob: measured, not faster -- profiles/r06_templates_ahead.md).  With them, with the kernel started behind
+    k_track_collect instead of behind the F-RANSAC (FLVIS_TPL_START=0), with event joins, and without them (the default: rounds 4-5) a
+    run must leave the same trajectories, landmarks, CorrectionInf and counters, bit for bit -- frame by frame and in batches."""
+    forms = (("off", {}), ("ahead", {"FLVIS_TPL_AHEAD": "1"}), ("start0", {"FLVIS_TPL_AHEAD": "1", "FLVIS_TPL_START": "0"}),
+             ("event", {"FLVIS_TPL_AHEAD": "1", "FLVIS_JOIN": "event"}))
+    _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, [5 + 3 * i for i in range(8)], "off")
 
 
 def test_chain_merge_forms_leave_the_same_results(ctx, monkeypatch):
     """Round 6: launches of the frame's chain folded into their neighbours (FLVIS_CHAIN_MERGE, bits: 1 = k_add_new + k_depth_seeds as one
     launch, 2 = k_track_collect as the prologue of k_ransac_f, by sixteen waves instead of one; default 3).  Every combination must leave
     the same trajectories, landmarks, CorrectionInf and counters as rounds 1-5's launches (0), bit for bit -- frame by frame and in batches."""
-    import flvis_amd
-    cfg, _ = _cfgs()
-    S, nframes = 8, 50 + 36
-    frames = _mode_frames(S, nframes, [2 + 5 * i for i in range(S)])
-    res = {}
-    for merge in ("0", "1", "2", "3", None):
-        monkeypatch.delenv("FLVIS_CHAIN_MERGE", raising=False)
-        if merge is not None:
-            monkeypatch.setenv("FLVIS_CHAIN_MERGE", merge)
-        for feed in ("frames", "batches"):
-            trk = flvis_amd.Tracker(ctx, cfg, S, seed_base=0xF1715, traj_capacity=nframes)
-            if feed == "frames":
-                for (i0, i1, ts, cnt, blk) in frames:
-                    for i in range(S):
-                        trk.imu_feed_flvis(i, blk[i, :cnt[i]])
-                    trk.image_feed(i0, i1, ts, want_out=False, with_local_map=True)
-            else:
-                f = 0
-                for nb in (50, 1, 5, 2, nframes):
-                    nb = min(nb, nframes - f)
-                    if nb > 0:
-                        trk.run_steps(frames[f:f + nb], with_local_map=True)
-                    f += nb
-            res[(merge, feed)] = _mode_result(trk, ctx, S, nframes)
-            del trk
-    monkeypatch.delenv("FLVIS_CHAIN_MERGE", raising=False)
-    ref = res[("0", "frames")]
-    assert np.all((ref[0][:, 50:, 8].astype(int) & 15) == 1) and ref[4].sum() > 2 * S and ref[5].sum() >= 1
-    for key, r in res.items():
-        _assert_same_run(ref, r, key)
+    forms = [(m, {"FLVIS_CHAIN_MERGE": m}) for m in ("0", "1", "2", "3")] + [(None, {})]
+    _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, [2 + 5 * i for i in range(8)], "0")
 
 
 def test_host_feed_upload_forms_leave_the_same_results(ctx, monkeypatch):

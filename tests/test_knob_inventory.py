@@ -87,9 +87,13 @@ def test_no_retired_build_variant_arms():
 
 
 def test_the_frame_path_reads_no_environment():
-    """The knobs are read once, when a tracker is created (read_knobs): none of the per-frame functions calls getenv."""
+    """The knobs are read once, when a tracker is created: the files of the per-frame path do not name getenv at all, and pipeline.cpp
+    only inside the three functions that read the knobs."""
+    for name in ("frame_schedule.cpp", "host_feed.cpp"):
+        assert "getenv" not in _read(os.path.join(CSRC, name)), name
     src = _read(os.path.join(CSRC, "pipeline.cpp"))
-    for fn in ("lane_frame", "pyramid_levels", "flvis_image_feed_host", "launch_local_map"):
+    readers = []
+    for fn in ("read_knobs", "env_is", "ba_lds_bytes_env"):
         m = re.search(r"^(?:static )?\w[\w:<>*& ]*\b%s\(" % fn, src, re.M)
         assert m, fn
         body_start = src.index("{", m.end())
@@ -100,4 +104,7 @@ def test_the_frame_path_reads_no_environment():
             if depth == 0:
                 break
             i += 1
-        assert "getenv" not in src[body_start:i], fn
+        assert "getenv" in src[body_start:i], fn
+        readers.append((body_start, i))
+    for m in re.finditer("getenv", src):
+        assert any(a < m.start() < b for a, b in readers), "pipeline.cpp:%d" % (src.count("\n", 0, m.start()) + 1)
