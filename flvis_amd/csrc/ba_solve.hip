@@ -28,8 +28,8 @@
 //     into the trial buffers, the records overwritten): an accepted trial -- the rule -- leaves the next iteration nothing to linearise.
 // The phase functions are kept small enough to live in the caller-saved registers: a called function that needs more stores and
 // reloads every callee-saved register it touches through scratch memory, per call.
-// This is latency-bound fp64 on a tiny problem (S is at most 90x90); the matrix cores were measured for the Schur complement (slower:
-// FLVIS_BA_MFMA=1, ba_phase_schur_mfma) and are not used.
+// This is latency-bound fp64 on a tiny problem (S is at most 90x90); the matrix cores were measured for the Schur complement and were
+// slower (profiles/r02_ba_phases.md); that path is retired.
 #include "dev_common.hpp"
 #include "dev_geom.hpp"
 #include "track_kernels.hpp"
@@ -41,23 +41,9 @@ namespace flvis {
 #define FLVIS_BA_IT1 12
 #define FLVIS_BA_IT2 8
 #endif
-#ifndef FLVIS_BA_T
-#define FLVIS_BA_T 512  // (build-variant knob: threads of a local-map workgroup)
-#endif
-constexpr int BA_T = FLVIS_BA_T;
-// (build-variant knob: waves per SIMD the kernel's register allocation aims at -- the backend hands the budget on to the out-of-line
-// phases.  By default (2: the workgroup's own two waves per SIMD) a local-map workgroup may take the whole register file of its CU, so
-// that no wave of another kernel fits beside it)
-#ifdef FLVIS_BA_WAVES
-#define BA_ATTR __attribute__((amdgpu_waves_per_eu(FLVIS_BA_WAVES, FLVIS_BA_WAVES)))
-#else
-#define BA_ATTR
-#endif
-// (build-variant knob: the per-trial phases as calls -- each with a register allocation of its own, and ~110 callee-saved VGPRs stored and
-// reloaded around every call -- or inlined into ba_optimize)
-#ifndef FLVIS_BA_PHASE_FN
-#define FLVIS_BA_PHASE_FN __noinline__
-#endif
+// 512 threads per window, the register budget of the workgroup's own two waves per SIMD, and the per-trial phases as calls: the other
+// values of the three were measured and lost (profiles/r04_local_map_and_streams_ab.md)
+constexpr int BA_T = 512;
 constexpr int BA_NW = BA_T / 64;
 constexpr int BA_PMAX = BA_WMAX - 1;   // free poses
 constexpr int BA_NRMAX = 6 * BA_PMAX;  // 90
@@ -143,14 +129,7 @@ struct BAShared {
   int fixed_slot;  // ring slot of the fixed pose if it has observations (its pixels are the only ones read from HBM per phase then), else -1
   int CI, CL, bufd, nchunk;         // chunk capacities (items, landmarks), doubles per buffer, chunk count
   int npairs, slices, rs;           // role partition of the Schur phase
-  // ... balanced (round 6): lanes per pose pair in proportion to the landmarks the pair shares (powers of two, 4 .. 64), the diagonal
-  // pairs in whole waves of their own.  pair_tab[pair] = first thread | log2(lanes) << 12 | i1 << 16 | i2 << 20; role_pair[thread] = its
-  // pair (255: none); pair_cnt = landmarks seen by both poses of the pair
-  int balance, balanced, max_slices;
-  int pair_cnt[64];
-  unsigned pair_tab[64];
-  unsigned char role_pair[BA_T];
-  int use_mfma, NRp, CLm, nchunk_m;  // MFMA variant of the Schur phase: padded system size, landmarks per dense chunk
+  // (lanes per pose pair in proportion to the landmarks the pair shares were measured with no gain: profiles/r06_ba_phases.md)
   // IMU rotation edges (optional factor): edge k links ring slots imu_a[k] -> imu_b[k]
   int n_imu, imu_a[BA_WMAX], imu_b[BA_WMAX];
   double imu_w[BA_WMAX], imu_dq[BA_WMAX][4], q_c_b[4];
@@ -172,7 +151,10 @@ struct BAShared {
 // all per-window working state lives in dynamic LDS; the phase functions re-derive it from this symbol so that the
 // compiler keeps LDS addressing (ds_* instructions) inside non-inlined functions
 extern __shared__ __attribute__((aligned(16))) unsigned char ba_smem[];
-constexpr size_t BA_SH_BYTES = ((sizeof(BAShared) + 15) / 16) * 16;
+// (a fixed reserve, not sizeof: the chunk table of a budget, and with it the order of summation of a streamed window, stays what it was when
+// the header loses or gains a field)
+constexpr size_t BA_SH_BYTES = 16528;
+static_assert(sizeof(BAShared) <= BA_SH_BYTES, "the header outgrew its reserve of the dynamic LDS");
 FD BAShared& ba_sh() { return *reinterpret_cast<BAShared*>(ba_smem); }
 // (ba_update_dev stages the bag's landmark ids at the start of the dynamic LDS -- and reads up to seven entries past them --: any admitted budget holds them)
 static_assert(BA_SH_BYTES + 8 * (BA_LMAX + 8) <= 64 * 1024, "the bookkeeping's id list must fit the smallest LDS budget");
@@ -380,108 +362,6 @@ FD Chol3 chol3(const double* H, double lambda) {
   return g;
 }
 
-// sum over the wave as a wave-uniform value
-FD int ba_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-FD int ba_wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
-// Lanes of the Schur accumulate per pose pair (round 6; ONE wave, lane = pair, pairs numbered as ba_schur_role numbers them: the P
-// diagonal pairs, then i1 < i2 row by row).  A pair's lanes split the landmarks both of its poses see among them; with 16 lanes for every
-// pair a window's neighbouring keyframes (~150-190 shared landmarks) kept their waves busy four to eight times as long as the pairs six
-// keyframes apart (~20), and the phase ended with the slowest wave (profiles/r05_ba_phases.md: 108 us of waiting per optimisation).
-// Here a pair gets a power of two of lanes (4 .. 64) in proportion to its landmark count (a diagonal pair's product, which carries the
-// right-hand side, counts 4 : 3), the largest counts that fit the workgroup: the diagonal pairs in whole waves of their own (a wave
-// holding both kinds would run the two product bodies one after the other), each region sorted by lane count so that a group never
-// straddles a DPP row it does not fill.  A function of the window's structure only: the same partition, the same order of summation, run
-// after run.
-FD void ba_balance_pairs() {
-  BAShared& sh = ba_sh();
-  const int p = threadIdx.x & 63, P = sh.P, NP = P + P * (P - 1) / 2;
-  const bool diag = p < P, on = p < NP;
-  // work of the pair per LM trial in units of a ninth of an off-diagonal block product (two records, a 6x6 tile: measured ~1.8 times the
-  // diagonal product with its lower triangle and right-hand side)
-  const int load = on ? sh.pair_cnt[p] * (diag ? 5 : 9) : 0;
-  const int total = ba_wave_sum_i(load);
-  int sl = on ? 4 : 0, dsum = 0, osum = 0;
-  if (total > 0) {
-    const float base = (float)load * (float)BA_T / (float)total;  // lanes at the even share of work per lane
-    for (int k = 0; k < 40; k++) {                                // ... at 2^(k/4) times that share: the first that fits
-      const float need = base * exp2f(-0.25f * (float)k);
-      const int c = !on ? 0 : need <= 4.f ? 4 : need <= 8.f ? 8 : need <= 16.f ? 16 : need <= 32.f ? 32 : 64;
-      dsum = ba_wave_sum_i(diag ? c : 0);
-      osum = ba_wave_sum_i(diag ? 0 : c);
-      if (((dsum + 63) & ~63) + osum <= BA_T) {
-        sl = c;
-        break;
-      }
-    }
-  }
-  dsum = ba_wave_sum_i(diag ? sl : 0);
-  osum = ba_wave_sum_i(diag ? 0 : sl);
-  // what is left over goes to the busiest lanes, one doubling at a time
-  for (int it = 0; it < 8; it++) {
-    const int q = on && sl < 64 ? (load << 8) / sl : -1;  // load per lane (sl is a power of two: a shift)
-    const int qm = ba_wave_max_i(q);
-    if (qm <= 0) break;
-    const unsigned long long who = __ballot(q == qm);
-    const int w0 = __builtin_ctzll(who);  // (one pair per step: the first of the busiest)
-    const int wsl = __shfl(sl, w0, 64);
-    const int nd = dsum + (w0 < P ? wsl : 0), no = osum + (w0 < P ? 0 : wsl);
-    if (((nd + 63) & ~63) + no > BA_T) break;
-    if (p == w0) sl *= 2;
-    dsum = nd;
-    osum = no;
-  }
-  // first thread of every pair: its region's pairs with more lanes in front of it, equal ones in pair order
-  int off = 0;
-  for (int q = 0; q < NP; q++) {
-    const int sq = __shfl(sl, q, 64);
-    if ((q < P) == diag && (sq > sl || (sq == sl && q < p))) off += sq;
-  }
-  if (!diag) off += (dsum + 63) & ~63;
-  if (on) {
-    int i1 = p, i2 = p;
-    if (!diag) {
-      int rem = p - P;
-      i1 = 0;
-      while (rem >= P - 1 - i1) {
-        rem -= P - 1 - i1;
-        i1++;
-      }
-      i2 = i1 + 1 + rem;
-    }
-    sh.pair_tab[p] = (unsigned)off | ((unsigned)(31 - __builtin_clz(sl)) << 12) | ((unsigned)i1 << 16) | ((unsigned)i2 << 20);
-  }
-  // role_pair: the lanes write the table side by side, pair after pair
-  for (int q = 0; q < NP; q++) {
-    const int sq = __shfl(sl, q, 64), oq = __shfl(off, q, 64);
-    if (p < sq) sh.role_pair[oq + p] = (unsigned char)q;
-  }
-  const int ms = ba_wave_max_i(sl);
-  if (p == 0) sh.max_slices = ms;
-#ifdef FLVIS_BA_PROF
-  // (the partition by keyframe distance: debug counters 48 + 2 d: lanes, 49 + 2 d: landmarks, d = i2 - i1 of the pair)
-  if (on && sh.prof) {
-    const unsigned tab = sh.pair_tab[p];
-    const int d = (int)((tab >> 20) & 15u) - (int)((tab >> 16) & 15u);
-    if (d < 7) {
-      atomicAdd((unsigned long long*)&sh.prof[40 + 2 * d], (unsigned long long)sl);
-      atomicAdd((unsigned long long*)&sh.prof[41 + 2 * d], (unsigned long long)sh.pair_cnt[p]);
-    }
-  }
-#endif
-}
-
 // rebuilds the observation table from the alive edges: free-pose numbering (hessian order = slot order), per-landmark
 // masks, the item numbering and the chunk table of the Schur phase
 __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
@@ -498,8 +378,6 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     sh.hidx_of[t] = -1;
     sh.slot_cnt[t] = 0;
   }
-  if (t < 64) sh.pair_cnt[t] = 0;
-  sh.role_pair[t] = 255;
   for (int i = t; i < W * Lc; i += BA_T) sc.eid[i] = -1;
   __syncthreads();
   int na = 0;
@@ -534,7 +412,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
         nfs++;
       }
     sh.fixed_slot = nfs == 1 ? fs : -1;
-    sh.fused = nfs <= 1 ? 1 : 0;  // (and one chunk, not the matrix-core variant: decided with the chunk table below)
+    sh.fused = nfs <= 1 ? 1 : 0;  // (and one chunk: decided with the chunk table below)
     const BALayout g = ba_layout(P, W, sh.n_imu > 0);
     const int NR = g.NR;
     sh.NR = NR;
@@ -553,16 +431,6 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     sh.npairs = npairs;
     sh.slices = slices;
     sh.rs = 1;
-    sh.balanced = sh.balance && P >= 2 && P + P * (P - 1) / 2 <= 64 ? 1 : 0;
-    sh.max_slices = slices;
-    // MFMA variant: the chunk is the DENSE (NR + 1 rows padded to 16) x (3 columns per landmark) slice of Z' = [Z; c^T]
-    const int NRp = (NR + 1 + 15) & ~15;
-    const int avail_m = ba_stage_avail(sh.lds_budget, sh.off_stage);
-    int CLm = (avail_m / (3 * NRp)) & ~3;  // 3 * CLm columns, a multiple of the MFMA's K = 4
-    if (CLm > 252) CLm = 252;
-    sh.NRp = NRp;
-    sh.CLm = CLm;
-    sh.nchunk_m = CLm > 0 ? (L + CLm - 1) / CLm : 0;
   }
   __syncthreads();
   for (int l = t; l < Lc; l += BA_T) {
@@ -577,26 +445,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     sc.omask[l] = m;
     sc.fmask[l] = fm;
   }
-  if (sh.balanced) {  // landmarks per pose pair (a, b), a <= b: the work of the pair's lanes in the Schur accumulate (one vote per pair and wave)
-    const int P = sh.P;
-    for (int l0 = 0; l0 < L; l0 += BA_T) {
-      const unsigned fm = l0 + t < L ? sc.fmask[l0 + t] : 0u;  // (this thread wrote it above)
-      int idx = 0;
-      for (int a = 0; a < P; a++) {
-        const int n = __popcll(__ballot((fm >> a) & 1u));
-        if (lane == 0 && n) atomicAdd(&sh.pair_cnt[a], n);
-      }
-      idx = P;
-      for (int a = 0; a < P; a++)
-        for (int b = a + 1; b < P; b++, idx++) {
-          const unsigned need = (1u << a) | (1u << b);
-          const int n = __popcll(__ballot((fm & need) == need));
-          if (lane == 0 && n) atomicAdd(&sh.pair_cnt[idx], n);
-        }
-    }
-  }
   __syncthreads();
-  if (sh.balanced && wv == 0) ba_balance_pairs();
   // item numbering: exclusive scan of popc(fmask) over the landmarks (thread = contiguous run of landmarks)
   int* lbase = reinterpret_cast<int*>(ba_dyn() + sh.off_stage);  // LDS copy of ibase for the chunk search below
   {
@@ -664,7 +513,7 @@ __device__ __noinline__ void ba_build_structure(const WindowDev& w) {
     // landmarks left over: the table is full, and a last chunk past CI / CL would run off its buffer.  nchunk = -1: the window is not
     // optimised (ba_optimize), ba_solve_dev marks and reports it.  (Unreachable at the budgets flvis_tracker_create admits: ba_lds_admits)
     sh.nchunk = l0 < L ? -1 : c;
-    if (c != 1 || sh.use_mfma) sh.fused = 0;
+    if (c != 1) sh.fused = 0;
   }
   __syncthreads();
   if (sh.fused) {
@@ -731,7 +580,7 @@ FD void ba_chol_subst() {
 // when it reached column kb, so the factor is the same bit for bit.  The one-wave form walked all finished block columns per panel with
 // seven waves waiting at the phase's barrier (12.5 us per LM trial, 20 trials per optimisation; profiles/r06_ba_phases.md); here a block
 // column costs its pivot chain, one 36-FMA update and two barriers.
-__device__ FLVIS_BA_PHASE_FN bool ba_chol_factor_wg() {
+__device__ __noinline__ bool ba_chol_factor_wg() {
   BAShared& sh = ba_sh();
   double* Hs = ba_dyn();
   double* Linv = Hs + sh.off_linv;
@@ -1040,9 +889,9 @@ FD double ba_linearize_resident(double lam) {
 
 // pose_sums == 0 (resident records only): Hpp / bp are not formed here at all -- the Schur phase sums them inside its own walk over the
 // records (ba_schur_accumulate, inl).  A function of its own: few registers, no callee-saved ones to store and reload per call.
-__device__ FLVIS_BA_PHASE_FN double ba_phase_linearize_rec(double lam) { return ba_linearize_resident<false>(lam); }
+__device__ __noinline__ double ba_phase_linearize_rec(double lam) { return ba_linearize_resident<false>(lam); }
 
-__device__ FLVIS_BA_PHASE_FN double ba_phase_linearize(double lam) {
+__device__ __noinline__ double ba_phase_linearize(double lam) {
   BAShared& sh = ba_sh();
   if (sh.fused) return ba_linearize_resident<true>(lam);
   const BAScratch sc = sh.sc;
@@ -1307,7 +1156,7 @@ FD void ba_phase_imu_trial() {
 }
 
 // largest diagonal entry of the (unreduced) hessian -> initial lambda (computeLambdaInit); this thread's share
-__device__ FLVIS_BA_PHASE_FN double ba_phase_max_diag() {
+__device__ __noinline__ double ba_phase_max_diag() {
   BAShared& sh = ba_sh();
   const BAScratch sc = sh.sc;
   const int t = threadIdx.x, L = sh.L, Lc = sc.Lc, P = sh.P;
@@ -1336,18 +1185,6 @@ struct SchurRole {
 };
 FD SchurRole ba_schur_role(int t, int P, int npairs, int slices) {
   SchurRole r{-1, -1, 0, slices};
-  if (ba_sh().balanced) {  // (ba_balance_pairs)
-    const BAShared& sh = ba_sh();
-    const int pr = sh.role_pair[t];
-    if (pr != 255) {
-      const unsigned tab = sh.pair_tab[pr];
-      r.sl = t - (int)(tab & 0xfffu);
-      r.slices = 1 << ((tab >> 12) & 15u);
-      r.i1 = (int)((tab >> 16) & 15u);
-      r.i2 = (int)((tab >> 20) & 15u);
-    }
-    return r;
-  }
   if (t < npairs * slices) {
     const int pr = t / slices, ppw = 64 / slices, dpad = ((P + ppw - 1) / ppw) * ppw;  // (diagonal pairs padded to whole waves)
     r.sl = t - pr * slices;
@@ -1459,12 +1296,6 @@ template <int CTRL>
 FD double ba_dpp(double v) {
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROWS>
-FD double ba_dpp_bcast(double v) {  // (rows outside ROWS read 0)
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWS, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, false);
   return __hiloint2double(hi, lo);
 }
 FD double ba_row16_sum_to_lane0(double v) {
@@ -1613,28 +1444,6 @@ FD void ba_schur_combine(const SchurRole& ro, double lambda, double (&acc)[36]) 
   BAShared& sh = ba_sh();
   double* Hs = ba_dyn();
   const int LD = sh.LD, slices = sh.slices;
-  if (sh.balanced) {
-    // a pair's lanes are contiguous and aligned to their (power of two) count: summed into the group's LAST lane, inside a DPP row by
-    // row shifts (a step as wide as the group or wider is switched off by a factor 0: the lane it would read belongs to another pair),
-    // across rows by the two row broadcasts -- no LDS
-    const double k4 = ro.slices >= 8 ? 1.0 : 0.0, k8 = ro.slices >= 16 ? 1.0 : 0.0, k16 = ro.slices >= 32 ? 1.0 : 0.0,
-                 k32 = ro.slices >= 64 ? 1.0 : 0.0;
-    const bool wide = sh.max_slices > 16;
-#pragma unroll
-    for (int k = 0; k < 36; k++) {
-      double v = acc[k];
-      v += ba_dpp<0x111>(v);  // row_shr:1 (lane i += lane i - 1; out-of-row sources read as 0)
-      v += ba_dpp<0x112>(v);  // row_shr:2
-      v = fma(ba_dpp<0x114>(v), k4, v);
-      v = fma(ba_dpp<0x118>(v), k8, v);
-      if (wide) {
-        v = fma(ba_dpp_bcast<0x142, 0xa>(v), k16, v);  // row_bcast:15 into rows 1 and 3
-        v = fma(ba_dpp_bcast<0x143, 0xc>(v), k32, v);  // row_bcast:31 into rows 2 and 3
-      }
-      acc[k] = v;
-    }
-    if (ro.i1 < 0 || ro.sl != ro.slices - 1) return;
-  } else {
   if (slices == 16) {
 #pragma unroll
     for (int k = 0; k < 36; k++) acc[k] = ba_row16_sum_to_lane0(acc[k]);
@@ -1645,7 +1454,6 @@ FD void ba_schur_combine(const SchurRole& ro, double lambda, double (&acc)[36]) 
     }
   }
   if (ro.i1 < 0 || ro.sl != 0) return;
-  }
   if (ro.i1 != ro.i2) {
 #pragma unroll
     for (int r = 0; r < 6; r++)
@@ -1675,7 +1483,7 @@ FD void ba_schur_combine(const SchurRole& ro, double lambda, double (&acc)[36]) 
 // butterfly order => bit-reproducible run to run, no atomics; the rhs threads sum Jp^T r likewise.
 
 // resident records, staged by the caller (ba_phase_stage) or by the linearisation: one chunk, no barrier inside
-__device__ FLVIS_BA_PHASE_FN void ba_phase_schur_resident(double lambda, int inl) {
+__device__ __noinline__ void ba_phase_schur_resident(double lambda, int inl) {
   BAShared& sh = ba_sh();
   const SchurRole ro = ba_schur_role(threadIdx.x, sh.P, sh.npairs, sh.slices);
   double acc[36];
@@ -1694,10 +1502,10 @@ __device__ FLVIS_BA_PHASE_FN void ba_phase_schur_resident(double lambda, int inl
   BAPROF(13);
 }
 // the staging of the resident chunk on its own (the first trial of an optimize() call, and a trial that follows a rejected one)
-__device__ FLVIS_BA_PHASE_FN void ba_phase_stage(double lambda) { ba_stage_chunk(0, 0, lambda); }
+__device__ __noinline__ void ba_phase_stage(double lambda) { ba_stage_chunk(0, 0, lambda); }
 
 // windows whose items do not fit one buffer: staged chunk by chunk through two buffers, one barrier per chunk
-__device__ FLVIS_BA_PHASE_FN void ba_phase_schur_chunked(double lambda) {
+__device__ __noinline__ void ba_phase_schur_chunked(double lambda) {
   BAShared& sh = ba_sh();
   const int nchunk = sh.nchunk;
   const SchurRole ro = ba_schur_role(threadIdx.x, sh.P, sh.npairs, sh.slices);
@@ -1716,154 +1524,9 @@ __device__ FLVIS_BA_PHASE_FN void ba_phase_schur_chunked(double lambda) {
   BAPROF(13);
 }
 
-// The same reduced system through the matrix cores (north_star: "an MFMA dense solve only for the reduced camera block").
-// Z' = [Z; c^T] is formed DENSE, (NR + 1) rows padded to NRp (a multiple of 16) by 3 columns per landmark, in LDS chunks of CLm
-// landmarks, k-major (Zt[column][NRp]); unobserved (landmark, pose) blocks are written as zeros.  S' = Z' Z'^T is a SYRK:
-// every 16 x 16 tile of its lower triangle is accumulated by one wave with v_mfma_f64_16x16x4_f64 over all columns (A = rows
-// of tile ti, B = rows of tile tj, both read from the same Zt).  S' holds sum Z Z^T in its leading NR x NR block and sum Z c in
-// row NR.  More arithmetic than the sparse register-tile version (zeros are multiplied too), on units that are otherwise idle.
-typedef double ba_d4 __attribute__((ext_vector_type(4)));
-__device__ __noinline__ void ba_phase_schur_mfma(double lambda) {
-  BAShared& sh = ba_sh();
-  const BAScratch sc = sh.sc;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, Lc = sc.Lc, P = sh.P, L = sh.L;
-  const int NR = sh.NR, NRp = sh.NRp, CLm = sh.CLm, LD = sh.LD;
-  double* Hs = ba_dyn();
-  double* Zt = Hs + sh.off_stage;
-  const int nt = NRp >> 4, ntiles = nt * (nt + 1) / 2;
-  // this wave's tiles (lower triangle, row-major enumeration): slot q handles tile index wv + q * BA_NW
-  constexpr int MAXQ = 3;  // 21 tiles (W = 16) over 8 waves
-  int ti[MAXQ], tj[MAXQ];
-  ba_d4 acc[MAXQ];
-#pragma unroll
-  for (int q = 0; q < MAXQ; q++) {
-    const int idx = wv + q * BA_NW;
-    ti[q] = -1;
-    tj[q] = 0;
-    if (idx < ntiles) {
-      int r = 0, rem = idx;
-      while (rem > r) {
-        rem -= r + 1;
-        r++;
-      }
-      ti[q] = r;
-      tj[q] = rem;
-    }
-    acc[q] = ba_d4{0, 0, 0, 0};
-  }
-  const int a_row = lane & 15, a_k = lane >> 4;
-  for (int c = 0; c < sh.nchunk_m; c++) {
-    const int l0 = c * CLm, nl = (L - l0 < CLm) ? L - l0 : CLm;
-    const int ncol = (3 * nl + 3) & ~3;
-    __syncthreads();  // the previous chunk's MFMAs are done with Zt
-    // stage: one (landmark, free pose) block per thread step -- Z = B G^-T or zeros; then the c row and the padding
-    for (int idx = t; idx < nl * P; idx += BA_T) {
-      const int ll = idx / P, h = idx - ll * P, l = l0 + ll;
-      const unsigned fm = sc.fmask[l];
-      double zz[18];
-      if ((fm >> h) & 1u) {  // Z = Jp^T M from the factors (see ba_phase_schur)
-        const int slot = sh.slot_of[h];
-        double rH[6], M[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) rH[k] = sc.Hll[(size_t)k * Lc + l];
-        const Chol3 g = chol3(rH, lambda);
-        const BAObs o = ba_obs(sh.RT[slot], sc.lmA[l], sc.lmA[Lc + l], sc.lmA[2 * Lc + l], sc.uv[(size_t)(2 * slot) * Lc + l],
-                               sc.uv[(size_t)(2 * slot + 1) * Lc + l], sh.K);
-        ba_item_scale(o.wJl, g, M);
-        const JpRows J = jp_rows(o.xn, o.yn, o.iz, sh.K[0], sh.K[1]);
-        const double ja[6] = {J.a0, J.a1, J.a2, J.a3, 0.0, J.a5}, jb[6] = {J.b0, J.b1, J.b2, 0.0, J.b4, J.b5};
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) zz[3 * r + j] = ja[r] * M[j] + jb[r] * M[3 + j];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 18; k++) zz[k] = 0.0;
-      }
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double* col = Zt + (size_t)(3 * ll + j) * NRp + 6 * h;
-#pragma unroll
-        for (int r = 0; r < 6; r++) col[r] = zz[3 * r + j];
-      }
-    }
-    for (int ll = t; ll < nl; ll += BA_T) {  // row NR: c = G^-1 bl; rows above it up to NRp: zero
-      const int l = l0 + ll;
-      double cv[3] = {0, 0, 0};
-      if (sc.fmask[l]) {
-        double rH2[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) rH2[k] = sc.Hll[(size_t)k * Lc + l];
-        const Chol3 g = chol3(rH2, lambda);
-        cv[0] = sc.bl[l] * g.i00;
-        cv[1] = (sc.bl[(size_t)Lc + l] - g.g10 * cv[0]) * g.i11;
-        cv[2] = (sc.bl[(size_t)2 * Lc + l] - g.g20 * cv[0] - g.g21 * cv[1]) * g.i22;
-      }
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double* col = Zt + (size_t)(3 * ll + j) * NRp;
-        col[NR] = cv[j];
-        for (int r = NR + 1; r < NRp; r++) col[r] = 0.0;
-      }
-    }
-    for (int i = t; i < (ncol - 3 * nl) * NRp; i += BA_T) Zt[(size_t)3 * nl * NRp + i] = 0.0;  // padding columns
-    __syncthreads();
-    BAPROF(2);
-    // SYRK on the matrix cores: operands of 8 k-steps are fetched from LDS before their 8 MFMAs are issued, two accumulators
-    // per tile (even / odd k-steps) keep consecutive MFMAs independent
-    const int ksteps = ncol >> 2;
-#pragma unroll
-    for (int q = 0; q < MAXQ; q++) {
-      if (ti[q] < 0) continue;
-      const double* pa = Zt + (size_t)a_k * NRp + 16 * ti[q] + a_row;
-      const double* pb = Zt + (size_t)a_k * NRp + 16 * tj[q] + a_row;
-      ba_d4 d0 = acc[q], d1 = ba_d4{0, 0, 0, 0};
-      int ks = 0;
-      for (; ks + 8 <= ksteps; ks += 8) {
-        double a[8], b[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-          a[u] = pa[(size_t)4 * (ks + u) * NRp];
-          b[u] = pb[(size_t)4 * (ks + u) * NRp];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u += 2) {
-          d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], d0, 0, 0, 0);
-          d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u + 1], b[u + 1], d1, 0, 0, 0);
-        }
-      }
-      for (; ks < ksteps; ks++) d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[(size_t)4 * ks * NRp], pb[(size_t)4 * ks * NRp], d0, 0, 0, 0);
-      acc[q] = d0 + d1;
-    }
-    BAPROF(12);
-  }
-  // S (lower triangle + full diagonal blocks) and the rhs from the accumulated tiles.  C/D layout of v_mfma_f64_16x16x4_f64:
-  // register v of lane l holds D[(l >> 4) + 4 v][l & 15] (NOT the f32 forms' 4 (l >> 4) + v)
-#pragma unroll
-  for (int q = 0; q < MAXQ; q++) {
-    if (ti[q] < 0) continue;
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int row = 16 * ti[q] + (lane >> 4) + 4 * v, col = 16 * tj[q] + (lane & 15);
-      const double a = acc[q][v];
-      if (row == NR && col < NR) {
-        sh.bfull[col] = sh.b[col];
-        sh.x[col] = sh.b[col] - a;  // bschur = bp - sum Z c
-      }
-      if (row < NR && col <= row) {
-        const bool same_block = (row / 6) == (col / 6);
-        double val = -a;
-        if (same_block) val += sh.Hpp[row / 6][6 * (col % 6) + (row % 6)] + (row == col ? lambda : 0.0);
-        Hs[row * LD + col] = val;
-        if (same_block && row != col) Hs[col * LD + row] = val;
-      }
-    }
-  }
-}
-
 // wave 0: factor + solve the reduced system, then form the trial poses x (+) pose (unchanged poses if the factorisation
 // failed) and their (R | t) tables
-__device__ FLVIS_BA_PHASE_FN void ba_phase_solve_poses(bool okc_wg) {
+__device__ __noinline__ void ba_phase_solve_poses(bool okc_wg) {
   BAShared& sh = ba_sh();
   const int lane = threadIdx.x & 63;
   const bool okc = okc_wg;
@@ -1892,7 +1555,7 @@ __device__ FLVIS_BA_PHASE_FN void ba_phase_solve_poses(bool okc_wg) {
 // are re-linearised at the accepted state (B^T dx_pose = w Jl^T (Jp dx_pose) needs no stored block), the step is solved
 // with the landmark's 3x3 factor, the trial landmark goes to lmB and its reprojection errors against the trial poses
 // are summed.  out[0] = share of the gain-ratio denominator, out[1] = share of the trial chi2.
-__device__ FLVIS_BA_PHASE_FN void ba_phase_update_chi2(double lambda, int ok2, double* out) {
+__device__ __noinline__ void ba_phase_update_chi2(double lambda, int ok2, double* out) {
   BAShared& sh = ba_sh();
   const BAScratch sc = sh.sc;
   const int t = threadIdx.x, L = sh.L, Lc = sc.Lc, W = sh.W;
@@ -1976,7 +1639,7 @@ __device__ FLVIS_BA_PHASE_FN void ba_phase_update_chi2(double lambda, int ok2, d
 // at the trial state here -- chi2, the landmark's Hll / bl (into Hll2 / bl2, swapped in on acceptance) and the record's (x/z, y/z, 1/z, w),
 // overwritten in place (the landmark's own thread has consumed them).  A rejected trial (rare: none in the benchmark's windows) leaves
 // records of a state that is not kept: the caller rebuilds them (ba_phase_linearize_rec).
-__device__ FLVIS_BA_PHASE_FN void ba_phase_update_lin(double lambda, int ok2, double* out) {
+__device__ __noinline__ void ba_phase_update_lin(double lambda, int ok2, double* out) {
   BAShared& sh = ba_sh();
   const BAScratch sc = sh.sc;
   const int t = threadIdx.x, L = sh.L, Lc = sc.Lc, CI = sh.CI, CL = sh.CL, fs = sh.fixed_slot;
@@ -2141,9 +1804,7 @@ __device__ __noinline__ void ba_optimize(const WindowDev& w, int iterations) {
     bool lambda_bad = false;
     do {
       BAPROF(0);
-      if (sh.use_mfma) {
-        ba_phase_schur_mfma(lambda);
-      } else if (sh.fused) {
+      if (sh.fused) {
         if (!staged) {
           ba_phase_stage(lambda);
         }
@@ -2266,8 +1927,6 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
     sh.sc = carve(p.ba_scratch + (size_t)s * p.ba_scratch_stride, L, E, W);
     sh.lds_budget = p.ba_lds_bytes;
     sh.W = W;
-    sh.use_mfma = p.ba_mfma;
-    sh.balance = p.ba_balance && !p.ba_mfma;
     sh.K[0] = w.K[0];  // (the window's rig: WindowDev::K)
     sh.K[1] = w.K[1];
     sh.K[2] = w.K[2];
@@ -2469,56 +2128,14 @@ __device__ __noinline__ void ba_solve_dev(const Pipe& p, int s, long long frame_
 // keyframes (one) and leaves the rest to the next launch unless ba_backlog or more are waiting.  The tracker therefore never waits
 // for the optimiser unless a stream has fallen behind by half a queue (KFQ keyframes).
 //
-// Which stream a workgroup serves (round 5).  A working workgroup takes its CU whole (512 threads at 253 registers, 159 KB of LDS), and
-// the dispatcher deals the workgroups of a launch to the eight XCDs in turn -- so with workgroup s serving stream s, the streams that
-// happen to have a keyframe decide how many CUs each XCD loses for the next 1.2 ms, while the tracker's kernels are dealt to the XCDs
-// evenly and finish with the XCD that has the fewest CUs left.  With p.ba_remap the FIRST workgroup of a launch to arrive (an arrival
-// counter per local-map HIP stream; launches on one HIP stream do not overlap) writes the list of the streams whose queue holds a
-// keyframe, publishes it under the launch's tag, and workgroup r serves the r-th stream of the list: the working workgroups are the
-// first n of the launch, n / 8 per XCD.  Every stream is still either found empty (when the list is made), found owned, or served: the
-// argument above and the back-pressure bound (pipeline.cpp) hold as before.  The others wait for the list in a sleep loop: the
-// workgroup they wait for is running by construction.  Off by default: measured, no effect on the LK launches (pipeline.cpp).
-__global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slot, unsigned launch_tag) {
+// Workgroup s serves stream s.  (Dealing the streams that have a keyframe to the first workgroups of a launch, n / 8 per XCD, had no
+// effect on the LK launches: profiles/r05_local_map_cost.md.)
+__global__ __launch_bounds__(BA_T) void k_ba_worker(Pipe p) {
   const int t = threadIdx.x;
-  __shared__ int s_go, s_pick;
+  __shared__ int s_go;
   __shared__ unsigned s_head, s_tail, s_skip;
   __shared__ int s_cnt[BA_NW];
-  if (p.ba_remap) {
-    if (t < 64) {
-      unsigned* plan = p.ba_plan + (size_t)plan_slot * (3 + p.S);
-      unsigned ticket = 0;
-      if (t == 0) {
-        ticket = atomicAdd(&plan[0], 1u);
-        // (the last arrival of a launch puts the counter back to 0 -- launches on one local-map HIP stream do not overlap -- so that it never
-        // wraps: with a grid size that is not a power of two a wrapped counter would leave a launch without a list maker)
-        if (ticket + 1u == gridDim.x) __hip_atomic_store(&plan[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      ticket = __shfl(ticket, 0);
-      if (ticket == 0) {
-        unsigned n = 0;
-        for (int j0 = 0; j0 < p.S; j0 += 64) {
-          const int j = j0 + t;
-          const bool waiting = j < p.S && __hip_atomic_load(&p.kfq_tail[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) !=
-                                              __hip_atomic_load(&p.kfq_head[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-          const unsigned long long m = __ballot(waiting);
-          if (waiting) plan[3 + n + __popcll(m & ((1ull << t) - 1ull))] = (unsigned)j;
-          n += (unsigned)__popcll(m);
-        }
-        if (t == 0) plan[2] = n;
-        __threadfence();
-        if (t == 0) __hip_atomic_store(&plan[1], launch_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (t == 0) {
-        while (__hip_atomic_load(&plan[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != launch_tag) __builtin_amdgcn_s_sleep(4);
-        const unsigned n = __hip_atomic_load(&plan[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_pick = blockIdx.x < n ? (int)__hip_atomic_load(&plan[3 + blockIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
-      }
-    }
-    __syncthreads();
-    if (s_pick < 0) return;
-  }
-  const int s = p.ba_remap ? s_pick : (int)blockIdx.x;
-#ifndef FLVIS_BA_WG_FENCES
+  const int s = (int)blockIdx.x;
   // Cache maintenance of the hand-over (round 5).  Every XCD has its own L2: an acquire at agent scope is a `buffer_inv sc1` (the XCD's L2
   // and the CU's L1 drop their lines), a release a `buffer_wbl2 sc1` (the L2 writes its dirty lines back) -- for EVERY wave that executes
   // one, and the tracker's kernels on the same XCD lose their cached pyramid rows and templates with it.  Up to round 4 the eight waves
@@ -2526,7 +2143,8 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
   // operations per keyframe, ~1200 per frame of 64 streams).  One wave is enough: thread 0 reads the queue counters with relaxed loads,
   // and only when it has taken the window does it execute ONE acquire fence; the other threads are ordered behind it by the workgroup
   // barrier (scoped happens-before is transitive), and they share its CU's L1 and its XCD's L2.  On the way out: barrier, ONE release
-  // fence by thread 0, then the head counter, then (release store) the ownership flag.  -DFLVIS_BA_WG_FENCES: the old form (A/B).
+  // fence by thread 0, then the head counter, then (release store) the ownership flag.  (The round-4 form lost:
+  // profiles/r05_local_map_cost.md.)
   while (true) {
     if (t == 0) {
       s_go = 0;
@@ -2599,81 +2217,10 @@ __global__ __launch_bounds__(BA_T) BA_ATTR void k_ba_worker(Pipe p, int plan_slo
     if (capped) return;
     // a keyframe may have arrived between the emptiness test and the release: look again
   }
-#else
-  while (true) {
-    if (t == 0) {
-      s_go = 0;
-      const unsigned tl = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned hd = __hip_atomic_load(&p.kfq_head[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-      if (tl != hd && atomicCAS(&p.ba_busy[s], 0, 1) == 0) s_go = 1;
-    }
-    __syncthreads();
-    if (!s_go) return;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    // only the owner advances the head: it is read once (after the acquire above) and then kept in a register
-    unsigned my_head = __hip_atomic_load(&p.kfq_head[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    int taken = 0;
-    bool capped = false;
-    while (true) {
-      if (t == 0) {
-        s_head = my_head;
-        s_tail = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        s_skip = __hip_atomic_load(&p.kfq_skip[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      const unsigned hd = s_head, tl = s_tail, sk = s_skip;
-      __syncthreads();
-      if (hd == tl) break;
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      const KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (hd % KFQ)];
-      const long long frame_id = kf.frame_id;
-      if ((int)(sk - hd) > 0) {  // (reset commands: as in the default form above)
-      } else if (kf.valid == KFQ_CMD_RESET) {
-        window_reset_dev(p, s);
-      } else {
-#ifdef FLVIS_BA_PROF
-      const long long tu0 = (long long)wall_clock64();
-#endif
-      ba_update_dev(p, s, kf, reinterpret_cast<long long*>(ba_dyn()), s_cnt);
-      __syncthreads();
-#ifdef FLVIS_BA_PROF
-      if (t == 0 && p.counters) {  // (counter 26 / 27: ticks in the bookkeeping of a keyframe, keyframes)
-        atomicAdd((unsigned long long*)&p.counters[26], (unsigned long long)((long long)wall_clock64() - tu0));
-        atomicAdd((unsigned long long*)&p.counters[27], 1ull);
-      }
-#endif
-      if (p.win[s].solve) ba_solve_dev(p, s, frame_id);
-      }
-      __atomic_thread_fence(__ATOMIC_RELEASE);
-      __syncthreads();
-      if (t == 0) __hip_atomic_store(&p.kfq_head[s], hd + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      my_head = hd + 1u;
-      if (p.ba_drain > 0 && ++taken >= p.ba_drain) {
-        // the next launch goes on (one follows every frame, and flvis_hip_synchronize launches until the queues are empty) -- unless
-        // the stream has fallen behind by ba_backlog keyframes: then the owner stays, so that a finished launch has left less than
-        // ba_backlog keyframes of the frames before it in every queue (what the tracker's back-pressure counts on, pipeline.cpp)
-        if (t == 0) s_tail = __hip_atomic_load(&p.kfq_tail[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const unsigned left = s_tail - my_head;
-        __syncthreads();
-        if (left < (unsigned)p.ba_backlog) {
-          capped = true;
-          break;
-        }
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __syncthreads();
-    if (t == 0) __hip_atomic_store(&p.ba_busy[s], 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (capped) return;
-    // a keyframe may have arrived between the emptiness test and the release: look again
-  }
-#endif
 }
 
-void launch_ba_worker(hipStream_t st, const Pipe& p, int plan_slot, unsigned launch_tag) {
-  hipLaunchKernelGGL(k_ba_worker, dim3(p.S), dim3(BA_T), p.ba_lds_bytes, st, p, plan_slot, launch_tag);
+void launch_ba_worker(hipStream_t st, const Pipe& p) {
+  hipLaunchKernelGGL(k_ba_worker, dim3(p.S), dim3(BA_T), p.ba_lds_bytes, st, p);
 }
 int ba_lds_budget_max() { return BA_LDS_BUDGET; }
 

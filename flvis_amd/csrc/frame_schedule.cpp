@@ -161,9 +161,9 @@ LmCloudRec flvis::lane_lmc(const Pipeline* pl, const Lane* L) {
 // the lane's launches one behind the other; the other callers wait on the host).  An owner still stays past its share at KFQ / 2
 // waiting entries, the back-pressure's last resort; that is out of reach here: a launch takes what the frames since the previous
 // launch can have queued.
-void flvis::local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int slot, int pairs, hipEvent_t prof_end) {
+void flvis::local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int pairs, hipEvent_t prof_end) {
   if (pl->lmc.cap <= 0) {
-    launch_ba_worker(bs, L->pipe, slot, ++L->ba_tag);
+    launch_ba_worker(bs, L->pipe);
     if (prof_end) hipEventRecord(prof_end, bs);
     return;
   }
@@ -171,7 +171,7 @@ void flvis::local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int slot, int 
   one.ba_drain = 1;
   const LmCloudRec r = lane_lmc(pl, L);
   for (int k = 0; k < pairs; k++) {
-    launch_ba_worker(bs, one, slot, ++L->ba_tag);
+    launch_ba_worker(bs, one);
     if (prof_end && k == 0) hipEventRecord(prof_end, bs);
     launch_lm_cloud_append(bs, one, r);
   }
@@ -194,7 +194,7 @@ void flvis::launch_local_map(Pipeline* pl, Lane* L, JoinId at, bool signal, hipE
   if (rec_on && L->ba_launches > 0) join_wait(pl, L, bs, J_BA(L->ba_launches - 1));
   if (prof_begin_end) hipEventRecord(prof_begin_end[0], bs);
   // (a reset command takes a queue entry like a keyframe, at most one per stream and frame)
-  local_map_work(pl, L, bs, bi, pl->ba_every + std::min(L->lmc_cmds, pl->ba_every), prof_begin_end ? prof_begin_end[1] : nullptr);
+  local_map_work(pl, L, bs, pl->ba_every + std::min(L->lmc_cmds, pl->ba_every), prof_begin_end ? prof_begin_end[1] : nullptr);
   L->lmc_cmds = 0;
   join_signal(pl, L, J_BA(L->ba_launches), bs);
   L->ba_launches++;
@@ -208,7 +208,6 @@ static void sync_streams(flvis_ctx* ctx) {
   for (Lane* L : pl->lanes) {
     hipStreamSynchronize(L->st);
     hipStreamSynchronize(L->det_stream);
-    if (L->tpl_stream) hipStreamSynchronize(L->tpl_stream);
   }
   for (int k = 0; k < Pipeline::NBA; k++)
     if (pl->ba_stream[k]) hipStreamSynchronize(pl->ba_stream[k]);
@@ -230,7 +229,7 @@ void flvis::sync_all(flvis_ctx* ctx) {
       bool pending = false;
       for (int i = 0; i < L->S; i++) pending = pending || hd[i] != tl[i];
       if (!pending) break;
-      local_map_work(pl, L, pl->ba_stream[0], 0, 1, nullptr);
+      local_map_work(pl, L, pl->ba_stream[0], 1, nullptr);
       hipStreamSynchronize(pl->ba_stream[0]);
     }
   }
@@ -299,7 +298,7 @@ struct Frame {
   void stage_host_inputs(const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times, const uint8_t* present);
   void stage_ingest_left(), stage_head(), stage_idle_tail(), stage_temporal_lk(), stage_collect_ransac_f(), stage_detection_fork();
   void stage_pnp_pose(), stage_new_landmarks(), stage_stereo_depth(), stage_frame_end();
-  void templates_ahead(), local_map_tail(hipEvent_t* p18, bool timed), frame_end(bool backpressure);
+  void local_map_tail(hipEvent_t* p18, bool timed), frame_end(bool backpressure);
   LKParams lk_params(int stats_at, int tc_mode, int order) const;
 };
 
@@ -389,7 +388,7 @@ void Frame::stage_host_inputs(const uint8_t* d_img0, const uint8_t* d_img1, cons
   // FLVIS_CHAIN_MERGE (round 6; bits, default 3): launches of the frame's chain folded into their neighbours -- every launch on the chain is
   // ~8 us of dispatch, ramp and drain whatever it computes.  Bit 0: k_add_new + k_depth_seeds as one launch (a barrier between them);
   // bit 1: k_track_collect as the prologue of k_ransac_f (and by sixteen waves instead of one).  0: rounds 1-5's launches.
-  merge_collect = (pl->chain_merge & 2) && !(p.tpl_ahead && pl->tpl_start == 0);
+  merge_collect = (pl->chain_merge & 2) != 0;
 }
 
 // left image -> level 0 of the slot this frame is going to use (+ the pyramid), on the detection stream BESIDE k_frame_head (the two
@@ -505,7 +504,7 @@ void Frame::stage_idle_tail() {
   if (!skipped) local_map_tail(nullptr, false);
 }
 
-// What the temporal (stats_at 36, tc_mode 2) and the stereo launch (48; tc_mode 1, or 3 with templates ahead) of k_lk_track share
+// What the temporal (stats_at 36, tc_mode 2) and the stereo launch (48, tc_mode 1) of k_lk_track share
 LKParams Frame::lk_params(int stats_at, int tc_mode, int order) const {
   LKParams prm{30, 1e-3 * 1e-3, 1e-4f, 1};
   if (pl->lk_stats) prm.stats = reinterpret_cast<unsigned long long*>(p.counters) + stats_at;  // counters[36 .. 47] / [48 .. 59]
@@ -542,26 +541,10 @@ void Frame::stage_temporal_lk() {
   pe(4, st);
 }
 
-// templates ahead of the stereo matcher (lane_create: FLVIS_TPL_AHEAD): the survivors' pixels are known when k_track_collect has run.
-// FLVIS_TPL_START (A/B knob): 1 (default) the kernel starts with the corner detection, behind the F-RANSAC, on that join's word;
-// 0 behind k_track_collect, beside the F-RANSAC, on a word of its own (one more one-lane launch on the chain)
-void Frame::templates_ahead() {
-  hipStream_t ts = L->tpl_stream;
-  join_wait(pl, L, ts, pl->tpl_start == 1 ? J_LM : J_TPL);
-  PyrSel img;
-  fill_pyr(pl, img, L->pyr0[0], L->pyr0[1], p.img_slot, 0, pl->levels_s);
-  launch_lk_templates_ahead(ts, img, p.tpl_pts, p.tpl_count, NMAX, S, L->tc, p.tc_cap, L->tc_stride, p.tpl_tag, pl->max_pts);
-  join_signal(pl, L, J_TPL, ts);
-}
-
 void Frame::stage_collect_ransac_f() {
   pb(5, st);
   if (!merge_collect) launch_track_collect(st, p);
   pe(5, st);
-  if (p.tpl_ahead && pl->tpl_start == 0) {
-    join_signal(pl, L, J_TPL, st);
-    templates_ahead();
-  }
   if (first_processed && pl->lanes.size() > 1) hipEventRecord(L->ev_stagger, st);
   pb(6, st);
   {
@@ -570,7 +553,6 @@ void Frame::stage_collect_ransac_f() {
     launch_ransac_f(st, p, merge_collect);
     pe(6, st);
   }
-  if (p.tpl_ahead && pl->tpl_start == 1) templates_ahead();
 }
 
 // fork, behind the F-RANSAC: the corner detection of the new left image (speculative for tracking frames: used only if tracking
@@ -656,8 +638,6 @@ void Frame::stage_new_landmarks() {
     pb(14, st);
     // ... and k_depth_seeds does not end before the right pyramid is there (the stereo LK follows it)
     seeds_post = j.fold_post(J_DET);
-    // ... and with templates ahead it looks them up: they must be there
-    if (p.tpl_ahead) j.wait(J_TPL);
     if (merge_seeds) launch_add_new_seeds(st, p);
     else launch_depth_seeds(st, p);
   }
@@ -680,10 +660,8 @@ void Frame::stage_stereo_depth() {
     next.pitch[0] = r_in_place ? w : pl->lpitch[0];
     next.stride[0] = r_in_place ? (size_t)w * h : pl->lstride[0];
     if (r_in_place) next.bx[0] = next.by[0] = 0;  // the caller's buffer has no border
-    // tc_mode 3: takes the templates k_lk_templates_ahead made, k_depth_seeds has looked the slots up.  order 1: the frame's new landmarks,
-    // which have no depth to start from, first (profiles/r06_chain_ab.md)
-    launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, lk_params(48, p.tpl_ahead ? 3 : 1, 1), p.det_mode,
-                    pl->max_pts, L->tc && p.tpl_ahead ? 4 : 2);
+    // order 1: the frame's new landmarks, which have no depth to start from, first (profiles/r06_chain_ab.md)
+    launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, lk_params(48, 1, 1), p.det_mode, pl->max_pts, 2);
   }
   pe(15, st);
   LaunchJoins j(pl, L, st, p.kj);
@@ -713,7 +691,7 @@ static void lane_frame(Pipeline* pl, Lane* L, const uint8_t* d_img0, const uint8
   f.stage_head();
   if (f.idle_step) return f.stage_idle_tail();
   f.stage_temporal_lk();
-  f.stage_collect_ransac_f();  // + templates ahead
+  f.stage_collect_ransac_f();
   f.stage_detection_fork();    // detection stream: gftt, FeatureDEM's image part, the right pyramid
   f.stage_pnp_pose();          // PnP RANSAC + the deferred local-map launch + pose LM + reprojection filter
   f.stage_new_landmarks();     // FeatureDEM + new landmarks + depth seeds (+ the triangulation on the detection stream)

@@ -139,10 +139,6 @@ static void lane_destroy(Lane* L) {
     hipStreamSynchronize(L->det_stream);
     hipStreamDestroy(L->det_stream);
   }
-  if (L->tpl_stream) {
-    hipStreamSynchronize(L->tpl_stream);
-    hipStreamDestroy(L->tpl_stream);
-  }
   if (L->own_st && L->st) hipStreamDestroy(L->st);
   for (Join& j : L->join)
     if (j.ev) hipEventDestroy(j.ev);
@@ -214,11 +210,6 @@ extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
   for (Lane* L : pl->lanes) lane_destroy(L);
   for (int k = 0; k < Pipeline::NBA; k++)
     if (pl->ba_stream[k]) hipStreamDestroy(pl->ba_stream[k]);
-  for (hipStream_t ps : pl->pad_streams) {
-    hipStreamSynchronize(ps);
-    hipStreamDestroy(ps);
-  }
-  pl->pad_streams.clear();
   if (pl->hf.strm) {
     hipStreamSynchronize(pl->hf.strm);
     hipStreamDestroy(pl->hf.strm);
@@ -292,10 +283,6 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   DA(lk_count, int, S);
   DA(lk_slot, int, (size_t)S * NMAX);
   DA(lk_tag, long long, S);
-  DA(tpl_pts, float, (size_t)S * NMAX * 2);
-  DA(tpl_count, int, S);
-  DA(tpl_tag, long long, S);
-  p.tpl_ahead = 0;
   DA(m1, float, (size_t)S * NMAX * 2);
   DA(m2, float, (size_t)S * NMAX * 2);
   DA(tri, double, (size_t)S * NMAX * 3);
@@ -321,7 +308,6 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   DA(kfq_base, unsigned, S);
   DA(kfq_kf, unsigned, S);
   DA(ba_busy, int, S);
-  DA(ba_plan, unsigned, (size_t)BA_PLAN_SLOTS * (3 + S));
   DA(win, WindowDev, S);
   DA(kfs_ring, KeyFrameDev, (size_t)S * BA_WMAX);
   DA(corr, CorrectionDev, S);
@@ -346,21 +332,11 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   // the full queue, where k_frame_end drops keyframes).  A launch takes at least the keyframes of the frames between two launches.
   p.ba_drain = std::max(p.ba_drain, pl->ba_every);
   p.ba_backlog = KFQ / 2;
-  // workgroup r of a local-map launch serves stream r (dealing the working workgroups to the XCDs evenly was no faster:
-  // profiles/r05_local_map_cost.md)
-  p.ba_remap = 0;
-  p.ba_mfma = pl->ba_mfma;
-  // FLVIS_BA_BALANCE=1 (opt-in, round 6): the Schur accumulate's lanes per pose pair in proportion to the landmarks the pair shares
-  // (ba_balance_pairs) instead of 16 each.  Measured (profiles/r06_ba_phases.md): the benchmark's windows share their landmarks almost
-  // evenly (155 per pose, 76-114 per pair of poses), the per-SIMD sums of the accumulate are 262-300 us either way -- the "wait for the
-  // slowest wave" of round 5 is the younger wave of each SIMD finishing behind the older one, not an imbalance -- and the partition's own
-  // cost (+27 us structure, +19 us combine per optimisation) is not paid back: off by default.
   // FLVIS_KF_CHECK=1 (test knob): k_frame_end leaves a checksum of the keyframe's landmark arrays (written by all of its waves) in the
   // payload, the local-map worker -- another workgroup, usually on another XCD -- recomputes it from what it reads after its acquire:
   // debug counters 30 (payloads checked) and 31 (mismatches).  The hand-over publishes with ONE agent-scope release by one thread behind a
   // workgroup barrier; tests/test_gpu_pipeline.py runs 64 streams under this check.
   p.kf_check = pl->kf_check;
-  p.ba_balance = pl->ba_balance;
   p.ba_lds_bytes = ba_lds_bytes_env();  // (admitted for the config's window by check_cfg)
   DA(ba_scratch, double, (size_t)S * p.ba_scratch_stride);
   // FLVIS_PNP_TAIL=cv (opt-in fidelity mode, round 6): behind k_ransac_pnp the pose of the ITERATIVE flag is replaced by what
@@ -415,19 +391,9 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   L->tc = nullptr;
   {
     const bool on = pl->lk_tcache && pl->cfg.cam_type != CAM_DEPTH && pl->levels_s == pl->levels_t;
-    // FLVIS_TPL_AHEAD=1 (round 6, opt-in A/B knob; default 0 = rounds 4-5): the templates of the landmarks the temporal tracker has followed
-    // into the frame are computed by k_lk_templates_ahead beside the frame's geometry kernels, the stereo launch takes them from the cache
-    // (lane_frame).  The signal that starts the corner detection behind the F-RANSAC starts it too.  Bit-identical results
-    // (test_templates_ahead_leave_the_same_results).  Measured (profiles/r06_templates_ahead.md): the stereo launch 0.259 -> 0.215 ms,
-    // and the kernels the template kernel runs beside pay it back -- k_ransac_pnp 0.187 -> 0.211 ms, k_gftt_pick 0.121 -> 0.157 ms
-    // (FeatureDEM then waits 25 us longer for the corners): 59.0k against 59.9k frames/s; and only with the template stream on a hardware
-    // queue of its own that does not share the main or the detection stream's pipe (two idle streams in front of it, tracker_create_impl;
-    // GPU_MAX_HW_QUEUES=8): 47.7k on the detection stream's pipe, 38.6k on the main stream's.
-    const bool ahead = pl->tpl_ahead;
+    // (Templates made ahead of the stereo launch on a stream of their own were not faster: profiles/r06_templates_ahead.md.)
     if (ok && on) {
-      // slots: the stereo launch's points (rounds 4-5) or, with templates ahead, the survivors of the temporal tracker followed by the
-      // frame's new landmarks
-      const int cap = std::min(NMAX, (pl->max_pts + 63) / 64 * 64 * (ahead ? 2 : 1));
+      const int cap = std::min(NMAX, (pl->max_pts + 63) / 64 * 64);  // slots: the stereo launch's points
       L->tc_stride = lk_tc_slot_dwords(pl->levels_t);
       const size_t n = (size_t)S * cap * L->tc_stride;
       L->tc = dalloc<uint32_t>(L->allocs, n, false);
@@ -436,7 +402,6 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
         p.tc_cap = cap;
         p.tc = L->tc;
         p.tc_stride = L->tc_stride;
-        p.tpl_ahead = ahead ? 1 : 0;
       } else {
         (void)hipGetLastError();  // no memory for it: run without
       }
@@ -490,7 +455,7 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
     if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) return false;
     L->h_progress = (volatile long long*)hp;
     L->d_progress = (long long*)dp;
-    for (int k = 0; k < 8; k++) L->h_progress[k] = 0;  // (word 0: frame progress, 1: scratch, 2: a timed-out join's sequence number,
+    for (int k = 0; k < 8; k++) L->h_progress[k] = 0;  // (word 0: frame progress, 1: unused, 2: a timed-out join's sequence number,
                                                         // 3: stream + 1 of a reset command that met a full keyframe queue,
                                                         // 4: BA_OVF_* << 32 | stream + 1 of a local-map window that exceeded a capacity)
     L->pipe.ba_ovf_word = L->d_progress + 4;
@@ -503,8 +468,7 @@ static bool lane_create(flvis_ctx* ctx, Pipeline* pl, Lane* L, int s0, int S, ui
   }
   // (the detection stream at the default priority; the lowest was measured no faster: DESIGN.md section 4)
   bool evok = hipStreamCreateWithFlags(&L->det_stream, hipStreamNonBlocking) == hipSuccess;
-  for (int id = 0; id < JOIN_IDS && evok; id++)  // (J_TPL only with templates ahead; its stream: flvis_tracker_create)
-    if (id != J_TPL || L->pipe.tpl_ahead) evok = hipEventCreateWithFlags(&L->join[id].ev, pl->ev_flags) == hipSuccess;
+  for (int id = 0; id < JOIN_IDS && evok; id++) evok = hipEventCreateWithFlags(&L->join[id].ev, pl->ev_flags) == hipSuccess;
   evok = evok && hipEventCreateWithFlags(&L->ev_stagger, pl->ev_flags) == hipSuccess;
   for (hipEvent_t& e : L->ev_end) evok = evok && hipEventCreateWithFlags(&e, pl->ev_flags) == hipSuccess;
   return evok;
@@ -588,8 +552,6 @@ static void read_knobs(Pipeline* pl) {
   }
   pl->lk_border = !env_is("FLVIS_LK_BORDER", 0);
   pl->lk_tcache = !env_is("FLVIS_LK_TCACHE", 0);
-  pl->tpl_ahead = env_is("FLVIS_TPL_AHEAD", 1);
-  pl->tpl_start = env_is("FLVIS_TPL_START", 0) ? 0 : 1;
   pl->head_prepare = !env_is("FLVIS_HEAD_PREPARE", 0);
   if (const char* e = getenv("FLVIS_HOST_LEAD")) pl->host_lead = std::max(1, std::min(atoi(e), (int)Lane::PIN_RING));
   if (const char* e = getenv("FLVIS_SYNC_EACH_FRAME")) pl->sync_each_frame = atoi(e) != 0;
@@ -598,8 +560,6 @@ static void read_knobs(Pipeline* pl) {
     const int v = atoi(e);
     if (v >= 1 && v <= KFQ / 4) pl->ba_every = v;  // (the back-pressure in lane_frame needs (D + 2) * ba_every <= KFQ / 2)
   }
-  if (const char* e = getenv("FLVIS_BA_MFMA")) pl->ba_mfma = atoi(e) != 0;
-  if (const char* e = getenv("FLVIS_BA_BALANCE")) pl->ba_balance = atoi(e) != 0;
   pl->kf_check = env_is("FLVIS_KF_CHECK", 1);
   if (const char* e = getenv("FLVIS_PNP_TAIL")) pl->pnp_tail_cv = !strcmp(e, "cv");
   if (const char* e = getenv("FLVIS_H2D_MODE")) pl->hf.mode = atoi(e) == 1 ? 1 : 2;
@@ -666,23 +626,6 @@ static int tracker_create_impl(flvis_ctx* ctx, const flvis_cfg* cfgs, int n_cfgs
   for (int k = 0; k < pl->nba && ok; k++)
     ok = hipStreamCreateWithPriority(&pl->ba_stream[k], hipStreamNonBlocking, prio_least) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&pl->ev_in, pl->ev_flags) == hipSuccess;
-  // the streams of k_lk_templates_ahead, at the lowest priority, created LAST and behind two idle streams: a fifth compute queue shares a
-  // pipe of the command processor with one of the first four (queue i sits on pipe i mod 4 in creation order, profiles/r06_h2d.md), and
-  // whichever queue that is pays for the neighbour in every dispatch -- it must not be the main stream's (profiles/r06_templates_ahead.md)
-  {
-    bool any = false;
-    for (Lane* L : pl->lanes) any = any || L->pipe.tpl_ahead;
-    for (int k = 0; k < 2 && ok && any; k++) {
-      hipStream_t ps = nullptr;
-      ok = hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, prio_least) == hipSuccess;
-      if (ok) {
-        pl->pad_streams.push_back(ps);
-        launch_store_progress(ps, pl->lanes[0]->d_progress + 1, 0);  // (a scratch word: the stream gets its hardware queue)
-      }
-    }
-    for (Lane* L : pl->lanes)
-      if (ok && L->pipe.tpl_ahead) ok = hipStreamCreateWithPriority(&L->tpl_stream, hipStreamNonBlocking, prio_least) == hipSuccess;
-  }
   if (!ok) {
     flvis_pipeline_destroy_internal(ctx);
     (void)hipGetLastError();
@@ -1592,7 +1535,7 @@ static int ba_push_impl(flvis_ctx* ctx, int stream, int64_t frame_id, const doub
   L.cmd_frame[ls] = -1;  // (a reset command queued before this keyframe is no longer the last entry)
   hipMemcpy(L.pipe.kfq_kf + ls, &tl, sizeof(unsigned), hipMemcpyHostToDevice);
   hipMemcpy(&L.pipe.corr[ls].valid, &zero, sizeof(int), hipMemcpyHostToDevice);
-  local_map_work(pl, &L, pl->ba_stream[0], 0, 1, nullptr);
+  local_map_work(pl, &L, pl->ba_stream[0], 1, nullptr);
   hipError_t e = hipStreamSynchronize(pl->ba_stream[0]);
   if (e != hipSuccess) return ctx->hip_fail(e, "ba_push_keyframe");
   sync_all(ctx);

@@ -30,7 +30,6 @@ enum JoinId {
   J_TRI,   // the two-view triangulation (detection stream)
   J_HEAD,  // k_frame_head's decisions
   J_ENDF,  // "k_frame_end has finished": the next frame's ingest and an immediate local-map launch wait for it (folded joins)
-  J_TPL,   // templates ahead (FLVIS_TPL_AHEAD): "the frame's templates are in the cache" (k_depth_seeds waits); its event exists only then
   J_BA0,
   JOIN_IDS = J_BA0 + BAQ
 };
@@ -90,9 +89,6 @@ struct Lane {
   // corner detection on its own HIP stream: goodFeaturesToTrack only needs the new image, so it runs beside the temporal
   // tracking chain (LK -> RANSACs -> pose LM) and joins before FeatureDEM consumes the corners
   hipStream_t det_stream = nullptr;
-  // templates ahead of the stereo matcher (FLVIS_TPL_AHEAD, round 6): k_lk_templates_ahead on a low-priority stream of its own, beside the
-  // one-workgroup-per-stream geometry kernels of the frame's chain
-  hipStream_t tpl_stream = nullptr;
   Join join[JOIN_IDS];
   long long* d_join = nullptr;     // [JOIN_IDS] words, 64 bytes apart (Join::word)
   unsigned* d_join_cnt = nullptr;  // [JOIN_IDS] (Join::cnt)
@@ -106,7 +102,6 @@ struct Lane {
   hipEvent_t ev_stagger = nullptr;
   long long ba_launches = 0;
   bool ba_pending = false;       // the local-map launch for the last frame's keyframes has not been enqueued yet (Pipeline::defer_ba)
-  unsigned ba_tag = 0;           // tag of the lane's last local-map launch (k_ba_worker's stream list is valid for one tag; 0 is never used)
   // reset commands in the keyframe queues (flvis_reset_streams / flvis_local_map_reset): per stream, the lane frame count when its last
   // command was appended (-1: none, or keyframes pushed behind it) -- a second request before the next frame adds no entry; and the lane
   // frame counts at which any stream of the lane had one appended, for the back-pressure (lane_backpressure_wait)
@@ -132,11 +127,9 @@ struct Pipeline {
   int n_lanes_req = 1;  // FLVIS_LANES: sub-batches of streams (1 .. 16)
   bool lk_border = true;  // FLVIS_LK_BORDER: pyramid levels with a physical border
   bool lk_tcache = true;  // FLVIS_LK_TCACHE: the LK template cache between a frame's stereo and the next frame's temporal LK
-  bool tpl_ahead = false;  // FLVIS_TPL_AHEAD: the stereo matcher's templates computed ahead, on a stream of their own
-  int tpl_start = 1;  // FLVIS_TPL_START: where k_lk_templates_ahead starts (stage_collect_ransac_f)
   int chain_merge = 3;  // FLVIS_CHAIN_MERGE: launches of the frame's chain folded into their neighbours (Frame::merge_collect)
   bool head_prepare = true;  // FLVIS_HEAD_PREPARE: k_frame_head and k_track_prepare as one launch
-  bool ba_mfma = false, ba_balance = false, kf_check = false;  // FLVIS_BA_MFMA, FLVIS_BA_BALANCE, FLVIS_KF_CHECK (Pipe fields)
+  bool kf_check = false;  // FLVIS_KF_CHECK (Pipe field)
   bool pnp_tail_cv = false;  // FLVIS_PNP_TAIL=cv
   unsigned prof_scope = 0;  // FLVIS_PROF_EVENT_SCOPE: release scope of the stage-timing events
   long long frames_fed = 0;
@@ -148,7 +141,6 @@ struct Pipeline {
   // launch per lane and frame on one of the shared local-map streams, round-robin) drains them.  Its output is never fed
   // back into the tracker in the reference (src/frontend/vo_tracking.cpp:373-385).
   static constexpr int NBA = 8;
-  static_assert(NBA == BA_PLAN_SLOTS, "one stream list per local-map HIP stream");
   int nba = 2;                   // local-map streams in use: 2 per lane (profiles/r04_local_map_and_streams_ab.md) ...
   int nba_lane = 2;              // ... of which every lane uses its own nba_lane
   int host_lead = 3;             // frames the host may run ahead of the GPU (FLVIS_HOST_LEAD, 1 .. PIN_RING; 2 until round 6: a host thread that is held up for a millisecond then leaves the GPU dry)
@@ -159,7 +151,6 @@ struct Pipeline {
   int ba_every = 1;              // launch the local-map worker every n-th frame (FLVIS_BA_EVERY)
   bool lk_stats = false;         // flvis_debug_lk_stats: the LK launches count their iterations per level into counters[36 .. 59]
   hipStream_t ba_stream[NBA] = {};
-  std::vector<hipStream_t> pad_streams;  // idle streams in front of the lanes' template streams (tracker_create_impl)
   long long ba_rr = 0;           // round-robin counter over the local-map streams
   hipEvent_t ev_in = nullptr;    // the caller's inputs are ready (recorded on the context's stream)
   bool defer_ba = false;         // inside flvis_run_steps, not its last step: the local-map launch of this frame waits for the next frame (stage_pnp_pose)
@@ -228,7 +219,7 @@ unsigned pyramid_levels(hipStream_t ds, bool bordered, ImgSel src0, int spitch0,
                         const PyrSel& pyr, int S, const int* active);
 void sync_all(flvis_ctx* ctx);
 LmCloudRec lane_lmc(const Pipeline* pl, const Lane* L);
-void local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int slot, int pairs, hipEvent_t prof_end);
+void local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int pairs, hipEvent_t prof_end);
 void launch_local_map(Pipeline* pl, Lane* L, JoinId at, bool signal, hipEvent_t* prof_begin_end);
 struct LaunchJoins;
 void lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded);

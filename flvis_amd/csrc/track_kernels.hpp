@@ -27,12 +27,6 @@ struct Pipe {
   int tc_cap;               // slots per stream of the lane's template cache (0: no cache)
   const uint32_t* tc;       // the cache itself (k_track_prepare compares the slot headers) and its slot size in dwords
   int tc_stride;
-  // templates ahead of the stereo matcher (round 6, lk_kernel.hip k_lk_templates_ahead): k_track_collect leaves the survivors' pixels, their
-  // count and the frame's id here and gives survivor j the cache slot j; k_depth_seeds looks the slots up for the stereo launch
-  int tpl_ahead;            // 0: the stereo launch computes every template itself (rounds 4-5)
-  float* tpl_pts;           // [S][NMAX][2]
-  int* tpl_count;           // [S]
-  long long* tpl_tag;       // [S]
   float* m1;                // [S][NMAX][2]  F-RANSAC inputs (ascending survivors)
   float* m2;
   double* tri;              // [S][NMAX][3]
@@ -66,9 +60,6 @@ struct Pipe {
   unsigned* kfq_kf;         // [S] entry index + 1 of the stream's last keyframe (0: none since creation or its last flvis_reset_streams): the
                             // keyframe getters read it, the last entry may be a command
   int* ba_busy;             // [S] a worker workgroup owns the stream's window
-  unsigned* ba_plan;        // [BA_PLAN_SLOTS][3 + S] per local-map HIP stream: arrival counter, tag of the launch whose list is valid, count, the streams
-                            // with a keyframe waiting (written by the first workgroup of a launch to arrive, k_ba_worker)
-  int ba_remap;             // workgroup r of a local-map launch serves the r-th stream of that list (1) or stream r (0)
   // local map
   WindowDev* win;           // [S]
   KeyFrameDev* kfs_ring;    // [S][BA_WMAX]
@@ -81,14 +72,12 @@ struct Pipe {
   int ba_lds_bytes;         // dynamic LDS of a k_ba_worker workgroup: what it leaves of a CU's 160 KB is there for the tracker's waves
   int ba_drain;             // keyframes a local-map workgroup takes from its stream's queue per launch (0: until the queue is empty) ...
   int ba_backlog;           // ... and it goes on while the queue still holds this many or more: the bound the back-pressure relies on
-  int ba_mfma;              // Schur complement of the window solver on the matrix cores (v_mfma_f64_16x16x4_f64) or as register tiles
   // FLVIS_PNP_TAIL=cv: the final solve of solvePnPRansac(ITERATIVE) as OpenCV runs it (DLT start + CvLevMarq on the inliers,
   // cv_solvers.hpp: find_extrinsic_iterative) in a kernel of its own behind k_ransac_pnp; workspace [S][pnp_tail_stride] doubles
   int pnp_tail_cv;
   double* pnp_tail_ws;
   size_t pnp_tail_stride;
   int kf_check;             // keyframe payloads carry a checksum the local-map worker verifies (FLVIS_KF_CHECK=1: stress test of the hand-over's fences)
-  int ba_balance;           // Schur accumulate: lanes per pose pair in proportion to the landmarks the pair shares (1) or 16 each (0)
   long long* counters;      // [8]: frames, keyframes, ba_runs, track_fail frames ...
   long long* ba_ovf_word;   // host-mapped: a window that exceeds a capacity stores (BA_OVF_* bits) << 32 | (lane-local stream + 1) (k_ba_worker)
   // local-map feedback (F2FTracking::correction_feed, dead in the reference's v2)
@@ -190,8 +179,7 @@ void launch_kfq_drop(hipStream_t st, const Pipe& p);
 // flvis_reset_streams_rigs: stream ls (lane-local) of the lane takes the rig r -- in stream order, ahead of its k_stream_reset
 void launch_set_rig(hipStream_t st, const Pipe& p, int ls, const RigParams& r);  // the queues emptied without a local map, a pending reset command applied
 // local map
-constexpr int BA_PLAN_SLOTS = 8;  // (= Pipeline::NBA: one list per local-map HIP stream, launches on one stream do not overlap)
-void launch_ba_worker(hipStream_t st, const Pipe& p, int plan_slot, unsigned launch_tag);
+void launch_ba_worker(hipStream_t st, const Pipe& p);
 hipError_t ba_kernels_init();
 hipError_t track_kernels_init();
 size_t ba_scratch_doubles();

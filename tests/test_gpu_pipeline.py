@@ -1067,14 +1067,10 @@ def test_local_map_imu_factor_at_window_size_16(ctx, pos_rows):
         trk.set_imu_factor_accel(0.0)
 
 
-@pytest.mark.parametrize("balance", ["0", "1"])
-def test_local_map_parity(ctx, monkeypatch, balance):
-    """The window optimiser against the oracle, keyframe by keyframe.  balance = 1: the Schur accumulate's lanes dealt to the pose pairs in
-    proportion to the landmarks they share (FLVIS_BA_BALANCE=1, opt-in; profiles/r06_ba_phases.md) -- another order of the same sums, the
-    same tolerance."""
+def test_local_map_parity(ctx):
+    """The window optimiser against the oracle, keyframe by keyframe."""
     import flvis_amd
     cfg, _ = _cfgs()
-    monkeypatch.setenv("FLVIS_BA_BALANCE", balance)
     trk = flvis_amd.Tracker(ctx, cfg, 2, seed_base=1)
     K4 = np.array([cfg.P0[0], cfg.P0[5], cfg.P0[2], cfg.P0[6]])
     for stream, seed in ((0, 11), (1, 12)):
@@ -1185,17 +1181,6 @@ def test_stream_join_forms_leave_the_same_results(ctx, monkeypatch):
     local-map launch behind k_ransac_pnp)."""
     forms = (("event", {"FLVIS_JOIN": "event"}), ("flag", {"FLVIS_JOIN_FOLD": "0"}), ("default", {}))
     _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, [3 + 7 * i for i in range(8)], "event")
-
-
-def test_templates_ahead_leave_the_same_results(ctx, monkeypatch):
-    """Round 6: the stereo matcher's templates of the landmarks the temporal tracker has followed into the frame are computed AHEAD, by
-    k_lk_templates_ahead on a stream of its own beside the frame's geometry kernels, and the stereo launch takes them from the cache
-    (FLVIS_TPL_AHEAD=1, an opt-in knob: measured, not faster -- profiles/r06_templates_ahead.md).  With them, with the kernel started behind
-    k_track_collect instead of behind the F-RANSAC (FLVIS_TPL_START=0), with event joins, and without them (the default: rounds 4-5) a
-    run must leave the same trajectories, landmarks, CorrectionInf and counters, bit for bit -- frame by frame and in batches."""
-    forms = (("off", {}), ("ahead", {"FLVIS_TPL_AHEAD": "1"}), ("start0", {"FLVIS_TPL_AHEAD": "1", "FLVIS_TPL_START": "0"}),
-             ("event", {"FLVIS_TPL_AHEAD": "1", "FLVIS_JOIN": "event"}))
-    _assert_forms_leave_the_same_results(ctx, monkeypatch, forms, [5 + 3 * i for i in range(8)], "off")
 
 
 def test_chain_merge_forms_leave_the_same_results(ctx, monkeypatch):

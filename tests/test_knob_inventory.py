@@ -14,8 +14,10 @@ RETIRED_KNOBS = [
     "FLVIS_BA_START", "FLVIS_DET_PRIO", "FLVIS_EVENT_SCOPE", "FLVIS_LANE_STAGGER", "FLVIS_BA_STREAMS", "FLVIS_BA_PRIORITY",
     "FLVIS_TPL_PRIO", "FLVIS_TPL_QPAD", "FLVIS_BA_REMAP", "FLVIS_BA_DRAIN", "FLVIS_H2D_WAIT", "FLVIS_H2D_QPAD", "FLVIS_H2D_LEAD",
     "FLVIS_H2D_CHUNK_MB", "FLVIS_PYR_PLAN", "FLVIS_PYR_BAND", "FLVIS_PYR_BAND2", "FLVIS_PYR_BAND3",
+    "FLVIS_BA_MFMA", "FLVIS_BA_BALANCE", "FLVIS_TPL_AHEAD", "FLVIS_TPL_START",
 ]
-RETIRED_BUILD_MACROS = ["FLVIS_LK_DIET", "FLVIS_LK_PREFETCH", "FLVIS_DEM_SORT_LANES", "FLVIS_BA_SOLVE_MFMA", "FLVIS_BA_CHOL_WG"]
+RETIRED_BUILD_MACROS = ["FLVIS_LK_DIET", "FLVIS_LK_PREFETCH", "FLVIS_DEM_SORT_LANES", "FLVIS_BA_SOLVE_MFMA", "FLVIS_BA_CHOL_WG",
+                        "FLVIS_BA_WG_FENCES", "FLVIS_BA_T", "FLVIS_BA_WAVES", "FLVIS_BA_PHASE_FN"]
 
 
 def _files(*dirs, ext=SOURCE_EXT):
