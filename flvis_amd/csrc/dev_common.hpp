@@ -31,13 +31,6 @@ __device__ __forceinline__ float f32_unordered(uint32_t u) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// The one-workgroup-per-stream kernels of the frame chain run beside full-chip kernels of the other stream (corner response, LK): with
-// FLVIS_CHAIN_PRIO = 1 .. 3 (build knob) their waves ask for the SIMD's issue slots first (s_setprio).  Measured in round 5 (session
-// s40: 56.9k / 56.7k frames/s at 0, 56.6k at 1, 56.5k / 56.5k at 3; every stage time unchanged to the microsecond): the chain's kernels
-// are not held up by their neighbours' instruction issue -- the default stays 0.
-#ifndef FLVIS_CHAIN_PRIO
-#define FLVIS_CHAIN_PRIO 0
-#endif
 // folded joins (KJoin, track_kernels.hpp).  kj_wait: thread 0 sleeps until the words have reached their numbers (system-scope loads: never
 // a cached line), the workgroup follows it through the barrier; gives up after ~4 s like k_wait_flag.  kj_signal: behind the workgroup's
 // last store -- barrier, one agent-scope release by thread 0, one arrival; the last arrival stores the number (release) and resets the counter.
@@ -88,10 +81,6 @@ __device__ __forceinline__ void kj_signal(const KJ& kj) {
       __hip_atomic_store(kj.sig, kj.sig_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-__device__ __forceinline__ void chain_priority() {
-  if (FLVIS_CHAIN_PRIO > 0) __builtin_amdgcn_s_setprio(FLVIS_CHAIN_PRIO);
 }
 
 // wave64 reductions over all 64 lanes (result valid in every lane)

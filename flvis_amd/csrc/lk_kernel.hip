@@ -388,9 +388,6 @@ __device__ __forceinline__ const uint8_t* lk_level_ptr(const PyrSel& P, int leve
   return I.b[I.cur ? (kc ^ I.flip) : 0] + (size_t)s * P.stride[level];
 }
 
-#ifndef FLVIS_LK_EARLY_REGION
-#define FLVIS_LK_EARLY_REGION 1  // (build-variant knob, round 6: a cached level stages its first search region beside the template loads)
-#endif
 #ifndef FLVIS_LK_WAVES
 #define FLVIS_LK_WAVES 4  // (build-variant knob: waves per SIMD the register allocation aims at)
 #endif
@@ -527,7 +524,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
       long long iA11, iA12, iA22;
       const bool cached = ROLE == 1 && tc_hit && ((tc_mask >> level) & 1u);
       // (the launches that may take templates from the cache look at the search image before the template stage: see below)
-      constexpr bool kEarlyRegion = ROLE == 1 && FLVIS_LK_EARLY_REGION;
+      constexpr bool kEarlyRegion = ROLE == 1;
       int JW = 0, JH = 0;
       const uint8_t* Jimg = nullptr;
       if (kEarlyRegion) {
@@ -594,13 +591,10 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
         const bool slow = lk_template_level(lk_level_ptr(prev, level, s, kc_prev, ind_prev0), W, H, prev.pitch[level], prev.bx[level], prev.by[level], ipx,
                                             ipy, iw00, iw01, iw10, iw11, patch, lane, tI, tX, tY, iA11, iA12, iA22);
         if (prm.stats_tc && slow && lane == 0) atomicAdd(&prm.stats_tc[1], 1ull);
-#ifndef FLVIS_LK_NO_TC_STORE  // (timing-only build variant: is the stereo launch bound by its template-cache stores?  the next frame's temporal
-                              //  launch then finds no templates; results unchanged -- profiles/r05_lk_ab.md)
         if (ROLE == 2 && tc_store) {
           lk_tc_store_level(tc_ptr, level, lane, tI, tX, tY, iA11, iA12, iA22);
           tc_mask |= 1u << level;
         }
-#endif
       }
       const float A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
       float D = A11 * A22 - A12 * A12;

@@ -10,21 +10,6 @@
 #include <vector>
 
 #include "dev_common.hpp"
-#ifdef FLVIS_RANSAC_PROF
-// sub-phase stamps of the 7-point solver (lane 0 of the hypothesis wave), counters[40..]
-#define SP_STAMP(i)                                                                                      \
-  do {                                                                                                   \
-    if (threadIdx.x == 0 && g_sp_prof) {                                                                 \
-      long long now_ = (long long)wall_clock64();                                                        \
-      atomicAdd((unsigned long long*)&g_sp_prof[i], (unsigned long long)(now_ - g_sp_last));            \
-      g_sp_last = now_;                                                                                  \
-    }                                                                                                    \
-  } while (0)
-namespace flvis {
-static __device__ long long* g_sp_prof = nullptr;
-static __device__ long long g_sp_last = 0;
-}
-#endif
 #include "dev_geom.hpp"
 #include "epnp_core.hpp"
 #include "track_kernels.hpp"
@@ -233,7 +218,6 @@ __global__ void k_frame_begin(Pipe p, const double* __restrict__ frame_time) {
 // its inputs need not arrive one global round trip at a time -- the wave copies the stream's staged samples into LDS first.
 __device__ __forceinline__ void k_frame_head_body(const Pipe& p, const double* __restrict__ frame_time, long long* __restrict__ host_progress,
                                                    long long frame_no) {
-  chain_priority();
   const int s = blockIdx.x, tid = threadIdx.x;
   // tell the host that this frame's inputs have been uploaded (this kernel follows the upload in stream order): the pinned
   // staging slot of the frame may be refilled (a store to host-mapped memory; the host polls it, see lane_frame)
@@ -384,7 +368,6 @@ __global__ __launch_bounds__(256) void k_track_prepare(Pipe p) { track_prepare_d
 // after a barrier instead of after a launch -- one dependent launch less at the head of every frame's chain
 __device__ __forceinline__ void k_frame_head_prepare_body(const Pipe& p, const double* __restrict__ frame_time, long long* __restrict__ host_progress,
                                                             long long frame_no) {
-  chain_priority();
   const int s = blockIdx.x, tid = threadIdx.x;
   if (s == 0 && tid == 0 && host_progress) __hip_atomic_store(host_progress, frame_no, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   __shared__ double s_in[IMU_MAX * 7];
@@ -483,7 +466,6 @@ __device__ __forceinline__ void track_collect_dev(const Pipe& p, int s, int* s_c
   }
 }
 __global__ __launch_bounds__(64) void k_track_collect(Pipe p) {
-  chain_priority();
   __shared__ int s_cnt[NMAX / 64 + 1];
   track_collect_dev<64>(p, blockIdx.x, s_cnt);
 }
@@ -530,10 +512,7 @@ __device__ unsigned long long g_f_rng7[F_TAB_N][F_TAB_B];
 #define RPROF2(base, i) do { } while (0)
 #endif
 
-#ifndef FLVIS_RF_T
-#define FLVIS_RF_T 1024
-#endif
-constexpr int RF_T = FLVIS_RF_T;  // (A/B knob: 256 or 512 threads leave room for the detection stream's waves on the workgroup's CU)
+constexpr int RF_T = 1024;
 // One body for the tracker's kernels (k_ransac_f / k_collect_ransac_f) and the call on caller arrays (k_fund_ransac_sets,
 // flvis_hip_find_fundamental_ransac).  What differs between them -- where the correspondences come from, threshold and confidence, where
 // the winning mask goes, OpenCV's dispatch below eight points -- is chosen by the compile-time SETS: the tracker's instantiations keep
@@ -552,7 +531,6 @@ struct FundSets {  // the arguments of k_fund_ransac_sets; unused (and empty) in
 };
 template <bool COLLECT, bool SETS>
 __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a) {
-  if (!SETS) chain_priority();
   const int s = blockIdx.x;
   StreamState* const stp = SETS ? nullptr : p.st + s;
   if (!SETS) {
@@ -580,17 +558,9 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a
   __shared__ float sm1[NMAX * 2], sm2[NMAX * 2];
   __shared__ unsigned char smask[SETS ? NMAX : 1];  // the winning mask of a caller's set
   __shared__ double Fm[64 * 3][9];
-#ifdef FLVIS_SOLVERS_PRODUCT
-  __shared__ double spw[63 * 64];  // 7-point workspaces of the 64 hypothesis lanes (element-major: conflict-free)
-#else
-  // run7Point's workspaces of the 64 hypotheses: element e of hypothesis h at spw[e * SPW_S + h].  (A/B knob FLVIS_SPW_S: 65 would keep the three lanes of a
-  // hypothesis, which work on rows 9 elements apart, out of one LDS bank -- measured: 59.5k / 59.7k against 59.8k frames/s, no gain)
-#ifndef FLVIS_SPW_S
-#define FLVIS_SPW_S 64
-#endif
-  constexpr int SPW_S = FLVIS_SPW_S;
+  // run7Point's workspaces of the 64 hypotheses: element e of hypothesis h at spw[e * SPW_S + h]
+  constexpr int SPW_S = 64;
   __shared__ double spw[cvs::SP_WORK * SPW_S];
-#endif
   __shared__ int hnm[64], mcnt[64 * 3];
   __shared__ int hcnt[64], hmodel[64];
   __shared__ int s_sub[64][8];  // the batch's subsets (7 indices each)
@@ -730,7 +700,6 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a
     __syncthreads();
     bool stop = false;
     for (int base = 0; base < niters && !stop; base += 64) {
-#ifndef FLVIS_SOLVERS_PRODUCT
       int nm = -1;
       double* const xw = spw + lane;
       if (wv == 0) {
@@ -779,72 +748,6 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a
             for (int j = 0; j < 9; j++) Fm[lane * 3 + m][j] = F[m][j];
           }
         }
-#else
-      SevenPointMid sp_mid;
-      PolyBracket sp_t;
-      double sp_roots[4];
-      int sp_nr = 0, sp_mode = -1;
-      int nm = -1;
-      double* const xw = spw + lane;
-      if (wv == 0) {
-        draw_batch(base, 64, niters, 1000, false);
-        const int iter = base + lane;
-        if (iter < niters) {
-          if (s_sub[lane][7]) {
-            double x1[7][2], x2[7][2];
-#pragma unroll
-            for (int k = 0; k < 7; k++) {
-              const int ik = s_sub[lane][k];
-              x1[k][0] = sm1[2 * ik];
-              x1[k][1] = sm1[2 * ik + 1];
-              x2[k][0] = sm2[2 * ik];
-              x2[k][1] = sm2[2 * ik + 1];
-            }
-            double cc[4];
-            nm = 0;
-            if (seven_point_a<64>(x1, x2, xw, sp_mid, cc)) sp_mode = poly_cubic_prepare(cc, sp_t, sp_roots, sp_nr);
-          } else {
-            nm = -2;
-          }
-        }
-        if (sp_mode == 1) {
-          // (one lane bisects its own intervals here: the LMedS branch is the rare low-feature case, not worth the wave hand-off)
-          bool bis[4] = {false, false, false, false};
-          double mid[4] = {0, 0, 0, 0};
-          poly_bracket_bisect(sp_t, 0, bis[0], mid[0]);
-          poly_bracket_bisect(sp_t, 1, bis[1], mid[1]);
-          poly_bracket_bisect(sp_t, 2, bis[2], mid[2]);
-          sp_nr = poly_bracket_emit(sp_t, bis, mid, sp_roots);
-        }
-        if (sp_mode >= 0) {
-          double F[3][9];
-          nm = seven_point_b(sp_mid, sp_roots, sp_nr, F);
-          for (int m = 0; m < nm; m++) {
-            // `std::sort(errf.ptr<int>(), errf.ptr<int>() + count)`: the float errors ordered through their bit patterns
-            int err[14];
-#pragma unroll
-            for (int i = 0; i < 14; i++)
-              err[i] = i < n ? __float_as_int(f_error(F[m], sm1[2 * i], sm1[2 * i + 1], sm2[2 * i], sm2[2 * i + 1])) : 0x7fffffff;
-            // (padding sorts last): odd-even transposition network on registers
-#pragma unroll
-            for (int pass = 0; pass < 14; pass++)
-#pragma unroll
-              for (int i = pass & 1; i + 1 < 14; i += 2) {
-                const int a = err[i], b = err[i + 1];
-                err[i] = a < b ? a : b;
-                err[i + 1] = a < b ? b : a;
-              }
-            float e_lo = 0.f, e_hi = 0.f, e_mid = 0.f;
-#pragma unroll
-            for (int i = 0; i < 14; i++) {
-              if (i == n / 2 - 1) e_lo = __int_as_float(err[i]);
-              if (i == n / 2) e_hi = e_mid = __int_as_float(err[i]);
-            }
-            s_med[lane * 3 + m] = (n & 1) ? (double)e_mid : ((double)(float)(e_lo + e_hi)) * 0.5;
-            for (int j = 0; j < 9; j++) Fm[lane * 3 + m][j] = F[m][j];
-          }
-        }
-#endif
         hnm[lane] = nm;
       }
       __syncthreads();
@@ -886,7 +789,6 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a
 #ifdef FLVIS_RANSAC_PROF
       if (tid == 0 && p.counters) atomicAdd((unsigned long long*)&p.counters[24 + 6], 1ull);
 #endif
-#ifndef FLVIS_SOLVERS_PRODUCT
       // hypotheses of this batch: cv::run7Point (cv_solvers.hpp).  Four lanes per hypothesis, sixteen hypotheses per wave (the first batch is
       // one wave's work): the one-sided Jacobi SVD of the 7 x 9 system lives in the hypothesis' LDS workspace and its rotations run on the
       // anti-diagonals of two overlapping sweeps, three pairs at a time (cvs::sp_slot: the bits of the cyclic order, in a third of its
@@ -954,79 +856,6 @@ __device__ __forceinline__ void k_ransac_f_body(const Pipe& p, const FundSets& a
         if (q == 0) hnm[hyp] = nm;
         RPROF2(40, 2);
       }
-#else
-      // hypotheses of this batch, one per lane of wave 0.  The bisections of the cubic's (up to three) sign-change intervals are
-      // handed to waves 0..2, one interval each (a lane's whole bracketing level inside wave 0 was a third of the generation time:
-      // a single wave is VALU-issue bound); the level travels through the per-lane workspace, which is free after the elimination
-      SevenPointMid sp_mid;
-      PolyBracket sp_t;
-      double sp_roots[4];
-      int sp_nr = 0, sp_mode = -1;  // -1: no polynomial, 0: roots final, 1: level to be bisected
-      int nm = -1;                  // -1: beyond niters, -2: subset impossible (the reference loop stops)
-      double* const xw = spw + lane;  // element e of this lane at xw[e * 64]
-      if (wv == 0) {
-        draw_batch(base, B, ctl[0], 10000, base == 0 && B == F_TAB_B && n < F_TAB_N);
-        const int iter = base + lane;
-        if (lane < B && iter < ctl[0]) {
-#ifdef FLVIS_RANSAC_PROF
-          if (tid == 0) {
-            g_sp_prof = p.counters ? p.counters + 40 : nullptr;
-            g_sp_last = (long long)wall_clock64();
-          }
-#endif
-          if (s_sub[lane][7]) {
-            double x1[7][2], x2[7][2];
-#pragma unroll
-            for (int k = 0; k < 7; k++) {
-              const int ik = s_sub[lane][k];
-              x1[k][0] = sm1[2 * ik];
-              x1[k][1] = sm1[2 * ik + 1];
-              x2[k][0] = sm2[2 * ik];
-              x2[k][1] = sm2[2 * ik + 1];
-            }
-            double cc[4];
-            nm = 0;
-            if (seven_point_a<64>(x1, x2, xw, sp_mid, cc)) sp_mode = poly_cubic_prepare(cc, sp_t, sp_roots, sp_nr);
-          } else {
-            nm = -2;
-          }
-        }
-        if (sp_mode == 1) {
-          xw[0 * 64] = sp_t.a0, xw[1 * 64] = sp_t.a1, xw[2 * 64] = sp_t.a2, xw[3 * 64] = sp_t.a3, xw[4 * 64] = sp_t.a4;
-          xw[5 * 64] = sp_t.k0, xw[6 * 64] = sp_t.k1, xw[7 * 64] = sp_t.k2, xw[8 * 64] = sp_t.k3, xw[9 * 64] = sp_t.k4;
-        }
-        xw[10 * 64] = sp_mode == 1 ? (double)sp_t.nk : 0.0;  // 0: nothing to bisect for this lane
-      }
-      __syncthreads();
-      if (wv < 3 && xw[10 * 64] != 0.0) {
-        PolyBracket t;
-        t.a0 = xw[0 * 64], t.a1 = xw[1 * 64], t.a2 = xw[2 * 64], t.a3 = xw[3 * 64], t.a4 = xw[4 * 64];
-        t.k0 = xw[5 * 64], t.k1 = xw[6 * 64], t.k2 = xw[7 * 64], t.k3 = xw[8 * 64], t.k4 = xw[9 * 64];
-        t.nk = (int)xw[10 * 64];
-        bool bis;
-        double root;
-        poly_bracket_bisect(t, wv, bis, root);
-        xw[(11 + wv) * 64] = root;
-        xw[(15 + wv) * 64] = bis ? 1.0 : 0.0;
-      }
-      __syncthreads();
-      if (wv == 0) {
-        if (sp_mode == 1) {
-          const bool bis[4] = {xw[15 * 64] != 0.0, xw[16 * 64] != 0.0, xw[17 * 64] != 0.0, false};
-          const double mid[4] = {xw[11 * 64], xw[12 * 64], xw[13 * 64], 0.0};
-          sp_nr = poly_bracket_emit(sp_t, bis, mid, sp_roots);
-        }
-        SP_STAMP(3);
-        if (sp_mode >= 0) {
-          double F[3][9];
-          nm = seven_point_b(sp_mid, sp_roots, sp_nr, F);
-          SP_STAMP(4);
-          for (int m = 0; m < nm; m++)
-            for (int j = 0; j < 9; j++) Fm[lane * 3 + m][j] = F[m][j];
-        }
-        hnm[lane] = nm;
-      }
-#endif
       __syncthreads();
       RPROF(24, 1);
       // score + replay in sub-batches of 16 hypotheses: the adaptive stop usually ends the search within the first few hypotheses
@@ -1155,8 +984,9 @@ __global__ __launch_bounds__(RF_T) void k_fund_ransac_sets(const float* __restri
 // cv::RNG((uint64)-1) in getSubset's order, serially by wave 0; PnPRansacCallback has no checkSubset.
 //   ITERATIVE  hypotheses by EPnP on the five sample points (epnp_core.hpp), one per wave, eight per batch; final solve on the inliers:
 //              Gauss-Newton on the reprojection error from the winning model (the minimum cv's Levenberg-Marquardt converges to)
-//   P3P        hypotheses by Grunert P3P on the first three sample points, the fourth picks among the <= 4 solutions (as cv::p3p does),
-//              one per lane, 16 then 64 per batch; final solve on the inliers: EPnP (solvePnPRansac hands SOLVEPNP_EPNP to solvePnP)
+//   P3P        hypotheses by Gao's P3P (cv_solvers.hpp) on the first three sample points, the fourth picks among the <= 4 solutions
+//              (as cv::p3p does), one per lane of wave 0, 16 then 64 per batch; final solve on the inliers: EPnP (solvePnPRansac hands
+//              SOLVEPNP_EPNP to solvePnP)
 // The core works on
 // correspondences staged in LDS by the caller (the tracker's kernel gathers a frame's landmarks; the standalone kernel of the loop
 // closing's geometric check loads caller arrays) and is entered by the WHOLE workgroup; only wave 0 returns with the result.
@@ -1230,11 +1060,7 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-#ifdef FLVIS_EPNP_WAVES
-    constexpr int NW = FLVIS_EPNP_WAVES;
-#else
     constexpr int NW = RP_T / 64;
-#endif
     for (int base = 0, B = iterative ? NW : 16; base < ctl[0]; base += B, B = iterative ? NW : 64) {
       if (PROF && tid == 0 && prof) atomicAdd((unsigned long long*)&prof[6], 1ull);
       if (iterative) {
@@ -1328,39 +1154,12 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
         if (lane == 0 && wv < NW) hcnt[wv] = cnt;
         __syncthreads();
       } else {
-      // hypotheses of this batch, one per lane of wave 0: P3P on the first 3 sample points, the rest disambiguate.  The bisections of
-      // the quartic's two bracketing levels (its derivative's <= 3 sign-change intervals, then its own <= 4) are handed to waves
-      // 0..3, one interval each: inside one lane they were most of the generation time (a single wave is VALU-issue bound).  The
-      // level travels through hpose[lane] (written only at the end of the generation), the results through gterms (used later).
+      // hypotheses of this batch, one per lane of wave 0: Gao's P3P on the first 3 sample points, the fourth picks among its solutions.
+      // A lane solves its whole hypothesis (the quartic in closed form) and writes the pose to hpose[lane]; the other waves wait at the
+      // barrier below and join for the scoring.
       int cnt = -1;  // -1: no model / beyond niters, -2: subset impossible, -3: model in hpose[lane], to be scored
       int idx[5];
       bool have = false;
-      P3PMid pm;
-      PolyBracket lvl;
-      double qa[5], c1[4], roots[4];
-      int nc1 = 0, nr = 0, qmode = -1;  // poly_quartic_stage1's result; -1: no polynomial for this lane
-      double* const task = hpose[lane];
-      double* const res = gterms + lane * PNP_GN_ROW;
-      auto put_task = [&](bool on) {
-        if (on) {
-          task[0] = lvl.a0, task[1] = lvl.a1, task[2] = lvl.a2, task[3] = lvl.a3, task[4] = lvl.a4;
-          task[5] = lvl.k0, task[6] = lvl.k1, task[7] = lvl.k2, task[8] = lvl.k3, task[9] = lvl.k4;
-        }
-        task[10] = on ? (double)lvl.nk : 0.0;
-      };
-      auto run_task = [&](int n_intervals) {  // waves 0 .. n_intervals-1: interval wv of lane's level
-        if (wv < n_intervals && task[10] != 0.0) {
-          PolyBracket t;
-          t.a0 = task[0], t.a1 = task[1], t.a2 = task[2], t.a3 = task[3], t.a4 = task[4];
-          t.k0 = task[5], t.k1 = task[6], t.k2 = task[7], t.k3 = task[8], t.k4 = task[9];
-          t.nk = (int)task[10];
-          bool bis;
-          double root;
-          poly_bracket_bisect(t, wv, bis, root);
-          res[wv] = root;
-          res[4 + wv] = bis ? 1.0 : 0.0;
-        }
-      };
       if (wv == 0) {
         // the batch's subsets: the first batch from the table, later ones drawn serially (wave-uniform) below the current iteration limit
         s_sub[lane][7] = 0;
@@ -1373,22 +1172,23 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
             s_sub[lane][7] = 1;
           }
           rng.state = g_pnp_rng4[np];
-        } else
-        for (int k = 0; k < B && base + k < ctl[0]; k++) {
-          int sidx[5];
-          bool ok = true;
-          if (np == modelPoints) {
+        } else {
+          for (int k = 0; k < B && base + k < ctl[0]; k++) {
+            int sidx[5];
+            bool ok = true;
+            if (np == modelPoints) {
 #pragma unroll
-            for (int j = 0; j < 5; j++) sidx[j] = j;
-          } else {
-            ok = cv_get_subset<5>(rng, mc, modelPoints, 10000, sidx, [](const int*) { return true; });
-          }
-          if (lane == 0) {
+              for (int j = 0; j < 5; j++) sidx[j] = j;
+            } else {
+              ok = cv_get_subset<5>(rng, mc, modelPoints, 10000, sidx, [](const int*) { return true; });
+            }
+            if (lane == 0) {
 #pragma unroll
-            for (int j = 0; j < 5; j++) s_sub[k][j] = sidx[j];
-            s_sub[k][7] = ok ? 1 : 0;
+              for (int j = 0; j < 5; j++) s_sub[k][j] = sidx[j];
+              s_sub[k][7] = ok ? 1 : 0;
+            }
+            if (!ok) break;
           }
-          if (!ok) break;
         }
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1398,7 +1198,6 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
 #pragma unroll
             for (int j = 0; j < 5; j++) idx[j] = s_sub[lane][j];
             have = true;
-#ifndef FLVIS_SOLVERS_PRODUCT
             // cv::solvePnP(SOLVEPNP_P3P) on the four sample points (cv_solvers.hpp): undistortPoints to normalised float coordinates,
             // mapped back with x * fx + cx by p3p::extract_points; Gao's solver on the first three, the fourth picks the pose
             const cvs::P3PCamera cam = cvs::p3p_camera(fx, fy, cx, cy);
@@ -1425,98 +1224,6 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
         hcnt[lane] = cnt;
       }
       __syncthreads();
-#else
-            V3 P[3], f[3];
-            for (int k = 0; k < 3; k++) {
-              P[k] = V3{(double)s3d[3 * idx[k]], (double)s3d[3 * idx[k] + 1], (double)s3d[3 * idx[k] + 2]};
-              V3 d{((double)s2d[2 * idx[k]] - cx) / fx, ((double)s2d[2 * idx[k] + 1] - cy) / fy, 1.0};
-              f[k] = (1.0 / norm(d)) * d;
-            }
-            double q[5];
-            qmode = p3p_grunert_a(P, f, pm, q) ? poly_quartic_stage1(q, qa, lvl, c1, nc1, roots, nr) : 0;
-          } else {
-            cnt = -2;
-          }
-        }
-        put_task(qmode == 1);
-      }
-      __syncthreads();
-      run_task(3);
-      __syncthreads();
-      if (wv == 0) {
-        if (qmode == 1) {
-          const bool bis[4] = {res[4] != 0.0, res[5] != 0.0, res[6] != 0.0, false};
-          const double mid[4] = {res[0], res[1], res[2], 0.0};
-          nc1 = poly_bracket_emit(lvl, bis, mid, c1);
-          qmode = 2;
-        }
-        if (qmode == 2) lvl = poly_quartic_stage2(qa, c1, nc1);
-        put_task(qmode == 2);
-      }
-      __syncthreads();
-      run_task(4);
-      __syncthreads();
-      if (wv == 0) {
-        if (qmode == 2) {
-          const bool bis[4] = {res[4] != 0.0, res[5] != 0.0, res[6] != 0.0, res[7] != 0.0};
-          const double mid[4] = {res[0], res[1], res[2], res[3]};
-          nr = poly_bracket_emit(lvl, bis, mid, roots);
-        }
-        if (have && qmode >= 0) {
-          V3 P[3], f[3];
-          for (int k = 0; k < 3; k++) {
-            P[k] = V3{(double)s3d[3 * idx[k]], (double)s3d[3 * idx[k] + 1], (double)s3d[3 * idx[k] + 2]};
-            V3 d{((double)s2d[2 * idx[k]] - cx) / fx, ((double)s2d[2 * idx[k] + 1] - cy) / fy, 1.0};
-            f[k] = (1.0 / norm(d)) * d;
-          }
-          // the first solution with the smallest reprojection error on the remaining sample points wins
-          int bk = -1;
-          double be = 1.7976931348623157e308;
-          M3 R;
-          V3 t;
-          V3 Pm[2];
-          double zm[2][2];
-#pragma unroll
-          for (int m = 3; m < 5; m++) {
-            const int im = m < modelPoints ? idx[m] : idx[3];
-            Pm[m - 3] = V3{(double)s3d[3 * im], (double)s3d[3 * im + 1], (double)s3d[3 * im + 2]};
-            zm[m - 3][0] = (double)s2d[2 * im];
-            zm[m - 3][1] = (double)s2d[2 * im + 1];
-          }
-          int kk = 0;
-          p3p_grunert_b(P, f, pm, roots, nr, [&](const M3& Rk, const V3& tk) {
-            double e = 0;
-#pragma unroll
-            for (int m = 3; m < 5; m++) {
-              if (m >= modelPoints) break;
-              V3 X = Rk * Pm[m - 3] + tk;
-              double z = X.z ? 1. / X.z : 1;
-              double du = fx * X.x * z + cx - zm[m - 3][0], dv = fy * X.y * z + cy - zm[m - 3][1];
-              e += du * du + dv * dv;
-            }
-            if (e < be) {
-              be = e;
-              bk = kk;
-              R = Rk;
-              t = tk;
-            }
-            kk++;
-          });
-          if (bk >= 0) {
-#pragma unroll
-            for (int r = 0; r < 3; r++)
-#pragma unroll
-              for (int c = 0; c < 3; c++) hpose[lane][3 * r + c] = R.m[r][c];
-            hpose[lane][9] = t.x;
-            hpose[lane][10] = t.y;
-            hpose[lane][11] = t.z;
-            cnt = -3;
-          }
-        }
-        hcnt[lane] = cnt;
-      }
-      __syncthreads();
-#endif
       }  // (P3P hypotheses)
       PNP_PROF(1);
       // score + replay in sub-batches of 16 hypotheses (the adaptive stop usually ends the search within the first few)
@@ -1734,7 +1441,6 @@ __device__ __forceinline__ void pnp_ransac_core(const PnpShared sh, const int np
 }
 
 __device__ __forceinline__ void k_ransac_pnp_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -2150,7 +1856,6 @@ __device__ inline void pose_lm_optimize(SE3d& T, PoseLMShared& sh, int n, int it
 }
 
 __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
-  chain_priority();
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -2318,7 +2023,6 @@ __global__ __launch_bounds__(PL_T) void k_pose_lm_sets(const double* __restrict_
 // calReprjInlierOutlier(1.5) + eraseReprjOutlier + viCorrectionFromVision; prepares the redetect inputs.
 // One workgroup of NMAX threads per stream, one landmark per thread.
 __device__ __forceinline__ void k_reproj_filter_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -2412,7 +2116,6 @@ __global__ void k_vi_correction(Pipe p) {
 // ------------------------------------------------------------------------------------------------ new landmarks
 template <int T>
 __device__ __forceinline__ void k_add_new_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -2494,7 +2197,6 @@ __device__ __forceinline__ void depth_seed_dev(const Pipe& p, int s, int i) {
   }
 }
 __device__ __forceinline__ void k_depth_seeds_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.y;
   if (p.det_mode[s] == 0) return;
   depth_seed_dev(p, s, blockIdx.x * 256 + threadIdx.x);
@@ -2519,7 +2221,6 @@ __global__ __launch_bounds__(256) void k_add_new_seeds(Pipe p) {
   kj_post_wait(p.kj);
 }
 __device__ __forceinline__ void k_depth_triangulate_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.y;
   CRig& rg = rig_of(p, s);
   const StreamState& st = p.st[s];
@@ -2561,7 +2262,6 @@ __global__ __launch_bounds__(256) void k_depth_triangulate(Pipe p) {
 // depths (quirk A11) are consumed in landmark order: failures are ranked with a workgroup prefix, thread 0 advances the
 // stream's glibc generator by the number of failures.
 __device__ __forceinline__ void k_depth_innovate_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -2672,7 +2372,6 @@ __global__ __launch_bounds__(NMAX) void k_depth_innovate(Pipe p) {
 // init_frame's success test, keyframe decision (f2f_tracking.cpp:329-354,442-452), outputs, KeyFrame payload.
 constexpr int FE_T = 256;
 __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
-  chain_priority();
   const int s = blockIdx.x;
   StreamState& st = p.st[s];
   const int lane = threadIdx.x;  // (first wave does the scalar bookkeeping)

@@ -410,8 +410,9 @@ int seven_point(const double x1[][2], const double x2[][2], double F[3][9]) {
 
 // The 7-point solver the RANSAC / LMedS loops run.  Default (round 6): OpenCV's run7Point as restated in flvis_amd/csrc/cv_solvers.hpp (SVD
 // null space of the unnormalised system, closed-form cubic, solutions in solveCubic's order, F(3,3) = 1).  -DFLVIS_SOLVERS_PRODUCT
-// (`make -C oracle SOLVERS=product` -> libflvis_ref_prod.so) keeps the product-defined solver of rounds 1-5 above buildable; the distance
-// between the two is measured on the lockstep sequences (tests/test_oracle_tracking.py, table in oracle/README.md).
+// (`make -C oracle SOLVERS=product` -> libflvis_ref_prod.so) selects the solver of rounds 1-5 above, which lives on in this checker only (the
+// kernels have one form, run7Point's) as the record of the distance between the two, asserted on the lockstep sequences
+// (tests/test_oracle_tracking.py, table in oracle/README.md).
 static int seven_point_sel(const double x1[][2], const double x2[][2], double F[3][9]) {
 #ifdef FLVIS_SOLVERS_PRODUCT
   return seven_point(x1, x2, F);

@@ -17,7 +17,9 @@ RETIRED_KNOBS = [
     "FLVIS_BA_MFMA", "FLVIS_BA_BALANCE", "FLVIS_TPL_AHEAD", "FLVIS_TPL_START",
 ]
 RETIRED_BUILD_MACROS = ["FLVIS_LK_DIET", "FLVIS_LK_PREFETCH", "FLVIS_DEM_SORT_LANES", "FLVIS_BA_SOLVE_MFMA", "FLVIS_BA_CHOL_WG",
-                        "FLVIS_BA_WG_FENCES", "FLVIS_BA_T", "FLVIS_BA_WAVES", "FLVIS_BA_PHASE_FN"]
+                        "FLVIS_BA_WG_FENCES", "FLVIS_BA_T", "FLVIS_BA_WAVES", "FLVIS_BA_PHASE_FN",
+                        "FLVIS_SOLVERS_PRODUCT", "FLVIS_SPW_S", "FLVIS_RF_T", "FLVIS_EPNP_WAVES", "FLVIS_CHAIN_PRIO",
+                        "FLVIS_LK_NO_TC_STORE", "FLVIS_LK_EARLY_REGION"]
 
 
 def _files(*dirs, ext=SOURCE_EXT):
