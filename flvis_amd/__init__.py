@@ -954,6 +954,13 @@ class FlvisImage(C.Structure):
                 ("t", C.c_double)]
 
 
+class FlvisKeyframe(C.Structure):
+    """flvis_keyframe of include/flvis_hip.h: the flvis/KeyFrame message on host arrays."""
+    _fields_ = [("frame_id", C.c_int64), ("command", C.c_int8), ("stamp", C.c_double), ("img0", FlvisImage), ("img1", FlvisImage),
+                ("lm_count", C.c_int32), ("lm_id", C.POINTER(C.c_int64)), ("lm_2d", C.POINTER(C.c_double)), ("lm_3d", C.POINTER(C.c_double)),
+                ("T_c_w", C.c_double * 7)]
+
+
 class LcParams(C.Structure):
     """flvis_lc_params of include/flvis_hip.h (LC_PARAS, vo_loopclosing.cpp:86-97)."""
     _fields_ = [("lcKFStart", C.c_int), ("lcKFDist", C.c_int), ("lcKFMaxDist", C.c_int), ("lcKFLast", C.c_int), ("lcNKFClosest", C.c_int),
@@ -1174,13 +1181,34 @@ class LoopCloser:
                          "loop_closer_add_keyframes_host")
         return ids
 
+    @staticmethod
+    def _events(ev):
+        return [dict(kf_prev=int(e.kf_prev), kf_curr=int(e.kf_curr), candidate=bool(e.candidate), n_matches=e.n_matches,
+                     n_inliers=e.n_inliers, accepted=bool(e.loop_accepted), optimised=bool(e.optimised), pgo_iterations=e.pgo_iterations,
+                     pose=[float(x) for x in e.loop_pose7], chi2_before=e.chi2_before, chi2_after=e.chi2_after) for e in ev]
+
     def process(self):
         """-> list of n_streams dicts (flvis_lc_event)"""
         ev = (LcEvent * self.n_streams)()
         self._ctx._check(self._lib.flvis_loop_closer_process(self._h, ev), "loop_closer_process")
-        return [dict(kf_prev=int(e.kf_prev), kf_curr=int(e.kf_curr), candidate=bool(e.candidate), n_matches=e.n_matches,
-                     n_inliers=e.n_inliers, accepted=bool(e.loop_accepted), optimised=bool(e.optimised), pgo_iterations=e.pgo_iterations,
-                     pose=[float(x) for x in e.loop_pose7], chi2_before=e.chi2_before, chi2_after=e.chi2_after) for e in ev]
+        return self._events(ev)
+
+    def add_logged(self, process=True, max_rounds=None):
+        """flvis_loop_closer_add_logged: every keyframe in the keyframe log of the tracker on this closer's context
+        (Tracker.keyframe_log_enable) goes into the closer on the device, in rounds (round r: entry r of every stream that has one).
+        -> the events per round, a list of `rounds` lists as process() returns them (empty lists with process=False).
+        max_rounds: rows of the event array (default: the closer's max_keyframes, which no accepted call exceeds)."""
+        cap = int(max_rounds) if max_rounds is not None else self.max_keyframes
+        S = self.n_streams
+        ev = (LcEvent * (cap * S))() if process else None
+        n = C.c_int(0)
+        fn = self._lib.flvis_loop_closer_add_logged
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        self._ctx._check(fn(self._h, int(bool(process)), C.cast(ev, C.c_void_p) if process else None, cap, C.byref(n)),
+                         "loop_closer_add_logged")
+        if not process:
+            return [[] for _ in range(n.value)]
+        return [self._events(ev[r * S:(r + 1) * S]) for r in range(n.value)]
 
     @staticmethod
     def _fixes(fix):
@@ -1822,6 +1850,73 @@ class Tracker:
         if ids:
             out = out + ([hi[g, :k[g]].copy() for g in range(n)],)
         return out
+
+    def _keyframe_msg(self, call, what, cap, images):
+        """a flvis_keyframe call on host arrays -> the message as a dict (None: no keyframe)"""
+        np = self.np
+        h, w = int(self.cfg.image_height), int(self.cfg.image_width)
+        ids, p2u, p3w = np.zeros(cap, np.int64), np.zeros((cap, 2)), np.zeros((cap, 3))
+        img0 = np.zeros((h, w), np.uint8) if images else None
+        img1 = np.zeros((h, w), np.uint16 if self.cfg.cam_type == 2 else np.uint8) if images else None
+        kf = FlvisKeyframe()
+        n = call(cap, C.byref(kf), _P(ids, C.c_int64), _P(p2u, C.c_double), _P(p3w, C.c_double),
+                 img0.ctypes.data if images else None, img1.ctypes.data if images else None)
+        if n < 0:
+            self.ctx._check(n, what)
+        if not kf.lm_id:  # (the call left the message untouched: no keyframe)
+            return None
+        n = min(n, cap)
+        return dict(frame_id=int(kf.frame_id), command=int(kf.command), stamp=float(kf.stamp), pose7=np.array(kf.T_c_w[:]),
+                    lm_id=ids[:n].copy(), lm_2d=p2u[:n].copy(), lm_3d=p3w[:n].copy(), img0=img0, img1=img1)
+
+    def keyframe_msg(self, stream, cap=2048, images=True):
+        """flvis_get_keyframe_msg: the stream's last keyframe as the flvis/KeyFrame message (call it right after the image_feed that
+        reported new_keyframe) -> dict(frame_id, command, stamp, pose7, lm_id, lm_2d, lm_3d, img0, img1), or None when the stream's last
+        frame was no keyframe.  img0 / img1: numpy [h, w] (img1 uint16 on a depth rig), None with images=False."""
+        fn = self.lib.flvis_get_keyframe_msg
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FlvisKeyframe), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                       C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        return self._keyframe_msg(lambda cap_, *a: fn(self.ctx._h, int(stream), cap_, *a), "get_keyframe_msg", cap, images)
+
+    def keyframe_log_enable(self, max_keyframes):
+        """flvis_keyframe_log_enable: keep every keyframe's whole message on the device, max_keyframes per stream (<= 0: off)."""
+        self.lib.flvis_keyframe_log_enable.argtypes = [C.c_void_p, C.c_int]
+        self.ctx._check(self.lib.flvis_keyframe_log_enable(self.ctx._h, int(max_keyframes)), "keyframe_log_enable")
+
+    def keyframe_log_clear(self, streams):
+        """flvis_keyframe_log_clear: empties the named streams' logs."""
+        self._stream_list(streams, "flvis_keyframe_log_clear")
+
+    def keyframe_log_info(self, stream):
+        """flvis_keyframe_log_info -> dict(logged, dropped, capacity) of the stream's log."""
+        v = (C.c_int64 * 3)()
+        self.lib.flvis_keyframe_log_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        self.ctx._check(self.lib.flvis_keyframe_log_info(self.ctx._h, int(stream), v), "keyframe_log_info")
+        return dict(logged=int(v[0]), dropped=int(v[1]), capacity=int(v[2]))
+
+    def keyframe_log_get(self, stream, index, cap=2048, images=True):
+        """flvis_keyframe_log_get: logged keyframe `index` of the stream, a dict like keyframe_msg's."""
+        fn = self.lib.flvis_keyframe_log_get
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FlvisKeyframe), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                       C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        return self._keyframe_msg(lambda cap_, *a: fn(self.ctx._h, int(stream), int(index), cap_, *a), "keyframe_log_get", cap, images)
+
+    def keyframe_log_images(self, stream, index):
+        """flvis_keyframe_log_images: the entry's two images as torch views of the log's device memory ([h, w] uint8; img1 int16 storage
+        on a depth rig).  Valid until the stream is cleared or reset, the log is enabled again or the tracker goes away."""
+        import torch
+        p0, p1 = C.c_void_p(0), C.c_void_p(0)
+        fn = self.lib.flvis_keyframe_log_images
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        self.ctx._check(fn(self.ctx._h, int(stream), int(index), C.byref(p0), C.byref(p1)), "keyframe_log_images")
+        h, w = int(self.cfg.image_height), int(self.cfg.image_width)
+        depth = self.cfg.cam_type == 2
+
+        def view(ptr, dtype, typestr):
+            class _Mem:  # (the CUDA array interface: a view, no copy; the log owns the memory)
+                __cuda_array_interface__ = dict(shape=(h, w), typestr=typestr, data=(int(ptr), False), version=2)
+            return torch.as_tensor(_Mem(), device=self.ctx.device)
+        return view(p0.value, torch.uint8, "|u1"), view(p1.value, torch.int16, "<i2") if depth else view(p1.value, torch.uint8, "|u1")
 
     def dropped_keyframes(self):
         """keyframes that met a full keyframe queue (flvis_get_counters_n [3]; 0 under the tracker's back-pressure)"""

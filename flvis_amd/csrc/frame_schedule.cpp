@@ -674,6 +674,9 @@ void Frame::stage_stereo_depth() {
 
 void Frame::stage_frame_end() {
   frame_end(with_local_map != 0);
+  // the keyframe log (opt-in): the streams that made a keyframe in this frame keep its message; in stream order behind k_frame_end, ahead
+  // of everything of the next step that overwrites what the kernel reads (kf_log.hip)
+  if (pl->kfl.cap > 0) kf_log_frame(pl, L, st, in1.b[0], depth_cam || r_in_place);
   local_map_tail(prof18, prof);
 }
 

@@ -42,6 +42,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "kf_log.hpp"
 #include "loop_kernels.hpp"
 
 namespace {
@@ -1406,6 +1407,82 @@ int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const 
     if (e == hipSuccess) e = e2;
   }
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_map_cloud_host");
+  return FLVIS_OK;
+}
+
+// The tracker's keyframe log (flvis_keyframe_log_enable) into the closer, without an image leaving the device.  Round r takes entry r of
+// every stream that has one: k_kf_log_gather lays their images out as add_keyframes takes them, and the round IS that call (and process).
+// Sequences are independent in the closer and a stream has at most one keyframe per step, so each sequence sees its keyframes one by one
+// in order, exactly as a caller that adds and processes after every keyframe.
+int flvis_loop_closer_add_logged(flvis_loop_closer* lc, int process, flvis_lc_event* h_events, int events_cap, int* n_rounds) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* what = "loop_closer_add_logged";
+  flvis::KfLogRec rec{};
+  int S = 0, cam = 0;
+  std::vector<long long> logged, dropped;
+  int rc = flvis::kf_log_settle(ctx, what, rec, S, cam, logged, dropped);
+  if (rc == FLVIS_ERR_INVALID_ARG)
+    return ctx->fail(rc, std::string(what) + ": the closer's context holds no tracker, or its keyframe log is off (flvis_keyframe_log_enable)");
+  if (rc != FLVIS_OK) return rc;
+  if (S != lc->S || rec.w != lc->w || rec.h != lc->h || cam != lc->cam_type)
+    return ctx->fail(FLVIS_ERR_CONFIG, std::string(what) + ": the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
+  // all or nothing: every refusal before anything is stored
+  int rounds = 0;
+  for (int s = 0; s < S; s++) {
+    if ((long long)lc->seq[s].n + logged[s] > (long long)lc->maxkf)
+      return ctx->fail(FLVIS_ERR_CAPACITY, std::string(what) + ": sequence " + std::to_string(s) + " has no room for its logged keyframes");
+    rounds = std::max(rounds, (int)logged[s]);
+  }
+  if (process && h_events && events_cap < rounds)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": events_cap is smaller than the number of rounds");
+  if (n_rounds) *n_rounds = rounds;
+  if (rounds == 0) return FLVIS_OK;
+  hipStream_t st = ctx->stream;
+  const size_t px = rec.px();
+  // the logged poses (KeyFrame.msg T_c_w: the round's T_c_w_odom), stream by stream
+  std::vector<std::vector<double>> T((size_t)S);
+  for (int s = 0; s < S; s++) {
+    if (logged[s] == 0) continue;
+    T[s].resize(7 * (size_t)logged[s]);
+    const char* src = reinterpret_cast<const char*>(rec.kf + (size_t)s * rec.cap) + offsetof(flvis::KeyFrameDev, T_c_w);
+    const hipError_t e = hipMemcpy2D(T[s].data(), 56, src, sizeof(flvis::KeyFrameDev), 56, (size_t)logged[s], hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return ctx->hip_fail(e, what);
+  }
+  // every round's stream and entry lists in one upload: [rounds][2][S]
+  std::vector<int> lists((size_t)rounds * 2 * S, -1);
+  std::vector<int> cnt((size_t)rounds, 0);
+  for (int r = 0; r < rounds; r++)
+    for (int s = 0; s < S; s++)
+      if (logged[s] > r) {
+        int* l = &lists[(size_t)r * 2 * S];
+        l[cnt[r]] = s, l[S + cnt[r]] = r;
+        cnt[r]++;
+      }
+  int* const d_lists = (int*)ctx->scratch("lc_log_lists", sizeof(int) * lists.size());
+  uint8_t* const d0 = (uint8_t*)ctx->scratch("lc_log_img0", px * (size_t)S);
+  uint8_t* const d1 = (uint8_t*)ctx->scratch("lc_log_img1", px * rec.bpp1 * (size_t)S);
+  if (!d_lists || !d0 || !d1) {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": staging allocation failed");
+  }
+  hipError_t e = hipMemcpyAsync(d_lists, lists.data(), sizeof(int) * lists.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  std::vector<double> Tr(7 * (size_t)S);
+  std::vector<flvis_lc_event> ev_tmp;
+  if (process && !h_events) ev_tmp.resize((size_t)S);
+  for (int r = 0; r < rounds; r++) {
+    const int n = cnt[r];
+    const int* l = &lists[(size_t)r * 2 * S];
+    for (int i = 0; i < n; i++) memcpy(&Tr[7 * (size_t)i], &T[l[i]][7 * (size_t)r], 56);
+    flvis::launch_kf_log_gather(st, rec, n, d_lists + (size_t)r * 2 * S, d_lists + (size_t)r * 2 * S + S, d0, d1);
+    e = hipGetLastError();
+    if (e != hipSuccess) return ctx->hip_fail(e, what);
+    rc = flvis_loop_closer_add_keyframes(lc, n, l, d0, d1, Tr.data(), nullptr);
+    if (rc == FLVIS_OK && process) rc = flvis_loop_closer_process(lc, h_events ? h_events + (size_t)r * S : ev_tmp.data());
+    if (rc != FLVIS_OK) return rc;
+  }
   return FLVIS_OK;
 }
 

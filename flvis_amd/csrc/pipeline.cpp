@@ -226,6 +226,7 @@ extern "C" void flvis_pipeline_destroy_internal(flvis_ctx* ctx) {
   if (pl->ev_in) hipEventDestroy(pl->ev_in);
   if (pl->lmc_ev) hipEventDestroy(pl->lmc_ev);
   lm_cloud_free(pl);
+  kf_log_free(pl);
   for (void* p : pl->allocs) hipFree(p);
   delete pl;
   ctx->pipe = nullptr;
@@ -1202,6 +1203,9 @@ static int reset_impl(flvis_ctx* ctx, int n, const int* streams, bool tracker, c
       for (int i = 0; i < rl.n; i++) rl.s[i] = todo[b + i].first, rl.mode[i] = todo[b + i].second;
       launch_stream_reset(L->st, L->pipe, rl, L->d_progress + 3);
     }
+    // the keyframe log of a stream that starts over is the old sequence's: emptied in order with the reset
+    if (tracker && pl->kfl.cap > 0)
+      for (const auto& e : todo) kf_log_reset_stream(pl, L, e.first);
     // the next frame's image ingest (detection stream) writes the slot k_stream_reset chose: it waits for a signal behind this launch, not
     // for the word the last k_frame_end stored
     L->endf_valid = false;

@@ -6,6 +6,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "kf_log.hpp"
 #include "lm_cloud.hpp"
 #include "track_kernels.hpp"
 
@@ -109,6 +110,7 @@ struct Lane {
   std::vector<long long> cmd_steps;
   int lmc_cmds = 0;              // reset calls that appended a command since the lane's last local-map launch (local_map_work)
   bool cmd_since_frame = false;  // a command was appended since the lane's last frame (a frame without the local map applies it: k_kfq_drop)
+  long long kfl_seq = 0;         // k_kf_log_append launches of the lane since the log was enabled: the next one's parity (kf_log.hpp)
 };
 
 struct Pipeline {
@@ -198,6 +200,8 @@ struct Pipeline {
   // orders the context's stream behind the tracker's for a fetch
   LmCloudRec lmc{};
   hipEvent_t lmc_ev = nullptr;
+  // flvis_keyframe_log_enable: the streams' keyframe logs (cap 0: off, and no k_kf_log_append is launched)
+  KfLogRec kfl{};
   Lane& lane_of(int stream, int& local) {
     const int k = stream / lane_size;
     local = stream - k * lane_size;
@@ -221,6 +225,12 @@ void sync_all(flvis_ctx* ctx);
 LmCloudRec lane_lmc(const Pipeline* pl, const Lane* L);
 void local_map_work(Pipeline* pl, Lane* L, hipStream_t bs, int pairs, hipEvent_t prof_end);
 void launch_local_map(Pipeline* pl, Lane* L, JoinId at, bool signal, hipEvent_t* prof_begin_end);
+// kf_log.hip: the lane's part of the log, its append kernel behind the lane's k_frame_end on `st`, a stream's record emptied in order
+// with its reset on the lane's tracking stream, and the log freed
+KfLogRec lane_kfl(const Pipeline* pl, const Lane* L);
+void kf_log_frame(Pipeline* pl, Lane* L, hipStream_t st, const uint8_t* in1, bool in_place);
+void kf_log_reset_stream(Pipeline* pl, Lane* L, int ls);
+void kf_log_free(Pipeline* pl);
 struct LaunchJoins;
 void lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded);
 

@@ -779,6 +779,45 @@ int flvis_local_map_cloud(flvis_ctx* ctx, int n, const int* h_stream, int mode, 
                           int* d_npts, int64_t* d_id, int64_t* h_n_out, int64_t* h_n_dropped);
 int flvis_local_map_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, int mode, double leaf, int min_points, int out_cap, float* h_xyz,
                                int* h_npts, int64_t* h_id, int64_t* h_n_out, int64_t* h_n_dropped);
+/* ---- the keyframe log (/vo_kf, KeyFrameMsg::pub, src/utils/keyframe_msg.cpp:30-124) ------------------------------------------------------
+ * flvis_get_keyframe_msg returns a stream's LAST keyframe, and its images only until the next frame overwrites them: a keyframe born
+ * inside a flvis_run_steps batch that is not its stream's last is gone when the call returns.  The log keeps, per stream and on the
+ * device, the whole flvis/KeyFrame message of a prefix of the stream's keyframes in order, each as flvis_get_keyframe_msg would have
+ * returned it right after its frame: img0 (the tracker's level 0, AFTER equalizeHist where the rig uses it, rows tightly packed), img1
+ * (mono8, or the Z16 depth image on depth rigs, tightly packed) and the payload (frame_id, stamp, T_c_w, lm_count, ids, undistorted
+ * pixels, world points).  Opt-in: with the log off no kernel is launched and nothing changes.
+ * With the log on, every lane's frame step launches one k_kf_log_append on the lane's tracking stream directly behind k_frame_end; the
+ * workgroups of a stream that made no keyframe in the step (absent under *_present included) retire at once.  No HIP stream is added.
+ * The kernel is what the log costs: 13 us on the frame chain, 1.5 % of the frame rate at 64 streams (profiles/r23_keyframe_log.md).
+ * Where the right / depth image is read in place from the caller's buffer (depth rigs; stereo rigs without equalizeHist whose rows are
+ * whole 16-byte lanes at 16-byte aligned bases), the copy reads that buffer inside the frame step: the rule on the caller's buffers
+ * that holds for the step (in stream order; flvis_set_input_hold) covers it.  Once copied the log owns the image: the LIFETIME clause
+ * of flvis_get_keyframe_msg does not apply to flvis_keyframe_log_get.
+ *
+ * flvis_keyframe_log_enable: after flvis_tracker_create(_rigs).  Room for max_keyframes messages per stream: n_streams * max_keyframes *
+ *   (width * height * (1 + bytes per pixel of img1) + 48 KB of payload) bytes.  max_keyframes <= 0 switches the log off and frees it;
+ *   enabling again, with the same capacity or another, starts empty.  Keyframes from before the call are not logged.  Waits for the
+ *   device.  FLVIS_ERR_INVALID_ARG without a tracker, FLVIS_ERR_CAPACITY if the size does not fit the index arithmetic, FLVIS_ERR_HIP if
+ *   the allocation fails (the log is then off).
+ * A keyframe that does not fit is not recorded and counted as dropped; after the first dropped one nothing more is recorded for the
+ *   stream until it is cleared (every later keyframe counts as dropped): the record stays a prefix, and capacity is the only cause of a
+ *   drop.  Nothing is ever written past a stream's record.
+ * flvis_reset_streams(_rigs) empties the record of each named stream, and of no other, in order with the reset; flvis_local_map_reset
+ *   leaves it alone.  Frames fed with with_local_map = 0 are logged as well.  Works with several lanes and flvis_set_input_hold.
+ * flvis_keyframe_log_clear: empties the named streams' records (entries and dropped count).  Waits for the device.  Errors as
+ *   flvis_local_map_cloud_clear: FLVIS_ERR_INVALID_ARG for a stream out of range, a bad list, and with the log off.
+ * flvis_keyframe_log_info: h_info3 = keyframes logged, keyframes dropped, capacity.  Waits for what is queued.
+ * flvis_keyframe_log_get: logged keyframe `index` (0 = the oldest) of the stream, arguments and result as flvis_get_keyframe_msg: returns
+ *   lm_count (>= 0), or FLVIS_ERR_INVALID_ARG for an index that is not logged.  Waits for what is queued.
+ * flvis_keyframe_log_images: device pointers to the entry's two images (tight rows; either may be NULL), valid until the stream is
+ *   cleared or reset, the log is enabled again or switched off, or the tracker is destroyed.
+ * info / get / images / clear with the log off: FLVIS_ERR_INVALID_ARG. */
+int flvis_keyframe_log_enable(flvis_ctx* ctx, int max_keyframes);
+int flvis_keyframe_log_clear(flvis_ctx* ctx, int n, const int* streams);
+int flvis_keyframe_log_info(flvis_ctx* ctx, int stream, int64_t* h_info3);
+int flvis_keyframe_log_get(flvis_ctx* ctx, int stream, int index, int cap, flvis_keyframe* kf, int64_t* h_lm_id, double* h_lm_2d,
+                           double* h_lm_3d, uint8_t* h_img0, uint8_t* h_img1);
+int flvis_keyframe_log_images(flvis_ctx* ctx, int stream, int index, const uint8_t** d_img0, const void** d_img1);
 /* Counters: [0] frames fed, [1] keyframes, [2] BA runs.  Cumulative over the context's work: a stream reset does not take them back. */
 int flvis_get_counters(flvis_ctx* ctx, int64_t* h_counters3);
 /* The first n (1 .. 4) of: [0] frames fed, [1] keyframes, [2] BA runs, [3] keyframes dropped at a full keyframe queue -- what the
@@ -942,6 +981,20 @@ int flvis_loop_closer_add_keyframes_host(flvis_loop_closer* lc, int n, const int
                                          const flvis_image* h_img1, const double* h_T_c_w_odom7, int64_t* h_kf_id);
 /* examines the newest keyframe of every sequence that got one since the last call; h_events [n_streams] */
 int flvis_loop_closer_process(flvis_loop_closer* lc, flvis_lc_event* h_events);
+/* The tracker's keyframe log (flvis_keyframe_log_enable) into the closer: every logged keyframe of every stream, no image leaving the
+ * device.  The closer's context must be the one that holds the tracker, and the tracker's n_streams, image_width, image_height and
+ * cam_type must be the closer's (FLVIS_ERR_CONFIG); with no tracker or the log off, FLVIS_ERR_INVALID_ARG.  Waits for the tracker's
+ * queued work, reads the streams' counts in one copy, and works in rounds r = 0 .. max logged - 1: the streams that have an r-th entry
+ * are round r's batch, in stream order; their images are gathered into one contiguous batch on the device and the round is exactly
+ * flvis_loop_closer_add_keyframes with the logged T_c_w as T_c_w_odom -- followed, with process != 0, by flvis_loop_closer_process,
+ * whose events are row r of h_events [events_cap][n_streams] (may be NULL).  *n_rounds (may be NULL): the number of rounds.
+ * EQUIVALENCE: sequences are independent in the closer and a stream has at most one keyframe per frame step, so every sequence ends up
+ * bit for bit as if add_keyframes / process had been called after each of its keyframes: database, similarity rows, events, poses, drift.
+ * All or nothing, checked before anything is stored: a sequence whose keyframes + logged entries exceed max_keyframes:
+ * FLVIS_ERR_CAPACITY; process with h_events and events_cap < rounds: FLVIS_ERR_INVALID_ARG.  A stream whose log dropped keyframes is NOT
+ * refused: the closer gets the logged prefix, and flvis_keyframe_log_info tells the caller.  The log is not consumed: feeding twice
+ * stores twice (flvis_keyframe_log_clear between batches).  flvis_loop_closer_set_stereo_unrect is honoured as by add_keyframes. */
+int flvis_loop_closer_add_logged(flvis_loop_closer* lc, int process, flvis_lc_event* h_events, int events_cap, int* n_rounds);
 /* kf_map_lc[i]->T_c_w of one sequence (host, [cap][7]); *n_out = keyframes in the sequence */
 int flvis_loop_closer_poses(flvis_loop_closer* lc, int stream, double* h_T_c_w7, int cap, int* n_out);
 /* one keyframe of the device-resident database on the host (KeyFrameLC, :100-112): the kept ORB landmarks (pixel, camera-frame position,

@@ -6,6 +6,7 @@
                   [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]
                    [--lc-stereo-unrect]]
                   [--local-map --lm-cloud <cloud.ply> [--lm-cloud-mode all|latest] [--leaf 0.08]]
+                  [--batch N]
 
 --imu-out : rigs with an IMU: additionally the IMU-rate trajectory of F2FTracking::imu_feed's outputs (pos_w_i, q_w_i per sample) -- the
 /imu_pose topic, which is what the reference's EuRoC launch file records as est.txt (launch/flvis_euroc_mav.launch:83-103) and scores;
@@ -35,7 +36,13 @@ output_sparse_map: True (vo_localmap.cpp:329-377): the optimised multi-view land
 estimate, the reference's cloud; latest: each landmark's newest estimate.  --leaf is shared with --map-cloud and defaults to 0.08: the
 file is then the voxel-filtered cloud; the reference's raw /map_cloud, point for point, is --lm-cloud-mode all --leaf 0.
 --lm-cloud-points: the record's capacity in points (32 bytes each; default 2^22), which the device record needs up front; a run that
-outgrows it is reported as runs_dropped in the JSON line.  When the yaml sets the key and no file is named, the JSON line says so."""
+outgrows it is reported as runs_dropped in the JSON line.  When the yaml sets the key and no file is named, the JSON line says so.
+
+--batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
+keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
+device (flvis_loop_closer_add_logged: the images the tracker worked on, img0 after equalizeHist where the rig uses it, as the KeyFrame
+message carries them) and the log is cleared.  Not with --imu-out (the IMU-rate rows are fetched per frame).  Without --batch: one
+flvis_image_feed per frame, the closer fed the caller's own images, as before."""
 import argparse
 import json
 import os
@@ -65,6 +72,7 @@ def main():
     ap.add_argument("--lm-cloud", default=None)
     ap.add_argument("--lm-cloud-mode", choices=["all", "latest"], default="all")
     ap.add_argument("--lm-cloud-points", type=int, default=1 << 22)
+    ap.add_argument("--batch", type=int, default=0)
     args = ap.parse_args()
     if args.lc_stereo_unrect and not args.loop_closing:
         ap.error("--lc-stereo-unrect needs --loop-closing")
@@ -74,6 +82,8 @@ def main():
         ap.error("--map-cloud needs --loop-closing and --backend hip")
     if args.lm_cloud and not (args.local_map and args.backend == "hip"):
         ap.error("--lm-cloud needs --local-map and --backend hip")
+    if args.batch and (args.backend != "hip" or args.imu_out or args.batch < 0):
+        ap.error("--batch N (N > 0) needs --backend hip and goes without --imu-out")
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -144,7 +154,34 @@ def main():
             closer = flvis_amd.LoopCloser(ctx, cfg, flvis_amd.load_lc_params(args.config), n_streams=1, max_keyframes=max(n, 1))
             if args.lc_stereo_unrect:
                 closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
+        if args.batch:
+            trk.keyframe_log_enable(args.batch)
+            imu_type = {1: 1, 3: 0, 5: 2, 0: 0, 2: 2, 4: 3}[cfg.type_of_vi]
+            dropped_logged, chunk = 0, []
+
+            def flush():
+                """the chunk through run_steps; its keyframes from the log into the closer; the log cleared"""
+                nonlocal dropped_logged
+                if not chunk:
+                    return
+                trk.run_steps(chunk, with_local_map=args.local_map)
+                info = trk.keyframe_log_info(0)
+                dropped_logged += info["dropped"]
+                if closer is not None:
+                    kf_stamps.extend(trk.keyframe_log_get(0, i, images=False)["stamp"] for i in range(info["logged"]))
+                    lc_events.extend(r[0] for r in closer.add_logged(process=True, max_rounds=args.batch))
+                trk.keyframe_log_clear([0])
+                del chunk[:]
         for t, i0, i1, imu in seq.frames(0, n):
+            if args.batch:
+                smp = np.zeros((1, max(len(imu), 1), 7))
+                for j, r in enumerate(imu):
+                    a, g = traj_io.sensor_to_flvis_imu(imu_type, r[4:7], r[1:4])
+                    smp[0, j] = np.concatenate([[r[0]], a, g])
+                chunk.append((torch.from_numpy(i0[None]).cuda(), torch.from_numpy(i1[None]).cuda(), [t], np.array([len(imu)], np.int32), smp))
+                if len(chunk) == args.batch:
+                    flush()
+                continue
             for r in imu:
                 trk.imu_feed_sensor(0, r[0], r[4:7], r[1:4])                   # the library applies the axis remap
             d0, d1 = torch.from_numpy(i0[None]).cuda(), torch.from_numpy(i1[None]).cuda()
@@ -155,6 +192,8 @@ def main():
                 closer.add_keyframes([0], d0, d1, [res[0]["pose7"]])
                 lc_events.append(closer.process()[0])
                 kf_stamps.append(t)
+        if args.batch:
+            flush()
         trk.write_trajectory(0, 0, n, args.out, 0)
         imu_rows = np.concatenate(imu_rows) if imu_rows else np.zeros((0, 11))
         if args.imu_out and len(imu_rows):
@@ -179,6 +218,8 @@ def main():
     out = {"backend": args.backend, "frames": len(seq) if args.frames is None else args.frames, "tracked": len(stamps)}
     if args.backend == "hip":
         import flvis_amd
+        if args.batch:
+            out["batch"] = {"steps": args.batch, "keyframes_dropped_by_the_log": dropped_logged}
         try:
             wants_cloud = flvis_amd.config_get_bool(args.config, "output_sparse_map")
         except flvis_amd.FlvisError:
