@@ -255,9 +255,11 @@ static long long lane_backpressure_depth(Pipeline* pl, Lane* L) {
 // KFQ / 2 - 1 + (D + 2) * ba_every < KFQ when k_frame_end appends: no keyframe is dropped, whatever the optimiser's pace.
 // (ba_every <= KFQ / 4, flvis_tracker_create.)  A reset command counts as a keyframe: lane_backpressure_depth.
 // The waits go into the launch `folded` carries the joins of (k_frame_end) as far as it has room, else on the tracking stream.
-void flvis::lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded) {
+// [k0, k1): which of the lane's local-map streams, newest launch first (all of them: 0, nba_lane) -- a caller may hand the older ones to
+// an earlier launch of the same frame, which waits no later than k_frame_end would (Frame::stage_new_landmarks).
+void flvis::lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded, int k0, int k1) {
   const long long D = lane_backpressure_depth(pl, L);
-  for (int k = 0; k < pl->nba_lane; k++) {
+  for (int k = k0; k < std::min(k1, pl->nba_lane); k++) {
     const long long j = L->ba_launches - 1 - D - k;
     if (j < 0 || L->ba_launches - j > BAQ) continue;
     if (folded) folded->wait(J_BA(j));
@@ -288,6 +290,9 @@ struct Frame {
   bool head_prepare;   // k_frame_head and k_track_prepare as one launch
   bool head_posts;     // the head kernel does not end before the left pyramid is there
   bool merge_collect;  // k_track_collect as the prologue of k_ransac_f
+  bool merge_end;      // k_depth_innovate and k_frame_end as one launch
+  bool merge_dem;      // k_feature_dem in the launch of k_add_new (and of k_depth_seeds where they are one)
+  bool merge_filter;   // k_reproj_filter as the epilogue of k_pose_lm
   // the begin (end = 0) / end (end = 1) event of stage i on the stream it runs on
   void mark(int i, int end, hipStream_t s) const {
     if (prof && ((pl->prof_mask >> i) & 1ull)) hipEventRecord(pev[2 * i + end], s);
@@ -298,7 +303,7 @@ struct Frame {
   void stage_host_inputs(const uint8_t* d_img0, const uint8_t* d_img1, const double* h_times, const uint8_t* present);
   void stage_ingest_left(), stage_head(), stage_idle_tail(), stage_temporal_lk(), stage_collect_ransac_f(), stage_detection_fork();
   void stage_pnp_pose(), stage_new_landmarks(), stage_stereo_depth(), stage_frame_end();
-  void local_map_tail(hipEvent_t* p18, bool timed), frame_end(bool backpressure);
+  void local_map_tail(hipEvent_t* p18, bool timed), frame_end(bool backpressure, bool with_innovate);
   LKParams lk_params(int stats_at, int tc_mode, int order) const;
 };
 
@@ -385,10 +390,17 @@ void Frame::stage_host_inputs(const uint8_t* d_img0, const uint8_t* d_img1, cons
   // the staged IMU samples and frame_begin take the temporal tracker's inputs into the same launch unless the local-map feedback has to be
   // applied in between (FLVIS_HEAD_PREPARE=0, A/B knob: two launches)
   head_prepare = pl->head_prepare && !pl->feedback_used && !idle_step;
-  // FLVIS_CHAIN_MERGE (round 6; bits, default 3): launches of the frame's chain folded into their neighbours -- every launch on the chain is
-  // ~8 us of dispatch, ramp and drain whatever it computes.  Bit 0: k_add_new + k_depth_seeds as one launch (a barrier between them);
+  // FLVIS_CHAIN_MERGE (round 6; bits, default 31): launches of the frame's chain folded into their neighbours -- every launch on the chain
+  // costs dispatch, ramp and drain whatever it computes (1-3 us between two one-workgroup-per-stream kernels, ~8 us around LK).
+  // Bit 0: k_add_new + k_depth_seeds as one launch (a barrier between them);
   // bit 1: k_track_collect as the prologue of k_ransac_f (and by sixteen waves instead of one).  0: rounds 1-5's launches.
+  // Bit 2: k_depth_innovate + k_frame_end as one launch of NMAX threads -- in a step in which every stream has a frame; an absent stream
+  // and an idle step keep the stand-alone k_frame_end.  Bit 3: k_feature_dem in front of k_add_new (+ k_depth_seeds with bit 0) in their
+  // launch.  Bit 4: k_reproj_filter as the epilogue of k_pose_lm, by its 256 threads.  (profiles/r26_chain_folds.md)
   merge_collect = (pl->chain_merge & 2) != 0;
+  merge_end = (pl->chain_merge & 4) != 0 && !idle_step && all_present;
+  merge_dem = (pl->chain_merge & 8) != 0;
+  merge_filter = (pl->chain_merge & 16) != 0;
 }
 
 // left image -> level 0 of the slot this frame is going to use (+ the pyramid), on the detection stream BESIDE k_frame_head (the two
@@ -478,13 +490,22 @@ void Frame::local_map_tail(hipEvent_t* p18, bool timed) {
 
 // k_frame_end, behind the keyframe queues' back-pressure where it may append keyframes; it stores J_ENDF's word itself where the joins
 // are folded (Lane::endf_valid)
-void Frame::frame_end(bool backpressure) {
+// with_innovate (Frame::merge_end): k_depth_innovate's work in front of it in the same launch, which then also waits for the two-view
+// triangulation; stage 16 is the launch, stage 17 reads ~0.  The older of the back-pressure waits went into an earlier launch
+// (stage_new_landmarks): the launch has two wait slots.
+void Frame::frame_end(bool backpressure, bool with_innovate) {
   LaunchJoins j(pl, L, st, p.kj);
-  if (backpressure) lane_backpressure_wait(pl, L, &j);
-  pb(17, st);
+  if (with_innovate) j.wait(J_TRI);
+  if (backpressure) lane_backpressure_wait(pl, L, &j, 0, with_innovate ? 1 : pl->nba_lane);
+  pb(with_innovate ? 16 : 17, st);
   L->endf_valid = j.fold_signal(J_ENDF);
-  launch_frame_end(st, p);
+  if (with_innovate) launch_depth_innovate_end(st, p);
+  else launch_frame_end(st, p);
   j.end();
+  if (with_innovate) {
+    pe(16, st);
+    pb(17, st);
+  }
   pe(17, st);
   pe(19, st);
 }
@@ -492,7 +513,7 @@ void Frame::frame_end(bool backpressure) {
 // the reference drops the first skip_first_n_imgs frames before any processing (vo_tracking.cpp image callback): every
 // stream is idle for this frame, so only the IMU filter, the frame counter and the per-frame outputs are advanced
 void Frame::stage_idle_tail() {
-  frame_end(false);
+  frame_end(false, false);
   if (prof)
     for (int i = 1; i < PROF_STAGES; i++)
       if (i != 17 && i != 19) {
@@ -560,8 +581,11 @@ void Frame::stage_collect_ransac_f() {
 // optimisation -- latency chains on 64 CUs that leave the rest of the chip to the detection (other placements and orders:
 // profiles/r03_stream_structure_ab.md)
 void Frame::stage_detection_fork() {
-  join_wait(pl, L, ds, J_LM);
+  // (the head kernel's word first: that wait is over long before the F-RANSAC ends, and the corner detection starts behind the F-RANSAC's
+  // word at once -- the other way round a k_wait_flag launch, ~5 us, stood between them on the frame's longer arm.  It also covers the
+  // right pyramid below: same stream, same word.  profiles/r26_chain_folds.md)
   join_wait(pl, L, ds, J_HEAD);
+  join_wait(pl, L, ds, J_LM);
   launch_gftt(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, L->gftt, nullptr, p.cam.gftt_ql, p.gftt_maxc, p.cam.gftt_num,
               (double)p.cam.gftt_dis, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num, p.gftt_act,
               (prof && ((pl->prof_mask >> 10) & 7ull) == 7ull) ? &pev[2 * 10] : nullptr, false);
@@ -572,7 +596,6 @@ void Frame::stage_detection_fork() {
     launch_feature_dem_prep(ds, l0cur, w, h, pl->lpitch[0], pl->lstride[0], S, p.cam.dem, L->gftt_xy, L->gftt_n, 2 * p.cam.gftt_num,
                             p.gftt_act, L->dem_sorted, L->dem_roff, &prep_kj);
   }
-  join_wait(pl, L, ds, J_HEAD);
   if (!depth_cam) {
     if (eq) launch_equalize_hist(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, L->eq_hist, L->eq_lut, p.act_img);
     else if (!aligned) launch_copy_image_any(ds, in1, img_plain(L->pyr1[0]), w, h, w, pl->lpitch[0], (size_t)w * h, pl->lstride[0], S, p.act_img);
@@ -597,10 +620,17 @@ void Frame::stage_pnp_pose() {
   pe(7, st);
   if (ba_here) launch_local_map(pl, L, J_FE, !pnp_signals, prof18);
   pb(8, st);
-  launch_pose_lm(st, p);  // (with k_track_post's work in its prologue)
-  pe(8, st);
-  pb(9, st);
-  {
+  if (merge_filter) {  // (stage 9 reads ~0)
+    LaunchJoins j(pl, L, st, p.kj);
+    j.signal(J_LM);
+    launch_pose_lm_filter(st, p);
+    pe(8, st);
+    pb(9, st);
+    pe(9, st);
+  } else {
+    launch_pose_lm(st, p);  // (with k_track_post's work in its prologue)
+    pe(8, st);
+    pb(9, st);
     LaunchJoins j(pl, L, st, p.kj);
     j.signal(J_LM);
     launch_reproj_filter(st, p);
@@ -612,7 +642,8 @@ void Frame::stage_pnp_pose() {
 }
 
 void Frame::stage_new_landmarks() {
-  {  // join: FeatureDEM (init: detect, tracking: redetect) consumes the corners; the right pyramid is joined before the stereo LK
+  // join: FeatureDEM (init: detect, tracking: redetect) consumes the corners; the right pyramid is joined before the stereo LK
+  if (!merge_dem) {
     KJoin dem_kj{};
     LaunchJoins j(pl, L, st, dem_kj);
     j.wait(J_GFTT);
@@ -621,16 +652,24 @@ void Frame::stage_new_landmarks() {
                        p.new_xy, p.n_new, NEW_MAX, &dem_kj);
   }
   const bool merge_seeds = (pl->chain_merge & 1) != 0;  // (k_add_new_seeds carries both launches' joins)
+  const DemLaunch dem{w, h, L->dem_sorted, L->dem_roff, 2 * p.cam.gftt_num};
   bool an_signals, seeds_post;
   {
     LaunchJoins j(pl, L, st, p.kj);
+    if (merge_dem) {  // (FeatureDEM in k_add_new's launch: the launch waits for the corners)
+      j.wait(J_GFTT);
+      pb(13, st);
+    }
+    // the merged frame end has one wait slot left behind the triangulation's: the keyframe queues' older back-pressure wait is this launch's
+    if (merge_end && with_local_map) lane_backpressure_wait(pl, L, &j, 1, pl->nba_lane);
     // k_add_new (one wave per stream) stores the word the two-view triangulation waits for: that kernel reads the landmarks as k_add_new
     // leaves them and nothing k_depth_seeds writes
     // (k_depth_seeds and k_depth_triangulate store no word themselves: 256 workgroups each -- every workgroup's release is a write-back of its
     // XCD's L2, and beside the stereo LK's template stores the kernels doubled their time: 5.9 -> 12.7 us, 87 -> 180 us)
     an_signals = j.fold_signal(J_LM);
     if (!merge_seeds) {
-      launch_add_new(st, p);
+      if (merge_dem) launch_dem_add_new_seeds(st, p, dem, false);
+      else launch_add_new(st, p);
       j.end();
     }
     pe(13, st);
@@ -638,8 +677,9 @@ void Frame::stage_new_landmarks() {
     pb(14, st);
     // ... and k_depth_seeds does not end before the right pyramid is there (the stereo LK follows it)
     seeds_post = j.fold_post(J_DET);
-    if (merge_seeds) launch_add_new_seeds(st, p);
-    else launch_depth_seeds(st, p);
+    if (!merge_seeds) launch_depth_seeds(st, p);
+    else if (merge_dem) launch_dem_add_new_seeds(st, p, dem, true);
+    else launch_add_new_seeds(st, p);
   }
   pe(14, st);
   // the two-view triangulation that k_depth_innovate consumes: on the detection stream (idle by now), under the stereo LK
@@ -664,6 +704,7 @@ void Frame::stage_stereo_depth() {
     launch_lk_track(st, prev, next, p.prev_pts, p.next_pts, p.lk_status, p.lk_count, NMAX, S, lk_params(48, 1, 1), p.det_mode, pl->max_pts, 2);
   }
   pe(15, st);
+  if (merge_end) return;  // (the depth innovation is the head of the frame's last launch: frame_end)
   LaunchJoins j(pl, L, st, p.kj);
   j.wait(J_TRI);
   pb(16, st);
@@ -673,7 +714,7 @@ void Frame::stage_stereo_depth() {
 }
 
 void Frame::stage_frame_end() {
-  frame_end(with_local_map != 0);
+  frame_end(with_local_map != 0, merge_end);
   // the keyframe log (opt-in): the streams that made a keyframe in this frame keep its message; in stream order behind k_frame_end, ahead
   // of everything of the next step that overwrites what the kernel reads (kf_log.hip)
   if (pl->kfl.cap > 0) kf_log_frame(pl, L, st, in1.b[0], depth_cam || r_in_place);

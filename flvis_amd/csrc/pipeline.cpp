@@ -556,7 +556,7 @@ static void read_knobs(Pipeline* pl) {
   pl->head_prepare = !env_is("FLVIS_HEAD_PREPARE", 0);
   if (const char* e = getenv("FLVIS_HOST_LEAD")) pl->host_lead = std::max(1, std::min(atoi(e), (int)Lane::PIN_RING));
   if (const char* e = getenv("FLVIS_SYNC_EACH_FRAME")) pl->sync_each_frame = atoi(e) != 0;
-  if (const char* e = getenv("FLVIS_CHAIN_MERGE")) pl->chain_merge = atoi(e) & 3;
+  if (const char* e = getenv("FLVIS_CHAIN_MERGE")) pl->chain_merge = atoi(e) & 31;
   if (const char* e = getenv("FLVIS_BA_EVERY")) {
     const int v = atoi(e);
     if (v >= 1 && v <= KFQ / 4) pl->ba_every = v;  // (the back-pressure in lane_frame needs (D + 2) * ba_every <= KFQ / 2)

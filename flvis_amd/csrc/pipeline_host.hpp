@@ -129,7 +129,7 @@ struct Pipeline {
   int n_lanes_req = 1;  // FLVIS_LANES: sub-batches of streams (1 .. 16)
   bool lk_border = true;  // FLVIS_LK_BORDER: pyramid levels with a physical border
   bool lk_tcache = true;  // FLVIS_LK_TCACHE: the LK template cache between a frame's stereo and the next frame's temporal LK
-  int chain_merge = 3;  // FLVIS_CHAIN_MERGE: launches of the frame's chain folded into their neighbours (Frame::merge_collect)
+  int chain_merge = 31;  // FLVIS_CHAIN_MERGE: launches of the frame's chain folded into their neighbours (Frame::merge_collect ...)
   bool head_prepare = true;  // FLVIS_HEAD_PREPARE: k_frame_head and k_track_prepare as one launch
   bool kf_check = false;  // FLVIS_KF_CHECK (Pipe field)
   bool pnp_tail_cv = false;  // FLVIS_PNP_TAIL=cv
@@ -232,6 +232,6 @@ void kf_log_frame(Pipeline* pl, Lane* L, hipStream_t st, const uint8_t* in1, boo
 void kf_log_reset_stream(Pipeline* pl, Lane* L, int ls);
 void kf_log_free(Pipeline* pl);
 struct LaunchJoins;
-void lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded);
+void lane_backpressure_wait(Pipeline* pl, Lane* L, LaunchJoins* folded, int k0 = 0, int k1 = 1 << 30);
 
 }  // namespace flvis

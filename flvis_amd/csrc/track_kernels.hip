@@ -12,6 +12,7 @@
 #include "dev_common.hpp"
 #include "dev_geom.hpp"
 #include "epnp_core.hpp"
+#include "feature_dem_dev.hpp"
 #include "track_kernels.hpp"
 #include "cv_solvers.hpp"
 #include "vi_motion.hpp"
@@ -1855,7 +1856,8 @@ __device__ inline void pose_lm_optimize(SE3d& T, PoseLMShared& sh, int n, int it
   }
 }
 
-__global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
+// (a body: its early exits are uniform per workgroup and leave the function, not the kernel -- k_pose_lm_filter goes on behind it)
+__device__ __forceinline__ void k_pose_lm_body(const Pipe& p) {
   const int s = blockIdx.x;
   CRig& rg = rig_of(p, s);
   StreamState& st = p.st[s];
@@ -1953,6 +1955,7 @@ __global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) {
   if (tid == 0 && p.counters) atomicAdd((unsigned long long*)&p.counters[48 + 7], 1ull);
 #endif
 }
+__global__ __launch_bounds__(PL_T) void k_pose_lm(Pipe p) { k_pose_lm_body(p); }
 
 // OptimizeInFrame::optimize on caller arrays (flvis_hip_optimize_in_frame), one workgroup per set: the arrays getValidInliersPair hands
 // the reference -- lm3d [n_sets][cap][3] world points, lm2d [n_sets][cap][2] undistorted pixels, lm_id [n_sets][cap] -- and pose7
@@ -2098,6 +2101,103 @@ __global__ __launch_bounds__(NMAX) void k_reproj_filter(Pipe p) {
   k_reproj_filter_body(p);
   kj_signal(p.kj);
 }
+// k_reproj_filter_body by a workgroup of T < NMAX threads, T landmarks at a time (the epilogue of k_pose_lm_filter): the same distances,
+// the same list of valid ones in index order, hence the same sequential mean and median; the erase chunk by chunk in index order -- a
+// chunk's landmarks are read in front of block_rank's barriers and go to positions at or below their own behind them, which no later
+// chunk reads.  valid: [NMAX] doubles in LDS.
+template <int T>
+__device__ __forceinline__ void reproj_filter_chunks_dev(const Pipe& p, double* valid) {
+  const int s = blockIdx.x;
+  CRig& rg = rig_of(p, s);
+  StreamState& st = p.st[s];
+  if (st.phase != PH_TRACK) return;
+  constexpr int NC = NMAX / T;
+  const int tid = threadIdx.x;
+  const int cur = st.cur;
+  Landmark* lms = lm_ptr(p, cur, s);
+  const int n = st.n_lm[cur];
+  __shared__ double sh_thr;
+  __shared__ int s_cnt[T / 64];
+  const SE3d Tcw = load_pose7(st.T_c_w[cur]);
+  double d[NC];
+  int nv = 0;
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    d[c] = 0;
+    if (c * T >= n) continue;  // (uniform)
+    const int i = c * T + tid;
+    bool v = false;
+    if (i < n) {
+      const Landmark& lm = lms[i];
+      V3 pc = se3_act(Tcw, V3{lm.p3w[0], lm.p3w[1], lm.p3w[2]});
+      double u = rg.fx * pc.x / pc.z + rg.cx, vv = rg.fy * pc.y / pc.z + rg.cy;
+      double ex = lm.p2u[0] - u, ey = lm.p2u[1] - vv;
+      d[c] = sqrt(ex * ex + ey * ey);
+      v = d[c] < 3.0;
+    }
+    int tot;
+    const int vr = block_rank<T / 64>(v, s_cnt, tot);
+    if (v) valid[nv + vr] = d[c];
+    nv += tot;
+  }
+  if (tid == 0 && nv == 0) sh_thr = 3.0;
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0;
+    for (int k = 0; k < nv; k++) sum += valid[k];
+    st.reproj_err = sum / (double)nv;
+  }
+  for (int i = tid; i < nv; i += T) {
+    const int target = nv / 2;
+    const double vi = valid[i];
+    int less = 0, eq = 0;
+    for (int j = 0; j < nv; j++) {
+      const double vj = valid[j];
+      less += vj < vi;
+      eq += vj == vi;
+    }
+    if (less <= target && target < less + eq) sh_thr = 1.5 * vi;
+  }
+  __syncthreads();
+  double sh = sh_thr;
+  if (sh >= 3.0) sh = 3.0;
+  int kept = 0;
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    if (c * T >= n) continue;
+    const int i = c * T + tid;
+    const bool keep = i < n && !(d[c] > sh);
+    Landmark lm;
+    if (keep) lm = lms[i];
+    int tot;
+    const int k = kept + block_rank<T / 64>(keep, s_cnt, tot);
+    if (keep) {
+      lm.inlier = 1;
+      lms[k] = lm;
+      double* ex = p.exist_xy + ((size_t)s * NMAX + k) * 2;
+      ex[0] = lm.p2d[0];
+      ex[1] = lm.p2d[1];
+    }
+    kept += tot;
+  }
+  if (tid == 0) {
+    st.n_lm[cur] = kept;
+    st.orig_size = kept;
+    p.n_exist[s] = kept;
+    p.det_mode[s] = 2;
+    p.det_maxc[s] = p.cam.gftt_num;
+    st.vi_corr_due = st.has_imu ? 1 : 0;
+  }
+}
+// k_pose_lm with k_reproj_filter as its epilogue (FLVIS_CHAIN_MERGE bit 4): PL_T threads, the optimiser's register budget; a stream
+// that leaves the optimisation early (no tracking frame, track_fail) meets the filter's own test of the phase, as behind a launch.
+__global__ __launch_bounds__(PL_T) void k_pose_lm_filter(Pipe p) {
+  kj_wait(p.kj);
+  k_pose_lm_body(p);
+  __syncthreads();  // (workgroup scope: the pose, phase and slot as the lanes above left them; the terms buffer is free)
+  reproj_filter_chunks_dev<PL_T>(p, reinterpret_cast<PoseLMShared*>(pl_smem)->terms);
+  kj_signal(p.kj);
+}
 // VIMOTION::viCorrectionFromVision of the Tracking branch (f2f_tracking.cpp:256-262, after eraseReprjOutlier): one thread per stream.
 // Nothing on the frame's chain before k_frame_end reads the filter state, and the searches through the IMU ring are dependent global
 // loads (25 us of one thread): the detection stream runs it beside FeatureDEM / the stereo LK.
@@ -2216,6 +2316,25 @@ __global__ __launch_bounds__(256) void k_add_new_seeds(Pipe p) {
     k_add_new_body<256>(p);
     __syncthreads();  // (workgroup scope: the landmarks and the count as the threads above left them)
     for (int i = threadIdx.x; i < NMAX; i += 256) depth_seed_dev(p, s, i);
+  }
+  kj_signal(p.kj);
+  kj_post_wait(p.kj);
+}
+// k_feature_dem in front of them, one launch (FLVIS_CHAIN_MERGE bit 3): FeatureDEM's output is consumed by the workgroup that wrote it,
+// behind a barrier.  with_seeds = 0 (bit 0 clear): the launch ends behind k_add_new's work and k_depth_seeds follows as a launch.
+static_assert(DEM_T == 256, "k_dem_add_new_seeds: FeatureDEM's body, k_add_new_body<256> and the seeds share one workgroup");
+__global__ __launch_bounds__(256) void k_dem_add_new_seeds(Pipe p, DemLaunch d, int with_seeds) {
+  kj_wait(p.kj);
+  const int s = blockIdx.x;
+  k_feature_dem_body(d.w, d.h, p.cam.dem, d.sorted_xy, d.region_off, d.corner_cap, p.det_mode, p.exist_xy, p.n_exist, NMAX, p.new_xy, p.n_new,
+                     NEW_MAX);
+  __syncthreads();  // (workgroup scope: the new points and their count as the threads above left them)
+  if (p.det_mode[s] != 0) {  // (uniform per workgroup)
+    k_add_new_body<256>(p);
+    if (with_seeds) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < NMAX; i += 256) depth_seed_dev(p, s, i);
+    }
   }
   kj_signal(p.kj);
   kj_post_wait(p.kj);
@@ -2371,12 +2490,14 @@ __global__ __launch_bounds__(NMAX) void k_depth_innovate(Pipe p) {
 // ------------------------------------------------------------------------------------------------ frame end
 // init_frame's success test, keyframe decision (f2f_tracking.cpp:329-354,442-452), outputs, KeyFrame payload.
 constexpr int FE_T = 256;
+// (T threads: FE_T in k_frame_end; the workgroup of the launch that carries it as its epilogue, k_depth_innovate_end)
+template <int T>
 __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
   const int s = blockIdx.x;
   StreamState& st = p.st[s];
   const int lane = threadIdx.x;  // (first wave does the scalar bookkeeping)
   __shared__ int s_newkf;
-  __shared__ int s_cnt[FE_T / 64];
+  __shared__ int s_cnt[T / 64];
   const bool s_chain = st.phase == PH_TRACK;  // a keyframe of the Tracking branch continues the keyframe chain
   if (lane == 0) s_newkf = 0;
   __syncthreads();
@@ -2384,10 +2505,10 @@ __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
     const int cur = st.cur;
     Landmark* lms = lm_ptr(p, cur, s);
     int valid = 0;
-    for (int base = 0; base < st.n_lm[cur]; base += FE_T) {
+    for (int base = 0; base < st.n_lm[cur]; base += T) {
       const int i = base + lane;
       int tot;
-      block_rank<FE_T / 64>(i < st.n_lm[cur] && lms[i].has3d && lms[i].inlier, s_cnt, tot);
+      block_rank<T / 64>(i < st.n_lm[cur] && lms[i].has3d && lms[i].inlier, s_cnt, tot);
       valid += tot;
     }
     if (lane == 0) {
@@ -2458,79 +2579,89 @@ __device__ __forceinline__ void k_frame_end_body(const Pipe& p) {
       s_tail = tl;
     }
     __syncthreads();
-    if (s_full) return;
-    KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (s_tail % KFQ)];
-    Landmark* lms = lm_ptr(p, cur, s);
-    const int n = st.n_lm[cur];
-    int cnt = 0;
-    unsigned hsum = 0u;
-    for (int base = 0; base < n; base += FE_T) {
-      int i = base + lane;
-      bool sel = i < n && lms[i].has3d && lms[i].inlier;
-      int tot;
-      const int rk = block_rank<FE_T / 64>(sel, s_cnt, tot);
-      if (sel) {
-        int k = cnt + rk;
-        if (k < KF_MAXLM) {
-          kf.lm_id[k] = lms[i].id;
-          kf.lm_2d[k][0] = lms[i].p2u[0];
-          kf.lm_2d[k][1] = lms[i].p2u[1];
-          kf.lm_3d[k][0] = lms[i].p3w[0];
-          kf.lm_3d[k][1] = lms[i].p3w[1];
-          kf.lm_3d[k][2] = lms[i].p3w[2];
-          if (p.kf_check) hsum += kf_entry_hash(k, lms[i].id, lms[i].p2u, lms[i].p3w);
+    if (!s_full) {  // (uniform per workgroup: every thread reaches the barriers below, or none)
+      KeyFrameDev& kf = p.kfq[(size_t)s * KFQ + (s_tail % KFQ)];
+      Landmark* lms = lm_ptr(p, cur, s);
+      const int n = st.n_lm[cur];
+      int cnt = 0;
+      unsigned hsum = 0u;
+      for (int base = 0; base < n; base += T) {
+        int i = base + lane;
+        bool sel = i < n && lms[i].has3d && lms[i].inlier;
+        int tot;
+        const int rk = block_rank<T / 64>(sel, s_cnt, tot);
+        if (sel) {
+          int k = cnt + rk;
+          if (k < KF_MAXLM) {
+            kf.lm_id[k] = lms[i].id;
+            kf.lm_2d[k][0] = lms[i].p2u[0];
+            kf.lm_2d[k][1] = lms[i].p2u[1];
+            kf.lm_3d[k][0] = lms[i].p3w[0];
+            kf.lm_3d[k][1] = lms[i].p3w[1];
+            kf.lm_3d[k][2] = lms[i].p3w[2];
+            if (p.kf_check) hsum += kf_entry_hash(k, lms[i].id, lms[i].p2u, lms[i].p3w);
+          }
         }
+        cnt += tot;
       }
-      cnt += tot;
-    }
-    if (p.kf_check) {  // (test knob: the checksum of what every wave wrote, verified by the consumer -- ba_update_dev)
-      if (hsum) atomicAdd(&s_hash, hsum);
+      if (p.kf_check) {  // (test knob: the checksum of what every wave wrote, verified by the consumer -- ba_update_dev)
+        if (hsum) atomicAdd(&s_hash, hsum);
+        __syncthreads();
+      }
+      if (lane == 0) {
+        kf.frame_id = st.frame_id[cur];
+        kf.stamp = st.frame_time[cur];
+        kf.lm_count = cnt < KF_MAXLM ? cnt : KF_MAXLM;
+        for (int j = 0; j < 7; j++) kf.T_c_w[j] = st.T_c_w[cur][j];
+        // the gyro preintegration since the previous keyframe travels with the payload and restarts; a keyframe made by
+        // init_frame() starts a new chain (nothing links it to the keyframes before the (re-)initialisation)
+        for (int j = 0; j < 4; j++) kf.imu_dq[j] = st.kf_dq[j];
+        kf.imu_dt = st.kf_dt;
+        kf.imu_valid = (s_chain && st.kf_dt > 0) ? 1 : 0;
+        kf.imu_pad = p.kf_check ? (int)s_hash : 0;
+        // ... and the position part: the displacement preintegrated over the same interval and the filter velocity recorded when the
+        // previous keyframe was made; the velocity at THIS keyframe is kept for the next payload
+        for (int j = 0; j < 3; j++) {
+          kf.imu_dp[j] = st.kf_dp[j];
+          kf.imu_va[j] = st.kf_va[j];
+          st.kf_dp[j] = st.kf_dv[j] = 0.0;
+        }
+        {
+          const bool have = st.has_imu && st.vi_count > 0;
+          const MotionState& mb = p.vi[(size_t)s * VI_QUEUE + (st.vi_head + (st.vi_count > 0 ? st.vi_count - 1 : 0)) % VI_QUEUE];
+          for (int j = 0; j < 3; j++) st.kf_va[j] = have ? mb.vel[j] : 0.0;
+        }
+        st.kf_dq[0] = 1.0, st.kf_dq[1] = st.kf_dq[2] = st.kf_dq[3] = 0.0;
+        st.kf_dt = 0;
+        {  // the rig the keyframe was made with (the local map's optimisation projects with it)
+          CRig& rg = rig_of(p, s);
+          kf.rig_K[0] = rg.fx, kf.rig_K[1] = rg.fy, kf.rig_K[2] = rg.cx, kf.rig_K[3] = rg.cy;
+          for (int j = 0; j < 7; j++) kf.rig_T_c_i[j] = rg.T_c_i[j];
+        }
+        kf.valid = KFQ_KEYFRAME;
+        p.kfq_kf[s] = s_tail + 1u;
+      }
+      // (one release, by the thread that publishes: the barrier orders the other threads' stores before it, and a `buffer_wbl2` per wave
+      // -- what a fence executed by every thread costs -- writes the XCD's L2 back once per wave, k_ba_worker)
       __syncthreads();
+      if (lane == 0) __hip_atomic_store(&p.kfq_tail[s], s_tail + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (lane == 0) {
-      kf.frame_id = st.frame_id[cur];
-      kf.stamp = st.frame_time[cur];
-      kf.lm_count = cnt < KF_MAXLM ? cnt : KF_MAXLM;
-      for (int j = 0; j < 7; j++) kf.T_c_w[j] = st.T_c_w[cur][j];
-      // the gyro preintegration since the previous keyframe travels with the payload and restarts; a keyframe made by
-      // init_frame() starts a new chain (nothing links it to the keyframes before the (re-)initialisation)
-      for (int j = 0; j < 4; j++) kf.imu_dq[j] = st.kf_dq[j];
-      kf.imu_dt = st.kf_dt;
-      kf.imu_valid = (s_chain && st.kf_dt > 0) ? 1 : 0;
-      kf.imu_pad = p.kf_check ? (int)s_hash : 0;
-      // ... and the position part: the displacement preintegrated over the same interval and the filter velocity recorded when the
-      // previous keyframe was made; the velocity at THIS keyframe is kept for the next payload
-      for (int j = 0; j < 3; j++) {
-        kf.imu_dp[j] = st.kf_dp[j];
-        kf.imu_va[j] = st.kf_va[j];
-        st.kf_dp[j] = st.kf_dv[j] = 0.0;
-      }
-      {
-        const bool have = st.has_imu && st.vi_count > 0;
-        const MotionState& mb = p.vi[(size_t)s * VI_QUEUE + (st.vi_head + (st.vi_count > 0 ? st.vi_count - 1 : 0)) % VI_QUEUE];
-        for (int j = 0; j < 3; j++) st.kf_va[j] = have ? mb.vel[j] : 0.0;
-      }
-      st.kf_dq[0] = 1.0, st.kf_dq[1] = st.kf_dq[2] = st.kf_dq[3] = 0.0;
-      st.kf_dt = 0;
-      {  // the rig the keyframe was made with (the local map's optimisation projects with it)
-        CRig& rg = rig_of(p, s);
-        kf.rig_K[0] = rg.fx, kf.rig_K[1] = rg.fy, kf.rig_K[2] = rg.cx, kf.rig_K[3] = rg.cy;
-        for (int j = 0; j < 7; j++) kf.rig_T_c_i[j] = rg.T_c_i[j];
-      }
-      kf.valid = KFQ_KEYFRAME;
-      p.kfq_kf[s] = s_tail + 1u;
-    }
-    // (one release, by the thread that publishes: the barrier orders the other threads' stores before it, and a `buffer_wbl2` per wave
-    // -- what a fence executed by every thread costs -- writes the XCD's L2 back once per wave, k_ba_worker)
-    __syncthreads();
-    if (lane == 0) __hip_atomic_store(&p.kfq_tail[s], s_tail + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 __global__ __launch_bounds__(FE_T) void k_frame_end(Pipe p) {
   kj_wait(p.kj);
   // a stream without a frame in this step: no output, trajectory row, feed count, next image slot or keyframe (its FrameOut stays its
   // last frame's).  Uniform per workgroup; the join signal below is reached either way.
-  if (stream_present(p, blockIdx.x)) k_frame_end_body(p);
+  if (stream_present(p, blockIdx.x)) k_frame_end_body<FE_T>(p);
+  kj_signal(p.kj);
+}
+// k_depth_innovate and k_frame_end in one launch (FLVIS_CHAIN_MERGE bit 2): the frame's end by the workgroup that compacted the stream's
+// landmarks, behind a barrier instead of behind a launch.  Only for steps in which every stream has a frame (the host's choice).
+__global__ __launch_bounds__(NMAX) void k_depth_innovate_end(Pipe p) {
+  kj_wait(p.kj);
+  k_depth_innovate_body(p);
+  __syncthreads();  // (workgroup scope: the landmarks and the count as the threads above left them)
+  k_frame_end_body<NMAX>(p);
   kj_signal(p.kj);
 }
 
@@ -2743,6 +2874,9 @@ hipError_t launch_pose_lm_sets(hipStream_t st, const double* lm3d, const double*
   return hipSuccess;
 }
 void launch_pose_lm(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_pose_lm, dim3(p.S), dim3(PL_T), sizeof(PoseLMShared), st, p); }
+void launch_pose_lm_filter(hipStream_t st, const Pipe& p) {
+  hipLaunchKernelGGL(k_pose_lm_filter, dim3(p.S), dim3(PL_T), sizeof(PoseLMShared), st, p);
+}
 // the tabulated first batches of the PnP RANSAC (see g_pnp_sub5): once per device, before the first launch that reads them
 static hipError_t pnp_tables_init() {
   static bool done[64] = {};
@@ -2807,6 +2941,10 @@ hipError_t track_kernels_init() {
     const hipError_t e = pnp_tables_init();
     if (e != hipSuccess) return e;
   }
+  {
+    const hipError_t e = hipFuncSetAttribute((const void*)k_pose_lm_filter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PoseLMShared));
+    if (e != hipSuccess) return e;
+  }
   return hipFuncSetAttribute((const void*)k_pose_lm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PoseLMShared));
 }
 void launch_reproj_filter(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_reproj_filter, dim3(p.S), dim3(NMAX), 0, st, p); }
@@ -2816,12 +2954,18 @@ void launch_depth_seeds(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_depth_seeds, dim3(NMAX / 256, p.S), dim3(256), 0, st, p);
 }
 void launch_add_new_seeds(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_add_new_seeds, dim3(p.S), dim3(256), 0, st, p); }
+void launch_dem_add_new_seeds(hipStream_t st, const Pipe& p, const DemLaunch& d, bool with_seeds) {
+  hipLaunchKernelGGL(k_dem_add_new_seeds, dim3(p.S), dim3(256), dem_body_lds(d.corner_cap), st, p, d, with_seeds ? 1 : 0);
+}
 void launch_depth_triangulate(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_depth_triangulate, dim3(NMAX / 256, p.S), dim3(256), 0, st, p);
 }
 void launch_depth_innovate(hipStream_t st, const Pipe& p) { hipLaunchKernelGGL(k_depth_innovate, dim3(p.S), dim3(NMAX), 0, st, p); }
 void launch_frame_end(hipStream_t st, const Pipe& p) {
   hipLaunchKernelGGL(k_frame_end, dim3(p.S), dim3(FE_T), 0, st, p);
+}
+void launch_depth_innovate_end(hipStream_t st, const Pipe& p) {
+  hipLaunchKernelGGL(k_depth_innovate_end, dim3(p.S), dim3(NMAX), 0, st, p);
 }
 
 }  // namespace flvis

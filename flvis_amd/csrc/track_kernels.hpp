@@ -158,13 +158,24 @@ void launch_pnp_tail_cv(hipStream_t st, const Pipe& p);
 void launch_track_post(hipStream_t st, const Pipe& p);
 void launch_pose_lm(hipStream_t st, const Pipe& p);
 void launch_reproj_filter(hipStream_t st, const Pipe& p);
+void launch_pose_lm_filter(hipStream_t st, const Pipe& p);  // the two above in one launch
 void launch_vi_correction(hipStream_t st, const Pipe& p);  // viCorrectionFromVision of the streams k_reproj_filter marked
 void launch_add_new(hipStream_t st, const Pipe& p);
 void launch_depth_seeds(hipStream_t st, const Pipe& p);        // stereo-LK seeds of the current landmarks (critical path)
 void launch_add_new_seeds(hipStream_t st, const Pipe& p);      // the two above in one launch
+// ... behind k_feature_dem's work in the same launch (launch_feature_dem's arguments that are not the Pipe's); with_seeds: up to and
+// including k_depth_seeds' work, else up to k_add_new's
+struct DemLaunch {
+  int w, h;
+  const float* sorted_xy;
+  const int* region_off;
+  int corner_cap;
+};
+void launch_dem_add_new_seeds(hipStream_t st, const Pipe& p, const DemLaunch& d, bool with_seeds);
 void launch_depth_triangulate(hipStream_t st, const Pipe& p);  // two-view triangulation for k_depth_innovate (beside the stereo LK)
 void launch_depth_innovate(hipStream_t st, const Pipe& p);
 void launch_frame_end(hipStream_t st, const Pipe& p);
+void launch_depth_innovate_end(hipStream_t st, const Pipe& p);  // the two above in one launch (a step in which every stream has a frame)
 // per-stream reset (flvis_reset_streams / flvis_local_map_reset, and the initial state at tracker creation): one workgroup per listed stream
 constexpr int RESET_LIST = 64;  // streams per launch
 enum { RS_TRACKER = 1, RS_CMD = 2, RS_SKIP = 4, RS_CREATE = 8 };  // what k_stream_reset does for a stream (bits)

@@ -22,7 +22,8 @@ out = []
 out.append("| kernel | launches | total ms | avg us (all) | launches/frame | avg us (last %d frames) |" % steps)
 out.append("|---|---:|---:|---:|---:|---:|")
 tot_all = sum(e - s for v in by.values() for s, e in v)
-nframes = max(len(v) for k, v in by.items() if k in ("k_frame_end", "k_frame_begin"))
+# (a frame ends with k_frame_end or, FLVIS_CHAIN_MERGE bit 2, with the launch that carries it: k_depth_innovate_end)
+nframes = max(len(by.get("k_frame_end", [])) + len(by.get("k_depth_innovate_end", [])), len(by.get("k_frame_begin", [])))
 nactive = len(by.get("k_ransac_f", [])) or nframes  # frames after the skipped start-up frames run the full sequence
 for k, v in sorted(by.items(), key=lambda kv: -sum(e - s for s, e in kv[1])):
     v.sort()
