@@ -485,6 +485,41 @@ class Context:
         self._check(self._lib.flvis_hip_voxel_cloud_stats(self._h, _P(st, C.c_int64)), "voxel_cloud_stats")
         return dict(passes_run=int(st[0]), passes_skipped=int(st[1]), workspace_bytes=int(st[2]), input_points=int(st[3]))
 
+    def lc_map_poses(self, T_odom, T_map, stamps, nkf, jobs, mode=0, drift=None):
+        """flvis_hip_lc_map_poses: pose rows into the map frame.  T_odom, T_map float64 [n_seq, kf_stride, 7], stamps float64 [n_seq,
+        kf_stride] (device tensors), nkf: keyframes per sequence, drift [n_seq, 7]: the sequences' T_odom_map (read for empty ones).
+        jobs: dicts seq / kind (LC_ROWS_*) / rows (device float64 [n, 8 | 9 | 11]) and optionally out (a device tensor of the same
+        shape, or "inplace"; default: a new tensor) and anchor (False: no anchor array).  mode: LC_TRAJ_ANCHOR or LC_TRAJ_BLEND.
+        -> per job (rows in the map frame, anchors int32 [n] or None), device tensors."""
+        import numpy as np
+        import torch
+        for t in (T_odom, T_map, stamps):
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+        n_seq, stride = int(stamps.shape[0]), int(stamps.shape[1])
+        assert tuple(T_odom.shape) == (n_seq, stride, 7) and tuple(T_map.shape) == (n_seq, stride, 7)
+        nkf = np.ascontiguousarray(nkf, np.int32)
+        assert len(nkf) == n_seq
+        dr = None if drift is None else np.ascontiguousarray(drift, np.float64).reshape(n_seq, 7)
+        arr = (FlvisLcTrajJob * max(1, len(jobs)))()
+        res = []
+        for k, j in enumerate(jobs):
+            rows = j["rows"]
+            assert rows.dtype == torch.float64 and rows.is_cuda and rows.is_contiguous() and rows.dim() == 2
+            assert rows.shape[1] == LC_ROW_WIDTH[int(j["kind"])], "rows do not have the width of their kind"
+            out = j.get("out")
+            out = rows if isinstance(out, str) and out == "inplace" else torch.empty_like(rows) if out is None else out
+            assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.shape == rows.shape
+            anc = torch.empty((rows.shape[0],), dtype=torch.int32, device=rows.device) if j.get("anchor", True) else None
+            arr[k] = FlvisLcTrajJob(int(j["seq"]), int(j["kind"]), int(rows.shape[0]), rows.data_ptr(), out.data_ptr(),
+                                    anc.data_ptr() if anc is not None else None)
+            res.append((out, anc))
+        fn = self._lib.flvis_hip_lc_map_poses
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int,
+                       C.POINTER(FlvisLcTrajJob), C.c_int]
+        self._check(fn(self._h, n_seq, stride, _P(nkf, C.c_int), _ptr(T_odom), _ptr(T_map), _ptr(stamps),
+                       _P(dr, C.c_double) if dr is not None else None, len(jobs), arr, int(mode)), "lc_map_poses")
+        return res
+
     def lc_select_maps(self, scores, seg_n, maps, n_best, min_score):
         """flvis_hip_lc_select_maps: scores float64 [n_q, n_seg, seg_len], seg_n int32 [n_seg], maps int32 [n_q] (a segment, or -1: all),
         device tensors -> (idx int32 [n_q, n_best] global index seg * seg_len + j or -1, score float64 [n_q, n_best], count int32 [n_q])."""
@@ -1006,6 +1041,16 @@ class FlvisLcMerge(C.Structure):
                 ("chi2_before", C.c_double), ("chi2_after", C.c_double)]
 
 
+LC_TRAJ_ANCHOR, LC_TRAJ_BLEND = 0, 1                       # FLVIS_LC_TRAJ_*
+LC_ROWS_POSE8, LC_ROWS_TRAJ9, LC_ROWS_IMU11 = 0, 1, 2      # FLVIS_LC_ROWS_*
+LC_ROW_WIDTH = {LC_ROWS_POSE8: 8, LC_ROWS_TRAJ9: 9, LC_ROWS_IMU11: 11}
+
+
+class FlvisLcTrajJob(C.Structure):
+    """flvis_lc_traj_job of include/flvis_hip.h: n rows of one kind of one sequence for flvis_hip_lc_map_poses / flvis_loop_closer_map_poses."""
+    _fields_ = [("seq", C.c_int), ("kind", C.c_int), ("n", C.c_int), ("d_in", C.c_void_p), ("d_out", C.c_void_p), ("d_anchor", C.c_void_p)]
+
+
 def links_from_fix(fix, stream, kf):
     """The links a localize_in result yields when its query frame is also stored as keyframe `kf` of sequence `stream`: one per accepted
     candidate, from (candidate's sequence, candidate's keyframe) to (stream, kf) with the candidate's PnP pose.  -> list of dicts
@@ -1403,6 +1448,74 @@ class LoopCloser:
         if n.value > cap:
             raise FlvisError("loop_closer_similarity_row: %d entries, buffer of %d" % (n.value, cap))
         return buf[:n.value].copy()
+
+    def set_keyframe_stamps(self, stream, first_kf, stamps):
+        """flvis_loop_closer_set_keyframe_stamps: the stamps of keyframes first_kf .. of the sequence (add_keyframes leaves them unset,
+        add_logged takes them from the log).  FlvisError, and nothing changes, where the sequence's stamps would not stay finite and
+        strictly increasing."""
+        import numpy as np
+        t = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        fn = self._lib.flvis_loop_closer_set_keyframe_stamps
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        self._ctx._check(fn(self._h, int(stream), int(first_kf), len(t), _P(t, C.c_double)), "loop_closer_set_keyframe_stamps")
+
+    def keyframe_stamps(self, stream=0):
+        """flvis_loop_closer_keyframe_stamps -> float64 [keyframes of the sequence], NaN where never set"""
+        import numpy as np
+        n = C.c_int(0)
+        buf = np.zeros(self.max_keyframes)
+        fn = self._lib.flvis_loop_closer_keyframe_stamps
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
+        self._ctx._check(fn(self._h, int(stream), _P(buf, C.c_double), self.max_keyframes, C.byref(n)), "loop_closer_keyframe_stamps")
+        return buf[:n.value].copy()
+
+    def map_poses(self, jobs, mode=LC_TRAJ_ANCHOR, host=False):
+        """flvis_loop_closer_map_poses[_host]: pose rows of the closer's sequences into the map frame, every row with the drift of the
+        keyframe it follows (LC_TRAJ_ANCHOR) or the chord between that keyframe's drift and the next one's (LC_TRAJ_BLEND).  jobs: (seq,
+        kind, rows) with rows [n, 8 | 9 | 11] of kind LC_ROWS_POSE8 / _TRAJ9 (Tracker.trajectory) / _IMU11 (Tracker.imu_states): device
+        float64 tensors, or with host=True numpy arrays.  -> per job (rows in the map frame, anchors int32 [n]: the keyframe, -1 in an
+        empty sequence, -2 for a NaN stamp), of the inputs' type.  FlvisError, and nothing is written, when a named sequence holds a
+        keyframe without a stamp."""
+        import numpy as np
+        import torch
+        arr = (FlvisLcTrajJob * max(1, len(jobs)))()
+        res = []
+        for k, (seq, kind, rows) in enumerate(jobs):
+            kind = int(kind)
+            if host:
+                rows = np.ascontiguousarray(rows, np.float64).reshape(-1, LC_ROW_WIDTH[kind])
+                out, anc = np.zeros_like(rows), np.zeros(len(rows), np.int32)
+                arr[k] = FlvisLcTrajJob(int(seq), kind, len(rows), rows.ctypes.data, out.ctypes.data, anc.ctypes.data)
+            else:
+                assert rows.dtype == torch.float64 and rows.is_cuda and rows.is_contiguous() and rows.dim() == 2
+                assert rows.shape[1] == LC_ROW_WIDTH[kind], "rows do not have the width of their kind"
+                out, anc = torch.empty_like(rows), torch.empty((rows.shape[0],), dtype=torch.int32, device=rows.device)
+                arr[k] = FlvisLcTrajJob(int(seq), kind, int(rows.shape[0]), rows.data_ptr(), out.data_ptr(), anc.data_ptr())
+            res.append((rows, out, anc))
+        fn = self._lib.flvis_loop_closer_map_poses_host if host else self._lib.flvis_loop_closer_map_poses
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlvisLcTrajJob), C.c_int]
+        self._ctx._check(fn(self._h, len(jobs), arr, int(mode)), "loop_closer_map_poses_host" if host else "loop_closer_map_poses")
+        return [(out, anc) for _, out, anc in res]
+
+    def map_trajectory(self, streams, first, n_frames, mode=LC_TRAJ_ANCHOR, device=False):
+        """flvis_loop_closer_map_trajectory: rows first .. first + n_frames - 1 of the trajectory record of the tracker on this closer's
+        context, streams `streams` (stream s <-> sequence s), in the map frame; no pose goes through the host on the way.
+        -> (rows float64 [n, n_frames, 9], anchors int32 [n, n_frames]) as numpy arrays; device=True: the rows as a device tensor."""
+        import numpy as np
+        import torch
+        st = np.ascontiguousarray(streams, np.int32)
+        n, m = len(st), int(n_frames)
+        anc = np.zeros((n, max(m, 0)), np.int32)
+        fn = self._lib.flvis_loop_closer_map_trajectory
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if device:
+            rows = torch.empty((n, max(m, 0), 9), dtype=torch.float64, device=self._ctx.device)
+            rc = fn(self._h, n, _P(st, C.c_int), int(first), m, int(mode), _ptr(rows), None, anc.ctypes.data)
+        else:
+            rows = np.zeros((n, max(m, 0), 9))
+            rc = fn(self._h, n, _P(st, C.c_int), int(first), m, int(mode), None, rows.ctypes.data, anc.ctypes.data)
+        self._ctx._check(rc, "loop_closer_map_trajectory")
+        return rows, anc
 
 
 class Tracker:

@@ -43,6 +43,7 @@
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
 #include "kf_log.hpp"
+#include "lc_traj.hpp"
 #include "loop_kernels.hpp"
 
 namespace {
@@ -193,6 +194,8 @@ struct Seq {
   int n = 0;
   bool fresh = false;
   std::vector<double> T_odom;  // 7 per keyframe
+  std::vector<double> stamp;   // 1 per keyframe, NaN: never set (flvis_loop_closer_set_keyframe_stamps, add_logged)
+  int uploaded = 0;            // keyframes whose T_odom and stamp the map_poses tables on the device hold
   double T_odom_map[7] = {0, 0, 0, 0, 0, 0, 1};
   std::vector<int> loop_ids;       // (earlier, later) per loop
   std::vector<double> loop_poses;  // 7 per loop
@@ -254,6 +257,8 @@ struct flvis_loop_closer {
   size_t mg_V_cap = 0, mg_stage_cap = 0, mg_out_cap = 0;
   std::vector<uint8_t> h_mg_stage;
   std::vector<double> h_mg_out;
+  // map_poses, allocated by its first call: T_odom [S][maxkf][7] and the stamps [S][maxkf], filled up to Seq::uploaded
+  double *tj_T_odom = nullptr, *tj_stamps = nullptr;
   std::vector<void*> owned;
   std::vector<Seq> seq;
   std::vector<double> h_rows;
@@ -554,6 +559,7 @@ int flvis_loop_closer_add_keyframes(flvis_loop_closer* lc, int n, const int* h_s
   for (int i = 0; i < n; i++) {
     Seq& q = lc->seq[h_stream[i]];
     q.T_odom.insert(q.T_odom.end(), h_T_c_w_odom7 + 7 * i, h_T_c_w_odom7 + 7 * i + 7);
+    q.stamp.push_back(NAN);
     if (h_kf_id) h_kf_id[i] = q.n;
     q.n++;
     q.fresh = true;
@@ -1410,6 +1416,233 @@ int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const 
   return FLVIS_OK;
 }
 
+// ---- keyframe stamps and whole trajectories in the map frame (include/flvis_hip.h; the rule and the kernels: lc_traj.hip) ---------------
+// may keyframes first .. first + n - 1 of the sequence get these stamps?  Finite, strictly increasing, above the last set stamp before
+// them and below the first set stamp behind them
+static bool lc_stamps_fit(const Seq& q, int first, int n, const double* t) {
+  for (int i = 0; i < n; i++)
+    if (!std::isfinite(t[i]) || (i > 0 && !(t[i - 1] < t[i]))) return false;
+  if (n == 0) return true;
+  for (int k = first - 1; k >= 0; k--)
+    if (!std::isnan(q.stamp[k])) {
+      if (!(q.stamp[k] < t[0])) return false;
+      break;
+    }
+  for (int k = first + n; k < q.n; k++)
+    if (!std::isnan(q.stamp[k])) {
+      if (!(t[n - 1] < q.stamp[k])) return false;
+      break;
+    }
+  return true;
+}
+
+// the stamp of the keyframe add_logged has just stored, where the sequence's stamps stay strictly increasing with it (a log fed twice:
+// the second copy stays unset)
+static void lc_stamp_logged(Seq& q, double stamp) {
+  if (lc_stamps_fit(q, q.n - 1, 1, &stamp)) q.stamp[(size_t)q.n - 1] = stamp;
+}
+
+int flvis_loop_closer_set_keyframe_stamps(flvis_loop_closer* lc, int stream, int first_kf, int n, const double* h_stamps) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* what = "loop_closer_set_keyframe_stamps";
+  if (stream < 0 || stream >= lc->S || first_kf < 0 || n < 0 || (n > 0 && !h_stamps))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": bad args");
+  Seq& q = lc->seq[stream];
+  if ((long long)first_kf + n > (long long)q.n)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": the sequence holds no such keyframes");
+  if (!lc_stamps_fit(q, first_kf, n, h_stamps))
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": the stamps of sequence " + std::to_string(stream) +
+                                                " would not be finite and strictly increasing");
+  if (n == 0) return FLVIS_OK;
+  std::copy(h_stamps, h_stamps + n, q.stamp.begin() + first_kf);
+  q.uploaded = std::min(q.uploaded, first_kf);  // (the device tables are behind from here on)
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_keyframe_stamps(flvis_loop_closer* lc, int stream, double* h_stamps, int cap, int* n_out) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  if (stream < 0 || stream >= lc->S || !h_stamps || !n_out || cap < 0) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_keyframe_stamps: bad args");
+  const Seq& q = lc->seq[stream];
+  *n_out = q.n;
+  std::copy(q.stamp.begin(), q.stamp.begin() + std::min(cap, q.n), h_stamps);
+  return FLVIS_OK;
+}
+
+// What a map_poses call needs before its kernels: the jobs checked, every named sequence fully stamped, and O_k / tau_k of the keyframes
+// added since a sequence's last upload queued for the device tables (the caller synchronises).  h_nkf [S], h_drift [S][7]: the
+// sequences' counts and T_odom_map.
+static int lc_traj_prepare(flvis_loop_closer* lc, const char* what, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode, std::vector<int>& h_nkf,
+                           std::vector<double>& h_drift) {
+  flvis_ctx* ctx = lc->ctx;
+  h_nkf.resize((size_t)lc->S), h_drift.resize(7 * (size_t)lc->S);
+  for (int s = 0; s < lc->S; s++) {
+    h_nkf[s] = lc->seq[s].n;
+    memcpy(&h_drift[7 * (size_t)s], lc->seq[s].T_odom_map, 56);
+  }
+  int rc = flvis::lc_map_poses_check(ctx, what, lc->S, lc->maxkf, h_nkf.data(), n_jobs, h_jobs, mode);
+  if (rc != FLVIS_OK) return rc;
+  std::vector<char> named((size_t)lc->S, 0);
+  for (int i = 0; i < n_jobs; i++)
+    if (h_jobs[i].n > 0) named[h_jobs[i].seq] = 1;
+  for (int s = 0; s < lc->S; s++) {
+    if (!named[s]) continue;
+    const Seq& q = lc->seq[s];
+    for (int k = 0; k < q.n; k++)
+      if (std::isnan(q.stamp[k]))
+        return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": sequence " + std::to_string(s) + ": keyframe " + std::to_string(k) +
+                                                    " has no stamp (flvis_loop_closer_set_keyframe_stamps)");
+  }
+  hipSetDevice(ctx->device);
+  const size_t slots = (size_t)lc->S * lc->maxkf;
+  if (!((lc->tj_T_odom || lc->alloc(lc->tj_T_odom, slots * 7)) && (lc->tj_stamps || lc->alloc(lc->tj_stamps, slots)))) {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+  }
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < lc->S && e == hipSuccess; s++) {
+    Seq& q = lc->seq[s];
+    if (!named[s] || q.uploaded >= q.n) continue;
+    const size_t at = (size_t)s * lc->maxkf + q.uploaded, cnt = (size_t)(q.n - q.uploaded);
+    e = hipMemcpyAsync(lc->tj_T_odom + at * 7, &q.T_odom[7 * (size_t)q.uploaded], sizeof(double) * 7 * cnt, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(lc->tj_stamps + at, &q.stamp[(size_t)q.uploaded], sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (e != hipSuccess) {
+    hipStreamSynchronize(ctx->stream);  // (copies out of the host mirrors may be in flight)
+    return ctx->hip_fail(e, what);
+  }
+  return FLVIS_OK;
+}
+
+// ... and behind them: lc_map_poses_dev returns synchronised, so the uploads are done, whatever it says
+static int lc_traj_run(flvis_loop_closer* lc, const char* what, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode, const std::vector<int>& h_nkf,
+                       const std::vector<double>& h_drift) {
+  const int rc = flvis::lc_map_poses_dev(lc->ctx, what, lc->S, lc->maxkf, h_nkf.data(), lc->tj_T_odom, lc->db_T, lc->tj_stamps, h_drift.data(),
+                                         n_jobs, h_jobs, mode, false);
+  if (hipStreamSynchronize(lc->ctx->stream) == hipSuccess)
+    for (int i = 0; i < n_jobs; i++)
+      if (h_jobs[i].n > 0) lc->seq[h_jobs[i].seq].uploaded = lc->seq[h_jobs[i].seq].n;
+  return rc;
+}
+
+int flvis_loop_closer_map_poses(flvis_loop_closer* lc, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "loop_closer_map_poses";
+  std::vector<int> h_nkf;
+  std::vector<double> h_drift;
+  const int rc = lc_traj_prepare(lc, what, n_jobs, h_jobs, mode, h_nkf, h_drift);
+  if (rc != FLVIS_OK) return rc;
+  return lc_traj_run(lc, what, n_jobs, h_jobs, mode, h_nkf, h_drift);
+}
+
+int flvis_loop_closer_map_poses_host(flvis_loop_closer* lc, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* what = "loop_closer_map_poses_host";
+  std::vector<int> h_nkf;
+  std::vector<double> h_drift;
+  int rc = lc_traj_prepare(lc, what, n_jobs, h_jobs, mode, h_nkf, h_drift);
+  if (rc != FLVIS_OK) return rc;
+  // the jobs' rows behind one another in the context's workspace (mapped in place), the anchors behind the rows
+  size_t n_dbl = 0, n_rows = 0;
+  for (int i = 0; i < n_jobs; i++) n_dbl += (size_t)h_jobs[i].n * flvis::lct_row_width(h_jobs[i].kind), n_rows += (size_t)h_jobs[i].n;
+  hipStream_t st = ctx->stream;
+  if (n_rows == 0) {
+    hipStreamSynchronize(st);
+    return FLVIS_OK;
+  }
+  double* const d_rows = (double*)ctx->scratch("lct_host_rows", n_dbl * sizeof(double) + n_rows * sizeof(int));
+  if (!d_rows) {
+    (void)hipGetLastError();
+    hipStreamSynchronize(st);
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+  }
+  int* const d_anchor = reinterpret_cast<int*>(d_rows + n_dbl);
+  std::vector<flvis_lc_traj_job> jobs(h_jobs, h_jobs + n_jobs);
+  hipError_t e = hipSuccess;
+  size_t at = 0, row = 0;
+  for (int i = 0; i < n_jobs && e == hipSuccess; i++) {
+    flvis_lc_traj_job& j = jobs[i];
+    const size_t cnt = (size_t)j.n * flvis::lct_row_width(j.kind);
+    j.d_in = j.d_out = d_rows + at;
+    j.d_anchor = d_anchor + row;
+    if (cnt) e = hipMemcpyAsync(d_rows + at, h_jobs[i].d_in, cnt * sizeof(double), hipMemcpyHostToDevice, st);
+    at += cnt, row += (size_t)j.n;
+  }
+  if (e != hipSuccess) {
+    hipStreamSynchronize(st);
+    return ctx->hip_fail(e, what);
+  }
+  rc = lc_traj_run(lc, what, n_jobs, jobs.data(), mode, h_nkf, h_drift);
+  if (rc != FLVIS_OK) return rc;
+  for (int i = 0; i < n_jobs && e == hipSuccess; i++) {
+    const flvis_lc_traj_job& j = jobs[i];
+    if (j.n == 0) continue;
+    e = hipMemcpyAsync(h_jobs[i].d_out, j.d_out, (size_t)j.n * flvis::lct_row_width(j.kind) * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && h_jobs[i].d_anchor) e = hipMemcpyAsync(h_jobs[i].d_anchor, j.d_anchor, (size_t)j.n * sizeof(int), hipMemcpyDeviceToHost, st);
+  }
+  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  return FLVIS_OK;
+}
+
+int flvis_loop_closer_map_trajectory(flvis_loop_closer* lc, int n, const int* h_stream, int first_frame, int n_frames, int mode, double* d_out_rows9,
+                                     double* h_out_rows9, int* h_anchor) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  flvis_ctx* ctx = lc->ctx;
+  const char* what = "loop_closer_map_trajectory";
+  if (n <= 0 || !h_stream) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": bad args");
+  for (int i = 0; i < n; i++)
+    if (h_stream[i] < 0 || h_stream[i] >= lc->S) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": stream out of range");
+  int S = 0, w = 0, h = 0, cam = 0;
+  std::vector<const double*> d_traj;
+  std::vector<int> cap;
+  if (flvis::lc_traj_tracker_rows(ctx, S, w, h, cam, d_traj, cap) != FLVIS_OK)
+    return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": the closer's context holds no tracker (flvis_tracker_create)");
+  if (S != lc->S || w != lc->w || h != lc->h || cam != lc->cam_type)
+    return ctx->fail(FLVIS_ERR_CONFIG, std::string(what) + ": the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
+  for (int i = 0; i < n; i++) {
+    const int s = h_stream[i];
+    if (!d_traj[s]) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": the tracker keeps no trajectory record (traj_capacity)");
+    if (first_frame < 0 || n_frames < 0 || (long long)first_frame + n_frames > (long long)cap[s])
+      return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": out of range");
+  }
+  const size_t rows = (size_t)n * (size_t)n_frames;
+  double* d_out = d_out_rows9;
+  int* d_anchor = nullptr;
+  if (rows > 0 && (!d_out || h_anchor)) {  // the outputs the caller keeps on the host alone: through the context's workspace
+    uint8_t* const p = (uint8_t*)ctx->scratch("lct_traj_out", rows * (9 * sizeof(double) + sizeof(int)));
+    if (!p) {
+      (void)hipGetLastError();
+      return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+    }
+    if (!d_out) d_out = reinterpret_cast<double*>(p);
+    if (h_anchor) d_anchor = reinterpret_cast<int*>(p + rows * 9 * sizeof(double));
+  }
+  std::vector<flvis_lc_traj_job> jobs((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const size_t at = (size_t)i * (size_t)n_frames;
+    jobs[i] = flvis_lc_traj_job{h_stream[i], FLVIS_LC_ROWS_TRAJ9, n_frames, d_traj[h_stream[i]] + (size_t)first_frame * 9,
+                                d_out ? d_out + at * 9 : nullptr, d_anchor ? d_anchor + at : nullptr};
+  }
+  std::vector<int> h_nkf;
+  std::vector<double> h_drift;
+  int rc = lc_traj_prepare(lc, what, n, jobs.data(), mode, h_nkf, h_drift);
+  if (rc != FLVIS_OK) return rc;
+  rc = lc_traj_run(lc, what, n, jobs.data(), mode, h_nkf, h_drift);
+  if (rc != FLVIS_OK || rows == 0) return rc;
+  hipError_t e = hipSuccess;
+  if (h_out_rows9) e = hipMemcpyAsync(h_out_rows9, d_out, rows * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && h_anchor) e = hipMemcpyAsync(h_anchor, d_anchor, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (h_out_rows9 || h_anchor) {
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  return FLVIS_OK;
+}
+
 // The tracker's keyframe log (flvis_keyframe_log_enable) into the closer, without an image leaving the device.  Round r takes entry r of
 // every stream that has one: k_kf_log_gather lays their images out as add_keyframes takes them, and the round IS that call (and process).
 // Sequences are independent in the closer and a stream has at most one keyframe per step, so each sequence sees its keyframes one by one
@@ -1440,13 +1673,14 @@ int flvis_loop_closer_add_logged(flvis_loop_closer* lc, int process, flvis_lc_ev
   if (rounds == 0) return FLVIS_OK;
   hipStream_t st = ctx->stream;
   const size_t px = rec.px();
-  // the logged poses (KeyFrame.msg T_c_w: the round's T_c_w_odom), stream by stream
+  // the logged poses (KeyFrame.msg T_c_w: the round's T_c_w_odom) and, behind each, its header.stamp, stream by stream
+  static_assert(offsetof(flvis::KeyFrameDev, stamp) == offsetof(flvis::KeyFrameDev, T_c_w) + 56, "T_c_w and stamp are copied as one block");
   std::vector<std::vector<double>> T((size_t)S);
   for (int s = 0; s < S; s++) {
     if (logged[s] == 0) continue;
-    T[s].resize(7 * (size_t)logged[s]);
+    T[s].resize(8 * (size_t)logged[s]);
     const char* src = reinterpret_cast<const char*>(rec.kf + (size_t)s * rec.cap) + offsetof(flvis::KeyFrameDev, T_c_w);
-    const hipError_t e = hipMemcpy2D(T[s].data(), 56, src, sizeof(flvis::KeyFrameDev), 56, (size_t)logged[s], hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy2D(T[s].data(), 64, src, sizeof(flvis::KeyFrameDev), 64, (size_t)logged[s], hipMemcpyDeviceToHost);
     if (e != hipSuccess) return ctx->hip_fail(e, what);
   }
   // every round's stream and entry lists in one upload: [rounds][2][S]
@@ -1475,11 +1709,13 @@ int flvis_loop_closer_add_logged(flvis_loop_closer* lc, int process, flvis_lc_ev
   for (int r = 0; r < rounds; r++) {
     const int n = cnt[r];
     const int* l = &lists[(size_t)r * 2 * S];
-    for (int i = 0; i < n; i++) memcpy(&Tr[7 * (size_t)i], &T[l[i]][7 * (size_t)r], 56);
+    for (int i = 0; i < n; i++) memcpy(&Tr[7 * (size_t)i], &T[l[i]][8 * (size_t)r], 56);
     flvis::launch_kf_log_gather(st, rec, n, d_lists + (size_t)r * 2 * S, d_lists + (size_t)r * 2 * S + S, d0, d1);
     e = hipGetLastError();
     if (e != hipSuccess) return ctx->hip_fail(e, what);
     rc = flvis_loop_closer_add_keyframes(lc, n, l, d0, d1, Tr.data(), nullptr);
+    if (rc == FLVIS_OK)
+      for (int i = 0; i < n; i++) lc_stamp_logged(lc->seq[l[i]], T[l[i]][8 * (size_t)r + 7]);
     if (rc == FLVIS_OK && process) rc = flvis_loop_closer_process(lc, h_events ? h_events + (size_t)r * S : ev_tmp.data());
     if (rc != FLVIS_OK) return rc;
   }

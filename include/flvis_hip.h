@@ -1224,6 +1224,74 @@ int flvis_loop_closer_map_cloud(flvis_loop_closer* lc, int n_groups, const int* 
 int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, double leaf,
                                      int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped);
 
+/* ---- whole trajectories in the map frame: every pose row, not only the keyframes ---------------------------------------------------------
+ * (The reference broadcasts ONE tf map -> odom, the newest drift, vo_loopclosing.cpp:908: older poses shown through it are off by whatever
+ * the pose graph has moved since.  Here every keyframe carries its own drift, and a row takes the drift of the keyframe it follows.)
+ * pose7 = tx ty tz qx qy qz qw; the products are the closer's own (Hamilton q_mul, q_rot, pose_mul with its renormalisation), and
+ *   pose_inv(T) = (-(R(q*) t), q*), q* = (-x, -y, -z, w).  fp64 without contraction, sqrt and / correctly rounded: every value is defined
+ *   bit for bit.
+ * Sequence s holds keyframes k = 0 .. n - 1 with O_k (the odometry pose it was added with, T_c_w_odom7), M_k (the stored pose, what
+ *   flvis_loop_closer_poses returns) and a stamp tau_k, strictly increasing.  Keyframe drift: D_k = pose_mul(pose_inv(O_k), M_k).
+ * Anchor of a row with stamp t: a = max{k : tau_k <= t}; a = 0 when t < tau_0; an empty sequence: a = -1 and D = h_drift7 of the sequence;
+ *   a row whose stamp is NaN is copied unchanged, anchor -2.
+ * FLVIS_LC_TRAJ_ANCHOR: D = D_a (for rows at or after the newest keyframe the reference's tf rule).
+ * FLVIS_LC_TRAJ_BLEND: D = D_a when t < tau_0 or a = n - 1; else with u = (t - tau_a) / (tau_{a+1} - tau_a) and w0 = 1 - u the translation
+ *   w0 * t_a + u * t_{a+1} and the quaternion w0 * q_a + (u * sigma) * q_{a+1}, sigma = -1 when dot(q_a, q_{a+1}) < 0 else 1, divided by
+ *   the square root of its sum of squares (x, y, z, w summed in this order).  Continuous over a keyframe; no transcendental function:
+ *   neighbouring drifts differ by what one pose graph spreads over a chain, where the chord is the geodesic to far below rounding.
+ * Rows: FLVIS_LC_ROWS_POSE8 (t, T_c_w7) -> (t, pose_mul(T_c_w, D));  FLVIS_LC_ROWS_TRAJ9 (t, T_c_w7, state | new_kf << 4), a row of
+ *   flvis_get_trajectory: the same, the last column copied, rows of every state;  FLVIS_LC_ROWS_IMU11 (t, qw qx qy qz, px py pz, vx vy vz),
+ *   a row of flvis_get_imu_states, the body in the world frame: with E = pose_inv(D) the pose becomes pose_mul(E, (p, q)) and the velocity
+ *   q_rot(E.q, v); w stays first.
+ * flvis_hip_lc_map_poses is the call on caller arrays: d_T_odom, d_T_map [n_seq][kf_stride][7], d_stamps [n_seq][kf_stride], h_nkf [n_seq]
+ *   the keyframes per sequence, h_drift7 [n_seq][7] (read for empty sequences; may be NULL when no job names one).  A job is n rows of one
+ *   kind of one sequence: d_in, d_out [n][8 | 9 | 11], d_anchor [n] ints (may be NULL).  d_out == d_in is allowed (in place, the same
+ *   pointer; any other overlap is the caller's error); a job with n == 0 is skipped; several jobs may name one sequence.  Rows need not be
+ *   in order; a row's result does not depend on the others.  One upload, two launches (the drifts of the named sequences' keyframes, the
+ *   rows), no atomics; the call returns synchronised with the context's stream.
+ * FLVIS_ERR_INVALID_ARG, and no row is written: a mode or kind that does not exist, n_seq <= 0, a negative kf_stride, n_jobs or n, a
+ *   keyframe count outside [0, kf_stride], a sequence out of range, a NULL h_nkf, h_jobs, d_in or d_out, a NULL table with a non-empty
+ *   sequence named, and a named sequence whose stamps are not finite and strictly increasing (found on the device).  More than 65535 jobs:
+ *   FLVIS_ERR_CAPACITY.  The context stays usable. */
+enum { FLVIS_LC_TRAJ_ANCHOR = 0, FLVIS_LC_TRAJ_BLEND = 1 };
+enum { FLVIS_LC_ROWS_POSE8 = 0, FLVIS_LC_ROWS_TRAJ9 = 1, FLVIS_LC_ROWS_IMU11 = 2 };
+typedef struct flvis_lc_traj_job {
+  int seq, kind, n;
+  const double* d_in;
+  double* d_out;
+  int* d_anchor;
+} flvis_lc_traj_job;
+int flvis_hip_lc_map_poses(flvis_ctx* ctx, int n_seq, int kf_stride, const int* h_nkf, const double* d_T_odom /* [n_seq][kf_stride][7] */,
+                           const double* d_T_map, const double* d_stamps, const double* h_drift7 /* [n_seq][7], for empty sequences */,
+                           int n_jobs, const flvis_lc_traj_job* h_jobs, int mode);
+/* The closer's keyframe stamps (host): unset (NaN) for a keyframe of flvis_loop_closer_add_keyframes[_host], KeyFrame.msg's header.stamp
+ * for one of flvis_loop_closer_add_logged -- where that keeps the sequence's stamps strictly increasing: a log fed twice leaves the
+ * second copy unset.  set: keyframes first_kf .. first_kf + n - 1 of the sequence; the stamps of a sequence must be finite and strictly
+ * increasing where set, and a call that would break this (or names keyframes the sequence does not hold) returns FLVIS_ERR_INVALID_ARG
+ * and changes nothing.  keyframe_stamps: as flvis_loop_closer_poses ([cap], *n_out = keyframes in the sequence).
+ * flvis_loop_closer_reset[_rigs] forgets the slot's stamps. */
+int flvis_loop_closer_set_keyframe_stamps(flvis_loop_closer* lc, int stream, int first_kf, int n, const double* h_stamps);
+int flvis_loop_closer_keyframe_stamps(flvis_loop_closer* lc, int stream, double* h_stamps, int cap, int* n_out);
+/* Rows of any number of sequences into the map frame by the rule above, with the closer's own tables: O_k as handed to add_keyframes,
+ * M_k the pose database as it is now (after every pose graph, flvis_loop_closer_set_drift and flvis_loop_closer_merge: for a merged
+ * group the rows come out in the anchor sequence's frame), tau_k the stamps, h_drift7 the sequences' T_odom_map.  Jobs as above with
+ * seq = the sequence; _host: d_in / d_out / d_anchor are HOST arrays (staged through the context's workspace).  O_k and tau_k reach the
+ * device here, only what was added since the sequence's last upload; add, process and merge do nothing for this call.
+ * Every stored keyframe counts, processed or not, and a pending keyframe stays pending: poses, drift, loops, similarity rows and events
+ * afterwards are bit for bit those of a closer that never made the call.
+ * FLVIS_ERR_INVALID_ARG, and nothing is written: the argument errors above, and a job on a sequence that holds an unstamped keyframe
+ * (flvis_last_error names the sequence and the keyframe). */
+int flvis_loop_closer_map_poses(flvis_loop_closer* lc, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode);
+int flvis_loop_closer_map_poses_host(flvis_loop_closer* lc, int n_jobs, const flvis_lc_traj_job* h_jobs, int mode);
+/* The tracker's own record into the map frame without a pose crossing to the host: rows first_frame .. first_frame + n_frames - 1 of the
+ * trajectory record (flvis_get_trajectory's rows and range checks) of the streams h_stream [n], stream s <-> sequence s, as
+ * FLVIS_LC_ROWS_TRAJ9 jobs.  The closer's context must hold the tracker (FLVIS_ERR_INVALID_ARG without one, or without a trajectory
+ * record), whose n_streams, image_width, image_height and cam_type must be the closer's (FLVIS_ERR_CONFIG); waits for the tracker's queued
+ * work.  d_out_rows9 [n][n_frames][9] (device), h_out_rows9 the same on the host, h_anchor [n][n_frames] (host): each may be NULL.  The
+ * record itself is not changed. */
+int flvis_loop_closer_map_trajectory(flvis_loop_closer* lc, int n, const int* h_stream, int first_frame, int n_frames, int mode,
+                                     double* d_out_rows9, double* h_out_rows9, int* h_anchor);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@
 
   run_sequence.py <sequence folder> <config yaml> <out.txt> [--backend hip|cpu] [--frames N] [--local-map] [--imu-out <est.txt>]
                   [--loop-closing --voc <DBoW3 vocabulary file> [--lc-out <keyframes.txt>] [--map-cloud <map.ply> [--leaf 0.08]]
-                   [--lc-stereo-unrect]]
+                   [--lc-stereo-unrect] [--lc-traj-out <camera.txt>] [--lc-imu-out <imu.txt>] [--lc-traj-mode anchor|blend]]
                   [--local-map --lm-cloud <cloud.ply> [--lm-cloud-mode all|latest] [--leaf 0.08]]
                   [--batch N]
 
@@ -25,6 +25,13 @@ hip: flvis_loop_closer; cpu: the same control flow assembled from the oracle's f
 landmark and no loop is ever verified, which stays the default here.  With this switch the keyframes' landmarks come from this project's
 rule: LK into the raw second image, both ends undistorted into the rectified plane, DLT (hip: flvis_loop_closer_set_stereo_unrect; cpu:
 the checker composed from the oracle's functions, tests/_lc_unrect.py).
+
+--lc-traj-out / --lc-imu-out : (hip) the FULL-RATE trajectories in the map frame, next to the keyframe path of --lc-out: every frame of the
+tracker's record (flvis_loop_closer_map_trajectory: no pose goes through the host) and every /imu_pose row (flvis_loop_closer_map_poses_host),
+each with the drift of the keyframe it follows -- --lc-traj-mode anchor, the reference's tf rule per keyframe -- or blended between that
+keyframe's drift and the next one's (blend: no jump at a keyframe).  Same `stamp x y z qw qx qy qz` writer; with ground truth present
+their ATE is printed beside the odometry's (ate_rmse_m_lc_traj, ate_rmse_m_lc_imu_pose).  The keyframes' stamps are the frames' times:
+set per keyframe (flvis_loop_closer_set_keyframe_stamps), or with --batch taken from the log.  --lc-imu-out goes without --batch.
 
 --map-cloud : (hip) the corrected map next to the corrected keyframe path: the landmarks of every keyframe in the map frame, one point per
 voxel of --leaf metres (0: every landmark, what the reference's /map_cloud carries), as ASCII PLY with the voxels' point counts
@@ -73,7 +80,12 @@ def main():
     ap.add_argument("--lm-cloud-mode", choices=["all", "latest"], default="all")
     ap.add_argument("--lm-cloud-points", type=int, default=1 << 22)
     ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--lc-traj-out", default=None)
+    ap.add_argument("--lc-imu-out", default=None)
+    ap.add_argument("--lc-traj-mode", choices=["anchor", "blend"], default="anchor")
     args = ap.parse_args()
+    if (args.lc_traj_out or args.lc_imu_out) and not (args.loop_closing and args.backend == "hip"):
+        ap.error("--lc-traj-out / --lc-imu-out need --loop-closing and --backend hip")
     if args.lc_stereo_unrect and not args.loop_closing:
         ap.error("--lc-stereo-unrect needs --loop-closing")
     if args.loop_closing and not args.voc:
@@ -82,8 +94,8 @@ def main():
         ap.error("--map-cloud needs --loop-closing and --backend hip")
     if args.lm_cloud and not (args.local_map and args.backend == "hip"):
         ap.error("--lm-cloud needs --local-map and --backend hip")
-    if args.batch and (args.backend != "hip" or args.imu_out or args.batch < 0):
-        ap.error("--batch N (N > 0) needs --backend hip and goes without --imu-out")
+    if args.batch and (args.backend != "hip" or args.imu_out or args.lc_imu_out or args.batch < 0):
+        ap.error("--batch N (N > 0) needs --backend hip and goes without --imu-out and --lc-imu-out")
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -186,10 +198,11 @@ def main():
                 trk.imu_feed_sensor(0, r[0], r[4:7], r[1:4])                   # the library applies the axis remap
             d0, d1 = torch.from_numpy(i0[None]).cuda(), torch.from_numpy(i1[None]).cuda()
             res = trk.image_feed(d0, d1, [t], want_out=closer is not None, with_local_map=args.local_map)
-            if args.imu_out and len(imu):
+            if (args.imu_out or args.lc_imu_out) and len(imu):
                 imu_rows.append(trk.imu_states(0)[0])
             if closer is not None and res[0]["new_keyframe"]:
-                closer.add_keyframes([0], d0, d1, [res[0]["pose7"]])
+                kid = closer.add_keyframes([0], d0, d1, [res[0]["pose7"]])
+                closer.set_keyframe_stamps(0, int(kid[0]), [t])
                 lc_events.append(closer.process()[0])
                 kf_stamps.append(t)
         if args.batch:
@@ -199,6 +212,21 @@ def main():
         if args.imu_out and len(imu_rows):
             trk.write_imu_trajectory(imu_rows, args.imu_out)
         kf_T_c_w = closer.poses(0) if closer is not None else None
+        lc_traj, lc_imu = None, None
+        lc_mode = flvis_amd.LC_TRAJ_BLEND if args.lc_traj_mode == "blend" else flvis_amd.LC_TRAJ_ANCHOR
+        if args.lc_traj_out:
+            rows9 = closer.map_trajectory([0], 0, n, lc_mode)[0][0]
+            rows9 = rows9[(rows9[:, 8].astype(np.int64) & 15) == 1]            # only frames of a TRACKING stream carry a pose
+            lc_pos, lc_quat = [], []
+            for p7 in rows9[:, 1:8]:
+                R = traj_io.quat_to_rot(p7[6], p7[3], p7[4], p7[5])
+                lc_pos.append(-R.T @ p7[:3])
+                lc_quat.append(traj_io.rot_to_quat(R.T))
+            traj_io.write_stamped(args.lc_traj_out, rows9[:, 0], lc_pos, lc_quat)
+            lc_traj = (rows9[:, 0], np.asarray(lc_pos).reshape(-1, 3), np.asarray(lc_quat).reshape(-1, 4))
+        if args.lc_imu_out and len(imu_rows):
+            lc_imu = closer.map_poses([(0, flvis_amd.LC_ROWS_IMU11, imu_rows)], lc_mode, host=True)[0][0]
+            traj_io.write_stamped(args.lc_imu_out, lc_imu[:, 0], lc_imu[:, 5:8], lc_imu[:, 1:5])
         kf_landmarks = [len(closer.keyframe(0, i)["lm2"]) for i in range(len(kf_stamps))] if args.lc_stereo_unrect else []
         map_cloud = None
         if args.map_cloud:
@@ -243,6 +271,8 @@ def main():
             out["loop_closing"]["stereo_unrect_landmarks"] = int(sum(kf_landmarks))
         if args.map_cloud:
             out["loop_closing"]["map_cloud"] = map_cloud
+        if args.lc_traj_out or args.lc_imu_out:
+            out["loop_closing"]["trajectory_mode"] = args.lc_traj_mode
     if seq.groundtruth is not None and len(stamps) >= 3:
         gt_t, gt_p, _ = seq.groundtruth
         if kitti:   # KITTI ground truth is the camera itself
@@ -263,6 +293,15 @@ def main():
             ka, kb = traj_io.associate(np.asarray(kf_stamps), gt_t, 0.02)
             if len(ka) >= 3:
                 out["loop_closing"]["ate_rmse_m_keyframe_path"] = traj_io.ate_rmse(kp[ka], gt_p[kb])
+        if args.lc_traj_out and len(lc_traj[0]) >= 3:   # the corrected full-rate trajectories, beside ate_rmse_m / ate_rmse_m_imu_pose
+            lp = lc_traj[1] if kitti else traj_io.camera_to_body(lc_traj[1], lc_traj[2], T_imu_cam)[0]
+            la, lb = traj_io.associate(lc_traj[0], gt_t, 0.02)
+            if len(la) >= 3:
+                out["loop_closing"]["ate_rmse_m_lc_traj"] = traj_io.ate_rmse(lp[la], gt_p[lb])
+        if args.lc_imu_out and lc_imu is not None and len(lc_imu) >= 3:
+            ma, mb = traj_io.associate(lc_imu[:, 0], gt_t, 0.02)
+            if len(ma) >= 3:
+                out["loop_closing"]["ate_rmse_m_lc_imu_pose"] = traj_io.ate_rmse(lc_imu[ma, 5:8], gt_p[mb])
     print(json.dumps(out))
 
 
