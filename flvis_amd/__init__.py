@@ -1576,6 +1576,18 @@ class Tracker:
                         "get_imu_states")
         return rows[:n.value].copy(), dropped.value
 
+    def debug_vi_state(self, stream, cap=400):
+        """Test aid (flvis_debug_vi_state): the stream's filter after the staged samples -> dict(rows [n, 11] oldest first as
+        (t, q_w_i wxyz, pos_w_i, vel_w_i), biases [6] (acc, gyro), flags [4] (has_imu, vi_first, vi_initialized, vi_count))."""
+        np = self.np
+        rows, biases, flags = np.zeros((cap, 11), np.float64), np.zeros(6, np.float64), np.zeros(4, np.int32)
+        self.lib.flvis_debug_vi_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_int32)]
+        n = self.lib.flvis_debug_vi_state(self.ctx._h, stream, cap, _P(rows, C.c_double), _P(biases, C.c_double), _P(flags, C.c_int32))
+        if n < 0:
+            self.ctx._check(n, "debug_vi_state")
+        return dict(rows=rows[:min(n, cap)].copy(), biases=biases, flags=flags)
+
     def local_map_counts(self):
         """(keyframes emitted, local-map optimisations run) per stream"""
         np = self.np

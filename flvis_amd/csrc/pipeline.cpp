@@ -1638,4 +1638,44 @@ int flvis_get_pose_records(flvis_ctx* ctx, int stream, int cap, double* h_rows8)
   return st.rec_count;
 }
 
+// the visual-inertial filter of a stream (test aid): VIMOTION's `states` oldest first as rows (t, qw qx qy qz, pos, vel), its two
+// biases and (has_imu, vi_first, vi_initialized, vi_count); staged samples are integrated first (as flvis_get_imu_states does).
+// Returns the count.
+int flvis_debug_vi_state(flvis_ctx* ctx, int stream, int cap, double* h_rows11, double* h_biases6, int* h_flags4) {
+  if (!ctx || !ctx->pipe) return FLVIS_ERR_INVALID_ARG;
+  Pipeline* pl = ctx->pipe;
+  if (stream < 0 || stream >= pl->S || cap < 0 || (cap && !h_rows11)) return ctx->fail(FLVIS_ERR_INVALID_ARG, "debug_vi_state: bad args");
+  hipSetDevice(ctx->device);
+  sync_all(ctx);
+  int ls;
+  Lane& L = pl->lane_of(stream, ls);
+  bool staged = false;
+  for (int s = 0; s < L.S; s++) staged = staged || L.h_nimu[s] > 0;
+  if (staged) {
+    const int rc = lane_flush_imu(ctx, L);
+    if (rc != FLVIS_OK) return rc;
+  }
+  StreamState st;
+  std::vector<MotionState> ring(VI_QUEUE);
+  if (hipMemcpy(&st, L.pipe.st + ls, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(ring.data(), L.pipe.vi + (size_t)ls * VI_QUEUE, sizeof(MotionState) * VI_QUEUE, hipMemcpyDeviceToHost) != hipSuccess)
+    return ctx->fail(FLVIS_ERR_HIP, "debug_vi_state: copy failed");
+  if (st.vi_count < 0 || st.vi_count > VI_QUEUE || st.vi_head < 0 || st.vi_head >= VI_QUEUE)
+    return ctx->fail(FLVIS_ERR_HIP, "debug_vi_state: ring cursor out of range");
+  for (int i = 0; i < st.vi_count && i < cap; i++) {
+    const MotionState& m = ring[(st.vi_head + i) % VI_QUEUE];
+    double* r = h_rows11 + (size_t)11 * i;
+    r[0] = m.t;
+    memcpy(r + 1, m.q, 32);
+    memcpy(r + 5, m.pos, 24);
+    memcpy(r + 8, m.vel, 24);
+  }
+  if (h_biases6) {
+    memcpy(h_biases6, st.acc_bias, 24);
+    memcpy(h_biases6 + 3, st.gyro_bias, 24);
+  }
+  if (h_flags4) h_flags4[0] = st.has_imu, h_flags4[1] = st.vi_first, h_flags4[2] = st.vi_initialized, h_flags4[3] = st.vi_count;
+  return st.vi_count;
+}
+
 }  // extern "C"

@@ -832,6 +832,11 @@ int flvis_get_local_map_counts(flvis_ctx* ctx, int64_t* h_keyframes, int64_t* h_
 /* Test aid: poses (tx ty tz qx qy qz qw) of a stream's last Tracking frame right after PnP-RANSAC and after the pose-only LM
  * (the two fp64 stages of LKORBTracking::tracking / OptimizeInFrame::optimize), h_out21 = 3 x 7 doubles (the third: the pose the LM starts from). */
 int flvis_debug_stage_poses(flvis_ctx* ctx, int stream, double* h_out21);
+/* Test aid: the visual-inertial filter of a stream (VIMOTION, src/processing/vi_motion.cpp).  Synchronises and integrates the samples
+ * staged since the last frame (as flvis_get_imu_states does), then returns the number of states in the filter's queue (at most
+ * STATES_QUEUE_SIZE - 1 = 399) and writes the first `cap` of them, oldest first, as rows (t, qw qx qy qz, pos_w_i, vel_w_i) into
+ * h_rows11; h_biases6 (may be NULL): acc_bias, gyro_bias; h_flags4 (may be NULL): has_imu, is_first_data, imu_initialized and the count. */
+int flvis_debug_vi_state(flvis_ctx* ctx, int stream, int cap, double* h_rows11, double* h_biases6, int* h_flags4);
 /* Measurement aid (bench.py's LK instruction budget): enable != 0 makes the tracker's two LK launches per frame count their Gauss-Newton
  * iterations and the points that iterated, per pyramid level, into flvis_debug_counters: [36 + 2 l], [37 + 2 l] temporal LK at level l,
  * [48 + 2 l], [49 + 2 l] stereo LK; and, over both launches, [61] templates the temporal LK took from the template cache (written by

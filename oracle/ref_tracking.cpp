@@ -1408,4 +1408,17 @@ int ref_vi_states(void* h, int cap, double* rows11, double* biases6) {
   memcpy(biases6, b, sizeof(b));
   return n;
 }
+// the same of the VIMOTION a tracker owns; flags4: has_imu, is_first_data, imu_initialized, the queue length
+int ref_tracker_vi_states(void* h, int cap, double* rows11, double* biases6, int* flags4) {
+  ref::F2FTracking* f = (ref::F2FTracking*)h;
+  if (!f->vimotion) {  // a rig without an IMU
+    memset(biases6, 0, 6 * sizeof(double));
+    memset(flags4, 0, 4 * sizeof(int));
+    return 0;
+  }
+  const int n = ref_vi_states(f->vimotion, cap, rows11, biases6);
+  flags4[0] = f->has_imu ? 1 : 0, flags4[1] = f->vimotion->is_first_data ? 1 : 0, flags4[2] = f->vimotion->imu_initialized ? 1 : 0;
+  flags4[3] = n;
+  return n;
+}
 }

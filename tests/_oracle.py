@@ -457,6 +457,13 @@ class Tracker:
         n = lib().ref_tracker_pose_records(self.h, cap, _p(rows, C.c_double))
         return rows[:n].copy()
 
+    def vi_states(self, cap=400):
+        """the tracker's VIMOTION -> dict(rows [n, 11] oldest first as (t, q_w_i wxyz, pos, vel), biases [6] (acc, gyro),
+        flags [4] (has_imu, is_first_data, imu_initialized, n)): what flvis_amd.Tracker.debug_vi_state returns"""
+        rows, biases, flags = np.zeros((cap, 11)), np.zeros(6), np.zeros(4, np.int32)
+        n = lib().ref_tracker_vi_states(self.h, cap, _p(rows, C.c_double), _p(biases, C.c_double), _p(flags, C.c_int32))
+        return dict(rows=rows[:min(n, cap)].copy(), biases=biases, flags=flags)
+
 
 # ------------------------------------------------------------------------------------------- ORB (oracle/ref_orb.cpp)
 def resize_linear(img, dw, dh):
