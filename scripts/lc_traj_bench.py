@@ -60,8 +60,6 @@ src = torch.empty(call_bytes // 2, dtype=torch.uint8, device="cuda")
 dst = torch.empty_like(src)
 
 fn = ctx._lib.flvis_hip_lc_map_poses
-fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int,
-               C.POINTER(flvis_amd.FlvisLcTrajJob), C.c_int]
 jobs = {}
 for order, d in d_rows.items():
     arr = (flvis_amd.FlvisLcTrajJob * S)()

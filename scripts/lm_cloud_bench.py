@@ -84,8 +84,6 @@ def main():
                     arr = np.arange(S, dtype=np.int32)
                     no, nd = np.zeros(S, np.int64), np.zeros(S, np.int64)
                     fn = trk.lib.flvis_local_map_cloud
-                    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
                     ms = []
                     for _ in range(args.reps):
                         t0 = time.perf_counter()

@@ -108,8 +108,6 @@ for K in KFS:
             seqs = np.ascontiguousarray([s for g in groups for s in g], np.int32)
             no, nd = np.zeros(ng, np.int64), np.zeros(ng, np.int64)
             fn = lc._lib.flvis_loop_closer_map_cloud
-            fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             P = flvis_amd._P
 
             def call():

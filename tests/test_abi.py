@@ -166,7 +166,6 @@ def test_imu_trajectory_recorder_throttle_is_per_run_not_per_batch(tmp_path):
     with all rows writes."""
     import flvis_amd
     lib = flvis_amd.load_library()
-    lib.flvis_write_imu_trajectory.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_double, C.c_int]
     rows = np.zeros((900, 11))
     rows[:, 0] = 100.0 + np.arange(900) * 0.005          # 200 Hz
     rows[:, 1] = 1.0                                     # q_w_i = identity
@@ -189,8 +188,6 @@ def test_imu_trajectory_recorder_first_batch_shorter_than_the_throttle(tmp_path)
     file equals the one a single call with all rows writes."""
     import flvis_amd
     lib = flvis_amd.load_library()
-    lib.flvis_write_imu_trajectory.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_double, C.c_int]
-    lib.flvis_write_imu_trajectory_run.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_double, C.c_int, C.c_double]
     rows = np.zeros((300, 11))
     rows[:, 0] = 1403636579.0 + np.arange(300) * 0.005
     rows[:, 1] = 1.0
@@ -209,3 +206,110 @@ def test_imu_trajectory_recorder_first_batch_shorter_than_the_throttle(tmp_path)
     assert open(one).read() == open(many).read()
     # NaN as the first stamp: no throttle
     assert lib.flvis_write_imu_trajectory_run(ptr(rows), 300, many, 0.1, 0, float("nan")) == 300
+
+
+# ---- the C signatures come from the header, once (flvis_amd/_abi.py) ---------------------------------------------------------------
+
+PUBLIC_NAMES = """FLVIS_OK FLVIS_ERR_INVALID_ARG FLVIS_ERR_NO_DEVICE FLVIS_ERR_CAPACITY FLVIS_ERR_CONFIG FlvisError lib_path load_library
+Context voxel_cloud_info loop_candidate read_vocabulary_file save_vocabulary_file convert_vocabulary_file VocTrainParams TrainedVocabulary
+OrbParams orb_default_pattern FlvisCfg FrameOut load_config config_get_bool FlvisImage FlvisKeyframe LcParams LcEvent FLVIS_LC_FIX_CAND
+FlvisLcFix FLVIS_LC_ALL_MAPS FlvisLcFixIn FlvisLcLink FlvisLcMerge LC_TRAJ_ANCHOR LC_TRAJ_BLEND LC_ROWS_POSE8 LC_ROWS_TRAJ9 LC_ROWS_IMU11
+LC_ROW_WIDTH FlvisLcTrajJob links_from_fix FlvisLcLinkQuery links_reverse load_lc_params LoopCloser Tracker _ptr _P _link_dict""".split()
+
+
+def test_every_declared_signature_is_in_force_on_the_loaded_library():
+    import flvis_amd
+    from flvis_amd import _abi
+    table = _abi.signatures()
+    assert sorted(table) == declared_symbols() and len(table) >= 150
+    lib = flvis_amd.load_library()
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)                                   # (AttributeError: declared and not exported)
+        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
+
+
+def test_signatures_match_the_header_where_written_out_by_hand():
+    from flvis_amd import _abi
+    t = _abi.signatures()
+    p, i = C.c_void_p, C.c_int
+    assert t["flvis_version"] == (C.c_char_p, [])
+    assert t["flvis_hip_stream"] == (C.c_void_p, [p])
+    assert t["flvis_prof_enable_stages"] == (i, [p, i, C.c_uint64])
+    assert t["flvis_debug_pyramid"] == (i, [p, p, i, i, i, i, i, i, i, p, C.c_size_t])
+    assert t["flvis_hip_stereo_depth"] == (i, [p, p, p, p, i, p, p, p, p, p, i, p, C.c_float, p, p, p])
+    assert t["flvis_lc_links_from_fix"] == (i, [p, i, C.c_int64, i, p])
+    assert t["flvis_hip_destroy"] == (None, [p])
+    assert t["flvis_hip_rand_seed"] == (i, [p, C.c_uint32, p, i])
+    assert t["flvis_set_imu_factor"] == (i, [p, i, C.c_double])
+
+
+def test_a_type_outside_the_table_is_an_error_not_a_guess():
+    import flvis_amd
+    from flvis_amd import _abi
+    assert _abi.parse("int flvis_a(int n, const double* x);\nvoid flvis_b(void);\n") == {"flvis_a": (C.c_int, [C.c_int, C.c_void_p]),
+                                                                                       "flvis_b": (None, [])}
+    for text, bad in (("int flvis_ok(int n);\nint flvis_odd(int n, long double x);\n", "long double"),
+                      ("int flvis_ok(int n);\nint flvis_odd(flvis_cfg by_value);\n", "flvis_cfg"),
+                      ("int flvis_ok(int n);\nint flvis_odd(short n);\n", "short"),
+                      ("int flvis_ok(int n);\ndouble flvis_odd(int n);\n", "double"),
+                      ("int flvis_ok(int n);\nunsigned int flvis_odd(int n);\n", "unsigned int")):
+        with pytest.raises(flvis_amd.FlvisError) as e:
+            _abi.parse(text)
+        assert "flvis_odd" in str(e.value) and "'%s'" % bad in str(e.value), (text, str(e.value))
+
+
+def _fix_with_one_accepted_candidate(seq, kf):
+    import flvis_amd
+    fix = flvis_amd.FlvisLcFixIn()
+    fix.fix.n_candidates, fix.fix.best = 1, 0
+    fix.fix.cand_kf[0], fix.cand_seq[0], fix.fix.cand_accepted[0] = kf, seq, 1
+    for k, v in enumerate((0.1, 0.2, 0.3, 0.0, 0.0, 0.0, 1.0)):
+        fix.fix.cand_pose7[0][k] = v
+    return fix
+
+
+def test_a_64_bit_argument_survives_unwrapped():
+    import flvis_amd
+    lib = flvis_amd.load_library()
+    fix = _fix_with_one_accepted_candidate(seq=0, kf=3)
+    out = (flvis_amd.FlvisLcLink * 1)()
+    kf = 2 ** 40 + 5
+    assert lib.flvis_lc_links_from_fix(C.byref(fix), 1, kf, 1, out) == 1
+    assert out[0].kf_to == kf and (out[0].seq_from, out[0].kf_from, out[0].seq_to) == (0, 3, 1)
+    assert list(out[0].pose7) == [0.1, 0.2, 0.3, 0.0, 0.0, 0.0, 1.0]
+    with pytest.raises(C.ArgumentError):                          # a ctypes instance of another width is refused: the declaration is in force
+        lib.flvis_lc_links_from_fix(C.byref(fix), 1, C.c_int(7), 1, out)
+
+
+def test_too_few_arguments_are_a_type_error():
+    import flvis_amd
+    from flvis_amd import _abi
+    lib = flvis_amd.load_library()
+    for name, (_, argtypes) in _abi.signatures().items():
+        if argtypes:
+            with pytest.raises(TypeError):
+                getattr(lib, name)(*([None] * (len(argtypes) - 1)))
+
+
+def test_no_signature_is_assigned_by_hand():
+    assign = re.compile(r"\.(argtypes|restype)\s*=[^=]")
+    for path in glob.glob(os.path.join(ROOT, "flvis_amd", "*.py")):
+        if os.path.basename(path) != "_abi.py":
+            hits = [l for l in open(path) if assign.search(l)]
+            assert not hits, (path, hits)
+    declared = "|".join(declared_symbols())
+    on_declared = re.compile(r"\b(%s)\.(argtypes|restype)\s*=[^=]" % declared)
+    for path in glob.glob(os.path.join(ROOT, "tests", "*.py")) + glob.glob(os.path.join(ROOT, "scripts", "*.py")):
+        hits = [l for l in open(path) if on_declared.search(l)]
+        assert not hits, (path, hits)
+
+
+def test_the_package_file_only_gathers_names():
+    import ast
+    import flvis_amd
+    tree = ast.parse(open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read())
+    own = [getattr(n, "name", "lambda") for n in ast.walk(tree) if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef, ast.Lambda))]
+    assert not own, own
+    missing = [n for n in PUBLIC_NAMES if not hasattr(flvis_amd, n)]
+    assert not missing, missing
+    assert flvis_amd.load_library() is flvis_amd.load_library()              # (the cache)

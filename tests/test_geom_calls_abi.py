@@ -5,6 +5,8 @@ import ctypes as C
 import os
 import re
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DECLS = {
     "flvis_hip_find_fundamental_ransac":
@@ -48,7 +50,7 @@ def test_calls_are_in_the_opening_list_with_their_anchors():
 def test_calls_are_exported_and_bound():
     import flvis_amd
     lib = flvis_amd.load_library()
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     for name, wrapper in WRAPPERS.items():
         assert hasattr(lib, name), "%s is not exported" % name
         assert re.search(r"_lib\.%s\b" % name, src), "%s is not bound by flvis_amd" % name
@@ -61,7 +63,7 @@ def test_null_handle_is_refused_without_a_device():
     null = C.c_void_p(0)
     K = (C.c_double * 4)(384, 385, 320, 240)
     bad = flvis_amd.FLVIS_ERR_INVALID_ARG
-    assert lib.flvis_hip_find_fundamental_ransac(null, null, null, null, 32, 1, C.c_double(5.0), C.c_double(0.99), null, null) == bad
+    assert lib.flvis_hip_find_fundamental_ransac(null, null, null, null, 32, 1, 5.0, 0.99, null, null) == bad
     assert lib.flvis_hip_optimize_in_frame(null, null, null, null, null, 32, 1, K, 1, null, null) == bad
     assert lib.flvis_hip_undistort_points(null, null, null, 32, 1, K, K, null, null, 1, null) == bad
     assert lib.flvis_hip_project_points(null, null, null, 32, 1, null, K, K, 1, null) == bad

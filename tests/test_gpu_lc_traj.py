@@ -169,8 +169,6 @@ def test_bad_arguments_leave_the_context_usable(ctx):
     out = torch.full_like(r, SENT)
     lib = ctx._lib
     fn = lib.flvis_hip_lc_map_poses
-    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int,
-                   C.POINTER(flvis_amd.FlvisLcTrajJob), C.c_int]
     nkf = np.array(tab.nkf, np.int32)
     drift = np.ascontiguousarray(tab.drift)
     P = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731

@@ -122,7 +122,6 @@ def test_unstamped_keyframes_refuse_the_job_and_nothing_is_written(world):
     rows = dev(T.rows_of(np.random.default_rng(1), T.TRAJ9, np.linspace(0, 4, 50)))
     out = torch.full_like(rows, 777.25)
     fn = w.ctx._lib.flvis_loop_closer_map_poses
-    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(flvis_amd.FlvisLcTrajJob), C.c_int]
     arr = (flvis_amd.FlvisLcTrajJob * 2)(flvis_amd.FlvisLcTrajJob(0, T.TRAJ9, 50, rows.data_ptr(), out.data_ptr(), None),
                                          flvis_amd.FlvisLcTrajJob(1, T.TRAJ9, 50, rows.data_ptr(), out.data_ptr(), None))
     assert fn(lc._h, 2, arr, T.ANCHOR) == INV

@@ -184,8 +184,6 @@ def test_refusals_leave_the_outputs_untouched(world):
     # null pointers: every device pointer in turn
     out = sentinels(n, cap)
     fn = w.ctx._lib.flvis_hip_lc_keyframe_landmarks_unrect
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(flvis_amd.FlvisCfg), C.c_int, C.c_void_p, C.c_void_p,
-                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     ptrs = [t.data_ptr() for t in (i0.contiguous(), i1.contiguous(), kps.contiguous(), desc.contiguous(), cnt.contiguous()) + out]
     arr = (flvis_amd.FlvisCfg * 1)(w.cfg)
     for k in range(len(ptrs)):

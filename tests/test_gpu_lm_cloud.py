@@ -270,8 +270,6 @@ def test_refusals_change_nothing(ctx):
     trk, runs = _history(ctx)
     lib, h = ctx._lib, ctx._h
     fn = lib.flvis_local_map_cloud
-    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     xyz = torch.full((2, 16, 3), 7.0, dtype=torch.float32, device="cuda")
     npts = torch.full((2, 16), 7, dtype=torch.int32, device="cuda")
     ids = torch.full((2, 16), 7, dtype=torch.int64, device="cuda")

@@ -72,8 +72,6 @@ def _raw_link(lc, queries, n_best, link_cap=None):
     links = (flvis_amd.FlvisLcLink * max(1, cap))()
     cnt = C.c_int(-1)
     lib = lc._lib
-    lib.flvis_loop_closer_link.argtypes = [C.c_void_p, C.c_int, C.POINTER(flvis_amd.FlvisLcLinkQuery), C.c_int, C.POINTER(flvis_amd.FlvisLcFixIn),
-                                           C.c_int, C.POINTER(flvis_amd.FlvisLcLink), C.POINTER(C.c_int)]
     rc = lib.flvis_loop_closer_link(lc._h, n, arr, n_best, fix, cap, links if cap else None, C.byref(cnt))
     return rc, [bytes(f) for f in fix], [bytes(l) for l in links[:max(0, min(cap, cnt.value))]], cnt.value
 
@@ -83,8 +81,6 @@ def _raw_localize_in(lc, stream, m, img0, img1, n_best):
     fix = (flvis_amd.FlvisLcFixIn * 1)()
     st, mp = (C.c_int * 1)(stream), (C.c_int * 1)(m)
     lib = lc._lib
-    lib.flvis_loop_closer_localize_in.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,
-                                                  C.POINTER(flvis_amd.FlvisLcFixIn)]
     assert lib.flvis_loop_closer_localize_in(lc._h, 1, st, mp, flvis_amd._ptr(img0), flvis_amd._ptr(img1), n_best, fix) == flvis_amd.FLVIS_OK
     return bytes(fix[0])
 

@@ -250,8 +250,6 @@ def test_arguments(world):
     arr = (flvis_amd.FlvisLcLink * 2)(*[flvis_amd.FlvisLcLink(l["seq_from"], l["seq_to"], l["kf_from"], l["kf_to"], (C.c_double * 7)(*l["pose"]))
                                         for l in ok])
     out = (flvis_amd.FlvisLcMerge * 1)()
-    lib.flvis_loop_closer_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(flvis_amd.FlvisLcLink),
-                                            C.c_int, C.POINTER(flvis_amd.FlvisLcMerge), C.POINTER(C.c_double)]
     assert lib.flvis_loop_closer_merge(lc._h, 1, None, seq, 2, arr, 100, out, None) == INVALID
     assert lib.flvis_loop_closer_merge(lc._h, 1, ptr, None, 2, arr, 100, out, None) == INVALID
     assert lib.flvis_loop_closer_merge(lc._h, 1, ptr, seq, 2, None, 100, out, None) == INVALID

@@ -167,10 +167,8 @@ def test_refusals_launch_nothing(ctx):
         """the library through the context's handle, as Context.stereo_depth calls it"""
         p = lambda t: C.c_void_p(t.data_ptr())               # noqa: E731
         f = ctx._lib.flvis_hip_stereo_depth
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                      C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         rc = f(ctx._h, C.byref(cfg_), p(dev["img0"]), p(dev["img1"]), n_sets, p(dev["p2d"]), p(dev["p2u"]), p(dev["p3w"]), p(dev["has"]),
-               p(dev["count"]), cap_, a["poses"].ctypes.data, C.c_float(3.0), p(state), p(out), p(mask))
+               p(dev["count"]), cap_, a["poses"].ctypes.data, 3.0, p(state), p(out), p(mask))
         ctx._check(rc, "stereo_depth")
 
     dcfg = E.load_yaml(synth.D435I_DEPTH_YAML, flvis_amd.load_config)

@@ -282,7 +282,6 @@ def test_all_present_equals_plain_entries(ctx):
         if null:  # the _present entry with a NULL array
             outs = []
             fn = trk.lib.flvis_image_feed_present
-            fn.argtypes = [C.c_void_p] * 6 + [C.c_int]
             for i0, i1, ts, smp in A:
                 for s in range(S8):
                     if len(smp[s]):
@@ -499,7 +498,6 @@ def test_presence_arguments(ctx):
                             arr[s].width, arr[s].height, arr[s].pitch, arr[s].channels = im.shape[1], im.shape[0], im.strides[0], 1
                 pr = np.ones(4, np.uint8)
                 fn = trk.lib.flvis_image_feed_host_present
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
                 rc = fn(trk.ctx._h, C.cast(a, C.c_void_p), C.cast(b, C.c_void_p), pr.ctypes.data, None, 1, 0)
                 assert rc == flvis_amd.FLVIS_ERR_INVALID_ARG, rc
                 with pytest.raises(flvis_amd.FlvisError):

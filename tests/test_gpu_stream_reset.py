@@ -287,8 +287,6 @@ def test_reset_arguments(ctx):
 
 def test_reset_needs_a_tracker(ctx):
     lib = ctx._lib
-    lib.flvis_reset_streams.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.flvis_local_map_reset.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     import flvis_amd
     c = flvis_amd.Context(0)
     one = (C.c_int * 1)(0)

@@ -146,7 +146,6 @@ def test_mask_F_may_be_null(ctx):
     a = call.arrays()
     o = _outputs(call)
     f = ctx._lib.flvis_hip_lkorb_tracking
-    f.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10
     cfg = call.rig.lib_cfg()
     d = {k: _dev(a[k]) for k in ("img_from", "img_to", "p2d", "p2u", "p3w", "flags", "count", "pose_in")}
     rc = f(ctx._h, C.byref(cfg), *(d[k].data_ptr() for k in ("img_from", "img_to")), 1, *(d[k].data_ptr() for k in ("p2d", "p2u", "p3w", "flags", "count")),
@@ -167,7 +166,6 @@ def test_refusals_leave_the_outputs_untouched(ctx):
     a = call.arrays()
     cfg = call.rig.lib_cfg()
     f = ctx._lib.flvis_hip_lkorb_tracking
-    f.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10
     d = {k: _dev(a[k]) for k in ("img_from", "img_to", "p2d", "p2u", "p3w", "flags", "count")}
     big = {k: _dev(np.zeros((1, 1025) + a[k].shape[2:], a[k].dtype)) for k in ("p2d", "p2u", "p3w", "flags")}
     ones = np.ones(1, np.uint8)

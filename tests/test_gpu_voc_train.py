@@ -172,7 +172,6 @@ def test_refusals_write_nothing_and_two_runs_are_bit_identical(ctx, big):
     lib = flvis_amd.load_library()
     kfs, _ = big
     desc, cnt = _batch(kfs[:2], 512)
-    lib.flvis_hip_voc_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     SENT = 0x5A5A5A5A
 
     def call(d=desc, c=cnt, cap=512, n_img=2, prm=(10, 3, 0, 1, 0, 0), no_prm=False, no_out=False):

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import _binding
 import _lc_unrect as U
 import _loop_chain as LC
 import _oracle as O
@@ -78,7 +79,7 @@ def test_two_keyframes_pass_the_reference_s_acceptance_rule(world):
 def test_entry_points_are_declared_exported_and_bound():
     import flvis_amd
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     lib = flvis_amd.load_library()
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), "%s is not declared in include/flvis_hip.h" % name
@@ -93,8 +94,5 @@ def test_null_handles_are_refused_without_a_device():
     cfg = flvis_amd.FlvisCfg()
     null = C.c_void_p(0)
     fn = lib.flvis_hip_lc_keyframe_landmarks_unrect
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(flvis_amd.FlvisCfg), C.c_int, C.c_void_p, C.c_void_p,
-                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert fn(null, null, null, U.W, U.H, 1, C.byref(cfg), 1, null, null, null, 1024, null, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
-    lib.flvis_loop_closer_set_stereo_unrect.argtypes = [C.c_void_p, C.c_int]
     assert lib.flvis_loop_closer_set_stereo_unrect(null, 1) == flvis_amd.FLVIS_ERR_INVALID_ARG

@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import re
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("flvis_loop_closer_create_rigs", "flvis_loop_closer_reset", "flvis_loop_closer_reset_rigs", "flvis_loop_closer_stream_cfg",
        "flvis_hip_lc_keyframe_landmarks_rigs", "flvis_hip_pnp_ransac_rigs")
@@ -22,7 +24,7 @@ def test_harness_binds_the_fleet_entry_points():
     import flvis_amd
     for name in ("reset", "stream_cfg"):
         assert callable(getattr(flvis_amd.LoopCloser, name))
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     for name in NEW:
         assert re.search(r"_lib\.%s\b" % name, src), "%s is not bound by flvis_amd" % name
 
@@ -39,7 +41,7 @@ def test_null_handles_are_refused_without_a_device():
     assert lib.flvis_loop_closer_reset(null, 1, one) == flvis_amd.FLVIS_ERR_INVALID_ARG
     assert lib.flvis_loop_closer_reset_rigs(null, 1, one, C.byref(cfg)) == flvis_amd.FLVIS_ERR_INVALID_ARG
     assert lib.flvis_loop_closer_stream_cfg(null, 0, C.byref(cfg)) == flvis_amd.FLVIS_ERR_INVALID_ARG
-    assert lib.flvis_hip_pnp_ransac_rigs(null, null, null, null, 1, 1, null, 100, C.c_double(2.0), C.c_double(0.99), null, null, null,
+    assert lib.flvis_hip_pnp_ransac_rigs(null, null, null, null, 1, 1, null, 100, 2.0, 0.99, null, null, null,
                                          null) == flvis_amd.FLVIS_ERR_INVALID_ARG
     assert lib.flvis_hip_lc_keyframe_landmarks_rigs(null, null, null, 640, 480, 1, 0, null, null, null, null, null, null, 1024, null, null, null,
                                                     null) == flvis_amd.FLVIS_ERR_INVALID_ARG

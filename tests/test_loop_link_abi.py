@@ -12,6 +12,7 @@ import tempfile
 
 import numpy as np
 
+import _binding
 import _pgo_synth as PS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,17 +22,13 @@ SYMBOLS = ("flvis_loop_closer_link", "flvis_hip_lc_select_maps_skip", "flvis_lc_
 def _lib():
     import flvis_amd
     lib = flvis_amd.load_library()
-    lib.flvis_lc_link_reverse.argtypes = [C.POINTER(flvis_amd.FlvisLcLink), C.POINTER(flvis_amd.FlvisLcLink)]
-    lib.flvis_lc_links_from_fix.argtypes = [C.POINTER(flvis_amd.FlvisLcFixIn), C.c_int, C.c_int64, C.c_int, C.POINTER(flvis_amd.FlvisLcLink)]
-    lib.flvis_loop_closer_link.argtypes = [C.c_void_p, C.c_int, C.POINTER(flvis_amd.FlvisLcLinkQuery), C.c_int, C.POINTER(flvis_amd.FlvisLcFixIn),
-                                           C.c_int, C.POINTER(flvis_amd.FlvisLcLink), C.POINTER(C.c_int)]
     return lib
 
 
 def test_entry_points_are_declared_exported_and_bound():
     import flvis_amd
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     lib = flvis_amd.load_library()
     for name in SYMBOLS + ("flvis_hip_lc_select_maps_skip_compact",):
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), "%s is not declared in include/flvis_hip.h" % name
@@ -66,8 +63,6 @@ def test_null_arguments_are_refused_without_a_device():
     q = flvis_amd.FlvisLcLinkQuery(0, 1, -1, -1)
     fix, link, n = flvis_amd.FlvisLcFixIn(), flvis_amd.FlvisLcLink(0, 1, 0, 0, (C.c_double * 7)(0, 0, 0, 0, 0, 0, 1)), C.c_int(0)
     assert lib.flvis_loop_closer_link(None, 1, C.byref(q), 4, C.byref(fix), 1, C.byref(link), C.byref(n)) == INVALID
-    lib.flvis_hip_lc_select_maps_skip.argtypes = [C.c_void_p] * 1 + [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
-        [C.c_int, C.c_double] + [C.c_void_p] * 3
     assert lib.flvis_hip_lc_select_maps_skip(None, 1, None, 1, 1, None, None, None, 1, 0.0, None, None, None) == INVALID
     assert lib.flvis_lc_link_reverse(None, C.byref(link)) == INVALID and lib.flvis_lc_link_reverse(C.byref(link), None) == INVALID
     assert lib.flvis_lc_links_from_fix(None, 0, 0, 1, C.byref(link)) == -1

@@ -7,6 +7,8 @@ import re
 import subprocess
 import tempfile
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("flvis_loop_closer_localize", "flvis_loop_closer_localize_host", "flvis_loop_closer_set_drift")
 
@@ -14,7 +16,7 @@ NEW = ("flvis_loop_closer_localize", "flvis_loop_closer_localize_host", "flvis_l
 def test_entry_points_are_declared_exported_and_bound():
     import flvis_amd
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     lib = flvis_amd.load_library()
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), "%s is not declared in include/flvis_hip.h" % name

@@ -8,6 +8,8 @@ import re
 import subprocess
 import tempfile
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("flvis_loop_closer_localize_in", "flvis_loop_closer_localize_in_host", "flvis_hip_bow_score_jobs_at", "flvis_hip_lc_select_maps")
 
@@ -15,7 +17,7 @@ NEW = ("flvis_loop_closer_localize_in", "flvis_loop_closer_localize_in_host", "f
 def test_entry_points_are_declared_exported_and_bound():
     import flvis_amd
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     lib = flvis_amd.load_library()
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), "%s is not declared in include/flvis_hip.h" % name
@@ -40,8 +42,6 @@ def test_null_closer_is_refused_without_a_device():
         flvis_amd.FLVIS_ERR_INVALID_ARG
     # ... and the kernel-level steps a NULL context
     assert lib.flvis_hip_bow_score_jobs_at(null, 1, one, null, null, null, 8, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
-    lib.flvis_hip_lc_select_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.flvis_hip_lc_select_maps(null, 1, null, 1, 1, null, null, 1, 0.0, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
 
 

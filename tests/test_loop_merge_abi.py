@@ -7,13 +7,15 @@ import re
 import subprocess
 import tempfile
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_entry_point_is_declared_exported_and_bound():
     import flvis_amd
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     lib = flvis_amd.load_library()
     name = "flvis_loop_closer_merge"
     assert re.search(r"\bint\s+%s\s*\(" % name, txt), "%s is not declared in include/flvis_hip.h" % name
@@ -30,8 +32,6 @@ def test_null_closer_is_refused_without_a_device():
     ptr, seq = (C.c_int * 2)(0, 2), (C.c_int * 2)(0, 1)
     link = flvis_amd.FlvisLcLink(0, 1, 0, 0, (C.c_double * 7)(0, 0, 0, 0, 0, 0, 1))
     out = flvis_amd.FlvisLcMerge()
-    lib.flvis_loop_closer_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(flvis_amd.FlvisLcLink),
-                                            C.c_int, C.POINTER(flvis_amd.FlvisLcMerge), C.POINTER(C.c_double)]
     assert lib.flvis_loop_closer_merge(None, 1, ptr, seq, 1, C.byref(link), 100, C.byref(out), None) == flvis_amd.FLVIS_ERR_INVALID_ARG
 
 

@@ -133,7 +133,6 @@ def test_argument_errors_without_a_device():
     import flvis_amd
     lib = flvis_amd.load_library()
     chk = lib.flvis_voxel_cloud_check
-    chk.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int]
     ints = lambda *v: (C.c_int * len(v))(*v)  # noqa: E731
     ptr, rng = ints(0, 1, 3), ints(0, 4, 2, 2, 9, 1)
     good = dict(n_rows=10, cap=16, n_clouds=2, ptr=ptr, rng=rng, leaf=0.08, min_points=1, out_cap=5)
@@ -149,12 +148,8 @@ def test_argument_errors_without_a_device():
     assert info["sort_tile"] % info["workgroup"] == 0 and info["workgroup"] % 64 == 0 and info["bytes_per_point"] == 48
     assert lib.flvis_hip_voxel_cloud_info(None) == flvis_amd.FLVIS_ERR_INVALID_ARG
     vc = lib.flvis_hip_voxel_cloud
-    vc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double,
-                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     n_out = (C.c_int64 * 2)()
     assert vc(None, None, None, None, 10, 16, 2, ptr, rng, 0.08, 1, 5, None, None, n_out, None) == flvis_amd.FLVIS_ERR_INVALID_ARG
     for name in ("flvis_loop_closer_map_cloud", "flvis_loop_closer_map_cloud_host"):
         fn = getattr(lib, name)
-        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         assert fn(None, 1, ints(0, 1), ints(0), 0.08, 1, 5, None, None, n_out, None) == flvis_amd.FLVIS_ERR_INVALID_ARG

@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import re
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "flvis_hip_debug_pnp_ransac_iterative"
 
@@ -13,7 +15,7 @@ def test_hook_is_declared_exported_and_bound():
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "flvis_hip.h")).read(), flags=re.S)
     assert re.search(r"\bint\s+%s\s*\(" % NAME, txt), "%s is not declared in include/flvis_hip.h" % NAME
     assert hasattr(flvis_amd.load_library(), NAME), "%s is not exported" % NAME
-    assert re.search(r"_lib\.%s\b" % NAME, open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()), "%s is not bound by flvis_amd" % NAME
+    assert re.search(r"_lib\.%s\b" % NAME, _binding.source()), "%s is not bound by flvis_amd" % NAME
     assert callable(flvis_amd.Context.debug_pnp_ransac_iterative)
 
 
@@ -31,5 +33,5 @@ def test_null_handle_is_refused_without_a_device():
     K = (C.c_double * 4)(384, 385, 320, 240)
     g = (C.c_double * 7)(0, 0, 0, 0, 0, 0, 1)
     fn = getattr(lib, NAME)
-    assert fn(null, null, null, null, 1, 1, null, 100, C.c_double(3.0), C.c_double(0.99), null, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
-    assert fn(null, null, null, null, 32, 1, K, 100, C.c_double(3.0), C.c_double(0.99), g, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
+    assert fn(null, null, null, null, 1, 1, null, 100, 3.0, 0.99, null, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG
+    assert fn(null, null, null, null, 32, 1, K, 100, 3.0, 0.99, g, null, null, null) == flvis_amd.FLVIS_ERR_INVALID_ARG

@@ -6,6 +6,8 @@ import inspect
 import os
 import re
 
+import _binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "flvis_hip_lkorb_tracking"
 DECL = ("flvis_ctx* ctx, const flvis_cfg* cfg, const uint8_t* d_img_from, const uint8_t* d_img_to, int n_sets, const float* d_from_2d_plane, "
@@ -37,7 +39,7 @@ def test_call_is_exported_and_bound():
     import flvis_amd
     lib = flvis_amd.load_library()
     assert hasattr(lib, NAME), "%s is not exported" % NAME
-    src = open(os.path.join(ROOT, "flvis_amd", "__init__.py")).read()
+    src = _binding.source()
     assert re.search(r"_lib\.%s\b" % NAME, src)
     assert list(inspect.signature(flvis_amd.Context.lkorb_tracking).parameters) == WRAPPER_ARGS
     assert flvis_amd.FLVIS_ERR_CONFIG == -5
@@ -47,5 +49,4 @@ def test_null_handle_is_refused_without_a_device():
     import flvis_amd
     lib = flvis_amd.load_library()
     f = getattr(lib, NAME)
-    f.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10
     assert f(*([None] * 4), 1, *([None] * 5), 32, *([None] * 10)) == flvis_amd.FLVIS_ERR_INVALID_ARG

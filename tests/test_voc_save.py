@@ -23,7 +23,6 @@ def voc():
 
 def _save_arrays(lib, path, layout, voc, k, L, null=None):
     cp, ci, ds, wt, wi = (np.ascontiguousarray(a, t) for a, t in zip(voc, (np.int32, np.int32, np.uint8, np.float64, np.int32)))
-    lib.flvis_voc_file_save_arrays.argtypes = [C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4
     ptrs = [cp.ctypes.data, ci.ctypes.data, ds.ctypes.data, wt.ctypes.data, wi.ctypes.data]
     if null is not None and null >= 0:
         ptrs[null] = None
@@ -60,7 +59,6 @@ def test_writer_refusals(voc, tmp_path):
         assert _save_arrays(lib, p, layout, voc, 6, 3) == INVALID
     for null in (-1, 0, 1, 2, 3, 4):
         assert _save_arrays(lib, p, 0, voc, 6, 3, null=null) == INVALID
-    lib.flvis_voc_file_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     assert lib.flvis_voc_file_save(None, os.fsencode(p), 0) == INVALID
     assert not os.path.exists(p)
     # links that do not form a tree are refused, not written
@@ -73,9 +71,6 @@ def test_converter_from_the_quicklz_golden(tmp_path):
     src = os.path.join(GOLD, "voc_k6_quicklz.dbow3")
     lib = flvis_amd.load_library()
     h = C.c_void_p(0)
-    lib.flvis_voc_file_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
-    lib.flvis_voc_file_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.flvis_voc_file_close.argtypes = [C.c_void_p]
     assert lib.flvis_voc_file_open(os.fsencode(src), C.byref(h), None, 0) == 0
     dst = str(tmp_path / "plain.dbow3")
     try:
