@@ -11,7 +11,8 @@ from ._loader import (FLVIS_ERR_CAPACITY, FLVIS_ERR_CONFIG, FLVIS_ERR_INVALID_AR
 from ._structs import (FLVIS_LC_ALL_MAPS, FLVIS_LC_FIX_CAND, LC_ROW_WIDTH, LC_ROWS_IMU11, LC_ROWS_POSE8, LC_ROWS_TRAJ9,  # noqa: F401
                        LC_TRAJ_ANCHOR, LC_TRAJ_BLEND, FlvisCfg, FlvisImage, FlvisKeyframe, FlvisLcFix, FlvisLcFixIn, FlvisLcLink,
                        FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, FlvisStep, FrameOut, LcEvent, LcParams, OrbParams,
-                       VocTrainParams, config_get_bool, load_config, load_lc_params, orb_default_pattern)
+                       VocTrainParams, config_get_bool, load_config, load_lc_params, orb_default_pattern,
+                       DepthCloudParams, depth_cloud_params, octomap_feeder_params)
 from ._vocfile import TrainedVocabulary, convert_vocabulary_file, read_vocabulary_file, save_vocabulary_file  # noqa: F401
 from ._context import Context, voxel_cloud_info  # noqa: F401
 from ._loop_closer import LoopCloser, _link_dict, links_from_fix, links_reverse, loop_candidate  # noqa: F401

@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
-from ._structs import LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams
+from ._structs import LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, depth_cloud_params
 from ._vocfile import TrainedVocabulary
 
 
@@ -414,6 +414,50 @@ class Context:
         hn = npts.cpu().numpy() if want_npts else None
         return ([hx[c, :k[c]].copy() for c in range(nc)], [hn[c, :k[c]].copy() for c in range(nc)] if want_npts else None,
                 n_out[:nc].copy(), n_drop[:nc].copy())
+
+    def depth_cloud(self, depth, T_c_w, clouds, cams, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None,
+                    want_npts=True):
+        """flvis_hip_depth_cloud: depth uint16 [n_img, h, w] (a device tensor; torch without uint16: int16 of the same bits), T_c_w
+        float64 [n_img, 7]; clouds: per cloud a list of (first image, image count) ranges; cams: one (fx, fy, cx, cy, depth_factor)
+        per range, in the ranges' order.  window (u0, v0, u1, v1) or a DepthCloudParams, step an int or (step_u, step_v), z_min / z_max
+        in metres.  cap: output rows per cloud (default: found by a call of its own).  -> (xyz [n_clouds] of float32 [k, 3], npts
+        [n_clouds] of int32 [k] or None, n_out, n_dropped, n_valid int64 [n_clouds]) as numpy arrays; k = min(n_out, cap)."""
+        import torch
+        assert depth.is_cuda and depth.is_contiguous() and depth.dim() == 3 and depth.element_size() == 2 and not depth.dtype.is_floating_point
+        assert T_c_w.dtype == torch.float64 and T_c_w.is_contiguous() and tuple(T_c_w.shape) == (int(depth.shape[0]), 7)
+        n_img, h, w = [int(x) for x in depth.shape]
+        clouds = [[(int(a), int(b)) for a, b in c] for c in clouds]
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) for c in clouds])]), np.int32)
+        rng = np.ascontiguousarray([r for c in clouds for r in c] + [(0, 0)], np.int32).reshape(-1, 2)
+        cam5 = np.ascontiguousarray(np.asarray(cams, np.float64).reshape(-1, 5))
+        assert len(cam5) == len(rng) - 1, "one camera per range"
+        prm = depth_cloud_params(window, step, z_min, z_max)
+        nc = len(clouds)
+        n_out, n_drop, n_valid = (np.zeros(max(nc, 1), np.int64) for _ in range(3))
+
+        def call(cap, xyz, npts):
+            self._check(self._lib.flvis_hip_depth_cloud(self._h, _ptr(depth), _ptr(T_c_w), n_img, w, h, nc, _P(ptr, C.c_int), _P(rng, C.c_int),
+                                                        _P(cam5, C.c_double), C.byref(prm), leaf, int(min_points), cap, _ptr(xyz), _ptr(npts),
+                                                        _P(n_out, C.c_int64), _P(n_drop, C.c_int64), _P(n_valid, C.c_int64)), "depth_cloud")
+        if cap is None:
+            call(0, None, None)
+            cap = int(max(list(n_out[:nc]) + [0]))
+        cap = int(cap)
+        xyz = torch.empty((max(nc, 1), max(cap, 0), 3), dtype=torch.float32, device=depth.device)
+        npts = torch.empty((max(nc, 1), max(cap, 0)), dtype=torch.int32, device=depth.device) if want_npts else None
+        call(cap, xyz, npts)
+        k = [int(min(n, cap)) for n in n_out[:nc]]
+        hx = xyz.cpu().numpy()
+        hn = npts.cpu().numpy() if want_npts else None
+        return ([hx[c, :k[c]].copy() for c in range(nc)], [hn[c, :k[c]].copy() for c in range(nc)] if want_npts else None,
+                n_out[:nc].copy(), n_drop[:nc].copy(), n_valid[:nc].copy())
+
+    def depth_cloud_times(self, enable=True):
+        """flvis_hip_depth_cloud_times: switch the stage timing of the dense calls on or off -> dict(count, keys, sort, rows) in
+        milliseconds of the last timed call."""
+        ms = np.zeros(4)
+        self._check(self._lib.flvis_hip_depth_cloud_times(self._h, int(bool(enable)), _P(ms, C.c_double)), "depth_cloud_times")
+        return dict(count=float(ms[0]), keys=float(ms[1]), sort=float(ms[2]), rows=float(ms[3]))
 
     def voxel_cloud_stats(self):
         """flvis_hip_voxel_cloud_stats: dict(passes_run, passes_skipped, workspace_bytes, input_points) of the context's last call"""

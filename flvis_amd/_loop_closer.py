@@ -5,7 +5,7 @@ import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
 from ._structs import (FLVIS_LC_FIX_CAND, LC_ROW_WIDTH, LC_TRAJ_ANCHOR, FlvisCfg, FlvisImage, FlvisLcFix, FlvisLcFixIn, FlvisLcLink,
-                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams)
+                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams, cloud_rows, depth_cloud_params)
 
 
 def loop_candidate(row, present, lcKFDist, lcKFMaxDist, lcNKFClosest, minScore):
@@ -334,6 +334,42 @@ class LoopCloser:
             hx, hn = xyz[:, :kmax].cpu().numpy(), npts[:, :kmax].cpu().numpy()
         k = [int(min(n, cap)) for n in n_out[:ng]]
         return ([hx[g, :k[g]].copy() for g in range(ng)], [hn[g, :k[g]].copy() for g in range(ng)], n_out[:ng].copy(), n_drop[:ng].copy())
+
+    def dense_cloud(self, groups, first_kf=None, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None, host=False):
+        """flvis_loop_closer_dense_cloud (depth rigs): per group one dense cloud of the tracker's logged depth keyframes of the group's
+        sequences, logged entry i under the closer's stored T_c_w of keyframe first_kf + i -- the map frame after process, set_drift
+        or merge.  groups: as map_cloud's; first_kf: per group a list with one first keyframe per sequence (None: 0 everywhere).
+        window / step / z_min / z_max: Context.depth_cloud's.  cap: rows per group (default: found by a call of its own).
+        -> (xyz [n_groups] of float32 [k, 3], npts [n_groups] of int32 [k], n_out, n_dropped, n_valid int64 [n_groups])."""
+        import torch
+        groups = [[int(s) for s in g] for g in groups]
+        ng = len(groups)
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(g) for g in groups])]), np.int32)
+        seqs = np.ascontiguousarray([s for g in groups for s in g] + [0], np.int32)
+        first = None if first_kf is None else np.ascontiguousarray([int(k) for g in first_kf for k in g] + [0], np.int32)
+        assert first is None or len(first) == len(seqs), "one first keyframe per listed sequence"
+        prm = depth_cloud_params(window, step, z_min, z_max)
+        n_out, n_drop, n_valid = (np.zeros(max(ng, 1), np.int64) for _ in range(3))
+        head = (self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), _P(first, C.c_int) if first is not None else None, C.byref(prm), leaf,
+                int(min_points))
+        tail = (_P(n_out, C.c_int64), _P(n_drop, C.c_int64), _P(n_valid, C.c_int64))
+        fn, what = ((self._lib.flvis_loop_closer_dense_cloud_host, "loop_closer_dense_cloud_host") if host else
+                    (self._lib.flvis_loop_closer_dense_cloud, "loop_closer_dense_cloud"))
+        if cap is None:                                      # a first call for the counts alone: the buffers then fit what comes
+            self._ctx._check(fn(*head, 0, None, None, *tail), what)
+            cap = int(max(list(n_out[:ng]) + [0]))
+        cap = int(cap)
+        shape = (max(ng, 1), max(cap, 0))
+        if host:
+            hx, hn = np.zeros(shape + (3,), np.float32), np.zeros(shape, np.int32)
+            self._ctx._check(fn(*head, cap, _P(hx, C.c_float), _P(hn, C.c_int), *tail), what)
+        else:
+            xyz = torch.empty(shape + (3,), dtype=torch.float32, device=self._ctx.device)
+            npts = torch.empty(shape, dtype=torch.int32, device=self._ctx.device)
+            self._ctx._check(fn(*head, cap, _ptr(xyz), _ptr(npts), *tail), what)
+            hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
+        rows = cloud_rows(hx, hn, n_out, cap, ng)
+        return rows + (n_out[:ng].copy(), n_drop[:ng].copy(), n_valid[:ng].copy())
 
     def poses(self, stream=0, cap=None):
         cap = int(cap) if cap else self.max_keyframes      # (never fewer rows than the sequence can hold: no silent truncation)

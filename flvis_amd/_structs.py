@@ -151,6 +151,34 @@ class FlvisLcLinkQuery(C.Structure):
     _fields_ = [("stream", C.c_int), ("map", C.c_int), ("kf", C.c_int64), ("own_gap", C.c_int64)]
 
 
+class DepthCloudParams(C.Structure):
+    """flvis_depth_cloud_params of include/flvis_hip.h: the sampled window (u1 / v1 <= 0: the image's width / height), the steps and the
+    inclusive z limits in metres of flvis_hip_depth_cloud."""
+    _fields_ = [("u0", C.c_int), ("v0", C.c_int), ("u1", C.c_int), ("v1", C.c_int), ("step_u", C.c_int), ("step_v", C.c_int),
+                ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
+def depth_cloud_params(window=None, step=1, z_min=0.3, z_max=10.0):
+    """-> DepthCloudParams.  window: (u0, v0, u1, v1), None: the whole image; step: one int or (step_u, step_v)."""
+    if isinstance(window, DepthCloudParams):
+        return window
+    u0, v0, u1, v1 = (0, 0, 0, 0) if window is None else [int(x) for x in window]
+    su, sv = (step, step) if np.isscalar(step) else step
+    return DepthCloudParams(u0, v0, u1, v1, int(su), int(sv), float(z_min), float(z_max))
+
+
+def octomap_feeder_params(height):
+    """The sampling of the reference's octomap feeder (octomap_feeder.cpp:35-61): every 7th pixel of every 7th row from height / 2 - 22
+    to height / 2 + 20 (seven rows), 0.5 m to 6.5 m."""
+    return DepthCloudParams(0, height // 2 - 22, 0, height // 2 + 21, 7, 7, 0.5, 6.5)
+
+
+def cloud_rows(xyz, npts, n_out, cap, n):
+    """the rows a cloud call wrote (arrays [n, cap, ...]) as per-cloud numpy arrays of min(n_out, cap) rows"""
+    k = [int(min(c, cap)) for c in n_out[:n]]
+    return [xyz[g, :k[g]].copy() for g in range(n)], [npts[g, :k[g]].copy() for g in range(n)]
+
+
 def load_lc_params(yaml_path):
     """flvis_lc_params_load: the loop-closing block of the reference's yaml files.  Host-only."""
     prm = LcParams()

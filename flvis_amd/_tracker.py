@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._loader import FlvisError, _P, _ptr
-from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut
+from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut, cloud_rows, depth_cloud_params
 
 
 class Tracker:
@@ -439,6 +439,41 @@ class Tracker:
         v = (C.c_int64 * 3)()
         self.ctx._check(self.lib.flvis_keyframe_log_info(self.ctx._h, int(stream), v), "keyframe_log_info")
         return dict(logged=int(v[0]), dropped=int(v[1]), capacity=int(v[2]))
+
+    def keyframe_log_depth_cloud(self, streams, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None, host=False,
+                                 slices=None):
+        """flvis_keyframe_log_depth_cloud (depth rigs): per listed stream one dense cloud of its logged keyframes' depth images, each
+        under its logged T_c_w and the stream's own camera, voxel-filtered on the device (leaf = 0: every valid sample).  window / step /
+        z_min / z_max: Context.depth_cloud's.  slices: per stream (first entry, count), None: every entry.  cap: rows per stream
+        (default: found by a call of its own).  host=True goes through the _host entry.
+        -> (xyz [n] of float32 [k, 3], npts [n] of int32 [k], n_out, n_dropped, n_valid int64 [n])."""
+        import torch
+        sl = [int(s) for s in streams]
+        n = len(sl)
+        arr = np.ascontiguousarray(sl + [0], np.int32)
+        sli = None if slices is None else np.ascontiguousarray(list(slices) + [(0, 0)], np.int32).reshape(-1, 2)
+        assert sli is None or len(sli) == n + 1, "one slice per listed stream"
+        prm = depth_cloud_params(window, step, z_min, z_max)
+        n_out, n_drop, n_valid = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        head = (self.ctx._h, n, _P(arr, C.c_int), _P(sli, C.c_int) if sli is not None else None, C.byref(prm), leaf, int(min_points))
+        tail = (_P(n_out, C.c_int64), _P(n_drop, C.c_int64), _P(n_valid, C.c_int64))
+        fn, what = ((self.lib.flvis_keyframe_log_depth_cloud_host, "keyframe_log_depth_cloud_host") if host else
+                    (self.lib.flvis_keyframe_log_depth_cloud, "keyframe_log_depth_cloud"))
+        if cap is None:
+            self.ctx._check(fn(*head, 0, None, None, *tail), what)
+            cap = int(max(list(n_out[:n]) + [0]))
+        cap = int(cap)
+        shape = (max(n, 1), max(cap, 0))
+        if host:
+            hx, hn = np.zeros(shape + (3,), np.float32), np.zeros(shape, np.int32)
+            self.ctx._check(fn(*head, cap, _P(hx, C.c_float), _P(hn, C.c_int), *tail), what)
+        else:
+            xyz = torch.empty(shape + (3,), dtype=torch.float32, device=self.ctx.device)
+            npts = torch.empty(shape, dtype=torch.int32, device=self.ctx.device)
+            self.ctx._check(fn(*head, cap, _ptr(xyz), _ptr(npts), *tail), what)
+            hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
+        rows = cloud_rows(hx, hn, n_out, cap, n)
+        return rows + (n_out[:n].copy(), n_drop[:n].copy(), n_valid[:n].copy())
 
     def keyframe_log_get(self, stream, index, cap=2048, images=True):
         """flvis_keyframe_log_get: logged keyframe `index` of the stream, a dict like keyframe_msg's."""

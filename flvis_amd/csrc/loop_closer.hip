@@ -45,6 +45,8 @@
 #include "kf_log.hpp"
 #include "lc_traj.hpp"
 #include "loop_kernels.hpp"
+#include "map_cloud.hpp"
+#include "pipeline_host.hpp"
 
 namespace {
 
@@ -1414,6 +1416,88 @@ int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const 
   }
   if (e != hipSuccess) return ctx->hip_fail(e, "loop_closer_map_cloud_host");
   return FLVIS_OK;
+}
+
+// The dense map (include/flvis_hip.h): the tracker's logged depth images under the closer's stored poses.  Reads the log, the pose
+// database and the sequences' configs; writes nothing of the closer's, the log's or the tracker's.
+static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                          const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                          int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid, bool check_only) {
+  flvis_ctx* ctx = lc->ctx;
+  const std::string pre = std::string(what) + ": ";
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
+  flvis::Pipeline* pl = ctx->pipe;
+  if (!pl || pl->kfl.cap <= 0) return bad("the closer's context holds no tracker, or its keyframe log is off (flvis_keyframe_log_enable)");
+  if (pl->S != lc->S || pl->kfl.w != lc->w || pl->kfl.h != lc->h || pl->cfg.cam_type != lc->cam_type)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
+  if (lc->cam_type != 2) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig has no depth image");
+  if (!prm) return bad("NULL prm");
+  std::vector<int> range2;  // (first row of the pose database, stored keyframes) per listed sequence: the group checks of map_cloud
+  int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
+  if (rc != FLVIS_OK) return rc;
+  const int E = h_group_ptr[n_groups];
+  std::vector<double> cam5(5 * (size_t)std::max(E, 1));
+  for (int e = 0; e < E; e++) {
+    const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
+    if (first < 0 || first > lc->seq[s].n) return bad("a first keyframe outside [0, stored keyframes]");
+    const flvis_cfg& g = lc->cfgs[s];
+    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], g.depth_factor};
+    memcpy(&cam5[5 * (size_t)e], v, sizeof(v));
+  }
+  std::string why;
+  rc = flvis::dc_check_sampling(lc->w, lc->h, prm, E, cam5.data(), &why);
+  if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
+  if (!(leaf >= 0) || !std::isfinite(leaf) || min_points < 1 || out_cap < 0 || (!d_xyz && out_cap > 0))
+    return bad("leaf must be finite and >= 0, min_points >= 1, out_cap >= 0 with rows to write to");
+  if (check_only) return FLVIS_OK;
+  flvis::KfLogRec rec{};
+  int S = 0, cam = 0;
+  std::vector<long long> logged, dropped;
+  rc = flvis::kf_log_settle(ctx, what, rec, S, cam, logged, dropped);
+  if (rc != FLVIS_OK) return rc;
+  std::vector<int> eptr((size_t)n_groups + 1), img, pose, camv;
+  for (int g = 0; g < n_groups; g++) {
+    eptr[g] = (int)img.size();
+    for (int e = h_group_ptr[g]; e < h_group_ptr[g + 1]; e++) {
+      const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
+      const long long n = std::min<long long>(logged[s], (long long)lc->seq[s].n - first);
+      for (long long i = 0; i < n; i++) {
+        if (img.size() >= (size_t)INT_MAX) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "2^31 listed keyframes or more");
+        img.push_back((int)((long long)s * rec.cap + i));
+        pose.push_back((int)((long long)s * lc->maxkf + first + i));  // (first + i < stored <= maxkf)
+        camv.push_back(e);
+      }
+    }
+  }
+  eptr[n_groups] = (int)img.size();
+  return flvis::dc_cloud(ctx, what, reinterpret_cast<const uint16_t*>(rec.img1), rec.w, rec.h, lc->db_T, 7, n_groups, eptr.data(), img.data(),
+                         pose.data(), camv.data(), E, cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid);
+}
+
+int flvis_loop_closer_dense_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                  const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                                  int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  return lc_dense_cloud(lc, "loop_closer_dense_cloud", n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, d_npts,
+                        h_n_out, h_n_dropped, h_n_valid, false);
+}
+
+int flvis_loop_closer_dense_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                       const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
+                                       int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "loop_closer_dense_cloud_host";
+  int rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, h_xyz, nullptr, h_n_out, h_n_dropped,
+                          h_n_valid, true);
+  if (rc != FLVIS_OK) return rc;
+  float* d_xyz = nullptr;
+  int* d_npts = nullptr;
+  rc = flvis::mc_host_rows_alloc(lc->ctx, what, n_groups, out_cap, &d_xyz, &d_npts);
+  if (rc != FLVIS_OK) return rc;
+  rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr,
+                      h_n_out, h_n_dropped, h_n_valid, false);
+  if (rc != FLVIS_OK) return rc;
+  return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
 }
 
 // ---- keyframe stamps and whole trajectories in the map frame (include/flvis_hip.h; the rule and the kernels: lc_traj.hip) ---------------

@@ -3,7 +3,9 @@
 // The reference's LocalMapNodeletClass publishes /map_cloud (vo_localmap.cpp:335-377, :458-461) and sets up a pcl::VoxelGrid of 0.08 m that it
 // never runs.  The local map's own cloud is flvis_local_map_cloud (lm_cloud.hip), which ends in this call; the loop closer's database goes
 // through it as flvis_loop_closer_map_cloud.  The radix passes (mc_sort) and the call with landmark ids (mc_voxel_cloud) are shared with
-// lm_cloud.hip through map_cloud.hpp.
+// lm_cloud.hip through map_cloud.hpp.  The call is cut in three so that the dense cloud (depth_cloud.hip) can bring its own front end:
+// the front end (counts, offsets, keys: here k_mc_counts .. k_mc_keys), mc_work (the workspace of the call's points) and mc_tail
+// (everything from the byte table and the sort on).  A point enters the workspace through mc_put (map_cloud.hpp) in both front ends.
 //
 // Steps of one call (every cloud of the call goes through each of them together):
 //   k_mc_counts, k_mc_scan     the listed rows' clamped counts and their running sum: where each row's points start in canonical order
@@ -19,6 +21,8 @@
 // consecutive elements -- and from ranking equal digits inside a wave with eight ballots.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -40,9 +44,6 @@ constexpr int MC_TILE = MC_T * MC_ITEMS;     // 4096: the sort tile (flvis_hip_v
 constexpr int MC_WAVE_SPAN = 64 * MC_ITEMS;  // a wave's contiguous part of a tile
 constexpr int MC_MAX_BLK = 2048;             // sort workgroups per pass at most (8 per CU): bounds a row of the histogram table
 constexpr int MC_RB = 1024;                  // sorted positions per workgroup of the output kernels
-constexpr int MC_KEY_DIGITS = 8;
-constexpr uint64_t MC_DROPPED = 1ull << 63;  // key of a dropped point: behind every voxel of its cloud
-constexpr double MC_HALF_RANGE = 1048576.0;  // 2^20
 constexpr int MC_BYTES_PER_POINT = 2 * 8 + 2 * 4 + 24;  // two key buffers, two index buffers, the map-frame point
 constexpr int MC_BYTES_PER_ROW = 8 + 2 * 4;             // running sum, row, count (+ 24 per cloud)
 
@@ -61,15 +62,6 @@ FD int mc_cloud_of(const int* __restrict__ cstart, int n_clouds, uint32_t i) {
     else hi = mid;
   }
   return lo;
-}
-
-FD uint64_t mc_key(V3 p, double leaf) {
-  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return MC_DROPPED;
-  if (leaf == 0) return 0;
-  const double ix = floor(p.x / leaf), iy = floor(p.y / leaf), iz = floor(p.z / leaf);
-  if (!(ix >= -MC_HALF_RANGE && ix < MC_HALF_RANGE && iy >= -MC_HALF_RANGE && iy < MC_HALF_RANGE && iz >= -MC_HALF_RANGE && iz < MC_HALF_RANGE))
-    return MC_DROPPED;
-  return ((uint64_t)((long long)iz + (1 << 20)) << 42) | ((uint64_t)((long long)iy + (1 << 20)) << 21) | (uint64_t)((long long)ix + (1 << 20));
 }
 
 __global__ __launch_bounds__(256) void k_mc_counts(const int* __restrict__ rows, int n_entries, const int* __restrict__ d_count, int cap,
@@ -160,19 +152,9 @@ __global__ __launch_bounds__(256) void k_mc_keys(const int* __restrict__ rows, c
   const Q4 qi = q_conj(T.q);
   for (int lm = tid; lm < n; lm += 256) {
     const double* s = p3 + ((size_t)row * cap + lm) * 3;
-    const V3 p = q_rotate(qi, V3{s[0], s[1], s[2]} - T.t);
-    const uint64_t key = mc_key(p, leaf);
     const size_t i = base + lm;
-    keys[i] = key;
-    idx[i] = (uint32_t)i;
-    pts[3 * i] = p.x, pts[3 * i + 1] = p.y, pts[3 * i + 2] = p.z;
+    mc_put(T, qi, V3{s[0], s[1], s[2]}, leaf, i, keys, idx, pts, seen);
     if (id_rows) idc[i] = id_rows[(size_t)row * cap + lm];  // (mc_voxel_cloud: the points' ids, in canonical order like the points)
-    if (key == MC_DROPPED) {
-      seen[7 * 256 + 0x80] = 1;  // (a dropped point counts in the top byte alone: it must end up behind the voxels, nothing else)
-    } else {
-#pragma unroll
-      for (int d = 0; d < MC_KEY_DIGITS; d++) seen[d * 256 + (int)((key >> (8 * d)) & 255)] = 1;
-    }
   }
   __syncthreads();
 #pragma unroll
@@ -454,6 +436,122 @@ int mc_sort(flvis_ctx* ctx, const int* occ, uint64_t* const d_keys[2], uint32_t*
   return FLVIS_OK;
 }
 
+void mc_offsets(hipStream_t st, const int* d_cnt, long long n, long long* d_off, const int* d_eptr, int n_clouds, long long* d_cs64,
+                int* d_cstart) {
+  k_mc_scan<int, long long><<<1, 1024, 0, st>>>(d_cnt, n, d_off);
+  k_mc_cloud_starts<<<(n_clouds + 1 + 255) / 256, 256, 0, st>>>(d_off, d_eptr, n_clouds, d_cs64, d_cstart);
+}
+
+// per point: keys [2][N] | points [N][3] | indices [2][N]; tables: byte values [8][256] | histogram [256][nblk] + 1 | output counts
+int mc_work(flvis_ctx* ctx, const char* what, int N, bool ids, McWork& W) {
+  const std::string w = std::string(what) + ": ";
+  auto no_mem = [&]() {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, w + "device allocation failed");
+  };
+  int tiles_per_blk, nblk;
+  mc_tiling(N, tiles_per_blk, nblk);
+  W.n_chunks = (N + MC_RB - 1) / MC_RB;
+  W.pt_bytes = (size_t)N * MC_BYTES_PER_POINT;
+  W.tab_ints = (size_t)MC_KEY_DIGITS * 256 + 256 * (size_t)nblk + 257 + (size_t)W.n_chunks + 1;
+  uint8_t* const pb = (uint8_t*)ctx->scratch("mc_points", W.pt_bytes);
+  if (!pb) return no_mem();
+  W.occ = (int*)ctx->scratch("mc_tables", sizeof(int) * W.tab_ints);
+  if (!W.occ) return no_mem();
+  W.keys[0] = (uint64_t*)pb, W.keys[1] = (uint64_t*)pb + N;
+  W.pts = (double*)(W.keys[1] + N);
+  W.idx[0] = (uint32_t*)(W.pts + 3 * (size_t)N), W.idx[1] = W.idx[0] + N;
+  W.hist = (uint32_t*)(W.occ + MC_KEY_DIGITS * 256);
+  W.bsum = (int*)(W.hist + 256 * (size_t)nblk + 257);
+  const hipError_t e = hipMemsetAsync(W.occ, 0, sizeof(int) * MC_KEY_DIGITS * 256, ctx->stream);
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  W.idc = nullptr;  // the points' ids in canonical order (only for a caller that wants the rows' ids)
+  if (ids) {
+    W.idc = (long long*)ctx->scratch("mc_ids", sizeof(long long) * (size_t)N);
+    if (!W.idc) return no_mem();
+  }
+  return FLVIS_OK;
+}
+
+int mc_tail(flvis_ctx* ctx, const char* what, const McWork& W, int N, int n_clouds, const int* d_cstart, int* d_kend, const long long* cs,
+            double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, long long* d_id_out, int64_t* h_n_out, int64_t* h_n_dropped,
+            size_t rows_bytes) {
+  hipStream_t st = ctx->stream;
+  const int NC1 = n_clouds + 1, n_chunks = W.n_chunks;
+  int* const d_cg = d_kend + NC1;
+  const std::string ws = std::string(what) + ": sort", wr = std::string(what) + ": rows", wk = std::string(what) + ": keys";
+  int occ[MC_KEY_DIGITS * 256];
+  hipError_t e = hipMemcpyAsync(occ, W.occ, sizeof(occ), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, wk.c_str());
+  const auto t_sort = std::chrono::steady_clock::now();
+  int cur = 0, n_passes = 0, cloud_digits = 0;
+  const int rc = mc_sort(ctx, occ, W.keys, W.idx, N, n_clouds, d_cstart, cs, W.hist, &cur, &n_passes, &cloud_digits);
+  if (rc != FLVIS_OK) return rc;
+  auto t_rows = t_sort;
+  if (W.ms_sort_rows) {  // (a caller that times its stages: one more wait, behind the sort)
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, ws.c_str());
+    t_rows = std::chrono::steady_clock::now();
+    W.ms_sort_rows[0] = std::chrono::duration<double, std::milli>(t_rows - t_sort).count();
+  }
+  // ---- the rows
+  const McOut o{W.keys[cur], d_cstart, d_kend, n_clouds, leaf == 0 ? 1 : 0, min_points};
+  k_mc_bounds<<<(n_clouds + 255) / 256, 256, 0, st>>>(W.keys[cur], d_cstart, n_clouds, d_kend);
+  k_mc_flags<<<n_chunks, 256, 0, st>>>(o, N, W.bsum);
+  k_mc_scan<int, int><<<1, 1024, 0, st>>>(W.bsum, (long long)n_chunks, W.bsum);
+  k_mc_cloud_rank<<<NC1, 256, 0, st>>>(o, N, W.bsum, d_cg);
+  if (out_cap > 0) k_mc_emit<<<n_chunks, 256, 0, st>>>(o, N, W.idx[cur], W.pts, W.bsum, d_cg, out_cap, d_xyz, d_npts, W.idc, d_id_out);
+  MC_LAUNCH(ctx, wr.c_str());
+  std::vector<int> back(2 * (size_t)NC1);  // kend | cg (adjacent on the device)
+  e = hipMemcpyAsync(back.data(), d_kend, sizeof(int) * back.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return ctx->hip_fail(e, wr.c_str());
+  if (W.ms_sort_rows) W.ms_sort_rows[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rows).count();
+  for (int c = 0; c < n_clouds; c++) {
+    h_n_out[c] = (int64_t)back[(size_t)NC1 + c + 1] - back[(size_t)NC1 + c];
+    if (h_n_dropped) h_n_dropped[c] = cs[c + 1] - back[c];
+  }
+  ctx->mc_stats[0] = n_passes;
+  ctx->mc_stats[1] = MC_KEY_DIGITS + cloud_digits - n_passes;
+  ctx->mc_stats[2] = (int64_t)(W.pt_bytes + rows_bytes + sizeof(int) * W.tab_ints);
+  ctx->mc_stats[3] = N;
+  return FLVIS_OK;
+}
+
+// rows and counts of every cloud in one staging buffer of the context
+int mc_host_rows_alloc(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, float** d_xyz, int** d_npts) {
+  *d_xyz = nullptr, *d_npts = nullptr;
+  if (out_cap <= 0 || n_clouds <= 0) return FLVIS_OK;
+  const size_t rows = (size_t)n_clouds * (size_t)out_cap;
+  *d_xyz = (float*)ctx->scratch("mc_host_rows", rows * (3 * sizeof(float) + sizeof(int)));
+  if (!*d_xyz) {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+  }
+  *d_npts = (int*)(*d_xyz + 3 * rows);
+  return FLVIS_OK;
+}
+
+int mc_host_rows_fetch(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, const int64_t* h_n_out, const float* d_xyz,
+                       const int* d_npts, float* h_xyz, int* h_npts) {
+  hipError_t e = hipSuccess;
+  bool any = false;
+  for (int g = 0; g < n_clouds && e == hipSuccess; g++) {
+    const size_t n = (size_t)std::min<int64_t>(h_n_out[g], out_cap), at = (size_t)g * (size_t)out_cap;
+    if (n == 0) continue;
+    any = true;
+    e = hipMemcpyAsync(h_xyz + 3 * at, d_xyz + 3 * at, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && h_npts) e = hipMemcpyAsync(h_npts + at, d_npts + at, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  if (any || e != hipSuccess) {
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return ctx->hip_fail(e, what);
+  return FLVIS_OK;
+}
+
 int mc_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const double* d_T_c_w7, int n_rows, int cap, int n_clouds,
                    const int* h_cloud_ptr, const int* h_range2, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
                    const long long* d_id_rows, long long* d_id_out, int64_t* h_n_out, int64_t* h_n_dropped) {
@@ -509,8 +607,7 @@ int mc_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const
     return code;
   };
   k_mc_counts<<<(R + 255) / 256, 256, 0, st>>>(d_rows, R, d_count, cap, d_cnt);
-  k_mc_scan<int, long long><<<1, 1024, 0, st>>>(d_cnt, (long long)R, d_off);
-  k_mc_cloud_starts<<<(NC1 + 255) / 256, 256, 0, st>>>(d_off, d_eptr, n_clouds, d_cs64, d_cstart);
+  mc_offsets(st, d_cnt, (long long)R, d_off, d_eptr, n_clouds, d_cs64, d_cstart);
   e = hipGetLastError();
   if (e != hipSuccess) return fail_sync(ctx->hip_fail(e, "voxel_cloud: counts"));
   std::vector<long long> cs((size_t)NC1);
@@ -520,58 +617,14 @@ int mc_voxel_cloud(flvis_ctx* ctx, const double* d_p3, const int* d_count, const
   if (cs[n_clouds] > (long long)INT_MAX) return ctx->fail(FLVIS_ERR_CAPACITY, "voxel_cloud: 2^31 input points or more");
   const int N = (int)cs[n_clouds];
   if (N == 0) return FLVIS_OK;
-  // ---- per point: keys [2][N] | points [N][3] | indices [2][N]; tables: byte values [8][256] | histogram [256][nblk] + 1 | output counts
-  const int n_tiles = (N + MC_TILE - 1) / MC_TILE, tiles_per_blk = (n_tiles + MC_MAX_BLK - 1) / MC_MAX_BLK,
-            nblk = (n_tiles + tiles_per_blk - 1) / tiles_per_blk, n_chunks = (N + MC_RB - 1) / MC_RB;
-  const size_t pt_bytes = (size_t)N * MC_BYTES_PER_POINT, tab_ints = (size_t)MC_KEY_DIGITS * 256 + 256 * (size_t)nblk + 257 + (size_t)n_chunks + 1;
-  uint8_t* const pb = (uint8_t*)ctx->scratch("mc_points", pt_bytes);
-  if (!pb) return no_mem();
-  int* const d_occ = (int*)ctx->scratch("mc_tables", sizeof(int) * tab_ints);
-  if (!d_occ) return no_mem();
-  uint64_t* d_keys[2] = {(uint64_t*)pb, (uint64_t*)pb + N};
-  double* const d_pts = (double*)(d_keys[1] + N);
-  uint32_t* d_idx[2] = {(uint32_t*)(d_pts + 3 * (size_t)N), (uint32_t*)(d_pts + 3 * (size_t)N) + N};
-  uint32_t* const d_hist = (uint32_t*)(d_occ + MC_KEY_DIGITS * 256);
-  uint32_t* const d_tot = d_hist + 256 * (size_t)nblk;  // [257]
-  int* const d_bsum = (int*)(d_tot + 257);
-  e = hipMemsetAsync(d_occ, 0, sizeof(int) * MC_KEY_DIGITS * 256, st);
-  if (e != hipSuccess) return ctx->hip_fail(e, "voxel_cloud");
-  long long* d_idc = nullptr;  // the points' ids in canonical order (only for a caller that wants the rows' ids)
-  if (d_id_out) {
-    d_idc = (long long*)ctx->scratch("mc_ids", sizeof(long long) * (size_t)N);
-    if (!d_idc) return no_mem();
-  }
-  k_mc_keys<<<R, 256, 0, st>>>(d_rows, d_cnt, d_off, d_p3, d_T_c_w7, cap, leaf, d_keys[0], d_idx[0], d_pts, d_occ, d_idc ? d_id_rows : nullptr,
-                               d_idc);
-  MC_LAUNCH(ctx, "voxel_cloud: keys");
-  int occ[MC_KEY_DIGITS * 256];
-  e = hipMemcpyAsync(occ, d_occ, sizeof(occ), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return ctx->hip_fail(e, "voxel_cloud: keys");
-  int cur = 0, n_passes = 0, cloud_digits = 0;
-  rc = mc_sort(ctx, occ, d_keys, d_idx, N, n_clouds, d_cstart, cs.data(), d_hist, &cur, &n_passes, &cloud_digits);
+  McWork W;
+  rc = mc_work(ctx, "voxel_cloud", N, d_id_out != nullptr, W);
   if (rc != FLVIS_OK) return rc;
-  // ---- the rows
-  const McOut o{d_keys[cur], d_cstart, d_kend, n_clouds, leaf == 0 ? 1 : 0, min_points};
-  k_mc_bounds<<<(n_clouds + 255) / 256, 256, 0, st>>>(d_keys[cur], d_cstart, n_clouds, d_kend);
-  k_mc_flags<<<n_chunks, 256, 0, st>>>(o, N, d_bsum);
-  k_mc_scan<int, int><<<1, 1024, 0, st>>>(d_bsum, (long long)n_chunks, d_bsum);
-  k_mc_cloud_rank<<<NC1, 256, 0, st>>>(o, N, d_bsum, d_cg);
-  if (out_cap > 0) k_mc_emit<<<n_chunks, 256, 0, st>>>(o, N, d_idx[cur], d_pts, d_bsum, d_cg, out_cap, d_xyz, d_npts, d_idc, d_id_out);
-  MC_LAUNCH(ctx, "voxel_cloud: rows");
-  std::vector<int> back(2 * (size_t)NC1);  // kend | cg (adjacent on the device)
-  e = hipMemcpyAsync(back.data(), d_kend, sizeof(int) * back.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return ctx->hip_fail(e, "voxel_cloud: rows");
-  for (int c = 0; c < n_clouds; c++) {
-    h_n_out[c] = (int64_t)back[(size_t)NC1 + c + 1] - back[(size_t)NC1 + c];
-    if (h_n_dropped) h_n_dropped[c] = cs[c + 1] - back[c];
-  }
-  ctx->mc_stats[0] = n_passes;
-  ctx->mc_stats[1] = MC_KEY_DIGITS + cloud_digits - n_passes;
-  ctx->mc_stats[2] = (int64_t)(pt_bytes + rows_bytes + sizeof(int) * tab_ints);
-  ctx->mc_stats[3] = N;
-  return FLVIS_OK;
+  k_mc_keys<<<R, 256, 0, st>>>(d_rows, d_cnt, d_off, d_p3, d_T_c_w7, cap, leaf, W.keys[0], W.idx[0], W.pts, W.occ, W.idc ? d_id_rows : nullptr,
+                               W.idc);
+  MC_LAUNCH(ctx, "voxel_cloud: keys");
+  return mc_tail(ctx, "voxel_cloud", W, N, n_clouds, d_cstart, d_kend, cs.data(), leaf, min_points, out_cap, d_xyz, d_npts, d_id_out, h_n_out,
+                 h_n_dropped, rows_bytes);
 }
 
 }  // namespace flvis

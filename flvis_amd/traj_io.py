@@ -210,6 +210,16 @@ def load_gray(path):
         return np.asarray(im.convert("L"), dtype=np.uint8).copy()
 
 
+def load_second(path):
+    """the second image of a pair: a 16-bit PNG is a depth image (Z16, the D435i's aligned depth) and stays uint16 [h,w]; anything else
+    is the right camera's 8-bit image (load_gray)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode.startswith("I;16"):
+            return np.asarray(im, dtype=np.uint16).copy()
+    return load_gray(path)
+
+
 class EurocSequence:
     """An EuRoC ASL sequence folder (`<seq>/mav0/{cam0,cam1,imu0,state_groundtruth_estimate0}`): stereo pairs with equal
     stamps (what the reference's ExactTime synchroniser delivers, vo_tracking.cpp:308-319), the IMU samples between
@@ -238,7 +248,7 @@ class EurocSequence:
         for k in range(first, last):
             t = self.stamps_ns[k] * 1e-9
             sel = (ti > t_prev) & (ti <= t)
-            yield t, load_gray(self.files[k][0]), load_gray(self.files[k][1]), self.imu[sel]
+            yield t, load_gray(self.files[k][0]), load_second(self.files[k][1]), self.imu[sel]
             t_prev = t
 
 

@@ -1297,6 +1297,85 @@ int flvis_loop_closer_map_poses_host(flvis_loop_closer* lc, int n_jobs, const fl
 int flvis_loop_closer_map_trajectory(flvis_loop_closer* lc, int n, const int* h_stream, int first_frame, int n_frames, int mode,
                                      double* d_out_rows9, double* h_out_rows9, int* h_anchor);
 
+/* ---- a dense map from depth keyframes: back-project, voxel-filter on the device ---------------------------------------------------------
+ * (The reference's octomap feeder, src/octofeeder/octomap_feeder.cpp:18-80, turns the depth image of every /vo_kf message into a point
+ * cloud in the camera frame and hands it to octomap with the keyframe's pose.  Here the cloud goes straight into the voxel filter of
+ * flvis_hip_voxel_cloud, in the map frame, without the 24-byte camera-frame rows ever existing.)
+ * Input: d_depth [n_img][h][w] uint16, rows tightly packed (the keyframe log's img1 on depth rigs); d_T_c_w7 [n_img][7], the images'
+ *   T_c_w.  Clouds are concatenations of image ranges exactly as flvis_hip_voxel_cloud's row ranges: h_cloud_ptr [n_clouds + 1],
+ *   h_range2 [h_cloud_ptr[n_clouds]][2] = (first image, image count); an image may be in several ranges and clouds.  One camera per
+ *   RANGE: h_cam5 [ranges][5] = fx, fy, cx, cy, depth_factor.
+ * Sampling (flvis_depth_cloud_params): the pixels u = u0 + i * step_u < u1, v = v0 + j * step_v < v1 of every listed image.
+ * A sample -- the tracker's own depth rule and order of operations (recover3DPts_c_FromDepthImg as the frame chain evaluates it):
+ *   raw is read as UNSIGNED 16 bit; z = (float)((double)raw / depth_factor); the sample is valid iff (double)z >= z_min and
+ *   (double)z <= z_max; p_c = (((double)u - cx) * (double)z / fx, ((double)v - cy) * (double)z / fy, (double)z), evaluated left to right
+ *   in fp64 without contraction.  An invalid sample is not a point: it is counted nowhere but in its absence from h_n_valid, and
+ *   h_n_dropped keeps flvis_hip_voxel_cloud's meaning (a map-frame coordinate that is not finite or a voxel index outside +-2^20).
+ * Canonical order of a cloud's points: its ranges in the caller's order, images ascending within a range, then the image's valid samples
+ *   in raster order (v ascending, then u).
+ * RESULT: bit for bit what flvis_hip_voxel_cloud returns for rows that hold each listed image's valid p_c in canonical order under that
+ *   image's pose: the same transform, division-then-floor key, stable sort, sequential fp64 sums and rounding to float (both front ends
+ *   put a point through one device function).  Several clouds in one call give the bits of as many single calls; a second run gives
+ *   the same bits (the compaction is a wave64 ballot and prefix count with per-wave bases in LDS: no atomic decides a position).
+ *   With an identity pose, leaf = 0, step_u = step_v = 7, v0 = h / 2 - 22, v1 = h / 2 + 21, z_min = 0.5 and z_max = 6.5 the rows are the
+ *   points octomap_feeder.cpp:35-61 pushes into its cloud.
+ * leaf, min_points, out_cap, d_xyz [n_clouds][out_cap][3], d_npts (may be NULL), h_n_out, h_n_dropped (may be NULL): that call's.
+ *   h_n_valid [n_clouds] (may be NULL): the valid samples per cloud, the voxel call's input points.
+ * The call waits for its own counts as the voxel call does and for nothing else.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: a step < 1; a window that is empty or not inside the image (u1 <= 0 / v1 <= 0 stand
+ *   for the width / height); z limits that are not finite or z_min > z_max; a camera entry that is not finite or whose fx, fy or
+ *   depth_factor is 0; w <= 0 or h <= 0; a NULL d_depth, d_T_c_w7, h_cam5 or prm; and the argument errors of flvis_hip_voxel_cloud with
+ *   n_img for n_rows.  flvis_depth_cloud_check is the host part of these checks on its own (no context).
+ * FLVIS_ERR_CAPACITY: 2^31 valid samples or more in one call (or as many listed images times row chunks).
+ * Workspace: the context's, grown on demand and kept: flvis_hip_voxel_cloud's 48 bytes per VALID sample, 12 bytes per listed image and
+ *   row chunk (a chunk is about 4096 samples of whole sampled rows), 16 per listed image, 24 per cloud and the fixed 2.1 MB.  A failed
+ *   allocation returns FLVIS_ERR_HIP and leaves the context usable.  flvis_hip_voxel_cloud_stats reports a dense call like a voxel call.
+ * flvis_hip_depth_cloud_times: enable != 0 makes the context's later dense calls wait once more, behind the sort, and keep the wall-clock
+ *   milliseconds of their four stages; h_ms4 (may be NULL) = count, keys, sort, rows of the last such call. */
+typedef struct flvis_depth_cloud_params {
+  int u0, v0, u1, v1;   /* sampled window, half-open; u1 <= 0 / v1 <= 0: the image's width / height */
+  int step_u, step_v;   /* >= 1: samples u = u0 + i * step_u < u1, v = v0 + j * step_v < v1 */
+  double z_min, z_max;  /* metres, both inclusive */
+} flvis_depth_cloud_params;
+int flvis_hip_depth_cloud(flvis_ctx* ctx, const uint16_t* d_depth, const double* d_T_c_w7, int n_img, int w, int h, int n_clouds,
+                          const int* h_cloud_ptr /* [n_clouds + 1] */, const int* h_range2, const double* h_cam5,
+                          const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                          int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_depth_cloud_check(int n_img, int w, int h, int n_clouds, const int* h_cloud_ptr, const int* h_range2, const double* h_cam5,
+                            const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap);
+int flvis_hip_depth_cloud_times(flvis_ctx* ctx, int enable, double* h_ms4);
+/* The keyframe log as dense clouds: cloud c holds the logged keyframes of stream h_stream[c] (a stream may be listed more than once) --
+ * all of them, or with h_slice2 [n][2] = (first entry, count) the entries first .. first + count - 1 that are logged (a slice reaching
+ * past the log is cut, a negative first or count is refused).  Each depth image enters with its logged T_c_w, read out of the record in
+ * place, and with the intrinsics (P0) and depth_factor of the stream's OWN config (flvis_tracker_create_rigs).  No image is copied.
+ * Waits for the tracker's queued work.  Changes nothing in the log or the tracker: a run that made the call equals one that did not, bit
+ * for bit.  A stream with no entry gives h_n_out = 0.  The other arguments and the _host form: as flvis_loop_closer_map_cloud's.
+ * FLVIS_ERR_CONFIG: the tracker is not a depth rig.  FLVIS_ERR_INVALID_ARG: no tracker, the log is off, n <= 0, a stream out of range,
+ * a bad slice, NULL h_stream, prm or h_n_out, and the argument errors of flvis_hip_depth_cloud. */
+int flvis_keyframe_log_depth_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm,
+                                   double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out,
+                                   int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_keyframe_log_depth_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm,
+                                        double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
+                                        int64_t* h_n_dropped, int64_t* h_n_valid);
+/* The dense map in the closer's frame: groups are written as for flvis_loop_closer_map_cloud; cloud g holds, for each sequence s =
+ * h_seq[e] of the group in order, the logged keyframes i = 0 .. min(logged(s), stored(s) - first) - 1 of the tracker's stream s, entry i
+ * under the closer's STORED T_c_w of keyframe first + i, first = h_first_kf[e] (per listed sequence; NULL: 0, the case after one
+ * flvis_loop_closer_add_logged into an empty closer).  So after process, flvis_loop_closer_set_drift or flvis_loop_closer_merge the cloud
+ * is in the map or the anchor's frame.  The camera is the closer's config of the sequence.  The context and shape conditions are those of
+ * flvis_loop_closer_add_logged (FLVIS_ERR_CONFIG, FLVIS_ERR_INVALID_ARG) and the rig must be a depth rig (FLVIS_ERR_CONFIG); a first
+ * outside [0, stored(s)] is FLVIS_ERR_INVALID_ARG, like the group errors of flvis_loop_closer_map_cloud.  Waits for the tracker's queued
+ * work.
+ * No side effect a caller can observe: poses, drift, loops, similarity rows and events afterwards are bit for bit those of a closer that
+ * never made the call; a keyframe that was added and not yet processed stays pending; the query slots of localize are not touched; the
+ * log and the tracker are not changed. */
+int flvis_loop_closer_dense_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                  const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
+                                  int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_loop_closer_dense_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                       const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
+                                       int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,13 @@ file is then the voxel-filtered cloud; the reference's raw /map_cloud, point for
 --lm-cloud-points: the record's capacity in points (32 bytes each; default 2^22), which the device record needs up front; a run that
 outgrows it is reported as runs_dropped in the JSON line.  When the yaml sets the key and no file is named, the JSON line says so.
 
+--dense-cloud FILE.ply : (hip, depth rigs -- cam_type 2 -- with --batch) the dense map: every logged keyframe's depth image back-projected
+and voxel-filtered on the device, as ASCII PLY with the voxels' sample counts.  Every --dense-step'th pixel of every --dense-step'th row
+(default 7, the reference's octomap feeder) between 0.3 m and the config's depth range (dr_para[1]), one point per voxel of --leaf metres.
+With --loop-closing the keyframes enter with the closer's stored poses (flvis_loop_closer_dense_cloud: the map frame), otherwise with the
+logged ones (flvis_keyframe_log_depth_cloud).  The log then holds the whole run (one entry per frame at most; 3 bytes per pixel and
+entry) and is handed to the closer once, after the last chunk, instead of chunk by chunk.
+
 --batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
 keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
 device (flvis_loop_closer_add_logged: the images the tracker worked on, img0 after equalizeHist where the rig uses it, as the KeyFrame
@@ -80,6 +87,8 @@ def main():
     ap.add_argument("--lm-cloud-mode", choices=["all", "latest"], default="all")
     ap.add_argument("--lm-cloud-points", type=int, default=1 << 22)
     ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--dense-cloud", default=None)
+    ap.add_argument("--dense-step", type=int, default=7)
     ap.add_argument("--lc-traj-out", default=None)
     ap.add_argument("--lc-imu-out", default=None)
     ap.add_argument("--lc-traj-mode", choices=["anchor", "blend"], default="anchor")
@@ -96,6 +105,8 @@ def main():
         ap.error("--lm-cloud needs --local-map and --backend hip")
     if args.batch and (args.backend != "hip" or args.imu_out or args.lc_imu_out or args.batch < 0):
         ap.error("--batch N (N > 0) needs --backend hip and goes without --imu-out and --lc-imu-out")
+    if args.dense_cloud and not (args.batch and args.backend == "hip" and args.dense_step >= 1):
+        ap.error("--dense-cloud needs --backend hip, --batch N and --dense-step >= 1")
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -166,23 +177,32 @@ def main():
             closer = flvis_amd.LoopCloser(ctx, cfg, flvis_amd.load_lc_params(args.config), n_streams=1, max_keyframes=max(n, 1))
             if args.lc_stereo_unrect:
                 closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
+        if args.dense_cloud and cfg.cam_type != 2:
+            ap.error("--dense-cloud: the config's rig has no depth image (cam_type 2)")
         if args.batch:
-            trk.keyframe_log_enable(args.batch)
+            trk.keyframe_log_enable(max(n, 1) if args.dense_cloud else args.batch)  # (the dense map reads the whole run's log at the end)
             imu_type = {1: 1, 3: 0, 5: 2, 0: 0, 2: 2, 4: 3}[cfg.type_of_vi]
             dropped_logged, chunk = 0, []
 
-            def flush():
+            def flush(last=False):
                 """the chunk through run_steps; its keyframes from the log into the closer; the log cleared"""
                 nonlocal dropped_logged
-                if not chunk:
+                if not chunk and not (last and args.dense_cloud):
                     return
-                trk.run_steps(chunk, with_local_map=args.local_map)
+                if chunk:
+                    trk.run_steps(chunk, with_local_map=args.local_map)
+                if args.dense_cloud and not last:                              # (the log keeps the run; the closer gets it after the last chunk)
+                    ctx.synchronize()
+                    del chunk[:]
+                    return
                 info = trk.keyframe_log_info(0)
                 dropped_logged += info["dropped"]
                 if closer is not None:
                     kf_stamps.extend(trk.keyframe_log_get(0, i, images=False)["stamp"] for i in range(info["logged"]))
-                    lc_events.extend(r[0] for r in closer.add_logged(process=True, max_rounds=args.batch))
-                trk.keyframe_log_clear([0])
+                    rounds = max(info["logged"], 1) if args.dense_cloud else args.batch
+                    lc_events.extend(r[0] for r in closer.add_logged(process=True, max_rounds=rounds))
+                if not args.dense_cloud:
+                    trk.keyframe_log_clear([0])
                 del chunk[:]
         for t, i0, i1, imu in seq.frames(0, n):
             if args.batch:
@@ -206,7 +226,7 @@ def main():
                 lc_events.append(closer.process()[0])
                 kf_stamps.append(t)
         if args.batch:
-            flush()
+            flush(last=True)
         trk.write_trajectory(0, 0, n, args.out, 0)
         imu_rows = np.concatenate(imu_rows) if imu_rows else np.zeros((0, 11))
         if args.imu_out and len(imu_rows):
@@ -233,6 +253,14 @@ def main():
             xyz, npts, n_out, n_drop = closer.map_cloud([[0]], leaf=args.leaf)
             traj_io.write_ply(args.map_cloud, xyz[0], npts[0])
             map_cloud = {"points": int(n_out[0]), "dropped": int(n_drop[0]), "leaf": args.leaf}
+        dense_cloud = None
+        if args.dense_cloud:
+            sampling = dict(step=args.dense_step, z_min=0.3, z_max=float(cfg.dr_para[1]), leaf=args.leaf)
+            got = closer.dense_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_depth_cloud([0], **sampling)
+            traj_io.write_ply(args.dense_cloud, got[0][0], got[1][0])
+            dense_cloud = {"points": int(got[2][0]), "dropped": int(got[3][0]), "valid_samples": int(got[4][0]), "leaf": args.leaf,
+                           "step": args.dense_step, "keyframes": trk.keyframe_log_info(0)["logged"],
+                           "frame": "map" if closer is not None else "odometry"}
         lm_cloud = None
         if args.lm_cloud:
             trk.local_map_counts()                                             # (drains the keyframe queue: the last optimisations too)
@@ -252,6 +280,8 @@ def main():
             wants_cloud = flvis_amd.config_get_bool(args.config, "output_sparse_map")
         except flvis_amd.FlvisError:
             wants_cloud = False                                                # (a yaml without the key: the reference would refuse it)
+        if args.dense_cloud:
+            out["dense_cloud"] = dense_cloud
         if args.lm_cloud:
             out["local_map_cloud"] = lm_cloud
         elif wants_cloud:
