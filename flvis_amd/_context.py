@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
-from ._structs import LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, depth_cloud_params
+from ._structs import LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, dense_stereo_params, depth_cloud_params
 from ._vocfile import TrainedVocabulary
 
 
@@ -451,6 +451,26 @@ class Context:
         hn = npts.cpu().numpy() if want_npts else None
         return ([hx[c, :k[c]].copy() for c in range(nc)], [hn[c, :k[c]].copy() for c in range(nc)] if want_npts else None,
                 n_out[:nc].copy(), n_drop[:nc].copy(), n_valid[:nc].copy())
+
+    def dense_stereo(self, img0, img1, bf, depth_factor=1000.0, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, want_disp=True, want_z=True):
+        """flvis_hip_dense_stereo: img0, img1 uint8 [n_img, h, w] device tensors, a RECTIFIED pair per image (a point at column u of
+        img0 lies at u - d of img1).  bf (focal length times baseline, pixel-metres) and depth_factor (the Z16 unit): a number each for
+        every image, or one per image.  d_min (or a DenseStereoParams), n_disp, agg_r, uniq, lr_tol: the header's definition.
+        -> (disp16, z16): device tensors int16 [n_img, h, w] that hold the UNSIGNED 16-bit results (torch without uint16, as
+        depth_cloud reads them), None for an output not asked for."""
+        import torch
+        assert img0.is_cuda and img0.dtype == torch.uint8 and img0.is_contiguous() and img0.dim() == 3
+        assert img1.is_cuda and img1.dtype == torch.uint8 and img1.is_contiguous() and img1.shape == img0.shape
+        n_img, h, w = [int(x) for x in img0.shape]
+        bf, df = np.atleast_1d(np.asarray(bf, np.float64)), np.atleast_1d(np.asarray(depth_factor, np.float64))
+        n_cam = max(len(bf), len(df))
+        cam2 = np.ascontiguousarray(np.stack([np.broadcast_to(bf, n_cam), np.broadcast_to(df, n_cam)], axis=1))
+        prm = dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol)
+        disp = torch.empty((n_img, h, w), dtype=torch.int16, device=img0.device) if want_disp else None
+        z16 = torch.empty((n_img, h, w), dtype=torch.int16, device=img0.device) if want_z else None
+        self._check(self._lib.flvis_hip_dense_stereo(self._h, _ptr(img0), _ptr(img1), n_img, w, h, n_cam, _P(cam2, C.c_double), C.byref(prm),
+                                                     _ptr(disp), _ptr(z16)), "dense_stereo")
+        return disp, z16
 
     def depth_cloud_times(self, enable=True):
         """flvis_hip_depth_cloud_times: switch the stage timing of the dense calls on or off -> dict(count, keys, sort, rows) in

@@ -5,7 +5,7 @@ import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
 from ._structs import (FLVIS_LC_FIX_CAND, LC_ROW_WIDTH, LC_TRAJ_ANCHOR, FlvisCfg, FlvisImage, FlvisLcFix, FlvisLcFixIn, FlvisLcLink,
-                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams, cloud_rows, depth_cloud_params)
+                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams, cloud_rows, dense_stereo_params, depth_cloud_params)
 
 
 def loop_candidate(row, present, lcKFDist, lcKFMaxDist, lcNKFClosest, minScore):
@@ -335,7 +335,8 @@ class LoopCloser:
         k = [int(min(n, cap)) for n in n_out[:ng]]
         return ([hx[g, :k[g]].copy() for g in range(ng)], [hn[g, :k[g]].copy() for g in range(ng)], n_out[:ng].copy(), n_drop[:ng].copy())
 
-    def dense_cloud(self, groups, first_kf=None, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None, host=False):
+    def dense_cloud(self, groups, first_kf=None, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None, host=False,
+                    _stereo=None):
         """flvis_loop_closer_dense_cloud (depth rigs): per group one dense cloud of the tracker's logged depth keyframes of the group's
         sequences, logged entry i under the closer's stored T_c_w of keyframe first_kf + i -- the map frame after process, set_drift
         or merge.  groups: as map_cloud's; first_kf: per group a list with one first keyframe per sequence (None: 0 everywhere).
@@ -350,11 +351,12 @@ class LoopCloser:
         assert first is None or len(first) == len(seqs), "one first keyframe per listed sequence"
         prm = depth_cloud_params(window, step, z_min, z_max)
         n_out, n_drop, n_valid = (np.zeros(max(ng, 1), np.int64) for _ in range(3))
-        head = (self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), _P(first, C.c_int) if first is not None else None, C.byref(prm), leaf,
-                int(min_points))
+        what = "loop_closer_%s_cloud%s" % ("stereo" if _stereo else "dense", "_host" if host else "")
+        fn = getattr(self._lib, "flvis_" + what)
+        front = (C.byref(_stereo[0]), float(_stereo[1])) if _stereo else ()   # (the stereo forms: the matcher's parameters, depth_factor)
+        head = (self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), _P(first, C.c_int) if first is not None else None) + front + (
+            C.byref(prm), leaf, int(min_points))
         tail = (_P(n_out, C.c_int64), _P(n_drop, C.c_int64), _P(n_valid, C.c_int64))
-        fn, what = ((self._lib.flvis_loop_closer_dense_cloud_host, "loop_closer_dense_cloud_host") if host else
-                    (self._lib.flvis_loop_closer_dense_cloud, "loop_closer_dense_cloud"))
         if cap is None:                                      # a first call for the counts alone: the buffers then fit what comes
             self._ctx._check(fn(*head, 0, None, None, *tail), what)
             cap = int(max(list(n_out[:ng]) + [0]))
@@ -370,6 +372,12 @@ class LoopCloser:
             hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
         rows = cloud_rows(hx, hn, n_out, cap, ng)
         return rows + (n_out[:ng].copy(), n_drop[:ng].copy(), n_valid[:ng].copy())
+
+    def stereo_cloud(self, groups, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
+        """flvis_loop_closer_stereo_cloud (rectified stereo rigs, cam_type 0): dense_cloud on the Z16 images dense stereo
+        (Context.dense_stereo: d_min .. lr_tol, or a DenseStereoParams as d_min) makes of the tracker's logged pairs, bf from each sequence's
+        own config, depth_factor the Z16 unit.  **cloud: dense_cloud's arguments.  -> what that call returns."""
+        return self.dense_cloud(groups, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor), **cloud)
 
     def poses(self, stream=0, cap=None):
         cap = int(cap) if cap else self.max_keyframes      # (never fewer rows than the sequence can hold: no silent truncation)

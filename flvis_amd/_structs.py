@@ -173,6 +173,19 @@ def octomap_feeder_params(height):
     return DepthCloudParams(0, height // 2 - 22, 0, height // 2 + 21, 7, 7, 0.5, 6.5)
 
 
+class DenseStereoParams(C.Structure):
+    """flvis_dense_stereo_params of include/flvis_hip.h: the disparities d_min .. d_min + n_disp - 1, the box sum's radius, the uniqueness
+    margin in per cent and the left-right tolerance in px (-1: no check) of flvis_hip_dense_stereo."""
+    _fields_ = [("d_min", C.c_int), ("n_disp", C.c_int), ("agg_r", C.c_int), ("uniq", C.c_int), ("lr_tol", C.c_int)]
+
+
+def dense_stereo_params(d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1):
+    """-> DenseStereoParams (d_min may be one already)."""
+    if isinstance(d_min, DenseStereoParams):
+        return d_min
+    return DenseStereoParams(int(d_min), int(n_disp), int(agg_r), int(uniq), int(lr_tol))
+
+
 def cloud_rows(xyz, npts, n_out, cap, n):
     """the rows a cloud call wrote (arrays [n, cap, ...]) as per-cloud numpy arrays of min(n_out, cap) rows"""
     k = [int(min(c, cap)) for c in n_out[:n]]

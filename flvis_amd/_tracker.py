@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._loader import FlvisError, _P, _ptr
-from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut, cloud_rows, depth_cloud_params
+from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut, cloud_rows, dense_stereo_params, depth_cloud_params
 
 
 class Tracker:
@@ -441,7 +441,7 @@ class Tracker:
         return dict(logged=int(v[0]), dropped=int(v[1]), capacity=int(v[2]))
 
     def keyframe_log_depth_cloud(self, streams, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, min_points=1, cap=None, host=False,
-                                 slices=None):
+                                 slices=None, _stereo=None):
         """flvis_keyframe_log_depth_cloud (depth rigs): per listed stream one dense cloud of its logged keyframes' depth images, each
         under its logged T_c_w and the stream's own camera, voxel-filtered on the device (leaf = 0: every valid sample).  window / step /
         z_min / z_max: Context.depth_cloud's.  slices: per stream (first entry, count), None: every entry.  cap: rows per stream
@@ -455,10 +455,11 @@ class Tracker:
         assert sli is None or len(sli) == n + 1, "one slice per listed stream"
         prm = depth_cloud_params(window, step, z_min, z_max)
         n_out, n_drop, n_valid = (np.zeros(max(n, 1), np.int64) for _ in range(3))
-        head = (self.ctx._h, n, _P(arr, C.c_int), _P(sli, C.c_int) if sli is not None else None, C.byref(prm), leaf, int(min_points))
+        what = "keyframe_log_%s_cloud%s" % ("stereo" if _stereo else "depth", "_host" if host else "")
+        fn = getattr(self.lib, "flvis_" + what)
+        front = (C.byref(_stereo[0]), float(_stereo[1])) if _stereo else ()   # (the stereo forms: the matcher's parameters, depth_factor)
+        head = (self.ctx._h, n, _P(arr, C.c_int), _P(sli, C.c_int) if sli is not None else None) + front + (C.byref(prm), leaf, int(min_points))
         tail = (_P(n_out, C.c_int64), _P(n_drop, C.c_int64), _P(n_valid, C.c_int64))
-        fn, what = ((self.lib.flvis_keyframe_log_depth_cloud_host, "keyframe_log_depth_cloud_host") if host else
-                    (self.lib.flvis_keyframe_log_depth_cloud, "keyframe_log_depth_cloud"))
         if cap is None:
             self.ctx._check(fn(*head, 0, None, None, *tail), what)
             cap = int(max(list(n_out[:n]) + [0]))
@@ -474,6 +475,25 @@ class Tracker:
             hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
         rows = cloud_rows(hx, hn, n_out, cap, n)
         return rows + (n_out[:n].copy(), n_drop[:n].copy(), n_valid[:n].copy())
+
+    def keyframe_log_stereo_cloud(self, streams, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
+        """flvis_keyframe_log_stereo_cloud (rectified stereo rigs, cam_type 0): keyframe_log_depth_cloud on the Z16 images dense stereo
+        (Context.dense_stereo: d_min .. lr_tol, or a DenseStereoParams as d_min) makes of the logged pairs, bf from each stream's own
+        config, depth_factor the Z16 unit.  **cloud: keyframe_log_depth_cloud's arguments.  -> what that call returns."""
+        return self.keyframe_log_depth_cloud(streams, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor), **cloud)
+
+    def keyframe_log_stereo_z16(self, entries, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0):
+        """flvis_keyframe_log_stereo_z16: the Z16 depth image dense stereo makes of the logged pairs entries = [(stream, index), ..]
+        -> a device tensor int16 [n, h, w] that holds the UNSIGNED 16-bit values (0: invalid); queued on the context's stream."""
+        import torch
+        ent = np.ascontiguousarray(list(entries) + [(0, 0)], np.int32).reshape(-1, 2)
+        n = len(ent) - 1
+        st, ix = np.ascontiguousarray(ent[:, 0]), np.ascontiguousarray(ent[:, 1])
+        prm = dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol)
+        z = torch.empty((max(n, 1), int(self.cfg.image_height), int(self.cfg.image_width)), dtype=torch.int16, device=self.ctx.device)
+        self.ctx._check(self.lib.flvis_keyframe_log_stereo_z16(self.ctx._h, n, _P(st, C.c_int), _P(ix, C.c_int), C.byref(prm), float(depth_factor),
+                                                               _ptr(z)), "keyframe_log_stereo_z16")
+        return z[:n]
 
     def keyframe_log_get(self, stream, index, cap=2048, images=True):
         """flvis_keyframe_log_get: logged keyframe `index` of the stream, a dict like keyframe_msg's."""

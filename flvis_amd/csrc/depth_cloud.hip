@@ -17,6 +17,9 @@
 // Loads: a lane reads one 16-bit pixel; with step_u == 1 a wave reads 128 contiguous bytes, with step_u == 7 it touches 7 lines of 128
 // bytes for 64 pixels.  Reading whole row segments instead would cut the lines touched but the kernel is bound by what it WRITES (36
 // bytes per valid sample); profiles/r25_depth_cloud.md has the figures.
+// A second image layout (DcSamp::packed) serves the stereo forms (flvis_keyframe_log_stereo_cloud, flvis_loop_closer_stereo_cloud): the
+// Z16 values dense_stereo.hip computes are kept at the samples alone, [item][nv][nu], so a sample is read at its own index and still
+// back-projected from its pixel.  Everything else -- lists, poses read in place, counts, keys, the tail -- is the depth-rig path.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +32,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "dense_stereo.hpp"
 #include "dev_math.hpp"
 #include "kf_log.hpp"
 #include "map_cloud.hpp"
@@ -45,6 +49,8 @@ constexpr int DC_CHUNK = 4096;  // samples per workgroup, in whole sampled rows 
 struct DcSamp {
   int u0, v0, su, sv, nu, nv, chunk_rows, chunks, w, h;
   double z_min, z_max;
+  int packed;  // the images hold the samples alone, [nv][nu] (the stereo forms: dense_stereo.hip writes them so), not [h][w]
+  __host__ __device__ size_t img_px() const { return packed ? (size_t)nu * nv : (size_t)w * h; }
 };
 
 // the call's listed images ("items"), cloud after cloud in the caller's order
@@ -62,11 +68,12 @@ FD bool dc_valid(uint16_t raw, double depth_factor, const DcSamp& s, float& z) {
   return (double)z >= s.z_min && (double)z <= s.z_max;
 }
 
-// sample j of chunk c (raster order inside the chunk): its pixel
-FD void dc_pixel(const DcSamp& s, int c, int j, int& u, int& v) {
-  const int jr = j / s.nu, ji = j - jr * s.nu;
+// sample j of chunk c (raster order inside the chunk): its pixel -> where the image holds it
+FD size_t dc_pixel(const DcSamp& s, int c, int j, int& u, int& v) {
+  const int jr = j / s.nu, ji = j - jr * s.nu, iv = c * s.chunk_rows + jr;
   u = s.u0 + ji * s.su;
-  v = s.v0 + (c * s.chunk_rows + jr) * s.sv;
+  v = s.v0 + iv * s.sv;
+  return s.packed ? (size_t)iv * s.nu + ji : (size_t)v * s.w + u;
 }
 FD int dc_chunk_samples(const DcSamp& s, int c) { return (min(s.nv, (c + 1) * s.chunk_rows) - c * s.chunk_rows) * s.nu; }
 
@@ -75,7 +82,7 @@ __global__ __launch_bounds__(DC_T) void k_dc_count(DcItems it, DcSamp s, int* __
   __shared__ int wsum[DC_T / 64];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int e = blockIdx.x / s.chunks, c = blockIdx.x - e * s.chunks;
-  const uint16_t* img = it.depth + (size_t)it.img[e] * s.w * s.h;
+  const uint16_t* img = it.depth + (size_t)it.img[e] * s.img_px();
   const double df = it.cam5[5 * (size_t)it.cam[e] + 4];
   const int n = dc_chunk_samples(s, c);
   int mine = 0;  // (lane 0: the wave's count)
@@ -85,8 +92,8 @@ __global__ __launch_bounds__(DC_T) void k_dc_count(DcItems it, DcSamp s, int* __
     if (j < n) {
       int u, v;
       float z;
-      dc_pixel(s, c, j, u, v);
-      f = dc_valid(img[(size_t)v * s.w + u], df, s, z);
+      const size_t at = dc_pixel(s, c, j, u, v);
+      f = dc_valid(img[at], df, s, z);
     }
     mine += __popcll(__ballot(f));
   }
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(DC_T) void k_dc_keys(DcItems it, DcSamp s, const in
   for (int i = t; i < MC_KEY_DIGITS * 256; i += DC_T) seen[i] = 0;
   __syncthreads();
   const int e = blockIdx.x / s.chunks, c = blockIdx.x - e * s.chunks;
-  const uint16_t* img = it.depth + (size_t)it.img[e] * s.w * s.h;
+  const uint16_t* img = it.depth + (size_t)it.img[e] * s.img_px();
   const double* cam = it.cam5 + 5 * (size_t)it.cam[e];
   const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], df = cam[4];
   const SE3d T = load_pose7(it.pose7 + (size_t)it.pose[e] * it.pose_stride);
@@ -125,8 +132,8 @@ __global__ __launch_bounds__(DC_T) void k_dc_keys(DcItems it, DcSamp s, const in
     int u = 0, v = 0;
     float z = 0.f;
     if (j < n) {
-      dc_pixel(s, c, j, u, v);
-      f = dc_valid(img[(size_t)v * s.w + u], df, s, z);
+      const size_t at = dc_pixel(s, c, j, u, v);
+      f = dc_valid(img[at], df, s, z);
     }
     const unsigned long long bal = __ballot(f);
     if (lane == 0) wsum[w] = __popcll(bal);
@@ -169,6 +176,7 @@ int dc_resolve(int w, int h, const flvis_depth_cloud_params* prm, DcSamp& s, std
   s.chunk_rows = std::max(1, DC_CHUNK / s.nu);
   s.chunks = (s.nv + s.chunk_rows - 1) / s.chunk_rows;
   s.z_min = prm->z_min, s.z_max = prm->z_max;
+  s.packed = 0;
   return FLVIS_OK;
 }
 
@@ -191,10 +199,38 @@ int dc_check_sampling(int w, int h, const flvis_depth_cloud_params* prm, int n_c
   return rc;
 }
 
+int dc_grid(int w, int h, const flvis_depth_cloud_params* prm, DsGrid* g) {
+  DcSamp s;
+  std::string why;
+  const int rc = dc_resolve(w, h, prm, s, why);
+  if (rc == FLVIS_OK) *g = DsGrid{s.u0, s.v0, s.su, s.sv, s.nu, s.nv};
+  return rc;
+}
+
+int dc_stereo_samples(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const std::vector<int>& slot, const std::vector<int>& cam,
+                      const double* h_cam2, const flvis_dense_stereo_params* sprm, const flvis_depth_cloud_params* prm, const uint16_t** d_z,
+                      std::vector<int>& iota) {
+  DsGrid g;
+  int rc = dc_grid(rec.w, rec.h, prm, &g);
+  if (rc != FLVIS_OK) return ctx->fail(rc, std::string(what) + ": bad sampling");
+  const size_t R = slot.size();
+  iota.resize(R);
+  std::vector<double> cam2(2 * std::max<size_t>(R, 1));
+  for (size_t e = 0; e < R; e++) iota[e] = (int)e, cam2[2 * e] = h_cam2[2 * (size_t)cam[e]], cam2[2 * e + 1] = h_cam2[2 * (size_t)cam[e] + 1];
+  uint16_t* z = (uint16_t*)ctx->scratch("ds_z16", 2 * std::max<size_t>(R, 1) * g.nu * g.nv);
+  if (!z) {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+  }
+  *d_z = z;
+  if (R == 0) return FLVIS_OK;
+  return ds_run(ctx, what, rec.img0, rec.img1, (int)R, rec.w, rec.h, (int)R, cam2.data(), sprm, nullptr, z, slot.data(), &g);
+}
+
 int dc_cloud(flvis_ctx* ctx, const char* what, const uint16_t* d_depth, int w, int h, const double* d_pose, size_t pose_stride, int n_clouds,
              const int* h_eptr, const int* h_img, const int* h_pose, const int* h_cam, int n_cams, const double* h_cam5,
              const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out,
-             int64_t* h_n_dropped, int64_t* h_n_valid) {
+             int64_t* h_n_dropped, int64_t* h_n_valid, bool packed) {
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
   if (!d_depth || !d_pose || !h_n_out || n_clouds <= 0 || !h_eptr) return bad("a NULL required pointer or no cloud");
@@ -207,6 +243,7 @@ int dc_cloud(flvis_ctx* ctx, const char* what, const uint16_t* d_depth, int w, i
   int rc = dc_check_sampling(w, h, prm, n_cams, h_cam5, &why);
   if (rc == FLVIS_OK) rc = dc_resolve(w, h, prm, s, why);
   if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
+  s.packed = packed ? 1 : 0;
   const int R = h_eptr[n_clouds], NC1 = n_clouds + 1;
   for (int c = 0; c < n_clouds; c++) {
     h_n_out[c] = 0;
@@ -320,25 +357,29 @@ int dc_check_public(int n_img, int w, int h, int n_clouds, const int* h_cloud_pt
 // flvis_keyframe_log_depth_cloud: the refusals, then (unless check_only) the call
 int kfl_depth_cloud(flvis_ctx* ctx, const char* what, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm,
                     double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped,
-                    int64_t* h_n_valid, bool check_only) {
+                    int64_t* h_n_valid, bool check_only, const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0) {
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
   Pipeline* pl = ctx->pipe;
   if (!pl) return bad("no tracker (flvis_tracker_create)");
-  if (pl->cfg.cam_type != CAM_DEPTH) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig has no depth image");
+  if (!sprm && pl->cfg.cam_type != CAM_DEPTH) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig has no depth image");
+  if (sprm && pl->cfg.cam_type != CAM_STEREO_RECT) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
   if (pl->kfl.cap <= 0) return bad("the keyframe log is off (flvis_keyframe_log_enable)");
   if (n <= 0 || !h_stream || !h_n_out || !prm) return bad("bad stream list, or a NULL prm or h_n_out");
-  std::vector<double> cam5(5 * (size_t)n);
+  std::vector<double> cam5(5 * (size_t)n), cam2(2 * (size_t)n);
   for (int c = 0; c < n; c++) {
     const int s = h_stream[c];
     if (s < 0 || s >= pl->S) return bad("stream out of range");
     if (h_slice2 && (h_slice2[2 * c] < 0 || h_slice2[2 * c + 1] < 0)) return bad("a negative slice");
     const flvis_cfg& g = pl->cfgs[s];  // (rig_from_cfg: the intrinsics the tracker itself back-projects with)
-    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], g.depth_factor};
+    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], sprm ? stereo_df : g.depth_factor};
     memcpy(&cam5[5 * (size_t)c], v, sizeof(v));
+    cam2[2 * (size_t)c] = -g.P1[3], cam2[2 * (size_t)c + 1] = stereo_df;
   }
   std::string why;
-  int rc = dc_check_sampling(pl->kfl.w, pl->kfl.h, prm, n, cam5.data(), &why);
+  int rc = FLVIS_OK;
+  for (int c = 0; sprm && rc == FLVIS_OK && c < n; c++) rc = ds_check(1, pl->kfl.w, pl->kfl.h, 1, &cam2[2 * (size_t)c], sprm, &why);
+  if (rc == FLVIS_OK) rc = dc_check_sampling(pl->kfl.w, pl->kfl.h, prm, n, cam5.data(), &why);
   if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
   if (!(leaf >= 0) || !std::isfinite(leaf) || min_points < 1 || out_cap < 0 || (!d_xyz && out_cap > 0))
     return bad("leaf must be finite and >= 0, min_points >= 1, out_cap >= 0 with rows to write to");
@@ -361,6 +402,14 @@ int kfl_depth_cloud(flvis_ctx* ctx, const char* what, int n, const int* h_stream
   eptr[n] = (int)img.size();
   static_assert(offsetof(KeyFrameDev, T_c_w) % 8 == 0 && sizeof(KeyFrameDev) % 8 == 0, "the logged poses are read in place as rows of doubles");
   const double* d_pose = reinterpret_cast<const double*>(reinterpret_cast<const char*>(rec.kf) + offsetof(KeyFrameDev, T_c_w));
+  if (sprm) {
+    const uint16_t* d_z = nullptr;
+    std::vector<int> iota;
+    rc = dc_stereo_samples(ctx, what, rec, img, cam, cam2.data(), sprm, prm, &d_z, iota);
+    if (rc != FLVIS_OK) return rc;
+    return dc_cloud(ctx, what, d_z, rec.w, rec.h, d_pose, sizeof(KeyFrameDev) / 8, n, eptr.data(), iota.data(), img.data(), cam.data(), n,
+                    cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid, true);
+  }
   return dc_cloud(ctx, what, reinterpret_cast<const uint16_t*>(rec.img1), rec.w, rec.h, d_pose, sizeof(KeyFrameDev) / 8, n, eptr.data(), img.data(),
                   img.data(), cam.data(), n, cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid);
 }
@@ -421,6 +470,67 @@ int flvis_keyframe_log_depth_cloud_host(flvis_ctx* ctx, int n, const int* h_stre
                        h_n_valid, false);
   if (rc != FLVIS_OK) return rc;
   return flvis::mc_host_rows_fetch(ctx, what, n, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
+}
+
+int flvis_keyframe_log_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                    double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                    float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  if (!sprm) return ctx->fail(FLVIS_ERR_INVALID_ARG, "keyframe_log_stereo_cloud: NULL stereo params");
+  return kfl_depth_cloud(ctx, "keyframe_log_stereo_cloud", n, h_stream, h_slice2, prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out,
+                         h_n_dropped, h_n_valid, false, sprm, depth_factor);
+}
+
+int flvis_keyframe_log_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                         double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                         float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "keyframe_log_stereo_cloud_host";
+  if (!sprm) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": NULL stereo params");
+  int rc = kfl_depth_cloud(ctx, what, n, h_stream, h_slice2, prm, leaf, min_points, out_cap, h_xyz, nullptr, h_n_out, h_n_dropped, h_n_valid, true,
+                           sprm, depth_factor);
+  if (rc != FLVIS_OK) return rc;
+  float* d_xyz = nullptr;
+  int* d_npts = nullptr;
+  rc = flvis::mc_host_rows_alloc(ctx, what, n, out_cap, &d_xyz, &d_npts);
+  if (rc != FLVIS_OK) return rc;
+  rc = kfl_depth_cloud(ctx, what, n, h_stream, h_slice2, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr, h_n_out, h_n_dropped,
+                       h_n_valid, false, sprm, depth_factor);
+  if (rc != FLVIS_OK) return rc;
+  return flvis::mc_host_rows_fetch(ctx, what, n, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
+}
+
+int flvis_keyframe_log_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* sprm,
+                                  double depth_factor, uint16_t* d_z16) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "keyframe_log_stereo_z16";
+  const std::string pre = std::string(what) + ": ";
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
+  Pipeline* pl = ctx->pipe;
+  if (!pl) return bad("no tracker (flvis_tracker_create)");
+  if (pl->cfg.cam_type != CAM_STEREO_RECT) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
+  if (pl->kfl.cap <= 0) return bad("the keyframe log is off (flvis_keyframe_log_enable)");
+  if (n <= 0 || !h_stream || !h_index || !sprm || !d_z16) return bad("no entry, or a NULL h_stream, h_index, prm or d_z16");
+  std::vector<double> cam2(2 * (size_t)n);
+  std::string why;
+  for (int i = 0; i < n; i++) {
+    const int s = h_stream[i];
+    if (s < 0 || s >= pl->S) return bad("stream out of range");
+    cam2[2 * (size_t)i] = -pl->cfgs[s].P1[3], cam2[2 * (size_t)i + 1] = depth_factor;
+    const int rc = ds_check(1, pl->kfl.w, pl->kfl.h, 1, &cam2[2 * (size_t)i], sprm, &why);
+    if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
+  }
+  KfLogRec rec{};
+  int S = 0, cam_type = 0;
+  std::vector<long long> logged, dropped;
+  int rc = kf_log_settle(ctx, what, rec, S, cam_type, logged, dropped);
+  if (rc != FLVIS_OK) return rc;
+  std::vector<int> slot((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (h_index[i] < 0 || h_index[i] >= logged[h_stream[i]]) return bad("an entry that is not logged");
+    slot[i] = (int)((long long)h_stream[i] * rec.cap + h_index[i]);
+  }
+  return ds_run(ctx, what, rec.img0, rec.img1, n, rec.w, rec.h, n, cam2.data(), sprm, nullptr, d_z16, slot.data(), nullptr);
 }
 
 }  // extern "C"

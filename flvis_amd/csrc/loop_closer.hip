@@ -42,6 +42,7 @@
 
 #include "../../include/flvis_hip.h"
 #include "ctx.hpp"
+#include "dense_stereo.hpp"
 #include "kf_log.hpp"
 #include "lc_traj.hpp"
 #include "loop_kernels.hpp"
@@ -1422,7 +1423,8 @@ int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const 
 // database and the sequences' configs; writes nothing of the closer's, the log's or the tracker's.
 static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
                           const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
-                          int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid, bool check_only) {
+                          int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid, bool check_only,
+                          const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0) {
   flvis_ctx* ctx = lc->ctx;
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
@@ -1430,21 +1432,27 @@ static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups,
   if (!pl || pl->kfl.cap <= 0) return bad("the closer's context holds no tracker, or its keyframe log is off (flvis_keyframe_log_enable)");
   if (pl->S != lc->S || pl->kfl.w != lc->w || pl->kfl.h != lc->h || pl->cfg.cam_type != lc->cam_type)
     return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
-  if (lc->cam_type != 2) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig has no depth image");
+  if (!sprm && lc->cam_type != 2) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig has no depth image");
+  if (sprm && lc->cam_type != 0) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig is no rectified stereo pair (cam_type 0)");
   if (!prm) return bad("NULL prm");
   std::vector<int> range2;  // (first row of the pose database, stored keyframes) per listed sequence: the group checks of map_cloud
   int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
   if (rc != FLVIS_OK) return rc;
   const int E = h_group_ptr[n_groups];
-  std::vector<double> cam5(5 * (size_t)std::max(E, 1));
+  std::vector<double> cam5(5 * (size_t)std::max(E, 1)), cam2(2 * (size_t)std::max(E, 1));
+  std::string why;
   for (int e = 0; e < E; e++) {
     const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
     if (first < 0 || first > lc->seq[s].n) return bad("a first keyframe outside [0, stored keyframes]");
     const flvis_cfg& g = lc->cfgs[s];
-    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], g.depth_factor};
+    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], sprm ? stereo_df : g.depth_factor};
     memcpy(&cam5[5 * (size_t)e], v, sizeof(v));
+    cam2[2 * (size_t)e] = -g.P1[3], cam2[2 * (size_t)e + 1] = stereo_df;
   }
-  std::string why;
+  const double unit_cam[2] = {1.0, 1.0};
+  rc = sprm ? flvis::ds_check(1, lc->w, lc->h, 1, unit_cam, sprm, &why) : FLVIS_OK;  // (the params alone, then each sequence's camera)
+  for (int e = 0; sprm && rc == FLVIS_OK && e < E; e++) rc = flvis::ds_check(1, lc->w, lc->h, 1, &cam2[2 * (size_t)e], sprm, &why);
+  if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
   rc = flvis::dc_check_sampling(lc->w, lc->h, prm, E, cam5.data(), &why);
   if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
   if (!(leaf >= 0) || !std::isfinite(leaf) || min_points < 1 || out_cap < 0 || (!d_xyz && out_cap > 0))
@@ -1470,6 +1478,14 @@ static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups,
     }
   }
   eptr[n_groups] = (int)img.size();
+  if (sprm) {
+    const uint16_t* d_z = nullptr;
+    std::vector<int> iota;
+    rc = flvis::dc_stereo_samples(ctx, what, rec, img, camv, cam2.data(), sprm, prm, &d_z, iota);
+    if (rc != FLVIS_OK) return rc;
+    return flvis::dc_cloud(ctx, what, d_z, rec.w, rec.h, lc->db_T, 7, n_groups, eptr.data(), iota.data(), pose.data(), camv.data(), E,
+                           cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid, true);
+  }
   return flvis::dc_cloud(ctx, what, reinterpret_cast<const uint16_t*>(rec.img1), rec.w, rec.h, lc->db_T, 7, n_groups, eptr.data(), img.data(),
                          pose.data(), camv.data(), E, cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid);
 }
@@ -1496,6 +1512,36 @@ int flvis_loop_closer_dense_cloud_host(flvis_loop_closer* lc, int n_groups, cons
   if (rc != FLVIS_OK) return rc;
   rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr,
                       h_n_out, h_n_dropped, h_n_valid, false);
+  if (rc != FLVIS_OK) return rc;
+  return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
+}
+
+int flvis_loop_closer_stereo_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                   const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm, double leaf,
+                                   int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped,
+                                   int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  if (!sprm) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_stereo_cloud: NULL stereo params");
+  return lc_dense_cloud(lc, "loop_closer_stereo_cloud", n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, d_npts,
+                        h_n_out, h_n_dropped, h_n_valid, false, sprm, depth_factor);
+}
+
+int flvis_loop_closer_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                        const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                        double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
+                                        int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "loop_closer_stereo_cloud_host";
+  if (!sprm) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": NULL stereo params");
+  int rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, h_xyz, nullptr, h_n_out, h_n_dropped,
+                          h_n_valid, true, sprm, depth_factor);
+  if (rc != FLVIS_OK) return rc;
+  float* d_xyz = nullptr;
+  int* d_npts = nullptr;
+  rc = flvis::mc_host_rows_alloc(lc->ctx, what, n_groups, out_cap, &d_xyz, &d_npts);
+  if (rc != FLVIS_OK) return rc;
+  rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr,
+                      h_n_out, h_n_dropped, h_n_valid, false, sprm, depth_factor);
   if (rc != FLVIS_OK) return rc;
   return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
 }

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/flvis_hip.h"
 #include "dev_math.hpp"
@@ -90,7 +91,14 @@ int dc_check_sampling(int w, int h, const flvis_depth_cloud_params* prm, int n_c
 int dc_cloud(flvis_ctx* ctx, const char* what, const uint16_t* d_depth, int w, int h, const double* d_pose, size_t pose_stride, int n_clouds,
              const int* h_eptr, const int* h_img, const int* h_pose, const int* h_cam, int n_cams, const double* h_cam5,
              const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out,
-             int64_t* h_n_dropped, int64_t* h_n_valid);
+             int64_t* h_n_dropped, int64_t* h_n_valid, bool packed = false);
+// The stereo forms (flvis_keyframe_log_stereo_cloud, flvis_loop_closer_stereo_cloud): the Z16 values of the log entries `slot` (item e:
+// camera h_cam2[2 * cam[e]] = bf, depth_factor) at the samples of `prm` ALONE, 2 bytes per sample, in the context's workspace -- the images
+// dc_cloud reads with packed = true and the image list `iota` (item e: image e)
+struct KfLogRec;
+int dc_stereo_samples(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const std::vector<int>& slot, const std::vector<int>& cam,
+                      const double* h_cam2, const flvis_dense_stereo_params* sprm, const flvis_depth_cloud_params* prm, const uint16_t** d_z,
+                      std::vector<int>& iota);
 // _host forms: rows of n_clouds clouds staged in the context's `name` buffer, then copied out (rows below min(h_n_out, out_cap))
 int mc_host_rows_alloc(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, float** d_xyz, int** d_npts);
 int mc_host_rows_fetch(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, const int64_t* h_n_out, const float* d_xyz,

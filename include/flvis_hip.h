@@ -1376,6 +1376,89 @@ int flvis_loop_closer_dense_cloud_host(flvis_loop_closer* lc, int n_groups, cons
                                        const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
                                        int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
 
+/* ---- dense stereo: a depth image from a rectified pair -----------------------------------------------------------------------------------
+ * (The reference has no dense matcher; like the voxel filter this is the project's own definition.  It is integer arithmetic until one
+ * fp64 division, so it is defined bit for bit; tests/_dense_stereo.py restates it in numpy.)
+ * Input: d_img0, d_img1 [n_img][h][w] uint8, rows tightly packed, RECTIFIED: a point at column u of image 0 lies at column u - d of
+ *   image 1, d >= 0 (the keyframe log's img0 / img1 on cam_type 0).  h_cam2 [n_cam][2] = (bf, depth_factor), n_cam 1 (every image) or
+ *   n_img (image i: entry i): bf = focal length times baseline in pixel-metres (-P1[3] of a config), depth_factor the Z16 unit of
+ *   flvis_hip_depth_cloud.
+ * Output, either may be NULL: d_disp16 [n_img][h][w] uint16, the disparity in 1/16 px, 0 = invalid; d_z16 [n_img][h][w] uint16, the
+ *   layout flvis_hip_depth_cloud reads, 0 = invalid.
+ * Definition (flvis_dense_stereo_params: d_min, n_disp, agg_r, uniq, lr_tol), every step integer:
+ *   census      c(u, v): the 62 comparisons neighbour < centre of the window 9 wide x 7 high, defined for 4 <= u <= w - 5,
+ *               3 <= v <= h - 4 (the bit order cannot be observed)
+ *   cost        H(u, v, d) = popcount(c0(u, v) ^ c1(u - d, v)), defined where both words are
+ *   aggregate   A(u, v, d) = the sum of H(u + du, v + dv, d) over |du|, |dv| <= agg_r, defined iff every term is:
+ *               u - d - agg_r >= 4, u + agg_r <= w - 5, v - agg_r >= 3, v + agg_r <= h - 4
+ *   candidates  D(u, v) = the d of [d_min, d_min + n_disp) with A defined; best = the argmin of A over D, the lowest d among equals;
+ *               the pixel is invalid if D is empty
+ *   uniqueness  invalid if some d' of D with |d' - best| > 1 has A(d') * (100 - uniq) < A(best) * 100
+ *   left-right  (lr_tol >= 0; -1: off) bestR = the argmin over d of A(u' + d, v, d) at u' = u - best, over the d of the same range for
+ *               which that is defined, the lowest d among equals; invalid if |bestR - best| > lr_tol
+ *   sub-pixel   best - 1 and best + 1 must both be in D(u, v), else invalid.  p = A(best - 1), n = A(best + 1), c = A(best),
+ *               den = max(p + n - 2 c, 1): d16 = 16 best + floor(((p - n) * 16 + den) / (2 den)), the division rounding toward minus
+ *               infinity.  d16 is the disparity output.
+ *   depth       fp64, no contraction: z = (bf * 16.0) / (double)d16, raw = rint(z * depth_factor), ties to even; raw outside 1 .. 65535
+ *               is invalid IN d_z16 ONLY (the disparity output keeps d16).
+ * Several images in one call give the bits of as many single calls; a second run gives the same bits; no atomic decides a value.  An
+ *   image too small to hold a valid pixel is no error: its outputs are all 0.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: n_disp < 1 or > 256; d_min < 0; d_min + n_disp > 4095 (16 d must fit 16 bits); agg_r
+ *   outside 0 .. 4; uniq outside 0 .. 99; lr_tol < -1; w, h or n_img <= 0; n_cam neither 1 nor n_img; a camera entry that is not finite or
+ *   not positive; both outputs NULL; a NULL image, h_cam2 or prm.  flvis_dense_stereo_check is the host part of these checks on its own
+ *   (no context, no device: the device pointers are only compared with NULL).
+ * No cost volume exists: a pair is read a small number of times through the cache and only the outputs are written.  Workspace, the
+ *   context's, grown on demand and kept: with lr_tol >= 0 the right view's argmin, 2 bytes per pixel of min(n_img, 64) images (a call
+ *   runs its images 64 at a time), and 16 bytes per camera.  A failed allocation returns FLVIS_ERR_HIP and leaves the context usable.
+ *   The call queues its kernels and returns; it waits only for the upload of the cameras. */
+typedef struct flvis_dense_stereo_params {
+  int d_min;   /* >= 0: the first disparity searched */
+  int n_disp;  /* 1 .. 256: the disparities d_min .. d_min + n_disp - 1 */
+  int agg_r;   /* 0 .. 4: the box sum covers (2 agg_r + 1)^2 pixels */
+  int uniq;    /* 0 .. 99, per cent */
+  int lr_tol;  /* >= 0: the left-right tolerance in px; -1: no check */
+} flvis_dense_stereo_params;
+int flvis_hip_dense_stereo(flvis_ctx* ctx, const uint8_t* d_img0, const uint8_t* d_img1, int n_img, int w, int h, int n_cam,
+                           const double* h_cam2, const flvis_dense_stereo_params* prm, uint16_t* d_disp16, uint16_t* d_z16);
+int flvis_dense_stereo_check(const uint8_t* d_img0, const uint8_t* d_img1, int n_img, int w, int h, int n_cam, const double* h_cam2,
+                             const flvis_dense_stereo_params* prm, const uint16_t* d_disp16, const uint16_t* d_z16);
+
+/* ---- the dense map on rectified stereo rigs: the keyframe log's pairs through flvis_hip_dense_stereo ------------------------------------
+ * On stereo rigs the log keeps both working images of every keyframe; on cam_type 0 (the D435i infra pair, the pixhawk variant, KITTI)
+ * the pair is rectified.  These calls put such pairs through flvis_hip_dense_stereo with bf = -P1[3] of the stream's (the sequence's) OWN
+ * config and the caller's depth_factor (the Z16 unit of the intermediate depth image; 1000 = millimetres), and hand the Z16 images to
+ * flvis_hip_depth_cloud.  cam_type 1 (EuRoC: the logged pair is NOT rectified and would need a remap in front, which is out of scope) and
+ * cam_type 2 (a depth rig: flvis_keyframe_log_depth_cloud) return FLVIS_ERR_CONFIG.  The depth-rig calls keep refusing stereo rigs.
+ * flvis_keyframe_log_stereo_z16: the whole Z16 image of the entries (h_stream[i], h_index[i]), i < n, into d_z16 [n][h][w] (device, the
+ *   caller's).  Waits for the tracker's queued work, queues the matcher and returns.  FLVIS_ERR_INVALID_ARG: no tracker, the log off,
+ *   n <= 0, a NULL pointer, a stream out of range, an entry that is not logged, and the argument errors of flvis_hip_dense_stereo.
+ * flvis_keyframe_log_stereo_cloud(_host), flvis_loop_closer_stereo_cloud(_host): the arguments and semantics of
+ *   flvis_keyframe_log_depth_cloud(_host) and flvis_loop_closer_dense_cloud(_host) with the stereo parameters and depth_factor in front of
+ *   the sampling.  RESULT: bit for bit flvis_hip_depth_cloud on the Z16 images flvis_keyframe_log_stereo_z16 gives for the same entries,
+ *   with the intrinsics of P0, depth_factor, and the logged poses (the closer's stored poses), exactly as the depth-rig calls take them.
+ *   The no-side-effect guarantees of the depth-rig calls hold: the log, the tracker and the closer are only read.
+ * Workspace, the context's, grown on demand and kept: the matcher is evaluated on whole images, 64 at a time, but only the Z16 values AT
+ *   THE CLOUD'S SAMPLES are kept: 2 bytes per sample (not per pixel) of every listed keyframe, 20 bytes per listed keyframe, the 2 bytes
+ *   per pixel of 64 images of flvis_hip_dense_stereo's left-right map (39 MB at 640 x 480), and flvis_hip_depth_cloud's own workspace.
+ *   27200 keyframes of 640 x 480 at step 7 (92 x 69 samples): 345 MB of samples.  A failed allocation returns FLVIS_ERR_HIP and leaves
+ *   the context usable. */
+int flvis_keyframe_log_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* prm,
+                                  double depth_factor, uint16_t* d_z16);
+int flvis_keyframe_log_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                    double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                    float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_keyframe_log_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                         double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                         float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_loop_closer_stereo_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                   const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm, double leaf,
+                                   int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped,
+                                   int64_t* h_n_valid);
+int flvis_loop_closer_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                        const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                        double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
+                                        int64_t* h_n_dropped, int64_t* h_n_valid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ With --loop-closing the keyframes enter with the closer's stored poses (flvis_lo
 logged ones (flvis_keyframe_log_depth_cloud).  The log then holds the whole run (one entry per frame at most; 3 bytes per pixel and
 entry) and is handed to the closer once, after the last chunk, instead of chunk by chunk.
 
+--dense-stereo FILE.ply : (hip, rectified stereo rigs -- cam_type 0 -- with --batch) the same dense map on a stereo rig: every logged
+keyframe's pair through the dense matcher (flvis_hip_dense_stereo; --stereo-disp disparities, default 64, the other parameters at their
+defaults, depth in millimetres), then as --dense-cloud (flvis_keyframe_log_stereo_cloud / flvis_loop_closer_stereo_cloud).  Not both
+in one run: a rig has a depth image or a second view.  The EuRoC rig (cam_type 1) logs an unrectified pair and is refused.
+
 --batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
 keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
 device (flvis_loop_closer_add_logged: the images the tracker worked on, img0 after equalizeHist where the rig uses it, as the KeyFrame
@@ -88,6 +93,8 @@ def main():
     ap.add_argument("--lm-cloud-points", type=int, default=1 << 22)
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--dense-cloud", default=None)
+    ap.add_argument("--dense-stereo", default=None)
+    ap.add_argument("--stereo-disp", type=int, default=64)
     ap.add_argument("--dense-step", type=int, default=7)
     ap.add_argument("--lc-traj-out", default=None)
     ap.add_argument("--lc-imu-out", default=None)
@@ -107,6 +114,9 @@ def main():
         ap.error("--batch N (N > 0) needs --backend hip and goes without --imu-out and --lc-imu-out")
     if args.dense_cloud and not (args.batch and args.backend == "hip" and args.dense_step >= 1):
         ap.error("--dense-cloud needs --backend hip, --batch N and --dense-step >= 1")
+    if args.dense_stereo and (args.dense_cloud or not (args.batch and args.backend == "hip" and args.dense_step >= 1)):
+        ap.error("--dense-stereo needs --backend hip, --batch N and --dense-step >= 1, and goes without --dense-cloud")
+    dense_out = args.dense_cloud or args.dense_stereo              # (either: the log keeps the whole run)
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -179,19 +189,21 @@ def main():
                 closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
         if args.dense_cloud and cfg.cam_type != 2:
             ap.error("--dense-cloud: the config's rig has no depth image (cam_type 2)")
+        if args.dense_stereo and cfg.cam_type != 0:
+            ap.error("--dense-stereo: the config's rig is no rectified stereo pair (cam_type 0)")
         if args.batch:
-            trk.keyframe_log_enable(max(n, 1) if args.dense_cloud else args.batch)  # (the dense map reads the whole run's log at the end)
+            trk.keyframe_log_enable(max(n, 1) if dense_out else args.batch)  # (the dense map reads the whole run's log at the end)
             imu_type = {1: 1, 3: 0, 5: 2, 0: 0, 2: 2, 4: 3}[cfg.type_of_vi]
             dropped_logged, chunk = 0, []
 
             def flush(last=False):
                 """the chunk through run_steps; its keyframes from the log into the closer; the log cleared"""
                 nonlocal dropped_logged
-                if not chunk and not (last and args.dense_cloud):
+                if not chunk and not (last and dense_out):
                     return
                 if chunk:
                     trk.run_steps(chunk, with_local_map=args.local_map)
-                if args.dense_cloud and not last:                              # (the log keeps the run; the closer gets it after the last chunk)
+                if dense_out and not last:                              # (the log keeps the run; the closer gets it after the last chunk)
                     ctx.synchronize()
                     del chunk[:]
                     return
@@ -199,9 +211,9 @@ def main():
                 dropped_logged += info["dropped"]
                 if closer is not None:
                     kf_stamps.extend(trk.keyframe_log_get(0, i, images=False)["stamp"] for i in range(info["logged"]))
-                    rounds = max(info["logged"], 1) if args.dense_cloud else args.batch
+                    rounds = max(info["logged"], 1) if dense_out else args.batch
                     lc_events.extend(r[0] for r in closer.add_logged(process=True, max_rounds=rounds))
-                if not args.dense_cloud:
+                if not dense_out:
                     trk.keyframe_log_clear([0])
                 del chunk[:]
         for t, i0, i1, imu in seq.frames(0, n):
@@ -254,13 +266,17 @@ def main():
             traj_io.write_ply(args.map_cloud, xyz[0], npts[0])
             map_cloud = {"points": int(n_out[0]), "dropped": int(n_drop[0]), "leaf": args.leaf}
         dense_cloud = None
-        if args.dense_cloud:
+        if dense_out:
             sampling = dict(step=args.dense_step, z_min=0.3, z_max=float(cfg.dr_para[1]), leaf=args.leaf)
-            got = closer.dense_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_depth_cloud([0], **sampling)
-            traj_io.write_ply(args.dense_cloud, got[0][0], got[1][0])
+            if args.dense_stereo:
+                sampling.update(n_disp=args.stereo_disp, depth_factor=1000.0)
+                got = closer.stereo_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_stereo_cloud([0], **sampling)
+            else:
+                got = closer.dense_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_depth_cloud([0], **sampling)
+            traj_io.write_ply(dense_out, got[0][0], got[1][0])
             dense_cloud = {"points": int(got[2][0]), "dropped": int(got[3][0]), "valid_samples": int(got[4][0]), "leaf": args.leaf,
                            "step": args.dense_step, "keyframes": trk.keyframe_log_info(0)["logged"],
-                           "frame": "map" if closer is not None else "odometry"}
+                           "frame": "map" if closer is not None else "odometry", "from": "stereo" if args.dense_stereo else "depth"}
         lm_cloud = None
         if args.lm_cloud:
             trk.local_map_counts()                                             # (drains the keyframe queue: the last optimisations too)
@@ -280,7 +296,7 @@ def main():
             wants_cloud = flvis_amd.config_get_bool(args.config, "output_sparse_map")
         except flvis_amd.FlvisError:
             wants_cloud = False                                                # (a yaml without the key: the reference would refuse it)
-        if args.dense_cloud:
+        if dense_out:
             out["dense_cloud"] = dense_cloud
         if args.lm_cloud:
             out["local_map_cloud"] = lm_cloud
