@@ -472,6 +472,24 @@ class Context:
                                                      _ptr(disp), _ptr(z16)), "dense_stereo")
         return disp, z16
 
+    def rectify(self, src, cams, cam_of=None, want_covered=True):
+        """flvis_hip_rectify: src uint8 [n_img, h, w] device tensor of raw images; cams float64 [n_cam, 21] = per camera K (fx fy cx cy),
+        D (k1 k2 p1 p2), R (9, row-major), Pn (fx' fy' cx' cy' of the rectified projection): one camera for every image, one per image,
+        or any number with cam_of [n_img] naming each image's.  The header has the definition (fp64 map rounded once to 1/32 px, integer
+        bilinear blend, uncovered pixels 0).  -> (dst, covered) uint8 [n_img, h, w] device tensors, covered None unless asked for; queued
+        on the context's stream."""
+        import torch
+        assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 3
+        n_img, h, w = [int(x) for x in src.shape]
+        cam21 = np.ascontiguousarray(np.asarray(cams, np.float64).reshape(-1, 21))
+        of = None if cam_of is None else np.ascontiguousarray(cam_of, np.int32)
+        assert of is None or len(of) == n_img, "one camera index per image"
+        dst = torch.empty_like(src)
+        cov = torch.empty_like(src) if want_covered else None
+        self._check(self._lib.flvis_hip_rectify(self._h, _ptr(src), n_img, w, h, len(cam21), _P(cam21, C.c_double),
+                                                _P(of, C.c_int) if of is not None else None, _ptr(dst), _ptr(cov)), "rectify")
+        return dst, cov
+
     def depth_cloud_times(self, enable=True):
         """flvis_hip_depth_cloud_times: switch the stage timing of the dense calls on or off -> dict(count, keys, sort, rows) in
         milliseconds of the last timed call."""

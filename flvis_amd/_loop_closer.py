@@ -351,7 +351,8 @@ class LoopCloser:
         assert first is None or len(first) == len(seqs), "one first keyframe per listed sequence"
         prm = depth_cloud_params(window, step, z_min, z_max)
         n_out, n_drop, n_valid = (np.zeros(max(ng, 1), np.int64) for _ in range(3))
-        what = "loop_closer_%s_cloud%s" % ("stereo" if _stereo else "dense", "_host" if host else "")
+        kind = "dense" if not _stereo else "unrect_stereo" if len(_stereo) > 2 and _stereo[2] else "stereo"
+        what = "loop_closer_%s_cloud%s" % (kind, "_host" if host else "")
         fn = getattr(self._lib, "flvis_" + what)
         front = (C.byref(_stereo[0]), float(_stereo[1])) if _stereo else ()   # (the stereo forms: the matcher's parameters, depth_factor)
         head = (self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), _P(first, C.c_int) if first is not None else None) + front + (
@@ -378,6 +379,12 @@ class LoopCloser:
         (Context.dense_stereo: d_min .. lr_tol, or a DenseStereoParams as d_min) makes of the tracker's logged pairs, bf from each sequence's
         own config, depth_factor the Z16 unit.  **cloud: dense_cloud's arguments.  -> what that call returns."""
         return self.dense_cloud(groups, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor), **cloud)
+
+    def unrect_stereo_cloud(self, groups, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
+        """flvis_loop_closer_unrect_stereo_cloud (the unrectified stereo rig, cam_type 1: EuRoC): stereo_cloud on the logged pairs
+        rectified under each sequence's own config (Tracker.keyframe_log_rectified_pair), stored poses, whether or not set_stereo_unrect
+        is on.  The same arguments -> what that call returns."""
+        return self.dense_cloud(groups, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor, True), **cloud)
 
     def poses(self, stream=0, cap=None):
         cap = int(cap) if cap else self.max_keyframes      # (never fewer rows than the sequence can hold: no silent truncation)

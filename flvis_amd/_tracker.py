@@ -455,7 +455,8 @@ class Tracker:
         assert sli is None or len(sli) == n + 1, "one slice per listed stream"
         prm = depth_cloud_params(window, step, z_min, z_max)
         n_out, n_drop, n_valid = (np.zeros(max(n, 1), np.int64) for _ in range(3))
-        what = "keyframe_log_%s_cloud%s" % ("stereo" if _stereo else "depth", "_host" if host else "")
+        kind = "depth" if not _stereo else "unrect_stereo" if len(_stereo) > 2 and _stereo[2] else "stereo"
+        what = "keyframe_log_%s_cloud%s" % (kind, "_host" if host else "")
         fn = getattr(self.lib, "flvis_" + what)
         front = (C.byref(_stereo[0]), float(_stereo[1])) if _stereo else ()   # (the stereo forms: the matcher's parameters, depth_factor)
         head = (self.ctx._h, n, _P(arr, C.c_int), _P(sli, C.c_int) if sli is not None else None) + front + (C.byref(prm), leaf, int(min_points))
@@ -482,7 +483,7 @@ class Tracker:
         config, depth_factor the Z16 unit.  **cloud: keyframe_log_depth_cloud's arguments.  -> what that call returns."""
         return self.keyframe_log_depth_cloud(streams, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor), **cloud)
 
-    def keyframe_log_stereo_z16(self, entries, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0):
+    def keyframe_log_stereo_z16(self, entries, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, _unrect=False):
         """flvis_keyframe_log_stereo_z16: the Z16 depth image dense stereo makes of the logged pairs entries = [(stream, index), ..]
         -> a device tensor int16 [n, h, w] that holds the UNSIGNED 16-bit values (0: invalid); queued on the context's stream."""
         import torch
@@ -491,9 +492,34 @@ class Tracker:
         st, ix = np.ascontiguousarray(ent[:, 0]), np.ascontiguousarray(ent[:, 1])
         prm = dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol)
         z = torch.empty((max(n, 1), int(self.cfg.image_height), int(self.cfg.image_width)), dtype=torch.int16, device=self.ctx.device)
-        self.ctx._check(self.lib.flvis_keyframe_log_stereo_z16(self.ctx._h, n, _P(st, C.c_int), _P(ix, C.c_int), C.byref(prm), float(depth_factor),
-                                                               _ptr(z)), "keyframe_log_stereo_z16")
+        fn, what = ((self.lib.flvis_keyframe_log_unrect_stereo_z16, "keyframe_log_unrect_stereo_z16") if _unrect else
+                    (self.lib.flvis_keyframe_log_stereo_z16, "keyframe_log_stereo_z16"))
+        self.ctx._check(fn(self.ctx._h, n, _P(st, C.c_int), _P(ix, C.c_int), C.byref(prm), float(depth_factor), _ptr(z)), what)
         return z[:n]
+
+    def keyframe_log_unrect_stereo_cloud(self, streams, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
+        """flvis_keyframe_log_unrect_stereo_cloud (the unrectified stereo rig, cam_type 1: EuRoC): keyframe_log_stereo_cloud on the pairs
+        keyframe_log_rectified_pair makes of the logged ones.  The same arguments -> what that call returns."""
+        return self.keyframe_log_depth_cloud(streams, _stereo=(dense_stereo_params(d_min, n_disp, agg_r, uniq, lr_tol), depth_factor, True),
+                                             **cloud)
+
+    def keyframe_log_unrect_stereo_z16(self, entries, **stereo):
+        """flvis_keyframe_log_unrect_stereo_z16 (cam_type 1): keyframe_log_stereo_z16 on the rectified pairs of the logged entries."""
+        return self.keyframe_log_stereo_z16(entries, _unrect=True, **stereo)
+
+    def keyframe_log_rectified_pair(self, entries, want0=True, want1=True):
+        """flvis_keyframe_log_rectified_pair (cam_type 1): the rectified pair of the logged entries = [(stream, index), ..], each under
+        the two cameras of its stream's own config (Context.rectify has the definition) -> (img0, img1) device tensors uint8 [n, h, w],
+        None for one not asked for; queued on the context's stream."""
+        import torch
+        ent = np.ascontiguousarray(list(entries) + [(0, 0)], np.int32).reshape(-1, 2)
+        n = len(ent) - 1
+        st, ix = np.ascontiguousarray(ent[:, 0]), np.ascontiguousarray(ent[:, 1])
+        shape = (max(n, 1), int(self.cfg.image_height), int(self.cfg.image_width))
+        out = [torch.empty(shape, dtype=torch.uint8, device=self.ctx.device) if want else None for want in (want0, want1)]
+        self.ctx._check(self.lib.flvis_keyframe_log_rectified_pair(self.ctx._h, n, _P(st, C.c_int), _P(ix, C.c_int), _ptr(out[0]), _ptr(out[1])),
+                        "keyframe_log_rectified_pair")
+        return tuple(None if o is None else o[:n] for o in out)
 
     def keyframe_log_get(self, stream, index, cap=2048, images=True):
         """flvis_keyframe_log_get: logged keyframe `index` of the stream, a dict like keyframe_msg's."""

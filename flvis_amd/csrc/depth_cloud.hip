@@ -20,6 +20,9 @@
 // A second image layout (DcSamp::packed) serves the stereo forms (flvis_keyframe_log_stereo_cloud, flvis_loop_closer_stereo_cloud): the
 // Z16 values dense_stereo.hip computes are kept at the samples alone, [item][nv][nu], so a sample is read at its own index and still
 // back-projected from its pixel.  Everything else -- lists, poses read in place, counts, keys, the tail -- is the depth-rig path.
+// The unrectified stereo rig (cam_type 1: flvis_keyframe_log_unrect_stereo_cloud, flvis_loop_closer_unrect_stereo_cloud) adds a source
+// stage in front of the matcher: the listed pairs go through rectify.hip RC_BATCH at a time into a workspace of one batch, and the matcher
+// runs batch by batch with its outputs offset (dc_unrect_match).  The workspace does not grow with the number of listed keyframes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +40,7 @@
 #include "kf_log.hpp"
 #include "map_cloud.hpp"
 #include "pipeline_host.hpp"
+#include "rectify.hpp"
 
 namespace {
 
@@ -207,9 +211,41 @@ int dc_grid(int w, int h, const flvis_depth_cloud_params* prm, DsGrid* g) {
   return rc;
 }
 
+void dc_unrect_cams(const flvis_cfg& g, double* cam21_0, double* cam21_1) {
+  rc_cam21(g.cam0_intrinsics, g.cam0_distortion, g.R0, g.P0, cam21_0);
+  rc_cam21(g.cam1_intrinsics, g.cam1_distortion, g.R1, g.P1, cam21_1);
+}
+
+int dc_rectify_batch(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const int* slot, const int* cam, int nb, const DcUnrect& un,
+                     uint8_t* d_out0, uint8_t* d_out1) {
+  int rc = FLVIS_OK;
+  if (d_out0) rc = rc_run(ctx, what, rec.img0, nb, rec.w, rec.h, un.n_cams, un.cam21_0, cam, slot, d_out0, nullptr);
+  if (rc == FLVIS_OK && d_out1) rc = rc_run(ctx, what, rec.img1, nb, rec.w, rec.h, un.n_cams, un.cam21_1, cam, slot, d_out1, nullptr);
+  return rc;
+}
+
+int dc_unrect_match(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const int* slot, const int* cam, int n, const DcUnrect& un,
+                    const double* h_cam2, const flvis_dense_stereo_params* sprm, uint16_t* d_z16, const DsGrid* grid) {
+  const size_t px = rec.px(), out_px = grid ? (size_t)grid->nu * grid->nv : px;
+  uint8_t* const pair = (uint8_t*)ctx->scratch("rc_pair", 2 * (size_t)std::min(n, RC_BATCH) * px);
+  if (!pair) {
+    (void)hipGetLastError();
+    return ctx->fail(FLVIS_ERR_HIP, std::string(what) + ": device allocation failed");
+  }
+  uint8_t* const pair1 = pair + (size_t)std::min(n, RC_BATCH) * px;
+  for (int i0 = 0; i0 < n; i0 += RC_BATCH) {
+    const int nb = std::min(RC_BATCH, n - i0);
+    int rc = dc_rectify_batch(ctx, what, rec, slot + i0, cam + i0, nb, un, pair, pair1);
+    if (rc != FLVIS_OK) return rc;
+    rc = ds_run(ctx, what, pair, pair1, nb, rec.w, rec.h, nb, h_cam2 + 2 * (size_t)i0, sprm, nullptr, d_z16 + (size_t)i0 * out_px, nullptr, grid);
+    if (rc != FLVIS_OK) return rc;
+  }
+  return FLVIS_OK;
+}
+
 int dc_stereo_samples(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const std::vector<int>& slot, const std::vector<int>& cam,
                       const double* h_cam2, const flvis_dense_stereo_params* sprm, const flvis_depth_cloud_params* prm, const uint16_t** d_z,
-                      std::vector<int>& iota) {
+                      std::vector<int>& iota, const DcUnrect* unrect) {
   DsGrid g;
   int rc = dc_grid(rec.w, rec.h, prm, &g);
   if (rc != FLVIS_OK) return ctx->fail(rc, std::string(what) + ": bad sampling");
@@ -224,6 +260,7 @@ int dc_stereo_samples(flvis_ctx* ctx, const char* what, const KfLogRec& rec, con
   }
   *d_z = z;
   if (R == 0) return FLVIS_OK;
+  if (unrect) return dc_unrect_match(ctx, what, rec, slot.data(), cam.data(), (int)R, *unrect, cam2.data(), sprm, z, &g);
   return ds_run(ctx, what, rec.img0, rec.img1, (int)R, rec.w, rec.h, (int)R, cam2.data(), sprm, nullptr, z, slot.data(), &g);
 }
 
@@ -357,16 +394,20 @@ int dc_check_public(int n_img, int w, int h, int n_clouds, const int* h_cloud_pt
 // flvis_keyframe_log_depth_cloud: the refusals, then (unless check_only) the call
 int kfl_depth_cloud(flvis_ctx* ctx, const char* what, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm,
                     double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped,
-                    int64_t* h_n_valid, bool check_only, const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0) {
+                    int64_t* h_n_valid, bool check_only, const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0,
+                    bool unrect = false) {
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
   Pipeline* pl = ctx->pipe;
   if (!pl) return bad("no tracker (flvis_tracker_create)");
   if (!sprm && pl->cfg.cam_type != CAM_DEPTH) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig has no depth image");
-  if (sprm && pl->cfg.cam_type != CAM_STEREO_RECT) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
+  if (sprm && !unrect && pl->cfg.cam_type != CAM_STEREO_RECT)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
+  if (sprm && unrect && pl->cfg.cam_type != CAM_STEREO_UNRECT)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no unrectified stereo pair (cam_type 1)");
   if (pl->kfl.cap <= 0) return bad("the keyframe log is off (flvis_keyframe_log_enable)");
   if (n <= 0 || !h_stream || !h_n_out || !prm) return bad("bad stream list, or a NULL prm or h_n_out");
-  std::vector<double> cam5(5 * (size_t)n), cam2(2 * (size_t)n);
+  std::vector<double> cam5(5 * (size_t)n), cam2(2 * (size_t)n), cam21_0(unrect ? 21 * (size_t)n : 0), cam21_1(cam21_0.size());
   for (int c = 0; c < n; c++) {
     const int s = h_stream[c];
     if (s < 0 || s >= pl->S) return bad("stream out of range");
@@ -375,9 +416,13 @@ int kfl_depth_cloud(flvis_ctx* ctx, const char* what, int n, const int* h_stream
     const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], sprm ? stereo_df : g.depth_factor};
     memcpy(&cam5[5 * (size_t)c], v, sizeof(v));
     cam2[2 * (size_t)c] = -g.P1[3], cam2[2 * (size_t)c + 1] = stereo_df;
+    if (unrect) dc_unrect_cams(g, &cam21_0[21 * (size_t)c], &cam21_1[21 * (size_t)c]);
   }
+  const DcUnrect un{n, cam21_0.data(), cam21_1.data()};
   std::string why;
   int rc = FLVIS_OK;
+  if (unrect) rc = rc_check(n, pl->kfl.w, pl->kfl.h, n, cam21_0.data(), nullptr, &why);
+  if (unrect && rc == FLVIS_OK) rc = rc_check(n, pl->kfl.w, pl->kfl.h, n, cam21_1.data(), nullptr, &why);
   for (int c = 0; sprm && rc == FLVIS_OK && c < n; c++) rc = ds_check(1, pl->kfl.w, pl->kfl.h, 1, &cam2[2 * (size_t)c], sprm, &why);
   if (rc == FLVIS_OK) rc = dc_check_sampling(pl->kfl.w, pl->kfl.h, prm, n, cam5.data(), &why);
   if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
@@ -405,7 +450,7 @@ int kfl_depth_cloud(flvis_ctx* ctx, const char* what, int n, const int* h_stream
   if (sprm) {
     const uint16_t* d_z = nullptr;
     std::vector<int> iota;
-    rc = dc_stereo_samples(ctx, what, rec, img, cam, cam2.data(), sprm, prm, &d_z, iota);
+    rc = dc_stereo_samples(ctx, what, rec, img, cam, cam2.data(), sprm, prm, &d_z, iota, unrect ? &un : nullptr);
     if (rc != FLVIS_OK) return rc;
     return dc_cloud(ctx, what, d_z, rec.w, rec.h, d_pose, sizeof(KeyFrameDev) / 8, n, eptr.data(), iota.data(), img.data(), cam.data(), n,
                     cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid, true);
@@ -472,43 +517,91 @@ int flvis_keyframe_log_depth_cloud_host(flvis_ctx* ctx, int n, const int* h_stre
   return flvis::mc_host_rows_fetch(ctx, what, n, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
 }
 
-int flvis_keyframe_log_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
-                                    double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
-                                    float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+}  // extern "C"
+
+namespace {
+
+// the stereo forms of the two cloud calls; unrect: the cam_type 1 forms (a rectification in front of the matcher)
+int kfl_stereo_cloud(flvis_ctx* ctx, const char* what, bool unrect, int n, const int* h_stream, const int* h_slice2,
+                     const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points,
+                     int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
-  if (!sprm) return ctx->fail(FLVIS_ERR_INVALID_ARG, "keyframe_log_stereo_cloud: NULL stereo params");
-  return kfl_depth_cloud(ctx, "keyframe_log_stereo_cloud", n, h_stream, h_slice2, prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out,
-                         h_n_dropped, h_n_valid, false, sprm, depth_factor);
+  if (!sprm) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": NULL stereo params");
+  return kfl_depth_cloud(ctx, what, n, h_stream, h_slice2, prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid, false,
+                         sprm, depth_factor, unrect);
 }
 
-int flvis_keyframe_log_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
-                                         double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
-                                         float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+int kfl_stereo_cloud_host(flvis_ctx* ctx, const char* what, bool unrect, int n, const int* h_stream, const int* h_slice2,
+                          const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm, double leaf,
+                          int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
-  const char* what = "keyframe_log_stereo_cloud_host";
   if (!sprm) return ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": NULL stereo params");
   int rc = kfl_depth_cloud(ctx, what, n, h_stream, h_slice2, prm, leaf, min_points, out_cap, h_xyz, nullptr, h_n_out, h_n_dropped, h_n_valid, true,
-                           sprm, depth_factor);
+                           sprm, depth_factor, unrect);
   if (rc != FLVIS_OK) return rc;
   float* d_xyz = nullptr;
   int* d_npts = nullptr;
   rc = flvis::mc_host_rows_alloc(ctx, what, n, out_cap, &d_xyz, &d_npts);
   if (rc != FLVIS_OK) return rc;
   rc = kfl_depth_cloud(ctx, what, n, h_stream, h_slice2, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr, h_n_out, h_n_dropped,
-                       h_n_valid, false, sprm, depth_factor);
+                       h_n_valid, false, sprm, depth_factor, unrect);
   if (rc != FLVIS_OK) return rc;
   return flvis::mc_host_rows_fetch(ctx, what, n, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
 }
 
-int flvis_keyframe_log_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* sprm,
-                                  double depth_factor, uint16_t* d_z16) {
+// the listed entries (h_stream[i], h_index[i]) of the settled log: their slots, and on the unrectified rig a camera per DISTINCT stream in
+// order of first appearance (entries listed stream by stream then form long runs of one camera: rectify.hip)
+struct KflEntries {
+  KfLogRec rec{};
+  std::vector<int> slot, cam;
+  std::vector<double> cam21_0, cam21_1;
+  int n_cams = 0;
+};
+
+int kfl_entries(flvis_ctx* ctx, const char* what, int n, const int* h_stream, const int* h_index, bool unrect, KflEntries& E) {
+  const std::string pre = std::string(what) + ": ";
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
+  Pipeline* pl = ctx->pipe;
+  E.cam.resize((size_t)n);
+  if (unrect) {
+    std::vector<int> cam_of_stream((size_t)pl->S, -1);
+    for (int i = 0; i < n; i++) {
+      int& c = cam_of_stream[h_stream[i]];
+      if (c < 0) {
+        c = E.n_cams++;
+        E.cam21_0.resize(21 * (size_t)E.n_cams), E.cam21_1.resize(21 * (size_t)E.n_cams);
+        dc_unrect_cams(pl->cfgs[h_stream[i]], &E.cam21_0[21 * (size_t)c], &E.cam21_1[21 * (size_t)c]);
+      }
+      E.cam[i] = c;
+    }
+    std::string why;
+    int rc = rc_check(E.n_cams, pl->kfl.w, pl->kfl.h, E.n_cams, E.cam21_0.data(), nullptr, &why);
+    if (rc == FLVIS_OK) rc = rc_check(E.n_cams, pl->kfl.w, pl->kfl.h, E.n_cams, E.cam21_1.data(), nullptr, &why);
+    if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
+  }
+  int S = 0, cam_type = 0;
+  std::vector<long long> logged, dropped;
+  int rc = kf_log_settle(ctx, what, E.rec, S, cam_type, logged, dropped);
+  if (rc != FLVIS_OK) return rc;
+  E.slot.resize((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (h_index[i] < 0 || h_index[i] >= logged[h_stream[i]]) return bad("an entry that is not logged");
+    E.slot[i] = (int)((long long)h_stream[i] * E.rec.cap + h_index[i]);
+  }
+  return FLVIS_OK;
+}
+
+int kfl_stereo_z16(flvis_ctx* ctx, const char* what, bool unrect, int n, const int* h_stream, const int* h_index,
+                   const flvis_dense_stereo_params* sprm, double depth_factor, uint16_t* d_z16) {
   if (!ctx) return FLVIS_ERR_INVALID_ARG;
-  const char* what = "keyframe_log_stereo_z16";
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
   Pipeline* pl = ctx->pipe;
   if (!pl) return bad("no tracker (flvis_tracker_create)");
-  if (pl->cfg.cam_type != CAM_STEREO_RECT) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
+  if (!unrect && pl->cfg.cam_type != CAM_STEREO_RECT)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no rectified stereo pair (cam_type 0)");
+  if (unrect && pl->cfg.cam_type != CAM_STEREO_UNRECT)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no unrectified stereo pair (cam_type 1)");
   if (pl->kfl.cap <= 0) return bad("the keyframe log is off (flvis_keyframe_log_enable)");
   if (n <= 0 || !h_stream || !h_index || !sprm || !d_z16) return bad("no entry, or a NULL h_stream, h_index, prm or d_z16");
   std::vector<double> cam2(2 * (size_t)n);
@@ -520,17 +613,77 @@ int flvis_keyframe_log_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, co
     const int rc = ds_check(1, pl->kfl.w, pl->kfl.h, 1, &cam2[2 * (size_t)i], sprm, &why);
     if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
   }
-  KfLogRec rec{};
-  int S = 0, cam_type = 0;
-  std::vector<long long> logged, dropped;
-  int rc = kf_log_settle(ctx, what, rec, S, cam_type, logged, dropped);
+  KflEntries E;
+  int rc = kfl_entries(ctx, what, n, h_stream, h_index, unrect, E);
   if (rc != FLVIS_OK) return rc;
-  std::vector<int> slot((size_t)n);
-  for (int i = 0; i < n; i++) {
-    if (h_index[i] < 0 || h_index[i] >= logged[h_stream[i]]) return bad("an entry that is not logged");
-    slot[i] = (int)((long long)h_stream[i] * rec.cap + h_index[i]);
+  const KfLogRec& rec = E.rec;
+  if (unrect) {
+    const DcUnrect un{E.n_cams, E.cam21_0.data(), E.cam21_1.data()};
+    return dc_unrect_match(ctx, what, rec, E.slot.data(), E.cam.data(), n, un, cam2.data(), sprm, d_z16, nullptr);
   }
-  return ds_run(ctx, what, rec.img0, rec.img1, n, rec.w, rec.h, n, cam2.data(), sprm, nullptr, d_z16, slot.data(), nullptr);
+  return ds_run(ctx, what, rec.img0, rec.img1, n, rec.w, rec.h, n, cam2.data(), sprm, nullptr, d_z16, E.slot.data(), nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int flvis_keyframe_log_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                    double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                    float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  return kfl_stereo_cloud(ctx, "keyframe_log_stereo_cloud", false, n, h_stream, h_slice2, sprm, depth_factor, prm, leaf, min_points, out_cap, d_xyz,
+                          d_npts, h_n_out, h_n_dropped, h_n_valid);
+}
+
+int flvis_keyframe_log_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                         double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                         float* h_xyz, int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  return kfl_stereo_cloud_host(ctx, "keyframe_log_stereo_cloud_host", false, n, h_stream, h_slice2, sprm, depth_factor, prm, leaf, min_points,
+                               out_cap, h_xyz, h_npts, h_n_out, h_n_dropped, h_n_valid);
+}
+
+int flvis_keyframe_log_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* sprm,
+                                  double depth_factor, uint16_t* d_z16) {
+  return kfl_stereo_z16(ctx, "keyframe_log_stereo_z16", false, n, h_stream, h_index, sprm, depth_factor, d_z16);
+}
+
+int flvis_keyframe_log_unrect_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                           double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                           float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  return kfl_stereo_cloud(ctx, "keyframe_log_unrect_stereo_cloud", true, n, h_stream, h_slice2, sprm, depth_factor, prm, leaf, min_points, out_cap,
+                          d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid);
+}
+
+int flvis_keyframe_log_unrect_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2,
+                                                const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                                double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
+                                                int64_t* h_n_dropped, int64_t* h_n_valid) {
+  return kfl_stereo_cloud_host(ctx, "keyframe_log_unrect_stereo_cloud_host", true, n, h_stream, h_slice2, sprm, depth_factor, prm, leaf,
+                               min_points, out_cap, h_xyz, h_npts, h_n_out, h_n_dropped, h_n_valid);
+}
+
+int flvis_keyframe_log_unrect_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* sprm,
+                                         double depth_factor, uint16_t* d_z16) {
+  return kfl_stereo_z16(ctx, "keyframe_log_unrect_stereo_z16", true, n, h_stream, h_index, sprm, depth_factor, d_z16);
+}
+
+int flvis_keyframe_log_rectified_pair(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, uint8_t* d_img0, uint8_t* d_img1) {
+  if (!ctx) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "keyframe_log_rectified_pair";
+  const std::string pre = std::string(what) + ": ";
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
+  Pipeline* pl = ctx->pipe;
+  if (!pl) return bad("no tracker (flvis_tracker_create)");
+  if (pl->cfg.cam_type != CAM_STEREO_UNRECT) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's rig is no unrectified stereo pair (cam_type 1)");
+  if (pl->kfl.cap <= 0) return bad("the keyframe log is off (flvis_keyframe_log_enable)");
+  if (n <= 0 || !h_stream || !h_index || (!d_img0 && !d_img1)) return bad("no entry, a NULL h_stream or h_index, or both outputs NULL");
+  for (int i = 0; i < n; i++)
+    if (h_stream[i] < 0 || h_stream[i] >= pl->S) return bad("stream out of range");
+  KflEntries E;
+  int rc = kfl_entries(ctx, what, n, h_stream, h_index, true, E);
+  if (rc != FLVIS_OK) return rc;
+  const DcUnrect un{E.n_cams, E.cam21_0.data(), E.cam21_1.data()};
+  return dc_rectify_batch(ctx, what, E.rec, E.slot.data(), E.cam.data(), n, un, d_img0, d_img1);
 }
 
 }  // extern "C"

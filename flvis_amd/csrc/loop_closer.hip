@@ -47,6 +47,7 @@
 #include "lc_traj.hpp"
 #include "loop_kernels.hpp"
 #include "map_cloud.hpp"
+#include "rectify.hpp"
 #include "pipeline_host.hpp"
 
 namespace {
@@ -1424,7 +1425,7 @@ int flvis_loop_closer_map_cloud_host(flvis_loop_closer* lc, int n_groups, const 
 static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
                           const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts,
                           int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid, bool check_only,
-                          const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0) {
+                          const flvis_dense_stereo_params* sprm = nullptr, double stereo_df = 0, bool unrect = false) {
   flvis_ctx* ctx = lc->ctx;
   const std::string pre = std::string(what) + ": ";
   auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
@@ -1433,13 +1434,15 @@ static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups,
   if (pl->S != lc->S || pl->kfl.w != lc->w || pl->kfl.h != lc->h || pl->cfg.cam_type != lc->cam_type)
     return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
   if (!sprm && lc->cam_type != 2) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig has no depth image");
-  if (sprm && lc->cam_type != 0) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig is no rectified stereo pair (cam_type 0)");
+  if (sprm && !unrect && lc->cam_type != 0) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig is no rectified stereo pair (cam_type 0)");
+  if (sprm && unrect && lc->cam_type != 1) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig is no unrectified stereo pair (cam_type 1)");
   if (!prm) return bad("NULL prm");
   std::vector<int> range2;  // (first row of the pose database, stored keyframes) per listed sequence: the group checks of map_cloud
   int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
   if (rc != FLVIS_OK) return rc;
   const int E = h_group_ptr[n_groups];
   std::vector<double> cam5(5 * (size_t)std::max(E, 1)), cam2(2 * (size_t)std::max(E, 1));
+  std::vector<double> cam21_0(unrect ? 21 * (size_t)std::max(E, 1) : 0), cam21_1(cam21_0.size());  // (the raw cameras: rectify.hip)
   std::string why;
   for (int e = 0; e < E; e++) {
     const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
@@ -1448,7 +1451,12 @@ static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups,
     const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], sprm ? stereo_df : g.depth_factor};
     memcpy(&cam5[5 * (size_t)e], v, sizeof(v));
     cam2[2 * (size_t)e] = -g.P1[3], cam2[2 * (size_t)e + 1] = stereo_df;
+    if (unrect) flvis::dc_unrect_cams(g, &cam21_0[21 * (size_t)e], &cam21_1[21 * (size_t)e]);
   }
+  const flvis::DcUnrect un{E, cam21_0.data(), cam21_1.data()};
+  rc = unrect && E > 0 ? flvis::rc_check(E, lc->w, lc->h, E, cam21_0.data(), nullptr, &why) : FLVIS_OK;
+  if (unrect && E > 0 && rc == FLVIS_OK) rc = flvis::rc_check(E, lc->w, lc->h, E, cam21_1.data(), nullptr, &why);
+  if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
   const double unit_cam[2] = {1.0, 1.0};
   rc = sprm ? flvis::ds_check(1, lc->w, lc->h, 1, unit_cam, sprm, &why) : FLVIS_OK;  // (the params alone, then each sequence's camera)
   for (int e = 0; sprm && rc == FLVIS_OK && e < E; e++) rc = flvis::ds_check(1, lc->w, lc->h, 1, &cam2[2 * (size_t)e], sprm, &why);
@@ -1481,7 +1489,7 @@ static int lc_dense_cloud(flvis_loop_closer* lc, const char* what, int n_groups,
   if (sprm) {
     const uint16_t* d_z = nullptr;
     std::vector<int> iota;
-    rc = flvis::dc_stereo_samples(ctx, what, rec, img, camv, cam2.data(), sprm, prm, &d_z, iota);
+    rc = flvis::dc_stereo_samples(ctx, what, rec, img, camv, cam2.data(), sprm, prm, &d_z, iota, unrect ? &un : nullptr);
     if (rc != FLVIS_OK) return rc;
     return flvis::dc_cloud(ctx, what, d_z, rec.w, rec.h, lc->db_T, 7, n_groups, eptr.data(), iota.data(), pose.data(), camv.data(), E,
                            cam5.data(), prm, leaf, min_points, out_cap, d_xyz, d_npts, h_n_out, h_n_dropped, h_n_valid, true);
@@ -1542,6 +1550,37 @@ int flvis_loop_closer_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, con
   if (rc != FLVIS_OK) return rc;
   rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr,
                       h_n_out, h_n_dropped, h_n_valid, false, sprm, depth_factor);
+  if (rc != FLVIS_OK) return rc;
+  return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
+}
+
+// the same on the unrectified rig (cam_type 1): the logged pairs are rectified in front of the matcher (rectify.hip)
+int flvis_loop_closer_unrect_stereo_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                          const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                          double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out,
+                                          int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  if (!sprm) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, "loop_closer_unrect_stereo_cloud: NULL stereo params");
+  return lc_dense_cloud(lc, "loop_closer_unrect_stereo_cloud", n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz,
+                        d_npts, h_n_out, h_n_dropped, h_n_valid, false, sprm, depth_factor, true);
+}
+
+int flvis_loop_closer_unrect_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq,
+                                               const int* h_first_kf, const flvis_dense_stereo_params* sprm, double depth_factor,
+                                               const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
+                                               int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "loop_closer_unrect_stereo_cloud_host";
+  if (!sprm) return lc->ctx->fail(FLVIS_ERR_INVALID_ARG, std::string(what) + ": NULL stereo params");
+  int rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, h_xyz, nullptr, h_n_out, h_n_dropped,
+                          h_n_valid, true, sprm, depth_factor, true);
+  if (rc != FLVIS_OK) return rc;
+  float* d_xyz = nullptr;
+  int* d_npts = nullptr;
+  rc = flvis::mc_host_rows_alloc(lc->ctx, what, n_groups, out_cap, &d_xyz, &d_npts);
+  if (rc != FLVIS_OK) return rc;
+  rc = lc_dense_cloud(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, min_points, out_cap, d_xyz, h_npts ? d_npts : nullptr,
+                      h_n_out, h_n_dropped, h_n_valid, false, sprm, depth_factor, true);
   if (rc != FLVIS_OK) return rc;
   return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
 }

@@ -96,9 +96,26 @@ int dc_cloud(flvis_ctx* ctx, const char* what, const uint16_t* d_depth, int w, i
 // camera h_cam2[2 * cam[e]] = bf, depth_factor) at the samples of `prm` ALONE, 2 bytes per sample, in the context's workspace -- the images
 // dc_cloud reads with packed = true and the image list `iota` (item e: image e)
 struct KfLogRec;
+struct DsGrid;
+struct DcUnrect;
 int dc_stereo_samples(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const std::vector<int>& slot, const std::vector<int>& cam,
                       const double* h_cam2, const flvis_dense_stereo_params* sprm, const flvis_depth_cloud_params* prm, const uint16_t** d_z,
-                      std::vector<int>& iota);
+                      std::vector<int>& iota, const DcUnrect* unrect = nullptr);
+// The unrectified rig (cam_type 1): `unrect` names the raw cameras of flvis_hip_rectify (rectify.hip), camera cam[e] of item e in both
+// tables; the listed pairs are then rectified RC_BATCH at a time into a workspace of one batch in front of the matcher.
+struct DcUnrect {
+  int n_cams;
+  const double *cam21_0, *cam21_1;  // [n_cams][21]: camera 0 (K0, D0, R0, P0) and camera 1 (K1, D1, R1, P1)
+};
+// the two cameras of a config (rc_cam21 of its fields)
+void dc_unrect_cams(const flvis_cfg& g, double* cam21_0, double* cam21_1);
+// items slot[0 .. nb) of the log, rectified into d_out0 / d_out1 [nb][h][w] (either may be NULL)
+int dc_rectify_batch(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const int* slot, const int* cam, int nb, const DcUnrect& un,
+                     uint8_t* d_out0, uint8_t* d_out1);
+// rectify + flvis_hip_dense_stereo batch by batch: item e with camera h_cam2[2 * e] into image e of d_z16 (whole images, or with `grid`
+// the samples alone)
+int dc_unrect_match(flvis_ctx* ctx, const char* what, const KfLogRec& rec, const int* slot, const int* cam, int n, const DcUnrect& un,
+                    const double* h_cam2, const flvis_dense_stereo_params* sprm, uint16_t* d_z16, const DsGrid* grid);
 // _host forms: rows of n_clouds clouds staged in the context's `name` buffer, then copied out (rows below min(h_n_out, out_cap))
 int mc_host_rows_alloc(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, float** d_xyz, int** d_npts);
 int mc_host_rows_fetch(flvis_ctx* ctx, const char* what, int n_clouds, int out_cap, const int64_t* h_n_out, const float* d_xyz,

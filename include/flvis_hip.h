@@ -1427,8 +1427,8 @@ int flvis_dense_stereo_check(const uint8_t* d_img0, const uint8_t* d_img1, int n
  * On stereo rigs the log keeps both working images of every keyframe; on cam_type 0 (the D435i infra pair, the pixhawk variant, KITTI)
  * the pair is rectified.  These calls put such pairs through flvis_hip_dense_stereo with bf = -P1[3] of the stream's (the sequence's) OWN
  * config and the caller's depth_factor (the Z16 unit of the intermediate depth image; 1000 = millimetres), and hand the Z16 images to
- * flvis_hip_depth_cloud.  cam_type 1 (EuRoC: the logged pair is NOT rectified and would need a remap in front, which is out of scope) and
- * cam_type 2 (a depth rig: flvis_keyframe_log_depth_cloud) return FLVIS_ERR_CONFIG.  The depth-rig calls keep refusing stereo rigs.
+ * flvis_hip_depth_cloud.  cam_type 1 (EuRoC: the logged pair is NOT rectified and needs a remap in front: the flvis_*_unrect_stereo_* calls
+ * below) and cam_type 2 (a depth rig: flvis_keyframe_log_depth_cloud) return FLVIS_ERR_CONFIG.  The depth-rig calls keep refusing stereo rigs.
  * flvis_keyframe_log_stereo_z16: the whole Z16 image of the entries (h_stream[i], h_index[i]), i < n, into d_z16 [n][h][w] (device, the
  *   caller's).  Waits for the tracker's queued work, queues the matcher and returns.  FLVIS_ERR_INVALID_ARG: no tracker, the log off,
  *   n <= 0, a NULL pointer, a stream out of range, an entry that is not logged, and the argument errors of flvis_hip_dense_stereo.
@@ -1458,6 +1458,74 @@ int flvis_loop_closer_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, con
                                         const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
                                         double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
                                         int64_t* h_n_dropped, int64_t* h_n_valid);
+
+/* ---- rectification: raw, distorted images into rectified ones ----------------------------------------------------------------------------
+ * (The reference never remaps an image -- it undistorts points -- so this is the project's own definition.  It is fp64 up to one rounding
+ * and integer after that, so it is defined bit for bit; tests/_rectify.py restates it twice in numpy.)
+ * Input: d_src [n_img][h][w] uint8, rows tightly packed.  h_cam21 [n_cam][21] doubles, a camera each: K = (fx, fy, cx, cy) the raw
+ *   intrinsics, D = (k1, k2, p1, p2) the raw radtan distortion, R[9] row-major the rectifying rotation, Pn = (fx', fy', cx', cy') =
+ *   (P[0], P[5], P[2], P[6]) of the rectified projection (a config's cam0_intrinsics, cam0_distortion, R0, P0, or cam1_*, R1, P1).
+ *   n_cam is 1 (every image), or n_img with h_cam_of NULL (image i: camera i), or any count with h_cam_of [n_img] naming a camera per image.
+ * Output: d_dst [n_img][h][w] uint8, and optionally (may be NULL) d_covered [n_img][h][w] uint8, 1 where the pixel is covered, else 0.
+ * Definition, for output pixel (u, v): every operation fp64, in exactly this order, left to right, no fused multiply-add:
+ *   x = (u - cx') / fx';  y = (v - cy') / fy'
+ *   X = R[0]*x + R[3]*y + R[6];  Y = R[1]*x + R[4]*y + R[7];  W = R[2]*x + R[5]*y + R[8]          (R^T (x, y, 1))
+ *   xp = X / W;  yp = Y / W
+ *   r2 = xp*xp + yp*yp;  rad = 1 + k1*r2 + k2*r2*r2
+ *   xd = xp*rad + 2*p1*xp*yp + p2*(r2 + 2*xp*xp);  yd = yp*rad + p1*(r2 + 2*yp*yp) + 2*p2*xp*yp
+ *   mx = fx*xd + cx;  my = fy*yd + cy;  tx = mx*32;  ty = my*32
+ *   uncovered if tx or ty is not finite or |tx| or |ty| >= 2^30; else ix = rint(tx), iy = rint(ty), ties to even;
+ *   sx = ix >> 5 (arithmetic: a floor), ax = ix & 31, and likewise sy, ay;
+ *   covered iff sx >= 0, sy >= 0, sx + (ax > 0) <= w - 1 and sy + (ay > 0) <= h - 1: every tap of non-zero weight lies in the image (an
+ *   identity camera reproduces its image, last row and column included);
+ *   covered: ((32-ax)(32-ay) I[sy][sx] + ax(32-ay) I[sy][sx+1] + (32-ax) ay I[sy+1][sx] + ax ay I[sy+1][sx+1] + 512) >> 10, a tap of weight
+ *   0 not read; uncovered: 0.
+ * Several images in one call give the bits of as many single calls; a second run gives the same bits.  One kernel, no map table in
+ *   memory: a thread evaluates the map once and walks the run of images that share its camera, so list the images camera by camera.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: a non-positive size or count; a NULL d_src, d_dst or h_cam21; n_cam neither 1 nor n_img
+ *   with h_cam_of NULL; a camera index out of range; a camera entry that is not finite, or fx, fy, fx' or fy' <= 0; d_dst or d_covered
+ *   overlapping d_src (the call is a gather and cannot run in place).  flvis_rectify_check is the host part on its own (no context, no
+ *   device: the device pointers are only compared with NULL and with each other).
+ * Workspace, the context's: 168 bytes per camera, 12 per run and nothing per pixel.  The call queues its kernel and returns; it waits only
+ *   for the upload of the cameras. */
+int flvis_hip_rectify(flvis_ctx* ctx, const uint8_t* d_src, int n_img, int w, int h, int n_cam, const double* h_cam21, const int* h_cam_of,
+                      uint8_t* d_dst, uint8_t* d_covered);
+int flvis_rectify_check(const uint8_t* d_src, int n_img, int w, int h, int n_cam, const double* h_cam21, const int* h_cam_of,
+                        const uint8_t* d_dst, const uint8_t* d_covered);
+
+/* ---- the dense map on the unrectified stereo rig (cam_type 1, EuRoC): the logged pairs rectified, then as above --------------------------
+ * The tracker's landmarks and poses on this rig are of the RECTIFIED camera 0 (undistortPoints with R0 / P0, triangulation with P0 / P1),
+ * so a cloud back-projected from a rectified depth image with P0 under the logged pose lies in the frame of the sparse map.
+ * flvis_keyframe_log_rectified_pair: the rectified pair of the entries (h_stream[i], h_index[i]), i < n, into d_img0 / d_img1 [n][h][w]
+ *   (device, the caller's; either may be NULL, not both): flvis_hip_rectify with camera 0 = (cam0_intrinsics, cam0_distortion, R0, P0) and
+ *   camera 1 = (cam1_*, R1, P1) of the stream's own config.  Waits for the tracker's queued work, queues the kernel and returns.
+ * flvis_keyframe_log_unrect_stereo_z16, flvis_keyframe_log_unrect_stereo_cloud(_host), flvis_loop_closer_unrect_stereo_cloud(_host): the
+ *   argument lists and semantics of their stereo_ namesakes.  RESULT: bit for bit flvis_hip_dense_stereo, then flvis_hip_depth_cloud
+ *   (intrinsics of P0, bf = -P1[3], the caller's depth_factor, logged or stored poses), on the pairs flvis_keyframe_log_rectified_pair
+ *   gives for the same entries.  The closer's form reads stored poses only, whether or not flvis_loop_closer_set_stereo_unrect is on.  The
+ *   log, the tracker and the closer are only read.  cam_type 0 and cam_type 2 return FLVIS_ERR_CONFIG.
+ * Uncovered pixels enter the matcher as 0; masking their depth is out of scope (the caller's sampling window crops them where it matters:
+ *   with alpha 0 they are none of camera 0 and a sliver at camera 1's border on the stock EuRoC rig).
+ * Workspace, the context's, grown on demand and kept: rectified pairs exist for one batch of 64 pairs at a time (46 MB at 752 x 480),
+ *   whatever the number of listed keyframes; the rest is the stereo forms' own. */
+int flvis_keyframe_log_rectified_pair(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, uint8_t* d_img0, uint8_t* d_img1);
+int flvis_keyframe_log_unrect_stereo_z16(flvis_ctx* ctx, int n, const int* h_stream, const int* h_index, const flvis_dense_stereo_params* prm,
+                                         double depth_factor, uint16_t* d_z16);
+int flvis_keyframe_log_unrect_stereo_cloud(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_dense_stereo_params* sprm,
+                                           double depth_factor, const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap,
+                                           float* d_xyz, int* d_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_keyframe_log_unrect_stereo_cloud_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2,
+                                                const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                                double leaf, int min_points, int out_cap, float* h_xyz, int* h_npts, int64_t* h_n_out,
+                                                int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_loop_closer_unrect_stereo_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                          const flvis_dense_stereo_params* sprm, double depth_factor, const flvis_depth_cloud_params* prm,
+                                          double leaf, int min_points, int out_cap, float* d_xyz, int* d_npts, int64_t* h_n_out,
+                                          int64_t* h_n_dropped, int64_t* h_n_valid);
+int flvis_loop_closer_unrect_stereo_cloud_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq,
+                                               const int* h_first_kf, const flvis_dense_stereo_params* sprm, double depth_factor,
+                                               const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
+                                               int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
 
 #ifdef __cplusplus
 }

@@ -52,10 +52,11 @@ With --loop-closing the keyframes enter with the closer's stored poses (flvis_lo
 logged ones (flvis_keyframe_log_depth_cloud).  The log then holds the whole run (one entry per frame at most; 3 bytes per pixel and
 entry) and is handed to the closer once, after the last chunk, instead of chunk by chunk.
 
---dense-stereo FILE.ply : (hip, rectified stereo rigs -- cam_type 0 -- with --batch) the same dense map on a stereo rig: every logged
+--dense-stereo FILE.ply : (hip, stereo rigs -- cam_type 0 and 1 -- with --batch) the same dense map on a stereo rig: every logged
 keyframe's pair through the dense matcher (flvis_hip_dense_stereo; --stereo-disp disparities, default 64, the other parameters at their
 defaults, depth in millimetres), then as --dense-cloud (flvis_keyframe_log_stereo_cloud / flvis_loop_closer_stereo_cloud).  Not both
-in one run: a rig has a depth image or a second view.  The EuRoC rig (cam_type 1) logs an unrectified pair and is refused.
+in one run: a rig has a depth image or a second view.  The EuRoC rig (cam_type 1) logs an unrectified pair: it is rectified on the device
+in front of the matcher (flvis_keyframe_log_unrect_stereo_cloud / flvis_loop_closer_unrect_stereo_cloud).
 
 --batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
 keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
@@ -189,8 +190,8 @@ def main():
                 closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
         if args.dense_cloud and cfg.cam_type != 2:
             ap.error("--dense-cloud: the config's rig has no depth image (cam_type 2)")
-        if args.dense_stereo and cfg.cam_type != 0:
-            ap.error("--dense-stereo: the config's rig is no rectified stereo pair (cam_type 0)")
+        if args.dense_stereo and cfg.cam_type not in (0, 1):
+            ap.error("--dense-stereo: the config's rig is no stereo pair (cam_type 0 or 1)")
         if args.batch:
             trk.keyframe_log_enable(max(n, 1) if dense_out else args.batch)  # (the dense map reads the whole run's log at the end)
             imu_type = {1: 1, 3: 0, 5: 2, 0: 0, 2: 2, 4: 3}[cfg.type_of_vi]
@@ -270,7 +271,11 @@ def main():
             sampling = dict(step=args.dense_step, z_min=0.3, z_max=float(cfg.dr_para[1]), leaf=args.leaf)
             if args.dense_stereo:
                 sampling.update(n_disp=args.stereo_disp, depth_factor=1000.0)
-                got = closer.stereo_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_stereo_cloud([0], **sampling)
+                if cfg.cam_type == 1:                                          # (EuRoC: the logged pair is rectified in front of the matcher)
+                    got = (closer.unrect_stereo_cloud([[0]], **sampling) if closer is not None else
+                           trk.keyframe_log_unrect_stereo_cloud([0], **sampling))
+                else:
+                    got = closer.stereo_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_stereo_cloud([0], **sampling)
             else:
                 got = closer.dense_cloud([[0]], **sampling) if closer is not None else trk.keyframe_log_depth_cloud([0], **sampling)
             traj_io.write_ply(dense_out, got[0][0], got[1][0])
