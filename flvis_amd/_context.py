@@ -5,7 +5,8 @@ import os
 import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
-from ._structs import LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, dense_stereo_params, depth_cloud_params
+from ._structs import (LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, dense_stereo_params, depth_cloud_params,
+                       occupancy_params, occupancy_rows)
 from ._vocfile import TrainedVocabulary
 
 
@@ -452,6 +453,51 @@ class Context:
         return ([hx[c, :k[c]].copy() for c in range(nc)], [hn[c, :k[c]].copy() for c in range(nc)] if want_npts else None,
                 n_out[:nc].copy(), n_drop[:nc].copy(), n_valid[:nc].copy())
 
+    def occupancy(self, depth, T_c_w, maps, cams, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, occ=None, prior=None, cap=None,
+                  centres=True):
+        """flvis_hip_occupancy: depth, T_c_w, maps (per map a list of (first image, image count) ranges; every listed image is a scan),
+        cams, window, step, z_min, z_max: depth_cloud's.  occ: an OccupancyParams (None: octomap's defaults).  prior: per map (keys int64
+        [k], logodds float32 [k]) or None, e.g. an earlier call's rows.  cap: output rows per map (default: found by a call of its own).
+        -> (keys [n_maps] of int64 [k], logodds [n_maps] of float32 [k], centres [n_maps] of float32 [k, 3] or None, n_out, n_rays,
+        n_dropped int64 [n_maps]) as numpy arrays; k = min(n_out, cap)."""
+        import torch
+        assert depth.is_cuda and depth.is_contiguous() and depth.dim() == 3 and depth.element_size() == 2 and not depth.dtype.is_floating_point
+        assert T_c_w.dtype == torch.float64 and T_c_w.is_contiguous() and tuple(T_c_w.shape) == (int(depth.shape[0]), 7)
+        n_img, h, w = [int(x) for x in depth.shape]
+        maps = [[(int(a), int(b)) for a, b in c] for c in maps]
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) for c in maps])]), np.int32)
+        rng = np.ascontiguousarray([r for c in maps for r in c] + [(0, 0)], np.int32).reshape(-1, 2)
+        cam5 = np.ascontiguousarray(np.asarray(cams, np.float64).reshape(-1, 5))
+        assert len(cam5) == len(rng) - 1, "one camera per range"
+        prm, occ = depth_cloud_params(window, step, z_min, z_max), occupancy_params(occ)
+        nm = len(maps)
+        n_out, n_rays, n_drop = (np.zeros(max(nm, 1), np.int64) for _ in range(3))
+        pk = pl = n_prior = None
+        pcap = 0
+        if prior is not None:
+            assert len(prior) == nm, "one prior per map"
+            n_prior = np.ascontiguousarray([len(k) for k, _ in prior] + [0], np.int64)
+            pcap = int(max(n_prior.max(), 1))
+            hk, hl = np.zeros((max(nm, 1), pcap), np.int64), np.zeros((max(nm, 1), pcap), np.float32)
+            for m, (k, l) in enumerate(prior):
+                hk[m, :len(k)], hl[m, :len(k)] = np.asarray(k, np.int64), np.asarray(l, np.float32)
+            pk, pl = torch.from_numpy(hk).to(depth.device), torch.from_numpy(hl).to(depth.device)
+
+        def call(cap, key, l, xyz):
+            self._check(self._lib.flvis_hip_occupancy(self._h, _ptr(depth), _ptr(T_c_w), n_img, w, h, nm, _P(ptr, C.c_int), _P(rng, C.c_int),
+                                                      _P(cam5, C.c_double), C.byref(prm), leaf, C.byref(occ), _ptr(pk), _ptr(pl), pcap,
+                                                      _P(n_prior, C.c_int64) if n_prior is not None else None, cap, key, l, xyz,
+                                                      _P(n_out, C.c_int64), _P(n_rays, C.c_int64), _P(n_drop, C.c_int64)), "occupancy")
+        rows = occupancy_rows(call, nm, cap, n_out, depth.device, centres=centres)
+        return rows + (n_out[:nm].copy(), n_rays[:nm].copy(), n_drop[:nm].copy())
+
+    def occupancy_stats(self):
+        """flvis_hip_occupancy_stats -> dict(records, rays, batches, workspace_bytes, ms=(count, emit, sort, reduce)) of the context's last
+        occupancy call; the milliseconds are kept while depth_cloud_times is enabled."""
+        st, ms = (C.c_int64 * 4)(), (C.c_double * 4)()
+        self._check(self._lib.flvis_hip_occupancy_stats(self._h, st, ms), "occupancy_stats")
+        return dict(records=int(st[0]), rays=int(st[1]), batches=int(st[2]), workspace_bytes=int(st[3]), ms=tuple(float(v) for v in ms))
+
     def dense_stereo(self, img0, img1, bf, depth_factor=1000.0, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, want_disp=True, want_z=True):
         """flvis_hip_dense_stereo: img0, img1 uint8 [n_img, h, w] device tensors, a RECTIFIED pair per image (a point at column u of
         img0 lies at u - d of img1).  bf (focal length times baseline, pixel-metres) and depth_factor (the Z16 unit): a number each for
@@ -778,3 +824,12 @@ def voxel_cloud_info():
     if lib.flvis_hip_voxel_cloud_info(info) != FLVIS_OK:
         raise FlvisError("voxel_cloud_info failed")
     return dict(sort_tile=info[0], workgroup=info[1], bytes_per_point=info[2], bytes_per_row=info[3])
+
+
+def occupancy_info():
+    """flvis_hip_occupancy_info: dict(workgroup, bytes_per_record, bytes_per_ray, bytes_per_image) -- constants of the build, no device needed"""
+    lib = load_library()
+    info = (C.c_int * 4)()
+    if lib.flvis_hip_occupancy_info(info) != FLVIS_OK:
+        raise FlvisError("occupancy_info failed")
+    return dict(workgroup=info[0], bytes_per_record=info[1], bytes_per_ray=info[2], bytes_per_image=info[3])

@@ -5,7 +5,8 @@ import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
 from ._structs import (FLVIS_LC_FIX_CAND, LC_ROW_WIDTH, LC_TRAJ_ANCHOR, FlvisCfg, FlvisImage, FlvisLcFix, FlvisLcFixIn, FlvisLcLink,
-                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams, cloud_rows, dense_stereo_params, depth_cloud_params)
+                       FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, LcEvent, LcParams, cloud_rows, dense_stereo_params, depth_cloud_params,
+                       occupancy_params, occupancy_rows)
 
 
 def loop_candidate(row, present, lcKFDist, lcKFMaxDist, lcNKFClosest, minScore):
@@ -373,6 +374,32 @@ class LoopCloser:
             hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
         rows = cloud_rows(hx, hn, n_out, cap, ng)
         return rows + (n_out[:ng].copy(), n_drop[:ng].copy(), n_valid[:ng].copy())
+
+    def occupancy(self, groups, first_kf=None, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, occ=None, max_records=0, cap=None,
+                  host=False, centres=True):
+        """flvis_loop_closer_occupancy (depth rigs): per group one occupancy map whose scans are dense_cloud's listed keyframes -- the
+        tracker's logged depth images under the closer's stored poses -- walked in batches of at most max_records records (0: 2^26).
+        occ: an OccupancyParams (None: octomap's defaults).  cap: rows per group (default: found by a call of its own).
+        -> (keys [n_groups] of int64 [k], logodds of float32 [k], centres of float32 [k, 3] or None, n_out, n_rays, n_dropped int64
+        [n_groups], the batches run)."""
+        groups = [[int(s) for s in g] for g in groups]
+        ng = len(groups)
+        ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(g) for g in groups])]), np.int32)
+        seqs = np.ascontiguousarray([s for g in groups for s in g] + [0], np.int32)
+        first = None if first_kf is None else np.ascontiguousarray([int(k) for g in first_kf for k in g] + [0], np.int32)
+        assert first is None or len(first) == len(seqs), "one first keyframe per listed sequence"
+        prm, occ = depth_cloud_params(window, step, z_min, z_max), occupancy_params(occ)
+        n_out, n_rays, n_drop = (np.zeros(max(ng, 1), np.int64) for _ in range(3))
+        batches = C.c_int(0)
+        what = "loop_closer_occupancy" + ("_host" if host else "")
+        fn = getattr(self._lib, "flvis_" + what)
+
+        def call(cap, key, l, xyz):
+            self._ctx._check(fn(self._h, ng, _P(ptr, C.c_int), _P(seqs, C.c_int), _P(first, C.c_int) if first is not None else None,
+                                C.byref(prm), leaf, C.byref(occ), int(max_records), cap, key, l, xyz, _P(n_out, C.c_int64),
+                                _P(n_rays, C.c_int64), _P(n_drop, C.c_int64), C.byref(batches)), what)
+        rows = occupancy_rows(call, ng, cap, n_out, self._ctx.device, host=host, centres=centres)
+        return rows + (n_out[:ng].copy(), n_rays[:ng].copy(), n_drop[:ng].copy(), int(batches.value))
 
     def stereo_cloud(self, groups, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
         """flvis_loop_closer_stereo_cloud (rectified stereo rigs, cam_type 0): dense_cloud on the Z16 images dense stereo

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._loader import FLVIS_OK, FlvisError, load_library
+from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
 
 
 class VocTrainParams(C.Structure):
@@ -184,6 +184,49 @@ def dense_stereo_params(d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1):
     if isinstance(d_min, DenseStereoParams):
         return d_min
     return DenseStereoParams(int(d_min), int(n_disp), int(agg_r), int(uniq), int(lr_tol))
+
+
+class OccupancyParams(C.Structure):
+    """flvis_occupancy_params of include/flvis_hip.h: the float log-odds a hit / a miss observation adds, and the clamp."""
+    _fields_ = [("l_hit", C.c_float), ("l_miss", C.c_float), ("l_min", C.c_float), ("l_max", C.c_float)]
+
+
+def occupancy_params(l_hit=None, l_miss=None, l_min=None, l_max=None):
+    """-> OccupancyParams: flvis_occupancy_params_default (octomap's documented 0.85, -0.4, -2.0, 3.5) with the given fields replaced
+    (l_hit may be an OccupancyParams already)."""
+    if isinstance(l_hit, OccupancyParams):
+        return l_hit
+    p = OccupancyParams()
+    load_library().flvis_occupancy_params_default(C.byref(p))
+    for k, v in (("l_hit", l_hit), ("l_miss", l_miss), ("l_min", l_min), ("l_max", l_max)):
+        if v is not None:
+            setattr(p, k, float(v))
+    return p
+
+
+def occupancy_rows(call, n, cap, n_out, device, host=False, centres=True):
+    """Runs an occupancy call with fitting row buffers.  call(cap, key, l, xyz) makes the C call with the three row pointers (None with
+    cap 0) and fills n_out; cap None: found by a call of its own.  -> (keys [n] of int64 [k], logodds [n] of float32 [k], centres [n] of
+    float32 [k, 3] or None) as numpy arrays, k = min(n_out, cap)."""
+    import torch
+    if cap is None:
+        call(0, None, None, None)
+        cap = int(max(list(n_out[:n]) + [0]))
+    cap = int(cap)
+    shape = (max(n, 1), max(cap, 0))
+    if host:
+        hk, hl = np.zeros(shape, np.int64), np.zeros(shape, np.float32)
+        hx = np.zeros(shape + (3,), np.float32) if centres else None
+        call(cap, _P(hk, C.c_int64), _P(hl, C.c_float), _P(hx, C.c_float) if centres else None)
+    else:
+        key = torch.empty(shape, dtype=torch.int64, device=device)
+        l = torch.empty(shape, dtype=torch.float32, device=device)
+        xyz = torch.empty(shape + (3,), dtype=torch.float32, device=device) if centres else None
+        call(cap, _ptr(key), _ptr(l), _ptr(xyz))
+        hk, hl, hx = key.cpu().numpy(), l.cpu().numpy(), xyz.cpu().numpy() if centres else None
+    k = [int(min(c, cap)) for c in n_out[:n]]
+    return ([hk[g, :k[g]].copy() for g in range(n)], [hl[g, :k[g]].copy() for g in range(n)],
+            [hx[g, :k[g]].copy() for g in range(n)] if centres else None)
 
 
 def cloud_rows(xyz, npts, n_out, cap, n):

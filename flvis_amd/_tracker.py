@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._loader import FlvisError, _P, _ptr
-from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut, cloud_rows, dense_stereo_params, depth_cloud_params
+from ._structs import FlvisCfg, FlvisImage, FlvisKeyframe, FlvisStep, FrameOut, cloud_rows, dense_stereo_params, depth_cloud_params, occupancy_params, occupancy_rows
 
 
 class Tracker:
@@ -476,6 +476,31 @@ class Tracker:
             hx, hn = xyz.cpu().numpy(), npts.cpu().numpy()
         rows = cloud_rows(hx, hn, n_out, cap, n)
         return rows + (n_out[:n].copy(), n_drop[:n].copy(), n_valid[:n].copy())
+
+    def keyframe_log_occupancy(self, streams, window=None, step=1, z_min=0.3, z_max=10.0, leaf=0.08, occ=None, max_records=0, cap=None,
+                               host=False, slices=None, centres=True):
+        """flvis_keyframe_log_occupancy (depth rigs): per listed stream one occupancy map of its logged keyframes' depth images as scans,
+        listed as keyframe_log_depth_cloud lists them and walked in batches of at most max_records records (0: 2^26).  occ: an
+        OccupancyParams (None: octomap's defaults).  cap: rows per stream (default: found by a call of its own).
+        -> (keys [n] of int64 [k], logodds [n] of float32 [k], centres [n] of float32 [k, 3] or None, n_out, n_rays, n_dropped int64 [n],
+        the batches run)."""
+        sl = [int(s) for s in streams]
+        n = len(sl)
+        arr = np.ascontiguousarray(sl + [0], np.int32)
+        sli = None if slices is None else np.ascontiguousarray(list(slices) + [(0, 0)], np.int32).reshape(-1, 2)
+        assert sli is None or len(sli) == n + 1, "one slice per listed stream"
+        prm, occ = depth_cloud_params(window, step, z_min, z_max), occupancy_params(occ)
+        n_out, n_rays, n_drop = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        batches = C.c_int(0)
+        what = "keyframe_log_occupancy" + ("_host" if host else "")
+        fn = getattr(self.lib, "flvis_" + what)
+
+        def call(cap, key, l, xyz):
+            self.ctx._check(fn(self.ctx._h, n, _P(arr, C.c_int), _P(sli, C.c_int) if sli is not None else None, C.byref(prm), leaf, C.byref(occ),
+                               int(max_records), cap, key, l, xyz, _P(n_out, C.c_int64), _P(n_rays, C.c_int64), _P(n_drop, C.c_int64),
+                               C.byref(batches)), what)
+        rows = occupancy_rows(call, n, cap, n_out, self.ctx.device, host=host, centres=centres)
+        return rows + (n_out[:n].copy(), n_rays[:n].copy(), n_drop[:n].copy(), int(batches.value))
 
     def keyframe_log_stereo_cloud(self, streams, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, depth_factor=1000.0, **cloud):
         """flvis_keyframe_log_stereo_cloud (rectified stereo rigs, cam_type 0): keyframe_log_depth_cloud on the Z16 images dense stereo

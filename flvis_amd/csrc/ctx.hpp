@@ -28,6 +28,8 @@ struct flvis_ctx {
   int64_t mc_stats[4] = {0, 0, 0, 0};  // the last flvis_hip_voxel_cloud call: sort passes run / skipped, workspace bytes, input points
   int dc_timing = 0;                  // flvis_hip_depth_cloud_times: time the stages of the dense calls
   double dc_ms[4] = {0, 0, 0, 0};     // ... the last timed call's count, keys, sort, rows
+  double oc_ms[4] = {0, 0, 0, 0};     // the last timed occupancy call's count, emit, sort, reduce (summed over its batches)
+  int64_t oc_stats[4] = {0, 0, 0, 0};  // the last occupancy call: records, rays, batches, workspace bytes
   std::string orb_pattern;  // the BRIEF pattern currently resident in the `orb_pattern` scratch buffer (1024 bytes) or empty
 
   // returns a device buffer of at least `bytes` bytes (contents undefined after growth)

@@ -47,6 +47,7 @@
 #include "lc_traj.hpp"
 #include "loop_kernels.hpp"
 #include "map_cloud.hpp"
+#include "occupancy.hpp"
 #include "rectify.hpp"
 #include "pipeline_host.hpp"
 
@@ -1522,6 +1523,93 @@ int flvis_loop_closer_dense_cloud_host(flvis_loop_closer* lc, int n_groups, cons
                       h_n_out, h_n_dropped, h_n_valid, false);
   if (rc != FLVIS_OK) return rc;
   return flvis::mc_host_rows_fetch(lc->ctx, what, n_groups, out_cap, h_n_out, d_xyz, d_npts, h_xyz, h_npts);
+}
+
+// The occupancy map (include/flvis_hip.h): lc_dense_cloud's lists -- the tracker's logged depth images under the closer's stored poses --
+// through occupancy.hip's batched walk.  Reads the log, the pose database and the sequences' configs; writes nothing of theirs.
+static int lc_occupancy(flvis_loop_closer* lc, const char* what, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                        const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int64_t max_records,
+                        const flvis::OcOut& out, int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped, int* h_n_batches, bool check_only) {
+  flvis_ctx* ctx = lc->ctx;
+  const std::string pre = std::string(what) + ": ";
+  auto bad = [&](const std::string& m) { return ctx->fail(FLVIS_ERR_INVALID_ARG, pre + m); };
+  flvis::Pipeline* pl = ctx->pipe;
+  if (!pl || pl->kfl.cap <= 0) return bad("the closer's context holds no tracker, or its keyframe log is off (flvis_keyframe_log_enable)");
+  if (pl->S != lc->S || pl->kfl.w != lc->w || pl->kfl.h != lc->h || pl->cfg.cam_type != lc->cam_type)
+    return ctx->fail(FLVIS_ERR_CONFIG, pre + "the tracker's n_streams, image_width, image_height and cam_type must be the closer's");
+  if (lc->cam_type != 2) return ctx->fail(FLVIS_ERR_CONFIG, pre + "the rig has no depth image");
+  if (!prm) return bad("NULL prm");
+  std::vector<int> range2;
+  int rc = lc_map_cloud_ranges(lc, n_groups, h_group_ptr, h_seq, h_n_out, range2);
+  if (rc != FLVIS_OK) return rc;
+  const int E = h_group_ptr[n_groups];
+  std::vector<double> cam5(5 * (size_t)std::max(E, 1));
+  for (int e = 0; e < E; e++) {
+    const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
+    if (first < 0 || first > lc->seq[s].n) return bad("a first keyframe outside [0, stored keyframes]");
+    const flvis_cfg& g = lc->cfgs[s];
+    const double v[5] = {g.P0[0], g.P0[5], g.P0[2], g.P0[6], g.depth_factor};
+    memcpy(&cam5[5 * (size_t)e], v, sizeof(v));
+  }
+  std::string why;
+  rc = flvis::dc_check_sampling(lc->w, lc->h, prm, E, cam5.data(), &why);
+  if (rc == FLVIS_OK) rc = flvis::oc_check_values(leaf, occ, &why);
+  if (rc != FLVIS_OK) return ctx->fail(rc, pre + why);
+  if (max_records < 0 || out.out_cap < 0 || ((!out.d_key || !out.d_l) && out.out_cap > 0))
+    return bad("max_records >= 0 and out_cap >= 0 with rows to write to");
+  if (check_only) return FLVIS_OK;
+  flvis::KfLogRec rec{};
+  int S = 0, cam = 0;
+  std::vector<long long> logged, dropped;
+  rc = flvis::kf_log_settle(ctx, what, rec, S, cam, logged, dropped);
+  if (rc != FLVIS_OK) return rc;
+  std::vector<int> eptr((size_t)n_groups + 1), img, pose, camv, item_seq, item_entry;
+  for (int g = 0; g < n_groups; g++) {
+    eptr[g] = (int)img.size();
+    for (int e = h_group_ptr[g]; e < h_group_ptr[g + 1]; e++) {
+      const int s = h_seq[e], first = h_first_kf ? h_first_kf[e] : 0;
+      const long long n = std::min<long long>(logged[s], (long long)lc->seq[s].n - first);
+      for (long long i = 0; i < n; i++) {
+        if (img.size() >= (size_t)INT_MAX) return ctx->fail(FLVIS_ERR_CAPACITY, pre + "2^31 listed keyframes or more");
+        img.push_back((int)((long long)s * rec.cap + i));
+        pose.push_back((int)((long long)s * lc->maxkf + first + i));  // (first + i < stored <= maxkf)
+        camv.push_back(e), item_seq.push_back(s), item_entry.push_back((int)i);
+      }
+    }
+  }
+  eptr[n_groups] = (int)img.size();
+  const flvis::OcLists L{reinterpret_cast<const uint16_t*>(rec.img1), rec.w, rec.h, lc->db_T, 7, n_groups, eptr.data(), img.data(), pose.data(),
+                         camv.data(), E, cam5.data()};
+  return flvis::oc_batched(ctx, what, L, prm, leaf, occ, max_records, out, h_n_out, h_n_rays, h_n_dropped, h_n_batches, [&](int e) {
+    return "entry " + std::to_string(item_entry[e]) + " of stream " + std::to_string(item_seq[e]);
+  });
+}
+
+int flvis_loop_closer_occupancy(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int64_t max_records,
+                                int out_cap, int64_t* d_key, float* d_l, float* d_xyz, int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped,
+                                int* h_n_batches) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  return lc_occupancy(lc, "loop_closer_occupancy", n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, occ, max_records,
+                      flvis::OcOut{out_cap, d_key, d_l, d_xyz}, h_n_out, h_n_rays, h_n_dropped, h_n_batches, false);
+}
+
+int flvis_loop_closer_occupancy_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                     const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int64_t max_records,
+                                     int out_cap, int64_t* h_key, float* h_l, float* h_xyz, int64_t* h_n_out, int64_t* h_n_rays,
+                                     int64_t* h_n_dropped, int* h_n_batches) {
+  if (!lc) return FLVIS_ERR_INVALID_ARG;
+  const char* what = "loop_closer_occupancy_host";
+  int rc = lc_occupancy(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, occ, max_records, flvis::OcOut{out_cap, h_key, h_l, h_xyz},
+                        h_n_out, h_n_rays, h_n_dropped, h_n_batches, true);
+  if (rc != FLVIS_OK) return rc;
+  flvis::OcOut dev;
+  rc = flvis::oc_host_alloc(lc->ctx, what, n_groups, out_cap, h_xyz != nullptr, &dev);
+  if (rc != FLVIS_OK) return rc;
+  rc = lc_occupancy(lc, what, n_groups, h_group_ptr, h_seq, h_first_kf, prm, leaf, occ, max_records, dev, h_n_out, h_n_rays, h_n_dropped, h_n_batches,
+                    false);
+  if (rc != FLVIS_OK) return rc;
+  return flvis::oc_host_fetch(lc->ctx, what, n_groups, dev, h_n_out, h_key, h_l, h_xyz);
 }
 
 int flvis_loop_closer_stereo_cloud(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,

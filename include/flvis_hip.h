@@ -1527,6 +1527,104 @@ int flvis_loop_closer_unrect_stereo_cloud_host(flvis_loop_closer* lc, int n_grou
                                                const flvis_depth_cloud_params* prm, double leaf, int min_points, int out_cap, float* h_xyz,
                                                int* h_npts, int64_t* h_n_out, int64_t* h_n_dropped, int64_t* h_n_valid);
 
+/* ---- an occupancy map from depth keyframes: free space by a ray walk on the device -------------------------------------------------------
+ * (The reference's octomap feeder, src/octofeeder/octomap_feeder.cpp:18-80, hands its cloud and the sensor pose to an octomap server, which
+ * casts a ray to every point.  The reference itself has no occupancy code: the rule below is this project's own, defined bit for bit;
+ * tests/_occupancy.py restates it twice in numpy.)
+ * Inputs: d_depth, d_T_c_w7, n_img, w, h, the ranges (h_map_ptr [n_maps + 1], h_range2), one camera per RANGE (h_cam5), the sampling `prm`
+ *   and the validity rule are flvis_hip_depth_cloud's, maps for clouds.  Every LISTING of an image is a SCAN of its own (an image listed
+ *   twice is two scans); a map's scans are numbered 0, 1, .. in canonical order: ranges in the caller's order, images ascending in a range.
+ * All arithmetic below is fp64 without contraction unless float is stated.
+ * Ray: one per valid sample.  Its end p is the sample's map-frame point, q_rotate(q_conj(q), p_c - t) with flvis_hip_depth_cloud's p_c:
+ *   bit for bit the point that call makes.  Its origin o is p_c = (0, 0, 0) through the same function (so o.x starts from 0.0 - t.x).
+ * Voxel index per axis: floor(x / leaf), one division and a floor, leaf > 0.  With io, ie the index triples of o and p: the ray is DROPPED
+ *   (counted in h_n_dropped and nowhere else) if any coordinate of o or p is not finite or any index is outside [-2^20, 2^20).
+ * Walk (integer-bounded: rounding cannot make it miss its end): per axis a, rem[a] = |ie[a] - io[a]|, sgn[a] = ie[a] >= io[a] ? 1 : -1, and
+ *   for the axes with rem[a] > 0
+ *     tmax[a] = ((double)(io[a] + (sgn[a] > 0 ? 1 : 0)) * leaf - o[a]) / (p[a] - o[a]),   tdel[a] = leaf / fabs(p[a] - o[a]).
+ *   The current cell c starts at io.  Exactly rem[0] + rem[1] + rem[2] steps follow.  A step picks, among the axes with rem[a] > 0 NOW, the
+ *   one with the smallest tmax: the axes are looked at in the order x, y, z and a later axis replaces the pick only if its tmax is
+ *   strictly less (<), so a tie goes to the lowest axis.  Then c[a] += sgn[a], rem[a] -= 1, tmax[a] = tmax[a] + tdel[a].  The walk ends in ie.
+ * Cells of a ray: its FREE cells are the cell before every step (the origin's cell and every visited cell but the last); its HIT cell is
+ *   ie.  A ray of zero steps has a hit and no free cell.
+ * Observation: per scan and voxel at most one -- a hit if any ray of the scan ends in the voxel, else a miss if any ray of the scan has it
+ *   as a free cell (octomap's insertPointCloud: one update per scan, occupied wins).
+ * Value (float): l starts from the prior's value of the voxel, or 0.0f.  For every scan that observes the voxel, in scan order:
+ *   l = l + (hit ? l_hit : l_miss) as one float addition, then l = l < l_min ? l_min : (l > l_max ? l_max : l).  The clamp makes the order
+ *   matter; the scan order is the definition.
+ * Output, per map m: one row per voxel that is observed or in the prior, ascending by key; key = (iz + 2^20) << 42 | (iy + 2^20) << 21 |
+ *   (ix + 2^20) (flvis_hip_voxel_cloud's sort key) in d_key [n_maps][out_cap], the value in d_l [n_maps][out_cap], and in d_xyz
+ *   [n_maps][out_cap][3] (may be NULL) the centre (float)(((double)i + 0.5) * leaf) per axis.  h_n_out [n_maps]: the full row count (at most
+ *   out_cap rows are written); h_n_rays, h_n_dropped [n_maps] (may be NULL): rays cast and rays dropped.
+ * Prior: map m may start from the first h_n_prior[m] rows of d_prior_key / d_prior_l [n_maps][prior_cap] (device; all of d_prior_key,
+ *   d_prior_l, h_n_prior may be NULL and prior_cap 0: no prior).  A map's prior keys must ascend strictly and be non-negative: checked on
+ *   the device.  That they are keys of the same leaf is the caller's contract.  The prior may not alias the output.  A prior voxel that no
+ *   scan observes comes out unchanged.
+ * Chaining: scans 0 .. k - 1 in one call, then scans k .. n - 1 with that call's output as prior, give bit for bit the map of one call over
+ *   scans 0 .. n - 1 (the value rule is a left fold over the scans, and the prior stands for a scan before scan 0).
+ * Reproducibility: several maps in one call give the bits of as many single calls; a second run gives the same bits.  No atomic decides a
+ *   position or a value (positions are prefix sums; the "any hit" of a scan is an OR, which no order changes).
+ * Method: every cell of every ray is a record (key, canonical index, scan << 1 | hit), written at its exact canonical position (map, scan,
+ *   raster, step; a ray's record count |ie - io|_1 + 1 is known without walking, so positions are prefix sums of a count pass);
+ *   flvis_hip_voxel_cloud's stable radix sort; then runs of one (voxel, scan) collapse to observations IN PARALLEL and one lane per voxel
+ *   applies its observations (at most one per scan, plus the prior) in order.  The call waits for its counts, for the byte table of the
+ *   sort and for the maps' row counts.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: leaf <= 0 or not finite; l_hit <= 0, l_miss >= 0, l_min >= 0, l_max <= 0 or any of them
+ *   not finite; h_n_prior[m] outside [0, prior_cap]; a NULL prior table with a non-zero count; a prior that overlaps the output; NULL occ,
+ *   or NULL d_key or d_l with out_cap > 0; and every argument error of flvis_hip_depth_cloud.  flvis_occupancy_check is the host part of
+ *   these checks on its own (no context, no pointer checks of device arrays).  A prior whose keys do not ascend: FLVIS_ERR_INVALID_ARG after
+ *   the device check, with no row written.
+ * FLVIS_ERR_CAPACITY: 2^31 - 1 records or more in one call (prior rows count as records), known after the count pass, before the record
+ *   buffers are allocated.
+ * Workspace: the context's, grown on demand and kept: 32 bytes per record (two key and two index buffers of the sort, the payload, and the
+ *   voxel rank of an observation; observations reuse the sort's second buffers), nothing per ray (a ray is derived from its sample in the
+ *   count and in the emit pass, never stored), 20 bytes per listed image, 20 per listed image and row chunk, 44 per map and the sort's
+ *   fixed tables.  flvis_hip_occupancy_info: h_info4 = workgroup size, workspace bytes per record, per ray, per listed image.  Host only.
+ *   A failed allocation returns FLVIS_ERR_HIP and leaves the context usable.
+ * flvis_hip_occupancy_stats: h_stats4 = records (prior rows included), rays, batches, workspace bytes of the context's last occupancy
+ *   call; h_ms4 = wall-clock milliseconds of count, emit, sort, reduce, summed over the call's batches, kept while
+ *   flvis_hip_depth_cloud_times is enabled (the call then waits behind every stage).  Either may be NULL. */
+typedef struct flvis_occupancy_params {
+  float l_hit, l_miss, l_min, l_max;  /* log-odds added per hit / miss observation, and the clamp */
+} flvis_occupancy_params;
+void flvis_occupancy_params_default(flvis_occupancy_params* p);  /* 0.85f, -0.4f, -2.0f, 3.5f: octomap's documented log-odds */
+int flvis_hip_occupancy(flvis_ctx* ctx, const uint16_t* d_depth, const double* d_T_c_w7, int n_img, int w, int h, int n_maps,
+                        const int* h_map_ptr /* [n_maps + 1] */, const int* h_range2, const double* h_cam5,
+                        const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, const int64_t* d_prior_key,
+                        const float* d_prior_l, int prior_cap, const int64_t* h_n_prior, int out_cap, int64_t* d_key, float* d_l, float* d_xyz,
+                        int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped);
+int flvis_occupancy_check(int n_img, int w, int h, int n_maps, const int* h_map_ptr, const int* h_range2, const double* h_cam5,
+                          const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int prior_cap,
+                          const int64_t* h_n_prior, int out_cap);
+int flvis_hip_occupancy_info(int* h_info4);
+int flvis_hip_occupancy_stats(flvis_ctx* ctx, int64_t* h_stats4, double* h_ms4);
+/* The keyframe log as occupancy maps (depth rigs, cam_type 2; a stereo rig: FLVIS_ERR_CONFIG): map c holds the logged keyframes of stream
+ * h_stream[c] as its scans, listed, posed and calibrated exactly as flvis_keyframe_log_depth_cloud lists them (h_slice2 included).
+ * The scans are walked in BATCHES whose scan records stay at or below max_records (0: 2^26; negative: FLVIS_ERR_INVALID_ARG): one count
+ * pass over every listed keyframe gives the records of every scan, read once; scans are taken in canonical order, map after map, while
+ * they fit; each batch is one flvis_hip_occupancy over all maps with the map so far as the prior, carried in two buffers of the context
+ * that a batch writes and the next reads.  By the chaining property the result is bit for bit the one-call result, and the workspace is
+ * bounded by max_records and the size of the maps, not by the number of keyframes.  *h_n_batches (may be NULL): the batches run.  A single
+ * scan above max_records: FLVIS_ERR_CAPACITY, the message names the stream and the entry.
+ * No image leaves HBM, nothing is added to the frame chain, the log and the tracker are only read: a run that made the call equals one that
+ * did not, bit for bit.  Outputs as flvis_hip_occupancy's, d_key / d_l / d_xyz [n][out_cap]; the _host form stages them in the context.
+ * The closer's form: the groups, stored poses, cameras and conditions of flvis_loop_closer_dense_cloud, so after process,
+ * flvis_loop_closer_set_drift or flvis_loop_closer_merge the map is in the map or the anchor's frame; no side effect on the closer. */
+int flvis_keyframe_log_occupancy(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm, double leaf,
+                                 const flvis_occupancy_params* occ, int64_t max_records, int out_cap, int64_t* d_key, float* d_l, float* d_xyz,
+                                 int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped, int* h_n_batches);
+int flvis_keyframe_log_occupancy_host(flvis_ctx* ctx, int n, const int* h_stream, const int* h_slice2, const flvis_depth_cloud_params* prm,
+                                      double leaf, const flvis_occupancy_params* occ, int64_t max_records, int out_cap, int64_t* h_key, float* h_l,
+                                      float* h_xyz, int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped, int* h_n_batches);
+int flvis_loop_closer_occupancy(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int64_t max_records,
+                                int out_cap, int64_t* d_key, float* d_l, float* d_xyz, int64_t* h_n_out, int64_t* h_n_rays, int64_t* h_n_dropped,
+                                int* h_n_batches);
+int flvis_loop_closer_occupancy_host(flvis_loop_closer* lc, int n_groups, const int* h_group_ptr, const int* h_seq, const int* h_first_kf,
+                                     const flvis_depth_cloud_params* prm, double leaf, const flvis_occupancy_params* occ, int64_t max_records,
+                                     int out_cap, int64_t* h_key, float* h_l, float* h_xyz, int64_t* h_n_out, int64_t* h_n_rays,
+                                     int64_t* h_n_dropped, int* h_n_batches);
+
 #ifdef __cplusplus
 }
 #endif

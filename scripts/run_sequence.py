@@ -58,6 +58,12 @@ defaults, depth in millimetres), then as --dense-cloud (flvis_keyframe_log_stere
 in one run: a rig has a depth image or a second view.  The EuRoC rig (cam_type 1) logs an unrectified pair: it is rectified on the device
 in front of the matcher (flvis_keyframe_log_unrect_stereo_cloud / flvis_loop_closer_unrect_stereo_cloud).
 
+--occupancy FILE.ply [--occupancy-leaf L] : (hip, depth rigs -- cam_type 2 -- with --batch) the occupancy map of the same logged
+keyframes: every valid sample of --dense-cloud's sampling is a ray from the camera, the voxels it crosses are seen free and its end voxel
+occupied, one clamped log-odds value per voxel of L metres (default 0.08; flvis_keyframe_log_occupancy, or with --loop-closing
+flvis_loop_closer_occupancy under the closer's stored poses).  The file holds the centres of the voxels with log-odds > 0; the JSON line
+counts occupied, free and all voxels.  Goes with or without --dense-cloud; the log holds the whole run as for that option.
+
 --batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
 keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
 device (flvis_loop_closer_add_logged: the images the tracker worked on, img0 after equalizeHist where the rig uses it, as the KeyFrame
@@ -97,6 +103,8 @@ def main():
     ap.add_argument("--dense-stereo", default=None)
     ap.add_argument("--stereo-disp", type=int, default=64)
     ap.add_argument("--dense-step", type=int, default=7)
+    ap.add_argument("--occupancy", default=None)
+    ap.add_argument("--occupancy-leaf", type=float, default=0.08)
     ap.add_argument("--lc-traj-out", default=None)
     ap.add_argument("--lc-imu-out", default=None)
     ap.add_argument("--lc-traj-mode", choices=["anchor", "blend"], default="anchor")
@@ -117,7 +125,10 @@ def main():
         ap.error("--dense-cloud needs --backend hip, --batch N and --dense-step >= 1")
     if args.dense_stereo and (args.dense_cloud or not (args.batch and args.backend == "hip" and args.dense_step >= 1)):
         ap.error("--dense-stereo needs --backend hip, --batch N and --dense-step >= 1, and goes without --dense-cloud")
-    dense_out = args.dense_cloud or args.dense_stereo              # (either: the log keeps the whole run)
+    if args.occupancy and (args.dense_stereo or not (args.batch and args.backend == "hip" and args.dense_step >= 1 and args.occupancy_leaf > 0)):
+        ap.error("--occupancy needs --backend hip, --batch N, --dense-step >= 1 and --occupancy-leaf > 0, and goes without --dense-stereo")
+    dense_out = args.dense_cloud or args.dense_stereo
+    keep_log = dense_out or args.occupancy                         # (any of them: the log keeps the whole run)
     seq = traj_io.open_sequence(args.sequence)
     kitti = isinstance(seq, traj_io.KittiSequence)
     stamps, pos, quat = [], [], []
@@ -188,23 +199,23 @@ def main():
             closer = flvis_amd.LoopCloser(ctx, cfg, flvis_amd.load_lc_params(args.config), n_streams=1, max_keyframes=max(n, 1))
             if args.lc_stereo_unrect:
                 closer.set_stereo_unrect(True)                                 # (FlvisError on a rig that is not cam_type 1)
-        if args.dense_cloud and cfg.cam_type != 2:
-            ap.error("--dense-cloud: the config's rig has no depth image (cam_type 2)")
+        if (args.dense_cloud or args.occupancy) and cfg.cam_type != 2:
+            ap.error("--dense-cloud / --occupancy: the config's rig has no depth image (cam_type 2)")
         if args.dense_stereo and cfg.cam_type not in (0, 1):
             ap.error("--dense-stereo: the config's rig is no stereo pair (cam_type 0 or 1)")
         if args.batch:
-            trk.keyframe_log_enable(max(n, 1) if dense_out else args.batch)  # (the dense map reads the whole run's log at the end)
+            trk.keyframe_log_enable(max(n, 1) if keep_log else args.batch)  # (the dense map reads the whole run's log at the end)
             imu_type = {1: 1, 3: 0, 5: 2, 0: 0, 2: 2, 4: 3}[cfg.type_of_vi]
             dropped_logged, chunk = 0, []
 
             def flush(last=False):
                 """the chunk through run_steps; its keyframes from the log into the closer; the log cleared"""
                 nonlocal dropped_logged
-                if not chunk and not (last and dense_out):
+                if not chunk and not (last and keep_log):
                     return
                 if chunk:
                     trk.run_steps(chunk, with_local_map=args.local_map)
-                if dense_out and not last:                              # (the log keeps the run; the closer gets it after the last chunk)
+                if keep_log and not last:                               # (the log keeps the run; the closer gets it after the last chunk)
                     ctx.synchronize()
                     del chunk[:]
                     return
@@ -212,9 +223,9 @@ def main():
                 dropped_logged += info["dropped"]
                 if closer is not None:
                     kf_stamps.extend(trk.keyframe_log_get(0, i, images=False)["stamp"] for i in range(info["logged"]))
-                    rounds = max(info["logged"], 1) if dense_out else args.batch
+                    rounds = max(info["logged"], 1) if keep_log else args.batch
                     lc_events.extend(r[0] for r in closer.add_logged(process=True, max_rounds=rounds))
-                if not dense_out:
+                if not keep_log:
                     trk.keyframe_log_clear([0])
                 del chunk[:]
         for t, i0, i1, imu in seq.frames(0, n):
@@ -282,6 +293,15 @@ def main():
             dense_cloud = {"points": int(got[2][0]), "dropped": int(got[3][0]), "valid_samples": int(got[4][0]), "leaf": args.leaf,
                            "step": args.dense_step, "keyframes": trk.keyframe_log_info(0)["logged"],
                            "frame": "map" if closer is not None else "odometry", "from": "stereo" if args.dense_stereo else "depth"}
+        occupancy = None
+        if args.occupancy:
+            sampling = dict(step=args.dense_step, z_min=0.3, z_max=float(cfg.dr_para[1]), leaf=args.occupancy_leaf)
+            got = closer.occupancy([[0]], **sampling) if closer is not None else trk.keyframe_log_occupancy([0], **sampling)
+            l, centres = got[1][0], got[2][0]
+            traj_io.write_ply(args.occupancy, centres[l > 0])
+            occupancy = {"occupied": int((l > 0).sum()), "free": int((l < 0).sum()), "voxels": int(got[3][0]), "rays": int(got[4][0]),
+                         "dropped_rays": int(got[5][0]), "batches": got[6], "leaf": args.occupancy_leaf, "step": args.dense_step,
+                         "keyframes": trk.keyframe_log_info(0)["logged"], "frame": "map" if closer is not None else "odometry"}
         lm_cloud = None
         if args.lm_cloud:
             trk.local_map_counts()                                             # (drains the keyframe queue: the last optimisations too)
@@ -303,6 +323,8 @@ def main():
             wants_cloud = False                                                # (a yaml without the key: the reference would refuse it)
         if dense_out:
             out["dense_cloud"] = dense_cloud
+        if args.occupancy:
+            out["occupancy"] = occupancy
         if args.lm_cloud:
             out["local_map_cloud"] = lm_cloud
         elif wants_cloud:
