@@ -13,8 +13,8 @@ from ._structs import (FLVIS_LC_ALL_MAPS, FLVIS_LC_FIX_CAND, LC_ROW_WIDTH, LC_RO
                        FlvisLcLinkQuery, FlvisLcMerge, FlvisLcTrajJob, FlvisStep, FrameOut, LcEvent, LcParams, OrbParams,
                        VocTrainParams, config_get_bool, load_config, load_lc_params, orb_default_pattern,
                        DepthCloudParams, depth_cloud_params, octomap_feeder_params, DenseStereoParams, dense_stereo_params,
-                       OccupancyParams, occupancy_params)
+                       OccupancyParams, occupancy_params, OccupancyCastParams, occupancy_cast_params)
 from ._vocfile import TrainedVocabulary, convert_vocabulary_file, read_vocabulary_file, save_vocabulary_file  # noqa: F401
-from ._context import Context, occupancy_info, voxel_cloud_info  # noqa: F401
+from ._context import OCCUPANCY_CAST_STATUS, Context, occupancy_info, voxel_cloud_info  # noqa: F401
 from ._loop_closer import LoopCloser, _link_dict, links_from_fix, links_reverse, loop_candidate  # noqa: F401
 from ._tracker import Tracker  # noqa: F401

@@ -6,7 +6,7 @@ import numpy as np
 
 from ._loader import FLVIS_OK, FlvisError, _P, _ptr, load_library
 from ._structs import (LC_ROW_WIDTH, FlvisCfg, FlvisLcTrajJob, OrbParams, VocTrainParams, dense_stereo_params, depth_cloud_params,
-                       occupancy_params, occupancy_rows)
+                       occupancy_cast_params, occupancy_params, occupancy_rows)
 from ._vocfile import TrainedVocabulary
 
 
@@ -498,6 +498,77 @@ class Context:
         self._check(self._lib.flvis_hip_occupancy_stats(self._h, st, ms), "occupancy_stats")
         return dict(records=int(st[0]), rays=int(st[1]), batches=int(st[2]), workspace_bytes=int(st[3]), ms=tuple(float(v) for v in ms))
 
+    def occupancy_cast(self, maps, segments, leaf, thres=0.0, ignore_unknown=False, max_cells=0, host=False, outputs=True, rows=None):
+        """flvis_hip_occupancy_cast: the first obstacle or unknown cell along segments through occupancy maps.  maps: per map (keys
+        int64 [k], logodds float32 [k]) as occupancy returns them and prior= takes them, numpy arrays that are uploaded -- or, for maps
+        that live on the device, ONE pair of device tensors (key int64 [n_maps, cap], logodds float32 [n_maps, cap]) with rows = the
+        maps' row counts.  segments: per map float64 [q, 6] (o.x o.y o.z p.x p.y p.z in the map's frame; q may be 0).  thres (or an
+        OccupancyCastParams), ignore_unknown, max_cells: the header's rule.  host: the _host form (segments and outputs cross as host
+        arrays).  outputs False: only status is asked for (the other arrays are NULL).
+        -> (status int32, k int32, cell int64, row int32, l float32, t float64: each a list of per-map numpy arrays [q], None for one
+        not asked for; counts int64 [n_maps, 5] per status END, OCCUPIED, UNKNOWN, DROPPED, LIMIT)."""
+        import torch
+        prm = occupancy_cast_params(thres, ignore_unknown, max_cells)
+        if rows is not None:
+            key, lo = maps
+            assert key.is_cuda and key.dtype == torch.int64 and key.is_contiguous() and key.dim() == 2
+            assert lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.shape == key.shape
+            nm, cap = int(key.shape[0]), int(key.shape[1])
+            n_rows = np.ascontiguousarray(list(rows) + [0], np.int64)
+            assert len(n_rows) == nm + 1, "one row count per map"
+        else:
+            nm = len(maps)
+            n_rows = np.ascontiguousarray([len(k) for k, _ in maps] + [0], np.int64)
+            cap = int(max(n_rows.max(), 1))
+            hk, hl = np.zeros((max(nm, 1), cap), np.int64), np.zeros((max(nm, 1), cap), np.float32)
+            for m, (k, l) in enumerate(maps):
+                hk[m, :len(k)], hl[m, :len(k)] = np.asarray(k, np.int64), np.asarray(l, np.float32)
+            key, lo = torch.from_numpy(hk).to(self.device), torch.from_numpy(hl).to(self.device)
+        assert len(segments) == nm, "one array of segments per map"
+        segs = [np.ascontiguousarray(s, np.float64).reshape(-1, 6) for s in segments]
+        qptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(s) for s in segs])]), np.int32)
+        nq = int(qptr[-1])
+        seg = np.ascontiguousarray(np.concatenate(segs + [np.zeros((1, 6))]))
+        counts = np.zeros((max(nm, 1), 5), np.int64)
+        kinds = (np.int32, np.int32, np.int64, np.int32, np.float32, np.float64)
+        want = [True] + [bool(outputs)] * 5
+        fn = self._lib.flvis_hip_occupancy_cast_host if host else self._lib.flvis_hip_occupancy_cast
+        if host:
+            out = [np.zeros(nq + 1, t) if w else None for t, w in zip(kinds, want)]
+            ptrs = [o.ctypes.data_as(C.c_void_p) if o is not None else None for o in out]
+            sp = seg.ctypes.data_as(C.c_void_p)
+        else:
+            tk = (torch.int32, torch.int32, torch.int64, torch.int32, torch.float32, torch.float64)
+            dev = [torch.zeros(nq + 1, dtype=t, device=self.device) if w else None for t, w in zip(tk, want)]
+            dseg = torch.from_numpy(seg).to(self.device)
+            ptrs, sp = [_ptr(o) for o in dev], _ptr(dseg)
+        self._check(fn(self._h, nm, _ptr(key), _ptr(lo), cap, _P(n_rows, C.c_int64), float(leaf), C.byref(prm), sp, _P(qptr, C.c_int),
+                       *ptrs, _P(counts, C.c_int64)), "occupancy_cast_host" if host else "occupancy_cast")
+        if not host:
+            out = [o.cpu().numpy() if o is not None else None for o in dev]
+        per = [[o[qptr[m]:qptr[m + 1]].copy() for m in range(nm)] if o is not None else None for o in out]
+        return tuple(per) + (counts[:nm].copy(),)
+
+    def occupancy_lookup(self, maps, points, leaf, thres=0.0, rows=None):
+        """The state of the voxel of every point: occupancy_cast of the segments p -> p (zero steps, ignore_unknown 0), octomap's
+        search().  points: per map float64 [q, 3].  -> (status [n_maps] of int32 [q]: 0 free, 1 occupied, 2 unknown, 3 dropped; row
+        int32 [q], -1 when absent; l float32 [q], 0 when absent; counts int64 [n_maps, 5])."""
+        pts = [np.asarray(p, np.float64).reshape(-1, 3) for p in points]
+        r = self.occupancy_cast(maps, [np.concatenate([p, p], axis=1) for p in pts], leaf, thres=thres, rows=rows)
+        return r[0], r[3], r[4], r[6]
+
+    def occupancy_cast_lookup(self, plain=False):
+        """flvis_hip_occupancy_cast_lookup: how the casts of this context find a cell's row from now on -- the line directory (default)
+        or, plain=True, one binary search over all rows per cell: the baseline, with the same bits."""
+        self._check(self._lib.flvis_hip_occupancy_cast_lookup(self._h, int(bool(plain))), "occupancy_cast_lookup")
+
+    def occupancy_cast_stats(self):
+        """flvis_hip_occupancy_cast_stats -> dict(queries, cells, index_bytes, workspace_bytes, ms=(index build, walk)) of the context's
+        last cast; the milliseconds are kept while depth_cloud_times is enabled."""
+        st, ms = (C.c_int64 * 4)(), (C.c_double * 2)()
+        self._check(self._lib.flvis_hip_occupancy_cast_stats(self._h, st, ms), "occupancy_cast_stats")
+        return dict(queries=int(st[0]), cells=int(st[1]), index_bytes=int(st[2]), workspace_bytes=int(st[3]), ms=tuple(float(v) for v in ms))
+
     def dense_stereo(self, img0, img1, bf, depth_factor=1000.0, d_min=0, n_disp=64, agg_r=2, uniq=10, lr_tol=1, want_disp=True, want_z=True):
         """flvis_hip_dense_stereo: img0, img1 uint8 [n_img, h, w] device tensors, a RECTIFIED pair per image (a point at column u of
         img0 lies at u - d of img1).  bf (focal length times baseline, pixel-metres) and depth_factor (the Z16 unit): a number each for
@@ -824,6 +895,9 @@ def voxel_cloud_info():
     if lib.flvis_hip_voxel_cloud_info(info) != FLVIS_OK:
         raise FlvisError("voxel_cloud_info failed")
     return dict(sort_tile=info[0], workgroup=info[1], bytes_per_point=info[2], bytes_per_row=info[3])
+
+
+OCCUPANCY_CAST_STATUS = ("end", "occupied", "unknown", "dropped", "limit")   # flvis_hip_occupancy_cast's d_status 0 .. 4
 
 
 def occupancy_info():

@@ -204,6 +204,28 @@ def occupancy_params(l_hit=None, l_miss=None, l_min=None, l_max=None):
     return p
 
 
+class OccupancyCastParams(C.Structure):
+    """flvis_occupancy_cast_params of include/flvis_hip.h: a row is OCCUPIED when l > thres; ignore_unknown 1 lets a walk pass UNKNOWN
+    cells; max_cells > 0 stops a walk with LIMIT before the test of that cell."""
+    _fields_ = [("thres", C.c_float), ("ignore_unknown", C.c_int), ("max_cells", C.c_int)]
+
+
+def occupancy_cast_params(thres=None, ignore_unknown=None, max_cells=None):
+    """-> OccupancyCastParams: flvis_occupancy_cast_params_default (0.0, 0, 0) with the given fields replaced (thres may be an
+    OccupancyCastParams already)."""
+    if isinstance(thres, OccupancyCastParams):
+        return thres
+    p = OccupancyCastParams()
+    load_library().flvis_occupancy_cast_params_default(C.byref(p))
+    if thres is not None:
+        p.thres = float(thres)
+    if ignore_unknown is not None:
+        p.ignore_unknown = int(ignore_unknown)
+    if max_cells is not None:
+        p.max_cells = int(max_cells)
+    return p
+
+
 def occupancy_rows(call, n, cap, n_out, device, host=False, centres=True):
     """Runs an occupancy call with fitting row buffers.  call(cap, key, l, xyz) makes the C call with the three row pointers (None with
     cap 0) and fills n_out; cap None: found by a call of its own.  -> (keys [n] of int64 [k], logodds [n] of float32 [k], centres [n] of

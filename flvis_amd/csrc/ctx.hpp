@@ -30,6 +30,9 @@ struct flvis_ctx {
   double dc_ms[4] = {0, 0, 0, 0};     // ... the last timed call's count, keys, sort, rows
   double oc_ms[4] = {0, 0, 0, 0};     // the last timed occupancy call's count, emit, sort, reduce (summed over its batches)
   int64_t oc_stats[4] = {0, 0, 0, 0};  // the last occupancy call: records, rays, batches, workspace bytes
+  int ocq_lookup = 0;                  // flvis_hip_occupancy_cast_lookup: 0 the line directory, 1 the plain search
+  double ocq_ms[2] = {0, 0};           // the last timed occupancy cast's index build (key check, line directory) and walk
+  int64_t ocq_stats[4] = {0, 0, 0, 0};  // the last occupancy cast: queries, cells tested, index bytes, workspace bytes
   std::string orb_pattern;  // the BRIEF pattern currently resident in the `orb_pattern` scratch buffer (1024 bytes) or empty
 
   // returns a device buffer of at least `bytes` bytes (contents undefined after growth)

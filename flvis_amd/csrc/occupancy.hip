@@ -45,6 +45,7 @@
 #include "dev_math.hpp"
 #include "kf_log.hpp"
 #include "map_cloud.hpp"
+#include "oc_cell.hpp"
 #include "occupancy.hpp"
 #include "pipeline_host.hpp"
 
@@ -76,20 +77,6 @@ struct OcItems {
   size_t pose_stride;
 };
 
-// floor(x / leaf) as mc_key computes it; false: not finite or outside [-2^20, 2^20)
-FD bool oc_index(double x, double leaf, int& i) {
-  const double f = floor(x / leaf);
-  if (!(f >= -MC_HALF_RANGE && f < MC_HALF_RANGE)) return false;
-  i = (int)f;
-  return true;
-}
-FD bool oc_cell(V3 p, double leaf, int& ix, int& iy, int& iz) {
-  const bool a = oc_index(p.x, leaf, ix), b = oc_index(p.y, leaf, iy), c = oc_index(p.z, leaf, iz);
-  return a && b && c;
-}
-FD uint64_t oc_key(int ix, int iy, int iz) {
-  return ((uint64_t)(iz + (1 << 20)) << 42) | ((uint64_t)(iy + (1 << 20)) << 21) | (uint64_t)(ix + (1 << 20));
-}
 // the sample's camera-frame point by the dense cloud's rule, through the dense cloud's transform
 FD V3 oc_end(const SE3d& T, const Q4& qi, int u, int v, float z, double fx, double fy, double cx, double cy) {
   const double zd = (double)z;

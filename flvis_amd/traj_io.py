@@ -203,6 +203,15 @@ def sensor_to_flvis_imu(imu_type, acc, gyro):
     return np.array([-a[0], -a[1], -a[2]]), np.array([g[0], g[1], g[2]])
 
 
+def path_segments(poses7):
+    """camera poses T_c_w [k, 7] (t xyz, q xyzw: the keyframe log's and the loop closer's rows) -> float64 [k - 1, 6]: the straight
+    segments between consecutive camera positions -R^T t, as occupancy_cast takes them."""
+    pos = np.zeros((0, 3))
+    if len(poses7):
+        pos = np.array([-quat_to_rot(p[6], p[3], p[4], p[5]).T @ np.asarray(p[:3], float) for p in np.asarray(poses7, float).reshape(-1, 7)])
+    return np.concatenate([pos[:-1], pos[1:]], axis=1).reshape(-1, 6)
+
+
 def load_gray(path):
     """8-bit grayscale image file -> uint8 [h,w] (PIL; EuRoC ships 8-bit PNGs)."""
     from PIL import Image

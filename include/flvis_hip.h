@@ -1625,6 +1625,78 @@ int flvis_loop_closer_occupancy_host(flvis_loop_closer* lc, int n_groups, const 
                                      int out_cap, int64_t* h_key, float* h_l, float* h_xyz, int64_t* h_n_out, int64_t* h_n_rays,
                                      int64_t* h_n_dropped, int* h_n_batches);
 
+/* ---- occupancy map queries: the state of a voxel, and the first obstacle or unknown cell along a segment -----------------------------------
+ * (An octomap consumer uses its map through search() and castRay(); these are the two calls for the maps above.  The rule is this
+ * project's own, defined bit for bit; tests/_occupancy_cast.py restates it twice in numpy.)
+ * A MAP is what the occupancy calls return: the first h_n_rows[m] rows of d_key [n_maps][map_cap] (int64) and d_l [n_maps][map_cap]
+ *   (float), keys strictly ascending and non-negative, key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20), and ONE leaf for the
+ *   whole call: that the keys belong to that leaf is the caller's contract, as it is for the prior.  Rows at and beyond h_n_rows[m] are
+ *   never read.
+ * A QUERY is a segment o -> p: six doubles (o.x o.y o.z p.x p.y p.z) in the map's frame, d_seg [n_q][6].  The queries of map m are
+ *   h_q_ptr[m] .. h_q_ptr[m + 1] - 1 (CSR; a map may have none; n_q = h_q_ptr[n_maps]).
+ * All arithmetic below is fp64 without contraction unless float is stated.
+ * Cells: io, ie, rem, sgn, tmax, tdel, the order of the steps and the tie rule are word for word those of flvis_hip_occupancy:
+ *   floor(x / leaf) per axis, exactly n = rem[0] + rem[1] + rem[2] steps, the step axis the one with the smallest tmax among the axes with
+ *   rem[a] > 0, looked at in the order x, y, z with strict <.  The walk visits the cells c_0 = io, c_1, .., c_n = ie.  o and p are used as
+ *   given: there is no pose and no camera.
+ * Dropped: a query with a coordinate that is not finite, or with an index of io or ie outside [-2^20, 2^20), is DROPPED.
+ * Entry parameter: t_0 = 0.0; for k >= 1, t_k is the value tmax[a] had when the step into c_k picked axis a, before tdel[a] was added.  It
+ *   is reported as computed: rounding and the integer bound may take it a little past 1 or make it non-monotone; it is not corrected.
+ * State of a cell: if its key is among the map's rows it is OCCUPIED when l > thres (one float comparison: l == thres is FREE, a NaN l is
+ *   FREE) and FREE otherwise; if its key is absent it is UNKNOWN.
+ * Walk: the cells are tested in the order k = 0, 1, ..  Before the test of cell k: if max_cells > 0 and k == max_cells, stop with LIMIT.
+ *   Then the state of cell k decides: OCCUPIED: stop with OCCUPIED.  UNKNOWN and ignore_unknown == 0: stop with UNKNOWN.  Otherwise, if
+ *   k == n: stop with END.  Otherwise step on.
+ * Output per query (any of the arrays but d_status may be NULL): d_status int32 0 END, 1 OCCUPIED, 2 UNKNOWN, 3 DROPPED, 4 LIMIT; d_k int32
+ *   the index of the cell where the walk stopped; d_cell int64 that cell's key; d_row int32 its row in the map, or -1 when it is absent or
+ *   the status is LIMIT (a LIMIT cell is not looked up); d_l_out float the row's value, 0.0f when d_row is -1; d_t double t_k.  A DROPPED
+ *   query gives k = 0, cell = -1, row = -1, l = 0.0f, t = 0.0.  h_counts5 [n_maps][5] (may be NULL): the queries per status.
+ * Point lookup: a segment with p == o has n = 0; with ignore_unknown = 0 its status is END for free, OCCUPIED or UNKNOWN, and row / l are
+ *   those of the point's voxel: that is search().
+ * Reproducibility: queries are independent; several maps in one call give the bits of single calls; a second run gives the same bits.
+ *   No atomics.
+ * Method: one lane per query, in the caller's order.  The lane walks its segment with the integer-bounded walk of flvis_hip_occupancy
+ *   and finds every cell's row in the map's sorted keys.  The keys of one (iz, iy) LINE share key >> 21 and lie together, ascending in
+ *   ix, so each call first builds a LINE DIRECTORY per map: the distinct key >> 21 and the first row of each (head flags over the sorted
+ *   keys, positions by prefix counts).  A lane keeps the row range of its current line and its place in it: after a step along x the next
+ *   key is the old one +- 1 and its row, if any, is the neighbouring row (one load); after a step along y the next line is the old one
+ *   +- 1 and its directory slot, if any, the neighbouring slot (one load), followed by a binary search inside that line; after a step
+ *   along z a binary search over the directory on the side the step went to.  flvis_hip_occupancy_cast_lookup(ctx, 1) replaces all of
+ *   that by one binary search over all rows of the map per cell (the baseline the directory is measured against; the same bits);
+ *   0 is the default.  The call waits for the key check together with the line counts, and for the counts per status.
+ * FLVIS_ERR_INVALID_ARG before anything is queued: leaf not finite or <= 0; thres not finite; max_cells < 0; ignore_unknown not 0 or 1;
+ *   n_maps < 1; map_cap < 0 (an int: a capacity of 2^31 or more cannot be passed); h_n_rows[m] outside [0, map_cap]; h_q_ptr not
+ *   starting at 0 or descending; NULL prm, h_n_rows or h_q_ptr; NULL d_key or d_l with a non-empty map; NULL d_seg or d_status with a query;
+ *   an output that overlaps a map, the segments or another output.  flvis_occupancy_cast_check is the host part of these checks on its
+ *   own (no context, no pointer checks of device arrays).  Map keys that do not ascend strictly, or a negative key:
+ *   FLVIS_ERR_INVALID_ARG after a device check, with no output written.
+ * FLVIS_ERR_CAPACITY: 2^31 - n_maps rows or more in the maps of one call (the directory holds ints).
+ * Workspace: the context's, grown on demand and kept: 4 bytes per query, 64 per map, 4 per map and 256 rows of the largest map, and the
+ *   directory, 12 bytes per row and per map (room for a line per row, so that its allocation waits for no count).  A failed allocation
+ *   returns FLVIS_ERR_HIP and leaves the context usable.
+ * flvis_hip_occupancy_cast_stats: h_stats4 = queries, cells tested, index bytes, workspace bytes of the context's last cast.  Cells
+ *   tested: the sum of k + 1 over the queries that are not dropped, k for those that stopped with LIMIT; summed per map by a workgroup's
+ *   tree, then over the maps.  Index bytes: the directory's lines and its head counts (0 with the plain search).  h_ms2 = wall-clock
+ *   milliseconds of the index build (the key check, the line counts and the directory) and of the walk, kept while
+ *   flvis_hip_depth_cloud_times is enabled (the call then waits behind the build).  Either may be NULL.
+ * The _host form takes the segments from the host and returns the outputs there, staged in the context; the maps stay device arrays. */
+typedef struct flvis_occupancy_cast_params {
+  float thres;         /* a row is OCCUPIED when l > thres */
+  int ignore_unknown;  /* 1: an UNKNOWN cell does not stop the walk */
+  int max_cells;       /* > 0: stop with LIMIT before the test of cell max_cells */
+} flvis_occupancy_cast_params;
+void flvis_occupancy_cast_params_default(flvis_occupancy_cast_params* p);  /* 0.0f (probability 0.5), 0, 0 */
+int flvis_hip_occupancy_cast(flvis_ctx* ctx, int n_maps, const int64_t* d_key, const float* d_l, int map_cap, const int64_t* h_n_rows,
+                             double leaf, const flvis_occupancy_cast_params* prm, const double* d_seg, const int* h_q_ptr /* [n_maps + 1] */,
+                             int* d_status, int* d_k, int64_t* d_cell, int* d_row, float* d_l_out, double* d_t, int64_t* h_counts5);
+int flvis_hip_occupancy_cast_host(flvis_ctx* ctx, int n_maps, const int64_t* d_key, const float* d_l, int map_cap, const int64_t* h_n_rows,
+                                  double leaf, const flvis_occupancy_cast_params* prm, const double* h_seg, const int* h_q_ptr, int* h_status,
+                                  int* h_k, int64_t* h_cell, int* h_row, float* h_l_out, double* h_t, int64_t* h_counts5);
+int flvis_occupancy_cast_check(int n_maps, int map_cap, const int64_t* h_n_rows, double leaf, const flvis_occupancy_cast_params* prm,
+                               const int* h_q_ptr);
+int flvis_hip_occupancy_cast_stats(flvis_ctx* ctx, int64_t* h_stats4, double* h_ms2);
+int flvis_hip_occupancy_cast_lookup(flvis_ctx* ctx, int lookup);  /* 0 the line directory (default), 1 the plain search */
+
 #ifdef __cplusplus
 }
 #endif

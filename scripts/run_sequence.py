@@ -63,6 +63,10 @@ keyframes: every valid sample of --dense-cloud's sampling is a ray from the came
 occupied, one clamped log-odds value per voxel of L metres (default 0.08; flvis_keyframe_log_occupancy, or with --loop-closing
 flvis_loop_closer_occupancy under the closer's stored poses).  The file holds the centres of the voxels with log-odds > 0; the JSON line
 counts occupied, free and all voxels.  Goes with or without --dense-cloud; the log holds the whole run as for that option.
+--occupancy-path-check : with --occupancy, the straight segments between consecutive keyframe positions (the logged poses, or with
+--loop-closing the closer's stored ones) are cast through the finished map on the device (flvis_hip_occupancy_cast, unknown cells
+stop a segment); the JSON line gets the segments per status under occupancy.path_check.  The vehicle flew there: an OCCUPIED segment
+is a finding about the map.
 
 --batch N : (hip) the frames go through flvis_run_steps in chunks of N -- the host sees nothing between the steps of a chunk -- with the
 keyframe log on (flvis_keyframe_log_enable, N entries): after each chunk the loop closing takes the chunk's keyframes from the log on the
@@ -105,6 +109,7 @@ def main():
     ap.add_argument("--dense-step", type=int, default=7)
     ap.add_argument("--occupancy", default=None)
     ap.add_argument("--occupancy-leaf", type=float, default=0.08)
+    ap.add_argument("--occupancy-path-check", action="store_true")
     ap.add_argument("--lc-traj-out", default=None)
     ap.add_argument("--lc-imu-out", default=None)
     ap.add_argument("--lc-traj-mode", choices=["anchor", "blend"], default="anchor")
@@ -127,6 +132,8 @@ def main():
         ap.error("--dense-stereo needs --backend hip, --batch N and --dense-step >= 1, and goes without --dense-cloud")
     if args.occupancy and (args.dense_stereo or not (args.batch and args.backend == "hip" and args.dense_step >= 1 and args.occupancy_leaf > 0)):
         ap.error("--occupancy needs --backend hip, --batch N, --dense-step >= 1 and --occupancy-leaf > 0, and goes without --dense-stereo")
+    if args.occupancy_path_check and not args.occupancy:
+        ap.error("--occupancy-path-check needs --occupancy")
     dense_out = args.dense_cloud or args.dense_stereo
     keep_log = dense_out or args.occupancy                         # (any of them: the log keeps the whole run)
     seq = traj_io.open_sequence(args.sequence)
@@ -302,6 +309,12 @@ def main():
             occupancy = {"occupied": int((l > 0).sum()), "free": int((l < 0).sum()), "voxels": int(got[3][0]), "rays": int(got[4][0]),
                          "dropped_rays": int(got[5][0]), "batches": got[6], "leaf": args.occupancy_leaf, "step": args.dense_step,
                          "keyframes": trk.keyframe_log_info(0)["logged"], "frame": "map" if closer is not None else "odometry"}
+            if args.occupancy_path_check:
+                logged = trk.keyframe_log_info(0)["logged"]
+                poses = closer.poses(0) if closer is not None else [trk.keyframe_log_get(0, i, images=False)["pose7"] for i in range(logged)]
+                path = traj_io.path_segments(poses)
+                counts = ctx.occupancy_cast([(got[0][0], l)], [path], args.occupancy_leaf, outputs=False)[6][0]
+                occupancy["path_check"] = dict(zip(flvis_amd.OCCUPANCY_CAST_STATUS, (int(c) for c in counts)), segments=len(path))
         lm_cloud = None
         if args.lm_cloud:
             trk.local_map_counts()                                             # (drains the keyframe queue: the last optimisations too)
