@@ -11,9 +11,16 @@
 // The search image is cached per level as a 41-row x 52-byte REGION around the current position (window + 4 px margin,
 // dword-aligned columns): iterations read their 32x32 window from LDS and only a move of more than the margin re-stages
 // it -- no global load and no barrier in a steady-state iteration.  The bilinear interpolation + residual run on packed
-// 16-bit pairs (v_perm_b32 to widen two bytes, v_dot2c_i32_i16 for the weights and for the b1/b2 accumulation): ~8
+// 16-bit pairs (v_perm_b32 to widen two bytes, v_dot2c_i32_i16 for the weights and for the b1/b2 accumulation): 6.5
 // instructions per pixel.  Sums are exact integers (int32 per lane; the wave total is reduced as 16-bit halves with DPP
 // row reductions + 4 readlanes) -> bit-exact vs the oracle.
+// A steady-state Gauss-Newton iteration (no re-staging) is ~285 instructions of the temporal launch, ~355 before the
+// cuts of profiles/r31_lk_diet.md (scripts/lk_isa_count.py prints the listing's counts): the point's positions are read
+// through v_readfirstlane, so the position, range, region, convergence and oscillation tests are scalar branches with
+// no exec-mask bookkeeping; a pixel pair is packed before it is shifted; all 64 lanes run the pixel loop.  What
+// remains: 104 of the 285 are the 16 pixels' interpolation and residual, ~10 wait-state no-ops among them, 37 the wave
+// sum, ~25 the weights and the LDS reads with their alignment, ~45 the update with the double-precision exit tests, ~35
+// scalar tests and loop bookkeeping.
 #include "dev_common.hpp"
 #include "img_kernels.hpp"
 
@@ -37,6 +44,23 @@ typedef __attribute__((address_space(1))) uint32_t lk_gu32;  // a dword in globa
 typedef uint32_t lk_u4 __attribute__((ext_vector_type(4)));  // (a native vector: the non-temporal builtins do not take HIP's uint4 class)
 // (by value: __builtin_bit_cast applied directly to a vector-element expression such as q.y reads element 0 with this compiler)
 __device__ __forceinline__ lk_s2 lk_as_s2(uint32_t v) { return __builtin_bit_cast(lk_s2, v); }
+// a float that is the same in every lane, said so to the compiler (v_readfirstlane_b32 of its bits)
+__device__ __forceinline__ float lk_uniform(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ long long lk_uniform64(long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+typedef unsigned short lk_u2 __attribute__((ext_vector_type(2)));
+// (a1 >> S, a0 >> S) as a pair of 16-bit lanes for 8 <= S <= 16 and 0 <= a0, a1 < 2^24: bytes 1 and 2 of both (one v_perm_b32), then ONE
+// packed logical shift by S - 8 instead of a shift per value before the pack
+template <int S>
+__device__ __forceinline__ lk_s2 lk_pack_shr(int a0, int a1) {
+  static_assert(S >= 8 && S <= 16, "bytes 1 and 2 hold bits 8 .. 23");
+  const lk_u2 p = __builtin_bit_cast(lk_u2, __builtin_amdgcn_perm((uint32_t)a1, (uint32_t)a0, 0x06050201u));
+  return __builtin_bit_cast(lk_s2, (lk_u2)(p >> (unsigned short)(S - 8)));
+}
 
 // patch[r][c] = img(X0 + c, Y0 + r) for r < nrows, c < 36, REFLECT_101 outside the image.  Item i = 9 r + k is dword k of row r; a lane
 // takes items lane, lane + 64, ...  When the whole patch lies inside the image (wave-uniform test; nearly every point) there is nothing to
@@ -153,7 +177,7 @@ __device__ __forceinline__ bool lk_load_region(const uint8_t* __restrict__ img, 
   ((((K)&3) == 3) ? __builtin_amdgcn_perm((D)[((K) >> 2) + 1], (D)[(K) >> 2], 0x0c040c03u)                         \
                   : __builtin_amdgcn_perm(0u, (D)[(K) >> 2], 0x0c000c00u | (uint32_t)((K)&3) | ((uint32_t)(((K)&3) + 1) << 16)))
 
-// Instruction diet of the iteration (round 6).  The LK launches are bound by INSTRUCTION ISSUE -- one instruction of any kind per 4 cycles
+// Instruction diet of the iteration (round 6; continued in profiles/r31_lk_diet.md).  The LK launches are bound by INSTRUCTION ISSUE -- one instruction of any kind per 4 cycles
 // and SIMD, vector, scalar, LDS, wait and no-op alike (profiles/r06_chain_ab.md; SQ counters: 0.44 scalar instructions per vector one) --
 // not by latency: what shortens them is fewer instructions per iteration (rounds 3-5's forms were measured against these there).
 // a . b + c with c in a SCALAR register (v_dot2_i32_i16, the three-source form): the rounding bias of a bilinear interpolation is a
@@ -462,8 +486,10 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
     //  start from, are appended behind the tracked ones)
     const int p = prm.order == 1 ? n - 1 - pb : pb;
     const size_t pi = ((size_t)s * nmax + p) * 2;
-    const float ppx0 = prev_pts[pi], ppy0 = prev_pts[pi + 1];
-    float nx = next_pts[pi], ny = next_pts[pi + 1];
+    // (one address for the whole wave, but a per-lane load: without the read-first-lane the compiler takes the positions, and with them
+    // every test of the level and of the iteration, for divergent, and guards each with an exec-mask save and restore)
+    const float ppx0 = lk_uniform(prev_pts[pi]), ppy0 = lk_uniform(prev_pts[pi + 1]);
+    float nx = lk_uniform(next_pts[pi]), ny = lk_uniform(next_pts[pi + 1]);
     int st = 1;
     // template cache: the slot this point stores its templates in (stereo matcher), or the slot it may take them from (temporal
     // tracker: valid if it was written for this very position of this very image)
@@ -584,9 +610,11 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
           tX[k] = lk_as_s2(T.w[8 + k]);
           tY[k] = lk_as_s2(T.w[16 + k]);
         }
-        iA11 = T.a11;
-        iA12 = T.a12;
-        iA22 = T.a22;
+        // (read back from the stack, per lane: said to be uniform, or the update they scale, and so every test of the iteration loop of
+        // this launch, counts as divergent -- also for the levels whose sums come out of the cache by read-lane)
+        iA11 = lk_uniform64(T.a11);
+        iA12 = lk_uniform64(T.a12);
+        iA22 = lk_uniform64(T.a22);
       } else {
         const bool slow = lk_template_level(lk_level_ptr(prev, level, s, kc_prev, ind_prev0), W, H, prev.pitch[level], prev.bx[level], prev.by[level], ipx,
                                             ipy, iw00, iw01, iw10, iw11, patch, lane, tI, tX, tY, iA11, iA12, iA22);
@@ -616,7 +644,9 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
       for (int j = 0; j < prm.max_iter; j++) {
         iters_run = j + 1;
         const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-        if (inx < -LK_WIN || inx >= JW || iny < -LK_WIN || iny >= JH) {
+        // (inx < -LK_WIN || inx >= JW as ONE unsigned comparison: inx + LK_WIN wraps to a huge value exactly when it is negative, and
+        // a conversion that saturated at either end of int lands outside as well)
+        if ((unsigned)inx + (unsigned)LK_WIN >= (unsigned)(JW + LK_WIN) || (unsigned)iny + (unsigned)LK_WIN >= (unsigned)(JH + LK_WIN)) {
           if (level == 0) st = 0;
           break;
         }
@@ -626,7 +656,8 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
         iw01 = __float2int_rn(a * (1.f - b) * (float)(1 << W_BITS));
         iw10 = __float2int_rn((1.f - a) * b * (float)(1 << W_BITS));
         iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
-        if (!region_ok || inx < RX0 || inx - RX0 > 15 || iny < RY0 || iny - RY0 > 2 * LK_RM) {
+        // (inx, iny and the region's corner are within a window of the image here: the differences cannot wrap)
+        if (!region_ok || (unsigned)(inx - RX0) > 15u || (unsigned)(iny - RY0) > (unsigned)(2 * LK_RM)) {
           RX0 = (inx - LK_RM) & ~3;
           RY0 = iny - LK_RM;
           __syncthreads();
@@ -635,8 +666,11 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
           if (prm.stats_tc && slow && lane == 0) atomicAdd(&prm.stats_tc[2], 1ull);
           region_ok = true;
         }
-        int b1 = 0, b2 = 0;
-        if (r < LK_WIN) {
+        int b1, b2;
+        {
+          // (all 64 lanes, no exec mask: the lanes of window row 31 read rows iny - RY0 + 31 and + 32 <= 40 of the 41 staged ones and
+          // the same columns as every other lane, and add nothing -- their tX and tY are 0, computed here or taken from the cache, where
+          // lane 63's tI carries the Hessian sums)
           const int bx = inx - RX0 + c0, sh = bx & 3;
           const uint8_t* rp = patch + (iny - RY0 + r) * LK_RS + (bx & ~3);
           uint32_t e[2][5];
@@ -649,19 +683,21 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
             for (int k = 0; k < 5; k++) e[q][k] = __builtin_amdgcn_alignbyte(dd[k + 1], dd[k], sh);
           }
           const lk_s2 wT = lk_s2{(short)iw00, (short)iw01}, wB = lk_s2{(short)iw10, (short)iw11};
+          // The two pixels of a pair side by side: the second dot product of a pixel stands behind the other pixel's first.  (Pipelining
+          // the pairs against each other as well -- pair c's interpolation issued before pair c - 1's residual, behind scheduling fences --
+          // took the last ten wait-state no-ops out of this loop and measured no gain: profiles/r31_lk_diet.md.)
+          // 0 < acc < 2^22: pixels <= 255, the four weights sum to 2^14, three of them are >= 0 and the fourth, 2^14 minus the three
+          // rounded ones, is >= -1 (each rounding adds at most 1/2, and where the exact fourth weight is 0 one of the others is exact), so
+          // acc >= 256 - 255 and acc <= 255 * (2^14 + 1) + 256
+          b1 = 0, b2 = 0;
 #pragma unroll
           for (int c2 = 0; c2 < 8; c2++) {
-            int iv[2];
-#pragma unroll
-            for (int hh = 0; hh < 2; hh++) {
-              const int c = 2 * c2 + hh;
-              const uint32_t pt = LK_PAIR(e[0], c), pb = LK_PAIR(e[1], c);
-              int acc = lk_dot2_bias(__builtin_bit_cast(lk_s2, pt), wT, 1 << (W_BITS - 5 - 1));
-              acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(lk_s2, pb), wB, acc, false);
-              iv[hh] = acc >> (W_BITS - 5);
-            }
-            const lk_s2 ivp = __builtin_bit_cast(lk_s2, __builtin_amdgcn_perm((uint32_t)iv[1], (uint32_t)iv[0], 0x05040100u));
-            const lk_s2 diff = ivp - tI[c2];
+            const int c = 2 * c2;
+            int acc0 = lk_dot2_bias(__builtin_bit_cast(lk_s2, LK_PAIR(e[0], c)), wT, 1 << (W_BITS - 5 - 1));
+            int acc1 = lk_dot2_bias(__builtin_bit_cast(lk_s2, LK_PAIR(e[0], c + 1)), wT, 1 << (W_BITS - 5 - 1));
+            acc0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(lk_s2, LK_PAIR(e[1], c)), wB, acc0, false);
+            acc1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(lk_s2, LK_PAIR(e[1], c + 1)), wB, acc1, false);
+            const lk_s2 diff = lk_pack_shr<W_BITS - 5>(acc0, acc1) - tI[c2];
             // columns >= 31 have tX = tY = 0, so they add nothing
             b1 = __builtin_amdgcn_sdot2(diff, tX[c2], b1, false);
             b2 = __builtin_amdgcn_sdot2(diff, tY[c2], b2, false);
@@ -676,7 +712,8 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
         npy += ddy;
         nx = npx + halfWin;
         ny = npy + halfWin;
-        if ((double)ddx * (double)ddx + (double)ddy * (double)ddy <= eps2) break;
+        // (eps2 sits in vector registers, which makes the comparison divergent to the compiler: the ballot says it is one decision)
+        if (__builtin_amdgcn_ballot_w64((double)ddx * (double)ddx + (double)ddy * (double)ddy <= eps2) != 0) break;
         if (j > 0 && fabs((double)(ddx + pdx)) < 0.01 && fabs((double)(ddy + pdy)) < 0.01) {
           nx -= ddx * 0.5f;
           ny -= ddy * 0.5f;
