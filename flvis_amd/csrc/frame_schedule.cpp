@@ -526,6 +526,7 @@ void Frame::stage_idle_tail() {
 }
 
 // What the temporal (stats_at 36, tc_mode 2) and the stereo launch (48, tc_mode 1) of k_lk_track share
+// (one min_eig for both: the template cache holds a level's 1 / D only where the level passed the STEREO launch's tests, lk_kernel.hip)
 LKParams Frame::lk_params(int stats_at, int tc_mode, int order) const {
   LKParams prm{30, 1e-3 * 1e-3, 1e-4f, 1};
   if (pl->lk_stats) prm.stats = reinterpret_cast<unsigned long long*>(p.counters) + stats_at;  // counters[36 .. 47] / [48 .. 59]

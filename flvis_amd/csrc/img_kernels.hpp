@@ -67,7 +67,8 @@ struct LKParams {
   // the slow (index-reflecting) path
   unsigned long long* stats_tc = nullptr;
   // Template cache (lk_kernel.hip).  The stereo matcher of frame t computes, for every landmark, the template -- interpolated I, Ix, Iy
-  // of the 31 x 31 window on every level + the Hessian sums -- at the landmark's pixel in the left image of frame t; the temporal
+  // of the 31 x 31 window on every level + the floats it derives from the Hessian sums (A11, A12, A22, D, minEig, 1 / D; the layout is
+  // at LK_TC_HDR in lk_kernel.hip) -- at the landmark's pixel in the left image of frame t; the temporal
   // tracker of frame t + 1 needs exactly that template (previous image = that image, previous point = that pixel).  tc_mode 1: every
   // point p < tc_cap stores its templates in slot p, with the position bits and tc_tag[s] in the slot's header.  tc_mode 2: the caller
   // has compared the headers already (lk_tc_lookup): tc_slot[s * nmax + p] = slot | (mask of the levels stored << 16) if the slot was

@@ -21,6 +21,12 @@
 // remains: 104 of the 285 are the 16 pixels' interpolation and residual, ~10 wait-state no-ops among them, 37 the wave
 // sum, ~25 the weights and the LDS reads with their alignment, ~45 the update with the double-precision exit tests, ~35
 // scalar tests and loop bookkeeping.
+// A level's set-up, outside the iteration loop (profiles/r32_lk_level_setup.md): everything a wave needs of a pyramid level
+// is one 64-byte descriptor (LKLevel, made on the host from the caller's PyrSel: adjacent scalar loads and one wait instead
+// of a dependent load per field); the level scale 2^-level is built from its bits; both staging fast paths keep one lane ->
+// (row, dword) map for the whole kernel (a block of rows per trip: the scalar base advances, the lane's offset and LDS
+// address stay); and a cached level hands the temporal launch the floats the stereo launch computed from the Hessian sums
+// (A11, A12, A22, D, minEig, 1 / D) instead of the sums.
 #include "dev_common.hpp"
 #include "img_kernels.hpp"
 
@@ -34,8 +40,12 @@ constexpr int LK_RS = 52;     // search-region row stride (bytes): 13 dwords (od
 constexpr int LK_RROWS = 33 + 2 * LK_RM;
 // template cache (LKParams::tc): one slot per (stream, point); LK_TC_HDR header dwords -- position bits (2), tag (2), mask of the levels
 // stored (1), the rest unused -- followed by LK_TC_LVL dwords per level: the 24 template registers (tI, tX, tY: 8 packed pairs each) of
-// the 64 lanes as six 1 KB rows (one dwordx4 per lane and row); lane 63, which holds no template (window row 31), carries the level's
-// three Hessian sums (int64) in its first six dwords
+// the 64 lanes as six 1 KB rows (one dwordx4 per lane and row); lane 63, which holds no template (window row 31), carries in its first
+// six dwords the level's floats as the stereo launch computed them from the three Hessian sums: A11, A12, A22, D = A11 A22 - A12^2, minEig
+// and 1 / D (computed only for a level that passes the stereo launch's tests, 0 otherwise) -- the temporal launch applies its own thresholds
+// to minEig and D and takes the rest as it is: the same IEEE operations on the same sums, done once instead of once per launch.  Both
+// launches get min_eig from one place (Frame::lk_params): a reader with a LOWER threshold than the writer's would pass a level whose 1 / D
+// was never computed
 constexpr int LK_TC_HDR = 64;
 constexpr int LK_TC_LVL = 64 * 24;
 
@@ -62,48 +72,40 @@ __device__ __forceinline__ lk_s2 lk_pack_shr(int a0, int a1) {
   return __builtin_bit_cast(lk_s2, (lk_u2)(p >> (unsigned short)(S - 8)));
 }
 
-// patch[r][c] = img(X0 + c, Y0 + r) for r < nrows, c < 36, REFLECT_101 outside the image.  Item i = 9 r + k is dword k of row r; a lane
-// takes items lane, lane + 64, ...  When the whole patch lies inside the image (wave-uniform test; nearly every point) there is nothing to
-// reflect and nothing to divide: a lane's (row, dword) advances by (7, 1) per trip (64 = 7 * 9 + 1) with one wrap test, its byte offset
-// into the image and its LDS address advance by constants, and the address is a uniform base + a 32-bit lane offset.
+// patch[r][c] = img(X0 + c, Y0 + r) for r < nrows, c < 36, REFLECT_101 outside the image.  Item 9 r + k is dword k of row r.  When the
+// whole patch lies inside the image (wave-uniform test; nearly every point) there is nothing to reflect and nothing to divide: a trip is a
+// block of 7 rows x 9 dwords on lanes 0 .. 62, and lane = 9 r + k keeps its (r, k) for the whole kernel -- the address of a load is a
+// uniform base that advances by 7 rows per trip + the lane's 32-bit offset, the LDS address the lane's own + a constant of the trip.
 // (bx, by) = the level's physical REFLECT_101 border: the fast path covers every block that lies inside the bordered storage.
 __device__ __forceinline__ bool lk_load_patch(const uint8_t* __restrict__ img, int w, int h, int pitch, int bx, int by, int X0, int Y0,
                                               int nrows, uint8_t* patch) {
   if (X0 >= -bx && Y0 >= -by && X0 + 39 < w + bx && Y0 + nrows <= h + by) {  // (+ 39: the second dword of the last item stays inside the row)
     // ALL loads of the lane are issued before the first one is consumed: one memory round trip for the patch instead of one per trip
     // (the loop form waited for every load before it issued the next -- five dependent round trips of ~1 us under load)
-    const lk_gu32* const base = (const lk_gu32*)(img + (ptrdiff_t)Y0 * pitch + (X0 & ~3));
+    const __attribute__((address_space(1))) uint8_t* const base =
+        (const __attribute__((address_space(1))) uint8_t*)(img + (ptrdiff_t)Y0 * pitch + (X0 & ~3));
     const int sh = X0 & 3;
-    int r = (int)threadIdx.x / 9, k = (int)threadIdx.x - 9 * r;
-    unsigned off = (unsigned)(r * pitch + 4 * k);
-    static_assert(LK_PROWS * 9 <= 5 * 64, "five trips");
-    const int n = nrows * 9;
+    static_assert(LK_PROWS <= 5 * 7 && LK_PROWS > 4 * 7, "five trips, and the last one starts on a row of the patch");
+    const int lane = (int)threadIdx.x, r = lane / 9, k = lane - 9 * r;
+    const unsigned off = lane < 63 ? (unsigned)(r * pitch + 4 * k) : 0u;
     uint32_t lo[5], hi[5];
 #pragma unroll
     for (int t = 0; t < 5; t++) {
-      const bool on = (int)threadIdx.x + 64 * t < n;
-      const unsigned o = on ? off : 0u;   // (a lane past the end re-reads item 0 of the patch: in bounds, never stored)
-      lo[t] = *(const lk_gu32*)((const __attribute__((address_space(1))) uint8_t*)base + o);
-      hi[t] = *(const lk_gu32*)((const __attribute__((address_space(1))) uint8_t*)base + o + 4);
-      k += 1;
-      const bool wrap = k >= 9;
-      k = wrap ? k - 9 : k;
-      off += (unsigned)(7 * pitch + 4) + (wrap ? (unsigned)(pitch - 36) : 0u);
+      const bool on = lane < 63 && 7 * t + r < nrows;
+      // (a lane past the end re-reads item 0 of the trip's block, row 7 t of the patch: never stored, and in bounds for nrows > 28 -- the
+      // rows the fast-path test has checked; the only caller passes LK_PROWS)
+      const unsigned o = on ? off : 0u;
+      const __attribute__((address_space(1))) uint8_t* const bt = base + (ptrdiff_t)(7 * t) * pitch;
+      lo[t] = *(const lk_gu32*)(bt + o);
+      hi[t] = *(const lk_gu32*)(bt + o + 4);
     }
-    // (every loaded value is "used" here, so the compiler cannot sink the last, predicated trip's loads behind the wait for the others)
+    // (every loaded value is "used" here, so the compiler cannot sink the last, predicated trip's loads behind the wait for the others; in
+    // ONE statement: the compiler waits for each statement's operands with an s_waitcnt of its own)
+    asm volatile("" : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3]), "+v"(lo[4]), "+v"(hi[4]));
+    uint8_t* const dst = patch + r * LK_PS + 4 * k;
 #pragma unroll
-    for (int t = 0; t < 5; t++) asm volatile("" : "+v"(lo[t]), "+v"(hi[t]));
-    r = (int)threadIdx.x / 9;
-    k = (int)threadIdx.x - 9 * r;
-    unsigned dst = (unsigned)(r * LK_PS + 4 * k);
-#pragma unroll
-    for (int t = 0; t < 5; t++) {
-      if ((int)threadIdx.x + 64 * t < n) *reinterpret_cast<uint32_t*>(patch + dst) = __builtin_amdgcn_alignbyte(hi[t], lo[t], sh);
-      k += 1;
-      const bool wrap = k >= 9;
-      k = wrap ? k - 9 : k;
-      dst += (unsigned)(7 * LK_PS + 4) + (wrap ? (unsigned)(LK_PS - 36) : 0u);
-    }
+    for (int t = 0; t < 5; t++)
+      if (lane < 63 && 7 * t + r < nrows) *reinterpret_cast<uint32_t*>(dst + 7 * LK_PS * t) = __builtin_amdgcn_alignbyte(hi[t], lo[t], sh);
     return false;
   }
   for (int i = threadIdx.x; i < nrows * 9; i += 64) {
@@ -128,31 +130,30 @@ __device__ __forceinline__ bool lk_load_patch(const uint8_t* __restrict__ img, i
 }
 
 // region[r][c] = img(X0 + c, Y0 + r), r < LK_RROWS, c < 52, X0 a multiple of 4 (aligned dword loads), REFLECT_101 outside.  Same fast
-// path when the region lies inside the image: (row, dword) advances by (4, 12) per trip (64 = 4 * 13 + 12).
+// path when the region lies inside the image: a trip is a block of 4 rows x 13 dwords on lanes 0 .. 51 (lane = 13 r + k: the block is
+// contiguous in LDS, item at byte 4 lane), eleven trips, the last one of a single row.  Two loads more than 64 items per trip would
+// take, and no address arithmetic on the vector unit but the lane's own offset.
 __device__ __forceinline__ bool lk_load_region(const uint8_t* __restrict__ img, int w, int h, int pitch, int bx, int by, int X0, int Y0,
                                                uint8_t* region) {
   if (X0 >= -bx && Y0 >= -by && X0 + 51 < w + bx && Y0 + LK_RROWS <= h + by) {
-    // nine loads per lane in flight at once, then nine LDS stores (see lk_load_patch)
+    // all loads of the lane in flight at once, then the LDS stores (see lk_load_patch)
     const __attribute__((address_space(1))) uint8_t* const base = (const __attribute__((address_space(1))) uint8_t*)(img + (ptrdiff_t)Y0 * pitch + X0);
-    int r = (int)threadIdx.x / 13, k = (int)threadIdx.x - 13 * r;
-    unsigned off = (unsigned)(r * pitch + 4 * k);
-    static_assert(LK_RS == 52, "the region rows are contiguous in LDS: item i sits at byte 4 i");
-    constexpr int N = LK_RROWS * 13, T = (N + 63) / 64;
+    static_assert(LK_RS == 52, "the region rows are contiguous in LDS: a block of four rows is 52 dwords");
+    constexpr int T = (LK_RROWS + 3) / 4, LAST = (LK_RROWS - 4 * (T - 1)) * 13;  // (lanes of the last trip)
+    const int lane = (int)threadIdx.x, r = lane / 13, k = lane - 13 * r;
+    const unsigned off = lane < 52 ? (unsigned)(r * pitch + 4 * k) : 0u;  // (an idle lane re-reads item 0 of the block: in bounds, never stored)
     uint32_t v[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) {
-      const bool on = 64 * (t + 1) <= N || (int)threadIdx.x + 64 * t < N;
-      v[t] = *(const lk_gu32*)(base + (on ? off : 0u));
-      k += 12;
-      const bool wrap = k >= 13;
-      k = wrap ? k - 13 : k;
-      off += (unsigned)(4 * pitch + 48) + (wrap ? (unsigned)(pitch - 52) : 0u);
+    for (int t = 0; t < T; t++) v[t] = *(const lk_gu32*)(base + (ptrdiff_t)(4 * t) * pitch + (t < T - 1 || lane < LAST ? off : 0u));
+    // (every loaded value is "used" in ONE statement: the compiler waits for each statement's operands with an s_waitcnt of its own)
+    static_assert(T == 11, "the operand list below");
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]),
+                 "+v"(v[10]));
+    if (lane < 52) {
+#pragma unroll
+      for (int t = 0; t < T - 1; t++) *reinterpret_cast<uint32_t*>(region + 4 * lane + 4 * LK_RS * t) = v[t];
+      if (lane < LAST) *reinterpret_cast<uint32_t*>(region + 4 * lane + 4 * LK_RS * (T - 1)) = v[T - 1];
     }
-#pragma unroll
-    for (int t = 0; t < T; t++) asm volatile("" : "+v"(v[t]));
-#pragma unroll
-    for (int t = 0; t < T; t++)
-      if (64 * (t + 1) <= N || (int)threadIdx.x + 64 * t < N) *reinterpret_cast<uint32_t*>(region + 4 * ((int)threadIdx.x + 64 * t)) = v[t];
     return false;
   }
   for (int i = threadIdx.x; i < LK_RROWS * 13; i += 64) {
@@ -381,17 +382,16 @@ __device__ __noinline__ void lk_template_level_cold(const uint8_t* img, int W, i
 }
 
 // one level's templates into a cache slot: the 24 template registers of the 64 lanes as six 1 KB rows; lane 63 (window row 31: no template)
-// carries the three Hessian sums in the place of its tI registers
+// carries the level's six floats (LK_TC_HDR's comment) in the place of its first six tI registers
 __device__ __forceinline__ void lk_tc_store_level(uint32_t* tc_ptr, int level, int lane, const lk_s2 (&tI)[8], const lk_s2 (&tX)[8],
-                                                  const lk_s2 (&tY)[8], long long iA11, long long iA12, long long iA22) {
+                                                  const lk_s2 (&tY)[8], float A11, float A12, float A22, float D, float minEig, float invD) {
   lk_u4* dst = reinterpret_cast<lk_u4*>(tc_ptr + LK_TC_HDR + (size_t)level * LK_TC_LVL) + lane;
   uint32_t wI[8];
 #pragma unroll
   for (int k = 0; k < 8; k++) wI[k] = __builtin_bit_cast(uint32_t, tI[k]);
   if (lane == 63) {
-    wI[0] = (uint32_t)iA11; wI[1] = (uint32_t)((unsigned long long)iA11 >> 32);
-    wI[2] = (uint32_t)iA12; wI[3] = (uint32_t)((unsigned long long)iA12 >> 32);
-    wI[4] = (uint32_t)iA22; wI[5] = (uint32_t)((unsigned long long)iA22 >> 32);
+    wI[0] = __float_as_uint(A11); wI[1] = __float_as_uint(A12); wI[2] = __float_as_uint(A22);
+    wI[3] = __float_as_uint(D); wI[4] = __float_as_uint(minEig); wI[5] = __float_as_uint(invD);
   }
 #pragma unroll
   for (int k = 0; k < 2; k++) {
@@ -403,13 +403,45 @@ __device__ __forceinline__ void lk_tc_store_level(uint32_t* tc_ptr, int level, i
   }
 }
 
+// What the kernels read of a pyramid: ONE 64-byte descriptor per level, made from the caller's PyrSel by launch_lk_track.  PyrSel is
+// structure-of-arrays, and with the level a run-time index every field of it cost a scalar load with its own address arithmetic and wait
+// (~18 per level and wave, profiles/r32_lk_level_setup.md); a descriptor is one s_load_dwordx16.  The slot choice is resolved as far as the
+// host can: b[k] is the base a wave whose stream's slot is k reads (ImgSel::flip applied; both the same where the level has no slot array).
+struct alignas(64) LKLevel {
+  const uint8_t* b[2];
+  const uint8_t* const* ind;  // ImgSel::ind
+  size_t stride;              // bytes between consecutive streams
+  int w, h, pitch, bx, by;
+  int pad_[3];
+};
+static_assert(sizeof(LKLevel) == 64, "one s_load_dwordx16");
+struct alignas(64) LKPyr {
+  LKLevel lvl[LK_MAX_LEVELS];
+  const int* cur;  // the slot array of the lowest level that has one (all levels share it: fill_pyr), or nullptr
+  int levels;
+};
+static LKPyr lk_pyr(const PyrSel& P) {
+  LKPyr q{};
+  q.levels = P.levels;
+  for (int l = P.levels < LK_MAX_LEVELS ? P.levels : LK_MAX_LEVELS - 1; l >= 0; l--) {
+    const ImgSel& I = P.lvl[l];
+    LKLevel& V = q.lvl[l];
+    V.b[0] = I.b[I.cur ? (I.flip & 1) : 0];
+    V.b[1] = I.b[I.cur ? ((I.flip & 1) ^ 1) : 0];
+    V.ind = I.ind;
+    V.stride = P.stride[l];
+    V.w = P.w[l], V.h = P.h[l], V.pitch = P.pitch[l], V.bx = P.bx[l], V.by = P.by[l];
+    if (I.cur) q.cur = I.cur;
+  }
+  return q;
+}
+
 // Base address of one pyramid level for stream s.  The slot choice cur[s] (a global load the compiler may not hoist: memory could have
 // changed) is read ONCE per wave and passed in: every level of a pyramid that selects by slot shares one slot array (fill_pyr); ind0 =
 // the already loaded base of an indirect level 0.  A level then costs kernel-argument reads only, no dependent global round trip.
-__device__ __forceinline__ const uint8_t* lk_level_ptr(const PyrSel& P, int level, int s, int kc, const uint8_t* ind0) {
-  const ImgSel& I = P.lvl[level];
-  if (I.ind) return (level == 0 ? ind0 : *I.ind) + (size_t)s * P.stride[level];
-  return I.b[I.cur ? (kc ^ I.flip) : 0] + (size_t)s * P.stride[level];
+__device__ __forceinline__ const uint8_t* lk_level_ptr(const LKLevel& V, int level, int s, int kc, const uint8_t* ind0) {
+  if (V.ind) return (level == 0 ? ind0 : *V.ind) + (size_t)s * V.stride;
+  return (kc ? V.b[1] : V.b[0]) + (size_t)s * V.stride;
 }
 
 #ifndef FLVIS_LK_WAVES
@@ -438,7 +470,7 @@ __device__ unsigned long long g_lk_wt[3][8][32768][2];
 #define LK_UTIL_END(ROLE)
 #endif
 template <int ROLE>
-__device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& next, const float* __restrict__ prev_pts,
+__device__ __forceinline__ void lk_track_body(const LKPyr& prev, const LKPyr& next, const float* __restrict__ prev_pts,
                                               float* __restrict__ next_pts, uint8_t* __restrict__ status,
                                               const int* __restrict__ count, int nmax, const LKParams& prm,
                                               const int* __restrict__ active) {
@@ -462,12 +494,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
   LK_UTIL_BEGIN
   __shared__ __attribute__((aligned(16))) uint8_t patch[LK_RROWS * LK_RS + 12];  // template patch, then search region
   const int lane = threadIdx.x;
-  int kc_prev = 0, kc_next = 0;
-#pragma unroll
-  for (int l = LK_MAX_LEVELS - 1; l >= 0; l--) {  // (the slot array of the lowest level that has one; all levels share it)
-    if (l <= prev.levels && prev.lvl[l].cur) kc_prev = prev.lvl[l].cur[s];
-    if (l <= next.levels && next.lvl[l].cur) kc_next = next.lvl[l].cur[s];
-  }
+  const int kc_prev = prev.cur ? prev.cur[s] : 0, kc_next = next.cur ? next.cur[s] : 0;
   const uint8_t* const ind_prev0 = prev.lvl[0].ind ? *prev.lvl[0].ind : nullptr;
   const uint8_t* const ind_next0 = next.lvl[0].ind ? *next.lvl[0].ind : nullptr;
   const int r = lane >> 1;
@@ -513,7 +540,12 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
     lk_u4 pq[6] = {};  // templates of level pq_level, in flight or arrived (-1: none)
     int pq_level = -1;
     for (int level = prev.levels; level >= 0; level--) {
-      const float sc = (float)(1. / (1 << level));
+      // 2^-level from its bits: the float that (float)(1. / (1 << level)) is, without the double-precision division (14 vector
+      // instructions per level)
+      static_assert(LK_MAX_LEVELS <= 126, "2^-level is a normal float");
+      const float sc = __uint_as_float((uint32_t)(127 - level) << 23);
+      // the level's two descriptors: everything a wave needs of the level, one wide scalar load per pyramid
+      const LKLevel PV = prev.lvl[level], NV = next.lvl[level];
       float ppx = ppx0 * sc, ppy = ppy0 * sc;
       float npx, npy;
       if (level == prev.levels) {
@@ -530,7 +562,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
       }
       nx = npx;
       ny = npy;
-      const int W = prev.w[level], H = prev.h[level];
+      const int W = PV.w, H = PV.h;
       ppx -= halfWin;
       ppy -= halfWin;
       const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
@@ -547,15 +579,18 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
       // ---- template.  Either from the cache (the stereo matcher of the previous frame made this very template: same image, same
       // position), or computed: stage source patch rows ipy-1..ipy+32, cols ipx-1..ipx+34, Scharr + bilinear interpolation
       lk_s2 tI[8], tX[8], tY[8];  // pixel pairs (c, c+1)
-      long long iA11, iA12, iA22;
+      long long iA11 = 0, iA12 = 0, iA22 = 0;
+      // A = the Hessian sums as floats, D its determinant (1 / D from the iterations on), minEig the smaller eigenvalue per pixel: from
+      // the sums, or -- a cached level -- as the stereo launch computed them from the same sums (cD: its 1 / D)
+      float A11 = 0.f, A12 = 0.f, A22 = 0.f, D = 0.f, minEig = 0.f, cD = 0.f;
       const bool cached = ROLE == 1 && tc_hit && ((tc_mask >> level) & 1u);
       // (the launches that may take templates from the cache look at the search image before the template stage: see below)
       constexpr bool kEarlyRegion = ROLE == 1;
       int JW = 0, JH = 0;
       const uint8_t* Jimg = nullptr;
       if (kEarlyRegion) {
-        JW = next.w[level], JH = next.h[level];
-        Jimg = lk_level_ptr(next, level, s, kc_next, ind_next0);
+        JW = NV.w, JH = NV.h;
+        Jimg = lk_level_ptr(NV, level, s, kc_next, ind_next0);
       }
       bool region_ok = false;
       int RX0 = 0, RY0 = 0;
@@ -576,7 +611,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
             RX0 = (einx - LK_RM) & ~3;
             RY0 = einy - LK_RM;
             __syncthreads();
-            const bool slow = lk_load_region(Jimg, JW, JH, next.pitch[level], next.bx[level], next.by[level], RX0, RY0, patch);
+            const bool slow = lk_load_region(Jimg, JW, JH, NV.pitch, NV.bx, NV.by, RX0, RY0, patch);
             __syncthreads();
             if (prm.stats_tc && slow && lane == 0) atomicAdd(&prm.stats_tc[2], 1ull);
             region_ok = true;
@@ -587,10 +622,13 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
 #pragma unroll
         for (int k = 0; k < 6; k++) q[k] = pq[k];
         pq_level = -1;
-        // (the three Hessian sums ride in lane 63's registers: the lanes of window row 31 hold no template)
-        iA11 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)q[0].y, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)q[0].x, 63));
-        iA12 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)q[0].w, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)q[0].z, 63));
-        iA22 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)q[1].y, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)q[1].x, 63));
+        // (the level's floats ride in lane 63's registers: the lanes of window row 31 hold no template)
+        A11 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[0].x, 63));
+        A12 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[0].y, 63));
+        A22 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[0].z, 63));
+        D = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[0].w, 63));
+        minEig = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[1].x, 63));
+        cD = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)q[1].y, 63));
 #pragma unroll
         for (int k = 0; k < 2; k++) {
           tI[4 * k + 0] = lk_as_s2(q[k].x); tI[4 * k + 1] = lk_as_s2(q[k].y);
@@ -602,7 +640,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
         }
       } else if (ROLE == 1) {
         LKTmpl T;
-        lk_template_level_cold(lk_level_ptr(prev, level, s, kc_prev, ind_prev0), W, H, prev.pitch[level], prev.bx[level], prev.by[level], ipx, ipy, iw00,
+        lk_template_level_cold(lk_level_ptr(PV, level, s, kc_prev, ind_prev0), W, H, PV.pitch, PV.bx, PV.by, ipx, ipy, iw00,
                                iw01, iw10, iw11, patch, lane, &T);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -611,34 +649,42 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
           tY[k] = lk_as_s2(T.w[16 + k]);
         }
         // (read back from the stack, per lane: said to be uniform, or the update they scale, and so every test of the iteration loop of
-        // this launch, counts as divergent -- also for the levels whose sums come out of the cache by read-lane)
+        // this launch, counts as divergent -- also for the levels whose floats come out of the cache by read-lane)
         iA11 = lk_uniform64(T.a11);
         iA12 = lk_uniform64(T.a12);
         iA22 = lk_uniform64(T.a22);
       } else {
-        const bool slow = lk_template_level(lk_level_ptr(prev, level, s, kc_prev, ind_prev0), W, H, prev.pitch[level], prev.bx[level], prev.by[level], ipx,
+        const bool slow = lk_template_level(lk_level_ptr(PV, level, s, kc_prev, ind_prev0), W, H, PV.pitch, PV.bx, PV.by, ipx,
                                             ipy, iw00, iw01, iw10, iw11, patch, lane, tI, tX, tY, iA11, iA12, iA22);
         if (prm.stats_tc && slow && lane == 0) atomicAdd(&prm.stats_tc[1], 1ull);
-        if (ROLE == 2 && tc_store) {
-          lk_tc_store_level(tc_ptr, level, lane, tI, tX, tY, iA11, iA12, iA22);
-          tc_mask |= 1u << level;
-        }
       }
-      const float A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
-      float D = A11 * A22 - A12 * A12;
-      const float minEig = __fdiv_rn(A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12),
-                                     (float)(2 * LK_WIN * LK_WIN));
-      if (minEig < prm.min_eig || D < 1.1920929e-07f) {
+      float invD = 0.f;
+      if (!cached) {
+        A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
+        D = A11 * A22 - A12 * A12;
+        minEig = __fdiv_rn(A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12), (float)(2 * LK_WIN * LK_WIN));
+      }
+      const bool skip = minEig < prm.min_eig || D < 1.1920929e-07f;
+      if (cached) {
+        invD = cD;
+      } else if (!skip) {
+        invD = __fdiv_rn(1.f, D);
+      }
+      if (ROLE == 2 && tc_store) {
+        lk_tc_store_level(tc_ptr, level, lane, tI, tX, tY, A11, A12, A22, D, minEig, invD);
+        tc_mask |= 1u << level;
+      }
+      if (skip) {
         if (level == 0) st = 0;
         continue;
       }
-      D = __fdiv_rn(1.f, D);
+      D = invD;
       npx -= halfWin;
       npy -= halfWin;
       float pdx = 0.f, pdy = 0.f;
       if (!kEarlyRegion) {
-        JW = next.w[level], JH = next.h[level];
-        Jimg = lk_level_ptr(next, level, s, kc_next, ind_next0);
+        JW = NV.w, JH = NV.h;
+        Jimg = lk_level_ptr(NV, level, s, kc_next, ind_next0);
       }
       int iters_run = 0;
       for (int j = 0; j < prm.max_iter; j++) {
@@ -661,7 +707,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
           RX0 = (inx - LK_RM) & ~3;
           RY0 = iny - LK_RM;
           __syncthreads();
-          const bool slow = lk_load_region(Jimg, JW, JH, next.pitch[level], next.bx[level], next.by[level], RX0, RY0, patch);
+          const bool slow = lk_load_region(Jimg, JW, JH, NV.pitch, NV.bx, NV.by, RX0, RY0, patch);
           __syncthreads();
           if (prm.stats_tc && slow && lane == 0) atomicAdd(&prm.stats_tc[2], 1ull);
           region_ok = true;
@@ -670,7 +716,7 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
         {
           // (all 64 lanes, no exec mask: the lanes of window row 31 read rows iny - RY0 + 31 and + 32 <= 40 of the 41 staged ones and
           // the same columns as every other lane, and add nothing -- their tX and tY are 0, computed here or taken from the cache, where
-          // lane 63's tI carries the Hessian sums)
+          // lane 63's tI carries the level's floats)
           const int bx = inx - RX0 + c0, sh = bx & 3;
           const uint8_t* rp = patch + (iny - RY0 + r) * LK_RS + (bx & ~3);
           uint32_t e[2][5];
@@ -749,24 +795,24 @@ __device__ __forceinline__ void lk_track_body(const PyrSel& prev, const PyrSel& 
 
 // the three launches (named apart in the profiles; the register budget is per launch kind)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FLVIS_LK_WAVES, FLVIS_LK_WAVES))) void k_lk_track(
-    PyrSel prev, PyrSel next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
+    LKPyr prev, LKPyr next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
     const int* __restrict__ count, int nmax, LKParams prm, const int* __restrict__ active) {
   lk_track_body<0>(prev, next, prev_pts, next_pts, status, count, nmax, prm, active);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FLVIS_LK_WAVES_T, FLVIS_LK_WAVES_T))) void k_lk_track_temporal(
-    PyrSel prev, PyrSel next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
+    LKPyr prev, LKPyr next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
     const int* __restrict__ count, int nmax, LKParams prm, const int* __restrict__ active) {
   lk_track_body<1>(prev, next, prev_pts, next_pts, status, count, nmax, prm, active);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FLVIS_LK_WAVES, FLVIS_LK_WAVES))) void k_lk_track_stereo(
-    PyrSel prev, PyrSel next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
+    LKPyr prev, LKPyr next, const float* __restrict__ prev_pts, float* __restrict__ next_pts, uint8_t* __restrict__ status,
     const int* __restrict__ count, int nmax, LKParams prm, const int* __restrict__ active) {
   lk_track_body<2>(prev, next, prev_pts, next_pts, status, count, nmax, prm, active);
 }
 
 int lk_tc_slot_dwords(int levels) { return LK_TC_HDR + (levels + 1) * LK_TC_LVL; }
 
-void launch_lk_track(hipStream_t st, const PyrSel& prev, const PyrSel& next, const float* prev_pts, float* next_pts,
+void launch_lk_track(hipStream_t st, const PyrSel& prev_sel, const PyrSel& next_sel, const float* prev_pts, float* next_pts,
                      uint8_t* status, const int* count, int nmax, int S, LKParams prm, const int* active, int max_pts, int role) {
   // one wave per point; the kernel strides by the grid width, so any width is correct.  Sized by the caller's bound on
   // the point count (the tracker holds <= 16 regions x max_region_feature_num landmarks), rounded so that the XCD-aware
@@ -774,6 +820,7 @@ void launch_lk_track(hipStream_t st, const PyrSel& prev, const PyrSel& next, con
   int gx = nmax < 512 ? nmax : 512;
   if (max_pts > 0 && max_pts < gx) gx = (max_pts + 7) & ~7;
   if (gx > nmax) gx = nmax;
+  const LKPyr prev = lk_pyr(prev_sel), next = lk_pyr(next_sel);
   if (role == 1)
     hipLaunchKernelGGL(k_lk_track_temporal, dim3(gx, S), dim3(64), 0, st, prev, next, prev_pts, next_pts, status, count, nmax, prm, active);
   else if (role == 2)
